@@ -7,16 +7,20 @@ view + cross-check.  A "step" is one Match() through the C ABI entry point pm_ma
 the seed maps already resident in HBM and the disparity maps written to HBM; the timed steps rotate over four
 distinct resident pairs, so the inputs are not the same cache-hot pair every step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Rank r matches its own pairs (stereo pairs are independent: no data-path collective, weak scaling).  The K
 timed steps are bracketed by barrier + synchronize on both sides; rank 0 prints ONE JSON line with the whole-job
-pairs/s (max elapsed over ranks), the roofline of the dominant kernel (per-launch duration from HIP events
-recorded by the engine on its own stream during the timed steps) and the CPU baseline (the oracle -- a port of
-the reference CPU path -- timed on this host, rank 0, N=1).
+pairs/s (max elapsed over ranks), ms_per_step and the roofline of the dominant kernel (per-launch duration from HIP
+events recorded by the engine on its own stream during the timed steps).  That is all a plain run does: set-up,
+warm-up, the timed steps, the outputs (--dump-outputs DIR: rank 0's disparity maps of the last timed step as .npy),
+the line.
 
-Side legs in the same line (rank 0, N=1, never `value`; all measured in THIS process, beside the headline's handle):
+--full adds, after the timed steps, the checks (determinism, quality against the synthetic truth, work counters, the
+whole frame against the oracle), the CPU baseline (the oracle -- a port of the reference CPU path -- timed on this
+host, rank 0, N=1) and the side legs below (rank 0, N=1, never `value`; all measured in THIS process, beside the
+headline's handle):
     planes            the slanted-plane mode (north_star kernels) at the same shape: fp32 state (configs[1] shape) and
                       fp16 state behind the on-device stereo-ready enhancement (configs[4] shape)
     host_buffers      PCIe-inclusive rates of the host-buffer entry points (pageable and page-locked caller memory,
@@ -26,7 +30,8 @@ Side legs in the same line (rank 0, N=1, never `value`; all measured in THIS pro
                       `value` (configs[2] incl. H2D / D2H; also in multi-rank runs)
     batch             4 and 32 pairs per pm_match_device call (configs[2]'s per-GPU share)
     reference_test_shape  the reference's own timed call pattern (patchmatch_gpu_test.cpp:68-88) with its CPU side
-    tiled_4096x2160   configs[3]: untiled, and through the C-ABI driver in 8 bands on this device
+    tiled_4096x2160   configs[3]: untiled, and through the C-ABI driver in 8 bands on this device (a multi-rank run:
+                      one band per rank, in a child process)
 Other workloads: --mode planes [--state f16] [--enhance] makes the plane mode the timed one; --pairs-per-gpu 32 is
 configs[2]'s per-GPU share; --tiled runs configs[3] (one 4096x2160 pair row-tiled over the ranks).
 """
@@ -52,6 +57,7 @@ PLANE_LAUNCH_BYTES = {"planes_spatial": 24, "planes_view": 64, "planes_refine": 
 # views one launch of the class covers (the spatial stage sweeps both views of a pair in one launch)
 PLANE_LAUNCH_VIEWS = {"planes_spatial": 2, "planes_view": 1, "planes_refine": 2, "planes_view_refine": 1}
 N_ROTATE = 4  # distinct device-resident pairs the timed steps rotate over
+DUMP_LIMIT_BYTES = 60 * 10**6  # --dump-outputs: data of all files together (under 64 MB with the .npy headers)
 
 
 def parse():
@@ -59,6 +65,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the checks, the CPU baselines and the side legs "
+                         "(--no-cpu-baseline, --cpu-baseline-full, --cpu-budget-s, --host-pairs, --no-side-legs, "
+                         "--tiled-rccl, --tiled-timeout and --rehearse-tiled-leg shape those and act only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write rank 0's disparity maps of the last timed step to DIR/disparity_{left,right}.npy "
+                         "(float32, pairs x rows x cols; over %d MB a fixed seeded sample of positions)"
+                         % (DUMP_LIMIT_BYTES // 10**6))
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL) on GPUs; gloo with --dry-run for CPU tests")
     ap.add_argument("--dry-run", action="store_true",
                     help="exercise sharding/barrier/reduction without a GPU (no compute, no engine)")
@@ -103,9 +117,14 @@ def parse():
     ap.add_argument("--tiled-timeout", type=int, default=150,
                     help="deadline (s) of the crash-isolated configs[3] leg of a multi-rank run")
     ap.add_argument("--rehearse-tiled-leg", action="store_true",
-                    help="with --dry-run: start the tiled children anyway (without a GPU they fail) -- tests that a "
-                         "failing leg ends up as an error entry and the line is still printed")
-    return ap.parse_args()
+                    help="with --dry-run --full: start the tiled children anyway (without a GPU they fail) -- tests "
+                         "that a failing leg ends up as an error entry and the line is still printed")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.dry_run or args.tiled):
+        ap.error("--dump-outputs needs the engine's timed path (not --dry-run, not --tiled)")
+    return args
 
 
 class Dist:
@@ -217,7 +236,7 @@ def no_cpu_leg(result, world):
     """The contract asks for the CPU leg on rank 0 at N = 1 only: the N = 1 point of a scaling run is the BENCH line, which
     carries it (and check.equals_oracle_full_frame) -- an N > 1 line says so instead of leaving the key out."""
     result["cpu_baseline"] = None
-    result["cpu_baseline_reason"] = ("timed on rank 0 at N = 1 only (bench.py --gpus 1 carries it together with "
+    result["cpu_baseline_reason"] = ("timed on rank 0 at N = 1 only (bench.py --gpus 1 --full carries it together with "
                                      "check.equals_oracle_full_frame); this is an N = %d line" % world)
 
 
@@ -673,6 +692,21 @@ def roofline_of(args, prof, n_prof, nb, mode, state, ms_per_step=None, variant="
                     "own streams) share the chip, so the chip-level rate is achieved_all_concurrent"}
 
 
+def dump_outputs(out_dir, w, np):
+    """What the timed path handed its caller in its last step: the left and right disparity maps of every pair of that
+    step, float32, pairs x rows x cols.  Above DUMP_LIMIT_BYTES in all, both maps are cut to the same fixed sample of
+    flat positions (seed 0), sorted, so that two builds still compare value for value."""
+    w.eng.synchronize()
+    maps = {"disparity_left": w.DL.cpu().numpy(), "disparity_right": w.DR.cpu().numpy()}
+    if sum(a.nbytes for a in maps.values()) > DUMP_LIMIT_BYTES:
+        n = DUMP_LIMIT_BYTES // (4 * len(maps))
+        idx = np.sort(np.random.default_rng(0).choice(w.DL.numel(), n, replace=False))
+        maps = {k: a.reshape(-1)[idx] for k, a in maps.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in maps.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def timed_loop(w, d, steps, warmup, every, no_profile):
     """W untimed steps, then exactly `steps` timed ones between barrier + synchronize on both sides (wall clock: the
     contract's figure).  Beside it every step boundary is a HIP event recorded on the ENGINE's stream (torch's own
@@ -909,7 +943,7 @@ def main():
         sys.exit(launch_ranks(args))
     planes = args.mode == "planes"
     tiled_result = None
-    if (int(os.environ.get("WORLD_SIZE", "1")) > 1 and not planes and not args.no_side_legs and not args.tiled
+    if (args.full and int(os.environ.get("WORLD_SIZE", "1")) > 1 and not planes and not args.no_side_legs and not args.tiled
             and max(1, args.pairs_per_gpu) == 1 and (not args.dry_run or args.rehearse_tiled_leg)):
         import torch  # noqa: F401 -- pages the libraries in before the children import them
         tiled_result = tiled_children(args)
@@ -948,14 +982,15 @@ def main():
             time.sleep(0.001 * (1 + d.rank))
         elapsed = d.max_over_ranks(time.perf_counter() - t0)
         d.barrier()
-        host_seq = host_sequence_all_ranks(None, args, None, d) if (not planes and args.host_pairs > 0) else None
+        host_seq = (host_sequence_all_ranks(None, args, None, d) if (args.full and not planes and args.host_pairs > 0)
+                    else None)
         if d.rank == 0:
             result.update(value=d.world * steps / elapsed, ms_per_step=1e3 * elapsed / steps, dry_run=True)
             if host_seq is not None:
                 result["host_sequence_all_ranks"] = host_seq
             if tiled_result is not None:
                 result["tiled_4096x2160"] = tiled_result
-            if d.world > 1:
+            if args.full and d.world > 1:
                 no_cpu_leg(result, d.world)
             print(json.dumps(result), flush=True)
         d.close()
@@ -976,6 +1011,25 @@ def main():
                  args.plane_neighbours if planes else 0)
     eng = w.eng
     elapsed, prof, n_prof, step_stats = timed_loop(w, d, steps, warmup, max(1, args.profile_every), args.no_profile)
+    if d.rank == 0:
+        gpu_ms = sum(v[1] for v in prof.values())
+        result.update(
+            value=d.world * nb * steps / elapsed, ms_per_step=1e3 * elapsed / steps,
+            ms_per_frame=1e3 * elapsed / steps / nb,
+            step_ms=step_stats,
+            roofline=roofline_of(args, prof, n_prof, nb, args.mode, args.state, 1e3 * elapsed / steps,
+                                 "@two_neighbours" if planes and args.plane_neighbours else "") if n_prof else None,
+            kernels_ms_per_step={k: v[1] / max(n_prof, 1) for k, v in prof.items() if v[0]},
+            gpu_busy_ms_per_step=gpu_ms / max(n_prof, 1),
+        )
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, w, np)
+    if not args.full:
+        if d.rank == 0:
+            print(json.dumps(result), flush=True)
+        eng.close()
+        d.close()
+        return
 
     # determinism: the same resident pair twice
     w.step(0)
@@ -1003,17 +1057,7 @@ def main():
     if not planes and args.host_pairs > 0 and nb == 1:
         host_seq = host_sequence_all_ranks(pm, args, w.pairs[:N_ROTATE], d)
     if d.rank == 0:
-        gpu_ms = sum(v[1] for v in prof.values())
-        result.update(
-            value=d.world * nb * steps / elapsed, ms_per_step=1e3 * elapsed / steps,
-            ms_per_frame=1e3 * elapsed / steps / nb,
-            step_ms=step_stats,
-            roofline=roofline_of(args, prof, n_prof, nb, args.mode, args.state, 1e3 * elapsed / steps,
-                                 "@two_neighbours" if planes and args.plane_neighbours else "") if n_prof else None,
-            kernels_ms_per_step={k: v[1] / max(n_prof, 1) for k, v in prof.items() if v[0]},
-            gpu_busy_ms_per_step=gpu_ms / max(n_prof, 1),
-            check=check,
-        )
+        result["check"] = check
         if counters is not None:
             result["run_engine_counters_per_step"] = counters
         if host_seq is not None:

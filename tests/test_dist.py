@@ -24,7 +24,7 @@ def test_bench_two_ranks_gloo_dry_run():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps",
-           "5", "--warmup", "1", "--backend", "gloo", "--dry-run"]
+           "5", "--warmup", "1", "--backend", "gloo", "--dry-run", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -44,13 +44,14 @@ def test_bench_two_ranks_gloo_dry_run():
 
 
 def test_failing_tiled_leg_does_not_cost_the_line():
-    """A multi-rank default run measures configs[3] in child processes started before the ranks touch the GPU
+    """A multi-rank --full run measures configs[3] in child processes started before the ranks touch the GPU
     (bench.tiled_children).  Here there is no GPU, so the children fail: the run must still exit 0 with ONE line
     that carries the headline fields and an error entry for the leg."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps",
-           "3", "--warmup", "1", "--backend", "gloo", "--dry-run", "--rehearse-tiled-leg", "--tiled-timeout", "120"]
+           "3", "--warmup", "1", "--backend", "gloo", "--dry-run", "--full", "--rehearse-tiled-leg", "--tiled-timeout",
+           "120"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -115,8 +116,8 @@ def test_bench_with_a_one_rank_rccl_group_on_the_gpu():
                MASTER_PORT=str(free_port()))
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--no-cpu-baseline",
-           "--host-pairs", "16", "--no-side-legs"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--full",
+           "--no-cpu-baseline", "--host-pairs", "16", "--no-side-legs"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -2,7 +2,7 @@
 # Final measurements of a round on the GPU box (one call): ROUND=r06 tools/final.sh <head-sha> [steps...]
 #   tests    the whole -m gpu suite
 #   fuzz     the six differential fuzzers, new seeds            -> gpurun_out/$ROUND/fuzz.txt
-#   bench    the driver's command                                -> gpurun_out/$ROUND/bench_default.json
+#   bench    bench.py --full (headline, checks and side legs)    -> $out/bench_default.json
 #   prof     tools/profile.sh                                    -> gpurun_out/prof_$ROUND/
 head=${1:-unknown}; shift
 steps=${@:-tests fuzz bench prof}
@@ -28,7 +28,7 @@ fuzz)
   run fuzz_tiled.py --cases 250 --seed 666 || { cat $f; exit 1; }
   cat $f;;
 bench)
-  python bench.py > $out/bench_default.json 2> $out/bench_default.err
+  python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
   python -c "
 import json
 j=json.load(open('$out/bench_default.json'))
