@@ -253,7 +253,7 @@ bool pair_planes_wanted(const pm_handle* h) {
   if (p.engine != PM_ENGINE_AUTO && p.engine != PM_ENGINE_RUNBLK2) return false;
   return true;
 }
-int pair_planes_alloc(pm_handle* h) {
+int pair_planes_alloc(pm_handle* h, hipStream_t stream) {
   if (h->rpg) return PM_OK;
   const size_t B = (size_t)h->max_batch;
   const size_t pitch_t = (size_t)align_up(h->max_rows, 64);
@@ -263,9 +263,9 @@ int pair_planes_alloc(pm_handle* h) {
   PM_HIP(h, hipMalloc((void**)&h->rqk, sizeof(uint32_t) * 2 * nrp));
   PM_HIP(h, hipMalloc((void**)&h->cpg, sizeof(float) * 4 * ncp));
   // row padding behind `cols` / `rows` is read (with weight 0 or by lanes out of reach) and must be finite
-  PM_HIP(h, hipMemsetAsync(h->rpg, 0, sizeof(float) * 4 * nrp, h->stream));
-  PM_HIP(h, hipMemsetAsync(h->rqk, 0, sizeof(uint32_t) * 2 * nrp, h->stream));
-  PM_HIP(h, hipMemsetAsync(h->cpg, 0, sizeof(float) * 4 * ncp, h->stream));
+  PM_HIP(h, hipMemsetAsync(h->rpg, 0, sizeof(float) * 4 * nrp, stream));
+  PM_HIP(h, hipMemsetAsync(h->rqk, 0, sizeof(uint32_t) * 2 * nrp, stream));
+  PM_HIP(h, hipMemsetAsync(h->cpg, 0, sizeof(float) * 4 * ncp, stream));
   return PM_OK;
 }
 
@@ -290,32 +290,32 @@ SeedParams seed_params(const pm_params& p) {
   return sp;
 }
 
-int alloc_seed_scratch(pm_handle* h, SeedScratch& sc) {
-  PM_HIP(h, seed_scratch_alloc(sc, (size_t)h->max_rows * h->max_pitch, h->stream));
-  PM_HIP(h, seed_subpix_prepare(sc, seed_params(h->params), h->stream));
+int alloc_seed_scratch(pm_handle* h, SeedScratch& sc, hipStream_t stream) {
+  PM_HIP(h, seed_scratch_alloc(sc, (size_t)h->max_rows * h->max_pitch, stream));
+  PM_HIP(h, seed_subpix_prepare(sc, seed_params(h->params), stream));
   return PM_OK;
 }
 
 // SparseInit for view `view` of pair `b` straight into its disparity plane.  View 1 is seeded on the
 // mirrored pair (patchmatch_gpu.cu:362-365), whose map is already in the mirrored coordinates the plane uses.
-int run_sparse_init(pm_handle* h, const PlaneSet& ps, int b, int view, int scratch, unsigned stages) {
+int run_sparse_init(pm_handle* h, const PlaneSet& ps, int b, int view, int scratch, unsigned stages, hipStream_t stream) {
   SeedScratch& sc = h->seeds[scratch];
   if (!sc.eig) {
     if (h->capturing) {
       set_err(h, "the seeder scratch of this lane does not exist yet: run this call once before capturing it");
       return PM_ERR_BUSY;
     }
-    if (int rc = alloc_seed_scratch(h, sc)) return rc;
+    if (int rc = alloc_seed_scratch(h, sc, stream)) return rc;
   }
   const uint8_t* ref = ps.img8 + ((size_t)b * 4 + (view == 0 ? 0 : 3)) * ps.plane;
   const uint8_t* tgt = ps.img8 + ((size_t)b * 4 + (view == 0 ? 1 : 2)) * ps.plane;
   float* out = ps.disp + ((size_t)b * 2 + view) * ps.splane;  // a state plane: rows interleaved (out_pitch < 0 below)
   if (h->params.cpu_initialize_factor == 1)  // Patchmatch::Initialize(il, ir, 1) (patchmatch_test.cpp:149-150): 5x5, / 2
     PM_HIP(h, seed_initialize(sc, seed_params(h->params), ref, tgt, ps.rows, ps.cols, ps.pitch, 1, out, -ps.pitch,
-                              h->stream, stages));
+                              stream, stages));
   else
     PM_HIP(h, seed_sparse_init(sc, seed_params(h->params), ref, tgt, ps.rows, ps.cols, ps.pitch,
-                               h->params.init_dilate_factor, out, -ps.pitch, h->stream, stages));
+                               h->params.init_dilate_factor, out, -ps.pitch, stream, stages));
   return PM_OK;
 }
 
@@ -362,20 +362,20 @@ namespace {
 
 // Launch number `idx` of a view's schedule -- per iteration {noise + cost, sweeps A B C D}, then the background mask:
 // PatchmatchGpu::Match(GpuMat...) (patchmatch_gpu.cu:379-411) / the recipe of patchmatch_test.cpp:173-183 -- enqueued
-// on h->stream for all `slots` of plane set `ps`.
-int view_op(pm_handle* h, const PlaneSet& ps, int idx, int slots) {
+// on `stream` for all `slots` of plane set `ps`.
+int view_op(pm_handle* h, const PlaneSet& ps, int idx, int slots, hipStream_t stream) {
   const pm_params& p = h->params;
   const int it = idx / 5, k = idx % 5;
   if (it < p.patchmatch_iters) {
     const CostParams cp = cost_params(p, p.patch_w[it], p.patch_h[it]);
     const Interior in = interior(p, ps.rows, ps.cols, cp.pw, cp.ph);
-    if (k > 0) return run_sweep(h, ps, cp, sweep_geom(p, in, k - 1), slots, p.noise_amp[it]);
+    if (k > 0) return run_sweep(h, ps, cp, sweep_geom(p, in, k - 1), slots, p.noise_amp[it], stream);
     {
-      Launch l(h, PM_K_NOISE);
+      Launch l(h, PM_K_NOISE, stream);
       // from the second iteration on the cost plane is valid for this window if the window is unchanged
       const CostParams prev = it > 0 ? cost_params(p, p.patch_w[it - 1], p.patch_h[it - 1]) : cp;
       const int keep_zero = (it > 0 && cp.pw == prev.pw && cp.ph == prev.ph) ? 1 : 0;
-      launch_noise_cost(h, ps, cp, in, p.noise_amp[it], slots, keep_zero);
+      launch_noise_cost(h, ps, cp, in, p.noise_amp[it], slots, keep_zero, stream);
     }
     return launch_check(h, "noise_cost");
   }
@@ -388,8 +388,8 @@ int view_op(pm_handle* h, const PlaneSet& ps, int idx, int slots) {
   }
   const float factor = p.semantics == PM_SEM_CPU ? p.win_by_factor : p.cost_improve_factor;
   {
-    Launch l(h, PM_K_BACKGROUND);
-    launch_background(h, ps, bcp, in, factor, cached, slots);
+    Launch l(h, PM_K_BACKGROUND, stream);
+    launch_background(h, ps, bcp, in, factor, cached, slots, stream);
   }
   return launch_check(h, "background");
 }
@@ -398,30 +398,13 @@ int view_op(pm_handle* h, const PlaneSet& ps, int idx, int slots) {
 // views on their view streams): the host enqueues launch k of EVERY set before launch k + 1 of any, so all
 // streams have work from the first microsecond on.  (Enqueuing one view's whole chain of ~45 launches first left
 // the other stream empty for the 0.2-0.4 ms that takes: visible in the rocprofv3 kernel trace.)
-int run_view_sets(pm_handle* h, const PlaneSet* pss, hipStream_t* streams, int sets, int slots) {
-  hipStream_t keep = h->stream;
-  struct Restore {
-    pm_handle* h;
-    hipStream_t s;
-    ~Restore() { h->stream = s; }
-  } restore{h, keep};
+int run_view_sets(pm_handle* h, const PlaneSet* pss, const hipStream_t* streams, int sets, int slots) {
   const int n_ops = 5 * h->params.patchmatch_iters + 1;
   for (int idx = 0; idx < n_ops; ++idx)
-    for (int s = 0; s < sets; ++s) {
-      h->stream = streams[s];  // every launch helper enqueues on h->stream
-      if (int rc = view_op(h, pss[s], idx, slots)) return rc;
-    }
+    for (int s = 0; s < sets; ++s)
+      if (int rc = view_op(h, pss[s], idx, slots, streams[s])) return rc;
   return PM_OK;
 }
-
-}  // namespace
-
-int run_one_view_set(pm_handle* h, const PlaneSet& ps, int slots) {
-  hipStream_t s = h->stream;
-  return run_view_sets(h, &ps, &s, 1, slots);
-}
-
-namespace {
 
 bool view_streams_enabled() {
   static bool v = [] {
@@ -431,11 +414,11 @@ bool view_streams_enabled() {
   return v;
 }
 
-int seed_views(pm_handle* h, const PlaneSet& ps, int n_pairs, int view, int scratch) {
+int seed_views(pm_handle* h, const PlaneSet& ps, int n_pairs, int view, int scratch, hipStream_t stream) {
   if (!h->need_seed[view]) return PM_OK;
-  Launch l(h, PM_K_SEED);
+  Launch l(h, PM_K_SEED, stream);
   for (int b = 0; b < n_pairs; ++b)
-    if (int rc = run_sparse_init(h, ps, b, view, scratch)) return rc;
+    if (int rc = run_sparse_init(h, ps, b, view, scratch, kSeedAllStages, stream)) return rc;
   return PM_OK;
 }
 
@@ -468,7 +451,25 @@ void mark_joined(pm_handle* h, hipStream_t s) {
       return;
     }
 }
-// `onto` waits for everything `from` holds now
+
+// the event a side stream is joined back into the handle's stream with
+hipEvent_t join_event(const pm_handle* h, hipStream_t s) {
+  return s == h->s_out ? h->out_join : (s == h->s_in ? h->in_join : h->view1_join);
+}
+
+}  // namespace
+
+// `onto` waits for `ev`, recorded here behind everything `from` holds (from null: `ev` as recorded before; ev null:
+// nothing to wait for), and counts as forked.  What `from` held is then behind `onto`: joining `onto` joins it too.
+int fork_stream(pm_handle* h, hipEvent_t ev, hipStream_t from, hipStream_t onto) {
+  if (from) PM_HIP(h, hipEventRecord(ev, from));
+  if (ev) PM_HIP(h, hipStreamWaitEvent(onto, ev, 0));
+  if (from) mark_joined(h, from);
+  mark_forked(h, onto);
+  prof_break(h, onto);
+  return PM_OK;
+}
+// `onto` waits for everything `from` holds now; `from` counts as joined when `onto` is the handle's stream
 int join_stream(pm_handle* h, hipStream_t from, hipEvent_t ev, hipStream_t onto) {
   PM_HIP(h, hipEventRecord(ev, from));
   PM_HIP(h, hipStreamWaitEvent(onto, ev, 0));
@@ -476,8 +477,6 @@ int join_stream(pm_handle* h, hipStream_t from, hipEvent_t ev, hipStream_t onto)
   prof_break(h, onto);
   return PM_OK;
 }
-
-}  // namespace
 
 // The roles of a handle's four streams (create_handle_streams):
 //   stream        the handle's own: every single-pair call, the FIRST view of every chunk
@@ -520,48 +519,34 @@ int seq_events_create(pm_handle* h) {
 
 namespace {
 
-// Both views of the pairs of `ps` on vstream[0] / vstream[1]; a stream other than the handle's (the handle's too with
-// wait_on_main) first waits for the non-null events of `waits`.  Enqueue only; the caller joins.  `scratch` = seeder scratch set of view 0 (view 1: + 1).
-int run_views_on(pm_handle* h, const PlaneSet& ps, int slots, const ViewSetup* setup, hipStream_t vstream[2],
-                 const hipEvent_t* waits, int n_waits, bool wait_on_main = false, int scratch = 0) {
-  hipStream_t main_stream = h->stream;
+// Both views of the pairs of `ps` on vstream[0] / vstream[1], each stream already forked; view v seeds with scratch
+// set v.  Enqueue only; the caller joins.
+int run_views_on(pm_handle* h, const PlaneSet& ps, int slots, const ViewSetup* setup, const hipStream_t vstream[2]) {
   int rc = PM_OK;
   PlaneSet pv[2] = {ps, ps};
-  for (int v = 0; v < 2 && rc == PM_OK; ++v) {
-    pv[v].view_fixed = v;
-    if (vstream[v] != main_stream || wait_on_main) {
-      for (int w = 0; w < n_waits && rc == PM_OK; ++w)
-        if (waits[w] && hipStreamWaitEvent(vstream[v], waits[w], 0) != hipSuccess) rc = PM_ERR_HIP;
-      if (rc != PM_OK) break;
-      mark_forked(h, vstream[v]);
-      prof_break(h, vstream[v]);
-    }
-  }
+  for (int v = 0; v < 2; ++v) pv[v].view_fixed = v;
   // The head of a view -- prep, transposed planes, the seeder's seven launches -- goes out like the sweeps behind it:
   // launch k of BOTH views before launch k + 1 of either.  (One view's whole head first left the other view's stream
   // empty for the ~55 us the host needs for nine launches, and the second view then ends that much later: a tenth of
   // the reference's own 376x240 call, profiles/r06_reference_call_timeline.txt.)
   for (int op = 0; op < 2 && setup && rc == PM_OK; ++op)
     for (int v = 0; v < 2 && rc == PM_OK; ++v) {
-      h->stream = vstream[v];
-      Launch l(h, PM_K_PREP);
+      Launch l(h, PM_K_PREP, vstream[v]);
       if (op == 0) {
         const PrepSeedMaps seeds{setup->d_seed_l, setup->d_seed_r};  // the seed copy rides along (one launch less)
-        launch_prep(h, ps, setup->d_left, setup->d_right, setup->n, (size_t)ps.cols, v, &seeds);
+        launch_prep(h, ps, setup->d_left, setup->d_right, setup->n, (size_t)ps.cols, v, &seeds, vstream[v]);
         rc = launch_check(h, "prep");
       } else {
-        rc = run_transpose(h, ps, setup->n, v);
+        rc = run_transpose(h, ps, setup->n, v, vstream[v]);
       }
     }
   for (int b = 0; b < slots / 2 && rc == PM_OK; ++b)  // a view's pairs share its scratch: pair by pair
     for (int st = 0; st < kSeedStages && rc == PM_OK; ++st)
       for (int v = 0; v < 2 && rc == PM_OK; ++v) {
         if (!h->need_seed[v]) continue;
-        h->stream = vstream[v];
-        Launch l(h, PM_K_SEED);
-        rc = run_sparse_init(h, ps, b, v, scratch + v, 1u << st);
+        Launch l(h, PM_K_SEED, vstream[v]);
+        rc = run_sparse_init(h, ps, b, v, v, 1u << st, vstream[v]);
       }
-  h->stream = main_stream;
   if (rc == PM_OK) rc = run_view_sets(h, pv, vstream, 2, slots / 2);
   if (rc == PM_ERR_HIP && !h->err[0]) set_err(h, "per-view stream setup failed");
   return rc;
@@ -570,12 +555,12 @@ int run_views_on(pm_handle* h, const PlaneSet& ps, int slots, const ViewSetup* s
 int run_views(pm_handle* h, const PlaneSet& ps, int slots, const ViewSetup* setup = nullptr) {
   if (ps.n_views != 2 || !view_streams_enabled()) {
     for (int v = 0; v < ps.n_views; ++v)
-      if (int rc = seed_views(h, ps, slots / ps.n_views, v, 0)) return rc;
-    return run_one_view_set(h, ps, slots);
+      if (int rc = seed_views(h, ps, slots / ps.n_views, v, 0, h->stream)) return rc;
+    return run_view_sets(h, &ps, &h->stream, 1, slots);
   }
   // one view stays on the caller's stream, the other forks off
   if (int rc = view_streams_create(h)) return rc;
-  PM_HIP(h, hipEventRecord(h->view_fork, h->stream));
+  if (int rc = fork_stream(h, h->view_fork, h->stream, h->view1_stream)) return rc;
   // the view that ended last the time before stays on the handle's stream, the other one forks off (pm_handle::late_view)
   if (!h->capturing && h->view_end_recorded) {
     float ms = 0.f;
@@ -591,14 +576,21 @@ int run_views(pm_handle* h, const PlaneSet& ps, int slots, const ViewSetup* setu
   hipStream_t vs[2];
   vs[h->late_view] = h->stream;
   vs[1 - h->late_view] = h->view1_stream;
-  if (int rc = run_views_on(h, ps, slots, setup, vs, &h->view_fork, 1)) return rc;
-  // sampled: a timed event is a command of its own on the stream, in front of the join of every call it is recorded in
-  if (!h->capturing && !h->view_end_recorded && (h->view_calls++ % pm_handle::kViewEndEvery) == 0) {
-    for (int v = 0; v < 2; ++v) PM_HIP(h, hipEventRecord(h->view_end[v], vs[v]));
-    h->view_end_recorded = true;
-  }
-  return join_stream(h, h->view1_stream, h->view1_join, h->stream);
+  auto views = [&]() -> int {
+    if (int rc = run_views_on(h, ps, slots, setup, vs)) return rc;
+    // sampled: a timed event is a command of its own on the stream, in front of the join of every call it is recorded in
+    if (!h->capturing && !h->view_end_recorded && (h->view_calls++ % pm_handle::kViewEndEvery) == 0) {
+      for (int v = 0; v < 2; ++v) PM_HIP(h, hipEventRecord(h->view_end[v], vs[v]));
+      h->view_end_recorded = true;
+    }
+    return PM_OK;
+  };
+  const int rc = views();
+  const int rc_join = join_stream(h, h->view1_stream, h->view1_join, h->stream);  // on every path: view 1 may be running
+  return rc != PM_OK ? rc : rc_join;
 }
+
+}  // namespace
 
 // The plane set of pair b alone (every per-pair array advanced to that pair; see make_view for the strides).
 PlaneSet plane_set_of_pair(const PlaneSet& ps, int b) {
@@ -632,24 +624,6 @@ int pair_chunk() {
   return v;
 }
 
-}  // namespace
-
-int seq_chunk_pairs() { return pair_chunk(); }
-
-PlaneSet pair_plane_set(const PlaneSet& ps, int b) { return plane_set_of_pair(ps, b); }
-
-// A second lane for half of a batch (plane mode, pm_planes_host.hip): view1_stream runs behind everything the handle's
-// stream holds now; lane_join makes the handle's stream wait for the lane again.
-int lane_fork(pm_handle* h) {
-  if (int rc = view_streams_create(h)) return rc;
-  PM_HIP(h, hipEventRecord(h->view_fork, h->stream));
-  PM_HIP(h, hipStreamWaitEvent(h->view1_stream, h->view_fork, 0));
-  mark_forked(h, h->view1_stream);
-  prof_break(h, h->view1_stream);
-  return PM_OK;
-}
-int lane_join(pm_handle* h) { return join_stream(h, h->view1_stream, h->view1_join, h->stream); }
-
 bool seq_pipelined(const pm_handle* h) {
   return h->params.mode == PM_MODE_SCALAR && h->params.left_right_check != 0 && view_streams_enabled() && !h->bgr;
 }
@@ -674,60 +648,46 @@ int seq_enqueue_chunk(pm_handle* h, int b, int c, const uint8_t* d_left, const u
   const PlaneSet pb = plane_set_of_pair(ps, b);
   h->need_seed[0] = h->params.sparse_init && !d_seed_l;
   h->need_seed[1] = h->params.sparse_init && !d_seed_r;
-  hipStream_t keep = h->stream;
-  struct Restore {
-    pm_handle* h;
-    hipStream_t s;
-    ~Restore() { h->stream = s; }
-  } restore{h, keep};
   // ---- head: on s_in when a view seeds itself (measured, frame sequence at 720p: self-seeded 396 -> 401 pairs/s with the
   // head aside, seeded 410 -> 402 -- without the seeder the head is too short to pay for one more cross-queue wait)
   const bool head_aside = h->need_seed[0] || h->need_seed[1];
-  hipStream_t vs[2] = {keep, h->view1_stream};
+  const hipStream_t vs[2] = {h->stream, h->view1_stream};
   if (head_aside) {
-    if (ready) PM_HIP(h, hipStreamWaitEvent(h->s_in, ready, 0));
-    if (slot_free) PM_HIP(h, hipStreamWaitEvent(h->s_in, slot_free, 0));
-    mark_forked(h, h->s_in);
-    prof_break(h, h->s_in);
-    h->stream = h->s_in;
+    for (hipEvent_t e : {ready, slot_free})
+      if (int rc = fork_stream(h, e, nullptr, h->s_in)) return rc;
     for (int v = 0; v < 2; ++v) {
       {
-        Launch l(h, PM_K_PREP);
+        Launch l(h, PM_K_PREP, h->s_in);
         const PrepSeedMaps seeds{d_seed_l, d_seed_r};  // the seed copy rides along (one launch less)
-        launch_prep(h, pb, d_left, d_right, c, (size_t)cols, v, &seeds);
+        launch_prep(h, pb, d_left, d_right, c, (size_t)cols, v, &seeds, h->s_in);
         if (int rc = launch_check(h, "prep")) return rc;
       }
       {
-        Launch l(h, PM_K_PREP);
-        if (int rc = run_transpose(h, pb, c, v)) return rc;
+        Launch l(h, PM_K_PREP, h->s_in);
+        if (int rc = run_transpose(h, pb, c, v, h->s_in)) return rc;
       }
     }
     for (int v = 0; v < 2; ++v) {
       PlaneSet pv = pb;
       pv.view_fixed = v;
-      if (int rc = seed_views(h, pv, c, v, v)) return rc;
+      if (int rc = seed_views(h, pv, c, v, v, h->s_in)) return rc;
     }
-    PM_HIP(h, hipEventRecord(head_done, h->s_in));
-    h->stream = keep;
     h->need_seed[0] = h->need_seed[1] = false;  // done in the head: the view streams start with the first noise + cost
-    if (int rc = run_views_on(h, pb, 2 * c, nullptr, vs, &head_done, 1, true)) return rc;
+    for (int v = 0; v < 2; ++v)  // (the first fork records head_done on s_in, the second waits for the same record)
+      if (int rc = fork_stream(h, head_done, v == 0 ? h->s_in : nullptr, vs[v])) return rc;
+    if (int rc = run_views_on(h, pb, 2 * c, nullptr, vs)) return rc;
   } else {
+    for (int v = 0; v < 2; ++v)
+      for (hipEvent_t e : {ready, slot_free})
+        if (int rc = fork_stream(h, e, nullptr, vs[v])) return rc;
     const ViewSetup sb{d_left, d_right, d_seed_l, d_seed_r, c};
-    const hipEvent_t waits[2] = {ready, slot_free};
-    if (int rc = run_views_on(h, pb, 2 * c, &sb, vs, waits, 2, true)) return rc;
+    if (int rc = run_views_on(h, pb, 2 * c, &sb, vs)) return rc;
   }
-  mark_joined(h, h->s_in);
-  for (int v = 0; v < 2; ++v) {
-    PM_HIP(h, hipEventRecord(v_done[v], vs[v]));
-    PM_HIP(h, hipStreamWaitEvent(h->s_out, v_done[v], 0));
-    mark_joined(h, vs[v]);
-  }
-  mark_forked(h, h->s_out);
-  prof_break(h, h->s_out);
-  h->stream = h->s_out;
+  for (int v = 0; v < 2; ++v)
+    if (int rc = fork_stream(h, v_done[v], vs[v], h->s_out)) return rc;
   {
-    Launch l(h, PM_K_FINALIZE);
-    launch_finalize(h, pb, d_disp_l, d_disp_r, c);
+    Launch l(h, PM_K_FINALIZE, h->s_out);
+    launch_finalize(h, pb, d_disp_l, d_disp_r, c, h->s_out);
     if (int rc = launch_check(h, "finalize")) return rc;
   }
   return PM_OK;
@@ -743,16 +703,20 @@ int run_pairs_as_chunks(pm_handle* h, int n, const ViewSetup& vs, int rows, int 
   if (int rc = seq_events_create(h)) return rc;
   PM_HIP(h, hipEventRecord(h->view_fork, h->stream));
   const size_t px = (size_t)rows * cols;
-  for (int b = 0; b < n; b += chunk) {
+  int rc = PM_OK;
+  for (int b = 0; b < n && rc == PM_OK; b += chunk) {
     const int c = n - b < chunk ? n - b : chunk;
-    if (int rc = seq_enqueue_chunk(h, b, c, vs.d_left + b * px, vs.d_right + b * px, rows, cols,
-                                   vs.d_seed_l ? vs.d_seed_l + b * px : nullptr,
-                                   vs.d_seed_r ? vs.d_seed_r + b * px : nullptr, d_disp_l + b * px,
-                                   d_disp_r ? d_disp_r + b * px : nullptr, b == 0 ? h->view_fork : nullptr, nullptr,
-                                   h->pipe[(size_t)b].v_done, h->pipe[(size_t)b].head_done))
-      return rc;
+    rc = seq_enqueue_chunk(h, b, c, vs.d_left + b * px, vs.d_right + b * px, rows, cols,
+                           vs.d_seed_l ? vs.d_seed_l + b * px : nullptr, vs.d_seed_r ? vs.d_seed_r + b * px : nullptr,
+                           d_disp_l + b * px, d_disp_r ? d_disp_r + b * px : nullptr, b == 0 ? h->view_fork : nullptr,
+                           nullptr, h->pipe[(size_t)b].v_done, h->pipe[(size_t)b].head_done);
   }
-  return join_stream(h, h->s_out, h->out_join, h->stream);
+  if (rc == PM_OK) return join_stream(h, h->s_out, h->out_join, h->stream);
+  // a chunk failed part way: the handle's stream waits for whatever the side streams hold (a capture's forks are
+  // joined by abort_capture, which knows which streams the capture reached)
+  if (!h->capturing)
+    for (hipStream_t s : {h->view1_stream, h->s_in, h->s_out}) (void)join_stream(h, s, join_event(h, s), h->stream);
+  return rc;
 }
 
 int validate_params(pm_handle* h, const pm_params& p) {
@@ -843,14 +807,22 @@ int validate_params(pm_handle* h, const pm_params& p) {
 
 }  // namespace
 
-// Ends a capture in progress and throws the partial graph away (error paths, pm_destroy).
-void abort_capture(pm_handle* h) {
-  if (!h->capturing) return;
-  for (hipStream_t st : h->cap_unjoined) {  // see pm_capture_end: an unjoined fork must not reach hipStreamEndCapture
-    hipEvent_t ev = st == h->s_out ? h->out_join : (st == h->s_in ? h->in_join : h->view1_join);
+// Joins every stream the open capture forked and left unjoined back into the handle's stream (an unjoined fork must not
+// reach hipStreamEndCapture: see capture_close); returns how many there were.
+static size_t join_unjoined(pm_handle* h) {
+  const size_t n = h->cap_unjoined.size();
+  for (hipStream_t st : h->cap_unjoined) {
+    const hipEvent_t ev = join_event(h, st);
     if (ev && hipEventRecord(ev, st) == hipSuccess) (void)hipStreamWaitEvent(h->stream, ev, 0);
   }
   h->cap_unjoined.clear();
+  return n;
+}
+
+// Ends a capture in progress and throws the partial graph away (error paths, pm_destroy).
+void abort_capture(pm_handle* h) {
+  if (!h->capturing) return;
+  join_unjoined(h);
   h->capturing = false;
   hipGraph_t graph = nullptr;
   (void)hipStreamEndCapture(h->stream, &graph);
@@ -873,7 +845,7 @@ int capture_open(pm_handle* h) {
   if (h->params.sparse_init)
     for (int i = 1; i < 2; ++i)
       if (!h->seeds[i].eig)
-        if (int rc = alloc_seed_scratch(h, h->seeds[i])) return rc;
+        if (int rc = alloc_seed_scratch(h, h->seeds[i], h->stream)) return rc;
   h->cap_unjoined.clear();
   PM_HIP(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
   h->capturing = true;
@@ -886,15 +858,7 @@ int capture_open(pm_handle* h) {
 // joined here so that the capture can be ended at all, the graph is thrown away, and the caller gets PM_ERR_STATE.
 int capture_close(pm_handle* h, hipGraphExec_t* exec, const char* what) {
   *exec = nullptr;
-  const size_t unjoined = h->cap_unjoined.size();
-  if (unjoined) {
-    std::vector<hipStream_t> open_streams = h->cap_unjoined;
-    for (hipStream_t st : open_streams) {
-      hipEvent_t ev = st == h->s_out ? h->out_join : (st == h->s_in ? h->in_join : h->view1_join);
-      if (hipEventRecord(ev, st) == hipSuccess) (void)hipStreamWaitEvent(h->stream, ev, 0);
-      mark_joined(h, st);
-    }
-  }
+  const size_t unjoined = join_unjoined(h);
   h->capturing = false;
   hipGraph_t graph = nullptr;
   PM_HIP(h, hipStreamEndCapture(h->stream, &graph));
@@ -948,24 +912,24 @@ int match_device_impl(pm_handle* h, int n, const uint8_t* d_left, const uint8_t*
     if (int rc = run_views(h, ps, n * n_views, &vs)) return rc;
   } else {
     {
-      Launch l(h, PM_K_PREP);
-      launch_prep(h, ps, d_left, d_right, n, (size_t)cols);
+      Launch l(h, PM_K_PREP, h->stream);
+      launch_prep(h, ps, d_left, d_right, n, (size_t)cols, -1, nullptr, h->stream);
     }
     if (int rc = launch_check(h, "prep")) return rc;
     {
-      Launch l(h, PM_K_PREP);
-      if (int rc = run_transpose(h, ps, n)) return rc;
+      Launch l(h, PM_K_PREP, h->stream);
+      if (int rc = run_transpose(h, ps, n, -1, h->stream)) return rc;
     }
     {
-      Launch l(h, PM_K_SEED);
-      launch_seed(h, ps, d_seed_l, d_seed_r, n);
+      Launch l(h, PM_K_SEED, h->stream);
+      launch_seed(h, ps, d_seed_l, d_seed_r, n, -1, h->stream);
     }
     if (int rc = launch_check(h, "seed")) return rc;
     if (int rc = run_views(h, ps, n * n_views)) return rc;
   }
   {
-    Launch l(h, PM_K_FINALIZE);
-    launch_finalize(h, ps, d_disp_l, d_disp_r, n);
+    Launch l(h, PM_K_FINALIZE, h->stream);
+    launch_finalize(h, ps, d_disp_l, d_disp_r, n, h->stream);
   }
   return launch_check(h, "finalize");
 }
@@ -1158,7 +1122,7 @@ int pm_create(const pm_params* params, int device, int max_rows, int max_cols, i
   PM_HIP(h, hipMemsetAsync(h->pk16, 0, sizeof(uint16_t) * (B * 4 * plane + 128), h->stream));
   PM_HIP(h, hipMemsetAsync(h->tpk16, 0, sizeof(uint16_t) * (B * 4 * plane_t + 128), h->stream));
   if (pair_planes_wanted(h))
-    if (int rc = pair_planes_alloc(h)) return rc;
+    if (int rc = pair_planes_alloc(h, h->stream)) return rc;
   const size_t splane = (size_t)align_up(max_rows, 4) * h->max_pitch;  // state planes: four rows interleaved (pm_device.hpp)
   PM_HIP(h, hipMalloc((void**)&h->disp, sizeof(float) * (B * 2 * splane + 64)));
   PM_HIP(h, hipMalloc((void**)&h->cost, sizeof(float) * (B * 2 * splane + 64)));
@@ -1166,9 +1130,9 @@ int pm_create(const pm_params* params, int device, int max_rows, int max_cols, i
   h->noise_capacity = plane;
   PM_HIP(h, hipMalloc((void**)&h->counters, sizeof(unsigned long long) * 16));  // [8..13]: timing builds only
   PM_HIP(h, hipMemsetAsync(h->counters, 0, sizeof(unsigned long long) * 16, h->stream));
-  if (int rc = alloc_seed_scratch(h, h->seeds[0])) return rc;
+  if (int rc = alloc_seed_scratch(h, h->seeds[0], h->stream)) return rc;
   if (params->mode == PM_MODE_PLANES)
-    if (int rc = planes_alloc(h)) return rc;
+    if (int rc = planes_alloc(h, h->stream)) return rc;
   const size_t tight = (size_t)max_rows * max_cols;
   // one block: a single small pair goes up as ONE copy, left and right back to back (pm_hostpath.hip::pm_match_u8)
   PM_HIP(h, hipMalloc((void**)&h->st_left, 2 * B * tight + 64));
@@ -1245,10 +1209,7 @@ int pm_debug_capture_fork(pm_handle* h) {
     set_err(h, "pm_debug_capture_fork: only between pm_capture_begin and pm_capture_end of a handle with view streams");
     return PM_ERR_STATE;
   }
-  PM_HIP(h, hipEventRecord(h->view_fork, h->stream));
-  PM_HIP(h, hipStreamWaitEvent(h->view1_stream, h->view_fork, 0));
-  mark_forked(h, h->view1_stream);
-  return PM_OK;
+  return fork_stream(h, h->view_fork, h->stream, h->view1_stream);
 }
 
 int pm_replay(pm_handle* h) {
@@ -1312,24 +1273,24 @@ int pm_match_view_device(pm_handle* h, const float* d_iml, const float* d_imr, c
   }
   PlaneSet ps = plane_set(h, rows, cols, 1);
   {
-    Launch l(h, PM_K_PREP);
-    launch_prep_view(h, ps, d_iml, d_imr, d_Gl, d_Gr, step / sizeof(float));
+    Launch l(h, PM_K_PREP, h->stream);
+    launch_prep_view(h, ps, d_iml, d_imr, d_Gl, d_Gr, step / sizeof(float), h->stream);
   }
   if (int rc = launch_check(h, "prep_view")) return rc;
   {
-    Launch l(h, PM_K_PREP);
-    if (int rc = run_transpose(h, ps, 1)) return rc;
+    Launch l(h, PM_K_PREP, h->stream);
+    if (int rc = run_transpose(h, ps, 1, -1, h->stream)) return rc;
   }
   {
-    Launch l(h, PM_K_SEED);
-    launch_copy_disp_strided(h, ps, d_disp, disp_step / sizeof(float), 0);
+    Launch l(h, PM_K_SEED, h->stream);
+    launch_copy_disp_strided(h, ps, d_disp, disp_step / sizeof(float), 0, h->stream);
   }
   if (int rc = launch_check(h, "seed")) return rc;
   h->need_seed[0] = h->need_seed[1] = false;
-  if (int rc = run_one_view_set(h, ps, 1)) return rc;
+  if (int rc = run_view_sets(h, &ps, &h->stream, 1, 1)) return rc;
   {
-    Launch l(h, PM_K_FINALIZE);
-    launch_copy_disp_strided(h, ps, d_disp, disp_step / sizeof(float), 1);
+    Launch l(h, PM_K_FINALIZE, h->stream);
+    launch_copy_disp_strided(h, ps, d_disp, disp_step / sizeof(float), 1, h->stream);
   }
   if (int rc = launch_check(h, "copy out")) return rc;
   if (foreign) {

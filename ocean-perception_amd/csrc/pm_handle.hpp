@@ -212,7 +212,7 @@ hipError_t create_stream(hipStream_t* s, int kind, int prio_class);
 int create_handle_streams(pm_handle* h);  // the handle's four streams, together (pm_engine.hip)
 
 // Brackets the launches of one kernel class with a pair of events while the handle is profiling.
-// While the handle is profiling, the launches of one kernel class are bracketed by events on the current stream.  An
+// While the handle is profiling, the launches of one kernel class are bracketed by events on the stream they go to.  An
 // in-stream event before a launch fires when the launch in front of it has finished: the stop event of the previous
 // bracket on the same stream IS the start of the next one, so a chain of launches costs one event per launch, not two
 // (each record is a serialising packet in the queue: with two per launch a profiled Match ran 7 % longer).  prof_break()
@@ -229,14 +229,15 @@ inline void prof_break_all(pm_handle* h) { h->n_prof_tail = 0; }
 struct Launch {
   pm_handle* h;
   int klass;
+  hipStream_t stream;
   bool timed;
   int rec = -1;
-  Launch(pm_handle* h_, int k) : h(h_), klass(k), timed(h_->profiling) {
+  Launch(pm_handle* h_, int k, hipStream_t s) : h(h_), klass(k), stream(s), timed(h_->profiling) {
     if (!timed) return;
     if (h->ev_used == (int)h->ev_pool.size()) {
       if ((int)h->ev_pool.size() >= kMaxEvents) {
         timed = false;  // drained by pm_profile_read; never block inside a launch path
-        prof_break(h, h->stream);
+        prof_break(h, stream);
         return;
       }
       EventRec r;
@@ -253,18 +254,18 @@ struct Launch {
     r.klass = k;
     r.start_ref = -1;
     for (int i = 0; i < h->n_prof_tail; ++i)
-      if (h->prof_tail[i].stream == h->stream) r.start_ref = h->prof_tail[i].rec;
-    if (r.start_ref < 0) (void)hipEventRecord(r.start, h->stream);
+      if (h->prof_tail[i].stream == stream) r.start_ref = h->prof_tail[i].rec;
+    if (r.start_ref < 0) (void)hipEventRecord(r.start, stream);
   }
   ~Launch() {
     if (!timed || rec < 0) return;
-    (void)hipEventRecord(h->ev_pool[rec].stop, h->stream);
+    (void)hipEventRecord(h->ev_pool[rec].stop, stream);
     for (int i = 0; i < h->n_prof_tail; ++i)
-      if (h->prof_tail[i].stream == h->stream) {
+      if (h->prof_tail[i].stream == stream) {
         h->prof_tail[i].rec = rec;
         return;
       }
-    if (h->n_prof_tail < pm_handle::kProfTails) h->prof_tail[h->n_prof_tail++] = {h->stream, rec};
+    if (h->n_prof_tail < pm_handle::kProfTails) h->prof_tail[h->n_prof_tail++] = {stream, rec};
   }
 };
 
@@ -282,27 +283,26 @@ int refuse_while_capturing(pm_handle* h, const char* what);
 int capture_open(pm_handle* h);                                             // pm_engine.hip
 int capture_close(pm_handle* h, hipGraphExec_t* exec, const char* what);
 bool pair_planes_wanted(const pm_handle* h);
-int pair_planes_alloc(pm_handle* h);
-int run_one_view_set(pm_handle* h, const PlaneSet& ps, int slots);
+int pair_planes_alloc(pm_handle* h, hipStream_t stream);
 int match_device_impl(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
                       const float* d_seed_l, const float* d_seed_r, float* d_disp_l, float* d_disp_r);
-// view streams, chunk events, and one chunk of a batch / frame sequence (pm_engine.hip)
+// view streams, chunk events, fork / join, and one chunk of a batch / frame sequence (pm_engine.hip)
 int view_streams_create(pm_handle* h);
-PlaneSet pair_plane_set(const PlaneSet& ps, int b);  // the plane set of the pairs from b on
-int lane_fork(pm_handle* h);
-int lane_join(pm_handle* h);
+PlaneSet plane_set_of_pair(const PlaneSet& ps, int b);  // the plane set of the pairs from b on
+int fork_stream(pm_handle* h, hipEvent_t ev, hipStream_t from, hipStream_t onto);
+int join_stream(pm_handle* h, hipStream_t from, hipEvent_t ev, hipStream_t onto);
 int seq_events_create(pm_handle* h);
-int seq_chunk_pairs();
+int pair_chunk();
 bool seq_pipelined(const pm_handle* h);
 int seq_enqueue_chunk(pm_handle* h, int b, int c, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
                       const float* d_seed_l, const float* d_seed_r, float* d_disp_l, float* d_disp_r, hipEvent_t ready,
                       hipEvent_t slot_free, hipEvent_t v_done[2], hipEvent_t head_done);
 SeedParams seed_params(const pm_params& p);
-int alloc_seed_scratch(pm_handle* h, SeedScratch& sc);
+int alloc_seed_scratch(pm_handle* h, SeedScratch& sc, hipStream_t stream);
 // SparseInit (or Patchmatch::Initialize(.., 1)) for view `view` of pair `b` straight into its disparity plane
-int run_sparse_init(pm_handle* h, const PlaneSet& ps, int b, int view, int scratch = 0, unsigned stages = kSeedAllStages);
+int run_sparse_init(pm_handle* h, const PlaneSet& ps, int b, int view, int scratch, unsigned stages, hipStream_t stream);
 
-// ---- pm_launch.hip: one function per scalar-mode kernel, enqueued on h->stream -----------------------------------
+// ---- pm_launch.hip: one function per scalar-mode kernel, enqueued on `stream` (the last parameter) ---------------
 // k_prep, or k_prep_bgr when the call came in through pm_match_bgr_device (the gray images are then never stored)
 // seeds != null: the launch also copies the seed maps (null members = all background) into the disparity planes of its
 // view(s), i.e. what launch_seed does
@@ -310,41 +310,49 @@ struct PrepSeedMaps {
   const float* l;
   const float* r;
 };
+// view >= 0: that view only; view -1: both
 void launch_prep(pm_handle* h, const PlaneSet& ps, const uint8_t* d_left, const uint8_t* d_right, int n, size_t stride,
-                 int view = -1, const PrepSeedMaps* seeds = nullptr);
+                 int view, const PrepSeedMaps* seeds, hipStream_t stream);
 void launch_prep_view(pm_handle* h, const PlaneSet& ps, const float* d_iml, const float* d_imr, const float* d_Gl,
-                      const float* d_Gr, size_t stride);
+                      const float* d_Gr, size_t stride, hipStream_t stream);
 // transposed copies + line-triple / quad planes of n pairs (run by every path that ran a prep kernel);
 // view >= 0: the planes of that view only (per-view streams: each stream derives its own planes)
-int run_transpose(pm_handle* h, const PlaneSet& ps, int n, int view = -1);
-void launch_seed(pm_handle* h, const PlaneSet& ps, const float* d_seed_l, const float* d_seed_r, int n, int view = -1);
+int run_transpose(pm_handle* h, const PlaneSet& ps, int n, int view, hipStream_t stream);
+void launch_seed(pm_handle* h, const PlaneSet& ps, const float* d_seed_l, const float* d_seed_r, int n, int view,
+                 hipStream_t stream);
 // noise + clamp + cost of the current disparity (amount < 0: cost only); RemoveBackground / MaskBackground
 void launch_noise_cost(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const Interior& in, float amount,
-                       int slots, int keep_zero);
-void launch_noise_only(pm_handle* h, const PlaneSet& ps, const CostParams& cp, float amount);
+                       int slots, int keep_zero, hipStream_t stream);
+void launch_noise_only(pm_handle* h, const PlaneSet& ps, const CostParams& cp, float amount, hipStream_t stream);
 void launch_background(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const Interior& in, float factor,
-                       int cached, int slots);
-int run_sweep(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, float amp = 1e30f);
-void launch_finalize(pm_handle* h, const PlaneSet& ps, float* d_disp_l, float* d_disp_r, int n);
-void launch_mask_occlusions(pm_handle* h, float* d_disp_l, const float* d_disp_r, int rows, int cols);
-void launch_state_row(pm_handle* h, const PlaneSet& ps, int r, float* d_buf, int to_buf);
+                       int cached, int slots, hipStream_t stream);
+// amp: the iteration's noise amplitude (1e30f: none)
+int run_sweep(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, float amp,
+              hipStream_t stream);
+void launch_finalize(pm_handle* h, const PlaneSet& ps, float* d_disp_l, float* d_disp_r, int n, hipStream_t stream);
+void launch_mask_occlusions(pm_handle* h, float* d_disp_l, const float* d_disp_r, int rows, int cols,
+                            hipStream_t stream);
+void launch_state_row(pm_handle* h, const PlaneSet& ps, int r, float* d_buf, int to_buf, hipStream_t stream);
 void launch_restore_cols(pm_handle* h, const PlaneSet& ps, const float* snap_disp, const float* snap_cost,
-                         const int* d_mask);
+                         const int* d_mask, hipStream_t stream);
 void launch_tile_round(pm_handle* h, const PlaneSet& ps, const float* snap_disp, const float* snap_cost,
                        const float* d_incoming, const float* d_used, float* d_used_next, int* d_mask, int pred_r,
-                       int y_lo, int y_hi);
-void launch_state_row_moved(pm_handle* h, const PlaneSet& ps, int r, const float* d_ref, int* d_flag);
-void launch_tile_presweep(pm_handle* h, const PlaneSet& ps, float* snap_disp, float* snap_cost, const float* d_row, int pred_r);
+                       int y_lo, int y_hi, hipStream_t stream);
+void launch_state_row_moved(pm_handle* h, const PlaneSet& ps, int r, const float* d_ref, int* d_flag,
+                            hipStream_t stream);
+void launch_tile_presweep(pm_handle* h, const PlaneSet& ps, float* snap_disp, float* snap_cost, const float* d_row,
+                          int pred_r, hipStream_t stream);
 // rows x cols floats from tight device memory into page-locked host memory (its DEVICE address), row stride in floats
 void launch_download(pm_handle* h, float* dst_dev, size_t dst_step_floats, const float* d_src, int rows, int cols,
                      hipStream_t stream);
 void launch_upload(pm_handle* h, float* d_dst, const float* src_dev, int words, hipStream_t stream);
-void launch_copy_in(pm_handle* h, const PlaneSet& ps, const float* d_src);
-void launch_copy_out(pm_handle* h, const PlaneSet& ps, float* d_dst, int which);
-void launch_copy_disp_strided(pm_handle* h, const PlaneSet& ps, float* d_buf, size_t stride, int to_buf);
+void launch_copy_in(pm_handle* h, const PlaneSet& ps, const float* d_src, hipStream_t stream);
+void launch_copy_out(pm_handle* h, const PlaneSet& ps, float* d_dst, int which, hipStream_t stream);
+void launch_copy_disp_strided(pm_handle* h, const PlaneSet& ps, float* d_buf, size_t stride, int to_buf,
+                              hipStream_t stream);
 
 // ---- pm_planes_host.hip ------------------------------------------------------------------------------------------
-int planes_alloc(pm_handle* h);
+int planes_alloc(pm_handle* h, hipStream_t stream);
 int planes_match(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
                  const float* d_seed_l, const float* d_seed_r, float* d_disp_l, float* d_disp_r);
 

@@ -177,7 +177,7 @@ bool can_gang(const pm_handle* h, const pm_handle::PipeSlot& a, const pm_handle:
 int enqueue_or_hold(pm_handle* h, int slot) {
   // (plane mode is not pipelined over the view streams, but two of its frames make a batch of two lanes)
   const bool gangs = seq_pipelined(h) || (h->params.mode == PM_MODE_PLANES && !h->bgr);
-  const bool hold = gangs && seq_chunk_pairs() >= 2 && slot + 1 < h->max_batch && device_busy(h);
+  const bool hold = gangs && pair_chunk() >= 2 && slot + 1 < h->max_batch && device_busy(h);
   return hold ? PM_OK : enqueue_frames(h, slot, 1);
 }
 
@@ -416,7 +416,7 @@ int pm_match_batch_u8(pm_handle* h, int n, const uint8_t* const* left, const uin
   const size_t frow = sizeof(float) * (size_t)cols;
   const bool any_sl = nl > 0, any_sr = nr > 0;
   const bool chunks = seq_pipelined(h);
-  const int chunk = chunks ? seq_chunk_pairs() : n;
+  const int chunk = chunks ? pair_chunk() : n;
   h->pipe_head = 0;
   for (int b = 0; b < n; b += chunk) {
     const int c = n - b < chunk ? n - b : chunk;
@@ -740,9 +740,9 @@ int stage_prep(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows
   PM_HIP(h, hipMemcpyAsync(h->st_left, left, px, hipMemcpyHostToDevice, h->stream));
   PM_HIP(h, hipMemcpyAsync(h->st_right, right ? right : left, px, hipMemcpyHostToDevice, h->stream));
   const PlaneSet ps = plane_set(h, rows, cols, 1);
-  launch_prep(h, ps, h->st_left, h->st_right, 1, (size_t)cols);
+  launch_prep(h, ps, h->st_left, h->st_right, 1, (size_t)cols, -1, nullptr, h->stream);
   if (int rc = launch_check(h, "prep")) return rc;
-  if (int rc = run_transpose(h, ps, 1)) return rc;
+  if (int rc = run_transpose(h, ps, 1, -1, h->stream)) return rc;
   *ps_out = ps;
   return PM_OK;
 }
@@ -750,13 +750,13 @@ int stage_prep(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows
 int stage_disp_in(pm_handle* h, const PlaneSet& ps, const float* disp) {
   const size_t px = (size_t)ps.rows * ps.cols;
   PM_HIP(h, hipMemcpyAsync(h->st_disp_l, disp, sizeof(float) * px, hipMemcpyHostToDevice, h->stream));
-  launch_copy_in(h, ps, h->st_disp_l);
+  launch_copy_in(h, ps, h->st_disp_l, h->stream);
   return launch_check(h, "copy_in");
 }
 
 int stage_out(pm_handle* h, const PlaneSet& ps, float* dst, int which) {
   const size_t px = (size_t)ps.rows * ps.cols;
-  launch_copy_out(h, ps, h->st_disp_l, which);
+  launch_copy_out(h, ps, h->st_disp_l, which, h->stream);
   if (int rc = launch_check(h, "copy_out")) return rc;
   PM_HIP(h, hipMemcpyAsync(dst, h->st_disp_l, sizeof(float) * px, hipMemcpyDeviceToHost, h->stream));
   PM_HIP(h, hipStreamSynchronize(h->stream));
@@ -805,7 +805,7 @@ int pm_add_noise(pm_handle* h, float* disp, int rows, int cols, float amount) {
   const PlaneSet ps = plane_set(h, rows, cols, 1);
   if (int rc = stage_disp_in(h, ps, disp)) return rc;
   CostParams cp = cost_params(h->params, 3, 3);
-  launch_noise_only(h, ps, cp, amount);
+  launch_noise_only(h, ps, cp, amount, h->stream);
   if (int rc = launch_check(h, "noise")) return rc;
   return stage_out(h, ps, disp, 0);
 }
@@ -825,11 +825,11 @@ int pm_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, int ro
   if (int rc = stage_disp_in(h, ps, disp)) return rc;
   const CostParams cp = cost_params(h->params, patch_w, patch_h);
   const Interior in = interior(h->params, rows, cols, cp.pw, cp.ph);
-  launch_noise_cost(h, ps, cp, in, -1.f, 1, 0);
+  launch_noise_cost(h, ps, cp, in, -1.f, 1, 0, h->stream);
   if (int rc = launch_check(h, "cost")) return rc;
   for (int k = 0; k < 4; ++k)
     if (pass_mask & (1 << k))
-      if (int rc = run_sweep(h, ps, cp, sweep_geom(h->params, in, k), 1)) return rc;
+      if (int rc = run_sweep(h, ps, cp, sweep_geom(h->params, in, k), 1, 1e30f, h->stream)) return rc;
   return stage_out(h, ps, disp, 0);
 }
 
@@ -848,7 +848,7 @@ int pm_remove_background(pm_handle* h, const uint8_t* left, const uint8_t* right
   if (int rc = stage_disp_in(h, ps, disp)) return rc;
   const CostParams cp = cost_params(h->params, patch_w, patch_h);
   const Interior in = interior(h->params, rows, cols, cp.pw, cp.ph);
-  launch_background(h, ps, cp, in, factor, 0, 1);
+  launch_background(h, ps, cp, in, factor, 0, 1, h->stream);
   if (int rc = launch_check(h, "background")) return rc;
   return stage_out(h, ps, disp, 0);
 }
@@ -922,7 +922,7 @@ int pm_mask_occlusions(pm_handle* h, float* disp_l, const float* disp_r, int row
   const size_t px = (size_t)rows * cols;
   PM_HIP(h, hipMemcpyAsync(h->st_disp_l, disp_l, sizeof(float) * px, hipMemcpyHostToDevice, h->stream));
   PM_HIP(h, hipMemcpyAsync(h->st_disp_r, disp_r, sizeof(float) * px, hipMemcpyHostToDevice, h->stream));
-  launch_mask_occlusions(h, h->st_disp_l, h->st_disp_r, rows, cols);
+  launch_mask_occlusions(h, h->st_disp_l, h->st_disp_r, rows, cols, h->stream);
   if (int rc = launch_check(h, "mask_occlusions")) return rc;
   PM_HIP(h, hipMemcpyAsync(disp_l, h->st_disp_l, sizeof(float) * px, hipMemcpyDeviceToHost, h->stream));
   PM_HIP(h, hipStreamSynchronize(h->stream));

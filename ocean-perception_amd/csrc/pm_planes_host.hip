@@ -52,7 +52,7 @@ static int planes_dbg() {
 }
 namespace eng {
 
-int planes_alloc(pm_handle* h) {
+int planes_alloc(pm_handle* h, hipStream_t stream) {
   if (h->planes_state) return PM_OK;
   {  // the tile of the widest stage must fit the CU's LDS: (128 + P-1 + max_disp + slope margin) x (8 + P-1) entries
     const PlanesParams pp = planes_params(h->params);
@@ -67,7 +67,7 @@ int planes_alloc(pm_handle* h) {
   const size_t plane = (size_t)h->max_rows * h->max_pitch;
   const size_t bytes = sizeof(float) * ((size_t)h->max_batch * 2 * 4 * plane + 64);
   PM_HIP(h, hipMalloc(&h->planes_state, bytes));
-  PM_HIP(h, hipMemsetAsync(h->planes_state, 0, bytes, h->stream));
+  PM_HIP(h, hipMemsetAsync(h->planes_state, 0, bytes, stream));
   return PM_OK;
 }
 
@@ -87,13 +87,14 @@ bool planes_two_lanes() {
 
 // pair0: the launch covers the pairs from pair0 on (`ps` is the plan's plane set; slots counts from that pair)
 template <int STAGE>
-int planes_stage(pm_handle* h, const PlaneSet& ps0, const PlArgs& ar, int slots, int klass, const char* what, int pair0 = 0) {
-  Launch l(h, klass);
+int planes_stage(pm_handle* h, const PlaneSet& ps0, const PlArgs& ar, int slots, int klass, const char* what, int pair0,
+                 hipStream_t stream) {
+  Launch l(h, klass, stream);
   const bool f16 = h->params.state_dtype == PM_STATE_F16;
-  const PlaneSet ps = pair0 ? pair_plane_set(ps0, pair0) : ps0;
+  const PlaneSet ps = pair0 ? plane_set_of_pair(ps0, pair0) : ps0;
   // PlaneState::arr: a pair holds 2 views x 4 arrays of `plane` elements
   char* state = (char*)h->planes_state + (size_t)pair0 * 8 * ps0.plane * (f16 ? sizeof(_Float16) : sizeof(float));
-  const hipError_t e = pl_launch<STAGE>(ps, state, f16, planes_params(h->params), ar, slots, h->stream);
+  const hipError_t e = pl_launch<STAGE>(ps, state, f16, planes_params(h->params), ar, slots, stream);
   if (e != hipSuccess) {
     set_err(h, "launch of planes %s failed: %s", what, hipGetErrorString(e));
     return PM_ERR_HIP;
@@ -101,7 +102,7 @@ int planes_stage(pm_handle* h, const PlaneSet& ps0, const PlArgs& ar, int slots,
   return PM_OK;
 }
 
-int planes_step(pm_handle* h, const PlaneSet& ps, int n, int stage, int arg, int pair0 = 0) {
+int planes_step(pm_handle* h, const PlaneSet& ps, int n, int stage, int arg, int pair0, hipStream_t stream) {
   const int nv = ps.n_views;
   PlArgs ar{};
   ar.dbg = planes_dbg();
@@ -110,22 +111,23 @@ int planes_step(pm_handle* h, const PlaneSet& ps, int n, int stage, int arg, int
   ar.view_fixed = -1;
   switch (stage) {
     case PM_PL_SPATIAL:
-      return planes_stage<PL_SPATIAL>(h, ps, ar, n * nv, PM_K_PL_SPATIAL, "spatial propagation", pair0);
+      return planes_stage<PL_SPATIAL>(h, ps, ar, n * nv, PM_K_PL_SPATIAL, "spatial propagation", pair0, stream);
     case PM_PL_VIEW:
       if (nv < 2) return PM_OK;
       ar.view_fixed = arg;
-      return planes_stage<PL_VIEW>(h, ps, ar, n, PM_K_PL_VIEW, "view propagation", pair0);
+      return planes_stage<PL_VIEW>(h, ps, ar, n, PM_K_PL_VIEW, "view propagation", pair0, stream);
     case PM_PL_REFINE:
       ar.refine_amp = h->params.noise_amp[arg];
-      return planes_stage<PL_REFINE>(h, ps, ar, n * nv, PM_K_PL_REFINE, "refinement", pair0);
+      return planes_stage<PL_REFINE>(h, ps, ar, n * nv, PM_K_PL_REFINE, "refinement", pair0, stream);
     case PM_PL_VIEW_REFINE: {  // arg = iteration * 2 + view: view propagation into `view`, then its refinement
       const int view = arg & 1, it = arg >> 1;
       if (view >= nv) return PM_OK;
       ar.arg = it;
       ar.view_fixed = view;
       ar.refine_amp = h->params.noise_amp[it];
-      if (nv < 2) return planes_stage<PL_REFINE>(h, ps, ar, n, PM_K_PL_REFINE, "refinement", pair0);
-      return planes_stage<PL_VIEW_REFINE>(h, ps, ar, n, PM_K_PL_VIEW_REFINE, "view propagation + refinement", pair0);
+      if (nv < 2) return planes_stage<PL_REFINE>(h, ps, ar, n, PM_K_PL_REFINE, "refinement", pair0, stream);
+      return planes_stage<PL_VIEW_REFINE>(h, ps, ar, n, PM_K_PL_VIEW_REFINE, "view propagation + refinement", pair0,
+                                          stream);
     }
     default:
       set_err(h, "unknown planes stage %d", stage);
@@ -135,13 +137,13 @@ int planes_step(pm_handle* h, const PlaneSet& ps, int n, int stage, int arg, int
 
 // prep (images, gradients, packed planes) + seeds + random initialisation of n pairs
 int planes_begin(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
-                 const float* d_seed_l, const float* d_seed_r) {
-  if (int rc = planes_alloc(h)) return rc;
+                 const float* d_seed_l, const float* d_seed_r, hipStream_t stream) {
+  if (int rc = planes_alloc(h, stream)) return rc;
   const int nv = h->params.left_right_check ? 2 : 1;
   PlaneSet ps = plane_set(h, rows, cols, nv);
   {
-    Launch l(h, PM_K_PREP);
-    launch_prep(h, ps, d_left, d_right, n, (size_t)cols);
+    Launch l(h, PM_K_PREP, stream);
+    launch_prep(h, ps, d_left, d_right, n, (size_t)cols, -1, nullptr, stream);
   }
   if (int rc = launch_check(h, "prep")) return rc;
   const float* sl = d_seed_l;
@@ -153,9 +155,9 @@ int planes_begin(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_ri
     // which the initialisation kernel takes the seeds (view 1's plane is already in mirrored coordinates)
     for (int v = 0; v < nv; ++v) {
       if (v == 0 ? sl != nullptr : sr != nullptr) continue;
-      Launch l(h, PM_K_SEED);
+      Launch l(h, PM_K_SEED, stream);
       for (int b = 0; b < n; ++b)
-        if (int rc = run_sparse_init(h, ps, b, v, 0)) return rc;
+        if (int rc = run_sparse_init(h, ps, b, v, 0, kSeedAllStages, stream)) return rc;
       ar.seed_in_disp |= 1 << v;
     }
   }
@@ -163,7 +165,7 @@ int planes_begin(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_ri
   ar.view_fixed = -1;
   ar.seed_l = sl;
   ar.seed_r = sr;
-  if (int rc = planes_stage<PL_INIT>(h, ps, ar, n * nv, PM_K_PL_INIT, "initialisation")) return rc;
+  if (int rc = planes_stage<PL_INIT>(h, ps, ar, n * nv, PM_K_PL_INIT, "initialisation", 0, stream)) return rc;
   h->pl_rows = rows;
   h->pl_cols = cols;
   h->pl_n = n;
@@ -171,18 +173,18 @@ int planes_begin(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_ri
   return PM_OK;
 }
 
-int planes_finish(pm_handle* h, float* d_disp_l, float* d_disp_r) {
+int planes_finish(pm_handle* h, float* d_disp_l, float* d_disp_r, hipStream_t stream) {
   const int nv = h->params.left_right_check ? 2 : 1;
   const PlaneSet ps = plane_set(h, h->pl_rows, h->pl_cols, nv);
   const PlanesParams pp = planes_params(h->params);
-  Launch l(h, PM_K_FINALIZE);
+  Launch l(h, PM_K_FINALIZE, stream);
   if (h->params.state_dtype == PM_STATE_F16) {
     PlaneState<_Float16> st{(_Float16*)h->planes_state, ps.plane, ps.pitch / 2};
-    hipLaunchKernelGGL(k_planes_finish<_Float16>, pixel_grid(ps.cols, ps.rows, h->pl_n), dim3(256), 0, h->stream, ps,
+    hipLaunchKernelGGL(k_planes_finish<_Float16>, pixel_grid(ps.cols, ps.rows, h->pl_n), dim3(256), 0, stream, ps,
                        st, pp, d_disp_l, d_disp_r, (size_t)ps.cols);
   } else {
     PlaneState<float> st{(float*)h->planes_state, ps.plane, ps.pitch / 2};
-    hipLaunchKernelGGL(k_planes_finish<float>, pixel_grid(ps.cols, ps.rows, h->pl_n), dim3(256), 0, h->stream, ps, st,
+    hipLaunchKernelGGL(k_planes_finish<float>, pixel_grid(ps.cols, ps.rows, h->pl_n), dim3(256), 0, stream, ps, st,
                        pp, d_disp_l, d_disp_r, (size_t)ps.cols);
   }
   return launch_check(h, "planes finish");
@@ -211,7 +213,7 @@ namespace eng {
 // The whole schedule of oracle/pm_planes_oracle.c::pmo_planes_match.
 int planes_match(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
                  const float* d_seed_l, const float* d_seed_r, float* d_disp_l, float* d_disp_r) {
-  if (int rc = planes_begin(h, n, d_left, d_right, rows, cols, d_seed_l, d_seed_r)) return rc;
+  if (int rc = planes_begin(h, n, d_left, d_right, rows, cols, d_seed_l, d_seed_r, h->stream)) return rc;
   const int nv = h->params.left_right_check ? 2 : 1;
   const PlaneSet ps = plane_set(h, rows, cols, nv);
   // A batch runs as TWO LANES: the first half of its pairs through the iterations on the handle's stream, the second
@@ -219,36 +221,33 @@ int planes_match(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_ri
   // with a tail in which a few tiles hold the chip; the other lane's launch fills it (two handles side by side matched
   // 560 pairs/s where one matched 469 / 521 / 552 with 1 / 2 / 4 pairs per launch: tools/multi_handle.py, round 6).
   const int n_lane[2] = {planes_two_lanes() && n >= 2 ? (n + 1) / 2 : n, planes_two_lanes() && n >= 2 ? n / 2 : 0};
-  hipStream_t lane_stream[2] = {h->stream, h->stream};
+  const hipStream_t lane_stream[2] = {h->stream, h->view1_stream};
   if (n_lane[1]) {
-    if (int rc = lane_fork(h)) return rc;
-    lane_stream[1] = h->view1_stream;
+    if (int rc = view_streams_create(h)) return rc;
+    if (int rc = fork_stream(h, h->view_fork, h->stream, h->view1_stream)) return rc;
   }
-  struct Restore {
-    pm_handle* h;
-    hipStream_t s;
-    ~Restore() { h->stream = s; }
-  } restore{h, h->stream};
   auto both = [&](int stage, int arg) -> int {
-    for (int lane = 0; lane < 2; ++lane) {
-      if (!n_lane[lane]) continue;
-      h->stream = lane_stream[lane];  // every launch helper enqueues on h->stream
-      if (int rc = planes_step(h, ps, n_lane[lane], stage, arg, lane ? n_lane[0] : 0)) return rc;
-    }
-    h->stream = restore.s;
+    for (int lane = 0; lane < 2; ++lane)
+      if (n_lane[lane])
+        if (int rc = planes_step(h, ps, n_lane[lane], stage, arg, lane ? n_lane[0] : 0, lane_stream[lane])) return rc;
     return PM_OK;
   };
-  for (int it = 0; it < h->params.patchmatch_iters; ++it) {
-    if (int rc = both(PM_PL_SPATIAL, 2 * it)) return rc;
-    if (int rc = both(PM_PL_SPATIAL, 2 * it + 1)) return rc;
-    // per view: view propagation then refinement, fused in one launch (one tile fill for 1 + R candidates)
-    for (int v = 0; v < nv; ++v)
-      if (int rc = both(PM_PL_VIEW_REFINE, it * 2 + v)) return rc;
+  auto iterations = [&]() -> int {
+    for (int it = 0; it < h->params.patchmatch_iters; ++it) {
+      if (int rc = both(PM_PL_SPATIAL, 2 * it)) return rc;
+      if (int rc = both(PM_PL_SPATIAL, 2 * it + 1)) return rc;
+      // per view: view propagation then refinement, fused in one launch (one tile fill for 1 + R candidates)
+      for (int v = 0; v < nv; ++v)
+        if (int rc = both(PM_PL_VIEW_REFINE, it * 2 + v)) return rc;
+    }
+    return PM_OK;
+  };
+  int rc = iterations();
+  if (n_lane[1]) {  // on every path: lane 1 may still be writing the plane state
+    const int rc_join = join_stream(h, h->view1_stream, h->view1_join, h->stream);
+    if (rc == PM_OK) rc = rc_join;
   }
-  h->stream = restore.s;
-  if (n_lane[1])
-    if (int rc = lane_join(h)) return rc;
-  return planes_finish(h, d_disp_l, d_disp_r);
+  return rc != PM_OK ? rc : planes_finish(h, d_disp_l, d_disp_r, h->stream);
 }
 
 }  // namespace eng
@@ -264,7 +263,7 @@ int pm_planes_begin(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d
     return PM_ERR_INVALID_ARG;
   }
   if (int rc = check_size(h, rows, cols, n)) return rc;
-  return planes_begin(h, n, d_left, d_right, rows, cols, d_seed_l, d_seed_r);
+  return planes_begin(h, n, d_left, d_right, rows, cols, d_seed_l, d_seed_r, h->stream);
 }
 
 int pm_planes_step(pm_handle* h, int stage, int arg) {
@@ -278,7 +277,7 @@ int pm_planes_step(pm_handle* h, int stage, int arg) {
     set_err(h, "pm_planes_step: stage %d / argument %d out of range", stage, arg);
     return PM_ERR_INVALID_ARG;
   }
-  return planes_step(h, plane_set(h, h->pl_rows, h->pl_cols, nv), h->pl_n, stage, arg);
+  return planes_step(h, plane_set(h, h->pl_rows, h->pl_cols, nv), h->pl_n, stage, arg, 0, h->stream);
 }
 
 static int planes_rw(pm_handle* h, int pair, int view, float* planes, int to_state, const char* what) {
@@ -330,7 +329,7 @@ int pm_planes_finish(pm_handle* h, float* d_disp_l, float* d_disp_r) {
     set_err(h, "pm_planes_finish: null output");
     return PM_ERR_INVALID_ARG;
   }
-  return planes_finish(h, d_disp_l, d_disp_r);
+  return planes_finish(h, d_disp_l, d_disp_r, h->stream);
 }
 
 }  // extern "C"

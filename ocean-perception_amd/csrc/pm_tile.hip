@@ -72,10 +72,10 @@ int pm_tile_begin(pm_handle* h, const pm_tile* tile, const uint8_t* d_left_band,
   h->tile_cols = cols;
   h->tile_on = true;
   const PlaneSet ps = tile_plane_set(h);
-  launch_prep(h, ps, d_left_band, d_right_band, 1, (size_t)cols);
+  launch_prep(h, ps, d_left_band, d_right_band, 1, (size_t)cols, -1, nullptr, h->stream);
   if (int rc = launch_check(h, "prep")) return rc;
-  if (int rc = run_transpose(h, ps, 1)) return rc;
-  launch_seed(h, ps, d_seed_l_band, d_seed_r_band, 1);
+  if (int rc = run_transpose(h, ps, 1, -1, h->stream)) return rc;
+  launch_seed(h, ps, d_seed_l_band, d_seed_r_band, 1, -1, h->stream);
   return launch_check(h, "seed");
 }
 
@@ -89,7 +89,7 @@ int pm_tile_noise(pm_handle* h, int it) {
   const PlaneSet ps = tile_plane_set(h);
   const CostParams cp = cost_params(p, p.patch_w[it], p.patch_h[it]);
   const Interior in = tile_interior(h, cp.pw, cp.ph);
-  launch_noise_cost(h, ps, cp, in, p.noise_amp[it], ps.n_views, 0);
+  launch_noise_cost(h, ps, cp, in, p.noise_amp[it], ps.n_views, 0, h->stream);
   return launch_check(h, "noise_cost");
 }
 
@@ -140,7 +140,7 @@ static int tile_sweep(pm_handle* h, int it, int k, const int* d_mask) {
     g.s_first -= t.band_row0;
     g.s_last -= t.band_row0;
   }
-  return run_sweep(h, ps, cp, g, ps.n_views, p.noise_amp[it]);
+  return run_sweep(h, ps, cp, g, ps.n_views, p.noise_amp[it], h->stream);
 }
 
 int pm_tile_snapshot(pm_handle* h) {
@@ -171,7 +171,7 @@ int pm_tile_presweep(pm_handle* h, int pred_image_row, const float* d_row) {
     PM_HIP(h, hipMalloc((void**)&h->snap_cost, sizeof(float) * 2 * plane));
   }
   const PlaneSet ps = tile_plane_set(h);
-  launch_tile_presweep(h, ps, h->snap_disp, h->snap_cost, d_row, d_row ? r : -4);
+  launch_tile_presweep(h, ps, h->snap_disp, h->snap_cost, d_row, d_row ? r : -4, h->stream);
   return launch_check(h, "tile_presweep");
 }
 
@@ -195,7 +195,7 @@ int pm_tile_restore_cols(pm_handle* h, const int* d_mask) {
     return PM_ERR_INVALID_ARG;
   }
   const PlaneSet ps = tile_plane_set(h);
-  launch_restore_cols(h, ps, h->snap_disp, h->snap_cost, d_mask);
+  launch_restore_cols(h, ps, h->snap_disp, h->snap_cost, d_mask, h->stream);
   return launch_check(h, "restore_cols");
 }
 
@@ -223,7 +223,7 @@ int pm_tile_exchange_round(pm_handle* h, int it, int k, int pred_image_row, cons
     set_err(h, "pm_tile_exchange_round: row %d is one of the band's own rows, not a neighbour's", pred_image_row);
     return PM_ERR_INVALID_ARG;
   }
-  launch_tile_round(h, ps, h->snap_disp, h->snap_cost, d_incoming, d_used, d_used_next, d_mask, r, y_lo, y_hi);
+  launch_tile_round(h, ps, h->snap_disp, h->snap_cost, d_incoming, d_used, d_used_next, d_mask, r, y_lo, y_hi, h->stream);
   if (int rc = launch_check(h, "tile_round")) return rc;
   return tile_sweep(h, it, k, d_mask);
 }
@@ -236,7 +236,7 @@ int pm_tile_row_moved(pm_handle* h, int image_row, const float* d_ref_row, int* 
     return PM_ERR_INVALID_ARG;
   }
   const PlaneSet ps = tile_plane_set(h);
-  launch_state_row_moved(h, ps, r, d_ref_row, d_flag);
+  launch_state_row_moved(h, ps, r, d_ref_row, d_flag, h->stream);
   return launch_check(h, "state_row_moved");
 }
 
@@ -249,7 +249,7 @@ static int tile_row_copy(pm_handle* h, int image_row, float* d_dst, const float*
   }
   const PlaneSet ps = tile_plane_set(h);
   // (the state planes keep four rows interleaved: a row is every fourth word of a stretch -- a small kernel, not a copy)
-  launch_state_row(h, ps, r, d_dst ? d_dst : const_cast<float*>(d_src), d_dst ? 1 : 0);
+  launch_state_row(h, ps, r, d_dst ? d_dst : const_cast<float*>(d_src), d_dst ? 1 : 0, h->stream);
   return launch_check(h, what);
 }
 
@@ -270,7 +270,7 @@ int pm_tile_background(pm_handle* h) {
   const int cached = (last >= 0 && bcp.pw == (p.semantics == PM_SEM_CPU ? p.patch_w[last] : 3) &&
                       bcp.ph == (p.semantics == PM_SEM_CPU ? p.patch_h[last] : 3)) ? 1 : 0;
   const float factor = p.semantics == PM_SEM_CPU ? p.win_by_factor : p.cost_improve_factor;
-  launch_background(h, ps, bcp, in, factor, cached, ps.n_views);
+  launch_background(h, ps, bcp, in, factor, cached, ps.n_views, h->stream);
   return launch_check(h, "background");
 }
 
@@ -281,7 +281,7 @@ int pm_tile_finish(pm_handle* h, float* d_disp_l_own, float* d_disp_r_own) {
     set_err(h, "pm_tile_finish: null output");
     return PM_ERR_INVALID_ARG;
   }
-  launch_finalize(h, ps, h->st_disp_l, ps.n_views > 1 ? h->st_disp_r : nullptr, 1);
+  launch_finalize(h, ps, h->st_disp_l, ps.n_views > 1 ? h->st_disp_r : nullptr, 1, h->stream);
   if (int rc = launch_check(h, "finalize")) return rc;
   const size_t ofs = (size_t)(h->tile.own_row0 - h->tile.band_row0) * ps.cols;
   const size_t bytes = sizeof(float) * (size_t)h->tile.own_rows * ps.cols;
