@@ -510,7 +510,7 @@ int seq_events_create(pm_handle* h) {
   }
   std::vector<pm_handle::PipeSlot> slots((size_t)h->max_batch);
   for (auto& sl : slots) {
-    hipEvent_t* evs[] = {&sl.in_done, &sl.head_done, &sl.v_done[0], &sl.v_done[1], &sl.fin_done, &sl.out_done};
+    hipEvent_t* evs[] = {&sl.in_done, &sl.head_done, &sl.v_done[0], &sl.v_done[1], &sl.out_done};
     for (hipEvent_t* e : evs) PM_HIP(h, hipEventCreateWithFlags(e, hipEventDisableTiming));
   }
   h->pipe.swap(slots);
@@ -629,12 +629,12 @@ bool seq_pipelined(const pm_handle* h) {
 }
 
 // One CHUNK of a batch or of a frame sequence: pairs [b, b + c) of the plan.
-//   the HEAD of the chunk, behind the non-null events `ready` (the chunk's inputs are in device memory) and `slot_free`
-//                 (whoever last used these plane slots is done with them): images, gradients, transposes and line
-//                 planes of both views, and the device seeder where a view seeds itself (a chain of latency-bound
-//                 launches, 0.11 ms per view and pair).  A chunk that seeds itself runs its head on s_in -- the stream
-//                 the uploads ran on -- BESIDE the sweeps of the chunk in front instead of between two chunks on the
-//                 view streams; the others keep it at the head of their view streams (see below);
+//   the HEAD of the chunk, behind the non-null events `ready` (the chunk's inputs are in device memory) and `ready2`
+//                 (those of its second frame, in a chunk of two device-resident frames): images, gradients, transposes
+//                 and line planes of both views, and the device seeder where a view seeds itself (a chain of
+//                 latency-bound launches, 0.11 ms per view and pair).  A chunk that seeds itself runs its head on
+//                 s_in -- the stream the uploads ran on -- BESIDE the sweeps of the chunk in front instead of between
+//                 two chunks on the view streams; the others keep it at the head of their view streams (see below);
 //   the handle's stream / view1_stream   the iterations of the first / second view (behind event head_done);
 //   s_out         behind both views (events v_done[0 / 1]): the cross-check / un-mirror into d_disp_l / d_disp_r
 //                 ([c][rows][cols]).
@@ -642,7 +642,7 @@ bool seq_pipelined(const pm_handle* h) {
 // Enqueue only; the caller orders what follows behind s_out.
 int seq_enqueue_chunk(pm_handle* h, int b, int c, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
                       const float* d_seed_l, const float* d_seed_r, float* d_disp_l, float* d_disp_r, hipEvent_t ready,
-                      hipEvent_t slot_free, hipEvent_t v_done[2], hipEvent_t head_done) {
+                      hipEvent_t ready2, hipEvent_t v_done[2], hipEvent_t head_done) {
   if (int rc = view_streams_create(h)) return rc;
   const PlaneSet ps = plane_set(h, rows, cols, 2);
   const PlaneSet pb = plane_set_of_pair(ps, b);
@@ -653,7 +653,7 @@ int seq_enqueue_chunk(pm_handle* h, int b, int c, const uint8_t* d_left, const u
   const bool head_aside = h->need_seed[0] || h->need_seed[1];
   const hipStream_t vs[2] = {h->stream, h->view1_stream};
   if (head_aside) {
-    for (hipEvent_t e : {ready, slot_free})
+    for (hipEvent_t e : {ready, ready2})
       if (int rc = fork_stream(h, e, nullptr, h->s_in)) return rc;
     for (int v = 0; v < 2; ++v) {
       {
@@ -678,7 +678,7 @@ int seq_enqueue_chunk(pm_handle* h, int b, int c, const uint8_t* d_left, const u
     if (int rc = run_views_on(h, pb, 2 * c, nullptr, vs)) return rc;
   } else {
     for (int v = 0; v < 2; ++v)
-      for (hipEvent_t e : {ready, slot_free})
+      for (hipEvent_t e : {ready, ready2})
         if (int rc = fork_stream(h, e, nullptr, vs[v])) return rc;
     const ViewSetup sb{d_left, d_right, d_seed_l, d_seed_r, c};
     if (int rc = run_views_on(h, pb, 2 * c, &sb, vs)) return rc;
@@ -1039,7 +1039,7 @@ void pm_destroy(pm_handle* h) {
     (void)hipEventDestroy(r.stop);
   }
   for (auto& sl : h->pipe) {
-    hipEvent_t evs[] = {sl.in_done, sl.head_done, sl.v_done[0], sl.v_done[1], sl.fin_done, sl.out_done};
+    hipEvent_t evs[] = {sl.in_done, sl.head_done, sl.v_done[0], sl.v_done[1], sl.out_done};
     for (hipEvent_t e : evs)
       if (e) (void)hipEventDestroy(e);
   }

@@ -104,7 +104,6 @@ struct pm_handle {
     hipEvent_t in_done = nullptr;   // s_in: the slot's inputs are in device memory
     hipEvent_t head_done = nullptr; // s_in: images, gradients, line planes and seeds of the chunk that STARTS here are ready
     hipEvent_t v_done[2] = {nullptr, nullptr};  // view stream v: the chunk that STARTS at this slot has run
-    hipEvent_t fin_done = nullptr;  // s_out: cross-check done, the slot's planes and input staging are free again
     hipEvent_t out_done = nullptr;  // s_out: the slot's maps have arrived on the host
     uint64_t tag = 0;
     int rows = 0, cols = 0;
@@ -114,7 +113,7 @@ struct pm_handle {
     const float *d_seed_l = nullptr, *d_seed_r = nullptr;
     float *d_out_l = nullptr, *d_out_r = nullptr;         // where the cross-check writes (staging or caller memory)
     bool device_io = false;         // pm_submit_device: no copies at all
-    hipEvent_t ready_ext = nullptr; // pm_submit_device_after: the caller's event behind the producer of the inputs
+    bool ready_in = false;          // pm_submit_device_after: in_done stands for the caller's "inputs are complete" event
     float *out_l = nullptr, *out_r = nullptr;  // host maps bound at submit (null: handed to pm_collect)
     size_t out_step = 0;
     bool direct_l = false, direct_r = false;   // the download goes straight into the bound (registered) host map
@@ -296,7 +295,7 @@ int pair_chunk();
 bool seq_pipelined(const pm_handle* h);
 int seq_enqueue_chunk(pm_handle* h, int b, int c, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
                       const float* d_seed_l, const float* d_seed_r, float* d_disp_l, float* d_disp_r, hipEvent_t ready,
-                      hipEvent_t slot_free, hipEvent_t v_done[2], hipEvent_t head_done);
+                      hipEvent_t ready2, hipEvent_t v_done[2], hipEvent_t head_done);
 SeedParams seed_params(const pm_params& p);
 int alloc_seed_scratch(pm_handle* h, SeedScratch& sc, hipStream_t stream);
 // SparseInit (or Patchmatch::Initialize(.., 1)) for view `view` of pair `b` straight into its disparity plane

@@ -94,16 +94,18 @@ int pipe_init(pm_handle* h) {
 
 // Frames [b, b + c) of the ring -- uploaded (or device resident) -- become ONE chunk of the sequence: both views on the
 // view streams behind the later frame's upload, cross-check and downloads on s_out.  Handles that cannot run as chunks
-// (plane mode, one view only) run the frame on the handle's stream instead, one frame after the other.
+// (plane mode, one view only) run the frames on the handle's stream instead.
 int enqueue_frames(pm_handle* h, int b, int c) {
   pm_handle::PipeSlot& f0 = h->pipe[(size_t)b];
+  const pm_handle::PipeSlot& fl = h->pipe[(size_t)(b + c - 1)];
   const int rows = f0.rows, cols = f0.cols;
   const size_t px = (size_t)rows * cols;
   const bool lr = h->params.left_right_check != 0;
   // host frames: the later frame's upload (s_in runs in order).  Device-resident frames: the caller's "inputs are
-  // complete" events (pm_submit_device_after), one per frame of the chunk, in front of both views and the head
-  hipEvent_t ready = f0.device_io ? f0.ready_ext : h->pipe[(size_t)(b + c - 1)].in_done;
-  hipEvent_t ready2 = (f0.device_io && c > 1) ? h->pipe[(size_t)(b + c - 1)].ready_ext : nullptr;
+  // complete" events (pm_submit_device_after; the slots' in_done stand for them), one per frame of the chunk, in front
+  // of both views and the head
+  hipEvent_t ready = !f0.device_io ? fl.in_done : f0.ready_in ? f0.in_done : nullptr;
+  hipEvent_t ready2 = (f0.device_io && c > 1 && fl.ready_in) ? fl.in_done : nullptr;
   if (seq_pipelined(h)) {
     if (int rc = seq_enqueue_chunk(h, b, c, f0.d_left, f0.d_right, rows, cols, f0.d_seed_l, f0.d_seed_r, f0.d_out_l,
                                    f0.d_out_r, ready, ready2, f0.v_done, f0.head_done))
@@ -111,20 +113,14 @@ int enqueue_frames(pm_handle* h, int b, int c) {
   } else {
     if (ready) PM_HIP(h, hipStreamWaitEvent(h->stream, ready, 0));
     if (ready2) PM_HIP(h, hipStreamWaitEvent(h->stream, ready2, 0));
-    if (c > 1 && h->params.mode == PM_MODE_PLANES) {
-      // plane mode: the frames of a chunk are neighbours in memory (can_gang) and run as ONE batch -- two lanes on two
-      // streams, each filling the other's launch tails (pm_planes_host.hip::planes_match)
-      if (int rc = match_device_impl(h, c, f0.d_left, f0.d_right, rows, cols, f0.d_seed_l, f0.d_seed_r, f0.d_out_l,
-                                     lr ? f0.d_out_r : nullptr))
-        return rc;
-    } else {
-      for (int i = 0; i < c; ++i) {
-        pm_handle::PipeSlot& f = h->pipe[(size_t)(b + i)];
-        if (int rc = match_device_impl(h, 1, f.d_left, f.d_right, rows, cols, f.d_seed_l, f.d_seed_r, f.d_out_l,
-                                       lr ? f.d_out_r : nullptr))
-          return rc;
-      }
-    }
+    // All frames of the chunk through every launch together (plane mode: two lanes on two streams, each filling the
+    // other's launch tails, pm_planes_host.hip::planes_match).  They are neighbours in memory: a chunk of more than one
+    // frame is either all pairs of pm_match_batch_u8 (ring slots 0 .. n - 1) or a held frame and the partner can_gang
+    // accepted -- and enqueue_or_hold holds a frame only if seq_pipelined(h) or in plane mode without bgr, so a scalar
+    // sequence reaches this branch one frame at a time.
+    if (int rc = match_device_impl(h, c, f0.d_left, f0.d_right, rows, cols, f0.d_seed_l, f0.d_seed_r, f0.d_out_l,
+                                   lr ? f0.d_out_r : nullptr))
+      return rc;
     PM_HIP(h, hipEventRecord(f0.v_done[0], h->stream));
     PM_HIP(h, hipStreamWaitEvent(h->s_out, f0.v_done[0], 0));
   }
@@ -194,29 +190,136 @@ struct SubmitArgs {
   hipEvent_t ready = nullptr;  // device_io: the caller's event behind the producer of the inputs, or null
 };
 
-int submit_impl(pm_handle* h, const SubmitArgs& a, const char* what) {
+// The argument checks of the host-buffer entry points (pm_match_u8, pm_match_batch_u8, the submits), in this order:
+// capture, null pointers (`ptrs`: all given), size, disp_r, pairs in flight (`idle`: the call needs an empty ring), row
+// steps.  The steps (0: tight rows) are set to their values; null: the call takes tight rows only.
+int check_host_call(pm_handle* h, const char* what, bool ptrs, int rows, int cols, int n, const void* out_l,
+                    const void* out_r, bool idle, size_t* image_step, size_t* seed_step, size_t* out_step) {
   if (int rc = refuse_while_capturing(h, what)) return rc;
-  if (!a.left || !a.right) {
-    set_err(h, "%s: null image pointer", what);
+  if (!ptrs) {
+    set_err(h, "%s: null image or output pointer", what);
     return PM_ERR_INVALID_ARG;
   }
-  const int rows = a.rows, cols = a.cols;
-  if (int rc = check_size(h, rows, cols, 1)) return rc;
-  const size_t image_step = a.image_step ? a.image_step : (size_t)cols;
-  const size_t frow = sizeof(float) * (size_t)cols;
-  const size_t seed_step = a.seed_step ? a.seed_step : frow;
-  const size_t out_step = a.out_step ? a.out_step : frow;
-  if (image_step < (size_t)cols || seed_step < frow || out_step < frow) {
-    set_err(h, "%s: a row step is smaller than a row", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  const bool lr = h->params.left_right_check != 0;
-  if (a.device_io && (!a.out_l || (lr && !a.out_r))) {
-    set_err(h, "%s: null output pointer", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (!a.device_io && a.out_l && lr && !a.out_r) {
+  if (int rc = check_size(h, rows, cols, n)) return rc;
+  if (out_l && !out_r && h->params.left_right_check) {
     set_err(h, "%s: disp_r required when left_right_check is set", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (idle && h->pipe_count > 0) {
+    set_err(h, "%s: pairs are in flight (pm_collect them first)", what);
+    return PM_ERR_BUSY;
+  }
+  if (image_step) {
+    const size_t frow = sizeof(float) * (size_t)cols;
+    if (!*image_step) *image_step = (size_t)cols;
+    if (!*seed_step) *seed_step = frow;
+    if (!*out_step) *out_step = frow;
+    if (*image_step < (size_t)cols || *seed_step < frow || *out_step < frow) {
+      set_err(h, "%s: a row step is smaller than a row", what);
+      return PM_ERR_INVALID_ARG;
+    }
+  }
+  return PM_OK;
+}
+
+// Frame `a` into ring slot `slot`, and the slot filled in.  A host frame goes up on s_in into the slot's staging (the
+// steps are checked; a.out_l / a.out_r: the maps bound at submit, or null) and in_done is recorded behind it; zero_l /
+// zero_r: a view without a seed map here starts from zeros -- in a batch that gives that view's map for other pairs.
+// A device-resident frame is read and written where it is.
+int stage_frame(pm_handle* h, int slot, const SubmitArgs& a, bool zero_l, bool zero_r) {
+  pm_handle::PipeSlot& sl = h->pipe[(size_t)slot];
+  const int rows = a.rows, cols = a.cols;
+  const size_t px = (size_t)rows * cols;
+  const size_t frow = sizeof(float) * (size_t)cols;
+  sl.tag = a.tag;
+  sl.rows = rows;
+  sl.cols = cols;
+  sl.device_io = a.device_io;
+  sl.ready_in = a.ready != nullptr;
+  sl.direct_l = sl.direct_r = false;
+  if (a.device_io) {
+    sl.d_left = a.left;
+    sl.d_right = a.right;
+    sl.d_seed_l = a.seed_l;
+    sl.d_seed_r = a.seed_r;
+    sl.d_out_l = a.out_l;
+    sl.d_out_r = a.out_r;
+    sl.out_l = sl.out_r = nullptr;
+    // The caller's "inputs are complete" event is CONSUMED here: s_in waits for it and the slot's own event is recorded
+    // behind it.  A held frame is only enqueued by a later submit / collect / flush -- by then the caller may have
+    // re-recorded or destroyed its event (a torch.cuda.Event dropped after the call); the slot's event is ours.
+    if (a.ready) {
+      PM_HIP(h, hipStreamWaitEvent(h->s_in, a.ready, 0));
+      PM_HIP(h, hipEventRecord(sl.in_done, h->s_in));
+    }
+  } else {
+    // ring slot k keeps its inputs and outputs at offset k * px of the staging arrays: frames in flight share one size
+    uint8_t* dl8 = h->st_left + (size_t)slot * px;
+    uint8_t* dr8 = h->st_right + (size_t)slot * px;
+    float* dsl = h->st_seed_l + (size_t)slot * px;
+    float* dsr = h->st_seed_r + (size_t)slot * px;
+    const PinnedSlot ps = pinned_slot(h, slot, px);
+    if (int rc = upload_plane(h, dl8, a.left, a.image_step, (size_t)cols, rows, ps.l, h->s_in)) return rc;
+    if (int rc = upload_plane(h, dr8, a.right, a.image_step, (size_t)cols, rows, ps.r, h->s_in)) return rc;
+    if (a.seed_l) {
+      if (int rc = upload_plane(h, dsl, a.seed_l, a.seed_step, frow, rows, ps.sl, h->s_in)) return rc;
+    } else if (zero_l) {
+      PM_HIP(h, hipMemsetAsync(dsl, 0, sizeof(float) * px, h->s_in));
+    }
+    if (a.seed_r) {
+      if (int rc = upload_plane(h, dsr, a.seed_r, a.seed_step, frow, rows, ps.sr, h->s_in)) return rc;
+    } else if (zero_r) {
+      PM_HIP(h, hipMemsetAsync(dsr, 0, sizeof(float) * px, h->s_in));
+    }
+    PM_HIP(h, hipEventRecord(sl.in_done, h->s_in));
+    sl.d_left = dl8;
+    sl.d_right = dr8;
+    sl.d_seed_l = a.seed_l || zero_l ? dsl : nullptr;
+    sl.d_seed_r = a.seed_r || zero_r ? dsr : nullptr;
+    sl.d_out_l = h->st_disp_l + (size_t)slot * px;
+    sl.d_out_r = h->st_disp_r + (size_t)slot * px;
+    sl.out_l = a.out_l;
+    sl.out_r = a.out_r;
+  }
+  sl.has_sl = sl.d_seed_l != nullptr;
+  sl.has_sr = sl.d_seed_r != nullptr;
+  sl.out_step = sl.out_l ? a.out_step : 0;
+  sl.state = 1;
+  return PM_OK;
+}
+
+// The end of the frame in ring slot `slot`: waits until its maps have arrived and, unless they were downloaded into
+// place, unpacks them from the slab into out_l / out_r (row step out_step).  The slot is free again either way.
+int finish_frame(pm_handle* h, int slot, float* out_l, float* out_r, size_t out_step) {
+  pm_handle::PipeSlot& f = h->pipe[(size_t)slot];
+  f.state = 0;
+  PM_HIP(h, hipEventSynchronize(f.out_done));
+  if (!f.device_io) {
+    const size_t frow = sizeof(float) * (size_t)f.cols;
+    const PinnedSlot ps = pinned_slot(h, slot, (size_t)f.rows * f.cols);
+    if (!f.direct_l) h->copy_pool->Copy2D(out_l, out_step, ps.dl, frow, frow, f.rows);
+    if (h->params.left_right_check && !f.direct_r) h->copy_pool->Copy2D(out_r, out_step, ps.dr, frow, frow, f.rows);
+  }
+  return PM_OK;
+}
+
+// An enqueue that failed midway may have left launches of the call on the streams.  Nothing of them may outlive the
+// call: the caller is told "not done" and is free to reuse its buffers.  Every ring slot outside the frames in flight
+// is free again, and with none in flight, none was enqueued last.
+void drain_after_failure(pm_handle* h) {
+  for (hipStream_t q : {h->stream, h->view1_stream, h->s_in, h->s_out})
+    if (q) (void)hipStreamSynchronize(q);
+  (void)hipGetLastError();
+  for (int i = h->pipe_count; i < h->max_batch; ++i) h->pipe[(size_t)((h->pipe_head + i) % h->max_batch)].state = 0;
+  if (h->pipe_count == 0) h->seq_last = -1;
+}
+
+int submit_impl(pm_handle* h, SubmitArgs a, const char* what) {
+  if (int rc = check_host_call(h, what, a.left && a.right, a.rows, a.cols, 1, a.out_l, a.out_r, false, &a.image_step,
+                               &a.seed_step, &a.out_step))
+    return rc;
+  if (a.device_io && !a.out_l) {
+    set_err(h, "%s: null output pointer", what);
     return PM_ERR_INVALID_ARG;
   }
   PM_HIP(h, hipSetDevice(h->device));
@@ -227,66 +330,16 @@ int submit_impl(pm_handle* h, const SubmitArgs& a, const char* what) {
   }
   if (h->pipe_count > 0) {
     const pm_handle::PipeSlot& first = h->pipe[(size_t)h->pipe_head];
-    if (first.rows != rows || first.cols != cols) {  // the frames in flight share the noise table and the slot layout
+    if (first.rows != a.rows || first.cols != a.cols) {  // the frames in flight share the noise table and the slot layout
       set_err(h, "%s: image size changed with pairs in flight; collect them first", what);
       return PM_ERR_BUSY;
     }
   } else if (h->params.mode == PM_MODE_SCALAR) {
-    if (int rc = ensure_noise(h, rows, cols)) return rc;
+    if (int rc = ensure_noise(h, a.rows, a.cols)) return rc;
   }
   const int slot = (h->pipe_head + h->pipe_count) % h->max_batch;
+  if (int rc = stage_frame(h, slot, a, false, false)) return rc;
   pm_handle::PipeSlot& sl = h->pipe[(size_t)slot];
-  const size_t px = (size_t)rows * cols;
-  sl.tag = a.tag;
-  sl.rows = rows;
-  sl.cols = cols;
-  sl.has_sl = a.seed_l != nullptr;
-  sl.has_sr = a.seed_r != nullptr;
-  sl.device_io = a.device_io;
-  sl.direct_l = sl.direct_r = false;
-  if (a.device_io) {
-    sl.d_left = a.left;
-    sl.d_right = a.right;
-    sl.d_seed_l = a.seed_l;
-    sl.d_seed_r = a.seed_r;
-    sl.d_out_l = a.out_l;
-    sl.d_out_r = a.out_r;
-    sl.out_l = sl.out_r = nullptr;
-    sl.out_step = 0;
-    // The caller's "inputs are complete" event is CONSUMED here: s_in waits for it and the slot's own event is recorded
-    // behind it.  A held frame is only enqueued by a later submit / collect / flush -- by then the caller may have
-    // re-recorded or destroyed its event (a torch.cuda.Event dropped after the call); the slot's event is ours.
-    sl.ready_ext = nullptr;
-    if (a.ready) {
-      PM_HIP(h, hipStreamWaitEvent(h->s_in, a.ready, 0));
-      PM_HIP(h, hipEventRecord(sl.in_done, h->s_in));
-      sl.ready_ext = sl.in_done;
-    }
-  } else {
-    // ring slot k keeps its inputs and outputs at offset k * px of the staging arrays: frames in flight share one size
-    uint8_t* dl8 = h->st_left + (size_t)slot * px;
-    uint8_t* dr8 = h->st_right + (size_t)slot * px;
-    float* dsl = h->st_seed_l + (size_t)slot * px;
-    float* dsr = h->st_seed_r + (size_t)slot * px;
-    const PinnedSlot ps = pinned_slot(h, slot, px);
-    if (int rc = upload_plane(h, dl8, a.left, image_step, (size_t)cols, rows, ps.l, h->s_in)) return rc;
-    if (int rc = upload_plane(h, dr8, a.right, image_step, (size_t)cols, rows, ps.r, h->s_in)) return rc;
-    if (a.seed_l)
-      if (int rc = upload_plane(h, dsl, a.seed_l, seed_step, frow, rows, ps.sl, h->s_in)) return rc;
-    if (a.seed_r)
-      if (int rc = upload_plane(h, dsr, a.seed_r, seed_step, frow, rows, ps.sr, h->s_in)) return rc;
-    PM_HIP(h, hipEventRecord(sl.in_done, h->s_in));
-    sl.d_left = dl8;
-    sl.d_right = dr8;
-    sl.d_seed_l = a.seed_l ? dsl : nullptr;
-    sl.d_seed_r = a.seed_r ? dsr : nullptr;
-    sl.d_out_l = h->st_disp_l + (size_t)slot * px;
-    sl.d_out_r = h->st_disp_r + (size_t)slot * px;
-    sl.out_l = a.out_l;
-    sl.out_r = a.out_r;
-    sl.out_step = a.out_l ? out_step : 0;
-  }
-  sl.state = 1;
   ++h->pipe_count;
   // Chunks: a frame that is being held takes this one as its partner if the two are neighbours in memory, and goes alone
   // otherwise.  This frame is held in turn while the device is busy with earlier chunks anyway and a neighbour slot
@@ -302,19 +355,11 @@ int submit_impl(pm_handle* h, const SubmitArgs& a, const char* what) {
     rc = enqueue_or_hold(h, slot);
   }
   if (rc != PM_OK) {
-    // An enqueue that failed midway may have left launches of this frame (or of the partner it was ganged with) on the
-    // streams.  Nothing of them may outlive this call: the caller is told "not submitted" and is free to reuse its
-    // buffers.  After the wait, a partner that is still marked as held is simply enqueued again by the next submit /
+    // The frame leaves the ring again, so that the caller's count of frames in flight (an error return = nothing
+    // submitted) stays right.  A partner that is still marked as held is simply enqueued again by the next submit /
     // collect -- a Match() is a pure function of its inputs, a second run rewrites the same maps.
-    for (hipStream_t q : {h->stream, h->view1_stream, h->s_in, h->s_out})
-      if (q) (void)hipStreamSynchronize(q);
-    (void)hipGetLastError();
-    if (sl.state == 1) {
-      // the frame leaves the ring again, so that the caller's count of frames in flight (an error return = nothing
-      // submitted) stays right
-      sl.state = 0;
-      --h->pipe_count;
-    }
+    if (sl.state == 1) --h->pipe_count;
+    drain_after_failure(h);
   }
   return rc;
 }
@@ -378,21 +423,10 @@ int pm_match_batch_u8(pm_handle* h, int n, const uint8_t* const* left, const uin
                       int cols, const float* const* seed_l, const float* const* seed_r, float* const* disp_l,
                       float* const* disp_r) {
   if (!h) return PM_ERR_INVALID_ARG;
-  if (int rc = refuse_while_capturing(h, "pm_match_batch_u8")) return rc;
-  if (!left || !right || !disp_l) {
-    set_err(h, "pm_match_batch_u8: null pointer array");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (int rc = check_size(h, rows, cols, n)) return rc;
+  if (int rc = check_host_call(h, "pm_match_batch_u8", left && right && disp_l, rows, cols, n, disp_l, disp_r, true,
+                               nullptr, nullptr, nullptr))
+    return rc;
   const bool lr = h->params.left_right_check != 0;
-  if (lr && !disp_r) {
-    set_err(h, "pm_match_batch_u8: disp_r required when left_right_check is set");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (h->pipe_count > 0) {
-    set_err(h, "pm_match_batch_u8: pairs are in flight (pm_collect them first)");
-    return PM_ERR_BUSY;
-  }
   int nl = 0, nr = 0;
   for (int i = 0; i < n; ++i) {
     if (!left[i] || !right[i] || !disp_l[i] || (lr && !disp_r[i])) {
@@ -412,87 +446,32 @@ int pm_match_batch_u8(pm_handle* h, int n, const uint8_t* const* left, const uin
   if (int rc = pipe_init(h)) return rc;
   if (h->params.mode == PM_MODE_SCALAR)
     if (int rc = ensure_noise(h, rows, cols)) return rc;
-  const size_t px = (size_t)rows * cols;
   const size_t frow = sizeof(float) * (size_t)cols;
-  const bool any_sl = nl > 0, any_sr = nr > 0;
-  const bool chunks = seq_pipelined(h);
-  const int chunk = chunks ? pair_chunk() : n;
+  // handles that cannot run as chunks (plane mode, one view only) take all pairs as one
+  const int chunk = seq_pipelined(h) ? pair_chunk() : n;
   h->pipe_head = 0;
-  for (int b = 0; b < n; b += chunk) {
+  int rc = PM_OK;
+  for (int b = 0; b < n && rc == PM_OK; b += chunk) {
     const int c = n - b < chunk ? n - b : chunk;
-    for (int i = b; i < b + c; ++i) {
-      pm_handle::PipeSlot& sl = h->pipe[(size_t)i];
-      const PinnedSlot ps = pinned_slot(h, i, px);
-      uint8_t* dl8 = h->st_left + (size_t)i * px;
-      uint8_t* dr8 = h->st_right + (size_t)i * px;
-      float* dsl = h->st_seed_l + (size_t)i * px;
-      float* dsr = h->st_seed_r + (size_t)i * px;
-      if (int rc = upload_plane(h, dl8, left[i], (size_t)cols, (size_t)cols, rows, ps.l, h->s_in)) return rc;
-      if (int rc = upload_plane(h, dr8, right[i], (size_t)cols, (size_t)cols, rows, ps.r, h->s_in)) return rc;
+    for (int i = b; i < b + c && rc == PM_OK; ++i) {
+      const SubmitArgs a{left[i], right[i], rows, cols, (size_t)cols, seed_l ? seed_l[i] : nullptr,
+                         seed_r ? seed_r[i] : nullptr, frow, disp_l[i], lr ? disp_r[i] : nullptr, frow, 0, false};
       // a view whose maps were given for some pairs only (allowed without sparse_init): the others start from zeros
-      if (seed_l && seed_l[i]) {
-        if (int rc = upload_plane(h, dsl, seed_l[i], frow, frow, rows, ps.sl, h->s_in)) return rc;
-      } else if (any_sl) {
-        PM_HIP(h, hipMemsetAsync(dsl, 0, sizeof(float) * px, h->s_in));
-      }
-      if (seed_r && seed_r[i]) {
-        if (int rc = upload_plane(h, dsr, seed_r[i], frow, frow, rows, ps.sr, h->s_in)) return rc;
-      } else if (any_sr) {
-        PM_HIP(h, hipMemsetAsync(dsr, 0, sizeof(float) * px, h->s_in));
-      }
-      PM_HIP(h, hipEventRecord(sl.in_done, h->s_in));
-      sl.tag = 0;
-      sl.rows = rows;
-      sl.cols = cols;
-      sl.has_sl = any_sl;
-      sl.has_sr = any_sr;
-      sl.device_io = false;
-      sl.d_left = dl8;
-      sl.d_right = dr8;
-      sl.d_seed_l = any_sl ? dsl : nullptr;
-      sl.d_seed_r = any_sr ? dsr : nullptr;
-      sl.d_out_l = h->st_disp_l + (size_t)i * px;
-      sl.d_out_r = h->st_disp_r + (size_t)i * px;
-      sl.out_l = disp_l[i];
-      sl.out_r = lr ? disp_r[i] : nullptr;
-      sl.out_step = frow;
-      sl.state = 1;
+      rc = stage_frame(h, i, a, nl > 0, nr > 0);
     }
-    if (chunks) {
-      if (int rc = enqueue_frames(h, b, c)) return rc;
-    } else {
-      // all pairs through every launch together on the handle's stream (plane mode, single view)
-      PM_HIP(h, hipStreamWaitEvent(h->stream, h->pipe[(size_t)(n - 1)].in_done, 0));
-      if (int rc = match_device_impl(h, n, h->st_left, h->st_right, rows, cols, any_sl ? h->st_seed_l : nullptr,
-                                     any_sr ? h->st_seed_r : nullptr, h->st_disp_l, lr ? h->st_disp_r : nullptr))
-        return rc;
-      PM_HIP(h, hipEventRecord(h->pipe[0].v_done[0], h->stream));
-      PM_HIP(h, hipStreamWaitEvent(h->s_out, h->pipe[0].v_done[0], 0));
-      for (int i = 0; i < n; ++i) {
-        pm_handle::PipeSlot& f = h->pipe[(size_t)i];
-        const PinnedSlot ps = pinned_slot(h, i, px);
-        if (int rc = download_plane(h, f.out_l, frow, f.d_out_l, frow, rows, ps.dl, h->s_out, &f.direct_l)) return rc;
-        if (lr)
-          if (int rc = download_plane(h, f.out_r, frow, f.d_out_r, frow, rows, ps.dr, h->s_out, &f.direct_r)) return rc;
-        PM_HIP(h, hipEventRecord(f.out_done, h->s_out));
-      }
-    }
+    if (rc == PM_OK) rc = enqueue_frames(h, b, c);
   }
-  int rc_all = PM_OK;
-  for (int i = 0; i < n; ++i) {
-    pm_handle::PipeSlot& f = h->pipe[(size_t)i];
-    f.state = 0;
-    if (hipEventSynchronize(f.out_done) != hipSuccess) {
+  if (rc != PM_OK) {
+    drain_after_failure(h);
+    return rc;
+  }
+  for (int i = 0; i < n; ++i)
+    if (finish_frame(h, i, disp_l[i], lr ? disp_r[i] : nullptr, frow) != PM_OK) {
       set_err(h, "pm_match_batch_u8: waiting for pair %d failed", i);
-      rc_all = PM_ERR_HIP;
-      continue;
+      rc = PM_ERR_HIP;
     }
-    const PinnedSlot ps = pinned_slot(h, i, px);
-    if (!f.direct_l) h->copy_pool->Copy2D(disp_l[i], frow, ps.dl, frow, frow, rows);
-    if (lr && !f.direct_r) h->copy_pool->Copy2D(disp_r[i], frow, ps.dr, frow, frow, rows);
-  }
   h->seq_last = -1;
-  return rc_all;
+  return rc;
 }
 
 #ifdef PM_HOST_PHASES  // analysis builds: where the HOST spends a pm_match_u8 call (stderr, every 25th call)
@@ -536,29 +515,11 @@ int pm_match_u8(pm_handle* h, const uint8_t* left, const uint8_t* right, int row
                 size_t disp_step) {
   if (!h) return PM_ERR_INVALID_ARG;
   HP(begin());
-  if (int rc = refuse_while_capturing(h, "pm_match_u8")) return rc;
-  if (!left || !right || !disp_l) {
-    set_err(h, "pm_match_u8: null image or output pointer");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (int rc = check_size(h, rows, cols, 1)) return rc;
+  if (int rc = check_host_call(h, "pm_match_u8", left && right && disp_l, rows, cols, 1, disp_l, disp_r, true,
+                               &image_step, &seed_step, &disp_step))
+    return rc;
   const bool lr = h->params.left_right_check != 0;
-  if (lr && !disp_r) {
-    set_err(h, "pm_match_u8: disp_r required when left_right_check is set");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (h->pipe_count > 0) {
-    set_err(h, "pm_match_u8: pairs are in flight (pm_collect them first)");
-    return PM_ERR_BUSY;
-  }
   const size_t frow = sizeof(float) * (size_t)cols;
-  if (image_step == 0) image_step = (size_t)cols;
-  if (seed_step == 0) seed_step = frow;
-  if (disp_step == 0) disp_step = frow;
-  if (image_step < (size_t)cols || seed_step < frow || disp_step < frow) {
-    set_err(h, "pm_match_u8: a row step is smaller than a row");
-    return PM_ERR_INVALID_ARG;
-  }
   PM_HIP(h, hipSetDevice(h->device));
   if (int rc = ensure_noise(h, rows, cols)) return rc;
   const size_t px = (size_t)rows * cols;
@@ -678,8 +639,7 @@ int pm_collect(pm_handle* h, float* disp_l, float* disp_r, size_t disp_step, uin
   }
   const bool lr = h->params.left_right_check != 0;
   pm_handle::PipeSlot& sl = h->pipe[(size_t)h->pipe_head];
-  const int rows = sl.rows, cols = sl.cols;
-  const size_t frow = sizeof(float) * (size_t)cols;
+  const size_t frow = sizeof(float) * (size_t)sl.cols;
   // where the maps go: the buffers bound at submit, else the ones given here (a device-resident frame has neither)
   float* out_l = sl.out_l ? sl.out_l : disp_l;
   float* out_r = sl.out_l ? sl.out_r : disp_r;
@@ -710,13 +670,8 @@ int pm_collect(pm_handle* h, float* disp_l, float* disp_r, size_t disp_step, uin
       if (int rc = enqueue_frames(h, held, 1)) return rc;
     if (pass == 0) PM_HIP(h, hipEventSynchronize(sl.out_done));
   }
-  if (!sl.device_io) {
-    const PinnedSlot ps = pinned_slot(h, h->pipe_head, (size_t)rows * cols);
-    if (!sl.direct_l) h->copy_pool->Copy2D(out_l, out_step, ps.dl, frow, frow, rows);
-    if (lr && !sl.direct_r) h->copy_pool->Copy2D(out_r, out_step, ps.dr, frow, frow, rows);
-  }
+  if (int rc = finish_frame(h, h->pipe_head, out_l, out_r, out_step)) return rc;  // (the maps are there: no wait)
   if (tag) *tag = sl.tag;
-  sl.state = 0;
   h->pipe_head = (h->pipe_head + 1) % h->max_batch;
   --h->pipe_count;
   if (h->pipe_count == 0) h->seq_last = -1;

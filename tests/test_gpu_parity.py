@@ -257,6 +257,30 @@ def test_batch_equals_singles(pm, oracle, synth, sem):
         assert_same(drs[i], er, f"pair {i} right")
 
 
+def test_host_batch_without_cross_check_and_with_some_seeds_missing(pm, synth):
+    """pm_match_batch_u8 off the sequence-chunk path: a scalar batch of 3 with left_right_check = 0 equals three single
+    matches bit for bit; and without sparse_init, a batch in which only some pairs give seed_l equals single matches
+    whose missing seed maps are zeros (with and without the cross-check)."""
+    rows, cols = 40, 70
+    pairs = [small_pair(synth, 70 + i, rows, cols, n_points=20, dilate_factor=2) for i in range(3)]
+    L, R, SL, SR = ([p[k] for p in pairs] for k in range(4))
+    with mk(pm, 0, patch=5, iters=2, lr=0, rows=rows, cols=cols, batch=3) as e:
+        dls, drs = e.match_batch(L, R, SL, SR)
+        assert drs is None
+        for i in range(3):
+            assert_same(dls[i], e.match(L[i], R[i], SL[i], SR[i])[0], f"left_right_check = 0, pair {i}")
+    some = [SL[0], None, SL[2]]
+    zeros = np.zeros((rows, cols), np.float32)
+    for sem, lr in ((1, 1), (0, 0)):
+        with mk(pm, sem, patch=3, iters=2, lr=lr, rows=rows, cols=cols, batch=3) as e:
+            dls, drs = e.match_batch(L, R, some, SR)
+            for i in range(3):
+                dl, dr = e.match(L[i], R[i], zeros if some[i] is None else some[i], SR[i])
+                assert_same(dls[i], dl, f"sem {sem}, lr {lr}: some seed_l missing, pair {i} left")
+                if lr:
+                    assert_same(drs[i], dr, f"sem {sem}, lr {lr}: some seed_l missing, pair {i} right")
+
+
 @pytest.mark.parametrize("sem,patch", [(0, 11), (0, 3), (1, 3)])
 def test_batch_pipelines_on_lanes_equal_singles(pm, oracle, synth, sem, patch):
     """A batch of more than two pairs runs as pipelines of two pairs that take two lanes of view streams in rotation
