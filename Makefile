@@ -36,6 +36,11 @@ $(LIB): $(OBJS)
 oracle:
 	$(MAKE) -C oracle
 
+# The reference's own CPU PatchMatch, compiled from the reference tree (REF=...) against the stand-in headers of
+# oracle/ref/ into oracle/_ref/ (never committed).  Not part of `all`: it needs the reference tree.
+ref:
+	$(MAKE) -C oracle/ref $(if $(REF),REF=$(REF))
+
 # The tuning build: the same sources with -DPM_TUNING, in which the A/B knobs of pm_tune.hpp are read from the
 # environment.  Not part of `all`; tools/ load it through PM_LIB.  The shipped library reads no environment variable.
 # TUNE_DEFS: extra -D switches of an experiment (e.g. -DPL_EARLY_EXIT=1); `rm -rf $(PKG)/build/tuning` between experiments
@@ -53,4 +58,4 @@ tuning: $(TLIB)
 
 clean:
 	rm -rf $(OBJDIR) $(LIB) $(TLIB); $(MAKE) -C oracle clean
-.PHONY: all oracle clean tuning
+.PHONY: all oracle ref clean tuning

@@ -307,7 +307,11 @@ int pm_unit_noise(pm_handle* h, int rows, int cols, float* noise);
 int pm_add_noise(pm_handle* h, float* disp, int rows, int cols, float amount);
 /* Patchmatch::Propagate (patchmatch.cpp:248-311) for PM_SEM_CPU, or the PropagateRow(+1),
  * PropagateCol(+1), PropagateRow(-1), PropagateCol(-1) sequence (patchmatch_gpu.cu:397-403) for
- * PM_SEM_GPU.  pass_mask bit k enables the k-th of those four sweeps.  disp is updated in place. */
+ * PM_SEM_GPU.  pass_mask bit k enables the k-th of those four sweeps.  disp is updated in place.
+ * PM_SEM_CPU: every value of disp must be >= 0 (not NaN), else PM_ERR_INVALID_ARG and disp is left untouched.  The
+ * reference clamps only a pixel's own value; a neighbour's negative one it tries as it stands, with the target window
+ * beyond the right border (getRectSubPix's border branch), which the kernels do not implement.  Every map that
+ * Patchmatch::AddNoise / pm_add_noise has produced is >= 0, so the reference's own call sequences never get there. */
 int pm_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols,
                  float* disp, int patch_h, int patch_w, int pass_mask);
 /* Patchmatch::RemoveBackground (patchmatch.cpp:314-360) / MaskBackground (patchmatch_gpu.cu:233-270). */

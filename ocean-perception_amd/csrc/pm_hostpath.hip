@@ -773,8 +773,20 @@ int pm_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, int ro
     set_err(h, "pm_propagate: null pointer");
     return PM_ERR_INVALID_ARG;
   }
-  if (h->params.semantics == PM_SEM_CPU)
+  if (h->params.semantics == PM_SEM_CPU) {
     if (int rc = check_patch(h, patch_w, patch_h)) return rc;
+    // The sweeps evaluate a neighbour's disparity as it stands (patchmatch.cpp:177,186: only d0 is clamped), and
+    // cpu_cost_lane holds for 0 <= d only: a negative candidate puts the target window beyond the right border, where
+    // the reference takes getRectSubPix's border branch and the kernels would index past the row.  Inside Match every
+    // map has been through AddNoise's max(disp, 0); here the caller's map arrives as it is, so it is checked.
+    if (rows > 0 && cols > 0)
+      for (size_t i = 0, n = (size_t)rows * (size_t)cols; i < n; ++i)
+        if (!(disp[i] >= 0.f)) {
+          set_err(h, "pm_propagate: disp[%zu] = %g; PM_SEM_CPU takes maps with every value >= 0 (pm_add_noise clamps)", i,
+                  (double)disp[i]);
+          return PM_ERR_INVALID_ARG;
+        }
+  }
   PlaneSet ps;
   if (int rc = stage_prep(h, left, right, rows, cols, &ps)) return rc;
   if (int rc = stage_disp_in(h, ps, disp)) return rc;

@@ -417,8 +417,8 @@ float pmo_cpu_cost_literal(const pmo_images* im, int pw, int ph, float x, float 
 /* Same value without materialising patches.  On the path the window centre has an integer y
  * (b = 0) and 0 <= x-d-(pw-1)/2 <= cols-pw, so every sample is the two-tap horizontal lerp of
  * getRectSubPix; its border branch is reached only with a = 0 (last interior column / row) where
- * it degenerates to a plain copy.  Valid for pw/2 <= x <= cols-pw/2-1, ph/2 <= y <= rows-ph/2-1,
- * 0 <= d <= x - pw/2. */
+ * it degenerates to a plain copy.  The two-tap form holds for pw/2 <= x <= cols-pw/2-1, ph/2 <= y <= rows-ph/2-1,
+ * 0 <= d <= x - pw/2; any other d is handed to the literal form. */
 float pmo_cpu_cost_direct(const pmo_images* im, int pw, int ph, int x, int y, float d,
                           const pmo_functor* f) {
   const int cols = im->cols;
@@ -426,6 +426,12 @@ float pmo_cpu_cost_direct(const pmo_images* im, int pw, int ph, int x, int y, fl
   cx -= (float)(pw - 1) * 0.5f;
   const int ipx = cv_floor_f(cx);
   const float a = cx - (float)ipx;
+  /* Outside that domain the target window leaves the image and getRectSubPix takes its border branch with a != 0
+   * (one column, weight 1 - b).  Propagate does reach it: only d0 is clamped, a neighbour's NEGATIVE disparity is a
+   * candidate as it stands (patchmatch.cpp:177,186) and puts the window beyond the right border.  The compiled
+   * reference (tests/test_reference_build.py) showed the two-tap form to differ there -- and to read past the row. */
+  if (ipx < 0 || ipx + pw > cols || (ipx + pw == cols && a != 0.f))
+    return pmo_cpu_cost_literal(im, pw, ph, (float)x, (float)y, d, f);
   const float ia = 1.f - a;
   const int a11 = cv_round_f(ia * 65536.f), a12 = cv_round_f(a * 65536.f);
   const int x0 = x - pw / 2, y0 = y - ph / 2;

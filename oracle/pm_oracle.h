@@ -6,16 +6,13 @@
  * `cpu_baseline` leg of bench.py, and there only as the checker or the reported
  * CPU baseline.  The product path (ocean-perception_amd/, include/) never calls it.
  *
- * PARITY UNPINNED.  The reference's tests for this path hold no assertions and no
- * golden vectors (test/stereo_matching/patchmatch_test.cpp, patchmatch_gpu_test.cpp:
- * imshow demos only), the reference cannot be compiled here (needs OpenCV 3.4.0 EXACT,
- * glog, Eigen, Boost, CUDA -- none present), and every arithmetic primitive of the path
- * lives in OpenCV 3.4.0 (CMakeLists.txt:28), which is not vendored.  This file restates
- * the reference's own code line by line and OpenCV 3.4's published algorithms
- * (getRectSubPix, Sobel, dilate, RNG, mean, saturate_cast) as documented per function;
- * it is pinned only by hand-computed known-answer tests and by an independent numpy
- * restatement (tests/pyref.py).  Floating point is evaluated without FMA contraction
- * (-ffp-contract=off), one IEEE-754 binary32 rounding per operation.
+ * PARITY.  The reference's tests for this path hold no assertions and no golden vectors.  Since oracle/ref/ exists the
+ * reference's own CPU PatchMatch (stereo_matching/patchmatch.cpp and the functor / ComputeGradient of its
+ * patchmatch_test.cpp) is compiled, unchanged, against a stand-in for OpenCV 3.4 / glog into oracle/_ref/, and
+ * PMO_SEM_CPU below is compared with it bit for bit (tests/test_reference_build.py, tolerance 0).  What stays restated
+ * and unpinned is OpenCV itself (getRectSubPix, Sobel, dilate, RNG, mean, saturate_cast: here and, written apart, in the
+ * stand-in), the seeder, and PMO_SEM_GPU.  Floating point is evaluated without FMA contraction (-ffp-contract=off), one
+ * IEEE-754 binary32 rounding per operation.
  *
  * Two semantics are restated:
  *   PMO_SEM_CPU  src/vehicle/stereo_matching/patchmatch.cpp + the cost functor and

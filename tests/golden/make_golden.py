@@ -4,6 +4,8 @@
     python tests/golden/make_golden.py --caddy    # also the CADDY 640x480 fixture (needs the
                                                   # reference tree's test/resources, this container only)
     python tests/golden/make_golden.py --farmsim  # also the fsl1 / fsr1 pair of the reference's two PatchMatch tests
+    python tests/golden/make_golden.py --reference  # ONLY the fixtures recorded from the compiled reference
+                                                  # (oracle/_ref/libpm_ref.so, built by `make ref`): ref_*.npz
 
 Fixtures are data: inputs + expected outputs.  The CADDY fixture holds the two JPEGs of the
 reference's test/resources (caddy_32_{left,right}.jpg, used by its sgbm/feature tests and named by
@@ -159,7 +161,41 @@ def farmsim():
           ((seeds > 0).mean(), (da > 0).mean(), (dbl > 0).mean()))
 
 
+def reference():
+    """Fixtures that the reference's OWN compiled code wrote (oracle/_ref/libpm_ref.so: its patchmatch.cpp and the functor
+    and ComputeGradient of its patchmatch_test.cpp, g++ -O3 -ffp-contract=off) -- the first ones here that this build's
+    oracle did not generate.  The OpenCV primitives underneath are the stand-in's (oracle/ref/), not OpenCV 3.4.0's."""
+    import ref_lib
+    import ref_inputs as T
+    R = ref_lib.load()
+    note = ("outputs of the reference's compiled Patchmatch::Propagate / RemoveBackground / AddNoise, L1GradientCostFunction "
+            "and ComputeGradient; the OpenCV primitives underneath are this project's stand-in (oracle/ref/), not OpenCV 3.4.0")
+    rows, cols = 61, 99
+    l, r = T.shifted_pair(61099, rows, cols)
+    # one seed field that holds every kind of (b): truth plus noise, values above x, the >= edge for both windows, fractions
+    rng = np.random.default_rng(61099)
+    pick = rng.integers(0, 5, (rows, cols))
+    seed = T.field("truth_noise", 1, rows, cols, 5)
+    for k, (kind, pw) in enumerate((("above_x", 5), ("edge", 5), ("edge", 3), ("fractional", 5)), start=1):
+        seed = np.where(pick == k, T.field(kind, k, rows, cols, pw), seed)
+    seed = seed.astype(np.float32)
+    assert (seed >= 0).all()   # the engine's domain (pm_propagate refuses negative values)
+    windows = [(5, 5), (7, 3)]
+    gl, gr = R.compute_gradient(l), R.compute_gradient(r)
+    assert gl.max() > 255
+    out = [R.propagate(l, r, seed, ph, pw) for ph, pw in windows]
+    out_bg = [R.remove_background(l, r, o, ph, pw, 1.5) for o, (ph, pw) in zip(out, windows)]
+    save("ref_propagate_61x99", left=l, right=r, gl=gl, gr=gr, seed=seed, windows=np.array(windows), out=np.array(out),
+         out_bg=np.array(out_bg), note=note)
+    fl, fr, fseed = T.farmsim_inputs(O)
+    save("ref_recipe_farmsim", seed=fseed, disp=R.recipe(fl, fr, fseed), note=note +
+         "; images: farmsim_fs1_376x240.npz; seed: this build's Patchmatch::Initialize restatement (the seeder is not pinned)")
+
+
 if __name__ == "__main__":
+    if "--reference" in sys.argv:
+        reference()
+        sys.exit(0)
     if "--farmsim-only" in sys.argv:
         farmsim()
         sys.exit(0)
