@@ -8,9 +8,11 @@
  *     (with SetMaxRangeWhereZero, :255-266)
  *   - ComputeIntensity                     src/vehicle/vision_core/image_util.cpp:97-102
  *   - imaging::FindDarkFast                src/vehicle/imaging/backscatter.cpp:41-78
- * i.e. the per-pixel stages of imaging::EnhanceUnderwater (src/vehicle/imaging/enhance.cpp:22-85).
- * The Levenberg-Marquardt parameter fits (EstimateBackscatter, EstimateBeta) and the guided filter
- * stay with the caller: they work on <= a few hundred sampled pixels and hand over B, beta_B, beta_D.
+ *   - imaging::EstimateIlluminantRangeGuided src/vehicle/imaging/illuminant.cpp:24-34
+ *     (fastGuidedFilter with a one-channel guide, src/vehicle/imaging/fast_guided_filter.cpp)
+ * i.e. every whole-image stage of imaging::EnhanceUnderwater (src/vehicle/imaging/enhance.cpp:22-85).
+ * The Levenberg-Marquardt parameter fits (EstimateBackscatter, EstimateBeta) stay with the caller: they
+ * work on <= a few hundred sampled pixels, which pm_gather_pixels fetches, and hand over B, beta_B, beta_D.
  *
  * Conventions: all image pointers are DEVICE memory, tightly packed; Image3f is interleaved BGR
  * float ([rows][cols][3]) like cv::Mat_<cv::Vec3f>; Image1f is [rows][cols] float.  Every function
@@ -58,6 +60,32 @@ int pm_compute_intensity(pm_handle* h, const float* d_bgr, int rows, int cols, f
  * returns the threshold through *threshold.  Synchronises the stream (the counts steer the search). */
 int pm_find_dark(pm_handle* h, const float* d_intensity, const float* d_range, int rows, int cols,
                  float percentile, uint8_t* d_mask, float* threshold);
+
+/* ---- the range-guided illuminant (EnhanceUnderwater's step between RemoveBackscatter and CorrectAttenuation) -----
+ * Unlike the exp-based stages above these are held to their CPU definition (tests/guided_ref.py) BIT FOR BIT: every
+ * operation is one binary32 rounding in the reference's order; the box means accumulate in binary64 like cv::blur on
+ * float images, in a fixed order (the k taps of a row left to right, then the k row sums top to bottom).  Scratch for
+ * the coarse image (rows / s x cols / s) is allocated on first use and reused.
+ *
+ * fastGuidedFilter(I = guide, p = src, r, eps, s) of fast_guided_filter.cpp:207-233 with a ONE-channel float guide
+ * (FastGuidedFilterMono, :90-123); src has 1..4 interleaved float channels, each filtered on its own (:74-84).
+ * dst may equal src.  scale multiplies the result (1.0f = the filter itself).  rows / s >= 1, cols / s >= 1, s >= 1,
+ * r >= 0, eps finite and >= 0.  The three-channel (colour) guide of FastGuidedFilterColor (:126-204) is NOT provided:
+ * nothing in the reference calls it. */
+int pm_fast_guided_filter(pm_handle* h, const float* d_guide, const float* d_src, int rows, int cols, int channels,
+                          int r, double eps, int s, float scale, float* d_dst);
+
+/* EstimateIlluminantRangeGuided (illuminant.cpp:24-34): 2.0f * fastGuidedFilter(range, bgr, r, eps, s). */
+int pm_estimate_illuminant_range_guided(pm_handle* h, const float* d_bgr, const float* d_range, int rows, int cols,
+                                        int r, double eps, int s, float* d_illuminant);
+
+/* n pixels (x, y) of a device image with 1..4 float channels -> host_out[n][channels]: the samples the caller's
+ * fits read (EstimateBeta: range and illuminant at <= num_px grid points, attenuation.cpp:43-69), without the image
+ * crossing to the host.  d_xy is a device array of n (x, y) pairs, or xy a host array (exactly one of them non-NULL).
+ * A coordinate outside the image is PM_ERR_INVALID_ARG (nothing is clamped; host_out is left untouched).  Returns
+ * after the values have arrived (synchronises the stream). */
+int pm_gather_pixels(pm_handle* h, const float* d_img, int rows, int cols, int channels, const int32_t* d_xy,
+                     const int32_t* xy, int n, float* host_out);
 
 /* ---- range-free enhancement in FRONT of stereo ---------------------------
  * The "stereo-ready" chain of test/imaging/enhance_test.cpp:69-73 and test/stereo_matching/sgbm_test.cpp:66-84:

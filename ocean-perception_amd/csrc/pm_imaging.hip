@@ -7,10 +7,12 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <new>
 #include <vector>
 
 #include "pm_enhance.hpp"
+#include "pm_guided.hpp"
 #include "pm_imaging.hpp"
 #include "pm_internal.hpp"
 #include "pm_tune.hpp"
@@ -34,6 +36,12 @@ struct ImagingState {
   int bgr_pairs = 0;      // pairs bgr_mm holds
   int enh_taps_cap = 0, enh_ksize = 0;
   double enh_sigma = 0;
+  // fast guided filter: binary64 row sums, a / b planes, interleaved mean_a / mean_b of the coarse image (one allocation)
+  void* gf_buf = nullptr;
+  size_t gf_bytes = 0;
+  // pm_gather_pixels: [bad flag, pad][n x channels floats][n x 2 coordinates]
+  void* gat_buf = nullptr;
+  size_t gat_bytes = 0;
 };
 
 #define PM_HIP(h, call)                                                                                     \
@@ -68,7 +76,7 @@ void pm_internal::release_imaging(pm_handle* h) {
   void** slot = pm_internal::imaging_slot(h);
   ImagingState* st = static_cast<ImagingState*>(*slot);
   if (!st) return;
-  void* dev[] = {st->img_scalars, st->enh_tmp, st->enh_q, st->enh_taps, st->bgr_blur, st->bgr_mm};
+  void* dev[] = {st->img_scalars, st->enh_tmp, st->enh_q, st->enh_taps, st->bgr_blur, st->bgr_mm, st->gf_buf, st->gat_buf};
   for (void* p : dev)
     if (p) (void)hipFree(p);
   delete st;
@@ -516,6 +524,142 @@ int pm_normalize_color_illuminant(pm_handle* h, const float* d_bgr, int rows, in
   if (int rc = ensure_enh_scratch(h, (size_t)rows * cols * 3)) return rc;
   if (int rc = run_gaussian<false>(h, d_bgr, rows, cols, 3, ksize, sigma, true, state_of(h)->enh_q)) return rc;
   return run_normalize(h, state_of(h)->enh_q, rows, cols, d_out, nullptr);
+}
+
+// ---- fast guided filter with a one-channel guide, and the pixel gather (pm_guided.hpp) -----------------------------
+namespace {
+
+int ensure_bytes(pm_handle* h, void** buf, size_t* have, size_t want) {
+  if (want <= *have) return PM_OK;
+  PM_HIP(h, hipStreamSynchronize(pm_internal::stream(h)));  // the old buffer may still be in use
+  if (*buf) PM_HIP(h, hipFree(*buf));
+  *buf = nullptr;
+  *have = 0;
+  PM_HIP(h, hipMalloc(buf, want));
+  *have = want;
+  return PM_OK;
+}
+
+int run_guided_filter(pm_handle* h, const char* what, const float* d_guide, const float* d_src, int rows, int cols,
+                      int channels, int r, double eps, int s, float scale, float* d_dst) {
+  if (int rc = imaging_begin(h, what, d_guide, d_src, rows, cols)) return rc;
+  if (!d_dst) {
+    set_err(h, "%s: null output", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (channels < 1 || channels > 4) {
+    set_err(h, "%s: %d channels (1 .. 4)", what, channels);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (s < 1 || r < 0 || rows / s < 1 || cols / s < 1) {
+    set_err(h, "%s: r = %d must be >= 0, s = %d >= 1, and the %dx%d image at least s x s", what, r, s, cols, rows);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (!(eps >= 0) || !std::isfinite(eps)) {
+    set_err(h, "%s: eps = %g must be finite and >= 0", what, eps);
+    return PM_ERR_INVALID_ARG;
+  }
+  GfShape g{};
+  g.rows = rows;
+  g.cols = cols;
+  g.crows = rows / s;
+  g.ccols = cols / s;
+  g.channels = channels;
+  g.k = 2 * (r / s) + 1;  // fast_guided_filter.cpp:211-214
+  g.inv_y = 1.0 / ((double)g.crows / rows);
+  g.inv_x = 1.0 / ((double)g.ccols / cols);
+  g.up_y = 1.0 / ((double)rows / g.crows);
+  g.up_x = 1.0 / ((double)cols / g.ccols);
+  const size_t row_lds = sizeof(float) * (size_t)g.ccols;
+  if (row_lds > 64 * 1024) {
+    set_err(h, "%s: a coarse row of %d pixels exceeds the row tile", what, g.ccols);
+    return PM_ERR_SIZE;
+  }
+  ImagingState* st = state_of(h);
+  const size_t cpx = (size_t)g.crows * g.ccols;
+  const int planes1 = 2 + 2 * channels, planes2 = 2 * channels;
+  const size_t sum_bytes = sizeof(double) * cpx * planes1, ab_bytes = sizeof(float) * cpx * planes2;
+  if (int rc = ensure_bytes(h, &st->gf_buf, &st->gf_bytes, sum_bytes + 2 * ab_bytes)) return rc;
+  double* rowsum = (double*)st->gf_buf;
+  float* ab = (float*)((char*)st->gf_buf + sum_bytes);
+  float* mean = (float*)((char*)st->gf_buf + sum_bytes + ab_bytes);
+  hipStream_t stream = pm_internal::stream(h);
+  const dim3 cgrid((unsigned)((cpx + 127) / 128), (unsigned)channels);
+  hipLaunchKernelGGL((k_gf_box_rows<true>), dim3((unsigned)g.crows, (unsigned)planes1), dim3(256), row_lds, stream, d_guide,
+                     d_src, (const float*)nullptr, g, rowsum);
+  hipLaunchKernelGGL(k_gf_box_cols_ab, cgrid, dim3(128), 0, stream, (const double*)rowsum, g, (float)eps, ab);
+  hipLaunchKernelGGL((k_gf_box_rows<false>), dim3((unsigned)g.crows, (unsigned)planes2), dim3(256), row_lds, stream,
+                     (const float*)nullptr, (const float*)nullptr, (const float*)ab, g, rowsum);
+  hipLaunchKernelGGL(k_gf_box_cols_mean, cgrid, dim3(128), 0, stream, (const double*)rowsum, g, mean);
+  const size_t n = (size_t)rows * cols;
+  const int vec = aligned16(d_guide) && aligned16(d_dst);
+  const dim3 agrid = stream_grid(n / 4 + 1);
+  switch (channels) {
+    case 1: hipLaunchKernelGGL((k_gf_apply<1>), agrid, dim3(256), 0, stream, d_guide, (const float*)mean, g, scale, d_dst, vec); break;
+    case 2: hipLaunchKernelGGL((k_gf_apply<2>), agrid, dim3(256), 0, stream, d_guide, (const float*)mean, g, scale, d_dst, vec); break;
+    case 3: hipLaunchKernelGGL((k_gf_apply<3>), agrid, dim3(256), 0, stream, d_guide, (const float*)mean, g, scale, d_dst, vec); break;
+    default: hipLaunchKernelGGL((k_gf_apply<4>), agrid, dim3(256), 0, stream, d_guide, (const float*)mean, g, scale, d_dst, vec); break;
+  }
+  return launch_check(h, "guided filter");
+}
+
+}  // namespace
+
+int pm_fast_guided_filter(pm_handle* h, const float* d_guide, const float* d_src, int rows, int cols, int channels, int r,
+                          double eps, int s, float scale, float* d_dst) {
+  return run_guided_filter(h, "pm_fast_guided_filter", d_guide, d_src, rows, cols, channels, r, eps, s, scale, d_dst);
+}
+
+int pm_estimate_illuminant_range_guided(pm_handle* h, const float* d_bgr, const float* d_range, int rows, int cols, int r,
+                                        double eps, int s, float* d_illuminant) {
+  // Akkaynak et al. multiply by a factor of 2 to get the illuminant map (illuminant.cpp:31-33)
+  return run_guided_filter(h, "pm_estimate_illuminant_range_guided", d_range, d_bgr, rows, cols, 3, r, eps, s, 2.0f,
+                           d_illuminant);
+}
+
+int pm_gather_pixels(pm_handle* h, const float* d_img, int rows, int cols, int channels, const int32_t* d_xy,
+                     const int32_t* xy, int n, float* host_out) {
+  if (int rc = imaging_begin(h, "pm_gather_pixels", d_img, d_img, rows, cols)) return rc;
+  if (channels < 1 || channels > 4 || n < 0 || (d_xy != nullptr) == (xy != nullptr) || (n > 0 && !host_out)) {
+    set_err(h, "pm_gather_pixels: 1 .. 4 channels, n >= 0, exactly one of d_xy / xy, and an output for n > 0");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (xy)
+    for (int i = 0; i < n; ++i)
+      if (xy[2 * i] < 0 || xy[2 * i] >= cols || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= rows) {
+        set_err(h, "pm_gather_pixels: entry %d (x = %d, y = %d) lies outside the %dx%d image", i, xy[2 * i], xy[2 * i + 1],
+                cols, rows);
+        return PM_ERR_INVALID_ARG;
+      }
+  if (n == 0) return PM_OK;
+  ImagingState* st = state_of(h);
+  const size_t head = 16, val_bytes = sizeof(float) * (size_t)n * channels, xy_bytes = sizeof(int32_t) * 2 * (size_t)n;
+  if (int rc = ensure_bytes(h, &st->gat_buf, &st->gat_bytes, head + val_bytes + xy_bytes)) return rc;
+  hipStream_t stream = pm_internal::stream(h);
+  unsigned* d_bad = (unsigned*)st->gat_buf;
+  float* d_val = (float*)((char*)st->gat_buf + head);
+  const int32_t* d_coords = d_xy;
+  if (xy) {
+    int32_t* d_copy = (int32_t*)((char*)st->gat_buf + head + val_bytes);
+    PM_HIP(h, hipMemcpyAsync(d_copy, xy, xy_bytes, hipMemcpyHostToDevice, stream));
+    d_coords = d_copy;
+  }
+  PM_HIP(h, hipMemsetAsync(st->gat_buf, 0, head + val_bytes, stream));
+  hipLaunchKernelGGL(k_gather_pixels, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_img, rows, cols, channels,
+                     d_coords, n, d_val, d_bad);
+  if (int rc = launch_check(h, "gather_pixels")) return rc;
+  // flag and values arrive together; host_out is written only when every entry was inside the image
+  std::vector<unsigned char> landed(head + val_bytes);
+  PM_HIP(h, hipMemcpyAsync(landed.data(), st->gat_buf, head + val_bytes, hipMemcpyDeviceToHost, stream));
+  PM_HIP(h, hipStreamSynchronize(stream));
+  unsigned bad = 0;
+  std::memcpy(&bad, landed.data(), sizeof(bad));
+  if (bad) {
+    set_err(h, "pm_gather_pixels: a coordinate of d_xy lies outside the %dx%d image", cols, rows);
+    return PM_ERR_INVALID_ARG;
+  }
+  std::memcpy(host_out, landed.data() + head, val_bytes);
+  return PM_OK;
 }
 
 int pm_device_malloc(pm_handle* h, size_t bytes, void** d_ptr) {

@@ -109,6 +109,37 @@ Image3f EstimateIlluminantGaussian(const Image3f& bgr, int ksizeX, int ksizeY, d
   return out;
 }
 
+namespace {
+template <typename T>
+Image<T> GuidedFilter(const Image1f& guide, const Image<T>& src, int channels, int r, double eps, int s, float scale) {
+  SameSize(guide.rows, guide.cols, src.rows, src.cols, "fastGuidedFilter");
+  std::lock_guard<std::mutex> lock(g_mutex);
+  pm_handle* h = Context();
+  DeviceBuffer d_g(h, Bytes(guide)), d_p(h, Bytes(src));
+  d_g.Upload(guide.data(), Bytes(guide));
+  d_p.Upload(src.data(), Bytes(src));
+  Check(pm_fast_guided_filter(h, d_g.as<float>(), d_p.as<float>(), src.rows, src.cols, channels, r, eps, s, scale,
+                              d_p.as<float>()),
+        "pm_fast_guided_filter");
+  Image<T> out(src.rows, src.cols);
+  d_p.Download(out.data(), Bytes(out));
+  return out;
+}
+}  // namespace
+
+Image1f fastGuidedFilter(const Image1f& guide, const Image1f& src, int r, double eps, int s) {
+  return GuidedFilter(guide, src, 1, r, eps, s, 1.0f);
+}
+
+Image3f fastGuidedFilter(const Image1f& guide, const Image3f& src, int r, double eps, int s) {
+  return GuidedFilter(guide, src, 3, r, eps, s, 1.0f);
+}
+
+Image3f EstimateIlluminantRangeGuided(const Image3f& bgr, const Image1f& range, int r, double eps, int s) {
+  // Akkaynak et al. multiply by a factor of 2 to get the illuminant map (illuminant.cpp:31-33): the kernel's scale
+  return GuidedFilter(range, bgr, 3, r, eps, s, 2.0f);
+}
+
 Image3f Normalize(const Image3f& bgr) {
   std::lock_guard<std::mutex> lock(g_mutex);
   pm_handle* h = Context();

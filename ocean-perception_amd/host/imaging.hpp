@@ -1,7 +1,8 @@
 // imaging.hpp -- host-side C++ mirror of the bm::imaging functions on the rows either side of the stereo
 // hot path, same names and signatures as the reference headers
 //   src/vehicle/imaging/normalization.hpp:12,41   Normalize, NormalizeColorIlluminant
-//   src/vehicle/imaging/illuminant.hpp:10-15      EstimateIlluminantGaussian
+//   src/vehicle/imaging/illuminant.hpp:10-21      EstimateIlluminantGaussian, EstimateIlluminantRangeGuided
+//   src/vehicle/imaging/fast_guided_filter.hpp:27 fastGuidedFilter (one-channel guide)
 //   src/vehicle/imaging/backscatter.hpp:13,45     FindDarkFast, RemoveBackscatter
 //   src/vehicle/imaging/attenuation.hpp:59        CorrectAttenuation
 //   src/vehicle/vision_core/image_util.hpp:34     ComputeIntensity
@@ -43,6 +44,11 @@ void SetDevice(int device);
 Image3f CastImage3bTo3f(const Image3b& im);
 Image1f ComputeIntensity(const Image3f& bgr);
 Image3f EstimateIlluminantGaussian(const Image3f& bgr, int ksizeX, int ksizeY, double sigmaX, double sigmaY);
+Image3f EstimateIlluminantRangeGuided(const Image3f& bgr, const Image1f& range, int r, double eps, int s);
+// fastGuidedFilter(I, p, r, eps, s) with a one-channel float guide I; p has one or three channels.  (The reference
+// takes cv::Mat and a depth argument; the colour guide, which nothing in the reference calls, is not provided.)
+Image1f fastGuidedFilter(const Image1f& guide, const Image1f& src, int r, double eps, int s = 1);
+Image3f fastGuidedFilter(const Image1f& guide, const Image3f& src, int r, double eps, int s = 1);
 Image3f Normalize(const Image3f& bgr);
 Image3f NormalizeColorIlluminant(const Image3f bgr);
 float FindDarkFast(const Image1f& intensity, const Image1f& range, float percentile, Image1b& mask);

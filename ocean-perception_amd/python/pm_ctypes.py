@@ -37,6 +37,7 @@ EXPORTS = [
     "pm_disp_to_range", "pm_remove_backscatter", "pm_correct_attenuation", "pm_range_enhance",
     "pm_compute_intensity", "pm_find_dark", "pm_stereo_ready", "pm_gaussian_blur", "pm_normalize",
     "pm_normalize_color_illuminant", "pm_match_bgr_device", "pm_device_malloc", "pm_device_free", "pm_upload", "pm_download",
+    "pm_fast_guided_filter", "pm_estimate_illuminant_range_guided", "pm_gather_pixels",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate",
     "pm_remove_background", "pm_mask_occlusions", "pm_foreground_texture_mask", "pm_sparse_init", "pm_corner_subpix", "pm_profile_enable", "pm_profile_read",
     "pm_kernel_name", "pm_debug_counters", "pm_debug_counters_enable",
@@ -205,6 +206,9 @@ def load():
     lib.pm_normalize.argtypes = [vp, vp, C.c_int, C.c_int, vp]
     lib.pm_normalize_color_illuminant.argtypes = [vp, vp, C.c_int, C.c_int, vp]
     lib.pm_normalize_color_illuminant.restype = C.c_int
+    lib.pm_fast_guided_filter.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_float, vp]
+    lib.pm_estimate_illuminant_range_guided.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp]
+    lib.pm_gather_pixels.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]
     lib.pm_device_malloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     lib.pm_device_free.argtypes = [vp, vp]
     lib.pm_upload.argtypes = [vp, vp, vp, C.c_size_t]
@@ -586,6 +590,28 @@ class Engine:
     def gaussian_blur(self, d_src, rows, cols, channels, ksize, sigma, d_dst):
         self._check(self.lib.pm_gaussian_blur(self.h, d_src, rows, cols, channels, ksize, sigma, d_dst),
                     "pm_gaussian_blur")
+
+    def fast_guided_filter(self, d_guide, d_src, rows, cols, channels, r, eps, s, scale, d_dst):
+        """fastGuidedFilter(guide, src, r, eps, s) * scale with a one-channel guide (raw device addresses)."""
+        self._check(self.lib.pm_fast_guided_filter(self.h, d_guide, d_src, rows, cols, channels, r, eps, s, scale, d_dst),
+                    "pm_fast_guided_filter")
+
+    def estimate_illuminant_range_guided(self, d_bgr, d_range, rows, cols, r, eps, s, d_illuminant):
+        self._check(self.lib.pm_estimate_illuminant_range_guided(self.h, d_bgr, d_range, rows, cols, r, eps, s,
+                                                                 d_illuminant), "pm_estimate_illuminant_range_guided")
+
+    def gather_pixels(self, d_img, rows, cols, channels, xy=None, d_xy=None, n=None):
+        """Values of a device image at n (x, y) pixels -> float32 array (n, channels).  xy: host coordinates, shape
+        (n, 2); or d_xy: device address of n int32 pairs, with n given."""
+        host = None
+        if xy is not None:
+            host = np.ascontiguousarray(xy, dtype=np.int32).reshape(-1, 2)
+            n = host.shape[0]
+        out = np.empty((int(n), channels), np.float32)
+        self._check(self.lib.pm_gather_pixels(self.h, d_img, rows, cols, channels, d_xy,
+                                              host.ctypes.data_as(C.c_void_p) if host is not None else None, int(n),
+                                              out.ctypes.data_as(C.c_void_p)), "pm_gather_pixels")
+        return out
 
     def normalize(self, d_bgr, rows, cols, d_out):
         self._check(self.lib.pm_normalize(self.h, d_bgr, rows, cols, d_out), "pm_normalize")
