@@ -117,6 +117,66 @@ int pm_normalize(pm_handle* h, const float* d_bgr, int rows, int cols, float* d_
 /* imaging::NormalizeColorIlluminant on a float image (normalization.cpp:178-185). */
 int pm_normalize_color_illuminant(pm_handle* h, const float* d_bgr, int rows, int cols, float* d_out);
 
+/* ---- undistortion + rectification of raw frames in FRONT of Match() ---------------------------------------------
+ * Every kernel of the matcher assumes a rectified pair (pm/patchmatch.h: "rectified stereo only looks along rows").  The
+ * reference ships a calibration with non-zero distortion (config/shared/ACFR.yaml:27,48) and only warns
+ * "distortion_coefficients are nonzero, but we don't handle undistortion yet" (src/vehicle/params/yaml_parser.cpp:153);
+ * this is the stage it lacks, as a per-frame device kernel, so that ingest -> enhancement -> Match -> range -> correction
+ * never needs an image on the host.
+ *
+ * Like the guided filter the kernel is held to its CPU definition (tests/rectify_ref.py) BIT FOR BIT.  It is THIS
+ * PROJECT'S definition: OpenCV's 15-bit coefficient table is not reproduced and nothing here claims parity with
+ * cv::remap.  For destination pixel (u, v), in binary64 with one rounding per operation, parentheses as written:
+ *   a = (u - cx_new) / fx_new      b = (v - cy_new) / fy_new
+ *   X = (R[0] a + R[3] b) + R[6]   Y = (R[1] a + R[4] b) + R[7]   W = (R[2] a + R[5] b) + R[8]      (R^T (a, b, 1))
+ *   not (W > 0): INVALID;  x = X / W, y = Y / W, xx = x x, yy = y y, xy = x y, r2 = xx + yy
+ *   rad = 1 + r2 (k1 + r2 (k2 + r2 k3))
+ *   tx = ((2 p1) xy) + (p2 (r2 + (2 xx)))      ty = (p1 (r2 + (2 yy))) + ((2 p2) xy)
+ *   sx = fx ((x rad) + tx) + cx                sy = fy ((y rad) + ty) + cy
+ *   qx = 32 sx, qy = 32 sy;  not (|qx| < 2^30 and |qy| < 2^30): INVALID (also NaN / inf)
+ *   ix = rint(qx), iy = rint(qy) (half to even);  x0 = ix >> 5, ax = ix & 31, likewise y0, ay
+ *   out = ((32-ax)(32-ay) p(x0,y0) + ax (32-ay) p(x0+1,y0) + (32-ax) ay p(x0,y0+1) + ax ay p(x0+1,y0+1) + 512) >> 10,
+ *   a tap outside the source reads border_value; valid = 255 iff every tap with a non-zero weight lies inside, else 0.
+ *   INVALID: out = border_value, valid = 0, map entry (INT32_MIN, INT32_MIN).
+ * No coordinate map is kept in memory: the view travels in the kernel arguments and the model is evaluated per pixel
+ * in registers, so a change of calibration allocates and invalidates nothing. */
+typedef struct pm_camera { double fx, fy, cx, cy, k1, k2, p1, p2, k3; } pm_camera; /* radial-tangential model */
+/* cam: the raw camera; R (3x3, row-major) rotates raw-camera coordinates into rectified ones, x_rect = R x_raw; the new
+ * pinhole of the rectified image. */
+typedef struct pm_rectify_view { pm_camera cam; double R[9]; double fx_new, fy_new, cx_new, cy_new; } pm_rectify_view;
+
+/* n raw images [n][src_rows] rows of src_step bytes (0 = packed) -> n rectified images [n][rows][cols], packed.
+ * d_valid ([n][rows][cols], 255 / 0) may be NULL.  stream: a hipStream_t or NULL = the handle's stream (as in
+ * pm_match_view_device), so that a sequence caller can rectify on its own stream and hand the event to
+ * pm_submit_device_after.
+ * PM_ERR_INVALID_ARG (nothing is enqueued): a null view / d_src / d_dst, n / rows / cols / src_rows / src_cols < 1,
+ * src_step smaller than src_cols, border_value outside 0 .. 255, a non-finite view entry, fx_new or fy_new == 0. */
+int pm_rectify_u8(pm_handle* h, const pm_rectify_view* view, const uint8_t* d_src, int n, int src_rows, int src_cols,
+                  size_t src_step, int rows, int cols, int border_value, uint8_t* d_dst, uint8_t* d_valid, void* stream);
+/* the Q5 source coordinates the kernel uses: [rows][cols][2] int32 (x, y); INVALID = INT32_MIN twice.  Written by the
+ * same kernel code that forms the pixels (a compile-time switch), on the handle's stream. */
+int pm_rectify_map(pm_handle* h, const pm_rectify_view* view, int rows, int cols, int32_t* d_xy);
+/* pm_rectify_u8 of both images into handle-owned scratch, then pm_match_device on them: same stream, same results,
+ * in every mode of the handle; seeds / outputs as pm_match_device (NULL seeds + sparse_init self-seed on the
+ * RECTIFIED pair).  border_value is 0.  rows x cols is the rectified size and is checked against the handle's plan like
+ * pm_match_device's (PM_ERR_SIZE) before anything is enqueued.  The scratch (2 n rows cols bytes) is allocated on first
+ * use, reused, and released with the handle; as for pm_match_device, a size must have run once before it is captured
+ * (pm_capture_begin): growing the scratch synchronises the stream. */
+int pm_match_raw_device(pm_handle* h, int n, const pm_rectify_view* left, const pm_rectify_view* right,
+                        const uint8_t* d_left_raw, const uint8_t* d_right_raw, int src_rows, int src_cols,
+                        size_t src_step, int rows, int cols, const float* d_seed_l, const float* d_seed_r,
+                        float* d_disp_l, float* d_disp_r);
+/* Host only, no handle, no device: rectifying rotations and a common pinhole for a calibrated pair,
+ * X2 = R X1 + T (camera 1 = left).  Returns the rectified baseline (> 0) through *baseline.
+ * Bouguet's construction: each camera is turned by half of R (camera 1 by R^(1/2), camera 2 by R^(-1/2)), then one
+ * rotation about the axis t x (-1, 0, 0) takes the turned baseline t = R^(-1/2) T onto the -x axis, so that
+ * v2->R T = (-baseline, 0, 0).  The common pinhole is fx_new = fy_new = min(c1.fy, c2.fy), (cx_new, cy_new) the mean of
+ * the two principal points; there is no ROI or alpha logic.  R = I and T = (-B, 0, 0) give v1->R = v2->R = I exactly.
+ * PM_ERR_INVALID_ARG: a null pointer, a non-finite entry, T = 0, a relative rotation of (nearly) 180 degrees, or a
+ * turned baseline that does not point towards -x (camera 1 is not the left one). */
+int pm_stereo_rectify(const pm_camera* c1, const pm_camera* c2, const double R[9], const double T[3],
+                      pm_rectify_view* v1, pm_rectify_view* v2, double* baseline);
+
 /* ---- device buffers for host code that does not include HIP (host/imaging.hpp uses them) ------------------
  * pm_device_malloc / pm_device_free wrap hipMalloc / hipFree on the handle's device; pm_upload / pm_download are
  * stream-ordered copies on the handle's stream from / to pageable host memory (pm_download returns after the

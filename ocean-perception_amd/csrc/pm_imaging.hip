@@ -15,6 +15,7 @@
 #include "pm_guided.hpp"
 #include "pm_imaging.hpp"
 #include "pm_internal.hpp"
+#include "pm_rectify.hpp"
 #include "pm_tune.hpp"
 
 using namespace pm;
@@ -42,6 +43,9 @@ struct ImagingState {
   // pm_gather_pixels: [bad flag, pad][n x channels floats][n x 2 coordinates]
   void* gat_buf = nullptr;
   size_t gat_bytes = 0;
+  // pm_match_raw_device: the rectified pairs, [left, right][n][rows][cols] bytes
+  void* rect_buf = nullptr;
+  size_t rect_bytes = 0;
 };
 
 #define PM_HIP(h, call)                                                                                     \
@@ -76,7 +80,8 @@ void pm_internal::release_imaging(pm_handle* h) {
   void** slot = pm_internal::imaging_slot(h);
   ImagingState* st = static_cast<ImagingState*>(*slot);
   if (!st) return;
-  void* dev[] = {st->img_scalars, st->enh_tmp, st->enh_q, st->enh_taps, st->bgr_blur, st->bgr_mm, st->gf_buf, st->gat_buf};
+  void* dev[] = {st->img_scalars, st->enh_tmp, st->enh_q, st->enh_taps, st->bgr_blur, st->bgr_mm, st->gf_buf, st->gat_buf,
+                 st->rect_buf};
   for (void* p : dev)
     if (p) (void)hipFree(p);
   delete st;
@@ -659,6 +664,221 @@ int pm_gather_pixels(pm_handle* h, const float* d_img, int rows, int cols, int c
     return PM_ERR_INVALID_ARG;
   }
   std::memcpy(host_out, landed.data() + head, val_bytes);
+  return PM_OK;
+}
+
+// ---- undistortion + rectification in front of Match() (pm_rectify.hpp) ----------------------------------------------
+namespace {
+
+// the checks of a view that every entry point shares; `which` names it in the error text
+int check_view(pm_handle* h, const char* what, const char* which, const pm_rectify_view* v) {
+  if (!v) {
+    set_err(h, "%s: null %s", what, which);
+    return PM_ERR_INVALID_ARG;
+  }
+  const double* e = reinterpret_cast<const double*>(v);
+  static_assert(sizeof(pm_rectify_view) == 22 * sizeof(double), "pm_rectify_view is 22 doubles");
+  for (int i = 0; i < 22; ++i)
+    if (!std::isfinite(e[i])) {
+      set_err(h, "%s: entry %d of %s is not finite", what, i, which);
+      return PM_ERR_INVALID_ARG;
+    }
+  if (v->fx_new == 0.0 || v->fy_new == 0.0) {
+    set_err(h, "%s: fx_new / fy_new of %s must not be 0", what, which);
+    return PM_ERR_INVALID_ARG;
+  }
+  return PM_OK;
+}
+
+int check_rectify_shape(pm_handle* h, const char* what, int n, int src_rows, int src_cols, size_t* src_step, int rows,
+                        int cols, int border_value) {
+  if (n < 1 || src_rows < 1 || src_cols < 1 || rows < 1 || cols < 1) {
+    set_err(h, "%s: %d images of %dx%d from %dx%d: every count and size must be >= 1", what, n, cols, rows, src_cols, src_rows);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (*src_step == 0) *src_step = (size_t)src_cols;
+  if (*src_step < (size_t)src_cols) {
+    set_err(h, "%s: src_step %zu is smaller than a row of %d bytes", what, *src_step, src_cols);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (border_value < 0 || border_value > 255) {
+    set_err(h, "%s: border_value %d outside 0 .. 255", what, border_value);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (n > 65535 || (rows + kRectifyBlockY - 1) / kRectifyBlockY > 65535) {
+    set_err(h, "%s: %d images of %d rows exceed the launch grid", what, n, rows);
+    return PM_ERR_SIZE;
+  }
+  return PM_OK;
+}
+
+inline dim3 rectify_grid(int rows, int cols, int n) {
+  const int px = kRectifyBlockX * 4;
+  return dim3((unsigned)((cols + px - 1) / px), (unsigned)((rows + kRectifyBlockY - 1) / kRectifyBlockY), (unsigned)n);
+}
+
+// arguments already checked
+void launch_rectify(const pm_rectify_view& view, const uint8_t* d_src, int n, int src_rows, int src_cols, size_t src_step,
+                    int rows, int cols, int border_value, uint8_t* d_dst, uint8_t* d_valid, hipStream_t stream) {
+  hipLaunchKernelGGL((k_rectify<false>), rectify_grid(rows, cols, n), dim3(kRectifyBlockX, kRectifyBlockY), 0, stream, view,
+                     d_src, src_rows, src_cols, src_step, rows, cols, border_value, d_dst, d_valid, (int32_t*)nullptr);
+}
+
+}  // namespace
+
+int pm_rectify_u8(pm_handle* h, const pm_rectify_view* view, const uint8_t* d_src, int n, int src_rows, int src_cols,
+                  size_t src_step, int rows, int cols, int border_value, uint8_t* d_dst, uint8_t* d_valid, void* stream) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (!d_src || !d_dst) {
+    set_err(h, "pm_rectify_u8: null image pointer");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_view(h, "pm_rectify_u8", "view", view)) return rc;
+  if (int rc = check_rectify_shape(h, "pm_rectify_u8", n, src_rows, src_cols, &src_step, rows, cols, border_value)) return rc;
+  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
+  launch_rectify(*view, d_src, n, src_rows, src_cols, src_step, rows, cols, border_value, d_dst, d_valid,
+                 stream ? (hipStream_t)stream : pm_internal::stream(h));
+  return launch_check(h, "rectify");
+}
+
+int pm_rectify_map(pm_handle* h, const pm_rectify_view* view, int rows, int cols, int32_t* d_xy) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (!d_xy) {
+    set_err(h, "pm_rectify_map: null output");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_view(h, "pm_rectify_map", "view", view)) return rc;
+  size_t step = 0;
+  if (int rc = check_rectify_shape(h, "pm_rectify_map", 1, 1, 1, &step, rows, cols, 0)) return rc;
+  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
+  hipLaunchKernelGGL((k_rectify<true>), rectify_grid(rows, cols, 1), dim3(kRectifyBlockX, kRectifyBlockY), 0,
+                     pm_internal::stream(h), *view, (const uint8_t*)nullptr, 0, 0, (size_t)0, rows, cols, 0, (uint8_t*)nullptr,
+                     (uint8_t*)nullptr, d_xy);
+  return launch_check(h, "rectify map");
+}
+
+int pm_match_raw_device(pm_handle* h, int n, const pm_rectify_view* left, const pm_rectify_view* right,
+                        const uint8_t* d_left_raw, const uint8_t* d_right_raw, int src_rows, int src_cols, size_t src_step,
+                        int rows, int cols, const float* d_seed_l, const float* d_seed_r, float* d_disp_l, float* d_disp_r) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (!d_left_raw || !d_right_raw || !d_disp_l) {
+    set_err(h, "pm_match_raw_device: null image or output pointer");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_view(h, "pm_match_raw_device", "left view", left)) return rc;
+  if (int rc = check_view(h, "pm_match_raw_device", "right view", right)) return rc;
+  if (int rc = check_rectify_shape(h, "pm_match_raw_device", n, src_rows, src_cols, &src_step, rows, cols, 0)) return rc;
+  int max_rows = 0, max_cols = 0;
+  pm_internal::plan_size(h, &max_rows, &max_cols);
+  if (rows < 8 || cols < 8) {
+    set_err(h, "pm_match_raw_device: rectified image %dx%d too small (min 8x8)", cols, rows);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (rows > max_rows || cols > max_cols) {
+    set_err(h, "pm_match_raw_device: rectified size %dx%d exceeds plan %dx%d", cols, rows, max_cols, max_rows);
+    return PM_ERR_SIZE;
+  }
+  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
+  ImagingState* st = state_of(h);
+  if (!st) {
+    set_err(h, "pm_match_raw_device: out of host memory");
+    return PM_ERR_NOMEM;
+  }
+  const size_t side = (size_t)n * rows * cols;
+  if (int rc = ensure_bytes(h, &st->rect_buf, &st->rect_bytes, 2 * side)) return rc;
+  uint8_t* rect_l = (uint8_t*)st->rect_buf;
+  uint8_t* rect_r = rect_l + side;
+  hipStream_t stream = pm_internal::stream(h);
+  launch_rectify(*left, d_left_raw, n, src_rows, src_cols, src_step, rows, cols, 0, rect_l, nullptr, stream);
+  launch_rectify(*right, d_right_raw, n, src_rows, src_cols, src_step, rows, cols, 0, rect_r, nullptr, stream);
+  if (int rc = launch_check(h, "rectify")) return rc;
+  return pm_match_device(h, n, rect_l, rect_r, rows, cols, d_seed_l, d_seed_r, d_disp_l, d_disp_r);
+}
+
+// Host only: Bouguet's construction (see pm/imaging.h).
+namespace {
+
+struct Mat3 {
+  double m[9];
+};
+Mat3 mul(const Mat3& a, const Mat3& b) {
+  Mat3 c{};
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) c.m[3 * i + j] = (a.m[3 * i] * b.m[j] + a.m[3 * i + 1] * b.m[3 + j]) + a.m[3 * i + 2] * b.m[6 + j];
+  return c;
+}
+Mat3 transpose(const Mat3& a) {
+  Mat3 t{};
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) t.m[3 * i + j] = a.m[3 * j + i];
+  return t;
+}
+// Rodrigues: the rotation by |w| about w; |w| == 0 gives I exactly
+Mat3 rotation_of(const double w[3]) {
+  const double th = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+  Mat3 r{{1, 0, 0, 0, 1, 0, 0, 0, 1}};
+  if (th == 0.0) return r;
+  const double k[3] = {w[0] / th, w[1] / th, w[2] / th};
+  const double c = std::cos(th), s = std::sin(th), v = 1.0 - c;
+  r.m[0] = c + v * k[0] * k[0];
+  r.m[1] = v * k[0] * k[1] - s * k[2];
+  r.m[2] = v * k[0] * k[2] + s * k[1];
+  r.m[3] = v * k[1] * k[0] + s * k[2];
+  r.m[4] = c + v * k[1] * k[1];
+  r.m[5] = v * k[1] * k[2] - s * k[0];
+  r.m[6] = v * k[2] * k[0] - s * k[1];
+  r.m[7] = v * k[2] * k[1] + s * k[0];
+  r.m[8] = c + v * k[2] * k[2];
+  return r;
+}
+
+}  // namespace
+
+int pm_stereo_rectify(const pm_camera* c1, const pm_camera* c2, const double R[9], const double T[3], pm_rectify_view* v1,
+                      pm_rectify_view* v2, double* baseline) {
+  if (!c1 || !c2 || !R || !T || !v1 || !v2 || !baseline) return PM_ERR_INVALID_ARG;
+  for (int i = 0; i < 9; ++i)
+    if (!std::isfinite(R[i]) || !std::isfinite(reinterpret_cast<const double*>(c1)[i]) ||
+        !std::isfinite(reinterpret_cast<const double*>(c2)[i]))
+      return PM_ERR_INVALID_ARG;
+  const double len = std::sqrt(T[0] * T[0] + T[1] * T[1] + T[2] * T[2]);
+  if (!std::isfinite(len) || len == 0.0) return PM_ERR_INVALID_ARG;
+  // R = exp([om]x): om = axis * angle, from the skew part (sine) and the trace (cosine)
+  const double sk[3] = {0.5 * (R[7] - R[5]), 0.5 * (R[2] - R[6]), 0.5 * (R[3] - R[1])};
+  const double s = std::sqrt(sk[0] * sk[0] + sk[1] * sk[1] + sk[2] * sk[2]);
+  const double c = 0.5 * ((R[0] + R[4] + R[8]) - 1.0);
+  if (c < -0.99) return PM_ERR_INVALID_ARG;  // cameras that look in opposite directions
+  double half[3] = {0, 0, 0};                // -om / 2
+  if (s > 0.0) {
+    const double scale = -0.5 * std::atan2(s, c) / s;
+    for (int i = 0; i < 3; ++i) half[i] = sk[i] * scale;
+  }
+  const Mat3 r_r = rotation_of(half);  // R^(-1/2): turns camera 2; its transpose turns camera 1
+  const double t[3] = {(r_r.m[0] * T[0] + r_r.m[1] * T[1]) + r_r.m[2] * T[2], (r_r.m[3] * T[0] + r_r.m[4] * T[1]) + r_r.m[5] * T[2],
+                       (r_r.m[6] * T[0] + r_r.m[7] * T[1]) + r_r.m[8] * T[2]};
+  if (!(t[0] < 0.0)) return PM_ERR_INVALID_ARG;  // camera 1 is not the left one
+  // the rotation that takes t onto -x: axis t x (-1, 0, 0) = (0, -t2, t1), angle acos(-t0 / |t|)
+  double ww[3] = {0.0, -t[2], t[1]};
+  const double nw = std::sqrt(ww[1] * ww[1] + ww[2] * ww[2]);
+  if (nw > 0.0) {
+    const double angle = std::atan2(nw, -t[0]);
+    ww[1] = ww[1] * (angle / nw);
+    ww[2] = ww[2] * (angle / nw);
+  }
+  const Mat3 w_r = rotation_of(ww);
+  const Mat3 r1 = mul(w_r, transpose(r_r)), r2 = mul(w_r, r_r);
+  const double f = c1->fy < c2->fy ? c1->fy : c2->fy;
+  pm_rectify_view* out[2] = {v1, v2};
+  const pm_camera* cam[2] = {c1, c2};
+  const Mat3* rot[2] = {&r1, &r2};
+  for (int i = 0; i < 2; ++i) {
+    out[i]->cam = *cam[i];
+    for (int k = 0; k < 9; ++k) out[i]->R[k] = rot[i]->m[k];
+    out[i]->fx_new = out[i]->fy_new = f;
+    out[i]->cx_new = 0.5 * (c1->cx + c2->cx);
+    out[i]->cy_new = 0.5 * (c1->cy + c2->cy);
+  }
+  *baseline = len;
   return PM_OK;
 }
 

@@ -231,5 +231,34 @@ Image1f DispToDepth(const Image1f& disp, double fx, double baseline) {
   return out;
 }
 
+double StereoRectify(const CameraModel& cam1, const CameraModel& cam2, const std::array<double, 9>& R,
+                     const std::array<double, 3>& T, RectifyView* view1, RectifyView* view2) {
+  const pm_camera c1{cam1.fx, cam1.fy, cam1.cx, cam1.cy, cam1.k1, cam1.k2, cam1.p1, cam1.p2, cam1.k3};
+  const pm_camera c2{cam2.fx, cam2.fy, cam2.cx, cam2.cy, cam2.k1, cam2.k2, cam2.p1, cam2.p2, cam2.k3};
+  double baseline = 0;
+  if (pm_stereo_rectify(&c1, &c2, R.data(), T.data(), view1, view2, &baseline) != PM_OK)
+    throw std::invalid_argument("StereoRectify: null view, non-finite calibration, or camera 1 is not the left camera");
+  return baseline;
+}
+
+Image1b Rectify(const Image1b& raw, const RectifyView& view, int rows, int cols, Image1b* valid) {
+  if (raw.rows <= 0 || raw.cols <= 0 || rows <= 0 || cols <= 0) throw std::invalid_argument("Rectify: empty image");
+  std::lock_guard<std::mutex> lock(g_mutex);
+  pm_handle* h = Context();
+  const size_t out_bytes = (size_t)rows * cols;
+  DeviceBuffer d_in(h, Bytes(raw)), d_out(h, out_bytes), d_valid(h, out_bytes);
+  d_in.Upload(raw.data(), Bytes(raw));
+  Check(pm_rectify_u8(h, &view, d_in.as<uint8_t>(), 1, raw.rows, raw.cols, 0, rows, cols, 0, d_out.as<uint8_t>(),
+                      valid ? d_valid.as<uint8_t>() : nullptr, nullptr),
+        "pm_rectify_u8");
+  Image1b out(rows, cols);
+  d_out.Download(out.data(), out_bytes);
+  if (valid) {
+    if (valid->rows != rows || valid->cols != cols) valid->create(rows, cols);
+    d_valid.Download(valid->data(), out_bytes);
+  }
+  return out;
+}
+
 }  // namespace imaging
 }  // namespace bm

@@ -61,5 +61,18 @@ Image1b StereoReady(const Image3b& bgr);
 // StereoCamera::DispToDepth (vision_core/stereo_camera.cpp:49-53) over a map; 0 where disp <= 0.
 Image1f DispToDepth(const Image1f& disp, double fx, double baseline);
 
+// Not in the reference, which warns "distortion_coefficients are nonzero, but we don't handle undistortion yet"
+// (src/vehicle/params/yaml_parser.cpp:153): undistortion + rectification of a raw frame (pm/imaging.h, pm_rectify_u8).
+struct CameraModel {  // radial-tangential, the entries of pm_camera
+  double fx = 0, fy = 0, cx = 0, cy = 0, k1 = 0, k2 = 0, p1 = 0, p2 = 0, k3 = 0;
+};
+typedef pm_rectify_view RectifyView;
+// Rectifying rotations and a common pinhole for a calibrated pair, X2 = R X1 + T (camera 1 = left; R row-major); returns
+// the rectified baseline.  Host only: needs no GPU.  Throws std::invalid_argument where pm_stereo_rectify refuses.
+double StereoRectify(const CameraModel& cam1, const CameraModel& cam2, const std::array<double, 9>& R,
+                     const std::array<double, 3>& T, RectifyView* view1, RectifyView* view2);
+// The raw image seen through `view`, rows x cols, pixels without a source 0; valid (255 / 0) where it is asked for.
+Image1b Rectify(const Image1b& raw, const RectifyView& view, int rows, int cols, Image1b* valid = nullptr);
+
 }  // namespace imaging
 }  // namespace bm

@@ -38,6 +38,7 @@ EXPORTS = [
     "pm_compute_intensity", "pm_find_dark", "pm_stereo_ready", "pm_gaussian_blur", "pm_normalize",
     "pm_normalize_color_illuminant", "pm_match_bgr_device", "pm_device_malloc", "pm_device_free", "pm_upload", "pm_download",
     "pm_fast_guided_filter", "pm_estimate_illuminant_range_guided", "pm_gather_pixels",
+    "pm_rectify_u8", "pm_rectify_map", "pm_match_raw_device", "pm_stereo_rectify",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate",
     "pm_remove_background", "pm_mask_occlusions", "pm_foreground_texture_mask", "pm_sparse_init", "pm_corner_subpix", "pm_profile_enable", "pm_profile_read",
     "pm_kernel_name", "pm_debug_counters", "pm_debug_counters_enable",
@@ -117,6 +118,44 @@ class PmTiledAuditRecord(C.Structure):  # include/pm/testing.h
     _fields_ = [("call", C.c_int), ("band", C.c_int), ("detail", C.c_int), ("current_device", C.c_int),
                 ("stream_device", C.c_int), ("object_device", C.c_int), ("source_device", C.c_int),
                 ("foreign_allowed", C.c_int), ("violation", C.c_int)]
+
+
+class PmCamera(C.Structure):  # include/pm/imaging.h: the radial-tangential model
+    _fields_ = [(name, C.c_double) for name in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
+
+
+class PmRectifyView(C.Structure):
+    _fields_ = [("cam", PmCamera), ("R", C.c_double * 9), ("fx_new", C.c_double), ("fy_new", C.c_double),
+                ("cx_new", C.c_double), ("cy_new", C.c_double)]
+
+
+def rectify_view(values):
+    """A PmRectifyView from its 22 doubles (cam[9], R[9] row-major, fx_new, fy_new, cx_new, cy_new); a PmRectifyView or
+    None passes through."""
+    if values is None or isinstance(values, PmRectifyView):
+        return values
+    v = np.ascontiguousarray(values, dtype=np.float64).reshape(22)
+    return PmRectifyView.from_buffer_copy(v.tobytes())
+
+
+def view_values(view):
+    """The 22 doubles of a PmRectifyView as a numpy array."""
+    return np.frombuffer(bytes(view), np.float64).copy()
+
+
+def stereo_rectify(cam1, cam2, R, T):
+    """pm_stereo_rectify (host only): cam1 / cam2: 9 doubles each, X2 = R X1 + T -> (view1, view2, baseline), the views as
+    arrays of 22 doubles."""
+    lib = load()
+    c1 = PmCamera.from_buffer_copy(np.ascontiguousarray(cam1, dtype=np.float64).reshape(9).tobytes())
+    c2 = PmCamera.from_buffer_copy(np.ascontiguousarray(cam2, dtype=np.float64).reshape(9).tobytes())
+    r = (C.c_double * 9)(*np.asarray(R, np.float64).reshape(9))
+    t = (C.c_double * 3)(*np.asarray(T, np.float64).reshape(3))
+    v1, v2, base = PmRectifyView(), PmRectifyView(), C.c_double(0)
+    rc = lib.pm_stereo_rectify(C.byref(c1), C.byref(c2), r, t, C.byref(v1), C.byref(v2), C.byref(base))
+    if rc != PM_OK:
+        raise PmError(rc, "pm_stereo_rectify", lib.pm_status_string(rc).decode())
+    return view_values(v1), view_values(v2), float(base.value)
 
 
 class PmProfile(C.Structure):
@@ -209,6 +248,15 @@ def load():
     lib.pm_fast_guided_filter.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_float, vp]
     lib.pm_estimate_illuminant_range_guided.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp]
     lib.pm_gather_pixels.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp]
+    view_p = C.POINTER(PmRectifyView)
+    lib.pm_rectify_u8.argtypes = [vp, view_p, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.pm_rectify_map.argtypes = [vp, view_p, C.c_int, C.c_int, vp]
+    lib.pm_match_raw_device.argtypes = [vp, C.c_int, view_p, view_p, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int,
+                                        vp, vp, vp, vp]
+    lib.pm_stereo_rectify.argtypes = [C.POINTER(PmCamera), C.POINTER(PmCamera), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                      view_p, view_p, C.POINTER(C.c_double)]
+    for name in ("pm_rectify_u8", "pm_rectify_map", "pm_match_raw_device", "pm_stereo_rectify"):
+        getattr(lib, name).restype = C.c_int
     lib.pm_device_malloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     lib.pm_device_free.argtypes = [vp, vp]
     lib.pm_upload.argtypes = [vp, vp, vp, C.c_size_t]
@@ -612,6 +660,29 @@ class Engine:
                                               host.ctypes.data_as(C.c_void_p) if host is not None else None, int(n),
                                               out.ctypes.data_as(C.c_void_p)), "pm_gather_pixels")
         return out
+
+    def rectify_u8(self, view, d_src, n, src_rows, src_cols, src_step, rows, cols, border_value, d_dst, d_valid=None,
+                   stream=None):
+        """n raw images -> n undistorted, rectified images (raw device addresses); view: 22 doubles or a PmRectifyView."""
+        v = rectify_view(view)
+        self._check(self.lib.pm_rectify_u8(self.h, C.byref(v) if v is not None else None, d_src, n, src_rows, src_cols,
+                                           src_step, rows, cols, border_value, d_dst, d_valid, stream), "pm_rectify_u8")
+
+    def rectify_map(self, view, rows, cols, d_xy):
+        """The Q5 source coordinates pm_rectify_u8 uses: int32 [rows][cols][2] at the device address d_xy."""
+        v = rectify_view(view)
+        self._check(self.lib.pm_rectify_map(self.h, C.byref(v) if v is not None else None, rows, cols, d_xy),
+                    "pm_rectify_map")
+
+    def match_raw_device(self, n, left_view, right_view, d_left_raw, d_right_raw, src_rows, src_cols, src_step, rows, cols,
+                         d_seed_l, d_seed_r, d_disp_l, d_disp_r):
+        """pm_rectify_u8 of both raw images followed by pm_match_device (raw device addresses)."""
+        self._pl_shape = (rows, cols)
+        vl, vr = rectify_view(left_view), rectify_view(right_view)
+        self._check(self.lib.pm_match_raw_device(self.h, n, C.byref(vl) if vl is not None else None,
+                                                 C.byref(vr) if vr is not None else None, d_left_raw, d_right_raw, src_rows,
+                                                 src_cols, src_step, rows, cols, d_seed_l, d_seed_r, d_disp_l, d_disp_r),
+                    "pm_match_raw_device")
 
     def normalize(self, d_bgr, rows, cols, d_out):
         self._check(self.lib.pm_normalize(self.h, d_bgr, rows, cols, d_out), "pm_normalize")
