@@ -12,6 +12,13 @@ extern "C" {
  * pm_capture_end (PM_ERR_STATE instead of a fault inside the runtime) can be exercised */
 int pm_debug_capture_fork(pm_handle* h);
 
+/* Device memory the process's handles hold right now -- allocations and their bytes, over every handle and device.
+ * Everything a handle allocates for itself goes through one owning type (csrc/pm_devbuf.hpp) that keeps these two
+ * counters, so a create / use / destroy cycle that does not bring them back to where they were has leaked.  Not counted:
+ * memory handed to the caller (pm_device_malloc), the band buffers of pm_tiled_* (logged by the audit below), host memory. */
+long long pm_debug_live_device_allocations(void);
+long long pm_debug_live_device_bytes(void);
+
 /* ---- the row-tiled driver's device discipline, provable on ONE GPU ------------------------------------------------
  * pm_tiled_create with the bands accounted to LOGICAL devices: band k lives on logical_devices[k] (>= 0; several bands
  * may share one) while every HIP call still goes to the physical device of the band's handle.  Such a plan logs every

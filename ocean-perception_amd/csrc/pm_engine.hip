@@ -257,15 +257,12 @@ int pair_planes_alloc(pm_handle* h, hipStream_t stream) {
   if (h->rpg) return PM_OK;
   const size_t B = (size_t)h->max_batch;
   const size_t pitch_t = (size_t)align_up(h->max_rows, 64);
-  const size_t nrp = B * 2 * (size_t)(h->max_rows + 2) * h->max_pitch + 64;
-  const size_t ncp = B * 2 * (size_t)(h->max_cols + kTransPad + 2) * pitch_t + 64;
-  PM_HIP(h, hipMalloc((void**)&h->rpg, sizeof(float) * 4 * nrp));
-  PM_HIP(h, hipMalloc((void**)&h->rqk, sizeof(uint32_t) * 2 * nrp));
-  PM_HIP(h, hipMalloc((void**)&h->cpg, sizeof(float) * 4 * ncp));
-  // row padding behind `cols` / `rows` is read (with weight 0 or by lanes out of reach) and must be finite
-  PM_HIP(h, hipMemsetAsync(h->rpg, 0, sizeof(float) * 4 * nrp, stream));
-  PM_HIP(h, hipMemsetAsync(h->rqk, 0, sizeof(uint32_t) * 2 * nrp, stream));
-  PM_HIP(h, hipMemsetAsync(h->cpg, 0, sizeof(float) * 4 * ncp, stream));
+  const size_t nrp = B * 2 * (size_t)(h->max_rows + 2) * h->max_pitch + kSlackElems;
+  const size_t ncp = B * 2 * (size_t)(h->max_cols + kTransPad + 2) * pitch_t + kSlackElems;
+  // zeroed: row padding behind `cols` / `rows` is read (with weight 0 or by lanes out of reach) and must be finite
+  PM_HIP(h, h->rpg.alloc_zeroed(sizeof(float) * 4 * nrp, stream));
+  PM_HIP(h, h->rqk.alloc_zeroed(sizeof(uint32_t) * 2 * nrp, stream));
+  PM_HIP(h, h->cpg.alloc_zeroed(sizeof(float) * 4 * ncp, stream));
   return PM_OK;
 }
 
@@ -329,13 +326,11 @@ int ensure_noise(pm_handle* h, int rows, int cols) {
     return PM_ERR_BUSY;
   }
   const size_t count = (size_t)rows * pitch;
+  // needed even when the table does not grow (the copy below overwrites one that may still be in use); reserve
+  // synchronises once more when it does grow, which costs nothing on a path that reallocates
   PM_HIP(h, hipStreamSynchronize(h->stream));
-  if (count > h->noise_capacity) {
-    if (h->noise) PM_HIP(h, hipFree(h->noise));
-    h->noise = nullptr;
-    PM_HIP(h, hipMalloc((void**)&h->noise, sizeof(float) * (count + 64)));
-    h->noise_capacity = count;
-  }
+  h->noise_rows = h->noise_cols = h->noise_pitch = 0;
+  PM_HIP(h, h->noise.reserve(sizeof(float) * (count + kSlackElems), h->stream));
   std::vector<float> host(count);
   fill_unit_noise(host.data(), rows, cols, pitch, h->params.noise_seed);
   PM_HIP(h, hipMemcpy(h->noise, host.data(), sizeof(float) * count, hipMemcpyHostToDevice));
@@ -1043,13 +1038,6 @@ void pm_destroy(pm_handle* h) {
     for (hipEvent_t e : evs)
       if (e) (void)hipEventDestroy(e);
   }
-  void* dev[] = {h->rpg,     h->rqk,      h->cpg,       h->img8,      h->g32,       h->g8,        h->timg8,
-                 h->tg32,    h->tg8,      h->pk16,      h->tpk16,     h->disp,      h->cost,      h->noise,
-                 h->counters, h->st_left, h->st_seed_l, h->st_seed_r, h->st_disp_l, h->st_disp_r,
-                 h->snap_disp, h->snap_cost, h->planes_state, h->texmask_scratch};
-  for (auto& sc : h->seeds) seed_scratch_free(sc);
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
   delete h->copy_pool;
   if (h->pinned) (void)hipHostFree(h->pinned);
   // memory handed out by pm_host_alloc and still held, registrations still standing
@@ -1057,9 +1045,11 @@ void pm_destroy(pm_handle* h) {
     if (r.owned) (void)hipHostFree(r.base);
     else (void)hipHostUnregister(r.base);
   }
+  // the handle's device memory goes with its members (pm_devbuf.hpp): the device is current, every stream has been
+  // synchronised above and still exists
+  delete h;
   for (hipStream_t st : streams)
     if (st) (void)hipStreamDestroy(st);
-  delete h;
 }
 
 int pm_create(const pm_params* params, int device, int max_rows, int max_cols, int max_batch, pm_handle** out) {
@@ -1101,46 +1091,37 @@ int pm_create(const pm_params* params, int device, int max_rows, int max_cols, i
   h->max_pitch = align_up(max_cols, 64);
   const size_t plane = (size_t)max_rows * h->max_pitch;
   const size_t B = (size_t)max_batch;
-  // +256 B of slack after the last plane: window loops may prefetch one element past a row end.
-  PM_HIP(h, hipMalloc((void**)&h->img8, B * 4 * plane + 256));
-  PM_HIP(h, hipMalloc((void**)&h->g32, sizeof(float) * (B * 4 * plane + 64)));
-  PM_HIP(h, hipMalloc((void**)&h->g8, B * 4 * plane + 256));
+  // Zeroed: row padding ([cols, pitch)) and the slack behind the last plane (pm_handle.hpp: kSlack*) are read (with
+  // weight 0) by the paired bilinear loads and never written afterwards: they must hold finite values.
   const size_t plane_t = (size_t)(max_cols + kTransPad) * align_up(max_rows, 64);
-  PM_HIP(h, hipMalloc((void**)&h->timg8, B * 4 * plane_t + 256));
-  PM_HIP(h, hipMalloc((void**)&h->tg32, sizeof(float) * (B * 4 * plane_t + 64)));
-  PM_HIP(h, hipMalloc((void**)&h->tg8, B * 4 * plane_t + 256));
-  // Row padding ([cols, pitch)) and the slack behind the last plane are read (with weight 0) by the
-  // paired bilinear loads and never written afterwards: they must hold finite values.
-  PM_HIP(h, hipMemsetAsync(h->img8, 0, B * 4 * plane + 256, h->stream));
-  PM_HIP(h, hipMemsetAsync(h->g32, 0, sizeof(float) * (B * 4 * plane + 64), h->stream));
-  PM_HIP(h, hipMemsetAsync(h->g8, 0, B * 4 * plane + 256, h->stream));
-  PM_HIP(h, hipMemsetAsync(h->timg8, 0, B * 4 * plane_t + 256, h->stream));
-  PM_HIP(h, hipMemsetAsync(h->tg32, 0, sizeof(float) * (B * 4 * plane_t + 64), h->stream));
-  PM_HIP(h, hipMemsetAsync(h->tg8, 0, B * 4 * plane_t + 256, h->stream));
-  PM_HIP(h, hipMalloc((void**)&h->pk16, sizeof(uint16_t) * (B * 4 * plane + 128)));
-  PM_HIP(h, hipMalloc((void**)&h->tpk16, sizeof(uint16_t) * (B * 4 * plane_t + 128)));
-  PM_HIP(h, hipMemsetAsync(h->pk16, 0, sizeof(uint16_t) * (B * 4 * plane + 128), h->stream));
-  PM_HIP(h, hipMemsetAsync(h->tpk16, 0, sizeof(uint16_t) * (B * 4 * plane_t + 128), h->stream));
+  PM_HIP(h, h->img8.alloc_zeroed(B * 4 * plane + kSlackBytes, h->stream));
+  PM_HIP(h, h->g32.alloc_zeroed(sizeof(float) * (B * 4 * plane + kSlackElems), h->stream));
+  PM_HIP(h, h->g8.alloc_zeroed(B * 4 * plane + kSlackBytes, h->stream));
+  PM_HIP(h, h->timg8.alloc_zeroed(B * 4 * plane_t + kSlackBytes, h->stream));
+  PM_HIP(h, h->tg32.alloc_zeroed(sizeof(float) * (B * 4 * plane_t + kSlackElems), h->stream));
+  PM_HIP(h, h->tg8.alloc_zeroed(B * 4 * plane_t + kSlackBytes, h->stream));
+  PM_HIP(h, h->pk16.alloc_zeroed(sizeof(uint16_t) * (B * 4 * plane + kSlackPk16), h->stream));
+  PM_HIP(h, h->tpk16.alloc_zeroed(sizeof(uint16_t) * (B * 4 * plane_t + kSlackPk16), h->stream));
   if (pair_planes_wanted(h))
     if (int rc = pair_planes_alloc(h, h->stream)) return rc;
   const size_t splane = (size_t)align_up(max_rows, 4) * h->max_pitch;  // state planes: four rows interleaved (pm_device.hpp)
-  PM_HIP(h, hipMalloc((void**)&h->disp, sizeof(float) * (B * 2 * splane + 64)));
-  PM_HIP(h, hipMalloc((void**)&h->cost, sizeof(float) * (B * 2 * splane + 64)));
-  PM_HIP(h, hipMalloc((void**)&h->noise, sizeof(float) * (plane + 64)));
-  h->noise_capacity = plane;
-  PM_HIP(h, hipMalloc((void**)&h->counters, sizeof(unsigned long long) * 16));  // [8..13]: timing builds only
-  PM_HIP(h, hipMemsetAsync(h->counters, 0, sizeof(unsigned long long) * 16, h->stream));
+  // the cost planes are read only where the noise kernel wrote them; cleared once so that tools that scan whole planes
+  // never see uninitialised memory
+  PM_HIP(h, h->disp.alloc_zeroed(sizeof(float) * (B * 2 * splane + kSlackElems), h->stream));
+  PM_HIP(h, h->cost.alloc_zeroed(sizeof(float) * (B * 2 * splane + kSlackElems), h->stream));
+  PM_HIP(h, h->noise.alloc(sizeof(float) * (plane + kSlackElems)));
+  PM_HIP(h, h->counters.alloc_zeroed(sizeof(unsigned long long) * 16, h->stream));  // [8..13]: timing builds only
   if (int rc = alloc_seed_scratch(h, h->seeds[0], h->stream)) return rc;
   if (params->mode == PM_MODE_PLANES)
     if (int rc = planes_alloc(h, h->stream)) return rc;
   const size_t tight = (size_t)max_rows * max_cols;
   // one block: a single small pair goes up as ONE copy, left and right back to back (pm_hostpath.hip::pm_match_u8)
-  PM_HIP(h, hipMalloc((void**)&h->st_left, 2 * B * tight + 64));
+  PM_HIP(h, h->st_left.alloc(2 * B * tight + kStagingPadBytes));
   h->st_right = h->st_left + B * tight;
-  PM_HIP(h, hipMalloc((void**)&h->st_seed_l, sizeof(float) * B * tight));
-  PM_HIP(h, hipMalloc((void**)&h->st_seed_r, sizeof(float) * B * tight));
-  PM_HIP(h, hipMalloc((void**)&h->st_disp_l, sizeof(float) * B * tight));
-  PM_HIP(h, hipMalloc((void**)&h->st_disp_r, sizeof(float) * B * tight));
+  PM_HIP(h, h->st_seed_l.alloc(sizeof(float) * B * tight));
+  PM_HIP(h, h->st_seed_r.alloc(sizeof(float) * B * tight));
+  PM_HIP(h, h->st_disp_l.alloc(sizeof(float) * B * tight));
+  PM_HIP(h, h->st_disp_r.alloc(sizeof(float) * B * tight));
   // pinned host staging: per pair 2 u8 images + 2 seeds + 2 outputs (also used for the noise table)
   h->pinned_bytes = B * tight * (2 + 4 * sizeof(float));
   const size_t noise_bytes = sizeof(float) * plane;
@@ -1151,10 +1132,6 @@ int pm_create(const pm_params* params, int device, int max_rows, int max_cols, i
     if (hipHostGetDevicePointer(&dp, h->pinned, 0) == hipSuccess) h->pinned_dev = (char*)dp;
     (void)hipGetLastError();
   }
-  // the cost planes are read only where the noise kernel wrote them; clear once so that tools that
-  // scan whole planes never see uninitialised memory
-  PM_HIP(h, hipMemsetAsync(h->cost, 0, sizeof(float) * (B * 2 * splane + 64), h->stream));
-  PM_HIP(h, hipMemsetAsync(h->disp, 0, sizeof(float) * (B * 2 * splane + 64), h->stream));
   PM_HIP(h, hipStreamSynchronize(h->stream));
   return PM_OK;
 }
@@ -1211,6 +1188,9 @@ int pm_debug_capture_fork(pm_handle* h) {
   }
   return fork_stream(h, h->view_fork, h->stream, h->view1_stream);
 }
+
+long long pm_debug_live_device_allocations(void) { return pm::g_devbuf_allocations.load(); }
+long long pm_debug_live_device_bytes(void) { return pm::g_devbuf_bytes.load(); }
 
 int pm_replay(pm_handle* h) {
   if (!h || !h->graph_exec) {

@@ -19,6 +19,7 @@
 
 #include "pm/patchmatch.h"
 #include "pm_color.hpp"
+#include "pm_devbuf.hpp"
 #include "pm_device.hpp"
 #include "pm_hostcopy.hpp"
 #include "pm_seed_api.hpp"
@@ -48,49 +49,48 @@ struct pm_handle {
   hipStream_t stream = nullptr;
 
   // engine planes (see pm::PlaneSet)
-  uint8_t* img8 = nullptr;
-  float* g32 = nullptr;
-  uint8_t* g8 = nullptr;
-  uint8_t* timg8 = nullptr;  // transposed copies for the column sweeps
-  float* tg32 = nullptr;
-  uint8_t* tg8 = nullptr;
-  uint16_t* pk16 = nullptr;
-  uint16_t* tpk16 = nullptr;
-  float* rpg = nullptr;      // row / column PAIR planes of the run engine (pm::PlaneSet)
-  uint32_t* rqk = nullptr;
-  float* cpg = nullptr;
-  float* disp = nullptr;
-  float* cost = nullptr;
-  float* noise = nullptr;
-  unsigned long long* counters = nullptr;  // device, 8 words
+  pm::DevBuf<uint8_t> img8;
+  pm::DevBuf<float> g32;
+  pm::DevBuf<uint8_t> g8;
+  pm::DevBuf<uint8_t> timg8;  // transposed copies for the column sweeps
+  pm::DevBuf<float> tg32;
+  pm::DevBuf<uint8_t> tg8;
+  pm::DevBuf<uint16_t> pk16;
+  pm::DevBuf<uint16_t> tpk16;
+  pm::DevBuf<float> rpg;      // row / column PAIR planes of the run engine (pm::PlaneSet)
+  pm::DevBuf<uint32_t> rqk;
+  pm::DevBuf<float> cpg;
+  pm::DevBuf<float> disp;
+  pm::DevBuf<float> cost;
+  pm::DevBuf<float> noise;    // grows with the largest table asked for (pm_engine.hip::ensure_noise)
+  pm::DevBuf<unsigned long long> counters;  // device, 8 words
   bool counters_on = false;                // same-address atomics serialise: opt-in only
   int noise_rows = 0, noise_cols = 0, noise_pitch = 0;
 
   // PM_MODE_PLANES: [max_batch][2 views][a, b, z, cost][rows][pitch], f32 or f16 (pm_planes.hpp)
-  void* planes_state = nullptr;
+  pm::DevBuf<void> planes_state;
   int pl_rows = 0, pl_cols = 0, pl_n = 0;  // what pm_planes_begin last prepared
   bool pl_on = false;
 
   // scratch of the device seeder (pm_seed.hpp), one set per (lane, view): index lane * 2 + view.  Set 0 exists from
   // pm_create on, the others are allocated on first use (seeders of different views / lanes run side by side).
-  pm::SeedScratch seeds[8] = {};
+  pm::SeedScratch seeds[8];
   bool need_seed[2] = {false, false};  // set by pm_match_device: views whose seed map the device computes
 
   // row-tiled mode (pm_tile_*)
   bool tile_on = false;
   pm_tile tile{};
   int tile_band_rows = 0, tile_cols = 0;
-  float* snap_disp = nullptr;  // snapshot of the disparity / cost planes (2 views)
-  float* snap_cost = nullptr;
-  size_t noise_capacity = 0;   // floats allocated for the noise table
+  pm::DevBuf<float> snap_disp;  // snapshot of the disparity / cost planes (2 views)
+  pm::DevBuf<float> snap_cost;
 
   // staging for the host-buffer entry points: tightly packed [B][rows][cols]
-  uint8_t* st_left = nullptr;
-  uint8_t* st_right = nullptr;
-  float* st_seed_l = nullptr;
-  float* st_seed_r = nullptr;
-  float* st_disp_l = nullptr;
-  float* st_disp_r = nullptr;
+  pm::DevBuf<uint8_t> st_left;  // one block: left, then right
+  uint8_t* st_right = nullptr;  // into st_left's block
+  pm::DevBuf<float> st_seed_l;
+  pm::DevBuf<float> st_seed_r;
+  pm::DevBuf<float> st_disp_l;
+  pm::DevBuf<float> st_disp_r;
   void* pinned = nullptr;  // host staging, pinned
   size_t pinned_bytes = 0;
   char* pinned_dev = nullptr;  // the device's address of the staging slab (k_download writes the maps through it)
@@ -147,7 +147,7 @@ struct pm_handle {
   hipEvent_t out_join = nullptr;  // s_out -> the handle's stream at the end of a batch
   hipEvent_t in_join = nullptr;   // s_in -> the handle's stream (only when a capture is ended with the head stream unjoined)
   void* imaging_state = nullptr;  // owned by pm_imaging.hip (pm_internal.hpp)
-  void* texmask_scratch = nullptr;  // pm_foreground_texture_mask: four byte planes, allocated on first use
+  pm::DevBuf<void> texmask_scratch;  // pm_foreground_texture_mask: four byte planes, allocated on first use
   // pm_match_bgr_device: the next Match reads enhanced BGR inputs through k_prep_bgr instead of 8-bit gray images
   const pm::BgrSource* bgr = nullptr;
   hipGraphExec_t graph_exec = nullptr;  // pm_capture_* / pm_replay
@@ -193,6 +193,14 @@ void set_err(pm_handle* h, const char* fmt, ...) __attribute__((format(printf, 2
   } while (0)
 
 inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
+
+// Slack behind the last plane of an allocation, allocated and cleared with it: window loops may prefetch one element
+// past a row end, and the paired bilinear loads read it with weight 0.
+constexpr size_t kSlackBytes = 256;  // byte planes
+constexpr size_t kSlackElems = 64;   // float planes, state planes, the noise table
+constexpr size_t kSlackPk16 = 128;   // packed 16-bit planes
+// not that slack: spare bytes behind the tight u8 staging block (left, right) -- a guard, never cleared, nothing reads it
+constexpr size_t kStagingPadBytes = 64;
 
 // Every stream of the engine is created through this.  PM_STREAM_PRIO = "main,view,copy,lane" (read once; one number
 // = all four): the priority class of the handle's stream, the second view's stream, the upload / download streams and

@@ -536,12 +536,12 @@ int pm_match_u8(pm_handle* h, const uint8_t* left, const uint8_t* right, int row
   const size_t span = span_bytes(rows, image_step, (size_t)cols);
   char* slab_dev = (px % 16 == 0 && 2 * px <= kSmallPairBytes && !host_pinned(h, left, span) && !host_pinned(h, right, span))
                        ? host_dev_address(h, ps.l, 2 * px) : nullptr;
-  if (slab_dev && ((uintptr_t)slab_dev % 16) == 0 && ((uintptr_t)h->st_left % 16) == 0) {
+  if (slab_dev && ((uintptr_t)slab_dev % 16) == 0 && ((uintptr_t)h->st_left.get() % 16) == 0) {
     h->copy_pool->Copy2D(ps.l, (size_t)cols, left, image_step, (size_t)cols, rows);
     h->copy_pool->Copy2D(ps.r, (size_t)cols, right, image_step, (size_t)cols, rows);
     d_right = h->st_left + px;
     const int words = (int)(2 * px / sizeof(float));
-    launch_upload(h, (float*)h->st_left, (const float*)slab_dev, words, h->stream);
+    launch_upload(h, (float*)h->st_left.get(), (const float*)slab_dev, words, h->stream);
     if (int rc = launch_check(h, "upload")) return rc;
   } else {
     if (int rc = upload_plane(h, h->st_left, left, image_step, (size_t)cols, rows, ps.l, h->stream)) return rc;

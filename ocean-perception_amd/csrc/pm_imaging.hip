@@ -5,12 +5,14 @@
 
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <new>
 #include <vector>
 
+#include "pm_devbuf.hpp"
 #include "pm_enhance.hpp"
 #include "pm_guided.hpp"
 #include "pm_imaging.hpp"
@@ -22,30 +24,25 @@ using namespace pm;
 
 namespace {
 
-// Device state of the imaging entry points, created on first use and released by pm_destroy.
+// Device state of the imaging entry points, created on first use and released by pm_destroy.  The scratch buffers grow
+// to the largest size asked for (DevBuf::reserve).
 struct ImagingState {
-  unsigned* img_scalars = nullptr;  // device: [0] max range / min disparity bits, [1] dark-pixel count, [2..3] V min / max
+  DevBuf<unsigned> img_scalars;  // device: [0] max range / min disparity bits, [1] dark-pixel count, [2..3] V min / max
   // stereo-ready enhancement: row-pass output, bgr / illuminant, Gaussian taps
-  float* enh_tmp = nullptr;
-  float* enh_q = nullptr;
-  float* enh_taps = nullptr;
-  size_t enh_values = 0;  // floats allocated in enh_tmp / enh_q
-  // pm_match_bgr_device: blurred illuminants of n pairs (left, right) and their value min / max words
-  float* bgr_blur = nullptr;
-  unsigned* bgr_mm = nullptr;
-  size_t bgr_values = 0;  // floats allocated in bgr_blur
-  int bgr_pairs = 0;      // pairs bgr_mm holds
-  int enh_taps_cap = 0, enh_ksize = 0;
+  DevBuf<float> enh_tmp;
+  DevBuf<float> enh_q;
+  DevBuf<float> enh_taps;
+  int enh_ksize = 0;  // what enh_taps holds
   double enh_sigma = 0;
+  // pm_match_bgr_device: blurred illuminants of n pairs (left, right) and their value min / max words
+  DevBuf<float> bgr_blur;
+  DevBuf<unsigned> bgr_mm;
   // fast guided filter: binary64 row sums, a / b planes, interleaved mean_a / mean_b of the coarse image (one allocation)
-  void* gf_buf = nullptr;
-  size_t gf_bytes = 0;
+  DevBuf<char> gf_buf;
   // pm_gather_pixels: [bad flag, pad][n x channels floats][n x 2 coordinates]
-  void* gat_buf = nullptr;
-  size_t gat_bytes = 0;
+  DevBuf<char> gat_buf;
   // pm_match_raw_device: the rectified pairs, [left, right][n][rows][cols] bytes
-  void* rect_buf = nullptr;
-  size_t rect_bytes = 0;
+  DevBuf<uint8_t> rect_buf;
 };
 
 #define PM_HIP(h, call)                                                                                     \
@@ -78,13 +75,7 @@ ImagingState* state_of(pm_handle* h) {
 
 void pm_internal::release_imaging(pm_handle* h) {
   void** slot = pm_internal::imaging_slot(h);
-  ImagingState* st = static_cast<ImagingState*>(*slot);
-  if (!st) return;
-  void* dev[] = {st->img_scalars, st->enh_tmp, st->enh_q, st->enh_taps, st->bgr_blur, st->bgr_mm, st->gf_buf, st->gat_buf,
-                 st->rect_buf};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  delete st;
+  delete static_cast<ImagingState*>(*slot);
   *slot = nullptr;
 }
 
@@ -102,10 +93,7 @@ int imaging_begin(pm_handle* h, const char* what, const void* a, const void* b, 
     set_err(h, "%s: out of host memory", what);
     return PM_ERR_NOMEM;
   }
-  if (!state_of(h)->img_scalars) {
-    PM_HIP(h, hipMalloc((void**)&state_of(h)->img_scalars, sizeof(unsigned) * 4));
-    PM_HIP(h, hipMemsetAsync(state_of(h)->img_scalars, 0, sizeof(unsigned) * 4, pm_internal::stream(h)));
-  }
+  if (!state_of(h)->img_scalars) PM_HIP(h, state_of(h)->img_scalars.alloc_zeroed(sizeof(unsigned) * 4, pm_internal::stream(h)));
   return PM_OK;
 }
 
@@ -266,14 +254,11 @@ namespace {
 
 // cv::getGaussianKernel(n, sigma, CV_32F), uploaded once per (n, sigma)
 int ensure_taps(pm_handle* h, int ksize, double sigma) {
-  if (state_of(h)->enh_ksize == ksize && state_of(h)->enh_sigma == sigma && state_of(h)->enh_taps) return PM_OK;
-  if (ksize > state_of(h)->enh_taps_cap) {
-    PM_HIP(h, hipStreamSynchronize(pm_internal::stream(h)));
-    if (state_of(h)->enh_taps) PM_HIP(h, hipFree(state_of(h)->enh_taps));
-    state_of(h)->enh_taps = nullptr;
-    PM_HIP(h, hipMalloc((void**)&state_of(h)->enh_taps, sizeof(float) * (size_t)ksize));
-    state_of(h)->enh_taps_cap = ksize;
-  }
+  ImagingState* st = state_of(h);
+  if (st->enh_ksize == ksize && st->enh_sigma == sigma && st->enh_taps) return PM_OK;
+  bool gone = false;
+  PM_HIP(h, st->enh_taps.reserve(sizeof(float) * (size_t)ksize, pm_internal::stream(h), &gone));
+  if (gone) st->enh_ksize = 0;  // the cached taps went with the old buffer
   std::vector<float> k((size_t)ksize);
   const double scale2x = -0.5 / (sigma * sigma);
   double sum = 0;
@@ -285,22 +270,15 @@ int ensure_taps(pm_handle* h, int ksize, double sigma) {
   sum = 1. / sum;
   for (int i = 0; i < ksize; ++i) k[(size_t)i] = (float)(k[(size_t)i] * sum);
   PM_HIP(h, hipStreamSynchronize(pm_internal::stream(h)));  // the previous taps may still be in use
-  PM_HIP(h, hipMemcpy(state_of(h)->enh_taps, k.data(), sizeof(float) * (size_t)ksize, hipMemcpyHostToDevice));
-  state_of(h)->enh_ksize = ksize;
-  state_of(h)->enh_sigma = sigma;
+  PM_HIP(h, hipMemcpy(st->enh_taps, k.data(), sizeof(float) * (size_t)ksize, hipMemcpyHostToDevice));
+  st->enh_ksize = ksize;
+  st->enh_sigma = sigma;
   return PM_OK;
 }
 
 int ensure_enh_scratch(pm_handle* h, size_t values) {
-  if (values <= state_of(h)->enh_values) return PM_OK;
-  PM_HIP(h, hipStreamSynchronize(pm_internal::stream(h)));
-  if (state_of(h)->enh_tmp) PM_HIP(h, hipFree(state_of(h)->enh_tmp));
-  if (state_of(h)->enh_q) PM_HIP(h, hipFree(state_of(h)->enh_q));
-  state_of(h)->enh_tmp = state_of(h)->enh_q = nullptr;
-  state_of(h)->enh_values = 0;
-  PM_HIP(h, hipMalloc((void**)&state_of(h)->enh_tmp, sizeof(float) * values));
-  PM_HIP(h, hipMalloc((void**)&state_of(h)->enh_q, sizeof(float) * values));
-  state_of(h)->enh_values = values;
+  PM_HIP(h, state_of(h)->enh_tmp.reserve(sizeof(float) * values, pm_internal::stream(h)));
+  PM_HIP(h, state_of(h)->enh_q.reserve(sizeof(float) * values, pm_internal::stream(h)));
   return PM_OK;
 }
 
@@ -346,22 +324,12 @@ int run_gaussian_batch(pm_handle* h, const void* const* d_src, float* const* d_d
   const int c = ksize / 2;
   int W = 0, T = 0, NT = 256;
   {
-    static const int forced[3] = {[] {
-      const char* e = pm::tune_env("PM_BLUR_COL");  // "W,T,threads" (experiments)
+    static const std::array<int, 3> forced = [] {  // PM_BLUR_COL = "W,T,threads" (experiments), read once
       int w = 0, t = 0, n = 0;
-      if (e && sscanf(e, "%d,%d,%d", &w, &t, &n) == 3) return w;
-      return 0;
-    }(), [] {
       const char* e = pm::tune_env("PM_BLUR_COL");
-      int w = 0, t = 0, n = 0;
-      if (e && sscanf(e, "%d,%d,%d", &w, &t, &n) == 3) return t;
-      return 0;
-    }(), [] {
-      const char* e = pm::tune_env("PM_BLUR_COL");
-      int w = 0, t = 0, n = 0;
-      if (e && sscanf(e, "%d,%d,%d", &w, &t, &n) == 3) return n;
-      return 0;
-    }()};
+      if (e && sscanf(e, "%d,%d,%d", &w, &t, &n) == 3) return std::array<int, 3>{w, t, n};
+      return std::array<int, 3>{0, 0, 0};
+    }();
     auto lds_of = [&](int w, int t) { return sizeof(float) * ((size_t)(t + 2 * c + 3) * (w + 2) + c + 1); };
     if (forced[0]) {
       W = forced[0];
@@ -460,20 +428,8 @@ int pm_match_bgr_device(pm_handle* h, int n, const uint8_t* d_left_bgr8, const u
   }
   ImagingState* st = state_of(h);
   const size_t ipx = (size_t)rows * cols, values = ipx * 3;
-  if (st->bgr_values < values * 2 * (size_t)n) {
-    if (st->bgr_blur) PM_HIP(h, hipFree(st->bgr_blur));
-    st->bgr_blur = nullptr;
-    st->bgr_values = 0;
-    PM_HIP(h, hipMalloc((void**)&st->bgr_blur, sizeof(float) * values * 2 * (size_t)n));
-    st->bgr_values = values * 2 * (size_t)n;
-  }
-  if (st->bgr_pairs < n) {
-    if (st->bgr_mm) PM_HIP(h, hipFree(st->bgr_mm));
-    st->bgr_mm = nullptr;
-    st->bgr_pairs = 0;
-    PM_HIP(h, hipMalloc((void**)&st->bgr_mm, sizeof(unsigned) * 8 * (size_t)n));
-    st->bgr_pairs = n;
-  }
+  PM_HIP(h, st->bgr_blur.reserve(sizeof(float) * values * 2 * (size_t)n, pm_internal::stream(h)));
+  PM_HIP(h, st->bgr_mm.reserve(sizeof(unsigned) * 8 * (size_t)n, pm_internal::stream(h)));
   // NormalizeColorIlluminant (normalization.cpp:178-185): ksize = NextOddInt(cols / 3), sigma = (float)ksize / 4
   const int third = cols / 3;
   const int ksize = third + (1 - third % 2);
@@ -534,17 +490,6 @@ int pm_normalize_color_illuminant(pm_handle* h, const float* d_bgr, int rows, in
 // ---- fast guided filter with a one-channel guide, and the pixel gather (pm_guided.hpp) -----------------------------
 namespace {
 
-int ensure_bytes(pm_handle* h, void** buf, size_t* have, size_t want) {
-  if (want <= *have) return PM_OK;
-  PM_HIP(h, hipStreamSynchronize(pm_internal::stream(h)));  // the old buffer may still be in use
-  if (*buf) PM_HIP(h, hipFree(*buf));
-  *buf = nullptr;
-  *have = 0;
-  PM_HIP(h, hipMalloc(buf, want));
-  *have = want;
-  return PM_OK;
-}
-
 int run_guided_filter(pm_handle* h, const char* what, const float* d_guide, const float* d_src, int rows, int cols,
                       int channels, int r, double eps, int s, float scale, float* d_dst) {
   if (int rc = imaging_begin(h, what, d_guide, d_src, rows, cols)) return rc;
@@ -584,11 +529,11 @@ int run_guided_filter(pm_handle* h, const char* what, const float* d_guide, cons
   const size_t cpx = (size_t)g.crows * g.ccols;
   const int planes1 = 2 + 2 * channels, planes2 = 2 * channels;
   const size_t sum_bytes = sizeof(double) * cpx * planes1, ab_bytes = sizeof(float) * cpx * planes2;
-  if (int rc = ensure_bytes(h, &st->gf_buf, &st->gf_bytes, sum_bytes + 2 * ab_bytes)) return rc;
-  double* rowsum = (double*)st->gf_buf;
-  float* ab = (float*)((char*)st->gf_buf + sum_bytes);
-  float* mean = (float*)((char*)st->gf_buf + sum_bytes + ab_bytes);
   hipStream_t stream = pm_internal::stream(h);
+  PM_HIP(h, st->gf_buf.reserve(sum_bytes + 2 * ab_bytes, stream));
+  double* rowsum = (double*)st->gf_buf.get();
+  float* ab = (float*)(st->gf_buf + sum_bytes);
+  float* mean = (float*)(st->gf_buf + sum_bytes + ab_bytes);
   const dim3 cgrid((unsigned)((cpx + 127) / 128), (unsigned)channels);
   hipLaunchKernelGGL((k_gf_box_rows<true>), dim3((unsigned)g.crows, (unsigned)planes1), dim3(256), row_lds, stream, d_guide,
                      d_src, (const float*)nullptr, g, rowsum);
@@ -639,13 +584,13 @@ int pm_gather_pixels(pm_handle* h, const float* d_img, int rows, int cols, int c
   if (n == 0) return PM_OK;
   ImagingState* st = state_of(h);
   const size_t head = 16, val_bytes = sizeof(float) * (size_t)n * channels, xy_bytes = sizeof(int32_t) * 2 * (size_t)n;
-  if (int rc = ensure_bytes(h, &st->gat_buf, &st->gat_bytes, head + val_bytes + xy_bytes)) return rc;
   hipStream_t stream = pm_internal::stream(h);
-  unsigned* d_bad = (unsigned*)st->gat_buf;
-  float* d_val = (float*)((char*)st->gat_buf + head);
+  PM_HIP(h, st->gat_buf.reserve(head + val_bytes + xy_bytes, stream));
+  unsigned* d_bad = (unsigned*)st->gat_buf.get();
+  float* d_val = (float*)(st->gat_buf + head);
   const int32_t* d_coords = d_xy;
   if (xy) {
-    int32_t* d_copy = (int32_t*)((char*)st->gat_buf + head + val_bytes);
+    int32_t* d_copy = (int32_t*)(st->gat_buf + head + val_bytes);
     PM_HIP(h, hipMemcpyAsync(d_copy, xy, xy_bytes, hipMemcpyHostToDevice, stream));
     d_coords = d_copy;
   }
@@ -785,10 +730,10 @@ int pm_match_raw_device(pm_handle* h, int n, const pm_rectify_view* left, const 
     return PM_ERR_NOMEM;
   }
   const size_t side = (size_t)n * rows * cols;
-  if (int rc = ensure_bytes(h, &st->rect_buf, &st->rect_bytes, 2 * side)) return rc;
-  uint8_t* rect_l = (uint8_t*)st->rect_buf;
-  uint8_t* rect_r = rect_l + side;
   hipStream_t stream = pm_internal::stream(h);
+  PM_HIP(h, st->rect_buf.reserve(2 * side, stream));
+  uint8_t* rect_l = st->rect_buf;
+  uint8_t* rect_r = rect_l + side;
   launch_rectify(*left, d_left_raw, n, src_rows, src_cols, src_step, rows, cols, 0, rect_l, nullptr, stream);
   launch_rectify(*right, d_right_raw, n, src_rows, src_cols, src_step, rows, cols, 0, rect_r, nullptr, stream);
   if (int rc = launch_check(h, "rectify")) return rc;

@@ -240,8 +240,8 @@ extern "C" int pm_foreground_texture_mask(pm_handle* h, const uint8_t* d_gray, i
   }
   PM_HIP(h, hipSetDevice(h->device));
   const size_t plane = (size_t)h->max_rows * h->max_cols;
-  if (!h->texmask_scratch) PM_HIP(h, hipMalloc(&h->texmask_scratch, 4 * plane));
-  uint8_t* small = (uint8_t*)h->texmask_scratch;
+  if (!h->texmask_scratch) PM_HIP(h, h->texmask_scratch.alloc(4 * plane));
+  uint8_t* small = (uint8_t*)h->texmask_scratch.get();
   uint8_t* lo = small + plane;
   uint8_t* hi = lo + plane;
   uint8_t* bin = hi + plane;

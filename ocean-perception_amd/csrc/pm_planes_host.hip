@@ -65,9 +65,7 @@ int planes_alloc(pm_handle* h, hipStream_t stream) {
     }
   }
   const size_t plane = (size_t)h->max_rows * h->max_pitch;
-  const size_t bytes = sizeof(float) * ((size_t)h->max_batch * 2 * 4 * plane + 64);
-  PM_HIP(h, hipMalloc(&h->planes_state, bytes));
-  PM_HIP(h, hipMemsetAsync(h->planes_state, 0, bytes, stream));
+  PM_HIP(h, h->planes_state.alloc_zeroed(sizeof(float) * ((size_t)h->max_batch * 2 * 4 * plane + kSlackElems), stream));
   return PM_OK;
 }
 
@@ -93,7 +91,7 @@ int planes_stage(pm_handle* h, const PlaneSet& ps0, const PlArgs& ar, int slots,
   const bool f16 = h->params.state_dtype == PM_STATE_F16;
   const PlaneSet ps = pair0 ? plane_set_of_pair(ps0, pair0) : ps0;
   // PlaneState::arr: a pair holds 2 views x 4 arrays of `plane` elements
-  char* state = (char*)h->planes_state + (size_t)pair0 * 8 * ps0.plane * (f16 ? sizeof(_Float16) : sizeof(float));
+  char* state = (char*)h->planes_state.get() + (size_t)pair0 * 8 * ps0.plane * (f16 ? sizeof(_Float16) : sizeof(float));
   const hipError_t e = pl_launch<STAGE>(ps, state, f16, planes_params(h->params), ar, slots, stream);
   if (e != hipSuccess) {
     set_err(h, "launch of planes %s failed: %s", what, hipGetErrorString(e));
@@ -179,11 +177,11 @@ int planes_finish(pm_handle* h, float* d_disp_l, float* d_disp_r, hipStream_t st
   const PlanesParams pp = planes_params(h->params);
   Launch l(h, PM_K_FINALIZE, stream);
   if (h->params.state_dtype == PM_STATE_F16) {
-    PlaneState<_Float16> st{(_Float16*)h->planes_state, ps.plane, ps.pitch / 2};
+    PlaneState<_Float16> st{(_Float16*)h->planes_state.get(), ps.plane, ps.pitch / 2};
     hipLaunchKernelGGL(k_planes_finish<_Float16>, pixel_grid(ps.cols, ps.rows, h->pl_n), dim3(256), 0, stream, ps,
                        st, pp, d_disp_l, d_disp_r, (size_t)ps.cols);
   } else {
-    PlaneState<float> st{(float*)h->planes_state, ps.plane, ps.pitch / 2};
+    PlaneState<float> st{(float*)h->planes_state.get(), ps.plane, ps.pitch / 2};
     hipLaunchKernelGGL(k_planes_finish<float>, pixel_grid(ps.cols, ps.rows, h->pl_n), dim3(256), 0, stream, ps, st,
                        pp, d_disp_l, d_disp_r, (size_t)ps.cols);
   }
@@ -291,18 +289,18 @@ static int planes_rw(pm_handle* h, int pair, int view, float* planes, int to_sta
   const size_t count = 4 * (size_t)ps.rows * ps.cols;
   // staged through the disparity staging buffers (4 * rows * cols floats fit st_disp_l .. only when max_batch
   // allows; a scratch allocation keeps this tool path independent of the plan)
-  float* d_buf = nullptr;
-  PM_HIP(h, hipMalloc((void**)&d_buf, sizeof(float) * count));
+  DevBuf<float> d_buf;  // released on every path out, after the synchronise below
+  PM_HIP(h, d_buf.alloc(sizeof(float) * count));
   int rc = PM_OK;
   if (to_state && hipMemcpyAsync(d_buf, planes, sizeof(float) * count, hipMemcpyHostToDevice, h->stream) != hipSuccess)
     rc = PM_ERR_HIP;
   if (rc == PM_OK) {
     const dim3 grid((unsigned)((ps.cols + 255) / 256), (unsigned)ps.rows, 4);
     if (h->params.state_dtype == PM_STATE_F16) {
-      PlaneState<_Float16> st{(_Float16*)h->planes_state, ps.plane, ps.pitch / 2};
+      PlaneState<_Float16> st{(_Float16*)h->planes_state.get(), ps.plane, ps.pitch / 2};
       hipLaunchKernelGGL(k_planes_copy<_Float16>, grid, dim3(256), 0, h->stream, ps, st, pair, view, d_buf, to_state);
     } else {
-      PlaneState<float> st{(float*)h->planes_state, ps.plane, ps.pitch / 2};
+      PlaneState<float> st{(float*)h->planes_state.get(), ps.plane, ps.pitch / 2};
       hipLaunchKernelGGL(k_planes_copy<float>, grid, dim3(256), 0, h->stream, ps, st, pair, view, d_buf, to_state);
     }
     rc = launch_check(h, what);
@@ -311,7 +309,6 @@ static int planes_rw(pm_handle* h, int pair, int view, float* planes, int to_sta
       hipMemcpyAsync(planes, d_buf, sizeof(float) * count, hipMemcpyDeviceToHost, h->stream) != hipSuccess)
     rc = PM_ERR_HIP;
   if (hipStreamSynchronize(h->stream) != hipSuccess && rc == PM_OK) rc = PM_ERR_HIP;
-  (void)hipFree(d_buf);
   if (rc == PM_ERR_HIP && !h->err[0]) set_err(h, "%s: copy failed", what);
   return rc;
 }

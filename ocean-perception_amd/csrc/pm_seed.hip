@@ -8,24 +8,19 @@ namespace pm {
 
 hipError_t seed_scratch_alloc(SeedScratch& sc, size_t plane_elems, hipStream_t stream) {
   hipError_t e;
-  sc.cap = (int)(plane_elems + 64);
-  if ((e = hipMalloc((void**)&sc.eig, sizeof(float) * plane_elems)) != hipSuccess) return e;
-  if ((e = hipMalloc((void**)&sc.keys, sizeof(unsigned long long) * sc.cap)) != hipSuccess) return e;
-  if ((e = hipMalloc((void**)&sc.keys_sorted, sizeof(unsigned long long) * sc.cap)) != hipSuccess) return e;
-  if ((e = hipMalloc((void**)&sc.counters, sizeof(unsigned) * kSeedCounters)) != hipSuccess) return e;
-  if ((e = hipMalloc((void**)&sc.kp_xy, sizeof(int) * 2 * kSeedMaxFeatures)) != hipSuccess) return e;
-  if ((e = hipMalloc((void**)&sc.kp_d, sizeof(float) * kSeedMaxFeatures)) != hipSuccess) return e;
-  if ((e = hipMalloc((void**)&sc.kp_f, sizeof(float) * 2 * kSeedMaxFeatures)) != hipSuccess) return e;
-  sc.sp_buf = nullptr;   // allocated with the masks, only for handles that ask for cornerSubPix (seed_subpix_prepare)
-  sc.sp_mask = nullptr;
-  sc.sp_mask_win = sc.sp_mask_zero = 0;
-  sc.sort_tmp = nullptr;
-  sc.sort_tmp_bytes = 0;
+  sc.cap = (int)(plane_elems + kSeedCapExtra);
+  if ((e = sc.eig.alloc(sizeof(float) * plane_elems)) != hipSuccess) return e;
+  if ((e = sc.keys.alloc(sizeof(unsigned long long) * sc.cap)) != hipSuccess) return e;
+  if ((e = sc.keys_sorted.alloc(sizeof(unsigned long long) * sc.cap)) != hipSuccess) return e;
+  if ((e = sc.counters.alloc(sizeof(unsigned) * kSeedCounters)) != hipSuccess) return e;
+  if ((e = sc.kp_xy.alloc(sizeof(int) * 2 * kSeedMaxFeatures)) != hipSuccess) return e;
+  if ((e = sc.kp_d.alloc(sizeof(float) * kSeedMaxFeatures)) != hipSuccess) return e;
+  if ((e = sc.kp_f.alloc(sizeof(float) * 2 * kSeedMaxFeatures)) != hipSuccess) return e;
   sc.counters_clean = false;
-  if ((e = hipcub::DeviceRadixSort::SortKeysDescending(nullptr, sc.sort_tmp_bytes, sc.keys, sc.keys_sorted, sc.cap, 0, 64,
-                                                       stream)) != hipSuccess)
+  if ((e = hipcub::DeviceRadixSort::SortKeysDescending(nullptr, sc.sort_tmp_bytes, sc.keys.get(), sc.keys_sorted.get(),
+                                                       sc.cap, 0, 64, stream)) != hipSuccess)
     return e;
-  return hipMalloc(&sc.sort_tmp, sc.sort_tmp_bytes);
+  return sc.sort_tmp.alloc(sc.sort_tmp_bytes);
 }
 
 // cornerSubPix needs its two window masks (computed on the HOST: std::exp of the C library, the function the oracle and
@@ -35,8 +30,8 @@ hipError_t seed_subpix_prepare(SeedScratch& sc, const SeedParams& sp, hipStream_
   hipError_t e;
   if (!sc.sp_buf) {
     const size_t side = 2 * kSubpixMaxWin + 3;
-    if ((e = hipMalloc((void**)&sc.sp_buf, sizeof(float) * side * side * kSeedMaxFeatures)) != hipSuccess) return e;
-    if ((e = hipMalloc((void**)&sc.sp_mask, sizeof(float) * 2 * kSubpixMaskStride)) != hipSuccess) return e;
+    if ((e = sc.sp_buf.alloc(sizeof(float) * side * side * kSeedMaxFeatures)) != hipSuccess) return e;
+    if ((e = sc.sp_mask.alloc(sizeof(float) * 2 * kSubpixMaskStride)) != hipSuccess) return e;
     sc.sp_mask_win = 0;
   }
   if (sc.sp_mask_win == sp.subpix_winsize && sc.sp_mask_zero == sp.subpix_zerozone) return hipSuccess;
@@ -62,13 +57,6 @@ hipError_t seed_subpix_prepare(SeedScratch& sc, const SeedParams& sp, hipStream_
   sc.sp_mask_win = sp.subpix_winsize;
   sc.sp_mask_zero = sp.subpix_zerozone;
   return hipSuccess;
-}
-
-void seed_scratch_free(SeedScratch& sc) {
-  void* dev[] = {sc.eig, sc.keys, sc.keys_sorted, sc.counters, sc.kp_xy, sc.kp_d, sc.kp_f, sc.sp_buf, sc.sp_mask, sc.sort_tmp};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  sc = SeedScratch{};
 }
 
 }  // namespace pm

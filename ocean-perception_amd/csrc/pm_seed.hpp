@@ -985,8 +985,8 @@ static hipError_t seed_map(const SeedScratch& sc, const SeedParams& sp, const ui
                        sc.cap, md, maxf, sp.quality_level, gx, gy, sc.kp_xy, sc.counters);
   } else if (stages & 4u) {
     size_t tmp_bytes = sc.sort_tmp_bytes;
-    if ((e = hipcub::DeviceRadixSort::SortKeysDescending(sc.sort_tmp, tmp_bytes, sc.keys, sc.keys_sorted, sc.cap, 0, 64,
-                                                         stream)) != hipSuccess)
+    if ((e = hipcub::DeviceRadixSort::SortKeysDescending(sc.sort_tmp, tmp_bytes, sc.keys.get(), sc.keys_sorted.get(),
+                                                         sc.cap, 0, 64, stream)) != hipSuccess)
       return e;
     const size_t grid_bytes = (size_t)gx * gy * 4 * sizeof(int);
     if (packed_ok && grid_bytes <= 150 * 1024) {  // LDS capacity

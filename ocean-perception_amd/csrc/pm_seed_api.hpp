@@ -1,11 +1,13 @@
 // pm_seed_api.hpp -- what the engine sees of the device seeder (pm_seed.hpp holds the kernels, pm_seed.hip is their
-// translation unit): parameters, the scratch a handle owns, and the enqueue-only entry points.
+// translation unit): parameters, the scratch a handle owns (released with it), and the enqueue-only entry points.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
+
+#include "pm_devbuf.hpp"
 
 namespace pm {
 
@@ -25,34 +27,35 @@ constexpr int kSubpixMatchWin = 10;     // StereoMatcher's fixed window (stereo_
 
 constexpr int kSeedMaxFeatures = 1024;  // capacity of the accepted-corner list
 constexpr int kSeedCounters = 8;        // SeedScratch::counters
+constexpr int kSeedCapExtra = 64;       // candidate slots beyond one per pixel (SeedScratch::cap; no plane slack)
 constexpr int kSubpixMaskStride = 1024;  // floats between the two masks of SeedScratch::sp_mask (31 * 31 = 961)
 
 // Scratch owned by the handle (sized for max_rows x max_cols).
 struct SeedScratch {
-  float* eig;                // [rows][pitch]
-  unsigned long long* keys;  // [cap] candidates, then sorted
-  unsigned long long* keys_sorted;
-  unsigned* counters;        // [kSeedCounters]: [0] = max response bits, [1] = candidate count, [2] = accepted
-                             // count, [3] = grid overflow flag
-  int* kp_xy;                // [kSeedMaxFeatures][2]
-  float* kp_d;               // [kSeedMaxFeatures] matched disparity of a corner, < 0 = no match
-  float* kp_f;               // [kSeedMaxFeatures][2] sub-pixel corner positions (subpixel_corners)
-  float* sp_buf;             // cornerSubPix neighbourhoods, [(2 * kSubpixMaxWin + 3)^2][kSeedMaxFeatures]
-  float* sp_mask;            // window masks: detector's [(2 w + 1)^2] at 0, matcher's [21 * 21] at kSubpixMaskStride
-  int sp_mask_win, sp_mask_zero;  // what the detector's mask was built for
-  void* sort_tmp;
-  size_t sort_tmp_bytes;
-  int cap;
+  DevBuf<float> eig;                 // [rows][pitch]
+  DevBuf<unsigned long long> keys;   // [cap] candidates, then sorted
+  DevBuf<unsigned long long> keys_sorted;
+  DevBuf<unsigned> counters;         // [kSeedCounters]: [0] = max response bits, [1] = candidate count, [2] = accepted
+                                     // count, [3] = grid overflow flag
+  DevBuf<int> kp_xy;                 // [kSeedMaxFeatures][2]
+  DevBuf<float> kp_d;                // [kSeedMaxFeatures] matched disparity of a corner, < 0 = no match
+  DevBuf<float> kp_f;                // [kSeedMaxFeatures][2] sub-pixel corner positions (subpixel_corners)
+  // only for handles that ask for cornerSubPix (seed_subpix_prepare):
+  DevBuf<float> sp_buf;              // neighbourhoods, [(2 * kSubpixMaxWin + 3)^2][kSeedMaxFeatures]
+  DevBuf<float> sp_mask;             // window masks: detector's [(2 w + 1)^2] at 0, matcher's [21 * 21] at kSubpixMaskStride
+  int sp_mask_win = 0, sp_mask_zero = 0;  // what the detector's mask was built for
+  DevBuf<void> sort_tmp;
+  size_t sort_tmp_bytes = 0;         // what hipcub asked for (it takes the size as an argument)
+  int cap = 0;
   // the selection kernels leave counters[0], [1] and [3] at zero for the next map; false after an allocation or an
   // enqueue that did not get as far as the selection: the next map then starts with a memset
-  mutable bool counters_clean;
+  mutable bool counters_clean = false;
 };
 
 // Allocates the scratch for planes of `plane_elems` pixels (rows x pitch of the plan).  Every pixel can be a candidate:
 // the 3x3 test is not strict, so plateaus of EQUAL responses (periodic images) pass whole; a capacity of a quarter of the
 // pixels dropped candidates there in whatever order the atomics fell.
 hipError_t seed_scratch_alloc(SeedScratch& sc, size_t plane_elems, hipStream_t stream);
-void seed_scratch_free(SeedScratch& sc);
 // the masks and the neighbourhood buffer of cv::cornerSubPix, for handles whose parameters ask for it (synchronises
 // the stream when it has to upload the masks: call outside captures)
 hipError_t seed_subpix_prepare(SeedScratch& sc, const SeedParams& sp, hipStream_t stream);

@@ -143,13 +143,18 @@ static int tile_sweep(pm_handle* h, int it, int k, const int* d_mask) {
   return run_sweep(h, ps, cp, g, ps.n_views, p.noise_amp[it], h->stream);
 }
 
+// the snapshot planes of the plan's two views, on first use
+static int snapshot_alloc(pm_handle* h) {
+  if (h->snap_disp) return PM_OK;
+  const size_t plane = (size_t)align_up(h->max_rows, 4) * h->max_pitch;  // state planes (pm_device.hpp::state_at)
+  PM_HIP(h, h->snap_disp.alloc(sizeof(float) * 2 * plane));
+  PM_HIP(h, h->snap_cost.alloc(sizeof(float) * 2 * plane));
+  return PM_OK;
+}
+
 int pm_tile_snapshot(pm_handle* h) {
   if (int rc = tile_check(h, "pm_tile_snapshot")) return rc;
-  const size_t plane = (size_t)align_up(h->max_rows, 4) * h->max_pitch;  // state planes (pm_device.hpp::state_at)
-  if (!h->snap_disp) {
-    PM_HIP(h, hipMalloc((void**)&h->snap_disp, sizeof(float) * 2 * plane));
-    PM_HIP(h, hipMalloc((void**)&h->snap_cost, sizeof(float) * 2 * plane));
-  }
+  if (int rc = snapshot_alloc(h)) return rc;
   const PlaneSet ps = tile_plane_set(h);
   const size_t bytes = sizeof(float) * ps.splane * ps.n_views;
   PM_HIP(h, hipMemcpyAsync(h->snap_disp, h->disp, bytes, hipMemcpyDeviceToDevice, h->stream));
@@ -165,11 +170,7 @@ int pm_tile_presweep(pm_handle* h, int pred_image_row, const float* d_row) {
     set_err(h, "pm_tile_presweep: row %d outside the band", pred_image_row);
     return PM_ERR_INVALID_ARG;
   }
-  const size_t plane = (size_t)align_up(h->max_rows, 4) * h->max_pitch;  // state planes (pm_device.hpp::state_at)
-  if (!h->snap_disp) {
-    PM_HIP(h, hipMalloc((void**)&h->snap_disp, sizeof(float) * 2 * plane));
-    PM_HIP(h, hipMalloc((void**)&h->snap_cost, sizeof(float) * 2 * plane));
-  }
+  if (int rc = snapshot_alloc(h)) return rc;
   const PlaneSet ps = tile_plane_set(h);
   launch_tile_presweep(h, ps, h->snap_disp, h->snap_cost, d_row, d_row ? r : -4, h->stream);
   return launch_check(h, "tile_presweep");

@@ -103,6 +103,35 @@ def test_the_shipped_library_carries_no_tuning_knob():
             assert "getenv" not in open(os.path.join(src, f)).read().replace("tune_env", ""), f
 
 
+def test_device_memory_is_allocated_by_its_one_owner_only():
+    """Every device allocation of a handle goes through csrc/pm_devbuf.hpp, whose counters tests/test_ownership.py
+    reads: an allocation made beside it would not be counted.  hipMalloc / hipFree may appear in that header, in
+    pm_tiled.hip (whose rt_* layer logs its own), in pm_device_malloc / pm_device_free (memory handed to the caller)
+    and in the PM_RUN3_STATS block of pm_run3.hpp (analysis builds)."""
+    src = os.path.join(ROOT, "ocean-perception_amd", "csrc")
+    # every device allocator and its free (hipMallocAsync, hipMallocManaged, hipExtMallocWithFlags ...); hipHostMalloc /
+    # hipHostFree are page-locked HOST memory and not the owner's business
+    call = re.compile(r"\bhip(?:Ext)?Malloc\w*\(|\bhipFree(?:Async)?\(")
+    found = {}
+    for f in sorted(os.listdir(src)):
+        if f in ("pm_devbuf.hpp", "pm_tiled.hip") or not os.path.isfile(os.path.join(src, f)):  # (not experimental/)
+            continue
+        text = open(os.path.join(src, f)).read()
+        if f == "pm_imaging.hip":
+            for name in ("pm_device_malloc", "pm_device_free"):
+                start = text.index("int %s(" % name)
+                end = text.index("\n}\n", start)
+                assert call.search(text[start:end]), name
+                text = text[:start] + text[end:]
+        if f == "pm_run3.hpp":
+            text, blocks = re.subn(r"#ifdef PM_RUN3_STATS\b.*?#endif", "", text, flags=re.S)
+            assert blocks >= 1
+        if call.search(text):
+            found[f] = [m.group(0) for m in call.finditer(text)]
+    assert found == {}, found
+    assert len(call.findall(open(os.path.join(src, "pm_devbuf.hpp")).read())) == 2  # one of each
+
+
 def _has_gpu():
     try:
         import torch
