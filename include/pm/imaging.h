@@ -95,7 +95,16 @@ int pm_gather_pixels(pm_handle* h, const float* d_img, int rows, int cols, int c
  *          stretched twice)
  *   gray = cv::cvtColor(J, BGR2GRAY), converted to 8 bit (x 255, saturate_cast) -- the image Match() consumes.
  * d_bgr8: [rows][cols][3] bytes.  d_J ([rows][cols][3] float) and d_gray8 ([rows][cols] bytes) are optional
- * outputs (at least one).  rows, cols >= 8.  Scratch for the image size is allocated on first use. */
+ * outputs (at least one).  rows, cols >= 8.  Scratch for the image size is allocated on first use.
+ * Edge cases, all equal to the CPU definition (oracle/pm_enhance_oracle.c) bit for bit:
+ *   - a gray image delivered as BGR (b == g == r, a monochrome camera): the first stretch puts the cell that defined its
+ *     minimum at 0 -+ rounding, so the second stretch's minimum may be slightly negative or -0.0; the min / max
+ *     reductions order floats of either sign.
+ *   - black regions: a zero illuminant divides to 0 (cv::divide), the first minimum is then exactly 0.
+ *   - a CONSTANT image (all-black included): vmax == vmin, the reference's arithmetic divides by zero.  Every value of
+ *     J is NaN (the second stretch sees no ordered value and keeps its initial minimum FLT_MAX and maximum -FLT_MAX) and
+ *     every byte of the gray image is 0 (NaN saturates to 0).  Nothing is detected or reported: as in the reference,
+ *     the caller is expected not to feed featureless frames. */
 int pm_stereo_ready(pm_handle* h, const uint8_t* d_bgr8, int rows, int cols, float* d_J, uint8_t* d_gray8);
 
 /* Match() on 8-bit BGR pairs with that enhancement FOLDED INTO THE LOAD PATH (BASELINE config 5: "underwater enhancement
@@ -113,6 +122,11 @@ int pm_match_bgr_device(pm_handle* h, int n, const uint8_t* d_left_bgr8, const u
  * (EstimateIlluminantGaussian = 2 x this, illuminant.cpp:10-21), and imaging::Normalize. */
 int pm_gaussian_blur(pm_handle* h, const float* d_src, int rows, int cols, int channels, int ksize, double sigma,
                      float* d_dst);
+/* pm_normalize takes ANY float image, negative channels and all-negative pixels included (its own output has them): the
+ * value channel is the largest of the three channels whatever its sign, and its minimum / maximum over the 1/8 image are
+ * taken over floats of either sign, like the CPU definition, bit for bit.  NaN cells of the 1/8 image are skipped; a
+ * constant image (vmax == vmin) gives NaN everywhere (see pm_stereo_ready).  rows, cols >= 8.
+ * pm_gaussian_blur: ksize odd and >= 1 (1 copies the image: the single tap is 1.0f), sigma > 0; ksize may exceed the image. */
 int pm_normalize(pm_handle* h, const float* d_bgr, int rows, int cols, float* d_out);
 /* imaging::NormalizeColorIlluminant on a float image (normalization.cpp:178-185). */
 int pm_normalize_color_illuminant(pm_handle* h, const float* d_bgr, int rows, int cols, float* d_out);

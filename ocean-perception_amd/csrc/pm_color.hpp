@@ -65,6 +65,12 @@ __device__ __forceinline__ void normalize_px(float b, float g, float r, float al
   v = v * alpha + beta;
   hsv2bgr_d(h, s, v, ob, og, orr);
 }
+// The min / max words of one value stretch: mm[0] = bits of the smallest, mm[1] = bits of the largest value of the 1/8
+// image, plain float bit patterns of EITHER sign (the second stretch of pm_stereo_ready sees the cell that defined the first
+// minimum at 0 -+ rounding).  Whoever launches a reduction starts them at the oracle's initial values, FLT_MAX and -FLT_MAX
+// (pm_enhance.hpp::atomic_min_float / atomic_max_float fold into them); an image whose cells are all NaN leaves them there.
+constexpr unsigned kValueMinInit = 0x7f7fffffu;  //  FLT_MAX
+constexpr unsigned kValueMaxInit = 0xff7fffffu;  // -FLT_MAX
 // alpha = (float)(1 / (vmax - vmin)), beta = (float)(-vmin / (vmax - vmin)) from the min / max bits of the 1/8 image
 __device__ __forceinline__ void stretch_coeffs(const unsigned* __restrict__ mm, float& alpha, float& beta) {
   const double vmin = (double)__uint_as_float(mm[0]), vmax = (double)__uint_as_float(mm[1]);
@@ -79,12 +85,13 @@ __device__ __forceinline__ float illuminant_div(uint8_t orig, float blur) {
   const float d = blur * 2.0f;
   return d != 0.f ? num / d : 0.f;
 }
-// BGR2GRAY + convertTo(CV_8U, 255) with saturate_cast<uchar>
+// BGR2GRAY + convertTo(CV_8U, 255) with saturate_cast<uchar>.  NaN (a constant image, vmax == vmin) gives 0 like the
+// oracle: fmaxf returns its other operand, and for every ordered value max(x, 0) converts like x (negatives saturate to 0).
 __device__ __forceinline__ uint8_t gray_u8(float b, float g, float r) {
   float gr = b * 0.114f;
   gr = gr + g * 0.587f;
   gr = gr + r * 0.299f;
-  return (uint8_t)__builtin_amdgcn_cvt_pk_u8_f32(gr * 255.f, 0, 0u);
+  return (uint8_t)__builtin_amdgcn_cvt_pk_u8_f32(fmaxf(gr * 255.f, 0.f), 0, 0u);
 }
 // The whole per-pixel tail of pm_stereo_ready from the 8-bit pixel and its blurred illuminant: q = I / (2 blur),
 // J1 = Normalize(q) (the one inside NormalizeColorIlluminant), J2 = Normalize(J1) (enhance_test.cpp:69), gray.

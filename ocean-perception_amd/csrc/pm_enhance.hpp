@@ -69,6 +69,23 @@ __global__ void __launch_bounds__(kBlurRowThreads) k_blur_rows(BlurBatch bb, int
   if (x0 + p0 >= cols) return;
   const float* base = lds + 5 * threadIdx.x;  // = lds + blur_skew(p0); sample u at base[u + (u >> 2)]
   float s[R][CH];
+  if (ksize < R) {
+    // 1 or 3 taps (pm_stereo_ready on images narrower than 12 pixels; pm_gaussian_blur with ksize 1 or 3): the blocked
+    // schedule below gives every output a tap at window positions R - 1 and ksize, which needs ksize >= R.  Each
+    // output on its own, taps in ascending order.
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int x = x0 + p0 + r;
+      if (x >= cols) break;
+#pragma unroll
+      for (int q = 0; q < CH; ++q) {
+        float acc = s_k[0] * base[q * plane + r + (r >> 2)];
+        for (int t = 1; t < ksize; ++t) acc = acc + s_k[t] * base[q * plane + (r + t) + ((r + t) >> 2)];
+        dst[((size_t)y * cols + x) * CH + q] = acc;
+      }
+    }
+    return;
+  }
   // window position u (sample x0 - c + p0 + u) contributes tap j = u - r to output r.
   // prologue u < R: the first taps of outputs 0 .. u (the sum starts WITH k[0] * w, it is not added to 0)
 #pragma unroll
@@ -269,11 +286,31 @@ __device__ __forceinline__ void linear_coeff_d(int d, int ssize, int dsize, int&
   w1 = f;
 }
 
-// ---- min / max of resize(V, size / 8); mm[0] = min bits (init 0x7f7fffff), mm[1] = max bits (init 0); V >= 0 ----
+// ---- float min / max into one word that holds a float's bit pattern, for values of either sign (never NaN) -------------
+// Non-negative floats order like their bit patterns read as SIGNED integers, and every negative float is a negative
+// integer, hence below them; negative floats (-0.0 included: it counts as the smallest of them, below +0.0) order
+// AGAINST their patterns read as unsigned integers, and every non-negative float is a smaller unsigned integer.  So a
+// non-negative candidate lowers the minimum through the signed atomic and a negative one through the unsigned atomic
+// of the other direction; the maximum mirrors it.  Whatever the word holds, each atomic either installs the candidate or
+// leaves a value that is smaller (larger) than it.
+__device__ __forceinline__ void atomic_min_float(unsigned* addr, float v) {
+  const unsigned b = __float_as_uint(v);
+  if (b >> 31) atomicMax(addr, b);
+  else atomicMin((int*)addr, (int)b);
+}
+__device__ __forceinline__ void atomic_max_float(unsigned* addr, float v) {
+  const unsigned b = __float_as_uint(v);
+  if (b >> 31) atomicMin(addr, b);
+  else atomicMax((int*)addr, (int)b);
+}
+
+// ---- min / max of resize(V, size / 8); mm[0] = min bits (init kValueMinInit), mm[1] = max bits (init kValueMaxInit).
+// V may be negative: Normalize's own output is (the stretch puts the smoothed minimum at 0 -+ rounding and single pixels
+// below it), and pm_normalize takes any float image.  NaN cells are skipped, as by the oracle's comparisons.
 __global__ void __launch_bounds__(256) k_value_minmax(const float* __restrict__ q, int rows, int cols, unsigned* mm) {
   __shared__ float s_lo[4], s_hi[4];
   const int dr = rows / 8, dc = cols / 8;
-  float lo = FLT_MAX, hi = 0.f;
+  float lo = FLT_MAX, hi = -FLT_MAX;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < dr * dc; i += gridDim.x * blockDim.x) {
     const int dy = i / dc, dx = i - dy * dc;
     int sy, sx;
@@ -300,8 +337,8 @@ __global__ void __launch_bounds__(256) k_value_minmax(const float* __restrict__ 
   if (threadIdx.x == 0) {
     lo = fminf(fminf(s_lo[0], s_lo[1]), fminf(s_lo[2], s_lo[3]));
     hi = fmaxf(fmaxf(s_hi[0], s_hi[1]), fmaxf(s_hi[2], s_hi[3]));
-    atomicMin(&mm[0], __float_as_uint(lo));
-    atomicMax(&mm[1], __float_as_uint(hi));
+    atomic_min_float(&mm[0], lo);
+    atomic_max_float(&mm[1], hi);
   }
 }
 
@@ -335,7 +372,7 @@ __global__ void __launch_bounds__(256) k_value_minmax_fused(BlurBatch bb, int ro
   const int dr = rows / 8, dc = cols / 8;
   float a1 = 0.f, b1 = 0.f;
   if (STAGE == 2) stretch_coeffs(mm, a1, b1);
-  float lo = FLT_MAX, hi = 0.f;
+  float lo = FLT_MAX, hi = -FLT_MAX;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < dr * dc; i += gridDim.x * blockDim.x) {
     const int dy = i / dc, dx = i - dy * dc;
     int sy, sx;
@@ -365,8 +402,8 @@ __global__ void __launch_bounds__(256) k_value_minmax_fused(BlurBatch bb, int ro
     lo = fminf(fminf(s_lo[0], s_lo[1]), fminf(s_lo[2], s_lo[3]));
     hi = fmaxf(fmaxf(s_hi[0], s_hi[1]), fmaxf(s_hi[2], s_hi[3]));
     unsigned* out = mm + (STAGE == 2 ? 2 : 0);
-    atomicMin(&out[0], __float_as_uint(lo));
-    atomicMax(&out[1], __float_as_uint(hi));
+    atomic_min_float(&out[0], lo);
+    atomic_max_float(&out[1], hi);
   }
 }
 

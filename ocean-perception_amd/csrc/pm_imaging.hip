@@ -371,7 +371,7 @@ int run_normalize(pm_handle* h, const float* d_q, int rows, int cols, float* d_J
     set_err(h, "normalize: the image must be at least 8x8 (its 1/8 resize would be empty)");
     return PM_ERR_INVALID_ARG;
   }
-  const unsigned init[2] = {0x7f7fffffu, 0u};
+  const unsigned init[2] = {kValueMinInit, kValueMaxInit};
   PM_HIP(h, hipMemcpyAsync(state_of(h)->img_scalars + 2, init, sizeof(init), hipMemcpyHostToDevice, pm_internal::stream(h)));
   const size_t small = (size_t)(rows / 8) * (cols / 8);
   hipLaunchKernelGGL(k_value_minmax, reduce_grid(small), dim3(256), 0, pm_internal::stream(h), d_q, rows, cols, state_of(h)->img_scalars + 2);
@@ -436,8 +436,8 @@ int pm_match_bgr_device(pm_handle* h, int n, const uint8_t* d_left_bgr8, const u
   const double sigma = (double)((float)ksize / 4.0f);
   std::vector<unsigned> init((size_t)n * 8);
   for (size_t i = 0; i < init.size(); i += 2) {
-    init[i] = 0x7f7fffffu;  // min
-    init[i + 1] = 0u;       // max
+    init[i] = kValueMinInit;
+    init[i + 1] = kValueMaxInit;
   }
   PM_HIP(h, hipMemcpyAsync(st->bgr_mm, init.data(), sizeof(unsigned) * init.size(), hipMemcpyHostToDevice, pm_internal::stream(h)));
   float* blur_l = st->bgr_blur;

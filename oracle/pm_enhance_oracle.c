@@ -223,7 +223,9 @@ void pmo_stereo_ready(const uint8_t* bgr8, int rows, int cols, float* J_out, uin
     g = g + J[i * 3 + 1] * 0.587f;
     g = g + J[i * 3 + 2] * 0.299f;
     const float r = nearbyintf(g * 255.f);
-    gray8[i] = (uint8_t)(r < 0.f ? 0 : (r > 255.f ? 255 : (int)r));
+    /* NaN (a constant image: vmax == vmin, the stretch divides by zero) -> 0, stated explicitly: (int)NaN is undefined
+     * in C.  cv::saturate_cast<uchar>(float) goes through cvRound, which yields INT_MIN for NaN on x86, saturated to 0. */
+    gray8[i] = (uint8_t)(r > 0.f ? (r > 255.f ? 255 : (int)r) : 0);
   }
   if (J_out) memcpy(J_out, J, sizeof(float) * n * 3);
   free(I);

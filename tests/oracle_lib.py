@@ -484,6 +484,13 @@ def normalize(bgr):
     return out
 
 
+def normalize_color_illuminant(bgr):
+    bgr = c_f32(bgr)
+    out = np.empty_like(bgr)
+    _enh_lib().pmo_normalize_color_illuminant(_p(bgr), bgr.shape[0], bgr.shape[1], _p(out))
+    return out
+
+
 def value_minmax_eighth(V):
     V = c_f32(V)
     lo, hi = C.c_double(0), C.c_double(0)
