@@ -194,8 +194,12 @@ const char* pm_status_string(int status);
 /* Replaces void PatchmatchGpu::Match(const Image1b& iml, const Image1b& imr, Image1f& disp,
  * Image1f& dispr) (patchmatch_gpu.h:99-102, patchmatch_gpu.cu:331-376) with host buffers.
  * seed_l / seed_r: sparse-init disparity maps (what SparseInit returns, .cu:414-442) in left /
- * right image coordinates, or NULL for "all background".  disp_r may be NULL when
- * left_right_check == 0. */
+ * right image coordinates, or NULL for "all background".  PM_MODE_SCALAR: a seed value that is not > 0 (negative, -0,
+ * NaN) is background as well: it is loaded as 0, which is what the first noise step would make of it; with
+ * patchmatch_iters == 0, where no noise step runs, that defines the result.  (PM_MODE_PLANES treats such a value as
+ * unseeded and starts that pixel from a random plane.)  disp_r may be NULL when left_right_check == 0.
+ * Images are at least 8x8; the scalar Match entry points with host or device buffers (not the BGR / raw ones) take 5
+ * rows and more when sparse_init == 0. */
 int pm_match_u8(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols,
                 size_t image_step, const float* seed_l, const float* seed_r, size_t seed_step,
                 float* disp_l, float* disp_r, size_t disp_step);
@@ -308,13 +312,19 @@ int pm_add_noise(pm_handle* h, float* disp, int rows, int cols, float amount);
 /* Patchmatch::Propagate (patchmatch.cpp:248-311) for PM_SEM_CPU, or the PropagateRow(+1),
  * PropagateCol(+1), PropagateRow(-1), PropagateCol(-1) sequence (patchmatch_gpu.cu:397-403) for
  * PM_SEM_GPU.  pass_mask bit k enables the k-th of those four sweeps.  disp is updated in place.
- * PM_SEM_CPU: every value of disp must be >= 0 (not NaN), else PM_ERR_INVALID_ARG and disp is left untouched.  The
- * reference clamps only a pixel's own value; a neighbour's negative one it tries as it stands, with the target window
- * beyond the right border (getRectSubPix's border branch), which the kernels do not implement.  Every map that
- * Patchmatch::AddNoise / pm_add_noise has produced is >= 0, so the reference's own call sequences never get there. */
+ * Both semantics: every value of disp must be >= 0 (not NaN), else PM_ERR_INVALID_ARG, pm_last_error names the first
+ * such index and value, and disp is left untouched.  PM_SEM_CPU: the reference clamps only a pixel's own value; a
+ * neighbour's negative one it tries as it stands, with the target window beyond the right border (getRectSubPix's border
+ * branch), which the kernels do not implement.  PM_SEM_GPU: the reference samples the target at max(x - d, 1) with no
+ * upper bound, so a negative d reads past the row (patchmatch_gpu.cu:156-171).  Every map that Patchmatch::AddNoise /
+ * pm_add_noise has produced is >= 0, so the reference's own call sequences never get there. */
 int pm_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols,
                  float* disp, int patch_h, int patch_w, int pass_mask);
-/* Patchmatch::RemoveBackground (patchmatch.cpp:314-360) / MaskBackground (patchmatch_gpu.cu:233-270). */
+/* Patchmatch::RemoveBackground (patchmatch.cpp:314-360) / MaskBackground (patchmatch_gpu.cu:233-270).
+ * PM_SEM_CPU takes any map: a pixel's value is clamped to [0, x - patch_w/2] as in the reference (NaN and negatives
+ * count as 0, +inf as the upper end).  PM_SEM_GPU: a value < 0 is refused with PM_ERR_INVALID_ARG (pm_last_error names
+ * the index and the value; disp is left untouched), because the reference's sample position max(x - d, 1) has no upper
+ * bound; NaN samples column 1 and is accepted. */
 int pm_remove_background(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols,
                          float* disp, int patch_h, int patch_w, float factor);
 /* PatchmatchGpu::SparseInit(iml, imr, dilate_factor) (patchmatch_gpu.h:110-112, patchmatch_gpu.cu:414-442):
@@ -337,7 +347,11 @@ int pm_initialize(pm_handle* h, const uint8_t* left, const uint8_t* right, int r
  * this function; it completes stereo_matching/patchmatch.{hpp,cpp}. */
 int pm_foreground_texture_mask(pm_handle* h, const uint8_t* d_gray, int rows, int cols, int ksize, double min_grad,
                                int downsize, uint8_t* d_mask);
-/* MaskOcclusions (patchmatch_gpu.cu:273-295). */
+/* MaskOcclusions (patchmatch_gpu.cu:273-295): disp_l(y, x) is zeroed when dr = disp_r(y, (int)max(x - disp_l, 0)) is
+ * > 1.4 * disp_l or < 0.7 * disp_l, compared in binary64.  Maps of 1x1 pixels and more, within the plan.  A value with
+ * !(max(x - disp_l, 0) < cols) (binary32) would index past the row and is refused with PM_ERR_INVALID_ARG before
+ * anything runs (pm_last_error names index and value; disp_l is left untouched).  What the reference defines stays:
+ * NaN and +inf read column 0, -0.0 and negatives with x - disp_l < cols stay in the row. */
 int pm_mask_occlusions(pm_handle* h, float* disp_l, const float* disp_r, int rows, int cols);
 
 /* ---- one large image row-tiled over several handles / GPUs (BASELINE config 4) ------------------

@@ -278,7 +278,7 @@ struct Launch {
 
 // ---- pm_engine.hip: geometry, checks, the Match() schedule -------------------------------------------------------
 int check_patch(pm_handle* h, int pw, int ph);
-int check_size(pm_handle* h, int rows, int cols, int n);
+int check_size(pm_handle* h, int rows, int cols, int n, bool match = false);  // match: a scalar Match() on caller seeds, 5 rows and up
 PlaneSet plane_set(const pm_handle* h, int rows, int cols, int n_views);
 CostParams cost_params(const pm_params& p, int pw, int ph);
 Interior interior(const pm_params& p, int rows, int cols, int pw, int ph);

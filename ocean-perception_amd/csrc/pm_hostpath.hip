@@ -200,7 +200,7 @@ int check_host_call(pm_handle* h, const char* what, bool ptrs, int rows, int col
     set_err(h, "%s: null image or output pointer", what);
     return PM_ERR_INVALID_ARG;
   }
-  if (int rc = check_size(h, rows, cols, n)) return rc;
+  if (int rc = check_size(h, rows, cols, n, /*match=*/true)) return rc;
   if (out_l && !out_r && h->params.left_right_check) {
     set_err(h, "%s: disp_r required when left_right_check is set", what);
     return PM_ERR_INVALID_ARG;
@@ -718,6 +718,20 @@ int stage_out(pm_handle* h, const PlaneSet& ps, float* dst, int which) {
   return PM_OK;
 }
 
+// A caller's disparity map for a stage that turns its values into sample positions x - d without an upper clamp: every
+// value must be >= 0 (nan_ok: or NaN, where the stage's fmaxf(x - NaN, 1) is in range).  Nothing is enqueued before this.
+int refuse_map_values(pm_handle* h, const char* who, const float* disp, int rows, int cols, bool nan_ok) {
+  for (size_t i = 0, n = (size_t)rows * (size_t)cols; i < n; ++i) {
+    const float d = disp[i];
+    if (nan_ok ? d < 0.f : !(d >= 0.f)) {
+      set_err(h, "%s: disp[%zu] = %g (y = %zu, x = %zu); the map must hold values >= 0%s only (pm_add_noise clamps)", who,
+              i, (double)d, i / (size_t)cols, i % (size_t)cols, nan_ok ? " or NaN" : "");
+      return PM_ERR_INVALID_ARG;
+    }
+  }
+  return PM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -773,20 +787,16 @@ int pm_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, int ro
     set_err(h, "pm_propagate: null pointer");
     return PM_ERR_INVALID_ARG;
   }
-  if (h->params.semantics == PM_SEM_CPU) {
+  if (h->params.semantics == PM_SEM_CPU)
     if (int rc = check_patch(h, patch_w, patch_h)) return rc;
-    // The sweeps evaluate a neighbour's disparity as it stands (patchmatch.cpp:177,186: only d0 is clamped), and
-    // cpu_cost_lane holds for 0 <= d only: a negative candidate puts the target window beyond the right border, where
-    // the reference takes getRectSubPix's border branch and the kernels would index past the row.  Inside Match every
-    // map has been through AddNoise's max(disp, 0); here the caller's map arrives as it is, so it is checked.
-    if (rows > 0 && cols > 0)
-      for (size_t i = 0, n = (size_t)rows * (size_t)cols; i < n; ++i)
-        if (!(disp[i] >= 0.f)) {
-          set_err(h, "pm_propagate: disp[%zu] = %g; PM_SEM_CPU takes maps with every value >= 0 (pm_add_noise clamps)", i,
-                  (double)disp[i]);
-          return PM_ERR_INVALID_ARG;
-        }
-  }
+  if (int rc = check_size(h, rows, cols, 1)) return rc;
+  // The sweeps evaluate a neighbour's disparity as it stands.  PM_SEM_CPU (patchmatch.cpp:177,186: only d0 is clamped):
+  // cpu_cost_lane holds for 0 <= d only; a negative candidate puts the target window beyond the right border, where the
+  // reference takes getRectSubPix's border branch and the kernels would index past the row.  PM_SEM_GPU
+  // (patchmatch_gpu.cu:156-171): the sample position max(x - d, r) has no upper clamp, in the reference neither, so a
+  // negative d reads past the row there as well.  Inside Match every map has been through the noise step's max(disp, 0);
+  // here the caller's map arrives as it is, so it is checked.
+  if (int rc = refuse_map_values(h, "pm_propagate", disp, rows, cols, /*nan_ok=*/false)) return rc;
   PlaneSet ps;
   if (int rc = stage_prep(h, left, right, rows, cols, &ps)) return rc;
   if (int rc = stage_disp_in(h, ps, disp)) return rc;
@@ -810,6 +820,12 @@ int pm_remove_background(pm_handle* h, const uint8_t* left, const uint8_t* right
   }
   if (h->params.semantics == PM_SEM_CPU)
     if (int rc = check_patch(h, patch_w, patch_h)) return rc;
+  if (int rc = check_size(h, rows, cols, 1)) return rc;
+  // PM_SEM_CPU clamps d to [0, x - pw/2] as the reference does (patchmatch.cpp:314-360): every value is defined.
+  // PM_SEM_GPU samples the target at max(x - d, 1) (patchmatch_gpu.cu:233-270), which a negative d puts past the row;
+  // NaN gives position 1 and passes.
+  if (h->params.semantics == PM_SEM_GPU)
+    if (int rc = refuse_map_values(h, "pm_remove_background", disp, rows, cols, /*nan_ok=*/true)) return rc;
   PlaneSet ps;
   if (int rc = stage_prep(h, left, right, rows, cols, &ps)) return rc;
   if (int rc = stage_disp_in(h, ps, disp)) return rc;
@@ -884,7 +900,27 @@ int pm_mask_occlusions(pm_handle* h, float* disp_l, const float* disp_r, int row
     set_err(h, "pm_mask_occlusions: null pointer");
     return PM_ERR_INVALID_ARG;
   }
-  if (int rc = check_size(h, rows, cols, 1)) return rc;
+  // (no window, no planes: any map of at least one pixel that fits the plan's staging buffers)
+  if (rows < 1 || cols < 1) {
+    set_err(h, "pm_mask_occlusions: empty map %dx%d", cols, rows);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (rows > h->max_rows || cols > h->max_cols) {
+    set_err(h, "request %dx%d exceeds plan %dx%d", cols, rows, h->max_cols, h->max_rows);
+    return PM_ERR_SIZE;
+  }
+  // The kernel reads disp_r at column (int)max(x - dl, 0) of the same row (patchmatch_gpu.cu:286-289, which has no upper
+  // bound either): NaN, +inf and every dl >= 0 give a column of the row, and so does a negative dl while x - dl < cols;
+  // beyond that the read leaves the row -- on the last row the buffer -- so the map is refused before anything is enqueued.
+  for (int y = 0; y < rows; ++y)
+    for (int x = 0; x < cols; ++x) {
+      const float dl = disp_l[(size_t)y * cols + x];
+      if (!(fmaxf((float)x - dl, 0.f) < (float)cols)) {
+        set_err(h, "pm_mask_occlusions: disp_l[%zu] = %g (y = %d, x = %d); the map must hold values with x - d < cols = %d only",
+                (size_t)y * cols + x, (double)dl, y, x, cols);
+        return PM_ERR_INVALID_ARG;
+      }
+    }
   PM_HIP(h, hipSetDevice(h->device));
   const size_t px = (size_t)rows * cols;
   PM_HIP(h, hipMemcpyAsync(h->st_disp_l, disp_l, sizeof(float) * px, hipMemcpyHostToDevice, h->stream));

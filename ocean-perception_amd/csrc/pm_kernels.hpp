@@ -33,6 +33,11 @@ __device__ __forceinline__ float sobel_mag(const uint8_t* im, size_t stride, int
 // with the two views on their own streams each stream prepares its own planes and nothing waits for the other.
 // seeds.on != 0: also what k_seed does for the view(s) of this launch (seed maps -> disparity planes), one launch less
 // at the head of a Match.
+// A caller's seed value as the state planes take it: background (0) unless positive, which is what the first noise step
+// makes of it anyway (AddForegroundNoise zeroes every value that is not > 0, NaN included, before anything reads it).
+// With patchmatch_iters == 0 no noise step runs and the background mask and the cross-check index with the value.
+__device__ __forceinline__ float seed_value(float s) { return s > 0.f ? s : 0.f; }
+
 struct PrepSeeds {
   const float* l;  // tightly packed [B][rows][cols] seed maps in left / right image coordinates, or null = all background
   const float* r;
@@ -47,9 +52,9 @@ __global__ void __launch_bounds__(256) k_prep(PlaneSet ps, const uint8_t* __rest
   if (seeds.on) {
     const size_t sp = (size_t)ps.rows * ps.cols, so = (size_t)b * sp + (size_t)y * ps.cols;
     const size_t o = state_at(x, y, ps.pitch);
-    if (view_sel != 1) ps.disp[((size_t)b * 2 + 0) * ps.splane + o] = seeds.l ? seeds.l[so + x] : 0.f;
+    if (view_sel != 1) ps.disp[((size_t)b * 2 + 0) * ps.splane + o] = seeds.l ? seed_value(seeds.l[so + x]) : 0.f;
     if (ps.n_views > 1 && view_sel != 0)
-      ps.disp[((size_t)b * 2 + 1) * ps.splane + o] = seeds.r ? seeds.r[so + (ps.cols - 1 - x)] : 0.f;
+      ps.disp[((size_t)b * 2 + 1) * ps.splane + o] = seeds.r ? seed_value(seeds.r[so + (ps.cols - 1 - x)]) : 0.f;
   }
   const size_t in_plane = (size_t)ps.rows * in_stride;
   const uint8_t* srcs[2] = {in_left + (size_t)b * in_plane, in_right + (size_t)b * in_plane};
@@ -350,7 +355,7 @@ __global__ void __launch_bounds__(256) k_setup(PlaneSet ps, SetupGrid sg) {
 }
 
 // seed maps -> disparity planes; the right-view seed is mirrored like the images
-// (patchmatch_gpu.cu:362-366).  A null seed pointer means "all background".
+// (patchmatch_gpu.cu:362-366).  A null seed pointer means "all background"; so does a value that is not > 0 (seed_value).
 __global__ void __launch_bounds__(256) k_seed(PlaneSet ps, const float* __restrict__ seed_l,
                                               const float* __restrict__ seed_r, size_t seed_stride, int view_sel) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
@@ -359,10 +364,10 @@ __global__ void __launch_bounds__(256) k_seed(PlaneSet ps, const float* __restri
   const size_t sp = (size_t)ps.rows * seed_stride;
   const size_t o = state_at(x, y, ps.pitch);
   if (view_sel != 1)
-    ps.disp[((size_t)b * 2 + 0) * ps.splane + o] = seed_l ? seed_l[(size_t)b * sp + (size_t)y * seed_stride + x] : 0.f;
+    ps.disp[((size_t)b * 2 + 0) * ps.splane + o] = seed_l ? seed_value(seed_l[(size_t)b * sp + (size_t)y * seed_stride + x]) : 0.f;
   if (ps.n_views > 1 && view_sel != 0)
     ps.disp[((size_t)b * 2 + 1) * ps.splane + o] =
-        seed_r ? seed_r[(size_t)b * sp + (size_t)y * seed_stride + (ps.cols - 1 - x)] : 0.f;
+        seed_r ? seed_value(seed_r[(size_t)b * sp + (size_t)y * seed_stride + (ps.cols - 1 - x)]) : 0.f;
 }
 
 // ---------------------------------------------------------------------------------------------

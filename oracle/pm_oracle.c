@@ -778,7 +778,9 @@ void pmo_match(const pmo_params* p, const uint8_t* left, const uint8_t* right, i
   pmo_gradient_magnitude(right, rows, cols, gr);
 
   pmo_images lv = {rows, cols, left, right, gl, gr};
-  if (seed_l) memcpy(disp_l, seed_l, sizeof(float) * n);
+  /* a seed that is not > 0 (negative, -0, NaN) is background: what the first noise step makes of it anyway; with
+   * n_iters == 0 no noise step runs and the value itself is turned into a column (the engine's k_seed does the same) */
+  if (seed_l) for (size_t i = 0; i < n; ++i) disp_l[i] = seed_l[i] > 0.f ? seed_l[i] : 0.f;
   else memset(disp_l, 0, sizeof(float) * n);
   pmo_match_view(p, &lv, disp_l);
 
@@ -793,8 +795,10 @@ void pmo_match(const pmo_params* p, const uint8_t* left, const uint8_t* right, i
     pmo_flip_h_u8(right, rf, rows, cols);
     pmo_flip_h_f32(gl, glf, rows, cols);
     pmo_flip_h_f32(gr, grf, rows, cols);
-    if (seed_r) pmo_flip_h_f32(seed_r, df, rows, cols);
-    else memset(df, 0, sizeof(float) * n);
+    if (seed_r) {
+      pmo_flip_h_f32(seed_r, df, rows, cols);
+      for (size_t i = 0; i < n; ++i) df[i] = df[i] > 0.f ? df[i] : 0.f;
+    } else memset(df, 0, sizeof(float) * n);
     pmo_images rv = {rows, cols, rf, lf, grf, glf};
     pmo_match_view(p, &rv, df);
     pmo_flip_h_f32(df, disp_r, rows, cols);

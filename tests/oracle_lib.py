@@ -265,9 +265,19 @@ def gpu_add_foreground_noise(disp, unit, scale):
     return d
 
 
+def _refuse(who, bad, d):
+    """ValueError for the first map value under `bad`: the C oracle indexes with x - d as the reference does, without an
+    upper bound, so a map that would take it out of the row never reaches it (the engine refuses the same maps)."""
+    if bad.any():
+        y, x = np.argwhere(bad)[0]
+        raise ValueError(f"{who}: disp[{y}, {x}] = {d[y, x]!r} puts the sample position past the row")
+
+
 def gpu_propagate(ims, disp, pass_mask=15, alpha=0.9, nthreads=1):
-    """The Row(+1), Col(+1), Row(-1), Col(-1) sequence of patchmatch_gpu.cu:397-403."""
+    """The Row(+1), Col(+1), Row(-1), Col(-1) sequence of patchmatch_gpu.cu:397-403.  Maps with a value that is not
+    >= 0 are refused (pm_propagate does the same): max(x - d, 1) has no upper clamp."""
     d = np.array(disp, np.float32, order="C", copy=True)
+    _refuse("gpu_propagate", ~(d >= 0), d)
     lib = load()
     if pass_mask & 1:
         lib.pmo_gpu_propagate_row(C.byref(ims.c), _p(d), 1, 3, alpha, nthreads)
@@ -281,14 +291,23 @@ def gpu_propagate(ims, disp, pass_mask=15, alpha=0.9, nthreads=1):
 
 
 def gpu_mask_background(ims, disp, alpha=0.9, improve=0.8, nthreads=1):
+    """MaskBackground.  d < 0 is refused (as by pm_remove_background under PM_SEM_GPU); NaN samples column 1 and passes."""
     d = np.array(disp, np.float32, order="C", copy=True)
+    _refuse("gpu_mask_background", d < 0, d)
     load().pmo_gpu_mask_background(C.byref(ims.c), _p(d), 3, alpha, improve, nthreads)
     return d
 
 
 def gpu_mask_occlusions(displ, dispr):
+    """MaskOcclusions.  Refused (as by pm_mask_occlusions): a value with !(max(x - dl, 0) < cols), in binary32."""
     dl = np.array(displ, np.float32, order="C", copy=True)
     dr = c_f32(dispr)
+    if dl.ndim != 2 or dr.shape != dl.shape:
+        raise ValueError("gpu_mask_occlusions: two maps of one 2-D shape")
+    xs = np.arange(dl.shape[1], dtype=np.float32)[None, :]
+    with np.errstate(invalid="ignore"):
+        col = np.fmax(xs - dl, np.float32(0))  # fmaxf: NaN -> 0
+    _refuse("gpu_mask_occlusions", ~(col < np.float32(dl.shape[1])), dl)
     load().pmo_gpu_mask_occlusions(_p(dl), _p(dr), dl.shape[0], dl.shape[1])
     return dl
 

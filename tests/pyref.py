@@ -250,7 +250,7 @@ def gpu_mask_occlusions(displ, dispr):
     for y in range(h):
         for x in range(w):
             dl = out[y, x]
-            dr = dispr[y, int(max(f32(f32(x) - dl), f32(0)))]
+            dr = dispr[y, int(np.fmax(f32(f32(x) - dl), f32(0)))]  # fmaxf: NaN -> column 0
             if float(dr) > 1.4 * float(dl) or float(dr) < 0.7 * float(dl):
                 out[y, x] = 0
     return out
