@@ -15,9 +15,17 @@ int pm_debug_capture_fork(pm_handle* h);
 /* Device memory the process's handles hold right now -- allocations and their bytes, over every handle and device.
  * Everything a handle allocates for itself goes through one owning type (csrc/pm_devbuf.hpp) that keeps these two
  * counters, so a create / use / destroy cycle that does not bring them back to where they were has leaked.  Not counted:
- * memory handed to the caller (pm_device_malloc), the band buffers of pm_tiled_* (logged by the audit below), host memory. */
+ * memory handed to the caller (pm_device_malloc). */
 long long pm_debug_live_device_allocations(void);
 long long pm_debug_live_device_bytes(void);
+/* The same for everything else handles and tiled plans take from the runtime (csrc/pm_hipres.hpp): events, streams,
+ * page-locked host buffers -- the staging slab, pm_host_alloc memory and pm_host_register registrations -- with their
+ * bytes, and instantiated graphs. */
+long long pm_debug_live_events(void);
+long long pm_debug_live_streams(void);
+long long pm_debug_live_host_buffers(void);
+long long pm_debug_live_host_bytes(void);
+long long pm_debug_live_graph_execs(void);
 
 /* ---- the row-tiled driver's device discipline, provable on ONE GPU ------------------------------------------------
  * pm_tiled_create with the bands accounted to LOGICAL devices: band k lives on logical_devices[k] (>= 0; several bands

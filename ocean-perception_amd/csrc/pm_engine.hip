@@ -94,23 +94,21 @@ hipError_t create_stream(hipStream_t* s, int kind, int prio_class) {
 int create_handle_streams(pm_handle* h) {
   static std::atomic<unsigned> handles_created{0};
   const unsigned k = handles_created.fetch_add(1u);
-  hipStream_t grp[4] = {nullptr, nullptr, nullptr, nullptr};
+  Stream grp[4];  // the handle gets them only once all four exist; until then they go with this array
   const int kinds[4] = {kStreamMain, kStreamView, kStreamCopy, kStreamCopy};
-  hipStream_t* roles[4] = {&h->stream, &h->view1_stream, &h->s_out, &h->s_in};
+  Stream* roles[4] = {&h->stream, &h->view1_stream, &h->s_out, &h->s_in};
   int role_at[4];
   for (int pos = 0; pos < 4; ++pos) {
     role_at[pos] = (int)((pos + 4u - (k & 3u)) & 3u);  // the role created at this position: (role + k) % 4 == pos
-    const hipError_t e = create_stream(&grp[pos], kinds[role_at[pos]], h->params.stream_priority);
+    hipStream_t st = nullptr;
+    hipError_t e = create_stream(&st, kinds[role_at[pos]], h->params.stream_priority);
+    if (e == hipSuccess) e = grp[pos].adopt(st);
     if (e != hipSuccess) {
-      // the handle's fields are assigned only once all four streams exist: pm_destroy (which the caller must still
-      // run on the handle pm_create hands back with the error) never sees a destroyed stream
-      for (hipStream_t st : grp)
-        if (st) (void)hipStreamDestroy(st);
       set_err(h, "stream creation failed: %s", hipGetErrorString(e));
       return PM_ERR_HIP;
     }
   }
-  for (int pos = 0; pos < 4; ++pos) *roles[role_at[pos]] = grp[pos];
+  for (int pos = 0; pos < 4; ++pos) *roles[role_at[pos]] = std::move(grp[pos]);
   return PM_OK;
 }
 
@@ -493,12 +491,10 @@ int view_streams_create(pm_handle* h) {
     set_err(h, "the view events do not exist yet: run this call once before capturing it");
     return PM_ERR_BUSY;
   }
-  if (!h->view_fork) PM_HIP(h, hipEventCreateWithFlags(&h->view_fork, hipEventDisableTiming));
-  if (!h->view1_join) PM_HIP(h, hipEventCreateWithFlags(&h->view1_join, hipEventDisableTiming));
-  if (!h->out_join) PM_HIP(h, hipEventCreateWithFlags(&h->out_join, hipEventDisableTiming));
-  if (!h->in_join) PM_HIP(h, hipEventCreateWithFlags(&h->in_join, hipEventDisableTiming));
-  for (int v = 0; v < 2; ++v)
-    if (!h->view_end[v]) PM_HIP(h, hipEventCreate(&h->view_end[v]));
+  for (Event* e : {&h->view_fork, &h->view1_join, &h->out_join, &h->in_join})
+    if (!*e) PM_HIP(h, e->create(hipEventDisableTiming));
+  for (Event& e : h->view_end)
+    if (!e) PM_HIP(h, e.create(hipEventDefault));  // timed
   return PM_OK;
 }
 
@@ -509,11 +505,10 @@ int seq_events_create(pm_handle* h) {
     set_err(h, "the chunk events do not exist yet: run this call once before capturing it");
     return PM_ERR_BUSY;
   }
-  std::vector<pm_handle::PipeSlot> slots((size_t)h->max_batch);
-  for (auto& sl : slots) {
-    hipEvent_t* evs[] = {&sl.in_done, &sl.head_done, &sl.v_done[0], &sl.v_done[1], &sl.out_done};
-    for (hipEvent_t* e : evs) PM_HIP(h, hipEventCreateWithFlags(e, hipEventDisableTiming));
-  }
+  std::vector<pm_handle::PipeSlot> slots((size_t)h->max_batch);  // all of them or none: a failure takes `slots` along
+  for (auto& sl : slots)
+    for (Event* e : {&sl.in_done, &sl.head_done, &sl.v_done[0], &sl.v_done[1], &sl.out_done})
+      PM_HIP(h, e->create(hipEventDisableTiming));
   h->pipe.swap(slots);
   return PM_OK;
 }
@@ -557,7 +552,8 @@ int run_views(pm_handle* h, const PlaneSet& ps, int slots, const ViewSetup* setu
   if (ps.n_views != 2 || !view_streams_enabled()) {
     for (int v = 0; v < ps.n_views; ++v)
       if (int rc = seed_views(h, ps, slots / ps.n_views, v, 0, h->stream)) return rc;
-    return run_view_sets(h, &ps, &h->stream, 1, slots);
+    const hipStream_t own = h->stream;
+    return run_view_sets(h, &ps, &own, 1, slots);
   }
   // one view stays on the caller's stream, the other forks off
   if (int rc = view_streams_create(h)) return rc;
@@ -643,7 +639,7 @@ bool seq_pipelined(const pm_handle* h) {
 // Enqueue only; the caller orders what follows behind s_out.
 int seq_enqueue_chunk(pm_handle* h, int b, int c, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
                       const float* d_seed_l, const float* d_seed_r, float* d_disp_l, float* d_disp_r, hipEvent_t ready,
-                      hipEvent_t ready2, hipEvent_t v_done[2], hipEvent_t head_done) {
+                      hipEvent_t ready2, const Event v_done[2], hipEvent_t head_done) {
   if (int rc = view_streams_create(h)) return rc;
   const PlaneSet ps = plane_set(h, rows, cols, 2);
   const PlaneSet pb = plane_set_of_pair(ps, b);
@@ -716,7 +712,7 @@ int run_pairs_as_chunks(pm_handle* h, int n, const ViewSetup& vs, int rows, int 
   // a chunk failed part way: the handle's stream waits for whatever the side streams hold (a capture's forks are
   // joined by abort_capture, which knows which streams the capture reached)
   if (!h->capturing)
-    for (hipStream_t s : {h->view1_stream, h->s_in, h->s_out}) (void)join_stream(h, s, join_event(h, s), h->stream);
+    for (hipStream_t s : {h->view1_stream.get(), h->s_in.get(), h->s_out.get()}) (void)join_stream(h, s, join_event(h, s), h->stream);
   return rc;
 }
 
@@ -857,8 +853,7 @@ int capture_open(pm_handle* h) {
 // been joined back into the handle's stream: ending a capture with an unjoined fork is an error the runtime answers with
 // a fault, not a status (gpurun_out/r03/crash.log: a schedule experiment that left a side stream forked).  The forks are
 // joined here so that the capture can be ended at all, the graph is thrown away, and the caller gets PM_ERR_STATE.
-int capture_close(pm_handle* h, hipGraphExec_t* exec, const char* what) {
-  *exec = nullptr;
+int capture_close(pm_handle* h, GraphExec* exec, const char* what) {
   const size_t unjoined = join_unjoined(h);
   h->capturing = false;
   hipGraph_t graph = nullptr;
@@ -869,10 +864,9 @@ int capture_close(pm_handle* h, hipGraphExec_t* exec, const char* what) {
                "was discarded", what, unjoined);
     return PM_ERR_STATE;
   }
-  const hipError_t e = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
+  const hipError_t e = exec->create(graph);
   (void)hipGraphDestroy(graph);
   if (e != hipSuccess) {
-    *exec = nullptr;
     set_err(h, "hipGraphInstantiate failed: %s", hipGetErrorString(e));
     return PM_ERR_HIP;
   }
@@ -1026,36 +1020,13 @@ void pm_destroy(pm_handle* h) {
   (void)hipSetDevice(h->device);
   abort_capture(h);
   // frames of a sequence may still be running on streams that never join the handle's own: wait for all of them
-  hipStream_t streams[] = {h->stream, h->view1_stream, h->s_in, h->s_out};
-  for (hipStream_t st : streams)
+  for (hipStream_t st : {h->stream.get(), h->view1_stream.get(), h->s_in.get(), h->s_out.get()})
     if (st) (void)hipStreamSynchronize(st);
   pm_internal::release_imaging(h);
-  hipEvent_t events[] = {h->ext_fork, h->ext_join, h->left_out, h->right_out, h->view1_join, h->out_join, h->in_join, h->view_fork,
-                         h->view_end[0], h->view_end[1]};
-  for (hipEvent_t e : events)
-    if (e) (void)hipEventDestroy(e);
-  if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
-  for (auto& r : h->ev_pool) {
-    (void)hipEventDestroy(r.start);
-    (void)hipEventDestroy(r.stop);
-  }
-  for (auto& sl : h->pipe) {
-    hipEvent_t evs[] = {sl.in_done, sl.head_done, sl.v_done[0], sl.v_done[1], sl.out_done};
-    for (hipEvent_t e : evs)
-      if (e) (void)hipEventDestroy(e);
-  }
-  delete h->copy_pool;
-  if (h->pinned) (void)hipHostFree(h->pinned);
-  // memory handed out by pm_host_alloc and still held, registrations still standing
-  for (auto& r : h->host_ranges) {
-    if (r.owned) (void)hipHostFree(r.base);
-    else (void)hipHostUnregister(r.base);
-  }
-  // the handle's device memory goes with its members (pm_devbuf.hpp): the device is current, every stream has been
-  // synchronised above and still exists
+  // everything else goes with the handle's members (pm_devbuf.hpp, pm_hipres.hpp) -- page-locked memory handed out by
+  // pm_host_alloc and registrations still standing included: the device is current, and the streams, which are
+  // declared first, go last
   delete h;
-  for (hipStream_t st : streams)
-    if (st) (void)hipStreamDestroy(st);
 }
 
 int pm_create(const pm_params* params, int device, int max_rows, int max_cols, int max_batch, pm_handle** out) {
@@ -1129,15 +1100,8 @@ int pm_create(const pm_params* params, int device, int max_rows, int max_cols, i
   PM_HIP(h, h->st_disp_l.alloc(sizeof(float) * B * tight));
   PM_HIP(h, h->st_disp_r.alloc(sizeof(float) * B * tight));
   // pinned host staging: per pair 2 u8 images + 2 seeds + 2 outputs (also used for the noise table)
-  h->pinned_bytes = B * tight * (2 + 4 * sizeof(float));
-  const size_t noise_bytes = sizeof(float) * plane;
-  if (h->pinned_bytes < noise_bytes) h->pinned_bytes = noise_bytes;
-  PM_HIP(h, hipHostMalloc(&h->pinned, h->pinned_bytes, hipHostMallocDefault));
-  {
-    void* dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, h->pinned, 0) == hipSuccess) h->pinned_dev = (char*)dp;
-    (void)hipGetLastError();
-  }
+  const size_t pinned_bytes = B * tight * (2 + 4 * sizeof(float)), noise_bytes = sizeof(float) * plane;
+  PM_HIP(h, h->pinned.alloc(pinned_bytes < noise_bytes ? noise_bytes : pinned_bytes));
   PM_HIP(h, hipStreamSynchronize(h->stream));
   return PM_OK;
 }
@@ -1177,10 +1141,9 @@ int pm_capture_begin(pm_handle* h) {
 
 int pm_capture_end(pm_handle* h) {
   if (!h || !h->capturing) return PM_ERR_INVALID_ARG;
-  hipGraphExec_t exec = nullptr;
+  GraphExec exec;
   if (int rc = pm::eng::capture_close(h, &exec, "pm_capture_end")) return rc;
-  if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
-  h->graph_exec = exec;
+  h->graph_exec = std::move(exec);  // the graph captured before goes with `exec`
   return PM_OK;
 }
 
@@ -1197,6 +1160,11 @@ int pm_debug_capture_fork(pm_handle* h) {
 
 long long pm_debug_live_device_allocations(void) { return pm::g_devbuf_allocations.load(); }
 long long pm_debug_live_device_bytes(void) { return pm::g_devbuf_bytes.load(); }
+long long pm_debug_live_events(void) { return pm::g_live_events.load(); }
+long long pm_debug_live_streams(void) { return pm::g_live_streams.load(); }
+long long pm_debug_live_host_buffers(void) { return pm::g_live_host_buffers.load(); }
+long long pm_debug_live_host_bytes(void) { return pm::g_live_host_bytes.load(); }
+long long pm_debug_live_graph_execs(void) { return pm::g_live_graph_execs.load(); }
 
 int pm_replay(pm_handle* h) {
   if (!h || !h->graph_exec) {
@@ -1250,10 +1218,7 @@ int pm_match_view_device(pm_handle* h, const float* d_iml, const float* d_imr, c
   hipStream_t user = (hipStream_t)stream;
   const bool foreign = user != nullptr && user != h->stream;
   if (foreign) {
-    if (!h->ext_fork) {
-      PM_HIP(h, hipEventCreateWithFlags(&h->ext_fork, hipEventDisableTiming));
-      PM_HIP(h, hipEventCreateWithFlags(&h->ext_join, hipEventDisableTiming));
-    }
+    if (!h->ext_fork) PM_HIP(h, create_event_pair(h->ext_fork, h->ext_join));
     PM_HIP(h, hipEventRecord(h->ext_fork, user));
     PM_HIP(h, hipStreamWaitEvent(h->stream, h->ext_fork, 0));
   }
@@ -1273,7 +1238,8 @@ int pm_match_view_device(pm_handle* h, const float* d_iml, const float* d_imr, c
   }
   if (int rc = launch_check(h, "seed")) return rc;
   h->need_seed[0] = h->need_seed[1] = false;
-  if (int rc = run_view_sets(h, &ps, &h->stream, 1, 1)) return rc;
+  const hipStream_t own = h->stream;
+  if (int rc = run_view_sets(h, &ps, &own, 1, 1)) return rc;
   {
     Launch l(h, PM_K_FINALIZE, h->stream);
     launch_copy_disp_strided(h, ps, d_disp, disp_step / sizeof(float), 1, h->stream);

@@ -15,12 +15,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <memory>
 #include <vector>
 
 #include "pm/patchmatch.h"
 #include "pm_color.hpp"
 #include "pm_devbuf.hpp"
 #include "pm_device.hpp"
+#include "pm_hipres.hpp"
 #include "pm_hostcopy.hpp"
 #include "pm_seed_api.hpp"
 #include "pm_sweep_defs.hpp"
@@ -32,9 +34,9 @@ namespace eng {
 constexpr int kMaxEvents = 16384;  // event pairs kept before a forced drain
 
 struct EventRec {
-  hipEvent_t start, stop;
-  int klass;
-  int start_ref;  // >= 0: the stop event of that record is this one's start (the launch before it on the same stream)
+  Event start, stop;  // timed
+  int klass = 0;
+  int start_ref = -1;  // >= 0: the stop event of that record is this one's start (the launch before it on the same stream)
 };
 
 }  // namespace eng
@@ -46,7 +48,10 @@ struct pm_handle {
   int device = 0;
   int max_rows = 0, max_cols = 0, max_batch = 0;
   int max_pitch = 0;
-  hipStream_t stream = nullptr;
+  // The four streams (pm_engine.hip::create_handle_streams; their roles: view_streams_create), declared in front of
+  // everything that is released while streams must still exist: members go in reverse order, so these go last -- the
+  // handle's own at the end.
+  pm::Stream s_out, s_in, view1_stream, stream;
 
   // engine planes (see pm::PlaneSet)
   pm::DevBuf<uint8_t> img8;
@@ -91,9 +96,7 @@ struct pm_handle {
   pm::DevBuf<float> st_seed_r;
   pm::DevBuf<float> st_disp_l;
   pm::DevBuf<float> st_disp_r;
-  void* pinned = nullptr;  // host staging, pinned
-  size_t pinned_bytes = 0;
-  char* pinned_dev = nullptr;  // the device's address of the staging slab (k_download writes the maps through it)
+  pm::HostBuf pinned;  // host staging slab; k_download writes the maps through its device address
 
   // The frame SEQUENCE (pm_submit_* / pm_collect, pm_match_batch_u8; pm_engine.hip::seq_enqueue_chunk): frame k lives in
   // ring slot k % max_batch -- plane slot, device staging slot and slab slot of that index.  Uploads run on s_in, the two
@@ -101,10 +104,10 @@ struct pm_handle {
   // the cross-check and the download on s_out; the handle's own stream is not involved, so nothing joins and nothing
   // forks per frame.
   struct PipeSlot {
-    hipEvent_t in_done = nullptr;   // s_in: the slot's inputs are in device memory
-    hipEvent_t head_done = nullptr; // s_in: images, gradients, line planes and seeds of the chunk that STARTS here are ready
-    hipEvent_t v_done[2] = {nullptr, nullptr};  // view stream v: the chunk that STARTS at this slot has run
-    hipEvent_t out_done = nullptr;  // s_out: the slot's maps have arrived on the host
+    pm::Event in_done;    // s_in: the slot's inputs are in device memory
+    pm::Event head_done;  // s_in: images, gradients, line planes and seeds of the chunk that STARTS here are ready
+    pm::Event v_done[2];  // view stream v: the chunk that STARTS at this slot has run
+    pm::Event out_done;   // s_out: the slot's maps have arrived on the host
     uint64_t tag = 0;
     int rows = 0, cols = 0;
     int state = 0;                  // 0 free, 1 uploaded and held for a partner, 2 enqueued
@@ -118,14 +121,9 @@ struct pm_handle {
     size_t out_step = 0;
     bool direct_l = false, direct_r = false;   // the download goes straight into the bound (registered) host map
   };
-  // caller memory the engine may DMA from / into without staging (pm_host_alloc, pm_host_register)
-  struct HostRange {
-    char* base;
-    size_t bytes;
-    bool owned;
-    char* dev_base;  // the device's address of `base` (null: not mapped -- downloads into it go through hipMemcpyAsync)
-  };
-  std::vector<HostRange> host_ranges;
+  // caller memory the engine may DMA from / into without staging (pm_host_alloc, pm_host_register); a range without a
+  // device address is not mapped -- downloads into it go through hipMemcpyAsync
+  std::vector<pm::HostBuf> host_ranges;
   // streams a capture forked work onto and has not joined back yet (pm_capture_end refuses to end such a capture)
   std::vector<hipStream_t> cap_unjoined;
   // Per-view streams: the two views are independent until the cross-check, so their launch chains run on two streams and
@@ -133,31 +131,29 @@ struct pm_handle {
   // handle's stream and forks the second onto view1_stream; the chunks of a batch or of a frame sequence run on the same
   // two streams, one chunk behind the other, with their cross-checks on s_out (pm_engine.hip::view_streams_create,
   // seq_enqueue_chunk).
-  hipEvent_t view_fork = nullptr;
-  hipStream_t view1_stream = nullptr;
-  hipEvent_t view1_join = nullptr;
+  pm::Event view_fork;
+  pm::Event view1_join;
   // Which view of a single pair ended last the time before (view_end: timed events behind the views' last launches).
   // That view goes onto the handle's stream: a join the waiting stream reaches AFTER its event has fired costs nothing,
   // one it reaches before costs a cross-queue wake-up (~12 us of the reference's own 0.46 ms call).
-  hipEvent_t view_end[2] = {nullptr, nullptr};
+  pm::Event view_end[2];
   bool view_end_recorded = false;
   static constexpr unsigned kViewEndEvery = 16;  // the order is sampled in every 16th single-pair call
   unsigned view_calls = 0;
   int late_view = 1;
-  hipEvent_t out_join = nullptr;  // s_out -> the handle's stream at the end of a batch
-  hipEvent_t in_join = nullptr;   // s_in -> the handle's stream (only when a capture is ended with the head stream unjoined)
+  pm::Event out_join;  // s_out -> the handle's stream at the end of a batch
+  pm::Event in_join;   // s_in -> the handle's stream (only when a capture is ended with the head stream unjoined)
   void* imaging_state = nullptr;  // owned by pm_imaging.hip (pm_internal.hpp)
   pm::DevBuf<void> texmask_scratch;  // pm_foreground_texture_mask: four byte planes, allocated on first use
   // pm_match_bgr_device: the next Match reads enhanced BGR inputs through k_prep_bgr instead of 8-bit gray images
   const pm::BgrSource* bgr = nullptr;
-  hipGraphExec_t graph_exec = nullptr;  // pm_capture_* / pm_replay
+  pm::GraphExec graph_exec;  // pm_capture_* / pm_replay
   bool capturing = false;
   bool no_tiled = false;        // PM_NO_TILED (experiment knob), read once by pm_create
-  hipEvent_t ext_fork = nullptr, ext_join = nullptr;  // pm_match_view_device: caller stream <-> handle stream
-  hipEvent_t left_out = nullptr;  // pm_match_u8: the left map has arrived in the pinned buffer
-  hipEvent_t right_out = nullptr;  // ... the right one
-  pm::CopyPool* copy_pool = nullptr;  // host threads sharing the pack / unpack copies of the host-buffer entry points
-  hipStream_t s_in = nullptr, s_out = nullptr;
+  pm::Event ext_fork, ext_join;  // pm_match_view_device: caller stream <-> handle stream
+  pm::Event left_out;   // pm_match_u8: the left map has arrived in the pinned buffer
+  pm::Event right_out;  // ... the right one
+  std::unique_ptr<pm::CopyPool> copy_pool;  // host threads sharing the pack / unpack copies of the host-buffer entry points
   std::vector<PipeSlot> pipe;
   int pipe_head = 0, pipe_count = 0;
   int seq_last = -1;  // ring slot of the frame enqueued last (is the device still busy with it?), -1: none
@@ -218,6 +214,17 @@ enum StreamKind { kStreamMain = 0, kStreamView = 1, kStreamCopy = 2, kStreamLane
 hipError_t create_stream(hipStream_t* s, int kind, int prio_class);
 int create_handle_streams(pm_handle* h);  // the handle's four streams, together (pm_engine.hip)
 
+// Two untimed events that exist together or not at all (the lazily created pairs test the first one only).
+inline hipError_t create_event_pair(Event& a, Event& b) {
+  Event x, y;
+  hipError_t e = x.create(hipEventDisableTiming);
+  if (e == hipSuccess) e = y.create(hipEventDisableTiming);
+  if (e != hipSuccess) return e;
+  a = std::move(x);
+  b = std::move(y);
+  return hipSuccess;
+}
+
 // Brackets the launches of one kernel class with a pair of events while the handle is profiling.
 // While the handle is profiling, the launches of one kernel class are bracketed by events on the stream they go to.  An
 // in-stream event before a launch fires when the launch in front of it has finished: the stop event of the previous
@@ -247,14 +254,12 @@ struct Launch {
         prof_break(h, stream);
         return;
       }
-      EventRec r;
-      r.klass = k;
-      r.start_ref = -1;
-      if (hipEventCreate(&r.start) != hipSuccess || hipEventCreate(&r.stop) != hipSuccess) {
+      EventRec r;  // a pair or nothing: a lone start event goes with `r`
+      if (r.start.create(hipEventDefault) != hipSuccess || r.stop.create(hipEventDefault) != hipSuccess) {
         timed = false;
         return;
       }
-      h->ev_pool.push_back(r);
+      h->ev_pool.push_back(std::move(r));
     }
     rec = h->ev_used++;
     EventRec& r = h->ev_pool[rec];
@@ -288,7 +293,7 @@ int ensure_noise(pm_handle* h, int rows, int cols);
 void abort_capture(pm_handle* h);
 int refuse_while_capturing(pm_handle* h, const char* what);
 int capture_open(pm_handle* h);                                             // pm_engine.hip
-int capture_close(pm_handle* h, hipGraphExec_t* exec, const char* what);
+int capture_close(pm_handle* h, GraphExec* exec, const char* what);  // *exec: empty
 bool pair_planes_wanted(const pm_handle* h);
 int pair_planes_alloc(pm_handle* h, hipStream_t stream);
 int match_device_impl(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
@@ -303,7 +308,7 @@ int pair_chunk();
 bool seq_pipelined(const pm_handle* h);
 int seq_enqueue_chunk(pm_handle* h, int b, int c, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
                       const float* d_seed_l, const float* d_seed_r, float* d_disp_l, float* d_disp_r, hipEvent_t ready,
-                      hipEvent_t ready2, hipEvent_t v_done[2], hipEvent_t head_done);
+                      hipEvent_t ready2, const Event v_done[2], hipEvent_t head_done);
 SeedParams seed_params(const pm_params& p);
 int alloc_seed_scratch(pm_handle* h, SeedScratch& sc, hipStream_t stream);
 // SparseInit (or Patchmatch::Initialize(.., 1)) for view `view` of pair `b` straight into its disparity plane

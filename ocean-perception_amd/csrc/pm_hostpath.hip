@@ -15,7 +15,7 @@ namespace {
 bool host_pinned(const pm_handle* h, const void* p, size_t span) {
   const char* c = (const char*)p;
   for (const auto& r : h->host_ranges)
-    if (c >= r.base && c + span <= r.base + r.bytes) return true;
+    if (c >= r.base() && c + span <= r.base() + r.bytes()) return true;
   return false;
 }
 size_t span_bytes(int rows, size_t step, size_t row_bytes) { return (size_t)(rows - 1) * step + row_bytes; }
@@ -38,10 +38,10 @@ int upload_plane(pm_handle* h, void* d_dst, const void* src, size_t step, size_t
 // the device's address of page-locked host memory, or null
 char* host_dev_address(const pm_handle* h, const void* p, size_t span) {
   const char* c = (const char*)p;
-  if (h->pinned_dev && c >= (const char*)h->pinned && c + span <= (const char*)h->pinned + h->pinned_bytes)
-    return h->pinned_dev + (c - (const char*)h->pinned);
+  const auto within = [&](const HostBuf& r) { return r.dev() && c >= r.base() && c + span <= r.base() + r.bytes(); };
+  if (within(h->pinned)) return h->pinned.dev() + (c - h->pinned.base());
   for (const auto& r : h->host_ranges)
-    if (r.dev_base && c >= r.base && c + span <= r.base + r.bytes) return r.dev_base + (c - r.base);
+    if (within(r)) return r.dev() + (c - r.base());
   return nullptr;
 }
 
@@ -73,7 +73,7 @@ struct PinnedSlot {
 };
 PinnedSlot pinned_slot(pm_handle* h, int slot, size_t px) {
   const size_t tight = (size_t)h->max_rows * h->max_cols;
-  char* base = (char*)h->pinned + (size_t)slot * tight * (2 + 4 * sizeof(float));
+  char* base = h->pinned.base() + (size_t)slot * tight * (2 + 4 * sizeof(float));
   PinnedSlot p;
   p.sl = (float*)base;  // floats first so every sub-buffer stays 4-byte aligned
   p.sr = p.sl + px;
@@ -85,7 +85,7 @@ PinnedSlot pinned_slot(pm_handle* h, int slot, size_t px) {
 }
 
 int pipe_init(pm_handle* h) {
-  if (!h->copy_pool) h->copy_pool = new pm::CopyPool();
+  if (!h->copy_pool) h->copy_pool.reset(new pm::CopyPool());
   if (int rc = seq_events_create(h)) return rc;
   if (seq_pipelined(h))
     if (int rc = view_streams_create(h)) return rc;
@@ -307,7 +307,7 @@ int finish_frame(pm_handle* h, int slot, float* out_l, float* out_r, size_t out_
 // call: the caller is told "not done" and is free to reuse its buffers.  Every ring slot outside the frames in flight
 // is free again, and with none in flight, none was enqueued last.
 void drain_after_failure(pm_handle* h) {
-  for (hipStream_t q : {h->stream, h->view1_stream, h->s_in, h->s_out})
+  for (hipStream_t q : {h->stream.get(), h->view1_stream.get(), h->s_in.get(), h->s_out.get()})
     if (q) (void)hipStreamSynchronize(q);
   (void)hipGetLastError();
   for (int i = h->pipe_count; i < h->max_batch; ++i) h->pipe[(size_t)((h->pipe_head + i) % h->max_batch)].state = 0;
@@ -372,24 +372,19 @@ int pm_host_alloc(pm_handle* h, size_t bytes, void** ptr) {
   if (!h || !ptr || bytes == 0) return PM_ERR_INVALID_ARG;
   *ptr = nullptr;
   PM_HIP(h, hipSetDevice(h->device));
-  void* p = nullptr;
-  PM_HIP(h, hipHostMalloc(&p, bytes, hipHostMallocDefault));
-  void* dp = nullptr;
-  if (hipHostGetDevicePointer(&dp, p, 0) != hipSuccess) dp = nullptr;
-  (void)hipGetLastError();
-  h->host_ranges.push_back({(char*)p, bytes, true, (char*)dp});
-  *ptr = p;
+  HostBuf buf;
+  PM_HIP(h, buf.alloc(bytes));
+  *ptr = buf.base();
+  h->host_ranges.push_back(std::move(buf));
   return PM_OK;
 }
 
 int pm_host_register(pm_handle* h, void* ptr, size_t bytes) {
   if (!h || !ptr || bytes == 0) return PM_ERR_INVALID_ARG;
   PM_HIP(h, hipSetDevice(h->device));
-  PM_HIP(h, hipHostRegister(ptr, bytes, hipHostRegisterMapped));
-  void* dp = nullptr;
-  if (hipHostGetDevicePointer(&dp, ptr, 0) != hipSuccess) dp = nullptr;
-  (void)hipGetLastError();
-  h->host_ranges.push_back({(char*)ptr, bytes, false, (char*)dp});
+  HostBuf buf;
+  PM_HIP(h, buf.lock(ptr, bytes));
+  h->host_ranges.push_back(std::move(buf));
   return PM_OK;
 }
 
@@ -400,15 +395,13 @@ static int host_release(pm_handle* h, void* ptr, bool owned, const char* what) {
     return PM_ERR_BUSY;
   }
   for (size_t i = 0; i < h->host_ranges.size(); ++i) {
-    if (h->host_ranges[i].base != (char*)ptr || h->host_ranges[i].owned != owned) continue;
+    if (h->host_ranges[i].base() != (char*)ptr || h->host_ranges[i].owned() != owned) continue;
     PM_HIP(h, hipSetDevice(h->device));
     // a synchronous entry point may have left a DMA into this range running only if it returned an error; be safe
     PM_HIP(h, hipStreamSynchronize(h->stream));
+    const hipError_t e = h->host_ranges[i].release();  // the range is forgotten whatever the runtime answers
     h->host_ranges.erase(h->host_ranges.begin() + (long)i);
-    if (owned)
-      PM_HIP(h, hipHostFree(ptr));
-    else
-      PM_HIP(h, hipHostUnregister(ptr));
+    PM_HIP(h, e);
     return PM_OK;
   }
   set_err(h, "%s: %p is not the start of a range this handle %s", what, ptr, owned ? "allocated" : "registered");
@@ -526,7 +519,7 @@ int pm_match_u8(pm_handle* h, const uint8_t* left, const uint8_t* right, int row
   const PinnedSlot ps = pinned_slot(h, 0, px);
   // every plane goes up as soon as it is ready -- by DMA from the caller's buffer if that is page-locked, else packed
   // into the pinned slab by a few host threads (pm_hostcopy.hpp): the DMA of one plane runs while the host packs the next
-  if (!h->copy_pool) h->copy_pool = new pm::CopyPool();
+  if (!h->copy_pool) h->copy_pool.reset(new pm::CopyPool());
   HP(mark(1));
   // A small pair in ordinary (not page-locked) memory: both images are packed back to back into the pinned slab and go up
   // as ONE copy, made by a few wavefronts reading the slab through its device address -- a DMA copy per image costs
@@ -557,10 +550,7 @@ int pm_match_u8(pm_handle* h, const uint8_t* left, const uint8_t* right, int row
     return rc;
   HP(mark(3));
   // the left map is unpacked into the caller's buffer while the right one is still on the bus
-  if (!h->left_out) {
-    PM_HIP(h, hipEventCreateWithFlags(&h->left_out, hipEventDisableTiming));
-    PM_HIP(h, hipEventCreateWithFlags(&h->right_out, hipEventDisableTiming));
-  }
+  if (!h->left_out) PM_HIP(h, create_event_pair(h->left_out, h->right_out));
   bool direct_l = false, direct_r = false;
   if (int rc = download_plane(h, disp_l, disp_step, h->st_disp_l, frow, rows, ps.dl, h->stream, &direct_l)) return rc;
   PM_HIP(h, hipEventRecord(h->left_out, h->stream));

@@ -25,10 +25,13 @@
 #include <cstring>
 #include <initializer_list>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "pm/patchmatch.h"
 #include "pm/testing.h"
+#include "pm_devbuf.hpp"
+#include "pm_hipres.hpp"
 #include "pm_internal.hpp"
 
 namespace {
@@ -41,17 +44,18 @@ struct Band {
   hipStream_t stream = nullptr;
   pm_tile tile{};
   int band_rows = 0;
-  uint8_t *d_left = nullptr, *d_right = nullptr;
-  float *d_seed_l = nullptr, *d_seed_r = nullptr, *d_out_l = nullptr, *d_out_r = nullptr;
-  float* sent[2] = {nullptr, nullptr};  // the boundary row this band hands to its successor (double-buffered)
-  float *used = nullptr, *incoming = nullptr;
-  int *mask = nullptr, *flag = nullptr;
-  hipEvent_t ev_sent[2] = {nullptr, nullptr};  // sent[i] is written (this band's event, this band's stream)
+  // what the band owns goes with it, in pm_tiled_destroy with the band's device current
+  pm::DevBuf<uint8_t> d_left, d_right;
+  pm::DevBuf<float> d_seed_l, d_seed_r, d_out_l, d_out_r;
+  pm::DevBuf<float> sent[2];  // the boundary row this band hands to its successor (double-buffered)
+  pm::DevBuf<float> used, incoming;
+  pm::DevBuf<int> mask, flag;
+  pm::Event ev_sent[2];  // sent[i] is written (this band's event, this band's stream)
   // this band, as the READER of its predecessor's sent[i], has consumed it: [sweep direction: 0 down, 1 up][i].
   // Created on THIS band's device and recorded on THIS band's stream; the predecessor waits for it.
-  hipEvent_t ev_done[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-  hipEvent_t unread[2] = {nullptr, nullptr};  // the reader's ev_done that guards sent[i], or null: nobody is reading it
-  hipEvent_t ev_probe = nullptr;  // logical-device plans only: an event nobody waits for (pm_tiled_debug_inject)
+  pm::Event ev_done[2][2];
+  hipEvent_t unread[2] = {nullptr, nullptr};  // the reader's ev_done that guards sent[i] (not owned), or null: nobody is reading it
+  pm::Event ev_probe;  // logical-device plans only: an event nobody waits for (pm_tiled_debug_inject)
   int last = 0;  // the buffer of `sent` that holds the row this band published last
   // peer access is enabled in both directions between this band's device and its neighbour's (pm_tiled_create)
   bool peer_prev = false, peer_next = false;
@@ -151,18 +155,19 @@ hipError_t rt_use(pm_tiled_plan* p, const Band& b) {
   }
   return e;
 }
-hipError_t rt_malloc(pm_tiled_plan* p, const Band& b, void** out, size_t bytes) {
-  const hipError_t e = hipMalloc(out, bytes);
+template <typename T>
+hipError_t rt_malloc(pm_tiled_plan* p, const Band& b, pm::DevBuf<T>& out, size_t bytes) {
+  const hipError_t e = out.alloc(bytes);
   if (p->audit) {
-    if (e == hipSuccess) p->audit->mem.push_back({(const char*)*out, bytes, p->audit->cur});
+    if (e == hipSuccess) p->audit->mem.push_back({(const char*)out.get(), bytes, p->audit->cur});
     au_log(p, PM_TILED_CALL_MALLOC, b.index, 0, false, -1, true, b.ldev, false, -1, false);
   }
   return e;
 }
-hipError_t rt_event_create(pm_tiled_plan* p, const Band& b, hipEvent_t* ev) {
-  const hipError_t e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+hipError_t rt_event_create(pm_tiled_plan* p, const Band& b, pm::Event& ev) {
+  const hipError_t e = ev.create(hipEventDisableTiming);
   if (p->audit) {
-    if (e == hipSuccess) p->audit->obj[(const void*)*ev] = p->audit->cur;  // an event belongs to the device current at its creation
+    if (e == hipSuccess) p->audit->obj[(const void*)ev.get()] = p->audit->cur;  // an event belongs to the device current at its creation
     au_log(p, PM_TILED_CALL_EVENT_CREATE, b.index, 0, false, -1, true, b.ldev, false, -1, false);
   }
   return e;
@@ -441,9 +446,7 @@ int attempt(pm_tiled_plan* p, int rounds, bool* moved, int* exchanges) {
                      pm_tile_exchange_round(b.h, it, k, pred_row(b), b.incoming, b.used, b.incoming, b.mask),
                      {b.incoming, false}, {b.used, false}, {b.incoming, false}, {b.mask, false});
           }
-          float* t = b.used;
-          b.used = b.incoming;
-          b.incoming = t;
+          std::swap(b.used, b.incoming);
         }
       }
       // did my boundary row move after the last row I sent?  then my successor is stale (only bands that HAVE one ask)
@@ -588,25 +591,25 @@ int create(pm_handle* const* bands, int n_bands, int rows, int cols, const int* 
     TL_HIP(p, rt_use(p, b));
     const size_t px = (size_t)b.band_rows * cols, own = (size_t)b.tile.own_rows * cols;
     const size_t row_bytes = sizeof(float) * (size_t)p->n_views * cols;
-    TL_HIP(p, rt_malloc(p, b, (void**)&b.d_left, px));
-    TL_HIP(p, rt_malloc(p, b, (void**)&b.d_right, px));
-    TL_HIP(p, rt_malloc(p, b, (void**)&b.d_seed_l, px * 4));
-    TL_HIP(p, rt_malloc(p, b, (void**)&b.d_seed_r, px * 4));
-    TL_HIP(p, rt_malloc(p, b, (void**)&b.d_out_l, own * 4));
-    TL_HIP(p, rt_malloc(p, b, (void**)&b.d_out_r, own * 4));
+    TL_HIP(p, rt_malloc(p, b, b.d_left, px));
+    TL_HIP(p, rt_malloc(p, b, b.d_right, px));
+    TL_HIP(p, rt_malloc(p, b, b.d_seed_l, px * 4));
+    TL_HIP(p, rt_malloc(p, b, b.d_seed_r, px * 4));
+    TL_HIP(p, rt_malloc(p, b, b.d_out_l, own * 4));
+    TL_HIP(p, rt_malloc(p, b, b.d_out_r, own * 4));
     for (int i = 0; i < 2; ++i) {
-      TL_HIP(p, rt_malloc(p, b, (void**)&b.sent[i], row_bytes));
-      TL_HIP(p, rt_event_create(p, b, &b.ev_sent[i]));
-      TL_HIP(p, rt_event_create(p, b, &b.ev_done[0][i]));
-      TL_HIP(p, rt_event_create(p, b, &b.ev_done[1][i]));
+      TL_HIP(p, rt_malloc(p, b, b.sent[i], row_bytes));
+      TL_HIP(p, rt_event_create(p, b, b.ev_sent[i]));
+      TL_HIP(p, rt_event_create(p, b, b.ev_done[0][i]));
+      TL_HIP(p, rt_event_create(p, b, b.ev_done[1][i]));
     }
-    TL_HIP(p, rt_malloc(p, b, (void**)&b.used, row_bytes));
-    TL_HIP(p, rt_malloc(p, b, (void**)&b.incoming, row_bytes));
-    TL_HIP(p, rt_malloc(p, b, (void**)&b.mask, sizeof(int) * (size_t)p->n_views * cols));
-    TL_HIP(p, rt_malloc(p, b, (void**)&b.flag, sizeof(int)));
+    TL_HIP(p, rt_malloc(p, b, b.used, row_bytes));
+    TL_HIP(p, rt_malloc(p, b, b.incoming, row_bytes));
+    TL_HIP(p, rt_malloc(p, b, b.mask, sizeof(int) * (size_t)p->n_views * cols));
+    TL_HIP(p, rt_malloc(p, b, b.flag, sizeof(int)));
     if (p->audit) {  // (not counted among a band's events by the tests: created outside the audited layer)
-      TL_HIP(p, hipEventCreateWithFlags(&b.ev_probe, hipEventDisableTiming));
-      p->audit->obj[(const void*)b.ev_probe] = b.ldev;
+      TL_HIP(p, b.ev_probe.create(hipEventDisableTiming));
+      p->audit->obj[(const void*)b.ev_probe.get()] = b.ldev;
       TL_HIP(p, hipEventRecord(b.ev_probe, b.stream));
     }
   }
@@ -687,16 +690,7 @@ void pm_tiled_destroy(pm_tiled_plan* plan) {
   for (Band& b : plan->bands) {
     (void)rt_use(plan, b);
     if (b.stream) (void)rt_sync(plan, b);
-    void* bufs[] = {b.d_left, b.d_right, b.d_seed_l, b.d_seed_r, b.d_out_l, b.d_out_r, b.sent[0], b.sent[1],
-                    b.used,   b.incoming, b.mask,    b.flag};
-    for (void* q : bufs)
-      if (q) (void)hipFree(q);
-    for (int i = 0; i < 2; ++i) {
-      if (b.ev_sent[i]) (void)hipEventDestroy(b.ev_sent[i]);
-      for (int d = 0; d < 2; ++d)
-        if (b.ev_done[d][i]) (void)hipEventDestroy(b.ev_done[d][i]);
-    }
-    if (b.ev_probe) (void)hipEventDestroy(b.ev_probe);
+    b = Band();  // the band's buffers and events go here, with its device current
   }
   delete plan->audit;
   delete plan;

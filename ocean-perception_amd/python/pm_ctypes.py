@@ -35,6 +35,8 @@ EXPORTS = [
     "pm_host_alloc", "pm_host_free", "pm_host_register", "pm_host_unregister",
     "pm_capture_begin", "pm_capture_end", "pm_replay", "pm_debug_capture_fork",
     "pm_debug_live_device_allocations", "pm_debug_live_device_bytes",
+    "pm_debug_live_events", "pm_debug_live_streams", "pm_debug_live_host_buffers", "pm_debug_live_host_bytes",
+    "pm_debug_live_graph_execs",
     "pm_disp_to_range", "pm_remove_backscatter", "pm_correct_attenuation", "pm_range_enhance",
     "pm_compute_intensity", "pm_find_dark", "pm_stereo_ready", "pm_gaussian_blur", "pm_normalize",
     "pm_normalize_color_illuminant", "pm_match_bgr_device", "pm_device_malloc", "pm_device_free", "pm_upload", "pm_download",
@@ -229,7 +231,9 @@ def load():
     lib.pm_host_unregister.restype = C.c_int
     lib.pm_debug_capture_fork.argtypes = [vp]
     lib.pm_debug_capture_fork.restype = C.c_int
-    for name in ("pm_debug_live_device_allocations", "pm_debug_live_device_bytes"):
+    for name in ("pm_debug_live_device_allocations", "pm_debug_live_device_bytes", "pm_debug_live_events",
+                 "pm_debug_live_streams", "pm_debug_live_host_buffers", "pm_debug_live_host_bytes",
+                 "pm_debug_live_graph_execs"):
         getattr(lib, name).argtypes = []
         getattr(lib, name).restype = C.c_longlong
     lib.pm_in_flight.argtypes = [vp]

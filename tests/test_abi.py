@@ -106,15 +106,15 @@ def test_the_shipped_library_carries_no_tuning_knob():
 def test_device_memory_is_allocated_by_its_one_owner_only():
     """Every device allocation of a handle goes through csrc/pm_devbuf.hpp, whose counters tests/test_ownership.py
     reads: an allocation made beside it would not be counted.  hipMalloc / hipFree may appear in that header, in
-    pm_tiled.hip (whose rt_* layer logs its own), in pm_device_malloc / pm_device_free (memory handed to the caller)
-    and in the PM_RUN3_STATS block of pm_run3.hpp (analysis builds)."""
+    pm_device_malloc / pm_device_free (memory handed to the caller) and in the PM_RUN3_STATS block of pm_run3.hpp
+    (analysis builds)."""
     src = os.path.join(ROOT, "ocean-perception_amd", "csrc")
     # every device allocator and its free (hipMallocAsync, hipMallocManaged, hipExtMallocWithFlags ...); hipHostMalloc /
-    # hipHostFree are page-locked HOST memory and not the owner's business
+    # hipHostFree are page-locked HOST memory and the business of the next test
     call = re.compile(r"\bhip(?:Ext)?Malloc\w*\(|\bhipFree(?:Async)?\(")
     found = {}
     for f in sorted(os.listdir(src)):
-        if f in ("pm_devbuf.hpp", "pm_tiled.hip") or not os.path.isfile(os.path.join(src, f)):  # (not experimental/)
+        if f == "pm_devbuf.hpp" or not os.path.isfile(os.path.join(src, f)):  # (not experimental/)
             continue
         text = open(os.path.join(src, f)).read()
         if f == "pm_imaging.hip":
@@ -130,6 +130,37 @@ def test_device_memory_is_allocated_by_its_one_owner_only():
             found[f] = [m.group(0) for m in call.finditer(text)]
     assert found == {}, found
     assert len(call.findall(open(os.path.join(src, "pm_devbuf.hpp")).read())) == 2  # one of each
+
+
+def test_events_streams_pinned_memory_and_graphs_have_one_owner_only():
+    """The same for everything else a handle or a tiled plan takes from the runtime: events, streams, page-locked host
+    memory and instantiated graphs are created and released in csrc/pm_hipres.hpp alone, whose counters
+    tests/test_ownership.py reads.  The one exception is the creation of a stream, which pm_engine.hip::create_stream does
+    (it knows the priority classes) for the owner to adopt."""
+    src = os.path.join(ROOT, "ocean-perception_amd", "csrc")
+    create_stream = re.compile(r"\bhip(?:Ext)?StreamCreate\w*\(")
+    call = re.compile(r"\bhipEventCreate\w*\(|\bhipEventDestroy\(|\bhip(?:Ext)?StreamCreate\w*\(|\bhipStreamDestroy\(|"
+                      r"\bhipHostMalloc\(|\bhipHostAlloc\(|\bhipHostFree\(|\bhipHostRegister\(|\bhipHostUnregister\(|"
+                      r"\bhipGraphInstantiate\w*\(|\bhipGraphExecDestroy\(")
+    found = {}
+    for f in sorted(os.listdir(src)):
+        if f == "pm_hipres.hpp" or not os.path.isfile(os.path.join(src, f)):  # (not experimental/)
+            continue
+        text = open(os.path.join(src, f)).read()
+        if f == "pm_engine.hip":
+            start = text.index("hipError_t create_stream(")
+            end = text.index("\n}\n", start)
+            assert len(create_stream.findall(text[start:end])) == 3  # default class, CU mask, priority
+            assert call.findall(text[start:end]) == create_stream.findall(text[start:end])
+            text = text[:start] + text[end:]
+        if call.search(text):
+            found[f] = [m.group(0) for m in call.finditer(text)]
+    assert found == {}, found
+    owner = open(os.path.join(src, "pm_hipres.hpp")).read()
+    assert not create_stream.search(owner)
+    assert sorted(m.group(0) for m in call.finditer(owner)) == [
+        "hipEventCreateWithFlags(", "hipEventDestroy(", "hipGraphExecDestroy(", "hipGraphInstantiate(", "hipHostFree(",
+        "hipHostMalloc(", "hipHostRegister(", "hipHostUnregister(", "hipStreamDestroy("]  # one of each
 
 
 def _has_gpu():

@@ -1,6 +1,8 @@
-"""Every device allocation of a handle has one owner (csrc/pm_devbuf.hpp): the process-wide counters of live
-allocations / bytes (include/pm/testing.h) return to where they were after pm_destroy -- also after a pm_create that
-failed half way -- and every scratch buffer that grows on demand gives the same bits small -> large -> small."""
+"""Everything a handle or a tiled plan takes from the runtime has one owner -- device allocations csrc/pm_devbuf.hpp;
+events, streams, page-locked host memory and instantiated graphs csrc/pm_hipres.hpp: the process-wide counters of what
+is live (include/pm/testing.h) return to where they were after pm_destroy / pm_tiled_destroy -- also after a pm_create
+that failed half way -- and every scratch buffer that grows on demand gives the same bits small -> large -> small."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -20,9 +22,12 @@ def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
+Live = collections.namedtuple("Live", "device_allocations device_bytes events streams host_buffers host_bytes graph_execs")
+
+
 def _live(pm):
     lib = pm.load()
-    return lib.pm_debug_live_device_allocations(), lib.pm_debug_live_device_bytes()
+    return Live(*(getattr(lib, "pm_debug_live_" + name)() for name in Live._fields))
 
 
 # the seeder's template, search range and cornerSubPix window cut down to what a 16x24 image holds
@@ -37,12 +42,25 @@ PARAM_SETS = {
 }
 
 
-def _exercise_every_lazy_family(pm, synth, e, seeded, tile):
-    """One call of every family that allocates on first use, at 16x24 on a 32x48 plan of two pairs."""
+def _exercise_every_lazy_family(pm, synth, e, seeded, scalar):
+    """One call of every family that allocates, or creates events, a graph or page-locked memory, on first use, at 16x24
+    on a 32x48 plan of two pairs.  Returns what has to outlive the handle."""
     import torch
     rows, cols = 16, 24
     l, r, sl, sr, _ = small_pair(synth, 3, rows, cols, n_points=6, dilate_factor=1)
-    e.match(l, r, *((sl, sr) if seeded else ()))                                       # pm_match_u8
+    seeds = (sl, sr) if seeded else ()
+    e.match(l, r, *seeds)                                                              # pm_match_u8: left_out / right_out
+    e.match_batch([l, l], [r, r], *([s, s] for s in seeds))                            # the ring-slot and view events
+    e.submit(l, r, *seeds)
+    e.collect()
+    e.profile_enable(True)                                                             # the pool of timed event pairs
+    e.match(l, r, *seeds)
+    e.profile_read()
+    e.profile_enable(False)
+    kept = e.host_alloc((rows, cols), np.float32, owned=True)  # never freed: pm_destroy gives it back (not touched after)
+    mine = np.empty((rows, cols), np.float32)                  # never unregistered either; the memory stays numpy's
+    e.host_register(mine)
+    del kept
     bgr8 = np.stack([color_image(rows, cols, 5 + i) for i in range(4)])
     B = _dev(bgr8)
     J = torch.empty((rows, cols, 3), device="cuda")
@@ -61,28 +79,54 @@ def _exercise_every_lazy_family(pm, synth, e, seeded, tile):
                        D[0].data_ptr(), D[1].data_ptr())
     mask = torch.empty((rows, cols), dtype=torch.uint8, device="cuda")
     e.foreground_texture_mask(L.data_ptr(), rows, cols, 4, 10.0, 2, mask.data_ptr())
-    if tile:  # the top band of a taller image (scalar mode only: the plane mode has no tile API)
-        SL, SR = _dev(sl), _dev(sr)
+    SL, SR = _dev(sl), _dev(sr)
+    if scalar:  # one view on a foreign stream: ext_fork / ext_join
+        IL, IR, GL, GR = (_dev(a.astype(np.float32)) for a in (l, r, e.gradient_magnitude(l), e.gradient_magnitude(r)))
+        DV = SL.clone()
+        torch.cuda.synchronize()
+        side = torch.cuda.Stream()
+        e.match_view_device(IL.data_ptr(), IR.data_ptr(), GL.data_ptr(), GR.data_ptr(), rows, cols, 0, DV.data_ptr(), 0,
+                            stream=side.cuda_stream)
+        side.synchronize()
+    if scalar and seeded:  # a captured Match() on caller seeds (what tests/test_gpu_parity.py captures), run once before
+        run = lambda: e.match_device(1, L.data_ptr(), R.data_ptr(), rows, cols, SL.data_ptr(), SR.data_ptr(),
+                                     D[0].data_ptr(), D[1].data_ptr())
+        run()
+        e.synchronize()
+        e.capture_begin()
+        run()
+        e.capture_end()
+        e.replay()
+        e.synchronize()
+    if scalar:  # the top band of a taller image (scalar mode only: the plane mode has no tile API)
         e.tile_begin(pm.PmTile(rows + 100, 0, 0, rows - 5), L.data_ptr(), R.data_ptr(), rows, cols, SL.data_ptr(),
                      SR.data_ptr())
         e.tile_snapshot()
     e.synchronize()
+    return mine
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", sorted(PARAM_SETS))
 def test_create_use_destroy_returns_every_byte(pm, synth, name):
-    params, tile = PARAM_SETS[name](pm)
+    params, scalar = PARAM_SETS[name](pm)
     seeded = not params.sparse_init
     before = _live(pm)
     for cycle in range(5):
         with pm.Engine(params, max_rows=32, max_cols=48, max_batch=2) as e:
             created = _live(pm)
-            assert created[0] > before[0] and created[1] > before[1]
-            _exercise_every_lazy_family(pm, synth, e, seeded, tile)
+            assert created.device_allocations > before.device_allocations and created.device_bytes > before.device_bytes
+            assert created.streams > before.streams, "the handle's streams are counted"
+            assert created.host_buffers > before.host_buffers and created.host_bytes > before.host_bytes, "the staging slab"
+            registered = _exercise_every_lazy_family(pm, synth, e, seeded, scalar)
             used = _live(pm)
-            assert used[0] > created[0] and used[1] > created[1], "the lazily allocated buffers are counted too"
-        assert _live(pm) == before, "cycle %d: %r allocations / bytes live, %r before the create" % (cycle, _live(pm), before)
+            assert used.device_allocations > created.device_allocations and used.device_bytes > created.device_bytes, \
+                "the lazily allocated buffers are counted too"
+            assert used.events > created.events, "the lazily created events are counted"
+            assert used.host_buffers == created.host_buffers + 2 and used.host_bytes == created.host_bytes + 2 * registered.nbytes
+            assert used.graph_execs == created.graph_execs + (1 if scalar and seeded else 0)
+        assert _live(pm) == before, "cycle %d: %r live, %r before the create" % (cycle, _live(pm), before)
+        registered[:] = 1.0  # the registered array was only unlocked: it is still numpy's memory
 
 
 @pytest.mark.gpu
@@ -99,7 +143,9 @@ def test_create_that_fails_half_way_leaks_nothing(pm):
     text = lib.pm_last_error(h).decode()
     assert "KB of LDS per tile" in text and "max_disp 1024" in text, text
     held = _live(pm)
-    assert held[0] > before[0] and held[1] > before[1], "the create got as far as allocating"
+    assert held.device_allocations > before.device_allocations and held.device_bytes > before.device_bytes, \
+        "the create got as far as allocating"
+    assert held.streams > before.streams, "... with its streams live"
     lib.pm_destroy(h)
     assert _live(pm) == before
 
@@ -208,15 +254,50 @@ def test_noise_table_is_rebuilt_for_each_size(engine, oracle, synth):
         assert_same(dr, er, "right %dx%d" % (cols, rows))
 
 
+@pytest.fixture(scope="module")
+def two_band_pair(oracle, synth):
+    """A 64x48 pair for two bands and its untiled maps: (left, right, seed_l, seed_r, want_l, want_r)."""
+    l, r, sl, sr, _ = small_pair(synth, 8, 64, 48, n_points=12, dilate_factor=2)
+    el, er = oracle.match(oracle.default_params(0, patch=5, n_iters=2, nthreads=4), l, r, sl, sr)
+    return l, r, sl, sr, el, er
+
+
 @pytest.mark.gpu
-def test_noise_table_of_a_band_grows_past_the_plan(pm, oracle, synth):
+def test_noise_table_of_a_band_grows_past_the_plan(pm, two_band_pair):
     """Two bands of a 64x48 image: each handle's plan holds its band only, its noise table the whole image's rows."""
     import tiled
-    rows, cols = 64, 48
-    l, r, sl, sr, _ = small_pair(synth, 8, rows, cols, n_points=12, dilate_factor=2)
+    l, r, sl, sr, el, er = two_band_pair
+    rows, cols = l.shape
     params = pm.default_params(0, patch=5, patchmatch_iters=2)
     assert tiled.band_of(0, 2, rows, tiled.halo_rows(params))[3] < rows
     dl, dr, _ = tiled.match_tiled_local(params, l, r, sl, sr, 2, pipelined=True)
-    el, er = oracle.match(oracle.default_params(0, patch=5, n_iters=2, nthreads=4), l, r, sl, sr)
     assert_same(dl, el, "tiled vs oracle (left)")
     assert_same(dr, er, "tiled vs oracle (right)")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("logical", [None, [0, 1]])
+def test_a_tiled_plan_returns_everything(pm, two_band_pair, logical):
+    """pm_tiled_create / pm_tiled_match_u8 / pm_tiled_destroy over two band handles: a band's twelve buffers and six
+    events (seven with the probe event of a logical-device plan) are counted while the plan lives and gone after it."""
+    l, r, sl, sr, el, er = two_band_pair
+    rows, cols = l.shape
+    params = pm.default_params(0, patch=5, patchmatch_iters=2)
+    n = 2
+    before = _live(pm)
+    band_rows = pm.load().pm_tiled_band_rows(C.byref(params), rows, n)
+    handles = [pm.Engine(params, max_rows=band_rows, max_cols=cols) for _ in range(n)]
+    alone = _live(pm)  # what the band handles hold by themselves
+    for h in handles:
+        h.close()
+    assert _live(pm) == before
+    with pm.TiledEngine(params, rows, cols, n, logical_devices=logical) as t:
+        planned = _live(pm)
+        assert planned.device_allocations == alone.device_allocations + 12 * n and planned.device_bytes > alone.device_bytes
+        assert planned.events == alone.events + (7 if logical else 6) * n
+        assert planned.streams == alone.streams and planned.host_buffers == alone.host_buffers
+        dl, dr, _ = t.match(l, r, sl, sr)
+        assert_same(dl, el, "tiled vs oracle (left)")
+        assert_same(dr, er, "tiled vs oracle (right)")
+        assert _live(pm).device_allocations >= planned.device_allocations and _live(pm).events >= planned.events
+    assert _live(pm) == before
