@@ -180,6 +180,34 @@ int pm_match_raw_device(pm_handle* h, int n, const pm_rectify_view* left, const 
                         const uint8_t* d_left_raw, const uint8_t* d_right_raw, int src_rows, int src_cols,
                         size_t src_step, int rows, int cols, const float* d_seed_l, const float* d_seed_r,
                         float* d_disp_l, float* d_disp_r);
+/* ---- the same for colour cameras: interleaved 8-bit BGR -------------------------------------------------------------
+ * Every colour stage (pm_match_bgr_device, pm_stereo_ready, pm_range_enhance and the stages it is made of) takes an
+ * interleaved BGR image that is already rectified.  The definition (tests/rectify_bgr_ref.py) is the one above, channel by
+ * channel at the SAME Q5 coordinates: one border_value for the three channels, one mask per image, the same map
+ * (pm_rectify_map).  The kernel evaluates the geometry once per destination pixel and shares the position, the weights and
+ * the mask among the channels.  Bit for bit, like pm_rectify_u8.
+ *
+ * n raw images [n][src_rows] rows of src_step BYTES (0 = packed = 3 * src_cols) -> n rectified images, packed.  At least
+ * one of d_dst_bgr8 and d_dst_bgr32f: the float image is (float)byte * (float)(1.0 / 255.0), one binary32 multiplication
+ * (CastImage3bTo3f, image_util.cpp:25-31), the form the range-dependent stages take.  d_valid and stream as in
+ * pm_rectify_u8.  PM_ERR_INVALID_ARG as for pm_rectify_u8, also for src_step smaller than 3 * src_cols and for a call
+ * without an image output; nothing is enqueued then. */
+int pm_rectify_bgr8(pm_handle* h, const pm_rectify_view* view, const uint8_t* d_src_bgr8, int n, int src_rows,
+                    int src_cols, size_t src_step, int rows, int cols, int border_value,
+                    uint8_t* d_dst_bgr8 /* [n][rows][cols][3], may be NULL */,
+                    float* d_dst_bgr32f /* [n][rows][cols][3], may be NULL */,
+                    uint8_t* d_valid /* [n][rows][cols], may be NULL */, void* stream);
+/* pm_rectify_bgr8 of both images (border_value 0), then pm_match_bgr_device on them: same stream, same results, in every
+ * mode of the handle; seeds / outputs as pm_match_bgr_device.  d_left_rect_bgr8 / d_right_rect_bgr8 ([n][rows][cols][3])
+ * are optional outputs: one that is given receives the rectified image and the match reads it from there -- the left one
+ * is the colour image in the geometry of the disparity map, what pm_range_enhance takes (as floats: pm_rectify_bgr8's
+ * d_dst_bgr32f) -- and one that is NULL is replaced by handle-owned scratch (3 n rows cols bytes each), allocated on first
+ * use, reused and released with the handle.  Size checks and the note on capture as for pm_match_raw_device. */
+int pm_match_raw_bgr_device(pm_handle* h, int n, const pm_rectify_view* left, const pm_rectify_view* right,
+                            const uint8_t* d_left_raw_bgr8, const uint8_t* d_right_raw_bgr8, int src_rows, int src_cols,
+                            size_t src_step, int rows, int cols, const float* d_seed_l, const float* d_seed_r,
+                            float* d_disp_l, float* d_disp_r, uint8_t* d_left_rect_bgr8 /* optional out */,
+                            uint8_t* d_right_rect_bgr8 /* optional out */);
 /* Host only, no handle, no device: rectifying rotations and a common pinhole for a calibrated pair,
  * X2 = R X1 + T (camera 1 = left).  Returns the rectified baseline (> 0) through *baseline.
  * Bouguet's construction: each camera is turned by half of R (camera 1 by R^(1/2), camera 2 by R^(-1/2)), then one

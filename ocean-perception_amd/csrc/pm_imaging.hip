@@ -41,7 +41,8 @@ struct ImagingState {
   DevBuf<char> gf_buf;
   // pm_gather_pixels: [bad flag, pad][n x channels floats][n x 2 coordinates]
   DevBuf<char> gat_buf;
-  // pm_match_raw_device: the rectified pairs, [left, right][n][rows][cols] bytes
+  // pm_match_raw_device: the rectified pairs, [left, right][n][rows][cols] bytes; pm_match_raw_bgr_device: the rectified
+  // BGR images the caller did not ask for, [n][rows][cols][3] bytes each
   DevBuf<uint8_t> rect_buf;
 };
 
@@ -738,6 +739,95 @@ int pm_match_raw_device(pm_handle* h, int n, const pm_rectify_view* left, const 
   launch_rectify(*right, d_right_raw, n, src_rows, src_cols, src_step, rows, cols, 0, rect_r, nullptr, stream);
   if (int rc = launch_check(h, "rectify")) return rc;
   return pm_match_device(h, n, rect_l, rect_r, rows, cols, d_seed_l, d_seed_r, d_disp_l, d_disp_r);
+}
+
+// ---- the same for interleaved BGR (k_rectify_bgr) ------------------------------------------------------------------------
+namespace {
+
+// src_step of a BGR source: 0 = packed; a row is 3 * src_cols bytes.  The other checks are check_rectify_shape's.
+int check_rectify_bgr_shape(pm_handle* h, const char* what, int n, int src_rows, int src_cols, size_t* src_step, int rows,
+                            int cols, int border_value) {
+  if (src_cols >= 1) {
+    if (*src_step == 0) *src_step = 3 * (size_t)src_cols;
+    if (*src_step < 3 * (size_t)src_cols) {
+      set_err(h, "%s: src_step %zu is smaller than a row of %d BGR pixels", what, *src_step, src_cols);
+      return PM_ERR_INVALID_ARG;
+    }
+  }
+  return check_rectify_shape(h, what, n, src_rows, src_cols, src_step, rows, cols, border_value);
+}
+
+// arguments already checked
+void launch_rectify_bgr(const pm_rectify_view& view, const uint8_t* d_src, int n, int src_rows, int src_cols, size_t src_step,
+                        int rows, int cols, int border_value, uint8_t* d_dst, float* d_dstf, uint8_t* d_valid,
+                        hipStream_t stream) {
+  const dim3 grid = rectify_grid(rows, cols, n), block(kRectifyBlockX, kRectifyBlockY);
+  if (d_dstf)
+    hipLaunchKernelGGL((k_rectify_bgr<true>), grid, block, 0, stream, view, d_src, src_rows, src_cols, src_step, rows, cols,
+                       border_value, d_dst, d_dstf, d_valid);
+  else
+    hipLaunchKernelGGL((k_rectify_bgr<false>), grid, block, 0, stream, view, d_src, src_rows, src_cols, src_step, rows, cols,
+                       border_value, d_dst, d_dstf, d_valid);
+}
+
+}  // namespace
+
+int pm_rectify_bgr8(pm_handle* h, const pm_rectify_view* view, const uint8_t* d_src_bgr8, int n, int src_rows, int src_cols,
+                    size_t src_step, int rows, int cols, int border_value, uint8_t* d_dst_bgr8, float* d_dst_bgr32f,
+                    uint8_t* d_valid, void* stream) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (!d_src_bgr8 || (!d_dst_bgr8 && !d_dst_bgr32f)) {
+    set_err(h, "pm_rectify_bgr8: null source, or neither the 8-bit nor the float image requested");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_view(h, "pm_rectify_bgr8", "view", view)) return rc;
+  if (int rc = check_rectify_bgr_shape(h, "pm_rectify_bgr8", n, src_rows, src_cols, &src_step, rows, cols, border_value))
+    return rc;
+  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
+  launch_rectify_bgr(*view, d_src_bgr8, n, src_rows, src_cols, src_step, rows, cols, border_value, d_dst_bgr8, d_dst_bgr32f,
+                     d_valid, stream ? (hipStream_t)stream : pm_internal::stream(h));
+  return launch_check(h, "rectify bgr");
+}
+
+int pm_match_raw_bgr_device(pm_handle* h, int n, const pm_rectify_view* left, const pm_rectify_view* right,
+                            const uint8_t* d_left_raw_bgr8, const uint8_t* d_right_raw_bgr8, int src_rows, int src_cols,
+                            size_t src_step, int rows, int cols, const float* d_seed_l, const float* d_seed_r,
+                            float* d_disp_l, float* d_disp_r, uint8_t* d_left_rect_bgr8, uint8_t* d_right_rect_bgr8) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (!d_left_raw_bgr8 || !d_right_raw_bgr8 || !d_disp_l) {
+    set_err(h, "pm_match_raw_bgr_device: null image or output pointer");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_view(h, "pm_match_raw_bgr_device", "left view", left)) return rc;
+  if (int rc = check_view(h, "pm_match_raw_bgr_device", "right view", right)) return rc;
+  if (int rc = check_rectify_bgr_shape(h, "pm_match_raw_bgr_device", n, src_rows, src_cols, &src_step, rows, cols, 0)) return rc;
+  int max_rows = 0, max_cols = 0;
+  pm_internal::plan_size(h, &max_rows, &max_cols);
+  if (rows < 8 || cols < 8) {
+    set_err(h, "pm_match_raw_bgr_device: rectified image %dx%d too small (min 8x8)", cols, rows);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (rows > max_rows || cols > max_cols) {
+    set_err(h, "pm_match_raw_bgr_device: rectified size %dx%d exceeds plan %dx%d", cols, rows, max_cols, max_rows);
+    return PM_ERR_SIZE;
+  }
+  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
+  ImagingState* st = state_of(h);
+  if (!st) {
+    set_err(h, "pm_match_raw_bgr_device: out of host memory");
+    return PM_ERR_NOMEM;
+  }
+  // an image the caller keeps is written where the caller says and matched from there; the others share the scratch
+  const size_t side = (size_t)n * rows * cols * 3;
+  const int own = (d_left_rect_bgr8 ? 0 : 1) + (d_right_rect_bgr8 ? 0 : 1);
+  hipStream_t stream = pm_internal::stream(h);
+  if (own) PM_HIP(h, st->rect_buf.reserve(own * side, stream));
+  uint8_t* rect_l = d_left_rect_bgr8 ? d_left_rect_bgr8 : st->rect_buf.get();
+  uint8_t* rect_r = d_right_rect_bgr8 ? d_right_rect_bgr8 : st->rect_buf.get() + (own - 1) * side;
+  launch_rectify_bgr(*left, d_left_raw_bgr8, n, src_rows, src_cols, src_step, rows, cols, 0, rect_l, nullptr, nullptr, stream);
+  launch_rectify_bgr(*right, d_right_raw_bgr8, n, src_rows, src_cols, src_step, rows, cols, 0, rect_r, nullptr, nullptr, stream);
+  if (int rc = launch_check(h, "rectify bgr")) return rc;
+  return pm_match_bgr_device(h, n, rect_l, rect_r, rows, cols, d_seed_l, d_seed_r, d_disp_l, d_disp_r);
 }
 
 // Host only: Bouguet's construction (see pm/imaging.h).

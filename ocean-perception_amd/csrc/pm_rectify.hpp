@@ -1,7 +1,7 @@
 // pm_rectify.hpp -- undistortion + rectification of raw 8-bit frames in front of Match() (include/pm/imaging.h:
-// pm_rectify_u8, pm_rectify_map, pm_match_raw_device).  The reference ships a calibration with non-zero distortion
-// (config/shared/ACFR.yaml:27,48) and only warns that it does not undistort (src/vehicle/params/yaml_parser.cpp:153);
-// this is the stage it lacks.  The definition the kernel is held to BIT FOR BIT is tests/rectify_ref.py (DESIGN.md
+// pm_rectify_u8, pm_rectify_map, pm_match_raw_device; interleaved BGR at the end of the file: pm_rectify_bgr8,
+// pm_match_raw_bgr_device).  The reference ships a calibration with non-zero distortion (config/shared/ACFR.yaml:27,48)
+// and only warns that it does not undistort (src/vehicle/params/yaml_parser.cpp:153); this is the stage it lacks.  The definition the kernel is held to BIT FOR BIT is tests/rectify_ref.py (DESIGN.md
 // section 8d): the project's own, not cv::remap's (OpenCV's 15-bit coefficient table is not reproduced).
 //
 // One kernel, no coordinate map in memory: a thread evaluates the radial-tangential model for four consecutive
@@ -135,6 +135,179 @@ __global__ void __launch_bounds__(kRectifyBlockX * kRectifyBlockY)
   const int y = (int)(blockIdx.y * kRectifyBlockY + threadIdx.y);
   if (x4 >= cols || y >= rows) return;
   rectify_four<MAP>(view, src, src_rows, src_cols, src_step, rows, cols, border, dst, valid, xy, x4, y, (int)blockIdx.z);
+}
+
+// ---- interleaved BGR (pm_rectify_bgr8, pm_match_raw_bgr_device) -------------------------------------------------------
+// The definition is tests/rectify_bgr_ref.py: the gray definition channel by channel at the SAME Q5 coordinates, one
+// border value, one mask per image.  The geometry above is therefore evaluated once per destination pixel; the three
+// channels share the position, the four weights and the mask.
+//
+// The two horizontally adjacent taps of a pixel are 6 contiguous bytes of a source row.  They are fetched as one 4-byte
+// and one 2-byte access at byte alignment (the copies below become global_load_dword + global_load_ushort: global memory
+// takes unaligned accesses on gfx950), 16 loads per thread like the gray kernel instead of 48 byte loads.  Nothing is read
+// for a row of taps that lies outside the image altogether.  Where ONE of the two taps is inside -- x0 = -1 or
+// x0 = src_cols - 1, the image's left and right edge -- the same 6-byte access is moved one pixel inwards (the window of
+// columns xc, xc + 1 with xc = clamp(x0, 0, src_cols - 2)) and the tap is taken from the other half of it, so that every
+// lane of a wave runs the same two loads, all eight pairs of a thread are in flight together, and no access reaches past
+// byte 3 * src_cols of a row or past the allocation.  An image of ONE column has no such window: its only tap is read as
+// 2 + 1 bytes (a branch every thread of the launch takes alike).
+
+// The six bytes of one row of taps, loaded but not yet taken apart: a = bytes 0 .. 3, b = bytes 4 .. 5 of the window
+// (src_cols == 1: a = bytes 0 .. 1, b = byte 2 of the only pixel).  in0 / in1: whether tap (x0, ty) / (x0 + 1, ty) is inside.
+struct RectifyRaw {
+  uint32_t a, b;
+};
+__host__ __device__ __forceinline__ RectifyRaw rectify_load_pair(const uint8_t* __restrict__ img, int src_cols, size_t src_step,
+                                                                 int x0, int ty, bool in0, bool in1) {
+  RectifyRaw r = {0u, 0u};
+  if (in0 || in1) {
+    const uint8_t* row = img + (size_t)ty * src_step;
+    if (src_cols >= 2) {
+      const int xc = x0 < 0 ? 0 : x0 > src_cols - 2 ? src_cols - 2 : x0;
+      uint16_t hi;
+      __builtin_memcpy(&r.a, row + (size_t)xc * 3, 4);
+      __builtin_memcpy(&hi, row + (size_t)xc * 3 + 4, 2);
+      r.b = hi;
+    } else {
+      uint16_t lo;
+      __builtin_memcpy(&lo, row, 2);
+      r.a = lo;
+      r.b = row[2];
+    }
+  }
+  return r;
+}
+// -> the left tap in bits 0 .. 23, the right one in bits 24 .. 47 (b | g << 8 | r << 16 each); a tap outside the image is
+// `border3`, the border value in all three bytes
+__host__ __device__ __forceinline__ uint64_t rectify_tap_pair(RectifyRaw r, int src_cols, int x0, bool in0, bool in1,
+                                                              uint32_t border3) {
+  uint32_t lo = r.a & 0xFFFFFFu, hi = (r.a >> 24) | (r.b << 8);  // columns xc and xc + 1 of the window
+  if (src_cols < 2) lo = hi = r.a | (r.b << 16);
+  const uint32_t left = !in0 ? border3 : x0 > src_cols - 2 ? hi : lo;  // x0 == src_cols - 1: the window moved left
+  const uint32_t right = !in1 ? border3 : x0 < 0 ? lo : hi;            // x0 == -1: the window moved right
+  return (uint64_t)left | ((uint64_t)right << 24);
+}
+
+// (w . taps + 512) >> 10 of channel c (0 .. 2) of the two tap pairs of a pixel
+__host__ __device__ __forceinline__ unsigned rectify_blend(const int w[4], uint64_t top, uint64_t bot, int c) {
+  const int sum = w[0] * (int)((top >> (8 * c)) & 255u) + w[1] * (int)((top >> (24 + 8 * c)) & 255u) +
+                  w[2] * (int)((bot >> (8 * c)) & 255u) + w[3] * (int)((bot >> (24 + 8 * c)) & 255u);
+  return (unsigned)((sum + 512) >> 10);
+}
+
+// The work of one thread: destination pixels x4 .. x4 + 3 of row y of image z, 12 bytes of dst (and / or 12 floats of
+// dstf = byte x (float)(1 / 255.), CastImage3bTo3f) and 4 bytes of mask.  dst / dstf / valid may each be null.
+// src_step: bytes per source row (>= 3 * src_cols).  The 12 bytes leave as three 32-bit words where the address is 4-byte
+// aligned and the row holds all four pixels, byte by byte otherwise (row tails, an unaligned dst, the rows of a packed
+// image of odd width, whose alignment alternates); the 12 floats as three 16-byte stores under the same rule for 16 bytes.
+__host__ __device__ __forceinline__ void rectify_four_bgr(const pm_rectify_view& view, const uint8_t* __restrict__ src,
+                                                          int src_rows, int src_cols, size_t src_step, int rows, int cols,
+                                                          int border, uint8_t* __restrict__ dst, float* __restrict__ dstf,
+                                                          uint8_t* __restrict__ valid, int x4, int y, int z) {
+  const int count = cols - x4 < 4 ? cols - x4 : 4;
+  const double b = ((double)y - view.cy_new) / view.fy_new;
+  int ix[4], iy[4];
+  bool ok[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double a = ((double)(x4 + k) - view.cx_new) / view.fx_new;
+    ok[k] = rectify_source_q5(view, a, b, &ix[k], &iy[k]);
+  }
+  const uint8_t* img = src + (size_t)z * src_rows * src_step;
+  const uint32_t border3 = (uint32_t)border * 0x010101u;
+  // the gathers first (independent loads in flight together), the blends after them
+  RectifyRaw top[4], bot[4];
+  bool in[4][4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int x0 = ix[k] >> 5, y0 = iy[k] >> 5;  // floor
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int tx = x0 + (t & 1), ty = y0 + (t >> 1);
+      in[k][t] = ok[k] && k < count && (unsigned)tx < (unsigned)src_cols && (unsigned)ty < (unsigned)src_rows;
+    }
+    top[k] = rectify_load_pair(img, src_cols, src_step, x0, y0, in[k][0], in[k][1]);
+    bot[k] = rectify_load_pair(img, src_cols, src_step, x0, y0 + 1, in[k][2], in[k][3]);
+  }
+  unsigned px[4], vm = 0;  // px[k]: b | g << 8 | r << 16 of pixel k
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int ax = ix[k] & 31, ay = iy[k] & 31;
+    const int w[4] = {(32 - ax) * (32 - ay), ax * (32 - ay), (32 - ax) * ay, ax * ay};
+    const uint64_t t01 = rectify_tap_pair(top[k], src_cols, ix[k] >> 5, in[k][0], in[k][1], border3);
+    const uint64_t t23 = rectify_tap_pair(bot[k], src_cols, ix[k] >> 5, in[k][2], in[k][3], border3);
+    bool all_in = ok[k];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) all_in = all_in && (in[k][t] || w[t] == 0);
+    px[k] = ok[k] ? rectify_blend(w, t01, t23, 0) | (rectify_blend(w, t01, t23, 1) << 8) | (rectify_blend(w, t01, t23, 2) << 16)
+                  : border3;
+    vm |= (all_in ? 255u : 0u) << (8 * k);
+  }
+  const size_t at = ((size_t)z * rows + y) * cols + x4;
+  if (dst) {
+    uint8_t* o = dst + at * 3;
+    if (count == 4 && ((uintptr_t)o & 3u) == 0) {
+      uint32_t* o32 = (uint32_t*)o;
+      o32[0] = px[0] | (px[1] << 24);
+      o32[1] = (px[1] >> 8) | (px[2] << 16);
+      o32[2] = (px[2] >> 16) | (px[3] << 8);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < count) {
+          o[3 * k] = (uint8_t)px[k];
+          o[3 * k + 1] = (uint8_t)(px[k] >> 8);
+          o[3 * k + 2] = (uint8_t)(px[k] >> 16);
+        }
+    }
+  }
+  if (dstf) {
+    const float s = (float)(1.0 / 255.0);
+    float f[12];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) f[3 * k + c] = (float)((px[k] >> (8 * c)) & 255u) * s;
+    float* o = dstf + at * 3;
+    if (count == 4 && ((uintptr_t)o & 15u) == 0) {
+      float4* o4 = (float4*)o;
+      o4[0] = make_float4(f[0], f[1], f[2], f[3]);
+      o4[1] = make_float4(f[4], f[5], f[6], f[7]);
+      o4[2] = make_float4(f[8], f[9], f[10], f[11]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < count) {
+          o[3 * k] = f[3 * k];
+          o[3 * k + 1] = f[3 * k + 1];
+          o[3 * k + 2] = f[3 * k + 2];
+        }
+    }
+  }
+  if (valid) {
+    uint8_t* m = valid + at;
+    if (count == 4 && ((uintptr_t)m & 3u) == 0) {
+      *(uint32_t*)m = vm;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (k < count) m[k] = (uint8_t)(vm >> (8 * k));
+    }
+  }
+}
+
+// grid and block as k_rectify.  FLOAT = false compiles the float image out (dstf is not read): the instantiation
+// pm_match_raw_bgr_device and every caller without a float image run.  (A template also for the host build of
+// tests/cpp/rectify_bgr_host_main.cpp, which must not instantiate a kernel.)
+template <bool FLOAT>
+__global__ void __launch_bounds__(kRectifyBlockX * kRectifyBlockY)
+    k_rectify_bgr(pm_rectify_view view, const uint8_t* __restrict__ src, int src_rows, int src_cols, size_t src_step, int rows,
+                  int cols, int border, uint8_t* __restrict__ dst, float* __restrict__ dstf, uint8_t* __restrict__ valid) {
+  const int x4 = (int)(blockIdx.x * kRectifyBlockX + threadIdx.x) * 4;
+  const int y = (int)(blockIdx.y * kRectifyBlockY + threadIdx.y);
+  if (x4 >= cols || y >= rows) return;
+  rectify_four_bgr(view, src, src_rows, src_cols, src_step, rows, cols, border, dst, FLOAT ? dstf : nullptr, valid, x4, y,
+                   (int)blockIdx.z);
 }
 
 }  // namespace pm

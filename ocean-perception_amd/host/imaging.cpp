@@ -260,5 +260,26 @@ Image1b Rectify(const Image1b& raw, const RectifyView& view, int rows, int cols,
   return out;
 }
 
+core::Image<core::Vec3b> Rectify(const core::Image<core::Vec3b>& raw, const RectifyView& view, int rows, int cols,
+                                 core::Image<uint8_t>* valid) {
+  if (raw.rows <= 0 || raw.cols <= 0 || rows <= 0 || cols <= 0) throw std::invalid_argument("Rectify: empty image");
+  static_assert(sizeof(core::Vec3b) == 3, "Image3b is interleaved bytes");
+  std::lock_guard<std::mutex> lock(g_mutex);
+  pm_handle* h = Context();
+  const size_t px = (size_t)rows * cols;
+  DeviceBuffer d_in(h, Bytes(raw)), d_out(h, 3 * px), d_valid(h, px);
+  d_in.Upload(raw.data(), Bytes(raw));
+  Check(pm_rectify_bgr8(h, &view, d_in.as<uint8_t>(), 1, raw.rows, raw.cols, 0, rows, cols, 0, d_out.as<uint8_t>(), nullptr,
+                        valid ? d_valid.as<uint8_t>() : nullptr, nullptr),
+        "pm_rectify_bgr8");
+  core::Image<core::Vec3b> out(rows, cols);
+  d_out.Download(out.data(), 3 * px);
+  if (valid) {
+    if (valid->rows != rows || valid->cols != cols) valid->create(rows, cols);
+    d_valid.Download(valid->data(), px);
+  }
+  return out;
+}
+
 }  // namespace imaging
 }  // namespace bm

@@ -73,6 +73,11 @@ double StereoRectify(const CameraModel& cam1, const CameraModel& cam2, const std
                      const std::array<double, 3>& T, RectifyView* view1, RectifyView* view2);
 // The raw image seen through `view`, rows x cols, pixels without a source 0; valid (255 / 0) where it is asked for.
 Image1b Rectify(const Image1b& raw, const RectifyView& view, int rows, int cols, Image1b* valid = nullptr);
+// The same for an interleaved 8-bit BGR frame (pm_rectify_bgr8): the three channels at one position, one mask.  Declared
+// with the image classes themselves, not the Image1b alias, which a caller that compiles next to OpenCV sees as cv::Mat1b:
+// the library exports this one signature whatever the caller includes.
+core::Image<core::Vec3b> Rectify(const core::Image<core::Vec3b>& raw, const RectifyView& view, int rows, int cols,
+                                 core::Image<uint8_t>* valid = nullptr);
 
 }  // namespace imaging
 }  // namespace bm

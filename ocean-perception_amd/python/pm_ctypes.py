@@ -42,6 +42,7 @@ EXPORTS = [
     "pm_normalize_color_illuminant", "pm_match_bgr_device", "pm_device_malloc", "pm_device_free", "pm_upload", "pm_download",
     "pm_fast_guided_filter", "pm_estimate_illuminant_range_guided", "pm_gather_pixels",
     "pm_rectify_u8", "pm_rectify_map", "pm_match_raw_device", "pm_stereo_rectify",
+    "pm_rectify_bgr8", "pm_match_raw_bgr_device",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate",
     "pm_remove_background", "pm_mask_occlusions", "pm_foreground_texture_mask", "pm_sparse_init", "pm_corner_subpix", "pm_profile_enable", "pm_profile_read",
     "pm_kernel_name", "pm_debug_counters", "pm_debug_counters_enable",
@@ -263,7 +264,12 @@ def load():
                                         vp, vp, vp, vp]
     lib.pm_stereo_rectify.argtypes = [C.POINTER(PmCamera), C.POINTER(PmCamera), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                       view_p, view_p, C.POINTER(C.c_double)]
-    for name in ("pm_rectify_u8", "pm_rectify_map", "pm_match_raw_device", "pm_stereo_rectify"):
+    lib.pm_rectify_bgr8.argtypes = [vp, view_p, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, vp, vp,
+                                    vp]
+    lib.pm_match_raw_bgr_device.argtypes = [vp, C.c_int, view_p, view_p, vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int,
+                                            vp, vp, vp, vp, vp, vp]
+    for name in ("pm_rectify_u8", "pm_rectify_map", "pm_match_raw_device", "pm_stereo_rectify", "pm_rectify_bgr8",
+                 "pm_match_raw_bgr_device"):
         getattr(lib, name).restype = C.c_int
     lib.pm_device_malloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     lib.pm_device_free.argtypes = [vp, vp]
@@ -691,6 +697,26 @@ class Engine:
                                                  C.byref(vr) if vr is not None else None, d_left_raw, d_right_raw, src_rows,
                                                  src_cols, src_step, rows, cols, d_seed_l, d_seed_r, d_disp_l, d_disp_r),
                     "pm_match_raw_device")
+
+    def rectify_bgr8(self, view, d_src, n, src_rows, src_cols, src_step, rows, cols, border_value, d_dst, d_dst_f=None,
+                     d_valid=None, stream=None):
+        """n raw interleaved BGR images -> n undistorted, rectified ones (raw device addresses): 8-bit (d_dst) and / or
+        float x 1/255 (d_dst_f), one mask per image (d_valid).  src_step in bytes, 0 = 3 * src_cols."""
+        v = rectify_view(view)
+        self._check(self.lib.pm_rectify_bgr8(self.h, C.byref(v) if v is not None else None, d_src, n, src_rows, src_cols,
+                                             src_step, rows, cols, border_value, d_dst, d_dst_f, d_valid, stream),
+                    "pm_rectify_bgr8")
+
+    def match_raw_bgr_device(self, n, left_view, right_view, d_left_raw, d_right_raw, src_rows, src_cols, src_step, rows, cols,
+                             d_seed_l, d_seed_r, d_disp_l, d_disp_r, d_left_rect=None, d_right_rect=None):
+        """pm_rectify_bgr8 of both raw BGR images followed by pm_match_bgr_device (raw device addresses); d_left_rect /
+        d_right_rect: optional outputs that receive the rectified images."""
+        self._pl_shape = (rows, cols)
+        vl, vr = rectify_view(left_view), rectify_view(right_view)
+        self._check(self.lib.pm_match_raw_bgr_device(self.h, n, C.byref(vl) if vl is not None else None,
+                                                     C.byref(vr) if vr is not None else None, d_left_raw, d_right_raw,
+                                                     src_rows, src_cols, src_step, rows, cols, d_seed_l, d_seed_r, d_disp_l,
+                                                     d_disp_r, d_left_rect, d_right_rect), "pm_match_raw_bgr_device")
 
     def normalize(self, d_bgr, rows, cols, d_out):
         self._check(self.lib.pm_normalize(self.h, d_bgr, rows, cols, d_out), "pm_normalize")

@@ -1,0 +1,56 @@
+"""The BGR overload of bm::imaging::Rectify (ocean-perception_amd/host/imaging.hpp), compiled with plain g++ and driven
+like a host caller (tests/cpp/rectify_bgr_main.cpp); its output is the fixture tests/golden/rectify_bgr_41x59.npz, which
+the definition (tests/rectify_bgr_ref.py) wrote."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, ROOT
+
+PKG = os.path.join(ROOT, "ocean-perception_amd")
+LIBDIR = os.path.join(PKG, "lib")
+FIXTURE = os.path.join(GOLDEN, "rectify_bgr_41x59.npz")
+
+
+@pytest.fixture(scope="module")
+def rectify_exe(tmp_path_factory):
+    out = tmp_path_factory.mktemp("cpprectbgr") / "rectify_bgr_main"
+    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
+           "-I" + os.path.join(PKG, "host"), os.path.join(ROOT, "tests", "cpp", "rectify_bgr_main.cpp"), "-L" + LIBDIR,
+           "-lvehicle_pm_gpu", "-Wl,-rpath," + LIBDIR, "-o", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return str(out)
+
+
+def _run(exe, tmp_path):
+    f = np.load(FIXTURE)
+    assert int(f["border_value"]) == 0  # the overload's border
+    f["src"].tofile(os.path.join(tmp_path, "raw.u8"))
+    np.asarray(f["view"], np.float64).tofile(os.path.join(tmp_path, "view.f64"))
+    return f, subprocess.run([exe, str(tmp_path), "41", "59", "37", "53"], capture_output=True, text=True)
+
+
+def _has_gpu():
+    try:
+        import torch
+        return torch.cuda.is_available()
+    except Exception:
+        return False
+
+
+@pytest.mark.skipif(_has_gpu(), reason="checks the no-GPU failure mode")
+def test_bgr_overload_builds_with_gxx_and_fails_loudly_without_gpu(rectify_exe, tmp_path):
+    _, r = _run(rectify_exe, tmp_path)
+    assert r.returncode == 10 and "no HIP device" in r.stdout
+
+
+@pytest.mark.gpu
+def test_bgr_overload_reproduces_the_fixture(rectify_exe, tmp_path):
+    f, r = _run(rectify_exe, tmp_path)
+    assert r.returncode == 0, r.stdout + r.stderr
+    out = np.fromfile(os.path.join(tmp_path, "out.u8"), np.uint8).reshape(37, 53, 3)
+    valid = np.fromfile(os.path.join(tmp_path, "valid.u8"), np.uint8).reshape(37, 53)
+    assert np.array_equal(out, f["out"]) and np.array_equal(valid, f["valid"])
