@@ -636,15 +636,19 @@ int check_view(pm_handle* h, const char* what, const char* which, const pm_recti
   return PM_OK;
 }
 
-int check_rectify_shape(pm_handle* h, const char* what, int n, int src_rows, int src_cols, size_t* src_step, int rows,
-                        int cols, int border_value) {
+// channels: bytes per source pixel (1 gray, 3 interleaved BGR).  *src_step == 0 means packed and becomes the row's
+// channels * src_cols bytes.
+int check_rectify_shape(pm_handle* h, const char* what, int channels, int n, int src_rows, int src_cols, size_t* src_step,
+                        int rows, int cols, int border_value) {
   if (n < 1 || src_rows < 1 || src_cols < 1 || rows < 1 || cols < 1) {
     set_err(h, "%s: %d images of %dx%d from %dx%d: every count and size must be >= 1", what, n, cols, rows, src_cols, src_rows);
     return PM_ERR_INVALID_ARG;
   }
-  if (*src_step == 0) *src_step = (size_t)src_cols;
-  if (*src_step < (size_t)src_cols) {
-    set_err(h, "%s: src_step %zu is smaller than a row of %d bytes", what, *src_step, src_cols);
+  const size_t row = (size_t)channels * src_cols;
+  if (*src_step == 0) *src_step = row;
+  if (*src_step < row) {
+    set_err(h, "%s: src_step %zu is smaller than a row of %d %s", what, *src_step, src_cols,
+            channels == 3 ? "BGR pixels" : "bytes");
     return PM_ERR_INVALID_ARG;
   }
   if (border_value < 0 || border_value > 255) {
@@ -658,16 +662,68 @@ int check_rectify_shape(pm_handle* h, const char* what, int n, int src_rows, int
   return PM_OK;
 }
 
-inline dim3 rectify_grid(int rows, int cols, int n) {
+// arguments already checked; n: the images of the launch (grid z)
+template <RectifyKind KIND>
+void launch_rectify(const RectifyArgs& a, int n, hipStream_t stream) {
   const int px = kRectifyBlockX * 4;
-  return dim3((unsigned)((cols + px - 1) / px), (unsigned)((rows + kRectifyBlockY - 1) / kRectifyBlockY), (unsigned)n);
+  const dim3 grid((unsigned)((a.cols + px - 1) / px), (unsigned)((a.rows + kRectifyBlockY - 1) / kRectifyBlockY), (unsigned)n);
+  hipLaunchKernelGGL((k_rectify<KIND>), grid, dim3(kRectifyBlockX, kRectifyBlockY), 0, stream, a);
+}
+// channels 1: gray (d_dstf null); 3: BGR, with the float image where d_dstf is given
+void launch_rectify(int channels, const pm_rectify_view& view, const uint8_t* d_src, int n, int src_rows, int src_cols,
+                    size_t src_step, int rows, int cols, int border_value, uint8_t* d_dst, float* d_dstf, uint8_t* d_valid,
+                    hipStream_t stream) {
+  const RectifyArgs a = {view, d_src, src_rows, src_cols, src_step, rows, cols, border_value, d_dst, d_dstf, d_valid, nullptr};
+  if (channels == 1)
+    launch_rectify<RectifyKind::Gray>(a, n, stream);
+  else if (d_dstf)
+    launch_rectify<RectifyKind::BgrFloat>(a, n, stream);
+  else
+    launch_rectify<RectifyKind::Bgr>(a, n, stream);
 }
 
-// arguments already checked
-void launch_rectify(const pm_rectify_view& view, const uint8_t* d_src, int n, int src_rows, int src_cols, size_t src_step,
-                    int rows, int cols, int border_value, uint8_t* d_dst, uint8_t* d_valid, hipStream_t stream) {
-  hipLaunchKernelGGL((k_rectify<false>), rectify_grid(rows, cols, n), dim3(kRectifyBlockX, kRectifyBlockY), 0, stream, view,
-                     d_src, src_rows, src_cols, src_step, rows, cols, border_value, d_dst, d_valid, (int32_t*)nullptr);
+// What pm_match_raw_device (channels 1) and pm_match_raw_bgr_device (channels 3) share: every check, then the two
+// rectifications into the handle's scratch -- or into d_keep_l / d_keep_r where the caller keeps a rectified image, which
+// is then matched from there -- and the Match() of `match` on the result.
+typedef int (*MatchFn)(pm_handle*, int, const uint8_t*, const uint8_t*, int, int, const float*, const float*, float*, float*);
+int match_raw(pm_handle* h, const char* what, int channels, MatchFn match, int n, const pm_rectify_view* left,
+              const pm_rectify_view* right, const uint8_t* d_left_raw, const uint8_t* d_right_raw, int src_rows, int src_cols,
+              size_t src_step, int rows, int cols, const float* d_seed_l, const float* d_seed_r, float* d_disp_l,
+              float* d_disp_r, uint8_t* d_keep_l, uint8_t* d_keep_r) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (!d_left_raw || !d_right_raw || !d_disp_l) {
+    set_err(h, "%s: null image or output pointer", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_view(h, what, "left view", left)) return rc;
+  if (int rc = check_view(h, what, "right view", right)) return rc;
+  if (int rc = check_rectify_shape(h, what, channels, n, src_rows, src_cols, &src_step, rows, cols, 0)) return rc;
+  int max_rows = 0, max_cols = 0;
+  pm_internal::plan_size(h, &max_rows, &max_cols);
+  if (rows < 8 || cols < 8) {
+    set_err(h, "%s: rectified image %dx%d too small (min 8x8)", what, cols, rows);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (rows > max_rows || cols > max_cols) {
+    set_err(h, "%s: rectified size %dx%d exceeds plan %dx%d", what, cols, rows, max_cols, max_rows);
+    return PM_ERR_SIZE;
+  }
+  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
+  ImagingState* st = state_of(h);
+  if (!st) {
+    set_err(h, "%s: out of host memory", what);
+    return PM_ERR_NOMEM;
+  }
+  const size_t side = (size_t)n * rows * cols * channels;
+  const int own = (d_keep_l ? 0 : 1) + (d_keep_r ? 0 : 1);
+  hipStream_t stream = pm_internal::stream(h);
+  if (own) PM_HIP(h, st->rect_buf.reserve(own * side, stream));
+  uint8_t* rect_l = d_keep_l ? d_keep_l : st->rect_buf.get();
+  uint8_t* rect_r = d_keep_r ? d_keep_r : st->rect_buf.get() + (own - 1) * side;
+  launch_rectify(channels, *left, d_left_raw, n, src_rows, src_cols, src_step, rows, cols, 0, rect_l, nullptr, nullptr, stream);
+  launch_rectify(channels, *right, d_right_raw, n, src_rows, src_cols, src_step, rows, cols, 0, rect_r, nullptr, nullptr, stream);
+  if (int rc = launch_check(h, channels == 3 ? "rectify bgr" : "rectify")) return rc;
+  return match(h, n, rect_l, rect_r, rows, cols, d_seed_l, d_seed_r, d_disp_l, d_disp_r);
 }
 
 }  // namespace
@@ -680,9 +736,9 @@ int pm_rectify_u8(pm_handle* h, const pm_rectify_view* view, const uint8_t* d_sr
     return PM_ERR_INVALID_ARG;
   }
   if (int rc = check_view(h, "pm_rectify_u8", "view", view)) return rc;
-  if (int rc = check_rectify_shape(h, "pm_rectify_u8", n, src_rows, src_cols, &src_step, rows, cols, border_value)) return rc;
+  if (int rc = check_rectify_shape(h, "pm_rectify_u8", 1, n, src_rows, src_cols, &src_step, rows, cols, border_value)) return rc;
   PM_HIP(h, hipSetDevice(pm_internal::device(h)));
-  launch_rectify(*view, d_src, n, src_rows, src_cols, src_step, rows, cols, border_value, d_dst, d_valid,
+  launch_rectify(1, *view, d_src, n, src_rows, src_cols, src_step, rows, cols, border_value, d_dst, nullptr, d_valid,
                  stream ? (hipStream_t)stream : pm_internal::stream(h));
   return launch_check(h, "rectify");
 }
@@ -695,82 +751,19 @@ int pm_rectify_map(pm_handle* h, const pm_rectify_view* view, int rows, int cols
   }
   if (int rc = check_view(h, "pm_rectify_map", "view", view)) return rc;
   size_t step = 0;
-  if (int rc = check_rectify_shape(h, "pm_rectify_map", 1, 1, 1, &step, rows, cols, 0)) return rc;
+  if (int rc = check_rectify_shape(h, "pm_rectify_map", 1, 1, 1, 1, &step, rows, cols, 0)) return rc;
   PM_HIP(h, hipSetDevice(pm_internal::device(h)));
-  hipLaunchKernelGGL((k_rectify<true>), rectify_grid(rows, cols, 1), dim3(kRectifyBlockX, kRectifyBlockY), 0,
-                     pm_internal::stream(h), *view, (const uint8_t*)nullptr, 0, 0, (size_t)0, rows, cols, 0, (uint8_t*)nullptr,
-                     (uint8_t*)nullptr, d_xy);
+  const RectifyArgs a = {*view, nullptr, 0, 0, 0, rows, cols, 0, nullptr, nullptr, nullptr, d_xy};
+  launch_rectify<RectifyKind::Map>(a, 1, pm_internal::stream(h));
   return launch_check(h, "rectify map");
 }
 
 int pm_match_raw_device(pm_handle* h, int n, const pm_rectify_view* left, const pm_rectify_view* right,
                         const uint8_t* d_left_raw, const uint8_t* d_right_raw, int src_rows, int src_cols, size_t src_step,
                         int rows, int cols, const float* d_seed_l, const float* d_seed_r, float* d_disp_l, float* d_disp_r) {
-  if (!h) return PM_ERR_INVALID_ARG;
-  if (!d_left_raw || !d_right_raw || !d_disp_l) {
-    set_err(h, "pm_match_raw_device: null image or output pointer");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (int rc = check_view(h, "pm_match_raw_device", "left view", left)) return rc;
-  if (int rc = check_view(h, "pm_match_raw_device", "right view", right)) return rc;
-  if (int rc = check_rectify_shape(h, "pm_match_raw_device", n, src_rows, src_cols, &src_step, rows, cols, 0)) return rc;
-  int max_rows = 0, max_cols = 0;
-  pm_internal::plan_size(h, &max_rows, &max_cols);
-  if (rows < 8 || cols < 8) {
-    set_err(h, "pm_match_raw_device: rectified image %dx%d too small (min 8x8)", cols, rows);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (rows > max_rows || cols > max_cols) {
-    set_err(h, "pm_match_raw_device: rectified size %dx%d exceeds plan %dx%d", cols, rows, max_cols, max_rows);
-    return PM_ERR_SIZE;
-  }
-  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
-  ImagingState* st = state_of(h);
-  if (!st) {
-    set_err(h, "pm_match_raw_device: out of host memory");
-    return PM_ERR_NOMEM;
-  }
-  const size_t side = (size_t)n * rows * cols;
-  hipStream_t stream = pm_internal::stream(h);
-  PM_HIP(h, st->rect_buf.reserve(2 * side, stream));
-  uint8_t* rect_l = st->rect_buf;
-  uint8_t* rect_r = rect_l + side;
-  launch_rectify(*left, d_left_raw, n, src_rows, src_cols, src_step, rows, cols, 0, rect_l, nullptr, stream);
-  launch_rectify(*right, d_right_raw, n, src_rows, src_cols, src_step, rows, cols, 0, rect_r, nullptr, stream);
-  if (int rc = launch_check(h, "rectify")) return rc;
-  return pm_match_device(h, n, rect_l, rect_r, rows, cols, d_seed_l, d_seed_r, d_disp_l, d_disp_r);
+  return match_raw(h, "pm_match_raw_device", 1, pm_match_device, n, left, right, d_left_raw, d_right_raw, src_rows, src_cols,
+                   src_step, rows, cols, d_seed_l, d_seed_r, d_disp_l, d_disp_r, nullptr, nullptr);
 }
-
-// ---- the same for interleaved BGR (k_rectify_bgr) ------------------------------------------------------------------------
-namespace {
-
-// src_step of a BGR source: 0 = packed; a row is 3 * src_cols bytes.  The other checks are check_rectify_shape's.
-int check_rectify_bgr_shape(pm_handle* h, const char* what, int n, int src_rows, int src_cols, size_t* src_step, int rows,
-                            int cols, int border_value) {
-  if (src_cols >= 1) {
-    if (*src_step == 0) *src_step = 3 * (size_t)src_cols;
-    if (*src_step < 3 * (size_t)src_cols) {
-      set_err(h, "%s: src_step %zu is smaller than a row of %d BGR pixels", what, *src_step, src_cols);
-      return PM_ERR_INVALID_ARG;
-    }
-  }
-  return check_rectify_shape(h, what, n, src_rows, src_cols, src_step, rows, cols, border_value);
-}
-
-// arguments already checked
-void launch_rectify_bgr(const pm_rectify_view& view, const uint8_t* d_src, int n, int src_rows, int src_cols, size_t src_step,
-                        int rows, int cols, int border_value, uint8_t* d_dst, float* d_dstf, uint8_t* d_valid,
-                        hipStream_t stream) {
-  const dim3 grid = rectify_grid(rows, cols, n), block(kRectifyBlockX, kRectifyBlockY);
-  if (d_dstf)
-    hipLaunchKernelGGL((k_rectify_bgr<true>), grid, block, 0, stream, view, d_src, src_rows, src_cols, src_step, rows, cols,
-                       border_value, d_dst, d_dstf, d_valid);
-  else
-    hipLaunchKernelGGL((k_rectify_bgr<false>), grid, block, 0, stream, view, d_src, src_rows, src_cols, src_step, rows, cols,
-                       border_value, d_dst, d_dstf, d_valid);
-}
-
-}  // namespace
 
 int pm_rectify_bgr8(pm_handle* h, const pm_rectify_view* view, const uint8_t* d_src_bgr8, int n, int src_rows, int src_cols,
                     size_t src_step, int rows, int cols, int border_value, uint8_t* d_dst_bgr8, float* d_dst_bgr32f,
@@ -781,11 +774,10 @@ int pm_rectify_bgr8(pm_handle* h, const pm_rectify_view* view, const uint8_t* d_
     return PM_ERR_INVALID_ARG;
   }
   if (int rc = check_view(h, "pm_rectify_bgr8", "view", view)) return rc;
-  if (int rc = check_rectify_bgr_shape(h, "pm_rectify_bgr8", n, src_rows, src_cols, &src_step, rows, cols, border_value))
-    return rc;
+  if (int rc = check_rectify_shape(h, "pm_rectify_bgr8", 3, n, src_rows, src_cols, &src_step, rows, cols, border_value)) return rc;
   PM_HIP(h, hipSetDevice(pm_internal::device(h)));
-  launch_rectify_bgr(*view, d_src_bgr8, n, src_rows, src_cols, src_step, rows, cols, border_value, d_dst_bgr8, d_dst_bgr32f,
-                     d_valid, stream ? (hipStream_t)stream : pm_internal::stream(h));
+  launch_rectify(3, *view, d_src_bgr8, n, src_rows, src_cols, src_step, rows, cols, border_value, d_dst_bgr8, d_dst_bgr32f,
+                 d_valid, stream ? (hipStream_t)stream : pm_internal::stream(h));
   return launch_check(h, "rectify bgr");
 }
 
@@ -793,41 +785,9 @@ int pm_match_raw_bgr_device(pm_handle* h, int n, const pm_rectify_view* left, co
                             const uint8_t* d_left_raw_bgr8, const uint8_t* d_right_raw_bgr8, int src_rows, int src_cols,
                             size_t src_step, int rows, int cols, const float* d_seed_l, const float* d_seed_r,
                             float* d_disp_l, float* d_disp_r, uint8_t* d_left_rect_bgr8, uint8_t* d_right_rect_bgr8) {
-  if (!h) return PM_ERR_INVALID_ARG;
-  if (!d_left_raw_bgr8 || !d_right_raw_bgr8 || !d_disp_l) {
-    set_err(h, "pm_match_raw_bgr_device: null image or output pointer");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (int rc = check_view(h, "pm_match_raw_bgr_device", "left view", left)) return rc;
-  if (int rc = check_view(h, "pm_match_raw_bgr_device", "right view", right)) return rc;
-  if (int rc = check_rectify_bgr_shape(h, "pm_match_raw_bgr_device", n, src_rows, src_cols, &src_step, rows, cols, 0)) return rc;
-  int max_rows = 0, max_cols = 0;
-  pm_internal::plan_size(h, &max_rows, &max_cols);
-  if (rows < 8 || cols < 8) {
-    set_err(h, "pm_match_raw_bgr_device: rectified image %dx%d too small (min 8x8)", cols, rows);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (rows > max_rows || cols > max_cols) {
-    set_err(h, "pm_match_raw_bgr_device: rectified size %dx%d exceeds plan %dx%d", cols, rows, max_cols, max_rows);
-    return PM_ERR_SIZE;
-  }
-  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
-  ImagingState* st = state_of(h);
-  if (!st) {
-    set_err(h, "pm_match_raw_bgr_device: out of host memory");
-    return PM_ERR_NOMEM;
-  }
-  // an image the caller keeps is written where the caller says and matched from there; the others share the scratch
-  const size_t side = (size_t)n * rows * cols * 3;
-  const int own = (d_left_rect_bgr8 ? 0 : 1) + (d_right_rect_bgr8 ? 0 : 1);
-  hipStream_t stream = pm_internal::stream(h);
-  if (own) PM_HIP(h, st->rect_buf.reserve(own * side, stream));
-  uint8_t* rect_l = d_left_rect_bgr8 ? d_left_rect_bgr8 : st->rect_buf.get();
-  uint8_t* rect_r = d_right_rect_bgr8 ? d_right_rect_bgr8 : st->rect_buf.get() + (own - 1) * side;
-  launch_rectify_bgr(*left, d_left_raw_bgr8, n, src_rows, src_cols, src_step, rows, cols, 0, rect_l, nullptr, nullptr, stream);
-  launch_rectify_bgr(*right, d_right_raw_bgr8, n, src_rows, src_cols, src_step, rows, cols, 0, rect_r, nullptr, nullptr, stream);
-  if (int rc = launch_check(h, "rectify bgr")) return rc;
-  return pm_match_bgr_device(h, n, rect_l, rect_r, rows, cols, d_seed_l, d_seed_r, d_disp_l, d_disp_r);
+  return match_raw(h, "pm_match_raw_bgr_device", 3, pm_match_bgr_device, n, left, right, d_left_raw_bgr8, d_right_raw_bgr8,
+                   src_rows, src_cols, src_step, rows, cols, d_seed_l, d_seed_r, d_disp_l, d_disp_r, d_left_rect_bgr8,
+                   d_right_rect_bgr8);
 }
 
 // Host only: Bouguet's construction (see pm/imaging.h).

@@ -1,5 +1,5 @@
 // pm_rectify.hpp -- undistortion + rectification of raw 8-bit frames in front of Match() (include/pm/imaging.h:
-// pm_rectify_u8, pm_rectify_map, pm_match_raw_device; interleaved BGR at the end of the file: pm_rectify_bgr8,
+// pm_rectify_u8, pm_rectify_map, pm_match_raw_device; interleaved BGR through the same code: pm_rectify_bgr8,
 // pm_match_raw_bgr_device).  The reference ships a calibration with non-zero distortion (config/shared/ACFR.yaml:27,48)
 // and only warns that it does not undistort (src/vehicle/params/yaml_parser.cpp:153); this is the stage it lacks.  The definition the kernel is held to BIT FOR BIT is tests/rectify_ref.py (DESIGN.md
 // section 8d): the project's own, not cv::remap's (OpenCV's 15-bit coefficient table is not reproduced).
@@ -9,9 +9,11 @@
 // uses -ffp-contract=off; binary64 division is IEEE on gfx950; no fma, no rsqrt, no fast-math intrinsic) -- quantises the
 // source position to 1/32 pixel, gathers the four source bytes of each pixel and blends them in integers.  The view
 // (22 doubles) travels by value in the kernel arguments, so nothing is allocated or invalidated when a calibration
-// changes, and a 720p pair moves 1.8 MB of image instead of reading 15 MB of map on top.  MAP = true makes the same
+// changes, and a 720p pair moves 1.8 MB of image instead of reading 15 MB of map on top.  RectifyKind::Map makes the same
 // code write the Q5 coordinates instead of the pixels: the map a test reads is the map the pixels were made from.
 // Per pixel: about 60 binary64 operations and 3 divisions, 4 one-byte gathers, one byte out (two with the mask).
+// Positions, inside test, weights, mask rule and the four-byte store are written once for every pixel format; a format has
+// its own gather and its own pixel store, nothing else.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -49,95 +51,77 @@ __host__ __device__ __forceinline__ bool rectify_source_q5(const pm_rectify_view
   return ok;
 }
 
-// grid = (ceil(cols / 256), ceil(rows / 4), n), block = (64, 4).  A thread owns destination pixels x4 .. x4 + 3 of row y
-// of image z and stores them as one 32-bit word where the address is 4-byte aligned and the row holds all four; byte
-// stores otherwise (row tails, unaligned d_dst, rows of a packed image whose width is no multiple of 4).
-// MAP: xy[(y * cols + x) * 2 + {0, 1}] = (ix, iy) instead; src / dst / valid are not touched and the grid has z = 1.
-// The work of one thread: destination pixels x4 .. x4 + 3 of row y of image z (host-callable, so that a CPU build can
-// run the kernel's own code).
-template <bool MAP>
-__host__ __device__ __forceinline__ void rectify_four(const pm_rectify_view& view, const uint8_t* __restrict__ src,
-                                                      int src_rows, int src_cols, size_t src_step, int rows, int cols,
-                                                      int border, uint8_t* __restrict__ dst, uint8_t* __restrict__ valid,
-                                                      int32_t* __restrict__ xy, int x4, int y, int z) {
-  const int count = cols - x4 < 4 ? cols - x4 : 4;
+// What a launch writes.  Gray: n gray images (+ mask).  Map: the Q5 coordinates, xy[(y * cols + x) * 2 + {0, 1}] =
+// (ix, iy); src / dst / valid are not touched and the grid has z = 1.  Bgr: interleaved BGR, the 8-bit image (+ mask).
+// BgrFloat: the float image = byte x (float)(1 / 255.) (CastImage3bTo3f), next to or instead of the 8-bit one (+ mask).
+enum class RectifyKind { Gray, Map, Bgr, BgrFloat };
+
+// The arguments of a launch, by value like the view inside them: filled once on the host, nothing allocated.
+// src_step: bytes per source row (>= src_cols, BGR: >= 3 * src_cols).  Images follow one another at src_rows * src_step
+// (source) and rows * cols pixels (destination, mask).  valid may be null; BgrFloat: dst may be null.
+struct RectifyArgs {
+  pm_rectify_view view;
+  const uint8_t* src;
+  int src_rows, src_cols;
+  size_t src_step;
+  int rows, cols;
+  int border;
+  uint8_t* dst;
+  float* dstf;
+  uint8_t* valid;
+  int32_t* xy;
+};
+
+// ---- what does not depend on the pixel format --------------------------------------------------------------------------
+// the Q5 source positions of destination pixels x4 .. x4 + 3 of row y
+__host__ __device__ __forceinline__ void rectify_positions(const pm_rectify_view& view, int x4, int y, int ix[4], int iy[4],
+                                                           bool ok[4]) {
   const double b = ((double)y - view.cy_new) / view.fy_new;
-  int ix[4], iy[4];
-  bool ok[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const double a = ((double)(x4 + k) - view.cx_new) / view.fx_new;
     ok[k] = rectify_source_q5(view, a, b, &ix[k], &iy[k]);
   }
-  if (MAP) {
-    int32_t* o = xy + ((size_t)y * cols + x4) * 2;
+}
+// in[t]: tap t (0 .. 3: x0, x0 + 1 of row y0, then of row y0 + 1) of pixel k of the thread is read from the image
+__host__ __device__ __forceinline__ void rectify_inside(int ix, int iy, bool ok, int k, int count, int src_rows, int src_cols,
+                                                        bool in[4]) {
+  const int x0 = ix >> 5, y0 = iy >> 5;  // floor
 #pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (k < count) {
-        o[2 * k] = ix[k];
-        o[2 * k + 1] = iy[k];
-      }
-    return;
+  for (int t = 0; t < 4; ++t) {
+    const int tx = x0 + (t & 1), ty = y0 + (t >> 1);
+    in[t] = ok && k < count && (unsigned)tx < (unsigned)src_cols && (unsigned)ty < (unsigned)src_rows;
   }
-  const uint8_t* img = src + (size_t)z * src_rows * src_step;
-  // the 16 gathers first (independent loads in flight together), the blends after them
-  int tap[4][4];
-  bool in[4][4];
+}
+// the Q5 weights of the four taps (their sum is 1024)
+__host__ __device__ __forceinline__ void rectify_weights(int ix, int iy, int w[4]) {
+  const int ax = ix & 31, ay = iy & 31;
+  w[0] = (32 - ax) * (32 - ay);
+  w[1] = ax * (32 - ay);
+  w[2] = (32 - ax) * ay;
+  w[3] = ax * ay;
+}
+// the mask byte of a pixel: 255 where every tap with a non-zero weight came from the image
+__host__ __device__ __forceinline__ unsigned rectify_mask_byte(bool ok, const bool in[4], const int w[4]) {
+  bool all_in = ok;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int x0 = ix[k] >> 5, y0 = iy[k] >> 5;  // floor
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int tx = x0 + (t & 1), ty = y0 + (t >> 1);
-      in[k][t] = ok[k] && k < count && (unsigned)tx < (unsigned)src_cols && (unsigned)ty < (unsigned)src_rows;
-      tap[k][t] = in[k][t] ? (int)img[(size_t)ty * src_step + tx] : border;
-    }
-  }
-  unsigned px = 0, vm = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int ax = ix[k] & 31, ay = iy[k] & 31;
-    const int w[4] = {(32 - ax) * (32 - ay), ax * (32 - ay), (32 - ax) * ay, ax * ay};
-    const int sum = w[0] * tap[k][0] + w[1] * tap[k][1] + w[2] * tap[k][2] + w[3] * tap[k][3];
-    bool all_in = ok[k];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) all_in = all_in && (in[k][t] || w[t] == 0);
-    const unsigned out = ok[k] ? (unsigned)((sum + 512) >> 10) : (unsigned)border;
-    px |= out << (8 * k);
-    vm |= (all_in ? 255u : 0u) << (8 * k);
-  }
-  const size_t at = ((size_t)z * rows + y) * cols + x4;
-  uint8_t* o = dst + at;
-  if (count == 4 && ((uintptr_t)o & 3u) == 0) {
-    *(uint32_t*)o = px;
+  for (int t = 0; t < 4; ++t) all_in = all_in && (in[t] || w[t] == 0);
+  return all_in ? 255u : 0u;
+}
+// The first `count` bytes of `word` (lowest first) to p: one 32-bit word where the address is 4-byte aligned and the row
+// holds all four; byte stores otherwise (row tails, an unaligned destination, rows of a packed image whose width is no
+// multiple of 4).
+__host__ __device__ __forceinline__ void rectify_store4(uint8_t* p, unsigned word, int count) {
+  if (count == 4 && ((uintptr_t)p & 3u) == 0) {
+    *(uint32_t*)p = word;
   } else {
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      if (k < count) o[k] = (uint8_t)(px >> (8 * k));
-  }
-  if (valid) {
-    uint8_t* m = valid + at;
-    if (count == 4 && ((uintptr_t)m & 3u) == 0) {
-      *(uint32_t*)m = vm;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (k < count) m[k] = (uint8_t)(vm >> (8 * k));
-    }
+      if (k < count) p[k] = (uint8_t)(word >> (8 * k));
   }
 }
 
-template <bool MAP>
-__global__ void __launch_bounds__(kRectifyBlockX * kRectifyBlockY)
-    k_rectify(pm_rectify_view view, const uint8_t* __restrict__ src, int src_rows, int src_cols, size_t src_step, int rows,
-              int cols, int border, uint8_t* __restrict__ dst, uint8_t* __restrict__ valid, int32_t* __restrict__ xy) {
-  const int x4 = (int)(blockIdx.x * kRectifyBlockX + threadIdx.x) * 4;
-  const int y = (int)(blockIdx.y * kRectifyBlockY + threadIdx.y);
-  if (x4 >= cols || y >= rows) return;
-  rectify_four<MAP>(view, src, src_rows, src_cols, src_step, rows, cols, border, dst, valid, xy, x4, y, (int)blockIdx.z);
-}
-
-// ---- interleaved BGR (pm_rectify_bgr8, pm_match_raw_bgr_device) -------------------------------------------------------
+// ---- the gather of interleaved BGR (pm_rectify_bgr8, pm_match_raw_bgr_device) ---------------------------------------------
 // The definition is tests/rectify_bgr_ref.py: the gray definition channel by channel at the SAME Q5 coordinates, one
 // border value, one mask per image.  The geometry above is therefore evaluated once per destination pixel; the three
 // channels share the position, the four weights and the mask.
@@ -195,57 +179,68 @@ __host__ __device__ __forceinline__ unsigned rectify_blend(const int w[4], uint6
   return (unsigned)((sum + 512) >> 10);
 }
 
-// The work of one thread: destination pixels x4 .. x4 + 3 of row y of image z, 12 bytes of dst (and / or 12 floats of
-// dstf = byte x (float)(1 / 255.), CastImage3bTo3f) and 4 bytes of mask.  dst / dstf / valid may each be null.
-// src_step: bytes per source row (>= 3 * src_cols).  The 12 bytes leave as three 32-bit words where the address is 4-byte
-// aligned and the row holds all four pixels, byte by byte otherwise (row tails, an unaligned dst, the rows of a packed
-// image of odd width, whose alignment alternates); the 12 floats as three 16-byte stores under the same rule for 16 bytes.
-__host__ __device__ __forceinline__ void rectify_four_bgr(const pm_rectify_view& view, const uint8_t* __restrict__ src,
-                                                          int src_rows, int src_cols, size_t src_step, int rows, int cols,
-                                                          int border, uint8_t* __restrict__ dst, float* __restrict__ dstf,
-                                                          uint8_t* __restrict__ valid, int x4, int y, int z) {
-  const int count = cols - x4 < 4 ? cols - x4 : 4;
-  const double b = ((double)y - view.cy_new) / view.fy_new;
+// ---- one thread, one kernel ---------------------------------------------------------------------------------------------
+// The work of one thread: destination pixels x4 .. x4 + 3 of row y of image z (host-callable, so that a CPU build can
+// run the kernel's own code).  Gray: four bytes of dst, stored by rectify_store4.  BGR: 12 bytes of dst as three 32-bit
+// words under the rule of rectify_store4, byte by byte otherwise (the alignment of the rows of a packed image of odd width
+// alternates); the 12 floats as three 16-byte stores under the same rule for 16 bytes.  The mask: four bytes, rectify_store4.
+template <RectifyKind KIND>
+__host__ __device__ __forceinline__ void rectify_four(const RectifyArgs& a, int x4, int y, int z) {
+  constexpr bool BGR = KIND == RectifyKind::Bgr || KIND == RectifyKind::BgrFloat;
+  const int count = a.cols - x4 < 4 ? a.cols - x4 : 4;
   int ix[4], iy[4];
   bool ok[4];
+  rectify_positions(a.view, x4, y, ix, iy, ok);
+  if constexpr (KIND == RectifyKind::Map) {
+    int32_t* o = a.xy + ((size_t)y * a.cols + x4) * 2;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double a = ((double)(x4 + k) - view.cx_new) / view.fx_new;
-    ok[k] = rectify_source_q5(view, a, b, &ix[k], &iy[k]);
+    for (int k = 0; k < 4; ++k)
+      if (k < count) {
+        o[2 * k] = ix[k];
+        o[2 * k + 1] = iy[k];
+      }
+    return;
   }
-  const uint8_t* img = src + (size_t)z * src_rows * src_step;
+  const uint8_t* img = a.src + (size_t)z * a.src_rows * a.src_step;
+  const int border = a.border;  // read once: a select below, no branch around each blend
   const uint32_t border3 = (uint32_t)border * 0x010101u;
-  // the gathers first (independent loads in flight together), the blends after them
-  RectifyRaw top[4], bot[4];
+  // the 16 gathers first (independent loads in flight together), the blends after them
+  [[maybe_unused]] int tap[4][4];            // gray: the taps themselves
+  [[maybe_unused]] RectifyRaw top[4], bot[4];  // BGR: the rows of taps, not yet taken apart
   bool in[4][4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const int x0 = ix[k] >> 5, y0 = iy[k] >> 5;  // floor
+    const int x0 = ix[k] >> 5, y0 = iy[k] >> 5;
+    rectify_inside(ix[k], iy[k], ok[k], k, count, a.src_rows, a.src_cols, in[k]);
+    if constexpr (BGR) {
+      top[k] = rectify_load_pair(img, a.src_cols, a.src_step, x0, y0, in[k][0], in[k][1]);
+      bot[k] = rectify_load_pair(img, a.src_cols, a.src_step, x0, y0 + 1, in[k][2], in[k][3]);
+    } else {
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int tx = x0 + (t & 1), ty = y0 + (t >> 1);
-      in[k][t] = ok[k] && k < count && (unsigned)tx < (unsigned)src_cols && (unsigned)ty < (unsigned)src_rows;
+      for (int t = 0; t < 4; ++t)
+        tap[k][t] = in[k][t] ? (int)img[(size_t)(y0 + (t >> 1)) * a.src_step + (x0 + (t & 1))] : border;
     }
-    top[k] = rectify_load_pair(img, src_cols, src_step, x0, y0, in[k][0], in[k][1]);
-    bot[k] = rectify_load_pair(img, src_cols, src_step, x0, y0 + 1, in[k][2], in[k][3]);
   }
-  unsigned px[4], vm = 0;  // px[k]: b | g << 8 | r << 16 of pixel k
+  unsigned px[4], vm = 0;  // px[k]: the byte of pixel k; BGR: b | g << 8 | r << 16
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const int ax = ix[k] & 31, ay = iy[k] & 31;
-    const int w[4] = {(32 - ax) * (32 - ay), ax * (32 - ay), (32 - ax) * ay, ax * ay};
-    const uint64_t t01 = rectify_tap_pair(top[k], src_cols, ix[k] >> 5, in[k][0], in[k][1], border3);
-    const uint64_t t23 = rectify_tap_pair(bot[k], src_cols, ix[k] >> 5, in[k][2], in[k][3], border3);
-    bool all_in = ok[k];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) all_in = all_in && (in[k][t] || w[t] == 0);
-    px[k] = ok[k] ? rectify_blend(w, t01, t23, 0) | (rectify_blend(w, t01, t23, 1) << 8) | (rectify_blend(w, t01, t23, 2) << 16)
-                  : border3;
-    vm |= (all_in ? 255u : 0u) << (8 * k);
+    int w[4];
+    rectify_weights(ix[k], iy[k], w);
+    if constexpr (BGR) {
+      const uint64_t t01 = rectify_tap_pair(top[k], a.src_cols, ix[k] >> 5, in[k][0], in[k][1], border3);
+      const uint64_t t23 = rectify_tap_pair(bot[k], a.src_cols, ix[k] >> 5, in[k][2], in[k][3], border3);
+      px[k] = ok[k] ? rectify_blend(w, t01, t23, 0) | (rectify_blend(w, t01, t23, 1) << 8) | (rectify_blend(w, t01, t23, 2) << 16)
+                    : border3;
+    } else {
+      const int sum = w[0] * tap[k][0] + w[1] * tap[k][1] + w[2] * tap[k][2] + w[3] * tap[k][3];
+      px[k] = ok[k] ? (unsigned)((sum + 512) >> 10) : (unsigned)border;
+    }
+    vm |= rectify_mask_byte(ok[k], in[k], w) << (8 * k);
   }
-  const size_t at = ((size_t)z * rows + y) * cols + x4;
-  if (dst) {
-    uint8_t* o = dst + at * 3;
+  const size_t at = ((size_t)z * a.rows + y) * a.cols + x4;
+  if constexpr (!BGR) rectify_store4(a.dst + at, px[0] | (px[1] << 8) | (px[2] << 16) | (px[3] << 24), count);
+  if (BGR && a.dst) {
+    uint8_t* o = a.dst + at * 3;
     if (count == 4 && ((uintptr_t)o & 3u) == 0) {
       uint32_t* o32 = (uint32_t*)o;
       o32[0] = px[0] | (px[1] << 24);
@@ -261,14 +256,14 @@ __host__ __device__ __forceinline__ void rectify_four_bgr(const pm_rectify_view&
         }
     }
   }
-  if (dstf) {
+  if constexpr (KIND == RectifyKind::BgrFloat) {
     const float s = (float)(1.0 / 255.0);
     float f[12];
 #pragma unroll
     for (int k = 0; k < 4; ++k)
 #pragma unroll
       for (int c = 0; c < 3; ++c) f[3 * k + c] = (float)((px[k] >> (8 * c)) & 255u) * s;
-    float* o = dstf + at * 3;
+    float* o = a.dstf + at * 3;
     if (count == 4 && ((uintptr_t)o & 15u) == 0) {
       float4* o4 = (float4*)o;
       o4[0] = make_float4(f[0], f[1], f[2], f[3]);
@@ -284,30 +279,18 @@ __host__ __device__ __forceinline__ void rectify_four_bgr(const pm_rectify_view&
         }
     }
   }
-  if (valid) {
-    uint8_t* m = valid + at;
-    if (count == 4 && ((uintptr_t)m & 3u) == 0) {
-      *(uint32_t*)m = vm;
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (k < count) m[k] = (uint8_t)(vm >> (8 * k));
-    }
-  }
+  if (a.valid) rectify_store4(a.valid + at, vm, count);
 }
 
-// grid and block as k_rectify.  FLOAT = false compiles the float image out (dstf is not read): the instantiation
-// pm_match_raw_bgr_device and every caller without a float image run.  (A template also for the host build of
-// tests/cpp/rectify_bgr_host_main.cpp, which must not instantiate a kernel.)
-template <bool FLOAT>
-__global__ void __launch_bounds__(kRectifyBlockX * kRectifyBlockY)
-    k_rectify_bgr(pm_rectify_view view, const uint8_t* __restrict__ src, int src_rows, int src_cols, size_t src_step, int rows,
-                  int cols, int border, uint8_t* __restrict__ dst, float* __restrict__ dstf, uint8_t* __restrict__ valid) {
+// grid = (ceil(cols / 256), ceil(rows / 4), n), block = (64, 4).  A thread owns destination pixels x4 .. x4 + 3 of row y
+// of image z.  Four instantiations, one per RectifyKind; Bgr compiles the float image out (dstf is not read): what
+// pm_match_raw_bgr_device and every caller without a float image run.
+template <RectifyKind KIND>
+__global__ void __launch_bounds__(kRectifyBlockX * kRectifyBlockY) k_rectify(RectifyArgs a) {
   const int x4 = (int)(blockIdx.x * kRectifyBlockX + threadIdx.x) * 4;
   const int y = (int)(blockIdx.y * kRectifyBlockY + threadIdx.y);
-  if (x4 >= cols || y >= rows) return;
-  rectify_four_bgr(view, src, src_rows, src_cols, src_step, rows, cols, border, dst, FLOAT ? dstf : nullptr, valid, x4, y,
-                   (int)blockIdx.z);
+  if (x4 >= a.cols || y >= a.rows) return;
+  rectify_four<KIND>(a, x4, y, (int)blockIdx.z);
 }
 
 }  // namespace pm

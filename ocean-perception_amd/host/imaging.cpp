@@ -241,44 +241,45 @@ double StereoRectify(const CameraModel& cam1, const CameraModel& cam2, const std
   return baseline;
 }
 
-Image1b Rectify(const Image1b& raw, const RectifyView& view, int rows, int cols, Image1b* valid) {
-  if (raw.rows <= 0 || raw.cols <= 0 || rows <= 0 || cols <= 0) throw std::invalid_argument("Rectify: empty image");
-  std::lock_guard<std::mutex> lock(g_mutex);
-  pm_handle* h = Context();
-  const size_t out_bytes = (size_t)rows * cols;
-  DeviceBuffer d_in(h, Bytes(raw)), d_out(h, out_bytes), d_valid(h, out_bytes);
-  d_in.Upload(raw.data(), Bytes(raw));
-  Check(pm_rectify_u8(h, &view, d_in.as<uint8_t>(), 1, raw.rows, raw.cols, 0, rows, cols, 0, d_out.as<uint8_t>(),
-                      valid ? d_valid.as<uint8_t>() : nullptr, nullptr),
-        "pm_rectify_u8");
-  Image1b out(rows, cols);
-  d_out.Download(out.data(), out_bytes);
-  if (valid) {
-    if (valid->rows != rows || valid->cols != cols) valid->create(rows, cols);
-    d_valid.Download(valid->data(), out_bytes);
-  }
-  return out;
-}
+namespace {
 
-core::Image<core::Vec3b> Rectify(const core::Image<core::Vec3b>& raw, const RectifyView& view, int rows, int cols,
-                                 core::Image<uint8_t>* valid) {
+// Both Rectify overloads: Pixel is uint8_t (pm_rectify_u8) or the three interleaved bytes of core::Vec3b (pm_rectify_bgr8).
+template <typename Pixel>
+Image<Pixel> RectifyImage(const Image<Pixel>& raw, const RectifyView& view, int rows, int cols, Image1b* valid) {
+  static_assert(sizeof(Pixel) == 1 || sizeof(Pixel) == 3, "gray, or interleaved BGR bytes");
   if (raw.rows <= 0 || raw.cols <= 0 || rows <= 0 || cols <= 0) throw std::invalid_argument("Rectify: empty image");
-  static_assert(sizeof(core::Vec3b) == 3, "Image3b is interleaved bytes");
   std::lock_guard<std::mutex> lock(g_mutex);
   pm_handle* h = Context();
+  Image<Pixel> out(rows, cols);
   const size_t px = (size_t)rows * cols;
-  DeviceBuffer d_in(h, Bytes(raw)), d_out(h, 3 * px), d_valid(h, px);
+  DeviceBuffer d_in(h, Bytes(raw)), d_out(h, Bytes(out)), d_valid(h, px);
   d_in.Upload(raw.data(), Bytes(raw));
-  Check(pm_rectify_bgr8(h, &view, d_in.as<uint8_t>(), 1, raw.rows, raw.cols, 0, rows, cols, 0, d_out.as<uint8_t>(), nullptr,
-                        valid ? d_valid.as<uint8_t>() : nullptr, nullptr),
-        "pm_rectify_bgr8");
-  core::Image<core::Vec3b> out(rows, cols);
-  d_out.Download(out.data(), 3 * px);
+  uint8_t* d_mask = valid ? d_valid.as<uint8_t>() : nullptr;
+  if constexpr (sizeof(Pixel) == 1)
+    Check(pm_rectify_u8(h, &view, d_in.as<uint8_t>(), 1, raw.rows, raw.cols, 0, rows, cols, 0, d_out.as<uint8_t>(), d_mask,
+                        nullptr),
+          "pm_rectify_u8");
+  else
+    Check(pm_rectify_bgr8(h, &view, d_in.as<uint8_t>(), 1, raw.rows, raw.cols, 0, rows, cols, 0, d_out.as<uint8_t>(), nullptr,
+                          d_mask, nullptr),
+          "pm_rectify_bgr8");
+  d_out.Download(out.data(), Bytes(out));
   if (valid) {
     if (valid->rows != rows || valid->cols != cols) valid->create(rows, cols);
     d_valid.Download(valid->data(), px);
   }
   return out;
+}
+
+}  // namespace
+
+Image1b Rectify(const Image1b& raw, const RectifyView& view, int rows, int cols, Image1b* valid) {
+  return RectifyImage(raw, view, rows, cols, valid);
+}
+
+core::Image<core::Vec3b> Rectify(const core::Image<core::Vec3b>& raw, const RectifyView& view, int rows, int cols,
+                                 core::Image<uint8_t>* valid) {
+  return RectifyImage(raw, view, rows, cols, valid);
 }
 
 }  // namespace imaging

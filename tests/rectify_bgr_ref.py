@@ -1,5 +1,5 @@
 """The CPU definition of undistortion + rectification of interleaved 8-bit BGR images (include/pm/imaging.h:
-pm_rectify_bgr8, pm_match_raw_bgr_device), in numpy.  The kernel (csrc/pm_rectify.hpp: rectify_four_bgr) is held to it bit
+pm_rectify_bgr8, pm_match_raw_bgr_device), in numpy.  The kernel (csrc/pm_rectify.hpp: rectify_four) is held to it bit
 for bit.
 
 It is the gray definition (tests/rectify_ref.py) channel by channel at the SAME Q5 coordinates:

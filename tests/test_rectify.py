@@ -278,9 +278,9 @@ def host_kernel_exe(tmp_path_factory):
 
 
 def test_kernel_code_on_the_host_equals_the_definition(host_kernel_exe, tmp_path):
-    """rectify_four -- what every thread of k_rectify runs -- over whole images on the CPU: pixels, mask and map equal the
-    definition with tolerance 0, nothing is written outside the images, and AddressSanitizer / UBSan see every access.
-    Random cases from the fuzzer's generator (sizes <= 48x64) plus the odd strided case of the device tests."""
+    """rectify_four<Gray> and <Map> -- what every thread of k_rectify runs -- over whole images on the CPU: pixels, mask and
+    map equal the definition with tolerance 0, nothing is written outside the images, and AddressSanitizer / UBSan see
+    every access.  Random cases from the fuzzer's generator (sizes <= 48x64) plus the odd strided case of the device tests."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from fuzz_rectify import random_view
     rng = np.random.default_rng(21)
@@ -300,7 +300,7 @@ def test_kernel_code_on_the_host_equals_the_definition(host_kernel_exe, tmp_path
             f.write(np.array([n, sr, sc, step, rows, cols, border, shift, mask], np.int32).tobytes())
             f.write(np.asarray(view, np.float64).tobytes())
             f.write(raws[-1].tobytes())
-    r = subprocess.run([host_kernel_exe, str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")], capture_output=True,
+    r = subprocess.run([host_kernel_exe, "gray", str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")], capture_output=True,
                        text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     buf, pos = np.fromfile(tmp_path / "out.bin", np.uint8), 0

@@ -3,7 +3,7 @@
 
 CPU tests pin the definition (tests/rectify_bgr_ref.py: the gray definition channel by channel at the same Q5
 coordinates, one border value, one mask, the float image = byte x (float)(1 / 255.)) and run the kernel's own per-thread
-code (csrc/pm_rectify.hpp: rectify_four_bgr) on the host under ASan / UBSan.  GPU tests hold the kernel to the definition
+code (csrc/pm_rectify.hpp: rectify_four) on the host under ASan / UBSan.  GPU tests hold the kernel to the definition
 with tolerance 0 on pixels, float image and mask: the geometry is the gray kernel's (binary64, one rounding per operation,
 -ffp-contract=off), the interpolation is integer, the float image is one binary32 multiplication."""
 import os
@@ -82,22 +82,23 @@ def test_definition_reproduces_its_fixture():
 # ---- 2. the kernel's own per-thread code, run on the host ----------------------------------------------------------------
 @pytest.fixture(scope="module")
 def host_kernel_exe(tmp_path_factory):
-    """tests/cpp/rectify_bgr_host_main.cpp: csrc/pm_rectify.hpp compiled for the host alone, with the sanitizers."""
+    """tests/cpp/rectify_host_main.cpp (the program of tests/test_rectify.py, run here in its bgr mode): csrc/pm_rectify.hpp
+    compiled for the host alone, with the sanitizers."""
     out = tmp_path_factory.mktemp("rectifybgrhost") / "rectify_bgr_host_main"
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     cmd = [hipcc, "-x", "hip", "--cuda-host-only", "-O1", "-std=c++17", "-ffp-contract=off",
            "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
            "-I" + os.path.join(ROOT, "ocean-perception_amd", "csrc"),
-           os.path.join(ROOT, "tests", "cpp", "rectify_bgr_host_main.cpp"), "-o", str(out)]
+           os.path.join(ROOT, "tests", "cpp", "rectify_host_main.cpp"), "-o", str(out)]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     return str(out)
 
 
 def test_kernel_code_on_the_host_equals_the_definition(host_kernel_exe, tmp_path):
-    """rectify_four_bgr -- what every thread of k_rectify_bgr runs -- over whole images on the CPU: pixels, float image and
-    mask equal the definition with tolerance 0 and the 0xA5 guards around them are intact.  The sources are exactly
-    sized heap allocations (packed ones included, where the last row ends with the allocation), so AddressSanitizer
+    """rectify_four<Bgr> and <BgrFloat> -- what every thread of k_rectify runs for BGR -- over whole images on the CPU:
+    pixels, float image and mask equal the definition with tolerance 0 and the 0xA5 guards around them are intact.  The
+    sources are exactly sized heap allocations (packed ones included, where the last row ends with the allocation), so AddressSanitizer
     reports a 4- or 2-byte load that reaches past byte 3 * src_cols of the last row.  The fixed shapes of the device tests
     (odd strided, odd packed, behind-camera, tiny, 64x96 radtan and identity, 1x1), three one-column sources (the path without a 6-byte window)
     and a two-column one (exactly one window), plus 40 random cases of at most 48x64 from the fuzzer's generator (seed 22)."""
@@ -131,7 +132,7 @@ def test_kernel_code_on_the_host_equals_the_definition(host_kernel_exe, tmp_path
             f.write(np.array([n, sr, sc, step, rows, cols, border, shift, outs], np.int32).tobytes())
             f.write(np.asarray(view, np.float64).tobytes())
             f.write(raws[-1].tobytes())
-    r = subprocess.run([host_kernel_exe, str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")], capture_output=True,
+    r = subprocess.run([host_kernel_exe, "bgr", str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")], capture_output=True,
                        text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     buf, pos = np.fromfile(tmp_path / "out.bin", np.uint8), 0

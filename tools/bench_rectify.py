@@ -32,6 +32,28 @@ def calibration(rows, cols):
     return cam1, cam2, rot(2, 0.3) @ rot(1, 0.8) @ rot(0, 0.5), np.array([-0.11, 0.0004, -0.0006])
 
 
+def event_timer(engine, steps, warmup):
+    """-> timed(fn): fn `warmup` times, then HIP events on the handle's stream around each of `steps` calls; ms."""
+    import torch
+    stream = torch.cuda.ExternalStream(engine.stream())
+
+    def timed(fn):
+        for _ in range(warmup):
+            fn()
+        engine.synchronize()
+        ms = []
+        for _ in range(steps):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record(stream)
+            fn()
+            t1.record(stream)
+            t1.synchronize()
+            ms.append(t0.elapsed_time(t1))
+        return {"median_ms": float(np.median(ms)), "min_ms": float(min(ms)), "max_ms": float(max(ms))}
+
+    return timed
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=720)
@@ -56,21 +78,7 @@ def main():
     res = {"rows": rows, "cols": cols, "steps": args.steps, "baseline": baseline,
            "pair_bytes_read_and_written": 4 * rows * cols}
     with pm.Engine(pm.default_params(0, patch=5), max_rows=64, max_cols=64) as e:
-        stream = torch.cuda.ExternalStream(e.stream())
-
-        def timed(fn):
-            for _ in range(args.warmup):
-                fn()
-            e.synchronize()
-            ms = []
-            for _ in range(args.steps):
-                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                t0.record(stream)
-                fn()
-                t1.record(stream)
-                t1.synchronize()
-                ms.append(t0.elapsed_time(t1))
-            return {"median_ms": float(np.median(ms)), "min_ms": float(min(ms)), "max_ms": float(max(ms))}
+        timed = event_timer(e, args.steps, args.warmup)
 
         def pair(with_mask):
             for i, v in enumerate((v1, v2)):

@@ -6,16 +6,16 @@
   bgr_float / bgr_all: the same with the float image instead of / next to the 8-bit one and the mask (for the record)
 
 Same run, same handle, same view: the left view of tools/bench_rectify.py's EuRoC-like calibration (radial-tangential
-distortion).  HIP events on the handle's stream around every call, median (and min / max) over --steps calls after
---warmup.  The criterion: the bgr median is below 3 x the gray median -- three gray launches are what the kernel
-replaces.  Prints one JSON line; --record FILE also writes the figures there, with the tree's sha when --sha gives one.
+distortion) and its timing loop: HIP events on the handle's stream around every call, median (and min / max) over
+--steps calls after --warmup.  The criterion: the bgr median is below 3 x the gray median -- three gray launches are
+what the kernel replaces.  Prints one JSON line; --record FILE also writes the figures there, with the tree's sha when --sha gives one.
 Exit status 1 when the criterion is missed."""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ocean-perception_amd", "python"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import numpy as np
-from bench_rectify import calibration
+from bench_rectify import calibration, event_timer
 
 
 def main():
@@ -41,21 +41,7 @@ def main():
     torch.cuda.synchronize()
     res = {"rows": rows, "cols": cols, "steps": args.steps, "warmup": args.warmup}
     with pm.Engine(pm.default_params(0, patch=5), max_rows=64, max_cols=64) as e:
-        stream = torch.cuda.ExternalStream(e.stream())
-
-        def timed(fn):
-            for _ in range(args.warmup):
-                fn()
-            e.synchronize()
-            ms = []
-            for _ in range(args.steps):
-                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                t0.record(stream)
-                fn()
-                t1.record(stream)
-                t1.synchronize()
-                ms.append(t0.elapsed_time(t1))
-            return {"median_ms": float(np.median(ms)), "min_ms": float(min(ms)), "max_ms": float(max(ms))}
+        timed = event_timer(e, args.steps, args.warmup)
 
         def run_bgr(d8, df, dm):
             e.rectify_bgr8(view, bgr.data_ptr(), 1, rows, cols, 0, rows, cols, 0, d8, df, dm)
