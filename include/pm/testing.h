@@ -27,6 +27,26 @@ long long pm_debug_live_host_buffers(void);
 long long pm_debug_live_host_bytes(void);
 long long pm_debug_live_graph_execs(void);
 
+/* ---- the directional sweeps as ONE iteration of Match() launches them ------------------------------------------------
+ * pm_propagate (include/pm/patchmatch.h) with the iteration's noise amplitude as an argument, and a record of the kernel
+ * variant every pass ran.  The amplitude changes no result: with the window, the axis and the direction it selects the
+ * lanes per chain segment of the run engine (csrc/pm_sweeps.hip), which pm_propagate always calls with 1e30f, "no noise".
+ * amp must be >= 0 (NaN is refused).  ran: null, or four records indexed by the pass (bit k of pass_mask: 0 = row +1,
+ * 1 = column +1, 2 = row -1, 3 = column -1); a pass the mask leaves out, or one whose interior is empty, stays all zero,
+ * and so do all four when the call is refused.  Errors name pm_debug_propagate.  The records are written on the host
+ * from what the launch code decided; no kernel differs for them. */
+typedef struct pm_debug_sweep_variant {
+  int engine;     /* PM_ENGINE_*: the engine that actually ran, after the serial fallback for chains beyond the LDS */
+  int axis, dir;  /* 0 = along a row, 1 = along a column; +1 / -1                                                    */
+  int group;      /* lanes per chain segment (16 / 32); 0 for engines without groups                                 */
+  int waves;      /* wavefronts per chain; 0 for engines without chain segments                                      */
+  int window;     /* compiled-in window TP of k_runblk3; 0 = the general kernel, and every other engine              */
+  int lref;       /* 1 = reference lines staged in LDS                                                               */
+  int chain_len, chains;
+} pm_debug_sweep_variant;
+int pm_debug_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
+                       int patch_h, int patch_w, int pass_mask, float amp, pm_debug_sweep_variant* ran);
+
 /* ---- the row-tiled driver's device discipline, provable on ONE GPU ------------------------------------------------
  * pm_tiled_create with the bands accounted to LOGICAL devices: band k lives on logical_devices[k] (>= 0; several bands
  * may share one) while every HIP call still goes to the physical device of the band's handle.  Such a plan logs every

@@ -338,9 +338,10 @@ void launch_noise_cost(pm_handle* h, const PlaneSet& ps, const CostParams& cp, c
 void launch_noise_only(pm_handle* h, const PlaneSet& ps, const CostParams& cp, float amount, hipStream_t stream);
 void launch_background(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const Interior& in, float factor,
                        int cached, int slots, hipStream_t stream);
-// amp: the iteration's noise amplitude (1e30f: none)
+// amp: the iteration's noise amplitude (1e30f: none); ran (may be null): the variant launched (pm_sweep_defs.hpp), left
+// as it is where the geometry has nothing to sweep
 int run_sweep(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, float amp,
-              hipStream_t stream);
+              hipStream_t stream, SweepVariant* ran = nullptr);
 void launch_finalize(pm_handle* h, const PlaneSet& ps, float* d_disp_l, float* d_disp_r, int n, hipStream_t stream);
 void launch_mask_occlusions(pm_handle* h, float* d_disp_l, const float* d_disp_r, int rows, int cols,
                             hipStream_t stream);

@@ -4,6 +4,7 @@
 // and synchronisation only: every kernel is reached through the launch functions of pm_handle.hpp.
 #include <cstring>
 
+#include "pm/testing.h"
 #include "pm_handle.hpp"
 
 using namespace pm;
@@ -769,12 +770,14 @@ int pm_add_noise(pm_handle* h, float* disp, int rows, int cols, float amount) {
   return stage_out(h, ps, disp, 0);
 }
 
-int pm_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
-                 int patch_h, int patch_w, int pass_mask) {
-  if (!h) return PM_ERR_INVALID_ARG;
-  if (int rc = refuse_while_capturing(h, "pm_propagate")) return rc;
+namespace {
+// pm_propagate and pm_debug_propagate: `who` names the entry point in error messages, ran (may be null) receives the
+// variant each pass launched, indexed by the pass
+int propagate_impl(pm_handle* h, const char* who, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
+                   int patch_h, int patch_w, int pass_mask, float amp, pm::SweepVariant* ran) {
+  if (int rc = refuse_while_capturing(h, who)) return rc;
   if (!left || !right || !disp) {
-    set_err(h, "pm_propagate: null pointer");
+    set_err(h, "%s: null pointer", who);
     return PM_ERR_INVALID_ARG;
   }
   if (h->params.semantics == PM_SEM_CPU)
@@ -786,7 +789,7 @@ int pm_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, int ro
   // (patchmatch_gpu.cu:156-171): the sample position max(x - d, r) has no upper clamp, in the reference neither, so a
   // negative d reads past the row there as well.  Inside Match every map has been through the noise step's max(disp, 0);
   // here the caller's map arrives as it is, so it is checked.
-  if (int rc = refuse_map_values(h, "pm_propagate", disp, rows, cols, /*nan_ok=*/false)) return rc;
+  if (int rc = refuse_map_values(h, who, disp, rows, cols, /*nan_ok=*/false)) return rc;
   PlaneSet ps;
   if (int rc = stage_prep(h, left, right, rows, cols, &ps)) return rc;
   if (int rc = stage_disp_in(h, ps, disp)) return rc;
@@ -796,8 +799,35 @@ int pm_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, int ro
   if (int rc = launch_check(h, "cost")) return rc;
   for (int k = 0; k < 4; ++k)
     if (pass_mask & (1 << k))
-      if (int rc = run_sweep(h, ps, cp, sweep_geom(h->params, in, k), 1, 1e30f, h->stream)) return rc;
+      if (int rc = run_sweep(h, ps, cp, sweep_geom(h->params, in, k), 1, amp, h->stream, ran ? ran + k : nullptr))
+        return rc;
   return stage_out(h, ps, disp, 0);
+}
+}  // namespace
+
+int pm_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
+                 int patch_h, int patch_w, int pass_mask) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  return propagate_impl(h, "pm_propagate", left, right, rows, cols, disp, patch_h, patch_w, pass_mask, 1e30f, nullptr);
+}
+
+// pm_propagate with the iteration's noise amplitude and a record of what was launched (include/pm/testing.h)
+int pm_debug_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
+                       int patch_h, int patch_w, int pass_mask, float amp, pm_debug_sweep_variant* ran) {
+  if (ran) memset(ran, 0, 4 * sizeof(*ran));  // before any refusal: a failed call leaves no stale record
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (!(amp >= 0.f)) {
+    set_err(h, "pm_debug_propagate: negative or NaN noise amplitude");
+    return PM_ERR_INVALID_ARG;
+  }
+  pm::SweepVariant v[4];
+  const int rc = propagate_impl(h, "pm_debug_propagate", left, right, rows, cols, disp, patch_h, patch_w, pass_mask, amp,
+                                ran ? v : nullptr);
+  if (ran)
+    for (int k = 0; k < 4; ++k)
+      ran[k] = pm_debug_sweep_variant{v[k].engine, v[k].axis, v[k].dir,       v[k].group, v[k].waves,
+                                      v[k].window, v[k].lref, v[k].chain_len, v[k].chains};
+  return rc;
 }
 
 int pm_remove_background(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,

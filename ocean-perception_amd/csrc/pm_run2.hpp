@@ -270,13 +270,14 @@ __global__ void __launch_bounds__(64 * kMaxSegWaves) k_runblk2(PlaneSet ps, Cost
 
 template <int GS, int AXIS>
 inline void launch_run2_k(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, int waves,
-                          hipStream_t stream) {
+                          hipStream_t stream, SweepVariant* ran) {
   const int chains = g.c_hi - g.c_lo + 1;
   const int n = (g.s_last - g.s_first) * g.dir + 1;
   const int nwv = waves < 1 ? 1 : (waves > kMaxSegWaves ? kMaxSegWaves : waves);
   const int per_block = (kWave / GS) * nwv;
   int len = (n + per_block - 1) / per_block;
   if (len < 8) len = 8;
+  if (ran) ran->group = GS, ran->waves = nwv;
   const int n1 = (n + 1 + 3) & ~3;
   const size_t lds_bytes = sizeof(float) * (5 * (size_t)n1 + per_block + 1 + 2);
   allow_big_lds(k_runblk2<GS, AXIS>, lds_bytes);
@@ -286,15 +287,15 @@ inline void launch_run2_k(const PlaneSet& ps, const CostParams& cp, const SweepG
 
 // PM_SEM_GPU, in place.  group = lanes per chain segment: 32, 16 or 8 (its window is 3 lanes).
 inline void launch_sweep_run2(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, int waves,
-                              int group, hipStream_t stream) {
+                              int group, hipStream_t stream, SweepVariant* ran = nullptr) {
   if (g.axis == 0) {
-    if (group <= 8) launch_run2_k<8, 0>(ps, cp, g, slots, waves, stream);
-    else if (group <= 16) launch_run2_k<16, 0>(ps, cp, g, slots, waves, stream);
-    else launch_run2_k<32, 0>(ps, cp, g, slots, waves, stream);
+    if (group <= 8) launch_run2_k<8, 0>(ps, cp, g, slots, waves, stream, ran);
+    else if (group <= 16) launch_run2_k<16, 0>(ps, cp, g, slots, waves, stream, ran);
+    else launch_run2_k<32, 0>(ps, cp, g, slots, waves, stream, ran);
   } else {
-    if (group <= 8) launch_run2_k<8, 1>(ps, cp, g, slots, waves, stream);
-    else if (group <= 16) launch_run2_k<16, 1>(ps, cp, g, slots, waves, stream);
-    else launch_run2_k<32, 1>(ps, cp, g, slots, waves, stream);
+    if (group <= 8) launch_run2_k<8, 1>(ps, cp, g, slots, waves, stream, ran);
+    else if (group <= 16) launch_run2_k<16, 1>(ps, cp, g, slots, waves, stream, ran);
+    else launch_run2_k<32, 1>(ps, cp, g, slots, waves, stream, ran);
   }
 }
 

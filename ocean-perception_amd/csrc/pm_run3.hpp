@@ -887,13 +887,14 @@ inline size_t run3_lds_bytes(int n, int nseg) { return sizeof(float) * (4 * (siz
 
 template <int GS, int AXIS, int TP, int DIR, bool LREF>
 inline void launch_run3_l(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, int waves,
-                          hipStream_t stream) {
+                          hipStream_t stream, SweepVariant* ran) {
   const int chains = g.c_hi - g.c_lo + 1;
   const int n = (g.s_last - g.s_first) * g.dir + 1;
   const int nwv = waves < 1 ? 1 : (waves > kMaxSegWaves ? kMaxSegWaves : waves);
   const int nseg = (kWave / GS) * nwv;
   int len = (n + nseg - 1) / nseg;
   if (len < 8) len = 8;
+  if (ran) ran->group = GS, ran->waves = nwv, ran->window = TP, ran->lref = LREF ? 1 : 0;
   size_t lds_bytes = run3_lds_bytes(n, nseg);
   if (LREF) lds_bytes += run3_lref_bytes<AXIS>(ps);
   {  // tuning build: PM_RUN3_LDS_EXTRA_KB pads the allocation (how sensitive is the step to workgroups per CU?)
@@ -915,51 +916,51 @@ inline void launch_run3_l(const PlaneSet& ps, const CostParams& cp, const SweepG
 }
 template <int GS, int AXIS, int TP>
 inline void launch_run3_d(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, int waves,
-                          hipStream_t stream) {
+                          hipStream_t stream, SweepVariant* ran) {
   // column sweeps of the benchmark window stage their reference lines in LDS while that leaves room for at least
   // four workgroups per CU (PM_RUN2_LREF / PM_RUN2_LREF_KB: A/B knobs)
   if constexpr (TP == 11) {
     const int n = (g.s_last - g.s_first) * g.dir + 1;
     const size_t total = run3_lds_bytes(n, 64) + run3_lref_bytes<AXIS>(ps);
     if (run3_lref_enabled(AXIS) && total <= run3_lref_limit()) {
-      if (g.dir > 0) launch_run3_l<GS, AXIS, TP, 1, true>(ps, cp, g, slots, waves, stream);
-      else launch_run3_l<GS, AXIS, TP, -1, true>(ps, cp, g, slots, waves, stream);
+      if (g.dir > 0) launch_run3_l<GS, AXIS, TP, 1, true>(ps, cp, g, slots, waves, stream, ran);
+      else launch_run3_l<GS, AXIS, TP, -1, true>(ps, cp, g, slots, waves, stream, ran);
       return;
     }
   }
-  if (g.dir > 0) launch_run3_l<GS, AXIS, TP, 1, false>(ps, cp, g, slots, waves, stream);
-  else launch_run3_l<GS, AXIS, TP, -1, false>(ps, cp, g, slots, waves, stream);
+  if (g.dir > 0) launch_run3_l<GS, AXIS, TP, 1, false>(ps, cp, g, slots, waves, stream, ran);
+  else launch_run3_l<GS, AXIS, TP, -1, false>(ps, cp, g, slots, waves, stream, ran);
 }
 
 // group = lanes per chain segment (32 or 16); windows of 3 and 5 always take 16, windows the fixed-size kernels do
 // not cover (not square, or wider than 11) take the general kernel with 32.
 template <int AXIS>
 inline void launch_run3_axis(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, int waves,
-                             int group, hipStream_t stream) {
+                             int group, hipStream_t stream, SweepVariant* ran) {
   const int sq = (cp.pw == cp.ph && cp.pw <= 11) ? cp.pw : 0;
   const bool g16 = group <= 16;
   switch (sq) {
-    case 3: launch_run3_d<16, AXIS, 3>(ps, cp, g, slots, waves, stream); break;
-    case 5: launch_run3_d<16, AXIS, 5>(ps, cp, g, slots, waves, stream); break;
+    case 3: launch_run3_d<16, AXIS, 3>(ps, cp, g, slots, waves, stream, ran); break;
+    case 5: launch_run3_d<16, AXIS, 5>(ps, cp, g, slots, waves, stream, ran); break;
     case 7:
-      if (g16) launch_run3_d<16, AXIS, 7>(ps, cp, g, slots, waves, stream);
-      else launch_run3_d<32, AXIS, 7>(ps, cp, g, slots, waves, stream);
+      if (g16) launch_run3_d<16, AXIS, 7>(ps, cp, g, slots, waves, stream, ran);
+      else launch_run3_d<32, AXIS, 7>(ps, cp, g, slots, waves, stream, ran);
       break;
     case 9:
-      if (g16) launch_run3_d<16, AXIS, 9>(ps, cp, g, slots, waves, stream);
-      else launch_run3_d<32, AXIS, 9>(ps, cp, g, slots, waves, stream);
+      if (g16) launch_run3_d<16, AXIS, 9>(ps, cp, g, slots, waves, stream, ran);
+      else launch_run3_d<32, AXIS, 9>(ps, cp, g, slots, waves, stream, ran);
       break;
     case 11:
-      if (g16) launch_run3_d<16, AXIS, 11>(ps, cp, g, slots, waves, stream);
-      else launch_run3_d<32, AXIS, 11>(ps, cp, g, slots, waves, stream);
+      if (g16) launch_run3_d<16, AXIS, 11>(ps, cp, g, slots, waves, stream, ran);
+      else launch_run3_d<32, AXIS, 11>(ps, cp, g, slots, waves, stream, ran);
       break;
-    default: launch_run3_d<32, AXIS, 0>(ps, cp, g, slots, waves, stream); break;
+    default: launch_run3_d<32, AXIS, 0>(ps, cp, g, slots, waves, stream, ran); break;
   }
 }
 inline void launch_sweep_run3(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, int waves,
-                              int group, hipStream_t stream) {
-  if (g.axis == 0) launch_run3_axis<0>(ps, cp, g, slots, waves, group, stream);
-  else launch_run3_axis<1>(ps, cp, g, slots, waves, group, stream);
+                              int group, hipStream_t stream, SweepVariant* ran = nullptr) {
+  if (g.axis == 0) launch_run3_axis<0>(ps, cp, g, slots, waves, group, stream, ran);
+  else launch_run3_axis<1>(ps, cp, g, slots, waves, group, stream, ran);
 }
 
 }  // namespace pm

@@ -28,4 +28,17 @@ struct SweepGeom {
   int s_first, s_last;  // first and last visited position along the chain (inclusive)
 };
 
+// What the host decided for one sweep launch: launch_sweep and the launch helpers of pm_run2.hpp / pm_run3.hpp write it
+// where a caller passes one (pm_debug_propagate, which copies it into the record of include/pm/testing.h); null
+// everywhere else.  Host-side only, no kernel sees it.
+struct SweepVariant {
+  int engine = 0;          // PM_ENGINE_*, after the serial fallback
+  int axis = 0, dir = 0;
+  int group = 0;           // lanes per chain segment; 0: the engine has no groups
+  int waves = 0;           // wavefronts per chain; 0: the engine has no chain segments
+  int window = 0;          // compiled-in window of k_runblk3; 0: the general kernel, and every other engine
+  int lref = 0;            // 1: reference lines staged in LDS
+  int chain_len = 0, chains = 0;
+};
+
 }  // namespace pm

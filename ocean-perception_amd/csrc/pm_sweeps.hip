@@ -94,7 +94,7 @@ int runblk_group(int semantics, int axis, float amp, int win, int dir = 1) {
 }  // namespace
 
 void launch_sweep(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, int engine, float amp,
-                  hipStream_t stream) {
+                  hipStream_t stream, SweepVariant* ran) {
   const int chains = g.c_hi - g.c_lo + 1;
   const int chain_len = (g.s_last - g.s_first) * g.dir + 1;
   if (engine == PM_ENGINE_AUTO) engine = PM_ENGINE_RUNBLK2;
@@ -102,6 +102,10 @@ void launch_sweep(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, 
   if (engine != PM_ENGINE_SERIAL && !(engine == PM_ENGINE_WAVE && cp.semantics == PM_SEM_CPU) &&
       chain_lds_bytes(chain_len, 4 * kMaxSegWaves + 4, cp.semantics == PM_SEM_CPU ? 4 : 5) > kChainLdsMax)
     engine = PM_ENGINE_SERIAL;
+  if (ran) {  // the run engines add group, waves, window and lref
+    *ran = SweepVariant();
+    ran->engine = engine, ran->axis = g.axis, ran->dir = g.dir, ran->chain_len = chain_len, ran->chains = chains;
+  }
   // PM_SEM_GPU has two parallel engines: lane-per-segment (WAVE) and the shared-tap run step (RUNBLK2)
   if (engine == PM_ENGINE_SERIAL) {
     hipLaunchKernelGGL(k_sweep_serial, dim3((unsigned)((chains + 63) / 64), 1, (unsigned)slots), dim3(64), 0, stream, ps,
@@ -111,12 +115,13 @@ void launch_sweep(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, 
   } else {
     const int group = runblk_group(cp.semantics, g.axis, amp, g.axis == 0 ? cp.pw : cp.ph, g.dir);
     if (cp.semantics == PM_SEM_CPU)
-      launch_sweep_run3(ps, cp, g, slots, runblk_waves(chain_len, chains * slots, g.axis, group), group, stream);
+      launch_sweep_run3(ps, cp, g, slots, runblk_waves(chain_len, chains * slots, g.axis, group), group, stream, ran);
     else {
       static const int gpu_w[2] = {[] { const char* e = pm::tune_env("PM_GPU_WAVES_FWD"); return e ? atoi(e) : 0; }(),
                                    [] { const char* e = pm::tune_env("PM_GPU_WAVES_BWD"); return e ? atoi(e) : 0; }()};
       const int wv = gpu_w[g.dir < 0 ? 1 : 0];
-      launch_sweep_run2(ps, cp, g, slots, wv ? wv : runblk_waves(chain_len, chains * slots, g.axis, group), group, stream);
+      launch_sweep_run2(ps, cp, g, slots, wv ? wv : runblk_waves(chain_len, chains * slots, g.axis, group), group, stream,
+                        ran);
     }
   }
 }

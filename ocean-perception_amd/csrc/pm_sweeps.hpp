@@ -9,7 +9,8 @@ namespace pm {
 
 // One directional sweep of every chain of `slots` slots, in place, on `stream`.  engine = pm_params.engine
 // (PM_ENGINE_*); amp = the noise amplitude of the iteration (tuning only: it selects the lanes per chain segment).
+// ran (may be null): receives the kernel variant that was launched.
 void launch_sweep(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, int engine, float amp,
-                  hipStream_t stream);
+                  hipStream_t stream, SweepVariant* ran = nullptr);
 
 }  // namespace pm

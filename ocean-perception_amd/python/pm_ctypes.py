@@ -43,7 +43,7 @@ EXPORTS = [
     "pm_fast_guided_filter", "pm_estimate_illuminant_range_guided", "pm_gather_pixels",
     "pm_rectify_u8", "pm_rectify_map", "pm_match_raw_device", "pm_stereo_rectify",
     "pm_rectify_bgr8", "pm_match_raw_bgr_device",
-    "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate",
+    "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
     "pm_remove_background", "pm_mask_occlusions", "pm_foreground_texture_mask", "pm_sparse_init", "pm_corner_subpix", "pm_profile_enable", "pm_profile_read",
     "pm_kernel_name", "pm_debug_counters", "pm_debug_counters_enable",
     "pm_tile_begin", "pm_tile_noise", "pm_tile_sweep", "pm_tile_snapshot", "pm_tile_restore", "pm_tile_get_row",
@@ -122,6 +122,11 @@ class PmTiledAuditRecord(C.Structure):  # include/pm/testing.h
     _fields_ = [("call", C.c_int), ("band", C.c_int), ("detail", C.c_int), ("current_device", C.c_int),
                 ("stream_device", C.c_int), ("object_device", C.c_int), ("source_device", C.c_int),
                 ("foreign_allowed", C.c_int), ("violation", C.c_int)]
+
+
+class PmDebugSweepVariant(C.Structure):  # include/pm/testing.h
+    _fields_ = [(name, C.c_int) for name in ("engine", "axis", "dir", "group", "waves", "window", "lref", "chain_len",
+                                             "chains")]
 
 
 class PmCamera(C.Structure):  # include/pm/imaging.h: the radial-tangential model
@@ -295,6 +300,9 @@ def load():
     lib.pm_add_noise.restype = C.c_int
     lib.pm_propagate.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_int, C.c_int]
     lib.pm_propagate.restype = C.c_int
+    lib.pm_debug_propagate.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                       C.POINTER(PmDebugSweepVariant)]
+    lib.pm_debug_propagate.restype = C.c_int
     lib.pm_remove_background.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_int, C.c_float]
     lib.pm_remove_background.restype = C.c_int
     lib.pm_mask_occlusions.argtypes = [vp, f32p, f32p, C.c_int, C.c_int]
@@ -783,6 +791,18 @@ class Engine:
         self._check(self.lib.pm_propagate(self.h, pl, pr, d.shape[0], d.shape[1], d.ctypes.data_as(C.c_void_p),
                                           patch_h, patch_w, pass_mask), "pm_propagate")
         return d
+
+    def debug_propagate(self, left, right, disp, patch_h, patch_w, pass_mask=15, amp=1e30):
+        """propagate() as an iteration with noise amplitude `amp` launches it -> (map, [variant of every pass of the
+        mask, in pass order]); a variant is a dict of the fields of pm_debug_sweep_variant (include/pm/testing.h)."""
+        left, pl = _u8(left)
+        right, pr = _u8(right)
+        d = np.array(disp, dtype=np.float32, order="C", copy=True)
+        ran = (PmDebugSweepVariant * 4)()
+        self._check(self.lib.pm_debug_propagate(self.h, pl, pr, d.shape[0], d.shape[1], d.ctypes.data_as(C.c_void_p),
+                                                patch_h, patch_w, pass_mask, amp, ran), "pm_debug_propagate")
+        return d, [{n: getattr(ran[k], n) for n, _ in PmDebugSweepVariant._fields_} for k in range(4)
+                   if pass_mask & (1 << k)]
 
     def remove_background(self, left, right, disp, patch_h, patch_w, factor):
         left, pl = _u8(left)

@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import sweep_fields
 from conftest import assert_same, small_pair
 
 pytestmark = pytest.mark.gpu
@@ -85,25 +86,9 @@ def test_gpu_propagate_each_sweep(pm, oracle, synth, engine):
 def test_gpu_propagate_adversarial_fields(pm, oracle, synth, engine, kind):
     """PM_SEM_GPU sweeps on disparity fields that exercise the clamp (x - d < 1), the single-position slow
     path, long runs of one value and binade crossings of the sample positions."""
-    rows, cols = 45, 333
-    l, r, _, _, _ = small_pair(synth, 21, rows, cols, n_points=20, dilate_factor=2)
+    l, r, d = sweep_fields.gpu_adversarial(synth, kind)
+    rows, cols = d.shape
     ims = oracle.ImageSet(l, r)
-    rng = np.random.default_rng(5)
-    if kind == "random":
-        d = rng.uniform(0.0, 90.0, (rows, cols)).astype(np.float32)
-    elif kind == "plateaus":
-        d = np.repeat(np.repeat(rng.uniform(0.0, 40.0, (rows // 5 + 1, cols // 9 + 1)), 5, 0), 9, 1)
-        d = d[:rows, :cols].astype(np.float32)
-        d[rng.random((rows, cols)) < 0.05] = 0.0
-    elif kind == "huge":  # mostly clamped candidates
-        d = rng.uniform(100.0, 600.0, (rows, cols)).astype(np.float32)
-        d[:, ::7] = 3.25
-    else:  # values around powers of two of x - d, and denormal-small disparities
-        xs = np.arange(cols, dtype=np.float32)[None, :].repeat(rows, 0)
-        pick = rng.choice(np.array([1, 2, 4, 8, 16, 32, 64, 128], np.float32), (rows, cols))
-        d = np.maximum(xs - pick + rng.choice(np.array([-1e-3, 0, 1e-3, 0.5], np.float32), (rows, cols)), 0)
-        d[rng.random((rows, cols)) < 0.1] = 1e-30
-        d = d.astype(np.float32)
     with mk(pm, 1, engine, rows=rows, cols=cols) as e:
         for mask in (1, 2, 4, 8, 15):
             assert_same(e.propagate(l, r, d, 3, 3, mask), oracle.gpu_propagate(ims, d, pass_mask=mask, nthreads=8),
@@ -116,19 +101,9 @@ def test_cpu_propagate_lerp_weight_extremes(pm, oracle, synth, engine, pw):
     """PM_SEM_CPU sweeps with sample positions within a few ulps of an integer column: the fixed-point lerp weights
     reach 0 and 65536 (the run engine packs them into 16 bits for v_dot2_u32_u16 and relies on the other weight
     being 0 then), on both sides of the integer, next to ordinary fractions and long runs."""
-    rows, cols = 40, 200
-    l, r, _, _, _ = small_pair(synth, 23, rows, cols, n_points=20, dilate_factor=2)
+    l, r, d = sweep_fields.weight_extremes(synth, pw)
+    rows, cols = d.shape
     ims = oracle.ImageSet(l, r)
-    rng = np.random.default_rng(17)
-    xs = np.arange(cols, dtype=np.float32)[None, :].repeat(rows, 0)
-    shift = np.float32((pw - 1) * 0.5)
-    # x - d - shift = k + eps  with  eps in {0, +-1 ulp ... +-2^-16, +-2^-17, +-2^-18}
-    k = rng.integers(0, 60, (rows, cols)).astype(np.float32)
-    eps = rng.choice(np.array([0.0, 2.0 ** -16, -2.0 ** -16, 2.0 ** -17, -2.0 ** -17, 2.0 ** -18, -2.0 ** -18, 7.6e-6,
-                               -7.6e-6, 7.7e-6, -7.7e-6, 0.25, 0.5], np.float32), (rows, cols))
-    d = np.maximum(xs - shift - k - eps, 0).astype(np.float32)
-    d = np.repeat(d[:, ::3], 3, axis=1)[:, :cols]        # runs of three equal values
-    d[rng.random((rows, cols)) < 0.3] = np.float32(13.99999)
     with mk(pm, 0, engine, rows=rows, cols=cols) as e:
         for mask in (1, 2, 4, 8, 15):
             assert_same(e.propagate(l, r, d, pw, pw, mask), oracle.cpu_propagate(ims, d, pw, pw, pass_mask=mask, nthreads=8),
@@ -145,27 +120,8 @@ def test_cpu_propagate_runs_through_every_segment(pm, oracle, engine, pw, layout
     the rule is a strict <).  The run engine hands such a run from segment to segment in its fix-up rounds, one round per
     segment, and since round 6 a re-run that is alone in its wavefront goes wide (run3_step<WIDE>: two or four groups on one
     run; windows of 5 take 16-lane groups, 11 takes 32 here); chains of 890 positions are 8 / 16 segments."""
-    rng = np.random.default_rng(23)
-    long_, short = 900, 22
-    rows, cols = (short, long_) if layout == "rows" else (long_, short + 30)
-    l = rng.integers(0, 256, (rows, cols)).astype(np.uint8)
-    if layout == "rows":
-        l[14:, 300:330] = 77          # no texture: the run stops here in the lower rows
-    else:
-        l[400:430, 30:] = 77
-    r = np.roll(l, -6, axis=1)        # left (x) = right (x - 6)
-    d = rng.uniform(8.0, 40.0, (rows, cols)).astype(np.float32)
-    h = pw // 2
-    if layout == "rows":
-        d[:8, h] = 6.0                # from the first position of the forward sweep
-        d[4:12, cols - 1 - h] = 6.0   # ... and of the backward sweep
-        for y in range(12, rows):
-            d[y, rng.integers(h, cols - h)] = 6.0
-    else:
-        d[h, 7:25] = 6.0
-        d[rows - 1 - h, 20:40] = 6.0
-        for x in range(40, cols):
-            d[rng.integers(h, rows - h), x] = 6.0
+    l, r, d = sweep_fields.one_value_runs(pw, layout)
+    rows, cols = d.shape
     ims = oracle.ImageSet(l, r)
     with mk(pm, 0, engine, rows=rows, cols=cols) as e:
         for mask in (1, 2, 4, 8, 15):
