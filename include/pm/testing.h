@@ -46,6 +46,13 @@ typedef struct pm_debug_sweep_variant {
 } pm_debug_sweep_variant;
 int pm_debug_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
                        int patch_h, int patch_w, int pass_mask, float amp, pm_debug_sweep_variant* ran);
+/* The record pm_debug_propagate's pass `pass` (0 = row +1, 1 = column +1, 2 = row -1, 3 = column -1) writes for images of
+ * rows x cols, from the host function that plans every sweep launch (csrc/pm_sweep_plan.hpp::plan_sweep) alone: no handle,
+ * no device.  params->semantics, params->engine and the window decide as in a launch (PM_SEM_GPU's window is 3 x 3
+ * whatever patch_h / patch_w say); slots = the slots of the launch (pm_debug_propagate: 1).  An empty interior gives an
+ * all-zero record.  PM_ERR_INVALID_ARG: a null pointer, a pass outside 0 .. 3, slots < 1, an amplitude that is not >= 0. */
+int pm_debug_sweep_plan(const pm_params* params, int rows, int cols, int patch_h, int patch_w, int pass, int slots,
+                        float amp, pm_debug_sweep_variant* out);
 
 /* ---- the row-tiled driver's device discipline, provable on ONE GPU ------------------------------------------------
  * pm_tiled_create with the bands accounted to LOGICAL devices: band k lives on logical_devices[k] (>= 0; several bands

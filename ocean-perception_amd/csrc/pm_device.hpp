@@ -84,6 +84,13 @@ __host__ __device__ __forceinline__ size_t chain_at(int axis, int chain, int s, 
   return axis == 0 ? state_at(s, chain, pitch) : state_at(chain, s, pitch);
 }
 
+// host side, before a launch: a kernel takes up to 64 KB of dynamic LDS by default and needs its limit raised beyond
+template <typename K>
+inline void allow_big_lds(K kernel, size_t bytes) {
+  if (bytes > 64 * 1024)
+    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
 // The planes one view works on.  View 1 is "the same algorithm on the horizontally mirrored
 // (R, L) pair" (src/vehicle/patchmatch_gpu/patchmatch_gpu.cu:357-368): the mirrored copies are
 // written once by the prep kernel, so no flip pass exists.

@@ -25,7 +25,7 @@
 #include "pm_hipres.hpp"
 #include "pm_hostcopy.hpp"
 #include "pm_seed_api.hpp"
-#include "pm_sweep_defs.hpp"
+#include "pm_sweep_plan.hpp"
 #include "pm_tune.hpp"
 
 namespace pm {
@@ -338,7 +338,7 @@ void launch_noise_cost(pm_handle* h, const PlaneSet& ps, const CostParams& cp, c
 void launch_noise_only(pm_handle* h, const PlaneSet& ps, const CostParams& cp, float amount, hipStream_t stream);
 void launch_background(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const Interior& in, float factor,
                        int cached, int slots, hipStream_t stream);
-// amp: the iteration's noise amplitude (1e30f: none); ran (may be null): the variant launched (pm_sweep_defs.hpp), left
+// amp: the iteration's noise amplitude (1e30f: none); ran (may be null): the variant launched (pm_sweep_plan.hpp), left
 // as it is where the geometry has nothing to sweep
 int run_sweep(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, float amp,
               hipStream_t stream, SweepVariant* ran = nullptr);

@@ -811,6 +811,12 @@ int pm_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, int ro
   return propagate_impl(h, "pm_propagate", left, right, rows, cols, disp, patch_h, patch_w, pass_mask, 1e30f, nullptr);
 }
 
+namespace {
+pm_debug_sweep_variant debug_record(const pm::SweepVariant& v) {
+  return pm_debug_sweep_variant{v.engine, v.axis, v.dir, v.group, v.waves, v.window, v.lref, v.chain_len, v.chains};
+}
+}  // namespace
+
 // pm_propagate with the iteration's noise amplitude and a record of what was launched (include/pm/testing.h)
 int pm_debug_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
                        int patch_h, int patch_w, int pass_mask, float amp, pm_debug_sweep_variant* ran) {
@@ -824,10 +830,21 @@ int pm_debug_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, 
   const int rc = propagate_impl(h, "pm_debug_propagate", left, right, rows, cols, disp, patch_h, patch_w, pass_mask, amp,
                                 ran ? v : nullptr);
   if (ran)
-    for (int k = 0; k < 4; ++k)
-      ran[k] = pm_debug_sweep_variant{v[k].engine, v[k].axis, v[k].dir,       v[k].group, v[k].waves,
-                                      v[k].window, v[k].lref, v[k].chain_len, v[k].chains};
+    for (int k = 0; k < 4; ++k) ran[k] = debug_record(v[k]);
   return rc;
+}
+
+// what pm_debug_propagate's pass would launch, from the plan alone: no handle, no device
+int pm_debug_sweep_plan(const pm_params* params, int rows, int cols, int patch_h, int patch_w, int pass, int slots,
+                        float amp, pm_debug_sweep_variant* out) {
+  if (!params || !out || pass < 0 || pass > 3 || slots < 1 || !(amp >= 0.f)) return PM_ERR_INVALID_ARG;
+  const CostParams cp = cost_params(*params, patch_w, patch_h);
+  const SweepGeom g = sweep_geom(*params, interior(*params, rows, cols, cp.pw, cp.ph), pass);
+  pm::SweepVariant v;
+  if (g.c_hi - g.c_lo + 1 > 0 && (g.s_last - g.s_first) * g.dir >= 0)  // (run_sweep's test: something to sweep)
+    v = pm::plan_sweep(cp.semantics, cp.pw, cp.ph, rows, cols, g, slots, params->engine, amp);
+  *out = debug_record(v);
+  return PM_OK;
 }
 
 int pm_remove_background(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,

@@ -37,12 +37,10 @@
 // rounds suffice.
 #pragma once
 
+#include "pm_device.hpp"
 #include "pm_sweep_defs.hpp"
 
 namespace pm {
-
-constexpr int kMaxSegWaves = 16;
-constexpr int kLref4Stride = 7;  // dwords per image row of the column sweeps' staged reference bytes (odd; 6 measures the same)
 
 // Workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share an XCD and its 4 MiB L2).
 // Adjacent chains read almost the same image rows, so chain k of the sweep goes to the block whose
@@ -266,37 +264,6 @@ __global__ void __launch_bounds__(64 * kMaxSegWaves) k_runblk2(PlaneSet ps, Cost
              AXIS, g.dir, chain, (int)blockIdx.z, ph[0], ph[1], ph[2], ph[3], n_steps, n_fix, n_rounds);
   }
 #endif
-}
-
-template <int GS, int AXIS>
-inline void launch_run2_k(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, int waves,
-                          hipStream_t stream, SweepVariant* ran) {
-  const int chains = g.c_hi - g.c_lo + 1;
-  const int n = (g.s_last - g.s_first) * g.dir + 1;
-  const int nwv = waves < 1 ? 1 : (waves > kMaxSegWaves ? kMaxSegWaves : waves);
-  const int per_block = (kWave / GS) * nwv;
-  int len = (n + per_block - 1) / per_block;
-  if (len < 8) len = 8;
-  if (ran) ran->group = GS, ran->waves = nwv;
-  const int n1 = (n + 1 + 3) & ~3;
-  const size_t lds_bytes = sizeof(float) * (5 * (size_t)n1 + per_block + 1 + 2);
-  allow_big_lds(k_runblk2<GS, AXIS>, lds_bytes);
-  hipLaunchKernelGGL((k_runblk2<GS, AXIS>), dim3((unsigned)chains, 1, (unsigned)slots), dim3(kWave * nwv), lds_bytes,
-                     stream, ps, cp, g, len);
-}
-
-// PM_SEM_GPU, in place.  group = lanes per chain segment: 32, 16 or 8 (its window is 3 lanes).
-inline void launch_sweep_run2(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, int waves,
-                              int group, hipStream_t stream, SweepVariant* ran = nullptr) {
-  if (g.axis == 0) {
-    if (group <= 8) launch_run2_k<8, 0>(ps, cp, g, slots, waves, stream, ran);
-    else if (group <= 16) launch_run2_k<16, 0>(ps, cp, g, slots, waves, stream, ran);
-    else launch_run2_k<32, 0>(ps, cp, g, slots, waves, stream, ran);
-  } else {
-    if (group <= 8) launch_run2_k<8, 1>(ps, cp, g, slots, waves, stream, ran);
-    else if (group <= 16) launch_run2_k<16, 1>(ps, cp, g, slots, waves, stream, ran);
-    else launch_run2_k<32, 1>(ps, cp, g, slots, waves, stream, ran);
-  }
 }
 
 }  // namespace pm

@@ -31,7 +31,6 @@
 #include <vector>
 
 #include "pm_run2.hpp"
-#include "pm_tune.hpp"
 
 namespace pm {
 
@@ -101,27 +100,6 @@ __device__ __forceinline__ float cost_from_packed_sums(int wsum, const CostParam
   const f32x2 wgt = {cp.alpha, cp.one_minus_alpha};
   const f32x2 t = wgt * e;
   return t.x + t.y;
-}
-
-// LDS bytes of the column sweeps' staged reference lines (LREF): kLref4Stride dwords per image row.
-template <int AXIS>
-inline size_t run3_lref_bytes(const PlaneSet& ps) {
-  return sizeof(unsigned) * (size_t)kLref4Stride * (AXIS == 1 ? ps.rows : ps.cols);
-}
-// PM_RUN2_LREF: bit 0 = row sweeps, bit 1 = column sweeps (default 2); PM_RUN2_LREF_KB: LDS budget per workgroup (A/B knobs)
-inline bool run3_lref_enabled(int axis) {
-  static const int v = [] {
-    const char* e = pm::tune_env("PM_RUN2_LREF");
-    return e ? atoi(e) : 2;
-  }();
-  return (v >> axis) & 1;
-}
-inline size_t run3_lref_limit() {
-  static const size_t v = [] {
-    const char* e = pm::tune_env("PM_RUN2_LREF_KB");
-    return (size_t)(e ? atoi(e) : 40) * 1024;
-  }();
-  return v;
 }
 
 // The LDS word that carries a group's candidate from the rejecting lane to the others: volatile keeps the accesses in
@@ -522,7 +500,7 @@ __device__ __forceinline__ void run3_step(const View& v, const PlaneSet& ps, con
 }
 
 // One workgroup per chain; a wavefront carries 64 / GS segments.  grid = (chains, 1, slots), block = 64 * nw,
-// dynamic LDS = run3_lds_bytes().
+// dynamic LDS = run3_lds_bytes() (pm_sweep_plan.hpp).
 template <int GS, int AXIS, int TP, int DIR, bool LREF>
 __global__ void __launch_bounds__(64 * kMaxSegWaves) k_runblk3(PlaneSet ps, CostParams cp, SweepGeom g, int seg_len
 #ifdef PM_RUN3_STATS
@@ -846,14 +824,6 @@ __global__ void __launch_bounds__(64 * kMaxSegWaves) k_runblk3(PlaneSet ps, Cost
   }
 }
 
-
-inline int run3_dbg() {
-  static const int v = [] {
-    const char* e = pm::tune_env("PM_RUN3_DBG");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
 #ifdef PM_RUN3_STATS
 // ---- per-chain log of the stats build (make tuning TUNE_DEFS=-DPM_RUN3_STATS; tools/chain_tail.py) -----------------------
 // Every k_runblk3 launch gets a slot of [workgroups][8] words in one device buffer and a host record of what it was;
@@ -883,84 +853,5 @@ inline unsigned* run3_stats_slot(hipStream_t stream, int axis, int dir, int gs, 
   return s.d_log + 8 * (size_t)Run3Stats::kMaxChains * (s.recs.size() - 1);
 }
 #endif
-inline size_t run3_lds_bytes(int n, int nseg) { return sizeof(float) * (4 * (size_t)(n + 1) + 2 * (size_t)nseg + 3); }
-
-template <int GS, int AXIS, int TP, int DIR, bool LREF>
-inline void launch_run3_l(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, int waves,
-                          hipStream_t stream, SweepVariant* ran) {
-  const int chains = g.c_hi - g.c_lo + 1;
-  const int n = (g.s_last - g.s_first) * g.dir + 1;
-  const int nwv = waves < 1 ? 1 : (waves > kMaxSegWaves ? kMaxSegWaves : waves);
-  const int nseg = (kWave / GS) * nwv;
-  int len = (n + nseg - 1) / nseg;
-  if (len < 8) len = 8;
-  if (ran) ran->group = GS, ran->waves = nwv, ran->window = TP, ran->lref = LREF ? 1 : 0;
-  size_t lds_bytes = run3_lds_bytes(n, nseg);
-  if (LREF) lds_bytes += run3_lref_bytes<AXIS>(ps);
-  {  // tuning build: PM_RUN3_LDS_EXTRA_KB pads the allocation (how sensitive is the step to workgroups per CU?)
-    static const int extra = [] {
-      const char* e = pm::tune_env("PM_RUN3_LDS_EXTRA_KB");
-      return e ? atoi(e) : 0;
-    }();
-    lds_bytes += (size_t)extra * 1024;
-  }
-  allow_big_lds(k_runblk3<GS, AXIS, TP, DIR, LREF>, lds_bytes);
-#ifdef PM_RUN3_STATS
-  hipLaunchKernelGGL((k_runblk3<GS, AXIS, TP, DIR, LREF>), dim3((unsigned)chains, 1, (unsigned)slots),
-                     dim3(kWave * nwv), lds_bytes, stream, ps, cp, g, len | (run3_dbg() << 24),
-                     run3_stats_slot(stream, AXIS, DIR, GS, n, chains, nwv));
-#else
-  hipLaunchKernelGGL((k_runblk3<GS, AXIS, TP, DIR, LREF>), dim3((unsigned)chains, 1, (unsigned)slots),
-                     dim3(kWave * nwv), lds_bytes, stream, ps, cp, g, len | (run3_dbg() << 24));
-#endif
-}
-template <int GS, int AXIS, int TP>
-inline void launch_run3_d(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, int waves,
-                          hipStream_t stream, SweepVariant* ran) {
-  // column sweeps of the benchmark window stage their reference lines in LDS while that leaves room for at least
-  // four workgroups per CU (PM_RUN2_LREF / PM_RUN2_LREF_KB: A/B knobs)
-  if constexpr (TP == 11) {
-    const int n = (g.s_last - g.s_first) * g.dir + 1;
-    const size_t total = run3_lds_bytes(n, 64) + run3_lref_bytes<AXIS>(ps);
-    if (run3_lref_enabled(AXIS) && total <= run3_lref_limit()) {
-      if (g.dir > 0) launch_run3_l<GS, AXIS, TP, 1, true>(ps, cp, g, slots, waves, stream, ran);
-      else launch_run3_l<GS, AXIS, TP, -1, true>(ps, cp, g, slots, waves, stream, ran);
-      return;
-    }
-  }
-  if (g.dir > 0) launch_run3_l<GS, AXIS, TP, 1, false>(ps, cp, g, slots, waves, stream, ran);
-  else launch_run3_l<GS, AXIS, TP, -1, false>(ps, cp, g, slots, waves, stream, ran);
-}
-
-// group = lanes per chain segment (32 or 16); windows of 3 and 5 always take 16, windows the fixed-size kernels do
-// not cover (not square, or wider than 11) take the general kernel with 32.
-template <int AXIS>
-inline void launch_run3_axis(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, int waves,
-                             int group, hipStream_t stream, SweepVariant* ran) {
-  const int sq = (cp.pw == cp.ph && cp.pw <= 11) ? cp.pw : 0;
-  const bool g16 = group <= 16;
-  switch (sq) {
-    case 3: launch_run3_d<16, AXIS, 3>(ps, cp, g, slots, waves, stream, ran); break;
-    case 5: launch_run3_d<16, AXIS, 5>(ps, cp, g, slots, waves, stream, ran); break;
-    case 7:
-      if (g16) launch_run3_d<16, AXIS, 7>(ps, cp, g, slots, waves, stream, ran);
-      else launch_run3_d<32, AXIS, 7>(ps, cp, g, slots, waves, stream, ran);
-      break;
-    case 9:
-      if (g16) launch_run3_d<16, AXIS, 9>(ps, cp, g, slots, waves, stream, ran);
-      else launch_run3_d<32, AXIS, 9>(ps, cp, g, slots, waves, stream, ran);
-      break;
-    case 11:
-      if (g16) launch_run3_d<16, AXIS, 11>(ps, cp, g, slots, waves, stream, ran);
-      else launch_run3_d<32, AXIS, 11>(ps, cp, g, slots, waves, stream, ran);
-      break;
-    default: launch_run3_d<32, AXIS, 0>(ps, cp, g, slots, waves, stream, ran); break;
-  }
-}
-inline void launch_sweep_run3(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, int waves,
-                              int group, hipStream_t stream, SweepVariant* ran = nullptr) {
-  if (g.axis == 0) launch_run3_axis<0>(ps, cp, g, slots, waves, group, stream, ran);
-  else launch_run3_axis<1>(ps, cp, g, slots, waves, group, stream, ran);
-}
 
 }  // namespace pm

@@ -1,6 +1,7 @@
 // pm_serial.hpp -- PM_ENGINE_SERIAL: the sweep whose equivalence with the reference loops is evident (pm_sweeps.hip only).
 #pragma once
 
+#include "pm_device.hpp"
 #include "pm_sweep_defs.hpp"
 
 namespace pm {

@@ -3,14 +3,15 @@
 // time is their template instantiations.
 #pragma once
 
-#include "pm_sweep_defs.hpp"
+#include "pm_device.hpp"
+#include "pm_sweep_plan.hpp"
 
 namespace pm {
 
-// One directional sweep of every chain of `slots` slots, in place, on `stream`.  engine = pm_params.engine
-// (PM_ENGINE_*); amp = the noise amplitude of the iteration (tuning only: it selects the lanes per chain segment).
-// ran (may be null): receives the kernel variant that was launched.
-void launch_sweep(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, int engine, float amp,
-                  hipStream_t stream, SweepVariant* ran = nullptr);
+// One directional sweep of every chain of `slots` slots, in place, on `stream`: plan_sweep (pm_sweep_plan.hpp) picks the
+// kernel variant, which is launched and returned.  engine = pm_params.engine (PM_ENGINE_*); amp = the noise amplitude
+// of the iteration (tuning only: it selects the lanes per chain segment).
+SweepVariant launch_sweep(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, int engine, float amp,
+                          hipStream_t stream);
 
 }  // namespace pm

@@ -14,6 +14,7 @@
 // changed ones written back with one store per 64 steps.
 #pragma once
 
+#include "pm_device.hpp"
 #include "pm_sweep_defs.hpp"
 
 namespace pm {
@@ -245,16 +246,15 @@ __global__ void __launch_bounds__(64) k_sweep_gpu_lanes(PlaneSet ps, CostParams 
   }
 }
 
-inline void launch_sweep_wave(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots,
+// lds_bytes: the plan's (pm_sweep_plan.hpp::wave_gpu_lds_bytes; none for PM_SEM_CPU)
+inline void launch_sweep_wave(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, size_t lds_bytes,
                               hipStream_t stream) {
   const int chains = g.c_hi - g.c_lo + 1;
   if (cp.semantics != 0) {
     // PM_SEM_GPU: the 5-tap cost is too small to spread over a wavefront; lanes take chain segments.
-    const int n = (g.s_last - g.s_first) * g.dir + 1;
-    const int n1 = (n + 1 + 3) & ~3;
-    allow_big_lds(k_sweep_gpu_lanes, sizeof(float) * (4 * (size_t)n1 + kWave + 1));
-    hipLaunchKernelGGL(k_sweep_gpu_lanes, dim3((unsigned)chains, 1, (unsigned)slots), dim3(kWave),
-                       sizeof(float) * (4 * (size_t)n1 + kWave + 1), stream, ps, cp, g);
+    allow_big_lds(k_sweep_gpu_lanes, lds_bytes);
+    hipLaunchKernelGGL(k_sweep_gpu_lanes, dim3((unsigned)chains, 1, (unsigned)slots), dim3(kWave), lds_bytes, stream, ps,
+                       cp, g);
     return;
   }
   const dim3 grid((unsigned)chains, 1, (unsigned)slots), block(kWave);

@@ -44,6 +44,7 @@ EXPORTS = [
     "pm_rectify_u8", "pm_rectify_map", "pm_match_raw_device", "pm_stereo_rectify",
     "pm_rectify_bgr8", "pm_match_raw_bgr_device",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
+    "pm_debug_sweep_plan",
     "pm_remove_background", "pm_mask_occlusions", "pm_foreground_texture_mask", "pm_sparse_init", "pm_corner_subpix", "pm_profile_enable", "pm_profile_read",
     "pm_kernel_name", "pm_debug_counters", "pm_debug_counters_enable",
     "pm_tile_begin", "pm_tile_noise", "pm_tile_sweep", "pm_tile_snapshot", "pm_tile_restore", "pm_tile_get_row",
@@ -303,6 +304,9 @@ def load():
     lib.pm_debug_propagate.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_float,
                                        C.POINTER(PmDebugSweepVariant)]
     lib.pm_debug_propagate.restype = C.c_int
+    lib.pm_debug_sweep_plan.argtypes = [C.POINTER(PmParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_float, C.POINTER(PmDebugSweepVariant)]
+    lib.pm_debug_sweep_plan.restype = C.c_int
     lib.pm_remove_background.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_int, C.c_float]
     lib.pm_remove_background.restype = C.c_int
     lib.pm_mask_occlusions.argtypes = [vp, f32p, f32p, C.c_int, C.c_int]
@@ -415,6 +419,16 @@ def default_params(semantics=PM_SEM_CPU, **kw):
                 raise AttributeError(k)
             setattr(p, k, v)
     return p
+
+
+def sweep_plan(params, rows, cols, patch_h, patch_w, pass_index, slots=1, amp=1e30):
+    """pm_debug_sweep_plan: the variant Engine.debug_propagate() reports for that pass, from the host-side plan alone (no
+    handle, no device) -> a dict of the fields of pm_debug_sweep_variant."""
+    out = PmDebugSweepVariant()
+    rc = load().pm_debug_sweep_plan(C.byref(params), rows, cols, patch_h, patch_w, pass_index, slots, amp, C.byref(out))
+    if rc != PM_OK:
+        raise PmError(rc, "pm_debug_sweep_plan")
+    return {n: getattr(out, n) for n, _ in PmDebugSweepVariant._fields_}
 
 
 def _u8(a):

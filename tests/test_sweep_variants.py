@@ -1,12 +1,14 @@
 """Every kernel variant of the directional sweeps, one sweep at a time, on crafted fields, against the oracle.
 
-launch_sweep (csrc/pm_sweeps.hip) and the launch helpers of csrc/pm_run3.hpp / pm_run2.hpp pick one of several dozen
-instantiations of k_runblk3 / k_runblk2 per launch -- by the window, the iteration's noise amplitude, the chain length,
-the chain count and the image height -- and pm_propagate, with its fixed "no noise" amplitude and its small images, meets
-about one in six of them.  pm_debug_propagate (include/pm/testing.h) takes the amplitude as an argument and reports the
-variant every pass ran.  Each case below
+plan_sweep (csrc/pm_sweep_plan.hpp) picks one of several dozen instantiations of k_runblk3 / k_runblk2 per launch -- by
+the window, the iteration's noise amplitude, the chain length, the chain count and the image height -- and launch_sweep
+(csrc/pm_sweeps.hip) launches it; pm_propagate, with its fixed "no noise" amplitude and its small images, meets about one
+in six of them.  pm_debug_propagate (include/pm/testing.h) takes the amplitude as an argument and reports the variant
+every pass ran.  Each case below
 
-  * compares the map after the sweep(s) with oracle.cpu_propagate / oracle.gpu_propagate at tolerance 0, and
+  * compares the map after the sweep(s) with oracle.cpu_propagate / oracle.gpu_propagate at tolerance 0,
+  * asserts that the record of what ran equals what pm_debug_sweep_plan plans for the same parameters, shape, pass and
+    amplitude without a device (tests/test_sweep_plan.py pins that plan on the CPU), and
   * asserts the variant record it was written for: a case that means to cover 16-lane groups, two wavefronts per chain or
     staged reference lines FAILS when a retuned threshold makes it cover something else.  The remedy is then another
     amplitude or shape in the case, never a weaker comparison.
@@ -14,8 +16,8 @@ variant every pass ran.  Each case below
 The fields are those of the stage tests of tests/test_gpu_parity.py (tests/sweep_fields.py): lerp weights of 0 and 65536,
 one value that runs through every chain segment, and PM_SEM_GPU's clamp / plateau / binade fields.  The last test asserts
 that the cases together have shown every variant; a case that has not run yet (a -k selection) is run by it.
-Wavefronts per chain are asserted on EVERY run-engine record, against runblk_waves() restated here and, on the axis a case
-is about, against the count the case was written for.
+Wavefronts per chain are asserted on EVERY run-engine record, against plan_sweep's rule restated here (runblk_waves) and,
+on the axis a case is about, against the count the case was written for.
 """
 import functools
 
@@ -31,18 +33,18 @@ SEM_CPU, SEM_GPU = 0, 1
 ENGINE_SERIAL, ENGINE_RUN = 1, 5        # PM_ENGINE_SERIAL, PM_ENGINE_RUNBLK2 (include/pm/patchmatch.h)
 ALL_MASKS = (1, 2, 4, 8, 15)            # bit k: 0 = row +1, 1 = column +1, 2 = row -1, 3 = column -1
 AXIS_MASKS = {0: (1, 4, 5), 1: (2, 8, 10)}
-# Noise amplitudes: runblk_group() takes 16-lane groups for windows 7 / 9 / 11 where the amplitude is at most a threshold per
+# Noise amplitudes: plan_sweep takes 16-lane groups for windows 7 / 9 / 11 where the amplitude is at most a threshold per
 # axis and direction (the smallest is the forward row sweeps'); 0.25 lies under all four, 1e30 -- pm_propagate's -- above.
 AMP_G16, AMP_G32 = 0.25, 1e30
 
 # ---- the host-side formulas the shapes below are derived from, restated (the records confirm them) --------------------
-K_WAVE, K_MAX_SEG_WAVES = 64, 16                   # csrc/pm_sweep_defs.hpp, pm_run2.hpp
+K_WAVE, K_MAX_SEG_WAVES = 64, 16                   # csrc/pm_sweep_defs.hpp
 K_CHAIN_LDS_MAX = 160 * 1024 - 1024                # csrc/pm_sweep_defs.hpp
-K_LREF4_STRIDE, LREF_LIMIT = 7, 40 * 1024          # csrc/pm_run2.hpp, pm_run3.hpp::run3_lref_limit
+K_LREF4_STRIDE, LREF_LIMIT = 7, 40 * 1024          # csrc/pm_sweep_defs.hpp, pm_sweep_plan.hpp::SweepKnobs::lref_limit
 
 
 def chain_lds_bytes(n, planes):
-    """chain_lds_bytes(n, 4 * kMaxSegWaves + 4, planes) of launch_sweep: beyond K_CHAIN_LDS_MAX the serial engine runs."""
+    """chain_lds_bytes(n, 4 * kMaxSegWaves + 4, planes) of plan_sweep: beyond K_CHAIN_LDS_MAX the serial engine runs."""
     return 4 * (planes * ((n + 1 + 3) & ~3) + 4 * K_MAX_SEG_WAVES + 4)
 
 
@@ -55,7 +57,7 @@ def longest_chain_in_lds(sem):
 
 
 def lref_stages(rows, ph=11):
-    """launch_run3_d<GS, 1, 11>: column sweeps stage their reference lines while the chain state (sized for 64
+    """plan_sweep, window 11: column sweeps stage their reference lines while the chain state (sized for 64
     segments) and kLref4Stride dwords per image row fit the budget."""
     n = rows - (ph - 1)
     return 4 * (4 * (n + 1) + 2 * 64 + 3) + 4 * K_LREF4_STRIDE * rows <= LREF_LIMIT
@@ -69,7 +71,7 @@ def tallest_staged_image():
 
 
 def runblk_waves(chain_len, chains):
-    """runblk_waves() of csrc/pm_sweeps.hip for one slot: wavefronts per chain"""
+    """plan_sweep's rule for one slot: wavefronts per chain"""
     return 8 if chain_len > 1600 else 2 if (chain_len < 400 and chains >= 2048) else 4
 
 
@@ -123,6 +125,8 @@ def run_sweeps(pm, oracle, synth, sem, ph, pw, key, amps, masks, expect, after_p
                 for k, rec in zip(passes, recs):
                     assert (rec["axis"], rec["dir"]) == (k & 1, 1 if k < 2 else -1), (what, rec)
                     assert (rec["chain_len"], rec["chains"]) == chain_geometry(sem, rows, cols, ph, pw, k & 1), (what, rec)
+                    # what ran is what was planned
+                    assert rec == pm.sweep_plan(prm, rows, cols, ph, pw, k, 1, amp), (what, rec)
                     expect(rec, amp, what)
                     SEEN.add((sem, rec["engine"], rec["axis"], rec["group"], rec["waves"], rec["window"], rec["lref"]))
                 out[mask, amp] = recs
@@ -149,7 +153,7 @@ def case_id(case):
 
 
 def fixed_window(ph, pw):
-    return pw if (ph == pw and pw <= 11) else 0       # launch_run3_axis: the compiled-in windows
+    return pw if (ph == pw and pw <= 11) else 0       # plan_sweep: the compiled-in windows
 
 
 def expect_waves(rec, waves, what):

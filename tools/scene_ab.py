@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Does the sweep engine's tuning hold on imagery it was not tuned on?
 
-The group-width rule of pm_sweeps.hip (16- or 32-lane chain segments by noise amplitude and sweep direction) and the
+The group-width rule of pm_sweep_plan.hpp (16- or 32-lane chain segments by noise amplitude and sweep direction) and the
 wavefronts-per-chain choice were measured on bench.py's synthetic pairs.  This tool times Match() (scalar mode,
 BASELINE configs[1] parameters, inputs resident, HIP events on the engine's stream) on a set of different scenes; the
 knobs are read once per process from the environment, so tools/scene_ab.sh runs it once per setting:
