@@ -219,6 +219,68 @@ int pm_match_raw_bgr_device(pm_handle* h, int n, const pm_rectify_view* left, co
 int pm_stereo_rectify(const pm_camera* c1, const pm_camera* c2, const double R[9], const double T[3],
                       pm_rectify_view* v1, pm_rectify_view* v2, double* baseline);
 
+/* ---- from a disparity map to what a mapping or meshing consumer takes: points, normals, a compacted cloud ------------
+ * The reference's consumers of disparity all do LeftCamera().Backproject(pixel, DispToDepth(disp))
+ * (src/vehicle/mesher/object_mesher.cpp:146-150, src/vehicle/vio/stereo_frontend.cpp:119,
+ * src/vehicle/vision_core/pinhole_camera.cpp:41-45) pixel by pixel on the host; these stages do it for a whole map that
+ * stays on the device.  Like the guided filter and the rectification they are held to their CPU definition
+ * (tests/pointcloud_ref.py) BIT FOR BIT; every operation is one rounding, parentheses as written:
+ *   point   fxB = fx * baseline, formed once on the host in binary64; per pixel (x, y) with disparity d, in binary64:
+ *             Zd = fxB / (double)d     Xd = (((double)x - cx) * Zd) / fx     Yd = (((double)y - cy) * Zd) / fy
+ *           P = ((float)Xd, (float)Yd, (float)Zd): its Z is pm_disp_to_range's value bit for bit.
+ *   normal  from the plane (a, b, z) PM_MODE_PLANES keeps per pixel, converted exactly to binary64 (f16 state included):
+ *             nx = a * fx     ny = b * fy     nz = z - ((a * ((double)x - cx)) + (b * ((double)y - cy)))
+ *           -- the 3-D plane through the pixel: n . P = fx * baseline > 0, so -n faces the camera -- each rounded to
+ *           binary32, then in binary32  s = ((nx*nx) + (ny*ny)) + (nz*nz),  l = sqrtf(s),
+ *           out = (-(nx / l), -(ny / l), -(nz / l)); (0, 0, 0) if l is not finite or not > 0.
+ * All pointers are device memory, images tightly packed; every call enqueues on the handle's stream and returns a status. */
+typedef struct pm_cloud_camera { double fx, fy, cx, cy, baseline; } pm_cloud_camera;
+/* the rectified pinhole: pm_rectify_view's fx_new .. cy_new and pm_stereo_rectify's *baseline */
+
+typedef struct pm_cloud_filter {
+  float min_disp;   /* a pixel counts iff disp > 0 and disp >= min_disp (NaN never counts)      */
+  float max_range;  /* > 0: and iff Z <= max_range (binary32, against the point's Z); 0 = no limit */
+  int   stride;     /* >= 1: only pixels with x % stride == 0 and y % stride == 0 are considered */
+} pm_cloud_filter;
+
+/* PM_ERR_INVALID_ARG, with pm_last_error naming the argument and nothing enqueued, for all three: a null camera, a
+ * non-finite camera entry, fx or fy == 0, a null required pointer, rows or cols < 1.  PM_ERR_SIZE: more than 2^31 - 1
+ * pixels (d_index_out is 32 bits wide). */
+
+/* organised: d_xyz is [rows][cols][3] floats, (0, 0, 0) where disp is not > 0 (0, negative, NaN).  One pass, 4 bytes in
+ * and 12 out per pixel. */
+int pm_backproject(pm_handle* h, const pm_cloud_camera* camera, const float* d_disp, int rows, int cols, float* d_xyz);
+
+/* organised unit normals ([rows][cols][3] floats) of the LEFT view of pair `pair`, facing the camera, read from the
+ * handle's RESIDENT plane state: the state of the LAST match on this handle (pm_match_device and every entry point built
+ * on it, or pm_planes_begin / _step / _write).  The next match overwrites it, so call this before matching again; work
+ * already enqueued on the handle's stream is ordered in front of it.  (0, 0, 0) where the state's z is not > 0 and, if
+ * d_disp_l is given, where d_disp_l is not > 0 -- pass the left map of that match to apply the cross-check's mask.
+ * PM_ERR_STATE: the handle is not in PM_MODE_PLANES, or holds no state for `pair` at rows x cols; the call is valid
+ * exactly when pm_planes_read is.  The scalar mode keeps no slopes and gets no normals. */
+int pm_planes_normals(pm_handle* h, int pair, const pm_cloud_camera* camera, const float* d_disp_l /* may be NULL */,
+                      int rows, int cols, float* d_normals);
+
+/* the compacted cloud in ROW-MAJOR ORDER: the k-th counted pixel goes to slot k of every output that is given.  Points are
+ * pm_backproject's, normals are copied from the organised d_normals, colour bytes from d_bgr8 (e.g. the d_left_rect_bgr8
+ * of pm_match_raw_bgr_device: the colour image in the geometry of the map), d_index_out receives y * cols + x.
+ * An output requires its input: d_normals_out without d_normals, or d_bgr8_out without d_bgr8, is PM_ERR_INVALID_ARG,
+ * as are stride < 1, capacity < 0, a NaN min_disp and a max_range that is not >= 0.
+ * *count (host) and *d_count (device) receive the number of counted pixels EVEN WHEN IT EXCEEDS capacity; then exactly
+ * the first `capacity` points in row-major order are written and nothing behind them: count > capacity tells the caller
+ * that the cloud was truncated.  capacity == 0 is legal and only counts (the outputs may then be NULL).  A non-NULL
+ * `count` synchronises the stream like pm_find_dark; with count == NULL the call only enqueues.
+ * Three small launches (per-block counts by wavefront ballot, one block of exclusive offsets, scatter); the order comes
+ * from that arithmetic, never from atomics, so the result is reproducible bit for bit.  Scratch for the block offsets
+ * (4 bytes per 256 considered pixels) is allocated on first use, reused, and released with the handle; growing it
+ * synchronises the stream, so a size must have run once before it is captured. */
+int pm_point_cloud(pm_handle* h, const pm_cloud_camera* camera, const pm_cloud_filter* filter, const float* d_disp,
+                   const float* d_normals /* organised, may be NULL */,
+                   const uint8_t* d_bgr8 /* [rows][cols][3], may be NULL */, int rows, int cols, int capacity,
+                   float* d_xyz_out /* [capacity][3], may be NULL */, float* d_normals_out /* [capacity][3], may be NULL */,
+                   uint8_t* d_bgr8_out /* [capacity][3], may be NULL */, int32_t* d_index_out /* [capacity], may be NULL */,
+                   int* d_count /* device, may be NULL */, int* count /* host, may be NULL */);
+
 /* ---- device buffers for host code that does not include HIP (host/imaging.hpp uses them) ------------------
  * pm_device_malloc / pm_device_free wrap hipMalloc / hipFree on the handle's device; pm_upload / pm_download are
  * stream-ordered copies on the handle's stream from / to pageable host memory (pm_download returns after the

@@ -54,6 +54,12 @@ int pm_debug_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, 
 int pm_debug_sweep_plan(const pm_params* params, int rows, int cols, int patch_h, int patch_w, int pass, int slots,
                         float amp, pm_debug_sweep_variant* out);
 
+/* ---- pm_point_cloud's launch constants (csrc/pm_cloud.hpp) ------------------------------------------------------------
+ * items_per_block: the considered pixels one block of the count / scatter launches takes; blocks_per_scan_pass: the block
+ * counts the offsets kernel turns into offsets per pass.  A map with more than items_per_block * blocks_per_scan_pass
+ * considered pixels makes that kernel loop: the size a test needs to reach its carry.  No handle, no device. */
+void pm_debug_cloud_constants(int* items_per_block, int* blocks_per_scan_pass);
+
 /* ---- the row-tiled driver's device discipline, provable on ONE GPU ------------------------------------------------
  * pm_tiled_create with the bands accounted to LOGICAL devices: band k lives on logical_devices[k] (>= 0; several bands
  * may share one) while every HIP call still goes to the physical device of the band's handle.  Such a plan logs every

@@ -4,11 +4,13 @@
 //   pm_launch.hip        the ONLY unit that includes the scalar-mode kernels (pm_kernels.hpp): one launch function each
 //   pm_sweeps.hip        the directional sweep kernels (pm_run3.hpp, pm_run2.hpp, pm_wave.hpp, pm_serial.hpp)
 //   pm_seed.hip          the device seeder (pm_seed.hpp)
-//   pm_planes_host.hip   PM_MODE_PLANES: kernels (pm_planes.hpp), schedule, pm_planes_* entry points
+//   pm_planes_host.hip   PM_MODE_PLANES: kernels (pm_planes.hpp, k_planes_normals among them), schedule, pm_planes_* entry
+//                        points, and the launch behind pm_planes_normals (pm_internal::planes_normals)
 //   pm_hostpath.hip      host-buffer entry points (pm_match_u8, submit / collect, the single-stage functions)
 //   pm_tile.hip          the row-tiled phase API pm_tile_*
 //   pm_tiled.hip         pm_tiled_*: n band handles of one process driven over that API
-//   pm_imaging.hip       the imaging rows; sees the handle through pm_internal.hpp only
+//   pm_imaging.hip       the imaging rows, the point and cloud kernels of pm_cloud.hpp among them; sees the handle through
+//                        pm_internal.hpp only
 // Every __global__ kernel lives in exactly one unit; the others reach it through the launch functions declared here.
 #pragma once
 

@@ -2,6 +2,7 @@
 //  and the device-buffer helpers.  A separate translation unit: it reaches the handle only
 // through pm_internal.hpp (device, stream, error text, one opaque state slot).
 #include "pm/imaging.h"
+#include "pm/testing.h"
 
 #include <hip/hip_runtime.h>
 
@@ -12,6 +13,7 @@
 #include <new>
 #include <vector>
 
+#include "pm_cloud.hpp"
 #include "pm_devbuf.hpp"
 #include "pm_enhance.hpp"
 #include "pm_guided.hpp"
@@ -44,6 +46,8 @@ struct ImagingState {
   // pm_match_raw_device: the rectified pairs, [left, right][n][rows][cols] bytes; pm_match_raw_bgr_device: the rectified
   // BGR images the caller did not ask for, [n][rows][cols][3] bytes each
   DevBuf<uint8_t> rect_buf;
+  // pm_point_cloud: [0] the count, [1 ..] one word per block of kCloudBlock items: its count, then its offset
+  DevBuf<int> cloud_blocks;
 };
 
 #define PM_HIP(h, call)                                                                                     \
@@ -788,6 +792,134 @@ int pm_match_raw_bgr_device(pm_handle* h, int n, const pm_rectify_view* left, co
   return match_raw(h, "pm_match_raw_bgr_device", 3, pm_match_bgr_device, n, left, right, d_left_raw_bgr8, d_right_raw_bgr8,
                    src_rows, src_cols, src_step, rows, cols, d_seed_l, d_seed_r, d_disp_l, d_disp_r, d_left_rect_bgr8,
                    d_right_rect_bgr8);
+}
+
+// ---- points, plane-mode normals and the compacted cloud behind the range stages (pm_cloud.hpp) -------------------------
+namespace {
+
+int check_cloud_camera(pm_handle* h, const char* what, const pm_cloud_camera* cam) {
+  if (!cam) {
+    set_err(h, "%s: null camera", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  static const char* const names[5] = {"fx", "fy", "cx", "cy", "baseline"};
+  const double* e = reinterpret_cast<const double*>(cam);
+  static_assert(sizeof(pm_cloud_camera) == 5 * sizeof(double), "pm_cloud_camera is 5 doubles");
+  for (int i = 0; i < 5; ++i)
+    if (!std::isfinite(e[i])) {
+      set_err(h, "%s: %s of the camera is not finite", what, names[i]);
+      return PM_ERR_INVALID_ARG;
+    }
+  if (cam->fx == 0.0 || cam->fy == 0.0) {
+    set_err(h, "%s: fx / fy of the camera must not be 0", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  return PM_OK;
+}
+
+int check_cloud_shape(pm_handle* h, const char* what, int rows, int cols) {
+  if (rows < 1 || cols < 1) {
+    set_err(h, "%s: empty image (%dx%d)", what, cols, rows);
+    return PM_ERR_INVALID_ARG;
+  }
+  if ((long long)rows * cols > INT32_MAX || (rows + kCloudBlockY - 1) / kCloudBlockY > 65535) {
+    set_err(h, "%s: %dx%d pixels exceed a 32-bit pixel index or the launch grid", what, cols, rows);
+    return PM_ERR_SIZE;
+  }
+  return PM_OK;
+}
+
+}  // namespace
+
+int pm_backproject(pm_handle* h, const pm_cloud_camera* camera, const float* d_disp, int rows, int cols, float* d_xyz) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (int rc = check_cloud_camera(h, "pm_backproject", camera)) return rc;
+  if (!d_disp || !d_xyz) {
+    set_err(h, "pm_backproject: null %s", !d_disp ? "d_disp" : "d_xyz");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_cloud_shape(h, "pm_backproject", rows, cols)) return rc;
+  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
+  const BackprojectArgs a = {cloud_cam(*camera), d_disp, rows, cols, d_xyz};
+  const int px = kCloudBlockX * 4;
+  const dim3 grid((unsigned)((cols + px - 1) / px), (unsigned)((rows + kCloudBlockY - 1) / kCloudBlockY));
+  hipLaunchKernelGGL(k_backproject, grid, dim3(kCloudBlockX, kCloudBlockY), 0, pm_internal::stream(h), a);
+  return launch_check(h, "backproject");
+}
+
+int pm_planes_normals(pm_handle* h, int pair, const pm_cloud_camera* camera, const float* d_disp_l, int rows, int cols,
+                      float* d_normals) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (int rc = check_cloud_camera(h, "pm_planes_normals", camera)) return rc;
+  if (!d_normals || pair < 0) {
+    set_err(h, "pm_planes_normals: %s", !d_normals ? "null d_normals" : "negative pair");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_cloud_shape(h, "pm_planes_normals", rows, cols)) return rc;
+  return pm_internal::planes_normals(h, pair, cloud_cam(*camera), d_disp_l, rows, cols, d_normals);
+}
+
+int pm_point_cloud(pm_handle* h, const pm_cloud_camera* camera, const pm_cloud_filter* filter, const float* d_disp,
+                   const float* d_normals, const uint8_t* d_bgr8, int rows, int cols, int capacity, float* d_xyz_out,
+                   float* d_normals_out, uint8_t* d_bgr8_out, int32_t* d_index_out, int* d_count, int* count) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_point_cloud";
+  if (int rc = check_cloud_camera(h, what, camera)) return rc;
+  if (!filter || !d_disp) {
+    set_err(h, "%s: null %s", what, !filter ? "filter" : "d_disp");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (filter->stride < 1) {
+    set_err(h, "%s: stride %d must be >= 1", what, filter->stride);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (std::isnan(filter->min_disp) || !(filter->max_range >= 0.f)) {
+    set_err(h, "%s: min_disp must not be NaN and max_range must be >= 0 (0 = no limit)", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (capacity < 0) {
+    set_err(h, "%s: capacity %d must be >= 0", what, capacity);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (d_normals_out && !d_normals) {
+    set_err(h, "%s: d_normals_out requested without d_normals", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (d_bgr8_out && !d_bgr8) {
+    set_err(h, "%s: d_bgr8_out requested without d_bgr8", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
+  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
+  ImagingState* st = state_of(h);
+  if (!st) {
+    set_err(h, "%s: out of host memory", what);
+    return PM_ERR_NOMEM;
+  }
+  const int stride = filter->stride;
+  const int sub_rows = (rows + stride - 1) / stride, sub_cols = (cols + stride - 1) / stride;
+  const CloudArgs a = {cloud_cam(*camera), *filter, d_disp, rows, cols, sub_cols, (long long)sub_rows * sub_cols};
+  const int blocks = (int)((a.items + kCloudBlock - 1) / kCloudBlock);
+  hipStream_t stream = pm_internal::stream(h);
+  PM_HIP(h, st->cloud_blocks.reserve(sizeof(int) * ((size_t)blocks + 1), stream));
+  int* d_total = st->cloud_blocks.get();
+  int* d_blocks = d_total + 1;
+  const CloudStreams s = {d_normals, d_bgr8, d_xyz_out, d_normals_out, d_bgr8_out, d_index_out, capacity};
+  hipLaunchKernelGGL(k_cloud_count, dim3((unsigned)blocks), dim3(kCloudBlock), 0, stream, a, d_blocks);
+  hipLaunchKernelGGL(k_cloud_offsets, dim3(1), dim3(kCloudScanThreads), 0, stream, d_blocks, blocks, d_total, d_count);
+  if (capacity > 0 && (d_xyz_out || d_normals_out || d_bgr8_out || d_index_out))
+    hipLaunchKernelGGL(k_cloud_scatter, dim3((unsigned)blocks), dim3(kCloudBlock), 0, stream, a, (const int*)d_blocks, s);
+  if (int rc = launch_check(h, "point cloud")) return rc;
+  if (count) {
+    PM_HIP(h, hipMemcpyAsync(count, d_total, sizeof(int), hipMemcpyDeviceToHost, stream));
+    PM_HIP(h, hipStreamSynchronize(stream));
+  }
+  return PM_OK;
+}
+
+void pm_debug_cloud_constants(int* items_per_block, int* blocks_per_scan_pass) {
+  if (items_per_block) *items_per_block = kCloudBlock;
+  if (blocks_per_scan_pass) *blocks_per_scan_pass = kCloudScanThreads;
 }
 
 // Host only: Bouguet's construction (see pm/imaging.h).

@@ -8,6 +8,7 @@
 
 namespace pm {
 struct BgrSource;
+struct CloudCam;
 }
 
 namespace pm_internal __attribute__((visibility("hidden"))) {
@@ -20,4 +21,8 @@ void** imaging_slot(pm_handle* h);     // storage for pm_imaging.hip's state
 // pm_match_bgr_device: while non-null, pm_match_device's prep stage reads this source (pm_kernels.hpp::k_prep_bgr)
 void set_bgr_source(pm_handle* h, const pm::BgrSource* src);
 void release_imaging(pm_handle* h);    // defined in pm_imaging.hip, called by pm_destroy
+// pm_planes_normals behind its argument checks (defined in pm_planes_host.hip, the unit of the plane-mode kernels):
+// PM_ERR_STATE unless the handle is in PM_MODE_PLANES and holds the state of pair `pair` at rows x cols
+int planes_normals(pm_handle* h, int pair, const pm::CloudCam& cam, const float* d_disp_l, int rows, int cols,
+                   float* d_normals);
 }  // namespace pm_internal

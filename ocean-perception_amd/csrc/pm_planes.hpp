@@ -23,6 +23,7 @@
 // (the channels sit 16 bits apart in the dword and cannot carry into each other), four taps per v_sad_u8.
 #pragma once
 
+#include "pm_cloud_body.hpp"
 #include "pm_device.hpp"
 #include "pm_sweep_defs.hpp"
 
@@ -1082,6 +1083,26 @@ __global__ void __launch_bounds__(256) k_planes_copy(PlaneSet ps, PlaneState<ST>
   float* q = buf + ((size_t)k * ps.rows + y) * ps.cols + x;
   if (to_state) *p = (ST)*q;
   else *q = (float)*p;
+}
+
+// pm_planes_normals (include/pm/imaging.h): the unit normals of the LEFT view of pair `pair`, organised
+// [rows][cols][3], from the resident state -- f32 or f16, converted exactly -- through cloud_normal
+// (pm_cloud_body.hpp; definition: tests/pointcloud_ref.py).  disp_l: null, or the map whose zeros mask the normals (the
+// cross-check's result).  grid = pixel grid, z = 1.
+template <typename ST>
+__global__ void __launch_bounds__(256) k_planes_normals(PlaneSet ps, PlaneState<ST> st, int pair, CloudCam cam,
+                                                        const float* __restrict__ disp_l, float* __restrict__ normals) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x;
+  const int y = blockIdx.y;
+  if (x >= ps.cols) return;
+  const size_t at = st.idx(x, y), px = (size_t)y * ps.cols + x;
+  const float a = (float)st.arr(pair, 0, 0)[at], b = (float)st.arr(pair, 0, 1)[at], z = (float)st.arr(pair, 0, 2)[at];
+  const bool masked = disp_l && !(disp_l[px] > 0.f);
+  float n[3];
+  cloud_normal(cam, a, b, z, x, y, masked, n);
+  normals[px * 3] = n[0];
+  normals[px * 3 + 1] = n[1];
+  normals[px * 3 + 2] = n[2];
 }
 
 }  // namespace pm

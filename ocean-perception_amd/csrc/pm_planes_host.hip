@@ -4,6 +4,7 @@
 #include <cmath>
 
 #include "pm_handle.hpp"
+#include "pm_internal.hpp"
 #include "pm_planes.hpp"
 #include "pm_tune.hpp"
 
@@ -250,6 +251,34 @@ int planes_match(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_ri
 
 }  // namespace eng
 }  // namespace pm
+
+// The state is the LAST match's (or pm_planes_begin / _step / _write's): valid exactly when pm_planes_read is.
+int pm_internal::planes_normals(pm_handle* h, int pair, const CloudCam& cam, const float* d_disp_l, int rows, int cols,
+                                float* d_normals) {
+  if (h->params.mode != PM_MODE_PLANES) {
+    set_err(h, "pm_planes_normals: the handle was created with mode != PM_MODE_PLANES (the scalar mode has no slopes)");
+    return PM_ERR_STATE;
+  }
+  if (!h->pl_on || pair >= h->pl_n || rows != h->pl_rows || cols != h->pl_cols) {
+    set_err(h, "pm_planes_normals: no plane state for pair %d at %dx%d (the last match left %d pair(s) at %dx%d)", pair, cols,
+            rows, h->pl_on ? h->pl_n : 0, h->pl_cols, h->pl_rows);
+    return PM_ERR_STATE;
+  }
+  PM_HIP(h, hipSetDevice(h->device));
+  prof_break_all(h);
+  const int nv = h->params.left_right_check ? 2 : 1;
+  const PlaneSet ps = plane_set(h, h->pl_rows, h->pl_cols, nv);
+  if (h->params.state_dtype == PM_STATE_F16) {
+    PlaneState<_Float16> st{(_Float16*)h->planes_state.get(), ps.plane, ps.pitch / 2};
+    hipLaunchKernelGGL(k_planes_normals<_Float16>, pixel_grid(ps.cols, ps.rows, 1), dim3(256), 0, h->stream, ps, st, pair,
+                       cam, d_disp_l, d_normals);
+  } else {
+    PlaneState<float> st{(float*)h->planes_state.get(), ps.plane, ps.pitch / 2};
+    hipLaunchKernelGGL(k_planes_normals<float>, pixel_grid(ps.cols, ps.rows, 1), dim3(256), 0, h->stream, ps, st, pair, cam,
+                       d_disp_l, d_normals);
+  }
+  return launch_check(h, "planes normals");
+}
 
 extern "C" {
 

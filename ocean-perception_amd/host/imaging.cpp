@@ -282,5 +282,98 @@ core::Image<core::Vec3b> Rectify(const core::Image<core::Vec3b>& raw, const Rect
   return RectifyImage(raw, view, rows, cols, valid);
 }
 
+namespace {
+pm_cloud_camera CloudCamera(const StereoModel& m) { return pm_cloud_camera{m.fx, m.fy, m.cx, m.cy, m.baseline}; }
+}  // namespace
+
+core::Image<core::Vec3f> Backproject(const core::Image<float>& disp, const StereoModel& model) {
+  if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("Backproject: empty map");
+  std::lock_guard<std::mutex> lock(g_mutex);
+  pm_handle* h = Context();
+  core::Image<core::Vec3f> out(disp.rows, disp.cols);
+  DeviceBuffer d_in(h, Bytes(disp)), d_out(h, Bytes(out));
+  d_in.Upload(disp.data(), Bytes(disp));
+  const pm_cloud_camera cam = CloudCamera(model);
+  Check(pm_backproject(h, &cam, d_in.as<float>(), disp.rows, disp.cols, d_out.as<float>()), "pm_backproject");
+  d_out.Download(out.data(), Bytes(out));
+  return out;
+}
+
+PointCloud MakePointCloud(const core::Image<float>& disp, const StereoModel& model, const CloudFilter& filter,
+                          const core::Image<core::Vec3f>* normals, const core::Image<core::Vec3b>* bgr) {
+  if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("MakePointCloud: empty map");
+  if (normals) SameSize(disp.rows, disp.cols, normals->rows, normals->cols, "MakePointCloud (normals)");
+  if (bgr) SameSize(disp.rows, disp.cols, bgr->rows, bgr->cols, "MakePointCloud (bgr)");
+  std::lock_guard<std::mutex> lock(g_mutex);
+  pm_handle* h = Context();
+  DeviceBuffer d_in(h, Bytes(disp)), d_n(h, normals ? Bytes(*normals) : 0), d_c(h, bgr ? Bytes(*bgr) : 0);
+  d_in.Upload(disp.data(), Bytes(disp));
+  if (normals) d_n.Upload(normals->data(), Bytes(*normals));
+  if (bgr) d_c.Upload(bgr->data(), Bytes(*bgr));
+  const pm_cloud_camera cam = CloudCamera(model);
+  const pm_cloud_filter flt = {filter.min_disp, filter.max_range, filter.stride};
+  // count first (capacity 0), then outputs of exactly that size
+  int count = 0;
+  Check(pm_point_cloud(h, &cam, &flt, d_in.as<float>(), nullptr, nullptr, disp.rows, disp.cols, 0, nullptr, nullptr, nullptr,
+                       nullptr, nullptr, &count),
+        "pm_point_cloud");
+  PointCloud pc;
+  if (count <= 0) return pc;
+  const size_t n = (size_t)count;
+  DeviceBuffer o_xyz(h, n * sizeof(core::Vec3f)), o_n(h, normals ? n * sizeof(core::Vec3f) : 0),
+      o_c(h, bgr ? n * sizeof(core::Vec3b) : 0), o_i(h, n * sizeof(int32_t));
+  int again = 0;
+  Check(pm_point_cloud(h, &cam, &flt, d_in.as<float>(), normals ? d_n.as<float>() : nullptr, bgr ? d_c.as<uint8_t>() : nullptr,
+                       disp.rows, disp.cols, count, o_xyz.as<float>(), normals ? o_n.as<float>() : nullptr,
+                       bgr ? o_c.as<uint8_t>() : nullptr, o_i.as<int32_t>(), nullptr, &again),
+        "pm_point_cloud");
+  if (again != count) throw std::runtime_error("MakePointCloud: the count changed between two passes over one map");
+  pc.xyz.resize(n);
+  pc.index.resize(n);
+  o_xyz.Download(pc.xyz.data(), n * sizeof(core::Vec3f));
+  o_i.Download(pc.index.data(), n * sizeof(int32_t));
+  if (normals) {
+    pc.normals.resize(n);
+    o_n.Download(pc.normals.data(), n * sizeof(core::Vec3f));
+  }
+  if (bgr) {
+    pc.bgr.resize(n);
+    o_c.Download(pc.bgr.data(), n * sizeof(core::Vec3b));
+  }
+  return pc;
+}
+
+core::Image<core::Vec3f> PlaneNormals(pm::PatchmatchGpu& matcher, const StereoModel& model, int rows, int cols,
+                                      const core::Image<float>* disp_l) {
+  pm_handle* h = matcher.handle();
+  if (!h) throw std::runtime_error("PlaneNormals: the matcher has not matched yet");
+  if (rows <= 0 || cols <= 0) throw std::invalid_argument("PlaneNormals: empty size");
+  if (disp_l) SameSize(rows, cols, disp_l->rows, disp_l->cols, "PlaneNormals");
+  auto check = [h](int status, const char* what) {  // the matcher's handle, not the imaging context's
+    if (status != PM_OK) throw std::runtime_error(std::string(what) + ": " + pm_status_string(status) + " -- " + pm_last_error(h));
+  };
+  core::Image<core::Vec3f> out(rows, cols);
+  void *d_out = nullptr, *d_mask = nullptr;
+  check(pm_device_malloc(h, Bytes(out), &d_out), "pm_device_malloc");
+  int rc = PM_OK;
+  if (disp_l) {
+    rc = pm_device_malloc(h, Bytes(*disp_l), &d_mask);
+    if (rc == PM_OK) rc = pm_upload(h, d_mask, disp_l->data(), Bytes(*disp_l));
+  }
+  const pm_cloud_camera cam = CloudCamera(model);
+  const char* what = "pm_planes_normals";
+  if (rc == PM_OK) rc = pm_planes_normals(h, 0, &cam, static_cast<const float*>(d_mask), rows, cols, static_cast<float*>(d_out));
+  if (rc == PM_OK) {
+    rc = pm_download(h, out.data(), d_out, Bytes(out));
+    what = "pm_download";
+  }
+  std::string error;
+  if (rc != PM_OK) error = std::string(what) + ": " + pm_status_string(rc) + " -- " + pm_last_error(h);
+  pm_device_free(h, d_mask);
+  pm_device_free(h, d_out);
+  if (rc != PM_OK) throw std::runtime_error(error);
+  return out;
+}
+
 }  // namespace imaging
 }  // namespace bm

@@ -15,6 +15,7 @@
 #pragma once
 
 #include <array>
+#include <vector>
 
 #include "patchmatch_gpu.hpp"
 #include "pm/imaging.h"
@@ -78,6 +79,38 @@ Image1b Rectify(const Image1b& raw, const RectifyView& view, int rows, int cols,
 // the library exports this one signature whatever the caller includes.
 core::Image<core::Vec3b> Rectify(const core::Image<core::Vec3b>& raw, const RectifyView& view, int rows, int cols,
                                  core::Image<uint8_t>* valid = nullptr);
+
+
+// Not in the reference as functions: what its consumers of disparity do pixel by pixel on the host,
+// LeftCamera().Backproject(pixel, DispToDepth(disp)) (src/vehicle/mesher/object_mesher.cpp:146-150,
+// src/vehicle/vio/stereo_frontend.cpp:119, vision_core/pinhole_camera.cpp:41-45), for a whole map on the device
+// (pm/imaging.h: pm_backproject, pm_point_cloud, pm_planes_normals; definition: tests/pointcloud_ref.py).  Declared with
+// core::Image<...> itself, not the Image1f alias, for the reason given at the BGR Rectify overload.
+struct StereoModel {  // the rectified left pinhole and the baseline: the entries of pm_cloud_camera
+  double fx = 0, fy = 0, cx = 0, cy = 0, baseline = 0;
+};
+// organised points, (0, 0, 0) where disp is not > 0
+core::Image<core::Vec3f> Backproject(const core::Image<float>& disp, const StereoModel& model);
+struct CloudFilter {  // pm_cloud_filter
+  float min_disp = 0.f;   // a pixel counts iff disp > 0 and disp >= min_disp
+  float max_range = 0.f;  // > 0: and iff Z <= max_range; 0 = no limit
+  int stride = 1;         // only pixels with x % stride == 0 and y % stride == 0
+};
+// The counted pixels in row-major order.  normals / bgr are empty where the matching input was not given.
+struct PointCloud {
+  std::vector<core::Vec3f> xyz;
+  std::vector<core::Vec3f> normals;
+  std::vector<core::Vec3b> bgr;
+  std::vector<int32_t> index;  // y * cols + x
+};
+PointCloud MakePointCloud(const core::Image<float>& disp, const StereoModel& model, const CloudFilter& filter = CloudFilter(),
+                          const core::Image<core::Vec3f>* normals = nullptr, const core::Image<core::Vec3b>* bgr = nullptr);
+// PM_MODE_PLANES only: the organised unit normals of the left view, facing the camera, from the plane state the LAST
+// Match() of `matcher` (rows x cols) left on the device -- the next Match() overwrites it.  disp_l: that Match()'s left map,
+// whose zeros (the cross-check's mask) zero the normals; null = no mask.  Throws std::runtime_error where
+// pm_planes_normals refuses (a scalar-mode matcher, no match yet, another size).
+core::Image<core::Vec3f> PlaneNormals(pm::PatchmatchGpu& matcher, const StereoModel& model, int rows, int cols,
+                                      const core::Image<float>* disp_l = nullptr);
 
 }  // namespace imaging
 }  // namespace bm

@@ -43,6 +43,7 @@ EXPORTS = [
     "pm_fast_guided_filter", "pm_estimate_illuminant_range_guided", "pm_gather_pixels",
     "pm_rectify_u8", "pm_rectify_map", "pm_match_raw_device", "pm_stereo_rectify",
     "pm_rectify_bgr8", "pm_match_raw_bgr_device",
+    "pm_backproject", "pm_planes_normals", "pm_point_cloud", "pm_debug_cloud_constants",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
     "pm_debug_sweep_plan",
     "pm_remove_background", "pm_mask_occlusions", "pm_foreground_texture_mask", "pm_sparse_init", "pm_corner_subpix", "pm_profile_enable", "pm_profile_read",
@@ -137,6 +138,28 @@ class PmCamera(C.Structure):  # include/pm/imaging.h: the radial-tangential mode
 class PmRectifyView(C.Structure):
     _fields_ = [("cam", PmCamera), ("R", C.c_double * 9), ("fx_new", C.c_double), ("fy_new", C.c_double),
                 ("cx_new", C.c_double), ("cy_new", C.c_double)]
+
+
+class PmCloudCamera(C.Structure):  # the rectified pinhole of the point-cloud stages
+    _fields_ = [(name, C.c_double) for name in ("fx", "fy", "cx", "cy", "baseline")]
+
+
+class PmCloudFilter(C.Structure):
+    _fields_ = [("min_disp", C.c_float), ("max_range", C.c_float), ("stride", C.c_int)]
+
+
+def cloud_camera(values):
+    """A PmCloudCamera from (fx, fy, cx, cy, baseline); a PmCloudCamera or None passes through."""
+    if values is None or isinstance(values, PmCloudCamera):
+        return values
+    return PmCloudCamera(*[float(v) for v in values])
+
+
+def cloud_constants():
+    """pm_debug_cloud_constants: (considered pixels per block, block counts per pass of the offsets kernel)."""
+    a, b = C.c_int(0), C.c_int(0)
+    load().pm_debug_cloud_constants(C.byref(a), C.byref(b))
+    return a.value, b.value
 
 
 def rectify_view(values):
@@ -277,6 +300,15 @@ def load():
     for name in ("pm_rectify_u8", "pm_rectify_map", "pm_match_raw_device", "pm_stereo_rectify", "pm_rectify_bgr8",
                  "pm_match_raw_bgr_device"):
         getattr(lib, name).restype = C.c_int
+    cam_p = C.POINTER(PmCloudCamera)
+    lib.pm_backproject.argtypes = [vp, cam_p, vp, C.c_int, C.c_int, vp]
+    lib.pm_planes_normals.argtypes = [vp, C.c_int, cam_p, vp, C.c_int, C.c_int, vp]
+    lib.pm_point_cloud.argtypes = [vp, cam_p, C.POINTER(PmCloudFilter), vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp,
+                                   vp, C.POINTER(C.c_int)]
+    for name in ("pm_backproject", "pm_planes_normals", "pm_point_cloud"):
+        getattr(lib, name).restype = C.c_int
+    lib.pm_debug_cloud_constants.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.pm_debug_cloud_constants.restype = None
     lib.pm_device_malloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     lib.pm_device_free.argtypes = [vp, vp]
     lib.pm_upload.argtypes = [vp, vp, vp, C.c_size_t]
@@ -739,6 +771,31 @@ class Engine:
                                                      C.byref(vr) if vr is not None else None, d_left_raw, d_right_raw,
                                                      src_rows, src_cols, src_step, rows, cols, d_seed_l, d_seed_r, d_disp_l,
                                                      d_disp_r, d_left_rect, d_right_rect), "pm_match_raw_bgr_device")
+
+    def backproject(self, camera, d_disp, rows, cols, d_xyz):
+        """pm_backproject (raw device addresses); camera: (fx, fy, cx, cy, baseline) or a PmCloudCamera."""
+        c = cloud_camera(camera)
+        self._check(self.lib.pm_backproject(self.h, C.byref(c) if c is not None else None, d_disp, rows, cols, d_xyz),
+                    "pm_backproject")
+
+    def planes_normals(self, pair, camera, d_disp_l, rows, cols, d_normals):
+        """pm_planes_normals: the left view's unit normals from the resident plane state of the last match."""
+        c = cloud_camera(camera)
+        self._check(self.lib.pm_planes_normals(self.h, pair, C.byref(c) if c is not None else None, d_disp_l, rows, cols,
+                                               d_normals), "pm_planes_normals")
+
+    def point_cloud(self, camera, d_disp, rows, cols, capacity, min_disp=0.0, max_range=0.0, stride=1, d_normals=None,
+                    d_bgr8=None, d_xyz_out=None, d_normals_out=None, d_bgr8_out=None, d_index_out=None, d_count=None,
+                    host_count=True):
+        """pm_point_cloud (raw device addresses) -> the number of counted pixels (None with host_count=False: the call
+        then only enqueues)."""
+        c = cloud_camera(camera)
+        f = PmCloudFilter(min_disp, max_range, stride)
+        n = C.c_int(-1)
+        self._check(self.lib.pm_point_cloud(self.h, C.byref(c) if c is not None else None, C.byref(f), d_disp, d_normals,
+                                            d_bgr8, rows, cols, capacity, d_xyz_out, d_normals_out, d_bgr8_out, d_index_out,
+                                            d_count, C.byref(n) if host_count else None), "pm_point_cloud")
+        return n.value if host_count else None
 
     def normalize(self, d_bgr, rows, cols, d_out):
         self._check(self.lib.pm_normalize(self.h, d_bgr, rows, cols, d_out), "pm_normalize")

@@ -1,0 +1,121 @@
+// cloud_host_main.cpp -- runs the point-cloud stages' own per-thread code (csrc/pm_cloud_body.hpp: backproject_four,
+// cloud_item, cloud_store, cloud_normal -- the bodies of the kernels of csrc/pm_cloud.hpp and of k_planes_normals) on the
+// HOST, so that tests/test_pointcloud.py can hold it to the definition (tests/pointcloud_ref.py) without a GPU and under
+// -fsanitize=address,undefined.  Every buffer is a heap
+// allocation of EXACTLY the bytes the stage may touch: a load past the last disparity, or a store behind slot
+// min(count, capacity) - 1, is reported.  Compiled as HIP source with the host-only switch of hipcc and -ffp-contract=off.
+//   cloud_host_main <dir>
+// <dir> holds .npy dumps (numpy's format, version 1, C order, little endian; the header is skipped and the payload size
+// checked): params.npy (float64: rows, cols, fx, fy, cx, cy, baseline, min_disp, max_range, stride, capacity, shift),
+// disp.npy (float32 [rows][cols]), planes.npy (float32 [3][rows][cols]: a, b, z), bgr.npy (uint8 [rows][cols][3]) and the
+// definition's results want_xyz.npy, want_normals.npy (masked by disp), want_count.npy (int32 [1]), want_cloud_xyz.npy,
+// want_cloud_normals.npy, want_cloud_bgr.npy, want_cloud_index.npy (each with min(count, capacity) entries).
+// shift: the organised outputs start `shift` floats into their allocation (an unaligned destination for shift % 4 != 0).
+// Exit status 0: every result equals its dump byte for byte; 1: a mismatch (named on stderr); 2: bad input.
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "pm_cloud_body.hpp"
+
+static bool read_npy(const std::string& path, size_t bytes, std::unique_ptr<uint8_t[]>* out) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return false;
+  uint8_t head[10];
+  bool ok = fread(head, 1, 10, f) == 10 && !memcmp(head, "\x93NUMPY\x01", 7);
+  const size_t hlen = ok ? (size_t)head[8] | ((size_t)head[9] << 8) : 0;
+  ok = ok && fseek(f, 0, SEEK_END) == 0 && (size_t)ftell(f) == 10 + hlen + bytes && fseek(f, (long)(10 + hlen), SEEK_SET) == 0;
+  if (ok) {
+    out->reset(new uint8_t[bytes ? bytes : 1]);  // exactly sized (one byte where the dump is empty)
+    ok = fread(out->get(), 1, bytes, f) == bytes;
+  }
+  fclose(f);
+  if (!ok) fprintf(stderr, "cannot read %zu payload bytes from %s\n", bytes, path.c_str());
+  return ok;
+}
+
+static int differ(const char* what, const void* got, const void* want, size_t bytes) {
+  if (!memcmp(got, want, bytes)) return 0;
+  const uint8_t* g = (const uint8_t*)got;
+  const uint8_t* w = (const uint8_t*)want;
+  size_t at = 0;
+  while (g[at] == w[at]) ++at;
+  fprintf(stderr, "%s differs from the definition at byte %zu of %zu\n", what, at, bytes);
+  return 1;
+}
+
+int main(int argc, char** argv) {
+  if (argc != 2) return 2;
+  const std::string dir = std::string(argv[1]) + "/";
+  std::unique_ptr<uint8_t[]> raw;
+  if (!read_npy(dir + "params.npy", 12 * sizeof(double), &raw)) return 2;
+  double p[12];
+  memcpy(p, raw.get(), sizeof p);
+  const int rows = (int)p[0], cols = (int)p[1], stride = (int)p[9], capacity = (int)p[10], shift = (int)p[11];
+  const pm_cloud_camera camera = {p[2], p[3], p[4], p[5], p[6]};
+  const pm_cloud_filter filter = {(float)p[7], (float)p[8], stride};
+  if (rows < 1 || cols < 1 || stride < 1 || capacity < 0 || shift < 0) return 2;
+  const size_t px = (size_t)rows * cols;
+  std::unique_ptr<uint8_t[]> disp_b, planes_b, bgr_b, want_xyz, want_normals, want_count;
+  if (!read_npy(dir + "disp.npy", 4 * px, &disp_b) || !read_npy(dir + "planes.npy", 12 * px, &planes_b) ||
+      !read_npy(dir + "bgr.npy", 3 * px, &bgr_b) || !read_npy(dir + "want_xyz.npy", 12 * px, &want_xyz) ||
+      !read_npy(dir + "want_normals.npy", 12 * px, &want_normals) || !read_npy(dir + "want_count.npy", 4, &want_count))
+    return 2;
+  const float* disp = (const float*)disp_b.get();  // operator new aligns to 16 bytes, like a device allocation
+  const float* planes = (const float*)planes_b.get();
+  const pm::CloudCam cam = pm::cloud_cam(camera);
+  int bad = 0;
+
+  // pm_backproject: every thread of k_backproject, into an allocation with `shift` floats in front and none behind
+  std::unique_ptr<float[]> xyz(new float[shift + 3 * px]);
+  for (int k = 0; k < shift; ++k) xyz[k] = -77.f;
+  const pm::BackprojectArgs ba = {cam, disp, rows, cols, xyz.get() + shift};
+  for (int y = 0; y < rows; ++y)
+    for (int x4 = 0; x4 < cols; x4 += 4) pm::backproject_four(ba, x4, y);
+  bad |= differ("xyz", xyz.get() + shift, want_xyz.get(), 12 * px);
+  for (int k = 0; k < shift; ++k) bad |= xyz[k] != -77.f;
+
+  // pm_planes_normals: cloud_normal per pixel, masked by the map
+  std::unique_ptr<float[]> normals(new float[3 * px]);
+  for (int y = 0; y < rows; ++y)
+    for (int x = 0; x < cols; ++x) {
+      const size_t i = (size_t)y * cols + x;
+      pm::cloud_normal(cam, planes[i], planes[px + i], planes[2 * px + i], x, y, !(disp[i] > 0.f), normals.get() + 3 * i);
+    }
+  bad |= differ("normals", normals.get(), want_normals.get(), 12 * px);
+
+  // pm_point_cloud: the items in order, the slot counted as the three launches compute it
+  int want_n = 0;
+  memcpy(&want_n, want_count.get(), 4);
+  const size_t m = (size_t)(want_n < capacity ? want_n : capacity);
+  std::unique_ptr<uint8_t[]> want_cxyz, want_cn, want_cbgr, want_cidx;
+  if (want_n < 0 || !read_npy(dir + "want_cloud_xyz.npy", 12 * m, &want_cxyz) ||
+      !read_npy(dir + "want_cloud_normals.npy", 12 * m, &want_cn) || !read_npy(dir + "want_cloud_bgr.npy", 3 * m, &want_cbgr) ||
+      !read_npy(dir + "want_cloud_index.npy", 4 * m, &want_cidx))
+    return 2;
+  std::unique_ptr<float[]> cxyz(new float[3 * m ? 3 * m : 1]), cn(new float[3 * m ? 3 * m : 1]);
+  std::unique_ptr<uint8_t[]> cbgr(new uint8_t[3 * m ? 3 * m : 1]);
+  std::unique_ptr<int32_t[]> cidx(new int32_t[m ? m : 1]);
+  const int sub_rows = (rows + stride - 1) / stride, sub_cols = (cols + stride - 1) / stride;
+  const pm::CloudArgs ca = {cam, filter, disp, rows, cols, sub_cols, (long long)sub_rows * sub_cols};
+  const pm::CloudStreams cs = {normals.get(), bgr_b.get(), cxyz.get(), cn.get(), cbgr.get(), cidx.get(), capacity};
+  long long slot = 0;
+  for (long long item = 0; item < ca.items; ++item) {
+    int x, y;
+    float pt[3];
+    if (!pm::cloud_item(ca, item, &x, &y, pt)) continue;
+    if (slot < capacity) pm::cloud_store(ca, cs, slot, x, y, pt);
+    ++slot;
+  }
+  if (slot != want_n) {
+    fprintf(stderr, "count %lld, the definition counts %d\n", slot, want_n);
+    bad = 1;
+  }
+  bad |= differ("cloud xyz", cxyz.get(), want_cxyz.get(), 12 * m);
+  bad |= differ("cloud normals", cn.get(), want_cn.get(), 12 * m);
+  bad |= differ("cloud bgr", cbgr.get(), want_cbgr.get(), 3 * m);
+  bad |= differ("cloud index", cidx.get(), want_cidx.get(), 4 * m);
+  return bad ? 1 : 0;
+}
