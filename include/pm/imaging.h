@@ -257,7 +257,7 @@ int pm_backproject(pm_handle* h, const pm_cloud_camera* camera, const float* d_d
  * already enqueued on the handle's stream is ordered in front of it.  (0, 0, 0) where the state's z is not > 0 and, if
  * d_disp_l is given, where d_disp_l is not > 0 -- pass the left map of that match to apply the cross-check's mask.
  * PM_ERR_STATE: the handle is not in PM_MODE_PLANES, or holds no state for `pair` at rows x cols; the call is valid
- * exactly when pm_planes_read is.  The scalar mode keeps no slopes and gets no normals. */
+ * exactly when pm_planes_read is.  The scalar mode keeps no slopes: its normals come from pm_disparity_normals below. */
 int pm_planes_normals(pm_handle* h, int pair, const pm_cloud_camera* camera, const float* d_disp_l /* may be NULL */,
                       int rows, int cols, float* d_normals);
 
@@ -280,6 +280,39 @@ int pm_point_cloud(pm_handle* h, const pm_cloud_camera* camera, const pm_cloud_f
                    float* d_xyz_out /* [capacity][3], may be NULL */, float* d_normals_out /* [capacity][3], may be NULL */,
                    uint8_t* d_bgr8_out /* [capacity][3], may be NULL */, int32_t* d_index_out /* [capacity], may be NULL */,
                    int* d_count /* device, may be NULL */, int* count /* host, may be NULL */);
+
+/* ---- normals for a disparity map that carries no slopes: a windowed, edge-aware plane fit per pixel -------------------
+ * What it is for: the d_normals input of pm_point_cloud for PM_MODE_SCALAR maps.  The scalar sweeps adopt a neighbour's
+ * value, so a map is runs of equal disparities with small steps between them: finite differences are zero inside a run and
+ * a spike at its edge; a least-squares plane over a (2r+1)^2 window is not.  Held to its CPU definition
+ * (tests/normals_fit_ref.py) BIT FOR BIT; every operation is one rounding, parentheses and the order of the sums as written:
+ *   taps    d0 = disp(y, x); not d0 > 0 (0, -0.0, negative, NaN): no fit, support 0.  A tap (dx, dy), dx, dy in -r..r,
+ *           COUNTS iff (x+dx, y+dy) lies in the image, t = disp there is > 0 and fabs(e) <= (double)max_diff with
+ *           e = (double)t - (double)d0 in binary64 (a NaN e never counts: d0 = +inf, the centre tap included).
+ *   sums    exact integers over the counting taps: n, Sx, Sy, Sxx, Sxy, Syy of 1, dx, dy, dx^2, dx dy, dy^2; binary64,
+ *           per window row dy = -r..r with dx = -r..r left to right from +0.0:  R0 = R0 + e,  R1 = R1 + ((double)dx * e);
+ *           then top to bottom from +0.0:  Se = Se + R0,  Sxe = Sxe + R1,  Sye = Sye + ((double)dy * R0).
+ *   solve   the integer cofactors of [[Sxx,Sxy,Sx],[Sxy,Syy,Sy],[Sx,Sy,n]]:
+ *             C00 = Syy*n - Sy*Sy   C01 = Sx*Sy - Sxy*n   C02 = Sxy*Sy - Syy*Sx
+ *             C11 = Sxx*n - Sx*Sx   C12 = Sxy*Sx - Sxx*Sy C22 = Sxx*Syy - Sxy*Sxy   det = Sxx*C00 + Sxy*C01 + Sx*C02
+ *           VALID iff n >= min_support and det > 0 (a collinear or single-pixel support has det == 0 exactly); in binary64
+ *             a64 = (((C00*Sxe) + (C01*Sye)) + (C02*Se)) / det,  b64 with (C01, C11, C12),  c64 with (C02, C12, C22);
+ *           a = (float)a64, b = (float)b64, z = (float)((double)d0 + c64): the fitted disparity at the pixel.
+ *   out     d_planes = (a, b, z) where VALID else (0, 0, 0); d_support = n, valid or not; d_normals = the normal of
+ *           pm_planes_normals above for the plane (a, b, z) of pixel (x, y), (0, 0, 0) where not VALID, where z is not > 0
+ *           and where its length is not finite.
+ * Valid in every mode of the handle: it reads a map, not the handle's state.  Images smaller than the window are legal;
+ * taps outside the image never count.  One launch; a workgroup stages its tile and an r-wide halo in LDS once.
+ * PM_ERR_INVALID_ARG, with pm_last_error naming the argument and nothing enqueued: a null fit or d_disp; no output at all;
+ * d_normals without a camera, or with one pm_backproject refuses (the camera is read for d_normals alone); radius outside
+ * 1..7; a max_diff that is not finite or < 0; min_support outside 3..(2r+1)^2; rows or cols < 1.  PM_ERR_SIZE as for
+ * pm_backproject. */
+typedef struct pm_normals_fit { int radius; float max_diff; int min_support; } pm_normals_fit;
+int pm_disparity_normals(pm_handle* h, const pm_cloud_camera* camera, const pm_normals_fit* fit,
+                         const float* d_disp, int rows, int cols,
+                         float* d_normals   /* [rows][cols][3], may be NULL */,
+                         float* d_planes    /* [3][rows][cols]: a, b, z, may be NULL */,
+                         uint8_t* d_support /* [rows][cols], may be NULL */);
 
 /* ---- device buffers for host code that does not include HIP (host/imaging.hpp uses them) ------------------
  * pm_device_malloc / pm_device_free wrap hipMalloc / hipFree on the handle's device; pm_upload / pm_download are

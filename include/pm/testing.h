@@ -60,6 +60,12 @@ int pm_debug_sweep_plan(const pm_params* params, int rows, int cols, int patch_h
  * considered pixels makes that kernel loop: the size a test needs to reach its carry.  No handle, no device. */
 void pm_debug_cloud_constants(int* items_per_block, int* blocks_per_scan_pass);
 
+/* ---- pm_disparity_normals' launch constants (csrc/pm_normals_fit_body.hpp) --------------------------------------------
+ * tile_cols x tile_rows: the pixels one workgroup owns (its LDS tile is that plus a halo of `radius` cells on every side);
+ * pixels_per_thread: the neighbouring pixels of a row one thread fits.  Tests place shapes at tile edges with them.  No
+ * handle, no device. */
+void pm_debug_normals_fit_constants(int* tile_cols, int* tile_rows, int* pixels_per_thread);
+
 /* ---- the row-tiled driver's device discipline, provable on ONE GPU ------------------------------------------------
  * pm_tiled_create with the bands accounted to LOGICAL devices: band k lives on logical_devices[k] (>= 0; several bands
  * may share one) while every HIP call still goes to the physical device of the band's handle.  Such a plan logs every

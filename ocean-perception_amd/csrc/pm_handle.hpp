@@ -9,8 +9,8 @@
 //   pm_hostpath.hip      host-buffer entry points (pm_match_u8, submit / collect, the single-stage functions)
 //   pm_tile.hip          the row-tiled phase API pm_tile_*
 //   pm_tiled.hip         pm_tiled_*: n band handles of one process driven over that API
-//   pm_imaging.hip       the imaging rows, the point and cloud kernels of pm_cloud.hpp among them; sees the handle through
-//                        pm_internal.hpp only
+//   pm_imaging.hip       the imaging rows, the point and cloud kernels of pm_cloud.hpp and the plane-fit kernel of
+//                        pm_normals_fit.hpp (k_normals_fit<R>) among them; sees the handle through pm_internal.hpp only
 // Every __global__ kernel lives in exactly one unit; the others reach it through the launch functions declared here.
 #pragma once
 

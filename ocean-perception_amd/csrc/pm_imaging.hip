@@ -19,6 +19,7 @@
 #include "pm_guided.hpp"
 #include "pm_imaging.hpp"
 #include "pm_internal.hpp"
+#include "pm_normals_fit.hpp"
 #include "pm_rectify.hpp"
 #include "pm_tune.hpp"
 
@@ -920,6 +921,75 @@ int pm_point_cloud(pm_handle* h, const pm_cloud_camera* camera, const pm_cloud_f
 void pm_debug_cloud_constants(int* items_per_block, int* blocks_per_scan_pass) {
   if (items_per_block) *items_per_block = kCloudBlock;
   if (blocks_per_scan_pass) *blocks_per_scan_pass = kCloudScanThreads;
+}
+
+// ---- normals for scalar-mode maps: the windowed plane fit (pm_normals_fit.hpp) ---------------------------------------------
+namespace {
+
+template <int R>
+void launch_normals_fit(const NormalsFitArgs& a, dim3 grid, hipStream_t stream) {
+  hipLaunchKernelGGL(k_normals_fit<R>, grid, dim3(kNormalsFitTileCols, kNormalsFitTileRows), 0, stream, a);
+}
+
+}  // namespace
+
+int pm_disparity_normals(pm_handle* h, const pm_cloud_camera* camera, const pm_normals_fit* fit, const float* d_disp, int rows,
+                         int cols, float* d_normals, float* d_planes, uint8_t* d_support) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_disparity_normals";
+  if (!fit || !d_disp) {
+    set_err(h, "%s: null %s", what, !fit ? "fit" : "d_disp");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (!d_normals && !d_planes && !d_support) {
+    set_err(h, "%s: no output (d_normals, d_planes and d_support are all null)", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (d_normals)  // the camera is read for the normals alone
+    if (int rc = check_cloud_camera(h, what, camera)) return rc;
+  if (fit->radius < 1 || fit->radius > kNormalsFitMaxRadius) {
+    set_err(h, "%s: radius %d outside 1..%d", what, fit->radius, kNormalsFitMaxRadius);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (!std::isfinite(fit->max_diff) || fit->max_diff < 0.f) {
+    set_err(h, "%s: max_diff must be finite and >= 0", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  const int window = (2 * fit->radius + 1) * (2 * fit->radius + 1);
+  if (fit->min_support < 3 || fit->min_support > window) {
+    set_err(h, "%s: min_support %d outside 3..%d", what, fit->min_support, window);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
+  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
+  const NormalsFitArgs a = {d_normals ? cloud_cam(*camera) : CloudCam{1.0, 1.0, 0.0, 0.0, 1.0}, d_disp, rows, cols, fit->radius,
+                            fit->max_diff, fit->min_support, d_normals, d_planes, d_support};
+  const dim3 grid((unsigned)((cols + kNormalsFitTileCols - 1) / kNormalsFitTileCols),
+                  (unsigned)((rows + kNormalsFitTileRows - 1) / kNormalsFitTileRows));
+  hipStream_t stream = pm_internal::stream(h);
+#ifdef PM_TUNING
+  static const bool runtime_radius = pm::tune_env("PM_NORMALS_FIT_RUNTIME_RADIUS") != nullptr;
+  if (runtime_radius) {
+    hipLaunchKernelGGL(k_normals_fit_any, grid, dim3(kNormalsFitTileCols, kNormalsFitTileRows), 0, stream, a);
+    return launch_check(h, "normals fit");
+  }
+#endif
+  switch (fit->radius) {
+    case 1: launch_normals_fit<1>(a, grid, stream); break;
+    case 2: launch_normals_fit<2>(a, grid, stream); break;
+    case 3: launch_normals_fit<3>(a, grid, stream); break;
+    case 4: launch_normals_fit<4>(a, grid, stream); break;
+    case 5: launch_normals_fit<5>(a, grid, stream); break;
+    case 6: launch_normals_fit<6>(a, grid, stream); break;
+    default: launch_normals_fit<7>(a, grid, stream); break;
+  }
+  return launch_check(h, "normals fit");
+}
+
+void pm_debug_normals_fit_constants(int* tile_cols, int* tile_rows, int* pixels_per_thread) {
+  if (tile_cols) *tile_cols = kNormalsFitTileCols;
+  if (tile_rows) *tile_rows = kNormalsFitTileRows;
+  if (pixels_per_thread) *pixels_per_thread = 1;
 }
 
 // Host only: Bouguet's construction (see pm/imaging.h).

@@ -343,6 +343,28 @@ PointCloud MakePointCloud(const core::Image<float>& disp, const StereoModel& mod
   return pc;
 }
 
+core::Image<core::Vec3f> DisparityNormals(const core::Image<float>& disp, const StereoModel& model, const NormalsFit& fit,
+                                          core::Image<uint8_t>* support) {
+  if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("DisparityNormals: empty map");
+  std::lock_guard<std::mutex> lock(g_mutex);
+  pm_handle* h = Context();
+  core::Image<core::Vec3f> out(disp.rows, disp.cols);
+  const size_t px = (size_t)disp.rows * disp.cols;
+  DeviceBuffer d_in(h, Bytes(disp)), d_out(h, Bytes(out)), d_sup(h, support ? px : 0);
+  d_in.Upload(disp.data(), Bytes(disp));
+  const pm_cloud_camera cam = CloudCamera(model);
+  const pm_normals_fit f = {fit.radius, fit.max_diff, fit.min_support};
+  Check(pm_disparity_normals(h, &cam, &f, d_in.as<float>(), disp.rows, disp.cols, d_out.as<float>(), nullptr,
+                             support ? d_sup.as<uint8_t>() : nullptr),
+        "pm_disparity_normals");
+  d_out.Download(out.data(), Bytes(out));
+  if (support) {
+    if (support->rows != disp.rows || support->cols != disp.cols) support->create(disp.rows, disp.cols);
+    d_sup.Download(support->data(), px);
+  }
+  return out;
+}
+
 core::Image<core::Vec3f> PlaneNormals(pm::PatchmatchGpu& matcher, const StereoModel& model, int rows, int cols,
                                       const core::Image<float>* disp_l) {
   pm_handle* h = matcher.handle();

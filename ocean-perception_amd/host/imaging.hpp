@@ -111,6 +111,17 @@ PointCloud MakePointCloud(const core::Image<float>& disp, const StereoModel& mod
 // pm_planes_normals refuses (a scalar-mode matcher, no match yet, another size).
 core::Image<core::Vec3f> PlaneNormals(pm::PatchmatchGpu& matcher, const StereoModel& model, int rows, int cols,
                                       const core::Image<float>* disp_l = nullptr);
+// Any map, PM_MODE_SCALAR's included (it keeps no slopes): the organised unit normals of a least-squares plane fitted per
+// pixel over a (2 radius + 1)^2 window (pm/imaging.h: pm_disparity_normals; definition: tests/normals_fit_ref.py), the input
+// MakePointCloud takes as `normals`.  (0, 0, 0) where the map is not > 0 and where the fit has no support.
+struct NormalsFit {  // pm_normals_fit
+  int radius = 5;       // 1..7
+  float max_diff = 1.f; // a tap counts iff its disparity is > 0 and within max_diff of the centre's (edge-aware)
+  int min_support = 9;  // 3..(2 radius + 1)^2 counting taps, not collinear, or there is no fit
+};
+// support: the counting taps per pixel, where it is asked for.  Throws std::runtime_error where pm_disparity_normals refuses.
+core::Image<core::Vec3f> DisparityNormals(const core::Image<float>& disp, const StereoModel& model,
+                                          const NormalsFit& fit = NormalsFit(), core::Image<uint8_t>* support = nullptr);
 
 }  // namespace imaging
 }  // namespace bm

@@ -44,6 +44,7 @@ EXPORTS = [
     "pm_rectify_u8", "pm_rectify_map", "pm_match_raw_device", "pm_stereo_rectify",
     "pm_rectify_bgr8", "pm_match_raw_bgr_device",
     "pm_backproject", "pm_planes_normals", "pm_point_cloud", "pm_debug_cloud_constants",
+    "pm_disparity_normals", "pm_debug_normals_fit_constants",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
     "pm_debug_sweep_plan",
     "pm_remove_background", "pm_mask_occlusions", "pm_foreground_texture_mask", "pm_sparse_init", "pm_corner_subpix", "pm_profile_enable", "pm_profile_read",
@@ -146,6 +147,17 @@ class PmCloudCamera(C.Structure):  # the rectified pinhole of the point-cloud st
 
 class PmCloudFilter(C.Structure):
     _fields_ = [("min_disp", C.c_float), ("max_range", C.c_float), ("stride", C.c_int)]
+
+
+class PmNormalsFit(C.Structure):  # the window of pm_disparity_normals
+    _fields_ = [("radius", C.c_int), ("max_diff", C.c_float), ("min_support", C.c_int)]
+
+
+def normals_fit_constants():
+    """pm_debug_normals_fit_constants: (tile columns, tile rows, pixels per thread) of pm_disparity_normals' launch."""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    load().pm_debug_normals_fit_constants(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
 
 
 def cloud_camera(values):
@@ -309,6 +321,10 @@ def load():
         getattr(lib, name).restype = C.c_int
     lib.pm_debug_cloud_constants.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.pm_debug_cloud_constants.restype = None
+    lib.pm_disparity_normals.argtypes = [vp, cam_p, C.POINTER(PmNormalsFit), vp, C.c_int, C.c_int, vp, vp, vp]
+    lib.pm_disparity_normals.restype = C.c_int
+    lib.pm_debug_normals_fit_constants.argtypes = [C.POINTER(C.c_int)] * 3
+    lib.pm_debug_normals_fit_constants.restype = None
     lib.pm_device_malloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     lib.pm_device_free.argtypes = [vp, vp]
     lib.pm_upload.argtypes = [vp, vp, vp, C.c_size_t]
@@ -796,6 +812,16 @@ class Engine:
                                             d_bgr8, rows, cols, capacity, d_xyz_out, d_normals_out, d_bgr8_out, d_index_out,
                                             d_count, C.byref(n) if host_count else None), "pm_point_cloud")
         return n.value if host_count else None
+
+    def disparity_normals(self, camera, d_disp, rows, cols, radius=5, max_diff=1.0, min_support=9, d_normals=None,
+                          d_planes=None, d_support=None):
+        """pm_disparity_normals (raw device addresses): the windowed plane fit of a disparity map -> unit normals
+        [rows][cols][3], planes [3][rows][cols] (a, b, z) and the support [rows][cols] bytes, each where given.  camera:
+        (fx, fy, cx, cy, baseline) or a PmCloudCamera; needed for d_normals only."""
+        c = cloud_camera(camera)
+        f = PmNormalsFit(radius, max_diff, min_support)
+        self._check(self.lib.pm_disparity_normals(self.h, C.byref(c) if c is not None else None, C.byref(f), d_disp, rows, cols,
+                                                  d_normals, d_planes, d_support), "pm_disparity_normals")
 
     def normalize(self, d_bgr, rows, cols, d_out):
         self._check(self.lib.pm_normalize(self.h, d_bgr, rows, cols, d_out), "pm_normalize")

@@ -1,0 +1,99 @@
+// normals_fit_host_main.cpp -- runs pm_disparity_normals' own code (csrc/pm_normals_fit_body.hpp: normals_fit_stage,
+// normals_fit_pixel<R>, normals_fit_store -- what every thread of k_normals_fit<R> runs) on the HOST, so that
+// tests/test_normals_fit.py can hold it to the definition (tests/normals_fit_ref.py) without a GPU and under
+// -fsanitize=address,undefined.  The map is walked tile by tile as the launch grid walks it; every tile is a heap allocation
+// of EXACTLY the floats a workgroup's LDS tile has at that radius, filled by the kernel's staging function, and every output
+// an allocation of exactly its bytes: a tap outside the staged halo, or a store outside the image, is reported.  Compiled
+// as HIP source with the host-only switch of hipcc and -ffp-contract=off.
+//   normals_fit_host_main <dir>
+// <dir> holds .npy dumps (numpy's format, version 1, C order, little endian; the header is skipped and the payload size
+// checked): params.npy (float64: rows, cols, fx, fy, cx, cy, baseline, radius, max_diff, min_support, shift), disp.npy
+// (float32 [rows][cols]) and the definition's want_normals.npy (float32 [rows][cols][3]), want_planes.npy (float32
+// [3][rows][cols]), want_support.npy (uint8 [rows][cols]).  shift: d_normals starts `shift` floats into its allocation.
+// Exit status 0: every result equals its dump byte for byte; 1: a mismatch (named on stderr); 2: bad input.
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <string>
+
+#include "pm_normals_fit_body.hpp"
+
+static bool read_npy(const std::string& path, size_t bytes, std::unique_ptr<uint8_t[]>* out) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return false;
+  uint8_t head[10];
+  bool ok = fread(head, 1, 10, f) == 10 && !memcmp(head, "\x93NUMPY\x01", 7);
+  const size_t hlen = ok ? (size_t)head[8] | ((size_t)head[9] << 8) : 0;
+  ok = ok && fseek(f, 0, SEEK_END) == 0 && (size_t)ftell(f) == 10 + hlen + bytes && fseek(f, (long)(10 + hlen), SEEK_SET) == 0;
+  if (ok) {
+    out->reset(new uint8_t[bytes]);
+    ok = fread(out->get(), 1, bytes, f) == bytes;
+  }
+  fclose(f);
+  if (!ok) fprintf(stderr, "cannot read %zu payload bytes from %s\n", bytes, path.c_str());
+  return ok;
+}
+
+static int differ(const char* what, const void* got, const void* want, size_t bytes) {
+  if (!memcmp(got, want, bytes)) return 0;
+  const uint8_t* g = (const uint8_t*)got;
+  const uint8_t* w = (const uint8_t*)want;
+  size_t at = 0;
+  while (g[at] == w[at]) ++at;
+  fprintf(stderr, "%s differs from the definition at byte %zu of %zu\n", what, at, bytes);
+  return 1;
+}
+
+// the grid of k_normals_fit<R>, workgroup by workgroup, thread by thread
+template <int R>
+static void run(const pm::NormalsFitArgs& a) {
+  constexpr int pitch = pm::normals_fit_tile_pitch(R);
+  for (int y0 = 0; y0 < a.rows; y0 += pm::kNormalsFitTileRows)
+    for (int x0 = 0; x0 < a.cols; x0 += pm::kNormalsFitTileCols) {
+      std::unique_ptr<float[]> tile(new float[pm::normals_fit_tile_cells(R)]);
+      pm::normals_fit_stage(tile.get(), R, a.disp, a.rows, a.cols, x0, y0, 0, 1);
+      for (int ty = 0; ty < pm::kNormalsFitTileRows && y0 + ty < a.rows; ++ty)
+        for (int tx = 0; tx < pm::kNormalsFitTileCols && x0 + tx < a.cols; ++tx) {
+          const float* centre = tile.get() + (ty + R) * pitch + tx + R;
+          pm::normals_fit_store(a, x0 + tx, y0 + ty, pm::normals_fit_pixel<R>(centre, pitch, R, a.max_diff, a.min_support));
+        }
+    }
+}
+
+int main(int argc, char** argv) {
+  if (argc != 2) return 2;
+  const std::string dir = std::string(argv[1]) + "/";
+  std::unique_ptr<uint8_t[]> raw;
+  if (!read_npy(dir + "params.npy", 11 * sizeof(double), &raw)) return 2;
+  double p[11];
+  memcpy(p, raw.get(), sizeof p);
+  const int rows = (int)p[0], cols = (int)p[1], radius = (int)p[7], min_support = (int)p[9], shift = (int)p[10];
+  const pm_cloud_camera camera = {p[2], p[3], p[4], p[5], p[6]};
+  const float max_diff = (float)p[8];
+  if (rows < 1 || cols < 1 || radius < 1 || radius > pm::kNormalsFitMaxRadius || shift < 0) return 2;
+  const size_t px = (size_t)rows * cols;
+  std::unique_ptr<uint8_t[]> disp_b, want_normals, want_planes, want_support;
+  if (!read_npy(dir + "disp.npy", 4 * px, &disp_b) || !read_npy(dir + "want_normals.npy", 12 * px, &want_normals) ||
+      !read_npy(dir + "want_planes.npy", 12 * px, &want_planes) || !read_npy(dir + "want_support.npy", px, &want_support))
+    return 2;
+  std::unique_ptr<float[]> normals(new float[shift + 3 * px]), planes(new float[3 * px]);
+  std::unique_ptr<uint8_t[]> support(new uint8_t[px]);
+  for (int k = 0; k < shift; ++k) normals[k] = -77.f;
+  const pm::NormalsFitArgs a = {pm::cloud_cam(camera), (const float*)disp_b.get(), rows,         cols,         radius,
+                                max_diff,              min_support,                 normals.get() + shift, planes.get(), support.get()};
+  switch (radius) {
+    case 1: run<1>(a); break;
+    case 2: run<2>(a); break;
+    case 3: run<3>(a); break;
+    case 4: run<4>(a); break;
+    case 5: run<5>(a); break;
+    case 6: run<6>(a); break;
+    default: run<7>(a); break;
+  }
+  int bad = 0;
+  bad |= differ("normals", normals.get() + shift, want_normals.get(), 12 * px);
+  bad |= differ("planes", planes.get(), want_planes.get(), 12 * px);
+  bad |= differ("support", support.get(), want_support.get(), px);
+  for (int k = 0; k < shift; ++k) bad |= normals[k] != -77.f;
+  return bad ? 1 : 0;
+}

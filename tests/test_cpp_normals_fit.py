@@ -1,0 +1,67 @@
+"""DisparityNormals of the C++ host mirror (ocean-perception_amd/host/imaging.hpp), compiled with plain g++ and driven like
+a host caller (tests/cpp/normals_fit_main.cpp): what it returns is, byte for byte, what the definition
+(tests/normals_fit_ref.py) says for the same map."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import normals_fit_ref as NR
+from conftest import ROOT
+
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import fuzz_cloud as FC  # noqa: E402
+import fuzz_normals as FN  # noqa: E402
+
+PKG = os.path.join(ROOT, "ocean-perception_amd")
+LIBDIR = os.path.join(PKG, "lib")
+ROWS, COLS = 37, 53
+CAMERA = (412.7, 398.3, COLS // 2 - 0.3, ROWS // 2 + 0.4, 0.12)  # what normals_fit_main.cpp sets
+
+
+@pytest.fixture(scope="module")
+def fit_exe(tmp_path_factory):
+    out = tmp_path_factory.mktemp("cppfit") / "normals_fit_main"
+    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
+           "-I" + os.path.join(PKG, "host"), os.path.join(ROOT, "tests", "cpp", "normals_fit_main.cpp"), "-L" + LIBDIR,
+           "-lvehicle_pm_gpu", "-Wl,-rpath," + LIBDIR, "-o", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return str(out)
+
+
+def _input(tmp_path):
+    disp = FN.run_map(np.random.default_rng(23), ROWS, COLS, valid=0.9, special=0.05)
+    disp.tofile(os.path.join(tmp_path, "disp.f32"))
+    return disp
+
+
+def _has_gpu():
+    try:
+        import torch
+        return torch.cuda.is_available()
+    except Exception:
+        return False
+
+
+@pytest.mark.skipif(_has_gpu(), reason="checks the no-GPU failure mode")
+def test_fit_mirror_builds_with_gxx_and_fails_loudly_without_gpu(fit_exe, tmp_path):
+    _input(tmp_path)
+    r = subprocess.run([fit_exe, str(tmp_path), str(ROWS), str(COLS)], capture_output=True, text=True)
+    assert r.returncode == 10 and "no HIP device" in r.stdout
+
+
+@pytest.mark.gpu
+def test_fit_mirror_gives_the_bytes_of_the_definition(fit_exe, tmp_path):
+    disp = _input(tmp_path)
+    res = subprocess.run([fit_exe, str(tmp_path), str(ROWS), str(COLS)], capture_output=True, text=True)
+    assert res.returncode == 0 and "refused: pm_disparity_normals" in res.stdout and "radius" in res.stdout, res.stdout + res.stderr
+    load = lambda name, dt, shape: np.fromfile(os.path.join(tmp_path, name), dt).reshape(shape)
+    want = NR.disparity_normals(disp, CAMERA, 5, 1.0, 9)
+    assert np.array_equal(FC.bits(load("normals.f32", np.float32, (ROWS, COLS, 3))), FC.bits(want["normals"]))
+    assert np.array_equal(load("support.u8", np.uint8, (ROWS, COLS)), want["support"])
+    assert want["valid"].sum() > 1000 and (want["normals"] != 0).any()
+    want = NR.disparity_normals(disp, CAMERA, 2, 30.0, 3)
+    assert np.array_equal(FC.bits(load("normals_r2.f32", np.float32, (ROWS, COLS, 3))), FC.bits(want["normals"]))
