@@ -314,6 +314,38 @@ int pm_disparity_normals(pm_handle* h, const pm_cloud_camera* camera, const pm_n
                          float* d_planes    /* [3][rows][cols]: a, b, z, may be NULL */,
                          uint8_t* d_support /* [rows][cols], may be NULL */);
 
+/* ---- speckle filter: the map's connected regions of similar disparity; small ones are set to 0 ------------------------
+ * What it is for: between Match() and the stages above.  The cross-check and pm_remove_background leave small islands of
+ * wrong disparity in weakly textured water; pm_point_cloud turns each into a cluster of floating points and
+ * pm_disparity_normals fits planes through it.  The step is cv::filterSpeckles'; the labels and sizes are outputs too, since
+ * a meshing consumer can use the segments.  It fills nothing and smooths nothing.  Held to its CPU definition
+ * (tests/speckle_ref.py) BIT FOR BIT:
+ *   valid      a pixel is valid iff d > 0: 0, -0.0, negatives and NaN are not, +inf is.
+ *   edge       two 4-neighbours p, q are joined iff both are valid and fabs((double)d(p) - (double)d(q)) <= (double)max_diff
+ *              in binary64.  A NaN difference never joins, so a +inf pixel is a component of its own.  No diagonals.
+ *   component  the transitive closure of the edges (a slow ramp is one component, as in OpenCV).
+ *   d_out      a valid pixel whose component has at most max_size pixels becomes +0.0f; every other pixel, invalid ones
+ *              included, keeps its input bits.  d_out may equal d_disp.  max_size == 0 removes nothing.
+ *   d_labels   the smallest linear index y * cols + x of the pixel's component, -1 where the pixel is invalid.  Labels are
+ *              those of the INPUT map, removed components included.
+ *   d_sizes    the component's pixel count, 0 where the pixel is invalid.
+ *   removed    the number of pixels set to 0, to *d_removed (device) and *removed (host), also where d_out is NULL.
+ * Every output is optional, but at least one must be given; each is a pure function of the input (across workgroups only
+ * integer min and integer add are used, so nothing depends on the order in which atomics arrive).  Valid in every mode of
+ * the handle: it reads a map, not the handle's state.  Images smaller than a tile, or no multiple of it, are legal.
+ * A non-NULL `removed` synchronises the stream like pm_point_cloud's `count`; with removed == NULL the call only enqueues.
+ * Four launches behind a 16-byte memset (label 64 x 16 tiles in LDS, unite across tile borders, flatten, apply), none of
+ * which waits for another workgroup.  Scratch (8 bytes per pixel: working labels and root sizes, and 16 bytes for the count)
+ * is allocated on first use, reused, and released with the handle; growing it synchronises the stream, so a size must
+ * have run once before it is captured.  The serpentine-shaped worst case takes longer than a natural map.
+ * PM_ERR_INVALID_ARG, with pm_last_error naming the argument and nothing enqueued: a null filter or d_disp; no output at
+ * all; a max_diff that is not finite or < 0; max_size < 0; rows or cols < 1.  PM_ERR_SIZE: more than 2^31 - 1 pixels. */
+typedef struct pm_speckle_filter { float max_diff; int max_size; } pm_speckle_filter;
+int pm_filter_speckles(pm_handle* h, const pm_speckle_filter* filter, const float* d_disp, int rows, int cols,
+                       float* d_out /* may be NULL, may equal d_disp */, int32_t* d_labels /* may be NULL */,
+                       int32_t* d_sizes /* may be NULL */, int* d_removed /* device, may be NULL */,
+                       int* removed /* host, may be NULL */);
+
 /* ---- device buffers for host code that does not include HIP (host/imaging.hpp uses them) ------------------
  * pm_device_malloc / pm_device_free wrap hipMalloc / hipFree on the handle's device; pm_upload / pm_download are
  * stream-ordered copies on the handle's stream from / to pageable host memory (pm_download returns after the

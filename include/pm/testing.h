@@ -66,6 +66,11 @@ void pm_debug_cloud_constants(int* items_per_block, int* blocks_per_scan_pass);
  * handle, no device. */
 void pm_debug_normals_fit_constants(int* tile_cols, int* tile_rows, int* pixels_per_thread);
 
+/* ---- pm_filter_speckles' launch constants (csrc/pm_speckle_body.hpp) ------------------------------------------------------
+ * tile_cols x tile_rows: the pixels one workgroup labels in LDS; components are united across the borders of these tiles
+ * by a launch of its own.  Tests place shapes and components at tile borders and corners with them.  No handle, no device. */
+void pm_debug_speckle_constants(int* tile_cols, int* tile_rows);
+
 /* ---- the row-tiled driver's device discipline, provable on ONE GPU ------------------------------------------------
  * pm_tiled_create with the bands accounted to LOGICAL devices: band k lives on logical_devices[k] (>= 0; several bands
  * may share one) while every HIP call still goes to the physical device of the band's handle.  Such a plan logs every

@@ -21,6 +21,7 @@
 #include "pm_internal.hpp"
 #include "pm_normals_fit.hpp"
 #include "pm_rectify.hpp"
+#include "pm_speckle.hpp"
 #include "pm_tune.hpp"
 
 using namespace pm;
@@ -49,6 +50,9 @@ struct ImagingState {
   DevBuf<uint8_t> rect_buf;
   // pm_point_cloud: [0] the count, [1 ..] one word per block of kCloudBlock items: its count, then its offset
   DevBuf<int> cloud_blocks;
+  // pm_filter_speckles: [0] the removed count (kSpeckleHeader words, cleared per call), then the working labels and the
+  // root sizes, one word per pixel each
+  DevBuf<int> speckle_buf;
 };
 
 #define PM_HIP(h, call)                                                                                     \
@@ -990,6 +994,75 @@ void pm_debug_normals_fit_constants(int* tile_cols, int* tile_rows, int* pixels_
   if (tile_cols) *tile_cols = kNormalsFitTileCols;
   if (tile_rows) *tile_rows = kNormalsFitTileRows;
   if (pixels_per_thread) *pixels_per_thread = 1;
+}
+
+// ---- speckle filter: connected components of similar disparity (pm_speckle.hpp) ------------------------------------------
+namespace {
+constexpr size_t kSpeckleHeader = 4;  // words in front of the labels: the counter's 16 bytes, cleared whole
+}
+
+int pm_filter_speckles(pm_handle* h, const pm_speckle_filter* filter, const float* d_disp, int rows, int cols, float* d_out,
+                       int32_t* d_labels, int32_t* d_sizes, int* d_removed, int* removed) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_filter_speckles";
+  if (!filter || !d_disp) {
+    set_err(h, "%s: null %s", what, !filter ? "filter" : "d_disp");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (!d_out && !d_labels && !d_sizes && !d_removed && !removed) {
+    set_err(h, "%s: no output (d_out, d_labels, d_sizes, d_removed and removed are all null)", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (!std::isfinite(filter->max_diff) || filter->max_diff < 0.f) {
+    set_err(h, "%s: max_diff must be finite and >= 0", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (filter->max_size < 0) {
+    set_err(h, "%s: max_size %d must be >= 0", what, filter->max_size);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (rows < 1 || cols < 1) {
+    set_err(h, "%s: empty image (%dx%d)", what, cols, rows);
+    return PM_ERR_INVALID_ARG;
+  }
+  if ((long long)rows * cols > INT32_MAX) {
+    set_err(h, "%s: %dx%d pixels exceed a 32-bit pixel index", what, cols, rows);
+    return PM_ERR_SIZE;
+  }
+  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
+  ImagingState* st = state_of(h);
+  if (!st) {
+    set_err(h, "%s: out of host memory", what);
+    return PM_ERR_NOMEM;
+  }
+  const int pixels = rows * cols;
+  hipStream_t stream = pm_internal::stream(h);
+  PM_HIP(h, st->speckle_buf.reserve(sizeof(int) * (kSpeckleHeader + 2 * (size_t)pixels), stream));
+  int* d_total = st->speckle_buf.get();
+  const SpeckleArgs a = {d_disp, rows, cols, filter->max_diff, d_total + kSpeckleHeader, d_total + kSpeckleHeader + pixels};
+  const SpeckleOut o = {d_out, d_labels, d_sizes, filter->max_size};
+  const int tiles_x = speckle_tiles_x(cols);
+  const long long tiles = (long long)tiles_x * speckle_tiles_y(rows), items = speckle_merge_items(rows, cols);
+  const unsigned per_pixel = (unsigned)(((long long)pixels + kSpeckleBlock - 1) / kSpeckleBlock);
+  PM_HIP(h, hipMemsetAsync(d_total, 0, sizeof(int) * kSpeckleHeader, stream));
+  hipLaunchKernelGGL(k_speckle_local, dim3((unsigned)tiles), dim3(kSpeckleTileCols, kSpeckleTileRows), 0, stream, a, tiles_x);
+  if (items > 0)
+    hipLaunchKernelGGL(k_speckle_merge, dim3((unsigned)((items + kSpeckleBlock - 1) / kSpeckleBlock)), dim3(kSpeckleBlock), 0,
+                       stream, a, items);
+  hipLaunchKernelGGL(k_speckle_flatten, dim3(per_pixel), dim3(kSpeckleBlock), 0, stream, a, pixels);
+  hipLaunchKernelGGL(k_speckle_apply, dim3(per_pixel), dim3(kSpeckleBlock), 0, stream, a, o, pixels, d_total);
+  if (int rc = launch_check(h, "speckle filter")) return rc;
+  if (d_removed) PM_HIP(h, hipMemcpyAsync(d_removed, d_total, sizeof(int), hipMemcpyDeviceToDevice, stream));
+  if (removed) {
+    PM_HIP(h, hipMemcpyAsync(removed, d_total, sizeof(int), hipMemcpyDeviceToHost, stream));
+    PM_HIP(h, hipStreamSynchronize(stream));
+  }
+  return PM_OK;
+}
+
+void pm_debug_speckle_constants(int* tile_cols, int* tile_rows) {
+  if (tile_cols) *tile_cols = kSpeckleTileCols;
+  if (tile_rows) *tile_rows = kSpeckleTileRows;
 }
 
 // Host only: Bouguet's construction (see pm/imaging.h).

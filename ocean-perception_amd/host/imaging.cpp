@@ -365,6 +365,27 @@ core::Image<core::Vec3f> DisparityNormals(const core::Image<float>& disp, const 
   return out;
 }
 
+core::Image<float> FilterSpeckles(const core::Image<float>& disp, const SpeckleFilter& filter, core::Image<int32_t>* labels,
+                                  int* removed) {
+  if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("FilterSpeckles: empty map");
+  std::lock_guard<std::mutex> lock(g_mutex);
+  pm_handle* h = Context();
+  core::Image<float> out(disp.rows, disp.cols);
+  const size_t px = (size_t)disp.rows * disp.cols;
+  DeviceBuffer d_map(h, Bytes(disp)), d_lab(h, labels ? sizeof(int32_t) * px : 0);
+  d_map.Upload(disp.data(), Bytes(disp));
+  const pm_speckle_filter f = {filter.max_diff, filter.max_size};
+  Check(pm_filter_speckles(h, &f, d_map.as<float>(), disp.rows, disp.cols, d_map.as<float>(),  // in place on the device
+                           labels ? d_lab.as<int32_t>() : nullptr, nullptr, nullptr, removed),
+        "pm_filter_speckles");
+  d_map.Download(out.data(), Bytes(out));
+  if (labels) {
+    if (labels->rows != disp.rows || labels->cols != disp.cols) labels->create(disp.rows, disp.cols);
+    d_lab.Download(labels->data(), sizeof(int32_t) * px);
+  }
+  return out;
+}
+
 core::Image<core::Vec3f> PlaneNormals(pm::PatchmatchGpu& matcher, const StereoModel& model, int rows, int cols,
                                       const core::Image<float>* disp_l) {
   pm_handle* h = matcher.handle();

@@ -122,6 +122,17 @@ struct NormalsFit {  // pm_normals_fit
 // support: the counting taps per pixel, where it is asked for.  Throws std::runtime_error where pm_disparity_normals refuses.
 core::Image<core::Vec3f> DisparityNormals(const core::Image<float>& disp, const StereoModel& model,
                                           const NormalsFit& fit = NormalsFit(), core::Image<uint8_t>* support = nullptr);
+// Between Match() and the stages above: the map with every connected region of similar disparity of at most max_size
+// pixels set to 0 (pm/imaging.h: pm_filter_speckles; definition: tests/speckle_ref.py).  4-neighbours are joined iff both
+// are > 0 and differ by at most max_diff; nothing is filled or smoothed.
+struct SpeckleFilter {  // pm_speckle_filter
+  float max_diff = 1.f;  // finite, >= 0
+  int max_size = 100;    // >= 0; 0 removes nothing
+};
+// labels: the smallest index y * cols + x of each pixel's component in the INPUT map (-1 where it is not > 0); removed: the
+// number of pixels set to 0; each where it is asked for.  Throws std::runtime_error where pm_filter_speckles refuses.
+core::Image<float> FilterSpeckles(const core::Image<float>& disp, const SpeckleFilter& filter = SpeckleFilter(),
+                                  core::Image<int32_t>* labels = nullptr, int* removed = nullptr);
 
 }  // namespace imaging
 }  // namespace bm

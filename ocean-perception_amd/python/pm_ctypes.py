@@ -45,6 +45,7 @@ EXPORTS = [
     "pm_rectify_bgr8", "pm_match_raw_bgr_device",
     "pm_backproject", "pm_planes_normals", "pm_point_cloud", "pm_debug_cloud_constants",
     "pm_disparity_normals", "pm_debug_normals_fit_constants",
+    "pm_filter_speckles", "pm_debug_speckle_constants",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
     "pm_debug_sweep_plan",
     "pm_remove_background", "pm_mask_occlusions", "pm_foreground_texture_mask", "pm_sparse_init", "pm_corner_subpix", "pm_profile_enable", "pm_profile_read",
@@ -158,6 +159,17 @@ def normals_fit_constants():
     a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
     load().pm_debug_normals_fit_constants(C.byref(a), C.byref(b), C.byref(c))
     return a.value, b.value, c.value
+
+
+class PmSpeckleFilter(C.Structure):  # pm_filter_speckles
+    _fields_ = [("max_diff", C.c_float), ("max_size", C.c_int)]
+
+
+def speckle_constants():
+    """pm_debug_speckle_constants: (tile columns, tile rows) of pm_filter_speckles' tile launch."""
+    a, b = C.c_int(0), C.c_int(0)
+    load().pm_debug_speckle_constants(C.byref(a), C.byref(b))
+    return a.value, b.value
 
 
 def cloud_camera(values):
@@ -325,6 +337,10 @@ def load():
     lib.pm_disparity_normals.restype = C.c_int
     lib.pm_debug_normals_fit_constants.argtypes = [C.POINTER(C.c_int)] * 3
     lib.pm_debug_normals_fit_constants.restype = None
+    lib.pm_filter_speckles.argtypes = [vp, C.POINTER(PmSpeckleFilter), vp, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(C.c_int)]
+    lib.pm_filter_speckles.restype = C.c_int
+    lib.pm_debug_speckle_constants.argtypes = [C.POINTER(C.c_int)] * 2
+    lib.pm_debug_speckle_constants.restype = None
     lib.pm_device_malloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     lib.pm_device_free.argtypes = [vp, vp]
     lib.pm_upload.argtypes = [vp, vp, vp, C.c_size_t]
@@ -822,6 +838,17 @@ class Engine:
         f = PmNormalsFit(radius, max_diff, min_support)
         self._check(self.lib.pm_disparity_normals(self.h, C.byref(c) if c is not None else None, C.byref(f), d_disp, rows, cols,
                                                   d_normals, d_planes, d_support), "pm_disparity_normals")
+
+    def filter_speckles(self, d_disp, rows, cols, max_diff=1.0, max_size=100, d_out=None, d_labels=None, d_sizes=None,
+                        d_removed=None, host_count=False):
+        """pm_filter_speckles (raw device addresses): components of at most max_size pixels become 0 in d_out (which may be
+        d_disp); d_labels / d_sizes [rows][cols] int32, d_removed one int, each where given.  host_count: also return the
+        removed count (this synchronises the stream); otherwise None."""
+        f = PmSpeckleFilter(max_diff, max_size)
+        n = C.c_int(-1)
+        self._check(self.lib.pm_filter_speckles(self.h, C.byref(f), d_disp, rows, cols, d_out, d_labels, d_sizes, d_removed,
+                                                C.byref(n) if host_count else None), "pm_filter_speckles")
+        return n.value if host_count else None
 
     def normalize(self, d_bgr, rows, cols, d_out):
         self._check(self.lib.pm_normalize(self.h, d_bgr, rows, cols, d_out), "pm_normalize")
