@@ -346,6 +346,57 @@ int pm_filter_speckles(pm_handle* h, const pm_speckle_filter* filter, const floa
                        int32_t* d_sizes /* may be NULL */, int* d_removed /* device, may be NULL */,
                        int* removed /* host, may be NULL */);
 
+/* ---- grid mesh: the triangle mesh of a disparity map's stride grid, vertices and triangles compacted on the device ----
+ * What it is for: the surface behind pm_point_cloud.  Every 2x2 cell of the grid becomes up to two triangles unless a depth
+ * edge runs through it; the vertex streams are pm_point_cloud's.  Held to its CPU definition (tests/mesh_ref.py) BIT FOR BIT:
+ *   grid       pm_cloud_filter's stride grid: sub_rows = ceil(rows / stride), sub_cols = ceil(cols / stride); item (xs, ys) is
+ *              pixel (xs * stride, ys * stride) and COUNTS iff pm_point_cloud would count that pixel (d > 0, d >= min_disp,
+ *              the max_range test on the point's binary32 Z).
+ *   edge       two items p, q pass iff both count and fabs((double)d(p) - (double)d(q)) <= (double)max_diff in binary64:
+ *              pm_filter_speckles' rule.  A NaN difference (+inf against +inf) never passes.
+ *   cell       (xs, ys) with xs < sub_cols - 1 and ys < sub_rows - 1 has the corners 00 = (xs, ys), 10 = (xs + 1, ys),
+ *              01 = (xs, ys + 1), 11 = (xs + 1, ys + 1); n of them count.  n == 4: diagonal 1 (10-01) iff
+ *              fabs(d10 - d01) < fabs(d00 - d11) (binary64, strict; a tie or a NaN gives diagonal 0, 00-11).  n == 3:
+ *              diagonal 1 if 00 or 11 is the missing corner, diagonal 0 if 10 or 01 is.  n < 3: no triangle.
+ *                diagonal 0:  T0 = (00, 01, 11)  T1 = (00, 11, 10)        diagonal 1:  T0 = (00, 01, 10)  T1 = (10, 01, 11)
+ *              A triangle is EMITTED iff its three corners count and its three edges pass.  In this corner order
+ *              (P1 - P0) x (P2 - P0) of the points has a negative Z (fx, fy, baseline > 0): the triangle faces the camera,
+ *              like the normals of pm_planes_normals.
+ *   vertices   PM_MESH_VERTICES_ALL: every counting item; the vertex streams are then EXACTLY pm_point_cloud's outputs for
+ *              the same arguments.  PM_MESH_VERTICES_REFERENCED: only the counting items that are a corner of an emitted
+ *              triangle (a function of the item's 3x3 neighbourhood), so the mesh has no floating points.  The k-th vertex
+ *              in row-major grid order gets slot k of d_xyz_out, d_normals_out, d_bgr8_out and d_index_out (y * cols + x of
+ *              the pixel), as in pm_point_cloud.
+ *   triangles  cells in row-major order, T0 before T1 inside a cell; the j-th emitted triangle goes to slot j of d_tri_out
+ *              as three int32 vertex slots in the order above.  The set of emitted triangles does not depend on
+ *              options->vertices, only their indices do.
+ *   counts     counts[0] / d_counts[0] = vertices, [1] = triangles, EVEN BEYOND the capacities; exactly the first
+ *              vertex_capacity vertices and tri_capacity triangles are written and nothing behind them.  Triangle indices
+ *              ALWAYS use the untruncated vertex numbering: vertex_count > vertex_capacity tells the caller that written
+ *              triangles may name vertices that were not written.
+ * Every output is optional; both capacities may be 0 and the call then only counts.  A grid with fewer than two rows or
+ * columns is legal and has no triangles.  Valid in every mode of the handle: it reads a map, not the handle's state.  It
+ * enqueues on the handle's stream; a non-NULL `counts` synchronises it like pm_point_cloud's `count`.
+ * Five small launches, none of which waits for another workgroup (per-block vertex and triangle counts by wavefront ballot
+ * over an LDS tile of three grid rows, two launches of pm_point_cloud's offsets kernel, the vertex scatter that also writes
+ * an organised slot map, the triangle scatter that reads it); the order comes from that arithmetic, never from atomics.
+ * Scratch (8 bytes per 256 grid items of a row, 4 bytes per grid item for the slot map, 8 for the counts) is ONE allocation,
+ * made on first use, reused, and released with the handle; growing it synchronises the stream, so a size must have run
+ * once before it is captured.
+ * PM_ERR_INVALID_ARG, with pm_last_error naming the argument and nothing enqueued: everything pm_point_cloud refuses (with
+ * either capacity < 0); null options; a max_diff that is not finite or < 0; a `vertices` outside the enum.  PM_ERR_SIZE as
+ * for pm_point_cloud, and where 2 * (sub_rows - 1) * (sub_cols - 1) exceeds 2^31 - 1. */
+typedef enum pm_mesh_vertices { PM_MESH_VERTICES_ALL = 0, PM_MESH_VERTICES_REFERENCED = 1 } pm_mesh_vertices;
+typedef struct pm_mesh_options { float max_diff; int vertices; } pm_mesh_options;
+int pm_grid_mesh(pm_handle* h, const pm_cloud_camera* camera, const pm_cloud_filter* filter,
+                 const pm_mesh_options* options, const float* d_disp,
+                 const float* d_normals /* organised, may be NULL */, const uint8_t* d_bgr8 /* may be NULL */,
+                 int rows, int cols, int vertex_capacity, int tri_capacity,
+                 float* d_xyz_out, float* d_normals_out, uint8_t* d_bgr8_out, int32_t* d_index_out,
+                 int32_t* d_tri_out /* [tri_capacity][3], may be NULL */,
+                 int* d_counts /* device int[2]: vertices, triangles; may be NULL */,
+                 int* counts /* host int[2]; may be NULL; non-NULL synchronises like pm_point_cloud's count */);
+
 /* ---- device buffers for host code that does not include HIP (host/imaging.hpp uses them) ------------------
  * pm_device_malloc / pm_device_free wrap hipMalloc / hipFree on the handle's device; pm_upload / pm_download are
  * stream-ordered copies on the handle's stream from / to pageable host memory (pm_download returns after the

@@ -71,6 +71,13 @@ void pm_debug_normals_fit_constants(int* tile_cols, int* tile_rows, int* pixels_
  * by a launch of its own.  Tests place shapes and components at tile borders and corners with them.  No handle, no device. */
 void pm_debug_speckle_constants(int* tile_cols, int* tile_rows);
 
+/* ---- pm_grid_mesh's launch constants (csrc/pm_mesh.hpp) ----------------------------------------------------------------
+ * items_per_block: the items of ONE grid row a block of the count / scatter launches takes, so a grid has
+ * sub_rows * ceil(sub_cols / items_per_block) blocks; blocks_per_scan_pass: the block counts pm_point_cloud's offsets kernel
+ * turns into offsets per pass.  A grid with more blocks than that makes both of the mesh's scans loop: the size a test
+ * needs to reach their carries.  No handle, no device. */
+void pm_debug_mesh_constants(int* items_per_block, int* blocks_per_scan_pass);
+
 /* ---- the row-tiled driver's device discipline, provable on ONE GPU ------------------------------------------------
  * pm_tiled_create with the bands accounted to LOGICAL devices: band k lives on logical_devices[k] (>= 0; several bands
  * may share one) while every HIP call still goes to the physical device of the band's handle.  Such a plan logs every

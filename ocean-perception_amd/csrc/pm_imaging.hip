@@ -19,6 +19,7 @@
 #include "pm_guided.hpp"
 #include "pm_imaging.hpp"
 #include "pm_internal.hpp"
+#include "pm_mesh.hpp"
 #include "pm_normals_fit.hpp"
 #include "pm_rectify.hpp"
 #include "pm_speckle.hpp"
@@ -53,6 +54,9 @@ struct ImagingState {
   // pm_filter_speckles: [0] the removed count (kSpeckleHeader words, cleared per call), then the working labels and the
   // root sizes, one word per pixel each
   DevBuf<int> speckle_buf;
+  // pm_grid_mesh: [0] the vertex count, [1] the triangle count, then one word per block of kMeshBlock items for each of
+  // the two (its count, then its offset), then the organised slot map, one word per grid item
+  DevBuf<int> mesh_buf;
 };
 
 #define PM_HIP(h, call)                                                                                     \
@@ -1063,6 +1067,96 @@ int pm_filter_speckles(pm_handle* h, const pm_speckle_filter* filter, const floa
 void pm_debug_speckle_constants(int* tile_cols, int* tile_rows) {
   if (tile_cols) *tile_cols = kSpeckleTileCols;
   if (tile_rows) *tile_rows = kSpeckleTileRows;
+}
+
+// ---- grid mesh: vertices and triangles of a disparity map's stride grid (pm_mesh.hpp) -------------------------------------
+int pm_grid_mesh(pm_handle* h, const pm_cloud_camera* camera, const pm_cloud_filter* filter, const pm_mesh_options* options,
+                 const float* d_disp, const float* d_normals, const uint8_t* d_bgr8, int rows, int cols, int vertex_capacity,
+                 int tri_capacity, float* d_xyz_out, float* d_normals_out, uint8_t* d_bgr8_out, int32_t* d_index_out,
+                 int32_t* d_tri_out, int* d_counts, int* counts) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_grid_mesh";
+  if (int rc = check_cloud_camera(h, what, camera)) return rc;
+  if (!filter || !options || !d_disp) {
+    set_err(h, "%s: null %s", what, !filter ? "filter" : !options ? "options" : "d_disp");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (filter->stride < 1) {
+    set_err(h, "%s: stride %d must be >= 1", what, filter->stride);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (std::isnan(filter->min_disp) || !(filter->max_range >= 0.f)) {
+    set_err(h, "%s: min_disp must not be NaN and max_range must be >= 0 (0 = no limit)", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (!std::isfinite(options->max_diff) || options->max_diff < 0.f) {
+    set_err(h, "%s: max_diff must be finite and >= 0", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (options->vertices != PM_MESH_VERTICES_ALL && options->vertices != PM_MESH_VERTICES_REFERENCED) {
+    set_err(h, "%s: vertices %d is neither PM_MESH_VERTICES_ALL nor PM_MESH_VERTICES_REFERENCED", what, options->vertices);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (vertex_capacity < 0 || tri_capacity < 0) {
+    set_err(h, "%s: %s %d must be >= 0", what, vertex_capacity < 0 ? "vertex_capacity" : "tri_capacity",
+            vertex_capacity < 0 ? vertex_capacity : tri_capacity);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (d_normals_out && !d_normals) {
+    set_err(h, "%s: d_normals_out requested without d_normals", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (d_bgr8_out && !d_bgr8) {
+    set_err(h, "%s: d_bgr8_out requested without d_bgr8", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
+  const int stride = filter->stride;
+  const int sub_rows = (rows + stride - 1) / stride, sub_cols = (cols + stride - 1) / stride;
+  if (2 * ((long long)(sub_rows - 1) * (sub_cols - 1)) > INT32_MAX) {
+    set_err(h, "%s: the %dx%d grid has more than 2^31 - 1 possible triangles", what, sub_cols, sub_rows);
+    return PM_ERR_SIZE;
+  }
+  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
+  ImagingState* st = state_of(h);
+  if (!st) {
+    set_err(h, "%s: out of host memory", what);
+    return PM_ERR_NOMEM;
+  }
+  const MeshArgs a = {{cloud_cam(*camera), *filter, d_disp, rows, cols, sub_cols, (long long)sub_rows * sub_cols},
+                      sub_rows, options->max_diff, options->vertices == PM_MESH_VERTICES_REFERENCED};
+  const int blocks = sub_rows * mesh_segments(sub_cols);  // <= rows * ceil(cols / 256): far below 2^31 (check_cloud_shape)
+  hipStream_t stream = pm_internal::stream(h);
+  PM_HIP(h, st->mesh_buf.reserve(sizeof(int) * (2 + 2 * (size_t)blocks + (size_t)a.c.items), stream));
+  int* d_totals = st->mesh_buf.get();
+  int* d_vertex_blocks = d_totals + 2;
+  int* d_tri_blocks = d_vertex_blocks + blocks;
+  int32_t* d_slot_map = d_tri_blocks + blocks;
+  const bool want_vertices = vertex_capacity > 0 && (d_xyz_out || d_normals_out || d_bgr8_out || d_index_out);
+  const bool want_tris = tri_capacity > 0 && d_tri_out;
+  const CloudStreams s = {d_normals, d_bgr8, d_xyz_out, d_normals_out, d_bgr8_out, d_index_out, want_vertices ? vertex_capacity : 0};
+  const dim3 grid((unsigned)blocks), block(kMeshBlock);
+  hipLaunchKernelGGL(k_mesh_count, grid, block, 0, stream, a, d_vertex_blocks, d_tri_blocks);
+  hipLaunchKernelGGL(k_cloud_offsets, dim3(1), dim3(kCloudScanThreads), 0, stream, d_vertex_blocks, blocks, d_totals,
+                     d_counts);
+  hipLaunchKernelGGL(k_cloud_offsets, dim3(1), dim3(kCloudScanThreads), 0, stream, d_tri_blocks, blocks, d_totals + 1,
+                     d_counts ? d_counts + 1 : nullptr);
+  if (want_vertices || want_tris)  // the triangles name the slots this launch leaves in the slot map
+    hipLaunchKernelGGL(k_mesh_vertices, grid, block, 0, stream, a, (const int*)d_vertex_blocks, s, d_slot_map);
+  if (want_tris)
+    hipLaunchKernelGGL(k_mesh_triangles, grid, block, 0, stream, a, (const int*)d_tri_blocks, (const int32_t*)d_slot_map,
+                       d_tri_out, tri_capacity);
+  if (int rc = launch_check(h, "grid mesh")) return rc;
+  if (counts) {
+    PM_HIP(h, hipMemcpyAsync(counts, d_totals, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    PM_HIP(h, hipStreamSynchronize(stream));
+  }
+  return PM_OK;
+}
+
+void pm_debug_mesh_constants(int* items_per_block, int* blocks_per_scan_pass) {
+  if (items_per_block) *items_per_block = kMeshBlock;
+  if (blocks_per_scan_pass) *blocks_per_scan_pass = kCloudScanThreads;
 }
 
 // Host only: Bouguet's construction (see pm/imaging.h).

@@ -1,6 +1,8 @@
 // imaging.cpp -- bm::imaging free functions over the C ABI (see imaging.hpp).
 #include "imaging.hpp"
 
+#include <cstdio>
+#include <cstring>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -341,6 +343,89 @@ PointCloud MakePointCloud(const core::Image<float>& disp, const StereoModel& mod
     o_c.Download(pc.bgr.data(), n * sizeof(core::Vec3b));
   }
   return pc;
+}
+
+TriangleMesh MakeGridMesh(const core::Image<float>& disp, const StereoModel& model, const CloudFilter& filter,
+                          const MeshOptions& options, const core::Image<core::Vec3f>* normals,
+                          const core::Image<core::Vec3b>* bgr) {
+  if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("MakeGridMesh: empty map");
+  if (normals) SameSize(disp.rows, disp.cols, normals->rows, normals->cols, "MakeGridMesh (normals)");
+  if (bgr) SameSize(disp.rows, disp.cols, bgr->rows, bgr->cols, "MakeGridMesh (bgr)");
+  std::lock_guard<std::mutex> lock(g_mutex);
+  pm_handle* h = Context();
+  DeviceBuffer d_in(h, Bytes(disp)), d_n(h, normals ? Bytes(*normals) : 0), d_c(h, bgr ? Bytes(*bgr) : 0);
+  d_in.Upload(disp.data(), Bytes(disp));
+  if (normals) d_n.Upload(normals->data(), Bytes(*normals));
+  if (bgr) d_c.Upload(bgr->data(), Bytes(*bgr));
+  const pm_cloud_camera cam = CloudCamera(model);
+  const pm_cloud_filter flt = {filter.min_disp, filter.max_range, filter.stride};
+  const pm_mesh_options opt = {options.max_diff, options.referenced_vertices ? PM_MESH_VERTICES_REFERENCED : PM_MESH_VERTICES_ALL};
+  // count first (both capacities 0), then outputs of exactly that size
+  int counts[2] = {0, 0};
+  Check(pm_grid_mesh(h, &cam, &flt, &opt, d_in.as<float>(), nullptr, nullptr, disp.rows, disp.cols, 0, 0, nullptr, nullptr,
+                     nullptr, nullptr, nullptr, nullptr, counts),
+        "pm_grid_mesh");
+  TriangleMesh mesh;
+  if (counts[0] <= 0) return mesh;
+  const size_t n = (size_t)counts[0], t = (size_t)(counts[1] > 0 ? counts[1] : 0);
+  DeviceBuffer o_xyz(h, n * sizeof(core::Vec3f)), o_n(h, normals ? n * sizeof(core::Vec3f) : 0),
+      o_c(h, bgr ? n * sizeof(core::Vec3b) : 0), o_i(h, n * sizeof(int32_t)), o_t(h, t * 3 * sizeof(int32_t));
+  int again[2] = {0, 0};
+  Check(pm_grid_mesh(h, &cam, &flt, &opt, d_in.as<float>(), normals ? d_n.as<float>() : nullptr,
+                     bgr ? d_c.as<uint8_t>() : nullptr, disp.rows, disp.cols, counts[0], counts[1], o_xyz.as<float>(),
+                     normals ? o_n.as<float>() : nullptr, bgr ? o_c.as<uint8_t>() : nullptr, o_i.as<int32_t>(),
+                     t ? o_t.as<int32_t>() : nullptr, nullptr, again),
+        "pm_grid_mesh");
+  if (again[0] != counts[0] || again[1] != counts[1])
+    throw std::runtime_error("MakeGridMesh: the counts changed between two passes over one map");
+  PointCloud& pc = mesh.vertices;
+  pc.xyz.resize(n);
+  pc.index.resize(n);
+  o_xyz.Download(pc.xyz.data(), n * sizeof(core::Vec3f));
+  o_i.Download(pc.index.data(), n * sizeof(int32_t));
+  if (normals) {
+    pc.normals.resize(n);
+    o_n.Download(pc.normals.data(), n * sizeof(core::Vec3f));
+  }
+  if (bgr) {
+    pc.bgr.resize(n);
+    o_c.Download(pc.bgr.data(), n * sizeof(core::Vec3b));
+  }
+  mesh.triangles.resize(t);
+  if (t) o_t.Download(mesh.triangles.data(), t * 3 * sizeof(int32_t));
+  return mesh;
+}
+
+void WritePly(const std::string& path, const TriangleMesh& mesh) {
+  const PointCloud& pc = mesh.vertices;
+  const size_t n = pc.xyz.size();
+  const bool has_n = !pc.normals.empty(), has_c = !pc.bgr.empty();
+  if ((has_n && pc.normals.size() != n) || (has_c && pc.bgr.size() != n))
+    throw std::invalid_argument("WritePly: the vertex streams differ in length");
+  std::string head = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(n) +
+                     "\nproperty float x\nproperty float y\nproperty float z\n";
+  if (has_n) head += "property float nx\nproperty float ny\nproperty float nz\n";
+  if (has_c) head += "property uchar red\nproperty uchar green\nproperty uchar blue\n";
+  head += "element face " + std::to_string(mesh.triangles.size()) + "\nproperty list uchar int vertex_indices\nend_header\n";
+  // the records are assembled byte by byte (binary32 and int32 are little-endian on every host this library builds for)
+  const size_t vbytes = 12 + (has_n ? 12 : 0) + (has_c ? 3 : 0);
+  std::vector<uint8_t> body(n * vbytes + mesh.triangles.size() * 13);
+  uint8_t* o = body.data();
+  for (size_t i = 0; i < n; ++i) {
+    std::memcpy(o, &pc.xyz[i], 12), o += 12;
+    if (has_n) std::memcpy(o, &pc.normals[i], 12), o += 12;
+    if (has_c) *o++ = pc.bgr[i].v[2], *o++ = pc.bgr[i].v[1], *o++ = pc.bgr[i].v[0];  // B G R -> red green blue
+  }
+  for (const std::array<int32_t, 3>& t : mesh.triangles) {
+    *o++ = 3;
+    std::memcpy(o, t.data(), 12), o += 12;
+  }
+  FILE* f = std::fopen(path.c_str(), "wb");
+  bool ok = f != nullptr;
+  ok = ok && std::fwrite(head.data(), 1, head.size(), f) == head.size();
+  ok = ok && (body.empty() || std::fwrite(body.data(), 1, body.size(), f) == body.size());
+  if (f) ok = (std::fclose(f) == 0) && ok;
+  if (!ok) throw std::runtime_error("WritePly: cannot write " + path);
 }
 
 core::Image<core::Vec3f> DisparityNormals(const core::Image<float>& disp, const StereoModel& model, const NormalsFit& fit,

@@ -15,6 +15,7 @@
 #pragma once
 
 #include <array>
+#include <string>
 #include <vector>
 
 #include "patchmatch_gpu.hpp"
@@ -133,6 +134,25 @@ struct SpeckleFilter {  // pm_speckle_filter
 // number of pixels set to 0; each where it is asked for.  Throws std::runtime_error where pm_filter_speckles refuses.
 core::Image<float> FilterSpeckles(const core::Image<float>& disp, const SpeckleFilter& filter = SpeckleFilter(),
                                   core::Image<int32_t>* labels = nullptr, int* removed = nullptr);
+// Behind the cloud: the organised grid mesh of a map (pm/imaging.h: pm_grid_mesh; definition: tests/mesh_ref.py).  Every
+// 2x2 cell of the stride grid becomes up to two triangles facing the camera, unless two of its corners differ by more than
+// max_diff or do not count.
+struct MeshOptions {  // pm_mesh_options
+  float max_diff = 1.f;            // finite, >= 0: the largest disparity step a triangle's edge may span
+  bool referenced_vertices = true; // true: only vertices some triangle names; false: every counted pixel (MakePointCloud's)
+};
+struct TriangleMesh {
+  PointCloud vertices;
+  std::vector<std::array<int32_t, 3>> triangles;  // indices into `vertices`, in row-major cell order
+};
+// Counts first, then sizes the buffers exactly.  Throws std::runtime_error where pm_grid_mesh refuses.
+TriangleMesh MakeGridMesh(const core::Image<float>& disp, const StereoModel& model, const CloudFilter& filter = CloudFilter(),
+                          const MeshOptions& options = MeshOptions(), const core::Image<core::Vec3f>* normals = nullptr,
+                          const core::Image<core::Vec3b>* bgr = nullptr);
+// Host only: the mesh as a binary little-endian PLY file -- element vertex with float x y z, float nx ny nz where the mesh
+// has normals and uchar red green blue where it has colour; element face with `list uchar int vertex_indices`.  Throws
+// std::runtime_error where the file cannot be written.
+void WritePly(const std::string& path, const TriangleMesh& mesh);
 
 }  // namespace imaging
 }  // namespace bm

@@ -46,6 +46,7 @@ EXPORTS = [
     "pm_backproject", "pm_planes_normals", "pm_point_cloud", "pm_debug_cloud_constants",
     "pm_disparity_normals", "pm_debug_normals_fit_constants",
     "pm_filter_speckles", "pm_debug_speckle_constants",
+    "pm_grid_mesh", "pm_debug_mesh_constants",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
     "pm_debug_sweep_plan",
     "pm_remove_background", "pm_mask_occlusions", "pm_foreground_texture_mask", "pm_sparse_init", "pm_corner_subpix", "pm_profile_enable", "pm_profile_read",
@@ -169,6 +170,20 @@ def speckle_constants():
     """pm_debug_speckle_constants: (tile columns, tile rows) of pm_filter_speckles' tile launch."""
     a, b = C.c_int(0), C.c_int(0)
     load().pm_debug_speckle_constants(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+PM_MESH_VERTICES_ALL, PM_MESH_VERTICES_REFERENCED = 0, 1
+
+
+class PmMeshOptions(C.Structure):  # pm_grid_mesh
+    _fields_ = [("max_diff", C.c_float), ("vertices", C.c_int)]
+
+
+def mesh_constants():
+    """pm_debug_mesh_constants: (items of a grid row per block, block counts per pass of the offsets kernel)."""
+    a, b = C.c_int(0), C.c_int(0)
+    load().pm_debug_mesh_constants(C.byref(a), C.byref(b))
     return a.value, b.value
 
 
@@ -341,6 +356,11 @@ def load():
     lib.pm_filter_speckles.restype = C.c_int
     lib.pm_debug_speckle_constants.argtypes = [C.POINTER(C.c_int)] * 2
     lib.pm_debug_speckle_constants.restype = None
+    lib.pm_grid_mesh.argtypes = [vp, C.POINTER(PmCloudCamera), C.POINTER(PmCloudFilter), C.POINTER(PmMeshOptions), vp, vp, vp,
+                                 C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int)]
+    lib.pm_grid_mesh.restype = C.c_int
+    lib.pm_debug_mesh_constants.argtypes = [C.POINTER(C.c_int)] * 2
+    lib.pm_debug_mesh_constants.restype = None
     lib.pm_device_malloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     lib.pm_device_free.argtypes = [vp, vp]
     lib.pm_upload.argtypes = [vp, vp, vp, C.c_size_t]
@@ -849,6 +869,21 @@ class Engine:
         self._check(self.lib.pm_filter_speckles(self.h, C.byref(f), d_disp, rows, cols, d_out, d_labels, d_sizes, d_removed,
                                                 C.byref(n) if host_count else None), "pm_filter_speckles")
         return n.value if host_count else None
+
+    def grid_mesh(self, camera, d_disp, rows, cols, vertex_capacity, tri_capacity, max_diff=1.0, vertices=PM_MESH_VERTICES_ALL,
+                  min_disp=0.0, max_range=0.0, stride=1, d_normals=None, d_bgr8=None, d_xyz_out=None, d_normals_out=None,
+                  d_bgr8_out=None, d_index_out=None, d_tri_out=None, d_counts=None, host_counts=True):
+        """pm_grid_mesh (raw device addresses) -> (vertex count, triangle count), both reported beyond the capacities (None
+        with host_counts=False: the call then only enqueues).  d_tri_out: [tri_capacity][3] int32 vertex slots; d_counts: two
+        device ints."""
+        c = cloud_camera(camera)
+        f = PmCloudFilter(min_disp, max_range, stride)
+        o = PmMeshOptions(max_diff, vertices)
+        n = (C.c_int * 2)(-1, -1)
+        self._check(self.lib.pm_grid_mesh(self.h, C.byref(c) if c is not None else None, C.byref(f), C.byref(o), d_disp, d_normals,
+                                          d_bgr8, rows, cols, vertex_capacity, tri_capacity, d_xyz_out, d_normals_out, d_bgr8_out,
+                                          d_index_out, d_tri_out, d_counts, n if host_counts else None), "pm_grid_mesh")
+        return (n[0], n[1]) if host_counts else None
 
     def normalize(self, d_bgr, rows, cols, d_out):
         self._check(self.lib.pm_normalize(self.h, d_bgr, rows, cols, d_out), "pm_normalize")

@@ -1,0 +1,154 @@
+// mesh_host_main.cpp -- runs pm_grid_mesh's own per-thread code (csrc/pm_mesh_body.hpp: mesh_value, mesh_cell,
+// mesh_referenced, mesh_store_vertex, mesh_store_triangles -- the bodies of the kernels of csrc/pm_mesh.hpp) on the HOST, so
+// that tests/test_mesh.py can hold it to the definition (tests/mesh_ref.py) without a GPU and under
+// -fsanitize=address,undefined.  The blocks of the three launches are walked as the device forms them -- a block is `block`
+// consecutive items of one grid row -- in forward or in reverse order: a slot may depend on the block offsets alone, never
+// on which block ran first.  Every buffer is a heap allocation of EXACTLY the bytes the stage may touch: a load past the
+// last disparity or slot-map entry, or a store behind slot min(count, capacity) - 1, is reported.  Compiled as HIP source
+// with the host-only switch of hipcc and -ffp-contract=off.
+//   mesh_host_main <dir>
+// <dir> holds .npy dumps (numpy's format, version 1, C order, little endian; the header is skipped and the payload size
+// checked): params.npy (float64: rows, cols, fx, fy, cx, cy, baseline, min_disp, max_range, stride, max_diff, vertices,
+// vertex_capacity, tri_capacity, block, reverse), disp.npy (float32 [rows][cols]), normals.npy (float32 [rows][cols][3]),
+// bgr.npy (uint8 [rows][cols][3]) and the definition's results want_counts.npy (int32 [2]: vertices, triangles),
+// want_xyz.npy, want_normals.npy, want_bgr.npy, want_index.npy (min(vertices, vertex_capacity) entries each) and
+// want_tris.npy (int32 [min(triangles, tri_capacity)][3]).
+// Exit status 0: every result equals its dump byte for byte; 1: a mismatch (named on stderr); 2: bad input.
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "pm_mesh_body.hpp"
+
+static bool read_npy(const std::string& path, size_t bytes, std::unique_ptr<uint8_t[]>* out) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return false;
+  uint8_t head[10];
+  bool ok = fread(head, 1, 10, f) == 10 && !memcmp(head, "\x93NUMPY\x01", 7);
+  const size_t hlen = ok ? (size_t)head[8] | ((size_t)head[9] << 8) : 0;
+  ok = ok && fseek(f, 0, SEEK_END) == 0 && (size_t)ftell(f) == 10 + hlen + bytes && fseek(f, (long)(10 + hlen), SEEK_SET) == 0;
+  if (ok) {
+    out->reset(new uint8_t[bytes ? bytes : 1]);  // exactly sized (one byte where the dump is empty)
+    ok = fread(out->get(), 1, bytes, f) == bytes;
+  }
+  fclose(f);
+  if (!ok) fprintf(stderr, "cannot read %zu payload bytes from %s\n", bytes, path.c_str());
+  return ok;
+}
+
+static int differ(const char* what, const void* got, const void* want, size_t bytes) {
+  if (!memcmp(got, want, bytes)) return 0;
+  const uint8_t* g = (const uint8_t*)got;
+  const uint8_t* w = (const uint8_t*)want;
+  size_t at = 0;
+  while (g[at] == w[at]) ++at;
+  fprintf(stderr, "%s differs from the definition at byte %zu of %zu\n", what, at, bytes);
+  return 1;
+}
+
+// what a thread of block (ys, xs0 + k) computes in the count and in the scatter launches
+static bool thread_vertex(const pm::MeshArgs& a, int xs, int ys) {
+  if (!a.referenced) return pm::mesh_value(a, xs, ys) > 0.f;
+  float v[3][3];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) v[r][c] = pm::mesh_value(a, xs - 1 + c, ys - 1 + r);
+  return pm::mesh_referenced(v, a.max_diff);
+}
+static unsigned thread_cell(const pm::MeshArgs& a, int xs, int ys) {
+  return pm::mesh_cell(pm::mesh_value(a, xs, ys), pm::mesh_value(a, xs + 1, ys), pm::mesh_value(a, xs, ys + 1),
+                       pm::mesh_value(a, xs + 1, ys + 1), a.max_diff);
+}
+
+int main(int argc, char** argv) {
+  if (argc != 2) return 2;
+  const std::string dir = std::string(argv[1]) + "/";
+  std::unique_ptr<uint8_t[]> raw;
+  if (!read_npy(dir + "params.npy", 16 * sizeof(double), &raw)) return 2;
+  double p[16];
+  memcpy(p, raw.get(), sizeof p);
+  const int rows = (int)p[0], cols = (int)p[1], stride = (int)p[9], vertices = (int)p[11], vcap = (int)p[12], tcap = (int)p[13],
+            block = (int)p[14], reverse = (int)p[15];
+  const pm_cloud_camera camera = {p[2], p[3], p[4], p[5], p[6]};
+  const pm_cloud_filter filter = {(float)p[7], (float)p[8], stride};
+  if (rows < 1 || cols < 1 || stride < 1 || vcap < 0 || tcap < 0 || block < 1 || (vertices != 0 && vertices != 1)) return 2;
+  const size_t px = (size_t)rows * cols;
+  std::unique_ptr<uint8_t[]> disp_b, normals_b, bgr_b, want_counts;
+  if (!read_npy(dir + "disp.npy", 4 * px, &disp_b) || !read_npy(dir + "normals.npy", 12 * px, &normals_b) ||
+      !read_npy(dir + "bgr.npy", 3 * px, &bgr_b) || !read_npy(dir + "want_counts.npy", 8, &want_counts))
+    return 2;
+  int want_n[2];
+  memcpy(want_n, want_counts.get(), 8);
+  if (want_n[0] < 0 || want_n[1] < 0) return 2;
+  const size_t m = (size_t)(want_n[0] < vcap ? want_n[0] : vcap), t = (size_t)(want_n[1] < tcap ? want_n[1] : tcap);
+  std::unique_ptr<uint8_t[]> want_xyz, want_nrm, want_bgr, want_idx, want_tris;
+  if (!read_npy(dir + "want_xyz.npy", 12 * m, &want_xyz) || !read_npy(dir + "want_normals.npy", 12 * m, &want_nrm) ||
+      !read_npy(dir + "want_bgr.npy", 3 * m, &want_bgr) || !read_npy(dir + "want_index.npy", 4 * m, &want_idx) ||
+      !read_npy(dir + "want_tris.npy", 12 * t, &want_tris))
+    return 2;
+
+  const int sub_rows = (rows + stride - 1) / stride, sub_cols = (cols + stride - 1) / stride;
+  const pm::MeshArgs a = {{pm::cloud_cam(camera), filter, (const float*)disp_b.get(), rows, cols, sub_cols,
+                           (long long)sub_rows * sub_cols},
+                          sub_rows, (float)p[10], vertices};
+  const int segments = (sub_cols + block - 1) / block, blocks = sub_rows * segments;
+  std::vector<int> order(blocks);
+  for (int b = 0; b < blocks; ++b) order[b] = reverse ? blocks - 1 - b : b;
+
+  // the count launch, then the two scans
+  std::vector<int> voff(blocks), toff(blocks);
+  for (int b : order) {
+    const int ys = b / segments, xs0 = (b % segments) * block;
+    int nv = 0, nt = 0;
+    for (int k = 0; k < block; ++k) {
+      nv += thread_vertex(a, xs0 + k, ys);
+      const unsigned cell = thread_cell(a, xs0 + k, ys);
+      nt += (int)(cell & pm::kMeshT0) + (int)((cell & pm::kMeshT1) != 0);
+    }
+    voff[b] = nv, toff[b] = nt;
+  }
+  int total[2] = {0, 0};
+  for (int b = 0; b < blocks; ++b) {
+    const int nv = voff[b], nt = toff[b];
+    voff[b] = total[0], toff[b] = total[1];
+    total[0] += nv, total[1] += nt;
+  }
+  int bad = 0;
+  if (total[0] != want_n[0] || total[1] != want_n[1]) {
+    fprintf(stderr, "counts %d vertices, %d triangles; the definition counts %d, %d\n", total[0], total[1], want_n[0], want_n[1]);
+    bad = 1;
+  }
+
+  // the vertex scatter: streams of exactly min(count, capacity) records, a slot map of exactly the grid
+  std::unique_ptr<float[]> xyz(new float[3 * m ? 3 * m : 1]), nrm(new float[3 * m ? 3 * m : 1]);
+  std::unique_ptr<uint8_t[]> bgr(new uint8_t[3 * m ? 3 * m : 1]);
+  std::unique_ptr<int32_t[]> idx(new int32_t[m ? m : 1]), tris(new int32_t[3 * t ? 3 * t : 1]);
+  std::unique_ptr<int32_t[]> slot_map(new int32_t[(size_t)a.c.items]);
+  const pm::CloudStreams cs = {(const float*)normals_b.get(), bgr_b.get(), xyz.get(), nrm.get(), bgr.get(), idx.get(), vcap};
+  for (int b : order) {
+    const int ys = b / segments, xs0 = (b % segments) * block;
+    int slot = voff[b];
+    for (int k = 0; k < block; ++k) {
+      const bool is_vertex = thread_vertex(a, xs0 + k, ys);
+      if (xs0 + k < sub_cols) pm::mesh_store_vertex(a, cs, slot_map.get(), xs0 + k, ys, is_vertex, slot);
+      slot += is_vertex;
+    }
+  }
+  // the triangle scatter
+  for (int b : order) {
+    const int ys = b / segments, xs0 = (b % segments) * block;
+    int slot = toff[b];
+    for (int k = 0; k < block; ++k) {
+      const unsigned cell = thread_cell(a, xs0 + k, ys);
+      if (cell & (pm::kMeshT0 | pm::kMeshT1)) pm::mesh_store_triangles(a, slot_map.get(), tris.get(), tcap, xs0 + k, ys, cell, slot);
+      slot += (int)(cell & pm::kMeshT0) + (int)((cell & pm::kMeshT1) != 0);
+    }
+  }
+  bad |= differ("mesh xyz", xyz.get(), want_xyz.get(), 12 * m);
+  bad |= differ("mesh normals", nrm.get(), want_nrm.get(), 12 * m);
+  bad |= differ("mesh bgr", bgr.get(), want_bgr.get(), 3 * m);
+  bad |= differ("mesh index", idx.get(), want_idx.get(), 4 * m);
+  bad |= differ("mesh triangles", tris.get(), want_tris.get(), 12 * t);
+  return bad ? 1 : 0;
+}
