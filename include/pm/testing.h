@@ -54,6 +54,29 @@ int pm_debug_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, 
 int pm_debug_sweep_plan(const pm_params* params, int rows, int cols, int patch_h, int patch_w, int pass, int slots,
                         float amp, pm_debug_sweep_variant* out);
 
+/* ---- the noise + clamp + cost stage of a scalar-mode iteration, on its own and with its cost plane -----------------------
+ * (k_noise_cost / k_noise_cost_tiled<W, W> of csrc/pm_kernels.hpp, chosen by launch_noise_cost.)
+ * pm_debug_noise_cost_constants: the pixels one workgroup of the tiled kernel owns (tile_cols x tile_rows) and the target
+ * columns its LDS tile holds (target_span): a tile whose windows span more falls back to the global-memory cost.  No
+ * handle, no device.
+ * pm_debug_noise_cost: prepares the pair as the other single stages do, copies disp into the disparity plane of view 0
+ * and -- if cost is not null -- cost into the WHOLE cost plane of view 0 (a sentinel there shows which pixels the stage
+ * did not write), makes the launch an iteration of Match() makes (one slot, view 0; the mirrored view is the call on the
+ * mirrored (right, left) pair) and copies both planes back.  amount < 0: no noise, as in pm_propagate; amount >= 0: the
+ * handle's unit noise (pm_unit_noise / pm_set_unit_noise) times amount, and every float value of disp is accepted.
+ * keep_zero = 1: what Match() passes from the second iteration of one window on (the tiled kernels honour it, the general
+ * one ignores it).  PM_ERR_INVALID_ARG: a null image or disp, a NaN amount, keep_zero outside {0, 1}, a window
+ * pm_propagate refuses, and under PM_SEM_GPU with amount < 0 a map with a value below 0 (pm_remove_background's rule).
+ * PM_ERR_BUSY between pm_capture_begin and pm_capture_end.
+ * pm_debug_remove_background: pm_remove_background with the caller's plane as the cost plane of view 0 and the stage told
+ * that it holds the cost of disp under this window (`cached`, what Match() passes when the last iteration used the
+ * background window); a null cost is pm_remove_background itself. */
+void pm_debug_noise_cost_constants(int* tile_cols, int* tile_rows, int* target_span);
+int pm_debug_noise_cost(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
+                        float* cost, int patch_h, int patch_w, float amount, int keep_zero);
+int pm_debug_remove_background(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
+                               const float* cost, int patch_h, int patch_w, float factor);
+
 /* ---- pm_point_cloud's launch constants (csrc/pm_cloud.hpp) ------------------------------------------------------------
  * items_per_block: the considered pixels one block of the count / scatter launches takes; blocks_per_scan_pass: the block
  * counts the offsets kernel turns into offsets per pass.  A map with more than items_per_block * blocks_per_scan_pass

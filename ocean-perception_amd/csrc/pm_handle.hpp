@@ -363,7 +363,9 @@ void launch_tile_presweep(pm_handle* h, const PlaneSet& ps, float* snap_disp, fl
 void launch_download(pm_handle* h, float* dst_dev, size_t dst_step_floats, const float* d_src, int rows, int cols,
                      hipStream_t stream);
 void launch_upload(pm_handle* h, float* d_dst, const float* src_dev, int words, hipStream_t stream);
-void launch_copy_in(pm_handle* h, const PlaneSet& ps, const float* d_src, hipStream_t stream);
+// tight caller planes <-> the planes of view 0; which: 0 = disparity, 1 = gradient magnitude, 2 = unit noise, 3 = cost
+// (copy_in: 0 and 3 only)
+void launch_copy_in(pm_handle* h, const PlaneSet& ps, const float* d_src, int which, hipStream_t stream);
 void launch_copy_out(pm_handle* h, const PlaneSet& ps, float* d_dst, int which, hipStream_t stream);
 void launch_copy_disp_strided(pm_handle* h, const PlaneSet& ps, float* d_buf, size_t stride, int to_buf,
                               hipStream_t stream);

@@ -693,10 +693,12 @@ int stage_prep(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows
   return PM_OK;
 }
 
-int stage_disp_in(pm_handle* h, const PlaneSet& ps, const float* disp) {
+// which: 0 = into the disparity plane of view 0, 3 = into its cost plane (test hooks; staged in a buffer of its own)
+int stage_disp_in(pm_handle* h, const PlaneSet& ps, const float* disp, int which = 0) {
   const size_t px = (size_t)ps.rows * ps.cols;
-  PM_HIP(h, hipMemcpyAsync(h->st_disp_l, disp, sizeof(float) * px, hipMemcpyHostToDevice, h->stream));
-  launch_copy_in(h, ps, h->st_disp_l, h->stream);
+  float* st = which == 3 ? h->st_disp_r.get() : h->st_disp_l.get();
+  PM_HIP(h, hipMemcpyAsync(st, disp, sizeof(float) * px, hipMemcpyHostToDevice, h->stream));
+  launch_copy_in(h, ps, st, which, h->stream);
   return launch_check(h, "copy_in");
 }
 
@@ -847,12 +849,14 @@ int pm_debug_sweep_plan(const pm_params* params, int rows, int cols, int patch_h
   return PM_OK;
 }
 
-int pm_remove_background(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
-                         int patch_h, int patch_w, float factor) {
-  if (!h) return PM_ERR_INVALID_ARG;
-  if (int rc = refuse_while_capturing(h, "pm_remove_background")) return rc;
+namespace {
+// pm_remove_background and pm_debug_remove_background: cost (may be null) = the caller's cost plane, used as the stage
+// uses the plane the last sweeps left (cached = 1)
+int remove_background_impl(pm_handle* h, const char* who, const uint8_t* left, const uint8_t* right, int rows, int cols,
+                           float* disp, const float* cost, int patch_h, int patch_w, float factor) {
+  if (int rc = refuse_while_capturing(h, who)) return rc;
   if (!left || !right || !disp || !(factor > 0.f)) {
-    set_err(h, "pm_remove_background: null pointer or non-positive factor");
+    set_err(h, "%s: null pointer or non-positive factor", who);
     return PM_ERR_INVALID_ARG;
   }
   if (h->params.semantics == PM_SEM_CPU)
@@ -862,14 +866,66 @@ int pm_remove_background(pm_handle* h, const uint8_t* left, const uint8_t* right
   // PM_SEM_GPU samples the target at max(x - d, 1) (patchmatch_gpu.cu:233-270), which a negative d puts past the row;
   // NaN gives position 1 and passes.
   if (h->params.semantics == PM_SEM_GPU)
-    if (int rc = refuse_map_values(h, "pm_remove_background", disp, rows, cols, /*nan_ok=*/true)) return rc;
+    if (int rc = refuse_map_values(h, who, disp, rows, cols, /*nan_ok=*/true)) return rc;
   PlaneSet ps;
   if (int rc = stage_prep(h, left, right, rows, cols, &ps)) return rc;
   if (int rc = stage_disp_in(h, ps, disp)) return rc;
+  if (cost)
+    if (int rc = stage_disp_in(h, ps, cost, 3)) return rc;
   const CostParams cp = cost_params(h->params, patch_w, patch_h);
   const Interior in = interior(h->params, rows, cols, cp.pw, cp.ph);
-  launch_background(h, ps, cp, in, factor, 0, 1, h->stream);
+  launch_background(h, ps, cp, in, factor, cost ? 1 : 0, 1, h->stream);
   if (int rc = launch_check(h, "background")) return rc;
+  return stage_out(h, ps, disp, 0);
+}
+}  // namespace
+
+int pm_remove_background(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
+                         int patch_h, int patch_w, float factor) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  return remove_background_impl(h, "pm_remove_background", left, right, rows, cols, disp, nullptr, patch_h, patch_w,
+                                factor);
+}
+
+// pm_remove_background on a caller-supplied cost plane (include/pm/testing.h)
+int pm_debug_remove_background(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
+                               const float* cost, int patch_h, int patch_w, float factor) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  return remove_background_impl(h, "pm_debug_remove_background", left, right, rows, cols, disp, cost, patch_h, patch_w,
+                                factor);
+}
+
+// the noise + clamp + cost stage as view_op launches it, with its cost plane (include/pm/testing.h)
+int pm_debug_noise_cost(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
+                        float* cost, int patch_h, int patch_w, float amount, int keep_zero) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (int rc = refuse_while_capturing(h, "pm_debug_noise_cost")) return rc;
+  if (!left || !right || !disp) {
+    set_err(h, "pm_debug_noise_cost: null pointer");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (amount != amount || (keep_zero != 0 && keep_zero != 1)) {
+    set_err(h, "pm_debug_noise_cost: NaN amount, or keep_zero = %d (0 or 1)", keep_zero);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (h->params.semantics == PM_SEM_CPU)
+    if (int rc = check_patch(h, patch_w, patch_h)) return rc;
+  if (int rc = check_size(h, rows, cols, 1)) return rc;
+  // With amount >= 0 the noise step defines every float value (what is not > 0, NaN included, becomes 0).  Without it
+  // PM_SEM_CPU still clamps d to [0, x - pw/2]; PM_SEM_GPU turns d into the sample position max(x - d, 1) as it stands:
+  // pm_remove_background's rule.
+  if (h->params.semantics == PM_SEM_GPU && amount < 0.f)
+    if (int rc = refuse_map_values(h, "pm_debug_noise_cost", disp, rows, cols, /*nan_ok=*/true)) return rc;
+  PlaneSet ps;
+  if (int rc = stage_prep(h, left, right, rows, cols, &ps)) return rc;
+  if (int rc = stage_disp_in(h, ps, disp)) return rc;
+  if (cost)
+    if (int rc = stage_disp_in(h, ps, cost, 3)) return rc;
+  const CostParams cp = cost_params(h->params, patch_w, patch_h);
+  launch_noise_cost(h, ps, cp, interior(h->params, rows, cols, cp.pw, cp.ph), amount, 1, keep_zero, h->stream);
+  if (int rc = launch_check(h, "noise_cost")) return rc;
+  if (cost)
+    if (int rc = stage_out(h, ps, cost, 3)) return rc;
   return stage_out(h, ps, disp, 0);
 }
 

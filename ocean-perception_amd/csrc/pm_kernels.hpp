@@ -488,6 +488,9 @@ __global__ void __launch_bounds__(256) k_noise_cost_tiled(PlaneSet ps, CostParam
   }
   const bool inside = inimg && x >= in.x_lo && x <= in.x_hi && y >= in.y_lo && y <= in.y_hi;
   if (keep_zero && inside && was_zero) {  // d == 0 stays 0 and its cost is already stored
+    // (d too: without the noise step -- amount < 0 -- it still holds the input, which may be -0.0, negative or NaN, and
+    // the store at the end of the kernel would put that back)
+    d = 0.f;
     v.disp[o] = 0.f;
   }
   const bool interior = inside && !(keep_zero && was_zero);
@@ -982,12 +985,13 @@ __global__ void __launch_bounds__(256) k_state_row(PlaneSet ps, int r, float* __
   else *p = buf[(size_t)v * ps.cols + x];
 }
 
-// Plain copies between caller planes and the pitched disparity plane of view 0.
-__global__ void __launch_bounds__(256) k_copy_in(PlaneSet ps, const float* __restrict__ src) {
+// Plain copies between caller planes and the pitched state planes of view 0 (single-stage entry points and test hooks
+// only).  which: 0 = the disparity plane, 3 = the cost plane (the numbers k_copy_out uses).
+__global__ void __launch_bounds__(256) k_copy_in(PlaneSet ps, const float* __restrict__ src, int which) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   const int y = blockIdx.y;
   if (x >= ps.cols) return;
-  ps.disp[state_at(x, y, ps.pitch)] = src[(size_t)y * ps.cols + x];
+  (which == 3 ? ps.cost : ps.disp)[state_at(x, y, ps.pitch)] = src[(size_t)y * ps.cols + x];
 }
 // caller plane with its own row stride (elements); to_caller != 0 copies the other way
 __global__ void __launch_bounds__(256) k_copy_disp_strided(PlaneSet ps, float* __restrict__ buf, size_t stride,
@@ -1027,8 +1031,10 @@ __global__ void __launch_bounds__(256) k_copy_out(PlaneSet ps, float* __restrict
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   const int y = blockIdx.y;
   if (x >= ps.cols) return;
-  const float* src = which == 0 ? ps.disp : (which == 1 ? ps.g32 : ps.noise);
-  dst[(size_t)y * ps.cols + x] = src[which == 0 ? state_at(x, y, ps.pitch) : (size_t)y * ps.pitch + x];
+  // which: 0 = disparity, 1 = gradient magnitude, 2 = unit noise, 3 = cost (0 and 3 are state planes)
+  const float* src = which == 0 ? ps.disp : (which == 1 ? ps.g32 : (which == 2 ? ps.noise : ps.cost));
+  const bool state = which == 0 || which == 3;
+  dst[(size_t)y * ps.cols + x] = src[state ? state_at(x, y, ps.pitch) : (size_t)y * ps.pitch + x];
 }
 
 }  // namespace pm

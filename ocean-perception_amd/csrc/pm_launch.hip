@@ -2,6 +2,7 @@
 // declared in pm_handle.hpp, each enqueuing on the stream it is given.  No other unit includes pm_kernels.hpp.
 #include <algorithm>
 
+#include "pm/testing.h"
 #include "pm_handle.hpp"
 #include "pm_kernels.hpp"
 #include "pm_sweeps.hpp"
@@ -201,8 +202,8 @@ void launch_upload(pm_handle* h, float* d_dst, const float* src_dev, int words, 
   hipLaunchKernelGGL(k_download, dim3((unsigned)blocks), dim3(256), 0, stream, d_dst, (size_t)words, src_dev, 1, words);
 }
 
-void launch_copy_in(pm_handle* h, const PlaneSet& ps, const float* d_src, hipStream_t stream) {
-  hipLaunchKernelGGL(k_copy_in, pixel_grid(ps.cols, ps.rows, 1), dim3(256), 0, stream, ps, d_src);
+void launch_copy_in(pm_handle* h, const PlaneSet& ps, const float* d_src, int which, hipStream_t stream) {
+  hipLaunchKernelGGL(k_copy_in, pixel_grid(ps.cols, ps.rows, 1), dim3(256), 0, stream, ps, d_src, which);
 }
 
 void launch_copy_out(pm_handle* h, const PlaneSet& ps, float* d_dst, int which, hipStream_t stream) {
@@ -217,6 +218,13 @@ void launch_copy_disp_strided(pm_handle* h, const PlaneSet& ps, float* d_buf, si
 
 }  // namespace eng
 }  // namespace pm
+
+// the tile geometry of k_noise_cost_tiled (include/pm/testing.h): no handle, no device
+extern "C" void pm_debug_noise_cost_constants(int* tile_cols, int* tile_rows, int* target_span) {
+  if (tile_cols) *tile_cols = pm::kTileW;
+  if (tile_rows) *tile_rows = pm::kTileH;
+  if (target_span) *target_span = pm::kTileRW;
+}
 
 // ---- ForegroundTextureMask (src/vehicle/stereo_matching/patchmatch.cpp:19-49), device images ------------------------------
 extern "C" int pm_foreground_texture_mask(pm_handle* h, const uint8_t* d_gray, int rows, int cols, int ksize,

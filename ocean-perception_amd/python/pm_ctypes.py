@@ -48,7 +48,7 @@ EXPORTS = [
     "pm_filter_speckles", "pm_debug_speckle_constants",
     "pm_grid_mesh", "pm_debug_mesh_constants",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
-    "pm_debug_sweep_plan",
+    "pm_debug_sweep_plan", "pm_debug_noise_cost_constants", "pm_debug_noise_cost", "pm_debug_remove_background",
     "pm_remove_background", "pm_mask_occlusions", "pm_foreground_texture_mask", "pm_sparse_init", "pm_corner_subpix", "pm_profile_enable", "pm_profile_read",
     "pm_kernel_name", "pm_debug_counters", "pm_debug_counters_enable",
     "pm_tile_begin", "pm_tile_noise", "pm_tile_sweep", "pm_tile_snapshot", "pm_tile_restore", "pm_tile_get_row",
@@ -185,6 +185,13 @@ def mesh_constants():
     a, b = C.c_int(0), C.c_int(0)
     load().pm_debug_mesh_constants(C.byref(a), C.byref(b))
     return a.value, b.value
+
+
+def noise_cost_constants():
+    """pm_debug_noise_cost_constants: (tile columns, tile rows, target columns held in LDS) of the tiled noise + cost kernel."""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    load().pm_debug_noise_cost_constants(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
 
 
 def cloud_camera(values):
@@ -393,6 +400,12 @@ def load():
     lib.pm_debug_sweep_plan.restype = C.c_int
     lib.pm_remove_background.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_int, C.c_float]
     lib.pm_remove_background.restype = C.c_int
+    lib.pm_debug_noise_cost_constants.argtypes = [C.POINTER(C.c_int)] * 3
+    lib.pm_debug_noise_cost_constants.restype = None
+    lib.pm_debug_noise_cost.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_float, C.c_int]
+    lib.pm_debug_noise_cost.restype = C.c_int
+    lib.pm_debug_remove_background.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_float]
+    lib.pm_debug_remove_background.restype = C.c_int
     lib.pm_mask_occlusions.argtypes = [vp, f32p, f32p, C.c_int, C.c_int]
     lib.pm_mask_occlusions.restype = C.c_int
     lib.pm_foreground_texture_mask.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp]
@@ -970,6 +983,29 @@ class Engine:
         self._check(self.lib.pm_remove_background(self.h, pl, pr, d.shape[0], d.shape[1],
                                                   d.ctypes.data_as(C.c_void_p), patch_h, patch_w, factor),
                     "pm_remove_background")
+        return d
+
+    def debug_noise_cost(self, left, right, disp, patch_h, patch_w, amount=-1.0, keep_zero=0, cost=None):
+        """The noise + clamp + cost stage of one iteration on its own (pm_debug_noise_cost, include/pm/testing.h) ->
+        (disp, cost); cost: the plane the stage finds (e.g. a sentinel), or None: no cost plane goes in or comes out."""
+        left, pl = _u8(left)
+        right, pr = _u8(right)
+        d = np.array(disp, dtype=np.float32, order="C", copy=True)
+        c = np.array(cost, dtype=np.float32, order="C", copy=True) if cost is not None else None
+        self._check(self.lib.pm_debug_noise_cost(self.h, pl, pr, d.shape[0], d.shape[1], d.ctypes.data_as(C.c_void_p),
+                                                 c.ctypes.data_as(C.c_void_p) if c is not None else None, patch_h, patch_w,
+                                                 amount, keep_zero), "pm_debug_noise_cost")
+        return d, c
+
+    def debug_remove_background(self, left, right, disp, cost, patch_h, patch_w, factor):
+        """remove_background() on a caller-supplied cost plane (pm_debug_remove_background); cost None: uncached."""
+        left, pl = _u8(left)
+        right, pr = _u8(right)
+        d = np.array(disp, dtype=np.float32, order="C", copy=True)
+        c, pc = _f32(cost) if cost is not None else (None, None)
+        self._check(self.lib.pm_debug_remove_background(self.h, pl, pr, d.shape[0], d.shape[1],
+                                                        d.ctypes.data_as(C.c_void_p), pc, patch_h, patch_w, factor),
+                    "pm_debug_remove_background")
         return d
 
     def sparse_init(self, left, right, dilate_factor=4):
