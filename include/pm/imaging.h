@@ -397,6 +397,51 @@ int pm_grid_mesh(pm_handle* h, const pm_cloud_camera* camera, const pm_cloud_fil
                  int* d_counts /* device int[2]: vertices, triangles; may be NULL */,
                  int* counts /* host int[2]; may be NULL; non-NULL synchronises like pm_point_cloud's count */);
 
+/* ---- temporal seeds: the left map of frame k carried into the two seed maps of frame k + 1 --------------------------------
+ * What it is for: the link between two frames of a sequence.  The d_seed_l / d_seed_r inputs of every Match entry point take a
+ * value > 0 as the start of that pixel and 0 as background; this stage makes both maps on the device from the OLD frame's left
+ * disparity map and the rigid motion between the two left cameras (from a VIO front end), the classic temporal PatchMatch
+ * step.  With R = I and t = 0 it is "reuse the last map" for a static camera, and it still produces the right-view map.
+ * Held to its CPU definition (tests/reproject_ref.py) BIT FOR BIT:
+ *   motion     X_new = R X_old + t between the LEFT camera frames, R row-major.  From two poses of the left camera in a
+ *              world frame: T_new_old = T_world_new^-1 * T_world_old.  R is NOT checked for orthonormality: the arithmetic
+ *              below is defined for any finite R and t.
+ *   splat      a source pixel (x, y) with value d takes part iff d > 0 and d >= min_disp (binary32: never for NaN).  In
+ *              binary64, fxB = fx * baseline formed once:  Z = fxB / (double)d;  X = (((double)x - cx) * Z) / fx;
+ *              Y = (((double)y - cy) * Z) / fy  (pm_backproject's values before their rounding);
+ *              Xn = (((R0*X) + (R1*Y)) + (R2*Z)) + t0;  Yn with R3..R5 and t1;  Zn with R6..R8 and t2;  dropped unless
+ *              Zn > 0;  dn = (float)(fxB / Zn), dropped unless dn > 0 and finite, and unless dn <= max_disp where
+ *              max_disp != 0;  u = (fx * (Xn / Zn)) + cx;  v = (fy * (Yn / Zn)) + cy;  dropped unless |u| < 2^30 and
+ *              |v| < 2^30;  iu = rint(u), iv = rint(v), half to even;  dropped unless 0 <= iu < cols and 0 <= iv < rows.
+ *              S_l(iv, iu) = the binary32 maximum of dn over every source pixel that lands there: the nearest surface wins.
+ *              Pixels nobody lands on are +0.0.
+ *   close      C(y, x) = S(y, x) where S(y, x) > 0; elsewhere the maximum of S over the (2r+1)^2 window, r = close_radius,
+ *              taps outside the image not counting, 0 if no tap is > 0.  r = 0 copies.  It closes the one-pixel cracks a
+ *              forward splat leaves when the camera advances or turns and never alters a pixel that was hit.
+ *   right      from the CLOSED left seed C_l: every (x, y) with s = C_l(y, x) > 0 gives q = rint((double)x - (double)s),
+ *              dropped unless 0 <= q < cols;  S_r(y, q) = the maximum of s over its contributors, else +0.0 -- a map in
+ *              right-image coordinates, the convention pm_mask_occlusions reads.  Then the same close with the same r.
+ *   counts     counts[0] / d_counts[0] = pixels > 0 of C_l (d_seed_l), [1] = pixels > 0 of C_r (d_seed_r).
+ * At least one of d_seed_l, d_seed_r, d_counts, counts must be given; d_seed_r alone is legal (the left seed then lives in
+ * scratch only).  d_seed_l and d_seed_r must not alias d_disp.  Valid in every mode of the handle: it reads a map, not the
+ * handle's state.  It enqueues on the handle's stream; a non-NULL `counts` synchronises it like pm_point_cloud's `count`,
+ * otherwise the call only enqueues.  pm_submit_device is NOT ordered behind the handle's stream: record an event on
+ * pm_stream(h) behind this call and hand it to pm_submit_device_after with the two seed maps.
+ * One memset and four launches, none of which waits for another workgroup (the splat with one integer atomicMax per
+ * surviving pixel, close + count over an LDS tile with an r-wide halo, the right splat, close + count again); only integer
+ * maximum and integer addition cross workgroups, so the result does not depend on the order of arrival.  Scratch (two maps
+ * of 4 bytes per pixel and the counts; a third map where d_seed_l is NULL) is ONE allocation, made on first use, reused, and
+ * released with the handle; growing it synchronises the stream, so a size must have run once before it is captured.
+ * PM_ERR_INVALID_ARG, with pm_last_error naming the argument and nothing enqueued: a null camera, motion, options or d_disp;
+ * a camera pm_backproject refuses; a non-finite entry of R or t; a NaN or negative min_disp / max_disp; a close_radius
+ * outside 0..3; rows or cols < 1; no output at all; an output equal to d_disp.  PM_ERR_SIZE as for pm_backproject. */
+typedef struct pm_motion { double R[9]; double t[3]; } pm_motion;   /* X_new = R X_old + t, left camera frames */
+typedef struct pm_reproject_options { float min_disp; float max_disp; int close_radius; } pm_reproject_options;
+int pm_reproject_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_motion* motion,
+                           const pm_reproject_options* options, const float* d_disp, int rows, int cols,
+                           float* d_seed_l /* may be NULL */, float* d_seed_r /* may be NULL */,
+                           int* d_counts /* device int[2], may be NULL */, int* counts /* host int[2], may be NULL */);
+
 /* ---- device buffers for host code that does not include HIP (host/imaging.hpp uses them) ------------------
  * pm_device_malloc / pm_device_free wrap hipMalloc / hipFree on the handle's device; pm_upload / pm_download are
  * stream-ordered copies on the handle's stream from / to pageable host memory (pm_download returns after the

@@ -101,6 +101,11 @@ void pm_debug_speckle_constants(int* tile_cols, int* tile_rows);
  * needs to reach their carries.  No handle, no device. */
 void pm_debug_mesh_constants(int* items_per_block, int* blocks_per_scan_pass);
 
+/* ---- pm_reproject_disparity's launch constants (csrc/pm_reproject_body.hpp) ------------------------------------------------
+ * tile_w x tile_h: the pixels one block of the close + count launch owns; it stages them with a close_radius-wide halo.
+ * Tests place holes on tile borders and corners with them.  No handle, no device. */
+void pm_debug_reproject_constants(int* tile_w, int* tile_h);
+
 /* ---- the row-tiled driver's device discipline, provable on ONE GPU ------------------------------------------------
  * pm_tiled_create with the bands accounted to LOGICAL devices: band k lives on logical_devices[k] (>= 0; several bands
  * may share one) while every HIP call still goes to the physical device of the band's handle.  Such a plan logs every

@@ -13,6 +13,8 @@
 //                        pm_normals_fit.hpp (k_normals_fit<R>) among them; sees the handle through pm_internal.hpp only
 //     pm_speckle.hpp     the four kernels of pm_filter_speckles (k_speckle_local / _merge / _flatten / _apply)
 //     pm_mesh.hpp        the three kernels of pm_grid_mesh (k_mesh_count / _vertices / _triangles)
+//     pm_reproject.hpp   the three kernels of pm_reproject_disparity (k_reproject_splat / _splat_right / _finish); their
+//                        bodies are pm_reproject_body.hpp's
 // Every __global__ kernel lives in exactly one unit; the others reach it through the launch functions declared here.
 #pragma once
 

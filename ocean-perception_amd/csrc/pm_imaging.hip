@@ -22,6 +22,7 @@
 #include "pm_mesh.hpp"
 #include "pm_normals_fit.hpp"
 #include "pm_rectify.hpp"
+#include "pm_reproject.hpp"
 #include "pm_speckle.hpp"
 #include "pm_tune.hpp"
 
@@ -57,6 +58,9 @@ struct ImagingState {
   // pm_grid_mesh: [0] the vertex count, [1] the triangle count, then one word per block of kMeshBlock items for each of
   // the two (its count, then its offset), then the organised slot map, one word per grid item
   DevBuf<int> mesh_buf;
+  // pm_reproject_disparity: kReprojectHeader words ([0], [1]: the counts), the left and the right splat map, one word per
+  // pixel each (the memset of a call clears up to here), then the closed left seed of a call without d_seed_l
+  DevBuf<unsigned> reproject_buf;
 };
 
 #define PM_HIP(h, call)                                                                                     \
@@ -1157,6 +1161,92 @@ int pm_grid_mesh(pm_handle* h, const pm_cloud_camera* camera, const pm_cloud_fil
 void pm_debug_mesh_constants(int* items_per_block, int* blocks_per_scan_pass) {
   if (items_per_block) *items_per_block = kMeshBlock;
   if (blocks_per_scan_pass) *blocks_per_scan_pass = kCloudScanThreads;
+}
+
+// ---- temporal seeds: a map carried into the next frame's two seed maps (pm_reproject.hpp) ------------------------------------
+namespace {
+constexpr size_t kReprojectHeader = 4;  // words in front of the maps: the two counts, padded to 16 bytes
+}
+
+int pm_reproject_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_motion* motion,
+                           const pm_reproject_options* options, const float* d_disp, int rows, int cols, float* d_seed_l,
+                           float* d_seed_r, int* d_counts, int* counts) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_reproject_disparity";
+  if (int rc = check_cloud_camera(h, what, camera)) return rc;
+  if (!motion || !options || !d_disp) {
+    set_err(h, "%s: null %s", what, !motion ? "motion" : !options ? "options" : "d_disp");
+    return PM_ERR_INVALID_ARG;
+  }
+  for (int i = 0; i < 12; ++i)
+    if (!std::isfinite(i < 9 ? motion->R[i] : motion->t[i - 9])) {
+      set_err(h, "%s: %s[%d] of the motion is not finite", what, i < 9 ? "R" : "t", i < 9 ? i : i - 9);
+      return PM_ERR_INVALID_ARG;
+    }
+  if (!(options->min_disp >= 0.f) || !(options->max_disp >= 0.f)) {
+    set_err(h, "%s: %s must be >= 0 and not NaN%s", what, !(options->min_disp >= 0.f) ? "min_disp" : "max_disp",
+            !(options->min_disp >= 0.f) ? "" : " (0 = no limit)");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (options->close_radius < 0 || options->close_radius > kReprojectMaxRadius) {
+    set_err(h, "%s: close_radius %d must be 0 .. %d", what, options->close_radius, kReprojectMaxRadius);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
+  if (!d_seed_l && !d_seed_r && !d_counts && !counts) {
+    set_err(h, "%s: no output: d_seed_l, d_seed_r, d_counts and counts are all null", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (d_seed_l == d_disp || d_seed_r == d_disp) {
+    set_err(h, "%s: %s must not alias d_disp", what, d_seed_l == d_disp ? "d_seed_l" : "d_seed_r");
+    return PM_ERR_INVALID_ARG;
+  }
+  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
+  ImagingState* st = state_of(h);
+  if (!st) {
+    set_err(h, "%s: out of host memory", what);
+    return PM_ERR_NOMEM;
+  }
+  const size_t px = (size_t)rows * cols;
+  const size_t cleared = kReprojectHeader + 2 * px;
+  hipStream_t stream = pm_internal::stream(h);
+  PM_HIP(h, st->reproject_buf.reserve(sizeof(unsigned) * (cleared + (d_seed_l ? 0 : px)), stream));
+  unsigned* base = st->reproject_buf.get();
+  int* d_totals = reinterpret_cast<int*>(base);
+  unsigned* splat_l = base + kReprojectHeader;
+  unsigned* splat_r = splat_l + px;
+  unsigned* closed_l = d_seed_l ? reinterpret_cast<unsigned*>(d_seed_l) : splat_r + px;
+  PM_HIP(h, hipMemsetAsync(base, 0, sizeof(unsigned) * cleared, stream));
+  ReprojectArgs a = {cloud_cam(*camera), {}, {}, options->min_disp, options->max_disp, d_disp, rows, cols, splat_l};
+  for (int i = 0; i < 9; ++i) a.R[i] = motion->R[i];
+  for (int i = 0; i < 3; ++i) a.t[i] = motion->t[i];
+  const int span = kReprojectSpan;
+  const dim3 block(kReprojectBlockX, kReprojectBlockY);
+  const dim3 splat_grid((unsigned)((cols + span - 1) / span), (unsigned)((rows + kReprojectBlockY - 1) / kReprojectBlockY));
+  const dim3 tile_grid((unsigned)((cols + kReprojectTileW - 1) / kReprojectTileW),
+                       (unsigned)((rows + kReprojectTileH - 1) / kReprojectTileH));
+  const int r = options->close_radius;
+  hipLaunchKernelGGL(k_reproject_splat, splat_grid, block, 0, stream, a);
+  hipLaunchKernelGGL(k_reproject_finish, tile_grid, block, 0, stream,
+                     ReprojectFinishArgs{splat_l, closed_l, rows, cols, r, d_totals});
+  if (d_seed_r || d_counts || counts) {  // the right view: from the CLOSED left seed
+    hipLaunchKernelGGL(k_reproject_splat_right, splat_grid, block, 0, stream,
+                       ReprojectRightArgs{reinterpret_cast<const float*>(closed_l), rows, cols, splat_r});
+    hipLaunchKernelGGL(k_reproject_finish, tile_grid, block, 0, stream,
+                       ReprojectFinishArgs{splat_r, reinterpret_cast<unsigned*>(d_seed_r), rows, cols, r, d_totals + 1});
+  }
+  if (int rc = launch_check(h, "reproject disparity")) return rc;
+  if (d_counts) PM_HIP(h, hipMemcpyAsync(d_counts, d_totals, 2 * sizeof(int), hipMemcpyDeviceToDevice, stream));
+  if (counts) {
+    PM_HIP(h, hipMemcpyAsync(counts, d_totals, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+    PM_HIP(h, hipStreamSynchronize(stream));
+  }
+  return PM_OK;
+}
+
+void pm_debug_reproject_constants(int* tile_w, int* tile_h) {
+  if (tile_w) *tile_w = kReprojectTileW;
+  if (tile_h) *tile_h = kReprojectTileH;
 }
 
 // Host only: Bouguet's construction (see pm/imaging.h).

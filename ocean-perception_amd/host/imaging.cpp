@@ -428,6 +428,42 @@ void WritePly(const std::string& path, const TriangleMesh& mesh) {
   if (!ok) throw std::runtime_error("WritePly: cannot write " + path);
 }
 
+Motion RelativeMotion(const double T_world_old[16], const double T_world_new[16]) {
+  // with T = [R | p]:  T_new^-1 = [Rn^T | -Rn^T pn], so  R = Rn^T Ro  and  t = Rn^T (po - pn)
+  const double* A = T_world_old;
+  const double* B = T_world_new;
+  Motion m;
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) {
+      double s = 0;
+      for (int k = 0; k < 3; ++k) s += B[4 * k + i] * A[4 * k + j];
+      m.R[(size_t)(3 * i + j)] = s;
+    }
+    double s = 0;
+    for (int k = 0; k < 3; ++k) s += B[4 * k + i] * (A[4 * k + 3] - B[4 * k + 3]);
+    m.t[(size_t)i] = s;
+  }
+  return m;
+}
+
+std::array<int, 2> ReprojectDisparity(pm::PatchmatchGpu& matcher, const StereoModel& model, const Motion& motion,
+                                      const float* d_disp, int rows, int cols, float* d_seed_l, float* d_seed_r,
+                                      const ReprojectOptions& options, bool want_counts) {
+  pm_handle* h = matcher.handle();
+  if (!h) throw std::runtime_error("ReprojectDisparity: the matcher has no handle yet (plan it or match once)");
+  const pm_cloud_camera cam = CloudCamera(model);
+  pm_motion m;
+  for (size_t i = 0; i < 9; ++i) m.R[i] = motion.R[i];
+  for (size_t i = 0; i < 3; ++i) m.t[i] = motion.t[i];
+  const pm_reproject_options opt = {options.min_disp, options.max_disp, options.close_radius};
+  int counts[2] = {-1, -1};
+  const int rc = pm_reproject_disparity(h, &cam, &m, &opt, d_disp, rows, cols, d_seed_l, d_seed_r, nullptr,
+                                        want_counts ? counts : nullptr);
+  if (rc != PM_OK)  // the matcher's handle, not the imaging context's
+    throw std::runtime_error(std::string("pm_reproject_disparity: ") + pm_status_string(rc) + " -- " + pm_last_error(h));
+  return {{counts[0], counts[1]}};
+}
+
 core::Image<core::Vec3f> DisparityNormals(const core::Image<float>& disp, const StereoModel& model, const NormalsFit& fit,
                                           core::Image<uint8_t>* support) {
   if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("DisparityNormals: empty map");

@@ -154,5 +154,30 @@ TriangleMesh MakeGridMesh(const core::Image<float>& disp, const StereoModel& mod
 // std::runtime_error where the file cannot be written.
 void WritePly(const std::string& path, const TriangleMesh& mesh);
 
+// Between two frames of a sequence: the OLD frame's left map carried into the NEW frame's two seed maps through the rigid
+// motion between the two left cameras (pm/imaging.h: pm_reproject_disparity; definition: tests/reproject_ref.py).  Unlike
+// the functions above it takes DEVICE pointers and works on the matcher's own handle and stream, because that is where a
+// sequence lives: the maps a device Match() left behind go in, and the seeds go to pm_submit_device_after behind an event
+// recorded on pm_stream(matcher.handle()).
+struct Motion {  // pm_motion: X_new = R X_old + t between the left camera frames, R row-major
+  std::array<double, 9> R{{1, 0, 0, 0, 1, 0, 0, 0, 1}};
+  std::array<double, 3> t{{0, 0, 0}};
+};
+struct ReprojectOptions {  // pm_reproject_options
+  float min_disp = 0.f;  // a source pixel takes part iff disp > 0 and disp >= min_disp
+  float max_disp = 0.f;  // > 0: a carried disparity above it is dropped; 0 = no limit
+  int close_radius = 1;  // 0..3: holes take the maximum of their (2 r + 1)^2 window
+};
+// Host only: T_new_old = T_world_new^-1 * T_world_old for two rigid 4x4 poses of the left camera (camera to world,
+// row-major; the last row is taken to be 0 0 0 1 and the rotation block to be orthonormal).
+Motion RelativeMotion(const double T_world_old[16], const double T_world_new[16]);
+// d_seed_l / d_seed_r: device maps of rows x cols floats, either may be null.  Returns {pixels > 0 of d_seed_l, of d_seed_r}
+// and synchronises the matcher's stream for them; with want_counts = false it only enqueues and returns {-1, -1}.  The
+// matcher must have planned its handle (Params::max_rows / max_cols, or a first Match()).  Throws std::runtime_error where
+// pm_reproject_disparity refuses.
+std::array<int, 2> ReprojectDisparity(pm::PatchmatchGpu& matcher, const StereoModel& model, const Motion& motion,
+                                      const float* d_disp, int rows, int cols, float* d_seed_l, float* d_seed_r,
+                                      const ReprojectOptions& options = ReprojectOptions(), bool want_counts = true);
+
 }  // namespace imaging
 }  // namespace bm

@@ -47,6 +47,7 @@ EXPORTS = [
     "pm_disparity_normals", "pm_debug_normals_fit_constants",
     "pm_filter_speckles", "pm_debug_speckle_constants",
     "pm_grid_mesh", "pm_debug_mesh_constants",
+    "pm_reproject_disparity", "pm_debug_reproject_constants",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
     "pm_debug_sweep_plan", "pm_debug_noise_cost_constants", "pm_debug_noise_cost", "pm_debug_remove_background",
     "pm_remove_background", "pm_mask_occlusions", "pm_foreground_texture_mask", "pm_sparse_init", "pm_corner_subpix", "pm_profile_enable", "pm_profile_read",
@@ -192,6 +193,32 @@ def noise_cost_constants():
     a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
     load().pm_debug_noise_cost_constants(C.byref(a), C.byref(b), C.byref(c))
     return a.value, b.value, c.value
+
+
+class PmMotion(C.Structure):  # pm_reproject_disparity: X_new = R X_old + t between the left camera frames
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3)]
+
+
+class PmReprojectOptions(C.Structure):
+    _fields_ = [("min_disp", C.c_float), ("max_disp", C.c_float), ("close_radius", C.c_int)]
+
+
+def as_motion(values):
+    """A PmMotion from (R, t) -- R: 9 values row-major or 3x3, t: 3 values; a PmMotion or None passes through."""
+    if values is None or isinstance(values, PmMotion):
+        return values
+    R, t = values
+    m = PmMotion()
+    m.R[:] = [float(v) for v in np.asarray(R, np.float64).ravel()]
+    m.t[:] = [float(v) for v in np.asarray(t, np.float64).ravel()]
+    return m
+
+
+def reproject_constants():
+    """pm_debug_reproject_constants: (tile_w, tile_h) of the close + count launch."""
+    a, b = C.c_int(0), C.c_int(0)
+    load().pm_debug_reproject_constants(C.byref(a), C.byref(b))
+    return a.value, b.value
 
 
 def cloud_camera(values):
@@ -368,6 +395,11 @@ def load():
     lib.pm_grid_mesh.restype = C.c_int
     lib.pm_debug_mesh_constants.argtypes = [C.POINTER(C.c_int)] * 2
     lib.pm_debug_mesh_constants.restype = None
+    lib.pm_reproject_disparity.argtypes = [vp, C.POINTER(PmCloudCamera), C.POINTER(PmMotion), C.POINTER(PmReprojectOptions), vp,
+                                           C.c_int, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
+    lib.pm_reproject_disparity.restype = C.c_int
+    lib.pm_debug_reproject_constants.argtypes = [C.POINTER(C.c_int)] * 2
+    lib.pm_debug_reproject_constants.restype = None
     lib.pm_device_malloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     lib.pm_device_free.argtypes = [vp, vp]
     lib.pm_upload.argtypes = [vp, vp, vp, C.c_size_t]
@@ -897,6 +929,21 @@ class Engine:
                                           d_bgr8, rows, cols, vertex_capacity, tri_capacity, d_xyz_out, d_normals_out, d_bgr8_out,
                                           d_index_out, d_tri_out, d_counts, n if host_counts else None), "pm_grid_mesh")
         return (n[0], n[1]) if host_counts else None
+
+    def reproject_disparity(self, camera, motion, d_disp, rows, cols, min_disp=0.0, max_disp=0.0, close_radius=1,
+                            d_seed_l=None, d_seed_r=None, d_counts=None, want_counts=False):
+        """pm_reproject_disparity (raw device addresses): the old frame's left map into the new frame's two seed maps, on the
+        handle's stream.  motion: (R, t) or a PmMotion.  -> (pixels > 0 of d_seed_l, of d_seed_r) with want_counts (the call
+        then synchronises), else None (it only enqueues).  d_counts: two device ints."""
+        c = cloud_camera(camera)
+        m = as_motion(motion)
+        o = PmReprojectOptions(min_disp, max_disp, close_radius)
+        n = (C.c_int * 2)(-1, -1)
+        self._check(self.lib.pm_reproject_disparity(self.h, C.byref(c) if c is not None else None,
+                                                    C.byref(m) if m is not None else None, C.byref(o), d_disp, rows, cols,
+                                                    d_seed_l, d_seed_r, d_counts, n if want_counts else None),
+                    "pm_reproject_disparity")
+        return (n[0], n[1]) if want_counts else None
 
     def normalize(self, d_bgr, rows, cols, d_out):
         self._check(self.lib.pm_normalize(self.h, d_bgr, rows, cols, d_out), "pm_normalize")
