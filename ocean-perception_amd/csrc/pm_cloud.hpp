@@ -1,4 +1,4 @@
-// pm_cloud.hpp -- the kernels of pm_backproject and pm_point_cloud (include/pm/imaging.h); included by pm_imaging.hip
+// pm_cloud.hpp -- the kernels of pm_backproject and pm_point_cloud (include/pm/imaging.h); included by pm_stages.hip
 // alone.  The arithmetic and the per-thread bodies (backproject_four, cloud_item, cloud_store) are pm_cloud_body.hpp's,
 // the definition is tests/pointcloud_ref.py (DESIGN.md sections 8b, 8c).
 //

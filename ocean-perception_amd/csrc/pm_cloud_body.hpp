@@ -1,6 +1,6 @@
 // pm_cloud_body.hpp -- the per-pixel arithmetic and the per-thread bodies of the point-cloud stages (include/pm/imaging.h:
 // pm_backproject, pm_planes_normals, pm_point_cloud), host-callable and free of kernels, so that the two translation units
-// that use it (pm_imaging.hip through pm_cloud.hpp, pm_planes_host.hip through pm_planes.hpp) and a CPU build
+// that use it (pm_stages.hip through pm_cloud.hpp, pm_planes_host.hip through pm_planes.hpp) and a CPU build
 // (tests/cpp/cloud_host_main.cpp, under the sanitizers) share ONE statement of it.  The definition it is held to BIT FOR
 // BIT is tests/pointcloud_ref.py: every operation is one rounding in the format written,
 // parentheses as written (the build uses -ffp-contract=off; binary64 division is IEEE on gfx950; binary32 division and
@@ -107,6 +107,14 @@ struct CloudArgs {
   int rows, cols, sub_cols;
   long long items;
 };
+
+// The stride grid of a rows x cols map (host only): cloud_grid of the rows and of the columns, and the launch's arguments.
+inline int cloud_grid(int n, int stride) { return (n + stride - 1) / stride; }
+inline CloudArgs cloud_args(const pm_cloud_camera& camera, const pm_cloud_filter& filter, const float* d_disp, int rows,
+                            int cols) {
+  const int sub_rows = cloud_grid(rows, filter.stride), sub_cols = cloud_grid(cols, filter.stride);
+  return CloudArgs{cloud_cam(camera), filter, d_disp, rows, cols, sub_cols, (long long)sub_rows * sub_cols};
+}
 
 // Item `item` of the stride grid: its pixel, its point, and whether it counts.  item < a.items.
 __host__ __device__ __forceinline__ bool cloud_item(const CloudArgs& a, long long item, int* x, int* y, float p[3]) {

@@ -1333,7 +1333,7 @@ int pm_profile_read(pm_handle* h, pm_profile* out) {
 }  // extern "C"
 
 
-// ---- the narrow interface pm_imaging.hip works through (pm_internal.hpp) ---------------------------------------
+// ---- the narrow interface pm_imaging.hip and pm_stages.hip work through (pm_internal.hpp) -----------------------
 namespace pm_internal {
 int device(const pm_handle* h) { return h->device; }
 hipStream_t stream(pm_handle* h) { return h->stream; }

@@ -9,8 +9,11 @@
 //   pm_hostpath.hip      host-buffer entry points (pm_match_u8, submit / collect, the single-stage functions)
 //   pm_tile.hip          the row-tiled phase API pm_tile_*
 //   pm_tiled.hip         pm_tiled_*: n band handles of one process driven over that API
-//   pm_imaging.hip       the imaging rows, the point and cloud kernels of pm_cloud.hpp and the plane-fit kernel of
-//                        pm_normals_fit.hpp (k_normals_fit<R>) among them; sees the handle through pm_internal.hpp only
+//   pm_imaging.hip       the imaging rows (range, enhancement, guided filter, rectification) and the device-buffer
+//                        helpers; sees the handle through pm_internal.hpp only
+//   pm_stages.hip        the stages that read a finished disparity map: the point and cloud kernels of pm_cloud.hpp and the
+//                        plane-fit kernel of pm_normals_fit.hpp (k_normals_fit<R>) among them; sees the handle through
+//                        pm_internal.hpp only and shares pm_imaging.hip's state (pm_imaging_state.hpp)
 //     pm_speckle.hpp     the four kernels of pm_filter_speckles (k_speckle_local / _merge / _flatten / _apply)
 //     pm_mesh.hpp        the three kernels of pm_grid_mesh (k_mesh_count / _vertices / _triangles)
 //     pm_reproject.hpp   the three kernels of pm_reproject_disparity (k_reproject_splat / _splat_right / _finish); their
@@ -149,7 +152,7 @@ struct pm_handle {
   int late_view = 1;
   pm::Event out_join;  // s_out -> the handle's stream at the end of a batch
   pm::Event in_join;   // s_in -> the handle's stream (only when a capture is ended with the head stream unjoined)
-  void* imaging_state = nullptr;  // owned by pm_imaging.hip (pm_internal.hpp)
+  void* imaging_state = nullptr;  // pm_imaging_state.hpp's, released by pm_imaging.hip (pm_internal.hpp)
   pm::DevBuf<void> texmask_scratch;  // pm_foreground_texture_mask: four byte planes, allocated on first use
   // pm_match_bgr_device: the next Match reads enhanced BGR inputs through k_prep_bgr instead of 8-bit gray images
   const pm::BgrSource* bgr = nullptr;

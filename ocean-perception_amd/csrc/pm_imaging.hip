@@ -1,8 +1,10 @@
-// pm_imaging.hip -- C-ABI implementation of include/pm/imaging.h: the rows either side of the stereo hot path
-//  and the device-buffer helpers.  A separate translation unit: it reaches the handle only
-// through pm_internal.hpp (device, stream, error text, one opaque state slot).
+// pm_imaging.hip -- C-ABI implementation of the imaging rows of include/pm/imaging.h: range and the range-dependent
+// corrections, the stereo-ready enhancement, the guided filter and the pixel gather, undistortion
+// and rectification in front of Match(), pm_stereo_rectify, and the device-buffer helpers.  The stages that read a
+// finished disparity map are pm_stages.hip's.  A separate translation unit: it reaches the handle only through
+// pm_internal.hpp (device, stream, error text, one opaque state slot); the state in that slot is
+// pm_imaging_state.hpp's, shared with pm_stages.hip and released here.
 #include "pm/imaging.h"
-#include "pm/testing.h"
 
 #include <hip/hip_runtime.h>
 
@@ -10,86 +12,16 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <new>
 #include <vector>
 
-#include "pm_cloud.hpp"
-#include "pm_devbuf.hpp"
 #include "pm_enhance.hpp"
 #include "pm_guided.hpp"
 #include "pm_imaging.hpp"
-#include "pm_internal.hpp"
-#include "pm_mesh.hpp"
-#include "pm_normals_fit.hpp"
+#include "pm_imaging_state.hpp"
 #include "pm_rectify.hpp"
-#include "pm_reproject.hpp"
-#include "pm_speckle.hpp"
 #include "pm_tune.hpp"
 
 using namespace pm;
-
-namespace {
-
-// Device state of the imaging entry points, created on first use and released by pm_destroy.  The scratch buffers grow
-// to the largest size asked for (DevBuf::reserve).
-struct ImagingState {
-  DevBuf<unsigned> img_scalars;  // device: [0] max range / min disparity bits, [1] dark-pixel count, [2..3] V min / max
-  // stereo-ready enhancement: row-pass output, bgr / illuminant, Gaussian taps
-  DevBuf<float> enh_tmp;
-  DevBuf<float> enh_q;
-  DevBuf<float> enh_taps;
-  int enh_ksize = 0;  // what enh_taps holds
-  double enh_sigma = 0;
-  // pm_match_bgr_device: blurred illuminants of n pairs (left, right) and their value min / max words
-  DevBuf<float> bgr_blur;
-  DevBuf<unsigned> bgr_mm;
-  // fast guided filter: binary64 row sums, a / b planes, interleaved mean_a / mean_b of the coarse image (one allocation)
-  DevBuf<char> gf_buf;
-  // pm_gather_pixels: [bad flag, pad][n x channels floats][n x 2 coordinates]
-  DevBuf<char> gat_buf;
-  // pm_match_raw_device: the rectified pairs, [left, right][n][rows][cols] bytes; pm_match_raw_bgr_device: the rectified
-  // BGR images the caller did not ask for, [n][rows][cols][3] bytes each
-  DevBuf<uint8_t> rect_buf;
-  // pm_point_cloud: [0] the count, [1 ..] one word per block of kCloudBlock items: its count, then its offset
-  DevBuf<int> cloud_blocks;
-  // pm_filter_speckles: [0] the removed count (kSpeckleHeader words, cleared per call), then the working labels and the
-  // root sizes, one word per pixel each
-  DevBuf<int> speckle_buf;
-  // pm_grid_mesh: [0] the vertex count, [1] the triangle count, then one word per block of kMeshBlock items for each of
-  // the two (its count, then its offset), then the organised slot map, one word per grid item
-  DevBuf<int> mesh_buf;
-  // pm_reproject_disparity: kReprojectHeader words ([0], [1]: the counts), the left and the right splat map, one word per
-  // pixel each (the memset of a call clears up to here), then the closed left seed of a call without d_seed_l
-  DevBuf<unsigned> reproject_buf;
-};
-
-#define PM_HIP(h, call)                                                                                     \
-  do {                                                                                                      \
-    hipError_t e_ = (call);                                                                                 \
-    if (e_ != hipSuccess) {                                                                                 \
-      pm_internal::set_error((h), "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return PM_ERR_HIP;                                                                                    \
-    }                                                                                                       \
-  } while (0)
-
-#define set_err pm_internal::set_error
-
-int launch_check(pm_handle* h, const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_err(h, "launch of %s failed: %s", what, hipGetErrorString(e));
-    return PM_ERR_HIP;
-  }
-  return PM_OK;
-}
-
-ImagingState* state_of(pm_handle* h) {
-  void** slot = pm_internal::imaging_slot(h);
-  if (!*slot) *slot = new (std::nothrow) ImagingState();
-  return static_cast<ImagingState*>(*slot);
-}
-
-}  // namespace
 
 void pm_internal::release_imaging(pm_handle* h) {
   void** slot = pm_internal::imaging_slot(h);
@@ -805,448 +737,6 @@ int pm_match_raw_bgr_device(pm_handle* h, int n, const pm_rectify_view* left, co
   return match_raw(h, "pm_match_raw_bgr_device", 3, pm_match_bgr_device, n, left, right, d_left_raw_bgr8, d_right_raw_bgr8,
                    src_rows, src_cols, src_step, rows, cols, d_seed_l, d_seed_r, d_disp_l, d_disp_r, d_left_rect_bgr8,
                    d_right_rect_bgr8);
-}
-
-// ---- points, plane-mode normals and the compacted cloud behind the range stages (pm_cloud.hpp) -------------------------
-namespace {
-
-int check_cloud_camera(pm_handle* h, const char* what, const pm_cloud_camera* cam) {
-  if (!cam) {
-    set_err(h, "%s: null camera", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  static const char* const names[5] = {"fx", "fy", "cx", "cy", "baseline"};
-  const double* e = reinterpret_cast<const double*>(cam);
-  static_assert(sizeof(pm_cloud_camera) == 5 * sizeof(double), "pm_cloud_camera is 5 doubles");
-  for (int i = 0; i < 5; ++i)
-    if (!std::isfinite(e[i])) {
-      set_err(h, "%s: %s of the camera is not finite", what, names[i]);
-      return PM_ERR_INVALID_ARG;
-    }
-  if (cam->fx == 0.0 || cam->fy == 0.0) {
-    set_err(h, "%s: fx / fy of the camera must not be 0", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  return PM_OK;
-}
-
-int check_cloud_shape(pm_handle* h, const char* what, int rows, int cols) {
-  if (rows < 1 || cols < 1) {
-    set_err(h, "%s: empty image (%dx%d)", what, cols, rows);
-    return PM_ERR_INVALID_ARG;
-  }
-  if ((long long)rows * cols > INT32_MAX || (rows + kCloudBlockY - 1) / kCloudBlockY > 65535) {
-    set_err(h, "%s: %dx%d pixels exceed a 32-bit pixel index or the launch grid", what, cols, rows);
-    return PM_ERR_SIZE;
-  }
-  return PM_OK;
-}
-
-}  // namespace
-
-int pm_backproject(pm_handle* h, const pm_cloud_camera* camera, const float* d_disp, int rows, int cols, float* d_xyz) {
-  if (!h) return PM_ERR_INVALID_ARG;
-  if (int rc = check_cloud_camera(h, "pm_backproject", camera)) return rc;
-  if (!d_disp || !d_xyz) {
-    set_err(h, "pm_backproject: null %s", !d_disp ? "d_disp" : "d_xyz");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (int rc = check_cloud_shape(h, "pm_backproject", rows, cols)) return rc;
-  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
-  const BackprojectArgs a = {cloud_cam(*camera), d_disp, rows, cols, d_xyz};
-  const int px = kCloudBlockX * 4;
-  const dim3 grid((unsigned)((cols + px - 1) / px), (unsigned)((rows + kCloudBlockY - 1) / kCloudBlockY));
-  hipLaunchKernelGGL(k_backproject, grid, dim3(kCloudBlockX, kCloudBlockY), 0, pm_internal::stream(h), a);
-  return launch_check(h, "backproject");
-}
-
-int pm_planes_normals(pm_handle* h, int pair, const pm_cloud_camera* camera, const float* d_disp_l, int rows, int cols,
-                      float* d_normals) {
-  if (!h) return PM_ERR_INVALID_ARG;
-  if (int rc = check_cloud_camera(h, "pm_planes_normals", camera)) return rc;
-  if (!d_normals || pair < 0) {
-    set_err(h, "pm_planes_normals: %s", !d_normals ? "null d_normals" : "negative pair");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (int rc = check_cloud_shape(h, "pm_planes_normals", rows, cols)) return rc;
-  return pm_internal::planes_normals(h, pair, cloud_cam(*camera), d_disp_l, rows, cols, d_normals);
-}
-
-int pm_point_cloud(pm_handle* h, const pm_cloud_camera* camera, const pm_cloud_filter* filter, const float* d_disp,
-                   const float* d_normals, const uint8_t* d_bgr8, int rows, int cols, int capacity, float* d_xyz_out,
-                   float* d_normals_out, uint8_t* d_bgr8_out, int32_t* d_index_out, int* d_count, int* count) {
-  if (!h) return PM_ERR_INVALID_ARG;
-  const char* const what = "pm_point_cloud";
-  if (int rc = check_cloud_camera(h, what, camera)) return rc;
-  if (!filter || !d_disp) {
-    set_err(h, "%s: null %s", what, !filter ? "filter" : "d_disp");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (filter->stride < 1) {
-    set_err(h, "%s: stride %d must be >= 1", what, filter->stride);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (std::isnan(filter->min_disp) || !(filter->max_range >= 0.f)) {
-    set_err(h, "%s: min_disp must not be NaN and max_range must be >= 0 (0 = no limit)", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (capacity < 0) {
-    set_err(h, "%s: capacity %d must be >= 0", what, capacity);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (d_normals_out && !d_normals) {
-    set_err(h, "%s: d_normals_out requested without d_normals", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (d_bgr8_out && !d_bgr8) {
-    set_err(h, "%s: d_bgr8_out requested without d_bgr8", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
-  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
-  ImagingState* st = state_of(h);
-  if (!st) {
-    set_err(h, "%s: out of host memory", what);
-    return PM_ERR_NOMEM;
-  }
-  const int stride = filter->stride;
-  const int sub_rows = (rows + stride - 1) / stride, sub_cols = (cols + stride - 1) / stride;
-  const CloudArgs a = {cloud_cam(*camera), *filter, d_disp, rows, cols, sub_cols, (long long)sub_rows * sub_cols};
-  const int blocks = (int)((a.items + kCloudBlock - 1) / kCloudBlock);
-  hipStream_t stream = pm_internal::stream(h);
-  PM_HIP(h, st->cloud_blocks.reserve(sizeof(int) * ((size_t)blocks + 1), stream));
-  int* d_total = st->cloud_blocks.get();
-  int* d_blocks = d_total + 1;
-  const CloudStreams s = {d_normals, d_bgr8, d_xyz_out, d_normals_out, d_bgr8_out, d_index_out, capacity};
-  hipLaunchKernelGGL(k_cloud_count, dim3((unsigned)blocks), dim3(kCloudBlock), 0, stream, a, d_blocks);
-  hipLaunchKernelGGL(k_cloud_offsets, dim3(1), dim3(kCloudScanThreads), 0, stream, d_blocks, blocks, d_total, d_count);
-  if (capacity > 0 && (d_xyz_out || d_normals_out || d_bgr8_out || d_index_out))
-    hipLaunchKernelGGL(k_cloud_scatter, dim3((unsigned)blocks), dim3(kCloudBlock), 0, stream, a, (const int*)d_blocks, s);
-  if (int rc = launch_check(h, "point cloud")) return rc;
-  if (count) {
-    PM_HIP(h, hipMemcpyAsync(count, d_total, sizeof(int), hipMemcpyDeviceToHost, stream));
-    PM_HIP(h, hipStreamSynchronize(stream));
-  }
-  return PM_OK;
-}
-
-void pm_debug_cloud_constants(int* items_per_block, int* blocks_per_scan_pass) {
-  if (items_per_block) *items_per_block = kCloudBlock;
-  if (blocks_per_scan_pass) *blocks_per_scan_pass = kCloudScanThreads;
-}
-
-// ---- normals for scalar-mode maps: the windowed plane fit (pm_normals_fit.hpp) ---------------------------------------------
-namespace {
-
-template <int R>
-void launch_normals_fit(const NormalsFitArgs& a, dim3 grid, hipStream_t stream) {
-  hipLaunchKernelGGL(k_normals_fit<R>, grid, dim3(kNormalsFitTileCols, kNormalsFitTileRows), 0, stream, a);
-}
-
-}  // namespace
-
-int pm_disparity_normals(pm_handle* h, const pm_cloud_camera* camera, const pm_normals_fit* fit, const float* d_disp, int rows,
-                         int cols, float* d_normals, float* d_planes, uint8_t* d_support) {
-  if (!h) return PM_ERR_INVALID_ARG;
-  const char* const what = "pm_disparity_normals";
-  if (!fit || !d_disp) {
-    set_err(h, "%s: null %s", what, !fit ? "fit" : "d_disp");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (!d_normals && !d_planes && !d_support) {
-    set_err(h, "%s: no output (d_normals, d_planes and d_support are all null)", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (d_normals)  // the camera is read for the normals alone
-    if (int rc = check_cloud_camera(h, what, camera)) return rc;
-  if (fit->radius < 1 || fit->radius > kNormalsFitMaxRadius) {
-    set_err(h, "%s: radius %d outside 1..%d", what, fit->radius, kNormalsFitMaxRadius);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (!std::isfinite(fit->max_diff) || fit->max_diff < 0.f) {
-    set_err(h, "%s: max_diff must be finite and >= 0", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  const int window = (2 * fit->radius + 1) * (2 * fit->radius + 1);
-  if (fit->min_support < 3 || fit->min_support > window) {
-    set_err(h, "%s: min_support %d outside 3..%d", what, fit->min_support, window);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
-  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
-  const NormalsFitArgs a = {d_normals ? cloud_cam(*camera) : CloudCam{1.0, 1.0, 0.0, 0.0, 1.0}, d_disp, rows, cols, fit->radius,
-                            fit->max_diff, fit->min_support, d_normals, d_planes, d_support};
-  const dim3 grid((unsigned)((cols + kNormalsFitTileCols - 1) / kNormalsFitTileCols),
-                  (unsigned)((rows + kNormalsFitTileRows - 1) / kNormalsFitTileRows));
-  hipStream_t stream = pm_internal::stream(h);
-#ifdef PM_TUNING
-  static const bool runtime_radius = pm::tune_env("PM_NORMALS_FIT_RUNTIME_RADIUS") != nullptr;
-  if (runtime_radius) {
-    hipLaunchKernelGGL(k_normals_fit_any, grid, dim3(kNormalsFitTileCols, kNormalsFitTileRows), 0, stream, a);
-    return launch_check(h, "normals fit");
-  }
-#endif
-  switch (fit->radius) {
-    case 1: launch_normals_fit<1>(a, grid, stream); break;
-    case 2: launch_normals_fit<2>(a, grid, stream); break;
-    case 3: launch_normals_fit<3>(a, grid, stream); break;
-    case 4: launch_normals_fit<4>(a, grid, stream); break;
-    case 5: launch_normals_fit<5>(a, grid, stream); break;
-    case 6: launch_normals_fit<6>(a, grid, stream); break;
-    default: launch_normals_fit<7>(a, grid, stream); break;
-  }
-  return launch_check(h, "normals fit");
-}
-
-void pm_debug_normals_fit_constants(int* tile_cols, int* tile_rows, int* pixels_per_thread) {
-  if (tile_cols) *tile_cols = kNormalsFitTileCols;
-  if (tile_rows) *tile_rows = kNormalsFitTileRows;
-  if (pixels_per_thread) *pixels_per_thread = 1;
-}
-
-// ---- speckle filter: connected components of similar disparity (pm_speckle.hpp) ------------------------------------------
-namespace {
-constexpr size_t kSpeckleHeader = 4;  // words in front of the labels: the counter's 16 bytes, cleared whole
-}
-
-int pm_filter_speckles(pm_handle* h, const pm_speckle_filter* filter, const float* d_disp, int rows, int cols, float* d_out,
-                       int32_t* d_labels, int32_t* d_sizes, int* d_removed, int* removed) {
-  if (!h) return PM_ERR_INVALID_ARG;
-  const char* const what = "pm_filter_speckles";
-  if (!filter || !d_disp) {
-    set_err(h, "%s: null %s", what, !filter ? "filter" : "d_disp");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (!d_out && !d_labels && !d_sizes && !d_removed && !removed) {
-    set_err(h, "%s: no output (d_out, d_labels, d_sizes, d_removed and removed are all null)", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (!std::isfinite(filter->max_diff) || filter->max_diff < 0.f) {
-    set_err(h, "%s: max_diff must be finite and >= 0", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (filter->max_size < 0) {
-    set_err(h, "%s: max_size %d must be >= 0", what, filter->max_size);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (rows < 1 || cols < 1) {
-    set_err(h, "%s: empty image (%dx%d)", what, cols, rows);
-    return PM_ERR_INVALID_ARG;
-  }
-  if ((long long)rows * cols > INT32_MAX) {
-    set_err(h, "%s: %dx%d pixels exceed a 32-bit pixel index", what, cols, rows);
-    return PM_ERR_SIZE;
-  }
-  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
-  ImagingState* st = state_of(h);
-  if (!st) {
-    set_err(h, "%s: out of host memory", what);
-    return PM_ERR_NOMEM;
-  }
-  const int pixels = rows * cols;
-  hipStream_t stream = pm_internal::stream(h);
-  PM_HIP(h, st->speckle_buf.reserve(sizeof(int) * (kSpeckleHeader + 2 * (size_t)pixels), stream));
-  int* d_total = st->speckle_buf.get();
-  const SpeckleArgs a = {d_disp, rows, cols, filter->max_diff, d_total + kSpeckleHeader, d_total + kSpeckleHeader + pixels};
-  const SpeckleOut o = {d_out, d_labels, d_sizes, filter->max_size};
-  const int tiles_x = speckle_tiles_x(cols);
-  const long long tiles = (long long)tiles_x * speckle_tiles_y(rows), items = speckle_merge_items(rows, cols);
-  const unsigned per_pixel = (unsigned)(((long long)pixels + kSpeckleBlock - 1) / kSpeckleBlock);
-  PM_HIP(h, hipMemsetAsync(d_total, 0, sizeof(int) * kSpeckleHeader, stream));
-  hipLaunchKernelGGL(k_speckle_local, dim3((unsigned)tiles), dim3(kSpeckleTileCols, kSpeckleTileRows), 0, stream, a, tiles_x);
-  if (items > 0)
-    hipLaunchKernelGGL(k_speckle_merge, dim3((unsigned)((items + kSpeckleBlock - 1) / kSpeckleBlock)), dim3(kSpeckleBlock), 0,
-                       stream, a, items);
-  hipLaunchKernelGGL(k_speckle_flatten, dim3(per_pixel), dim3(kSpeckleBlock), 0, stream, a, pixels);
-  hipLaunchKernelGGL(k_speckle_apply, dim3(per_pixel), dim3(kSpeckleBlock), 0, stream, a, o, pixels, d_total);
-  if (int rc = launch_check(h, "speckle filter")) return rc;
-  if (d_removed) PM_HIP(h, hipMemcpyAsync(d_removed, d_total, sizeof(int), hipMemcpyDeviceToDevice, stream));
-  if (removed) {
-    PM_HIP(h, hipMemcpyAsync(removed, d_total, sizeof(int), hipMemcpyDeviceToHost, stream));
-    PM_HIP(h, hipStreamSynchronize(stream));
-  }
-  return PM_OK;
-}
-
-void pm_debug_speckle_constants(int* tile_cols, int* tile_rows) {
-  if (tile_cols) *tile_cols = kSpeckleTileCols;
-  if (tile_rows) *tile_rows = kSpeckleTileRows;
-}
-
-// ---- grid mesh: vertices and triangles of a disparity map's stride grid (pm_mesh.hpp) -------------------------------------
-int pm_grid_mesh(pm_handle* h, const pm_cloud_camera* camera, const pm_cloud_filter* filter, const pm_mesh_options* options,
-                 const float* d_disp, const float* d_normals, const uint8_t* d_bgr8, int rows, int cols, int vertex_capacity,
-                 int tri_capacity, float* d_xyz_out, float* d_normals_out, uint8_t* d_bgr8_out, int32_t* d_index_out,
-                 int32_t* d_tri_out, int* d_counts, int* counts) {
-  if (!h) return PM_ERR_INVALID_ARG;
-  const char* const what = "pm_grid_mesh";
-  if (int rc = check_cloud_camera(h, what, camera)) return rc;
-  if (!filter || !options || !d_disp) {
-    set_err(h, "%s: null %s", what, !filter ? "filter" : !options ? "options" : "d_disp");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (filter->stride < 1) {
-    set_err(h, "%s: stride %d must be >= 1", what, filter->stride);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (std::isnan(filter->min_disp) || !(filter->max_range >= 0.f)) {
-    set_err(h, "%s: min_disp must not be NaN and max_range must be >= 0 (0 = no limit)", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (!std::isfinite(options->max_diff) || options->max_diff < 0.f) {
-    set_err(h, "%s: max_diff must be finite and >= 0", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (options->vertices != PM_MESH_VERTICES_ALL && options->vertices != PM_MESH_VERTICES_REFERENCED) {
-    set_err(h, "%s: vertices %d is neither PM_MESH_VERTICES_ALL nor PM_MESH_VERTICES_REFERENCED", what, options->vertices);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (vertex_capacity < 0 || tri_capacity < 0) {
-    set_err(h, "%s: %s %d must be >= 0", what, vertex_capacity < 0 ? "vertex_capacity" : "tri_capacity",
-            vertex_capacity < 0 ? vertex_capacity : tri_capacity);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (d_normals_out && !d_normals) {
-    set_err(h, "%s: d_normals_out requested without d_normals", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (d_bgr8_out && !d_bgr8) {
-    set_err(h, "%s: d_bgr8_out requested without d_bgr8", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
-  const int stride = filter->stride;
-  const int sub_rows = (rows + stride - 1) / stride, sub_cols = (cols + stride - 1) / stride;
-  if (2 * ((long long)(sub_rows - 1) * (sub_cols - 1)) > INT32_MAX) {
-    set_err(h, "%s: the %dx%d grid has more than 2^31 - 1 possible triangles", what, sub_cols, sub_rows);
-    return PM_ERR_SIZE;
-  }
-  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
-  ImagingState* st = state_of(h);
-  if (!st) {
-    set_err(h, "%s: out of host memory", what);
-    return PM_ERR_NOMEM;
-  }
-  const MeshArgs a = {{cloud_cam(*camera), *filter, d_disp, rows, cols, sub_cols, (long long)sub_rows * sub_cols},
-                      sub_rows, options->max_diff, options->vertices == PM_MESH_VERTICES_REFERENCED};
-  const int blocks = sub_rows * mesh_segments(sub_cols);  // <= rows * ceil(cols / 256): far below 2^31 (check_cloud_shape)
-  hipStream_t stream = pm_internal::stream(h);
-  PM_HIP(h, st->mesh_buf.reserve(sizeof(int) * (2 + 2 * (size_t)blocks + (size_t)a.c.items), stream));
-  int* d_totals = st->mesh_buf.get();
-  int* d_vertex_blocks = d_totals + 2;
-  int* d_tri_blocks = d_vertex_blocks + blocks;
-  int32_t* d_slot_map = d_tri_blocks + blocks;
-  const bool want_vertices = vertex_capacity > 0 && (d_xyz_out || d_normals_out || d_bgr8_out || d_index_out);
-  const bool want_tris = tri_capacity > 0 && d_tri_out;
-  const CloudStreams s = {d_normals, d_bgr8, d_xyz_out, d_normals_out, d_bgr8_out, d_index_out, want_vertices ? vertex_capacity : 0};
-  const dim3 grid((unsigned)blocks), block(kMeshBlock);
-  hipLaunchKernelGGL(k_mesh_count, grid, block, 0, stream, a, d_vertex_blocks, d_tri_blocks);
-  hipLaunchKernelGGL(k_cloud_offsets, dim3(1), dim3(kCloudScanThreads), 0, stream, d_vertex_blocks, blocks, d_totals,
-                     d_counts);
-  hipLaunchKernelGGL(k_cloud_offsets, dim3(1), dim3(kCloudScanThreads), 0, stream, d_tri_blocks, blocks, d_totals + 1,
-                     d_counts ? d_counts + 1 : nullptr);
-  if (want_vertices || want_tris)  // the triangles name the slots this launch leaves in the slot map
-    hipLaunchKernelGGL(k_mesh_vertices, grid, block, 0, stream, a, (const int*)d_vertex_blocks, s, d_slot_map);
-  if (want_tris)
-    hipLaunchKernelGGL(k_mesh_triangles, grid, block, 0, stream, a, (const int*)d_tri_blocks, (const int32_t*)d_slot_map,
-                       d_tri_out, tri_capacity);
-  if (int rc = launch_check(h, "grid mesh")) return rc;
-  if (counts) {
-    PM_HIP(h, hipMemcpyAsync(counts, d_totals, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    PM_HIP(h, hipStreamSynchronize(stream));
-  }
-  return PM_OK;
-}
-
-void pm_debug_mesh_constants(int* items_per_block, int* blocks_per_scan_pass) {
-  if (items_per_block) *items_per_block = kMeshBlock;
-  if (blocks_per_scan_pass) *blocks_per_scan_pass = kCloudScanThreads;
-}
-
-// ---- temporal seeds: a map carried into the next frame's two seed maps (pm_reproject.hpp) ------------------------------------
-namespace {
-constexpr size_t kReprojectHeader = 4;  // words in front of the maps: the two counts, padded to 16 bytes
-}
-
-int pm_reproject_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_motion* motion,
-                           const pm_reproject_options* options, const float* d_disp, int rows, int cols, float* d_seed_l,
-                           float* d_seed_r, int* d_counts, int* counts) {
-  if (!h) return PM_ERR_INVALID_ARG;
-  const char* const what = "pm_reproject_disparity";
-  if (int rc = check_cloud_camera(h, what, camera)) return rc;
-  if (!motion || !options || !d_disp) {
-    set_err(h, "%s: null %s", what, !motion ? "motion" : !options ? "options" : "d_disp");
-    return PM_ERR_INVALID_ARG;
-  }
-  for (int i = 0; i < 12; ++i)
-    if (!std::isfinite(i < 9 ? motion->R[i] : motion->t[i - 9])) {
-      set_err(h, "%s: %s[%d] of the motion is not finite", what, i < 9 ? "R" : "t", i < 9 ? i : i - 9);
-      return PM_ERR_INVALID_ARG;
-    }
-  if (!(options->min_disp >= 0.f) || !(options->max_disp >= 0.f)) {
-    set_err(h, "%s: %s must be >= 0 and not NaN%s", what, !(options->min_disp >= 0.f) ? "min_disp" : "max_disp",
-            !(options->min_disp >= 0.f) ? "" : " (0 = no limit)");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (options->close_radius < 0 || options->close_radius > kReprojectMaxRadius) {
-    set_err(h, "%s: close_radius %d must be 0 .. %d", what, options->close_radius, kReprojectMaxRadius);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
-  if (!d_seed_l && !d_seed_r && !d_counts && !counts) {
-    set_err(h, "%s: no output: d_seed_l, d_seed_r, d_counts and counts are all null", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (d_seed_l == d_disp || d_seed_r == d_disp) {
-    set_err(h, "%s: %s must not alias d_disp", what, d_seed_l == d_disp ? "d_seed_l" : "d_seed_r");
-    return PM_ERR_INVALID_ARG;
-  }
-  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
-  ImagingState* st = state_of(h);
-  if (!st) {
-    set_err(h, "%s: out of host memory", what);
-    return PM_ERR_NOMEM;
-  }
-  const size_t px = (size_t)rows * cols;
-  const size_t cleared = kReprojectHeader + 2 * px;
-  hipStream_t stream = pm_internal::stream(h);
-  PM_HIP(h, st->reproject_buf.reserve(sizeof(unsigned) * (cleared + (d_seed_l ? 0 : px)), stream));
-  unsigned* base = st->reproject_buf.get();
-  int* d_totals = reinterpret_cast<int*>(base);
-  unsigned* splat_l = base + kReprojectHeader;
-  unsigned* splat_r = splat_l + px;
-  unsigned* closed_l = d_seed_l ? reinterpret_cast<unsigned*>(d_seed_l) : splat_r + px;
-  PM_HIP(h, hipMemsetAsync(base, 0, sizeof(unsigned) * cleared, stream));
-  ReprojectArgs a = {cloud_cam(*camera), {}, {}, options->min_disp, options->max_disp, d_disp, rows, cols, splat_l};
-  for (int i = 0; i < 9; ++i) a.R[i] = motion->R[i];
-  for (int i = 0; i < 3; ++i) a.t[i] = motion->t[i];
-  const int span = kReprojectSpan;
-  const dim3 block(kReprojectBlockX, kReprojectBlockY);
-  const dim3 splat_grid((unsigned)((cols + span - 1) / span), (unsigned)((rows + kReprojectBlockY - 1) / kReprojectBlockY));
-  const dim3 tile_grid((unsigned)((cols + kReprojectTileW - 1) / kReprojectTileW),
-                       (unsigned)((rows + kReprojectTileH - 1) / kReprojectTileH));
-  const int r = options->close_radius;
-  hipLaunchKernelGGL(k_reproject_splat, splat_grid, block, 0, stream, a);
-  hipLaunchKernelGGL(k_reproject_finish, tile_grid, block, 0, stream,
-                     ReprojectFinishArgs{splat_l, closed_l, rows, cols, r, d_totals});
-  if (d_seed_r || d_counts || counts) {  // the right view: from the CLOSED left seed
-    hipLaunchKernelGGL(k_reproject_splat_right, splat_grid, block, 0, stream,
-                       ReprojectRightArgs{reinterpret_cast<const float*>(closed_l), rows, cols, splat_r});
-    hipLaunchKernelGGL(k_reproject_finish, tile_grid, block, 0, stream,
-                       ReprojectFinishArgs{splat_r, reinterpret_cast<unsigned*>(d_seed_r), rows, cols, r, d_totals + 1});
-  }
-  if (int rc = launch_check(h, "reproject disparity")) return rc;
-  if (d_counts) PM_HIP(h, hipMemcpyAsync(d_counts, d_totals, 2 * sizeof(int), hipMemcpyDeviceToDevice, stream));
-  if (counts) {
-    PM_HIP(h, hipMemcpyAsync(counts, d_totals, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
-    PM_HIP(h, hipStreamSynchronize(stream));
-  }
-  return PM_OK;
-}
-
-void pm_debug_reproject_constants(int* tile_w, int* tile_h) {
-  if (tile_w) *tile_w = kReprojectTileW;
-  if (tile_h) *tile_h = kReprojectTileH;
 }
 
 // Host only: Bouguet's construction (see pm/imaging.h).

@@ -1,4 +1,4 @@
-// pm_mesh.hpp -- the kernels of pm_grid_mesh (include/pm/imaging.h); included by pm_imaging.hip alone.  The arithmetic
+// pm_mesh.hpp -- the kernels of pm_grid_mesh (include/pm/imaging.h); included by pm_stages.hip alone.  The arithmetic
 // and the per-thread bodies (mesh_value, mesh_cell, mesh_referenced, mesh_store_vertex, mesh_store_triangles) are
 // pm_mesh_body.hpp's, the definition is tests/mesh_ref.py.
 //

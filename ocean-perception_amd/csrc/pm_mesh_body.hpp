@@ -1,6 +1,6 @@
 // pm_mesh_body.hpp -- the arithmetic and the per-thread bodies of pm_grid_mesh (include/pm/imaging.h), host-callable and
 // free of kernels like pm_cloud_body.hpp, on which it builds: what COUNTS is cloud_point() + cloud_counts(), a vertex is
-// stored by cloud_store().  pm_imaging.hip uses it through pm_mesh.hpp, a CPU build (tests/cpp/mesh_host_main.cpp, under
+// stored by cloud_store().  pm_stages.hip uses it through pm_mesh.hpp, a CPU build (tests/cpp/mesh_host_main.cpp, under
 // the sanitizers) runs the same bodies.  The definition it is held to BIT FOR BIT is tests/mesh_ref.py.
 //
 // Every body works on VALUES: the value of a grid item is its disparity where the item counts and +0.0f where it does not

@@ -1,4 +1,4 @@
-// pm_normals_fit.hpp -- the kernel of pm_disparity_normals (include/pm/imaging.h); included by pm_imaging.hip alone.  The
+// pm_normals_fit.hpp -- the kernel of pm_disparity_normals (include/pm/imaging.h); included by pm_stages.hip alone.  The
 // staging, the per-pixel fit and the store are pm_normals_fit_body.hpp's, the definition is tests/normals_fit_ref.py
 // (DESIGN.md section 8c-2).
 //
@@ -8,7 +8,7 @@
 // the image runs normals_fit_pixel over its (2r+1)^2 window: lanes read neighbouring floats of a tile row, so every LDS
 // read is conflict-free.  A lane whose centre is not > 0 leaves the fit at once; a wavefront of such lanes skips the loop
 // (the compiler branches on the empty exec mask).  No atomics, no wait between workgroups, no inline assembly.
-// R = 1..7: the radius as a template constant, the window loops fully unrolled (pm_imaging.hip dispatches).
+// R = 1..7: the radius as a template constant, the window loops fully unrolled (pm_stages.hip dispatches).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // pm_normals_fit_body.hpp -- the staging, the per-pixel plane fit and the store of pm_disparity_normals
-// (include/pm/imaging.h), host-callable and free of kernels, so that the kernel (pm_normals_fit.hpp, in pm_imaging.hip) and a
+// (include/pm/imaging.h), host-callable and free of kernels, so that the kernel (pm_normals_fit.hpp, in pm_stages.hip) and a
 // CPU build (tests/cpp/normals_fit_host_main.cpp, under the sanitizers) share ONE statement of them.  The definition it is
 // held to BIT FOR BIT is tests/normals_fit_ref.py: every operation is one rounding in the format
 // written, parentheses and the order of the binary64 sums as written (the build uses -ffp-contract=off; binary64 add,

@@ -1,4 +1,4 @@
-// pm_reproject.hpp -- the kernels of pm_reproject_disparity (include/pm/imaging.h); included by pm_imaging.hip alone.  The
+// pm_reproject.hpp -- the kernels of pm_reproject_disparity (include/pm/imaging.h); included by pm_stages.hip alone.  The
 // arithmetic and the per-thread bodies (reproject_splat_lane, reproject_right_lane, reproject_stage_cell,
 // reproject_finish_pixel) are pm_reproject_body.hpp's, the definition is tests/reproject_ref.py.
 //

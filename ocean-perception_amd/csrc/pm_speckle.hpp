@@ -1,4 +1,4 @@
-// pm_speckle.hpp -- the kernels of pm_filter_speckles (include/pm/imaging.h); included by pm_imaging.hip alone.  What a
+// pm_speckle.hpp -- the kernels of pm_filter_speckles (include/pm/imaging.h); included by pm_stages.hip alone.  What a
 // thread does is pm_speckle_body.hpp's, the definition is tests/speckle_ref.py.
 //
 // Four launches on one stream; the boundary between two of them is the only thing a workgroup ever waits for:

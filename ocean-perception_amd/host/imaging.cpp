@@ -58,6 +58,13 @@ class DeviceBuffer {
 template <typename T>
 size_t Bytes(const Image<T>& im) { return sizeof(T) * (size_t)im.rows * im.cols; }
 
+// The download into an optional output image, which takes the result's size first.
+template <typename T>
+void DownloadInto(DeviceBuffer& d, Image<T>* out, int rows, int cols) {
+  if (out->rows != rows || out->cols != cols) out->create(rows, cols);
+  d.Download(out->data(), Bytes(*out));
+}
+
 void SameSize(int r0, int c0, int r1, int c1, const char* what) {
   if (r0 != r1 || c0 != c1 || r0 <= 0 || c0 <= 0) throw std::invalid_argument(std::string(what) + ": image sizes differ or are empty");
 }
@@ -176,8 +183,7 @@ float FindDarkFast(const Image1f& intensity, const Image1f& range, float percent
   Check(pm_find_dark(h, d_i.as<float>(), d_r.as<float>(), intensity.rows, intensity.cols, percentile,
                      d_m.as<uint8_t>(), &thr),
         "pm_find_dark");
-  if (mask.rows != intensity.rows || mask.cols != intensity.cols) mask.create(intensity.rows, intensity.cols);
-  d_m.Download(mask.data(), Bytes(mask));
+  DownloadInto(d_m, &mask, intensity.rows, intensity.cols);
   return thr;
 }
 
@@ -266,10 +272,7 @@ Image<Pixel> RectifyImage(const Image<Pixel>& raw, const RectifyView& view, int 
                           d_mask, nullptr),
           "pm_rectify_bgr8");
   d_out.Download(out.data(), Bytes(out));
-  if (valid) {
-    if (valid->rows != rows || valid->cols != cols) valid->create(rows, cols);
-    d_valid.Download(valid->data(), px);
-  }
+  if (valid) DownloadInto(d_valid, valid, rows, cols);
   return out;
 }
 
@@ -301,96 +304,113 @@ core::Image<core::Vec3f> Backproject(const core::Image<float>& disp, const Stere
   return out;
 }
 
+namespace {
+
+// What MakePointCloud and MakeGridMesh share: the size checks (`who` names the caller), ...
+void CheckCloudSizes(const std::string& who, const core::Image<float>& disp, const core::Image<core::Vec3f>* normals,
+                     const core::Image<core::Vec3b>* bgr) {
+  if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument(who + ": empty map");
+  if (normals) SameSize(disp.rows, disp.cols, normals->rows, normals->cols, (who + " (normals)").c_str());
+  if (bgr) SameSize(disp.rows, disp.cols, bgr->rows, bgr->cols, (who + " (bgr)").c_str());
+}
+
+// ... the inputs on the device (normals / bgr null where not given) with the camera and the filter of the C ABI, ...
+struct CloudInputs {
+  CloudInputs(pm_handle* h, const core::Image<float>& disp_in, const StereoModel& model, const CloudFilter& filter,
+              const core::Image<core::Vec3f>* n, const core::Image<core::Vec3b>* c)
+      : d_in(h, Bytes(disp_in)), d_n(h, n ? Bytes(*n) : 0), d_c(h, c ? Bytes(*c) : 0), disp(d_in.as<float>()),
+        normals(n ? d_n.as<float>() : nullptr), bgr(c ? d_c.as<uint8_t>() : nullptr), cam(CloudCamera(model)),
+        flt{filter.min_disp, filter.max_range, filter.stride} {
+    d_in.Upload(disp_in.data(), Bytes(disp_in));
+    if (n) d_n.Upload(n->data(), Bytes(*n));
+    if (c) d_c.Upload(c->data(), Bytes(*c));
+  }
+  DeviceBuffer d_in, d_n, d_c;
+  float* const disp;
+  float* const normals;
+  uint8_t* const bgr;
+  const pm_cloud_camera cam;
+  const pm_cloud_filter flt;
+};
+
+// ... and the four vertex streams of `n` records, which come back into a PointCloud.
+struct VertexStreams {
+  VertexStreams(pm_handle* h, size_t n, const CloudInputs& in)
+      : n(n), o_xyz(h, n * sizeof(core::Vec3f)), o_n(h, in.normals ? n * sizeof(core::Vec3f) : 0),
+        o_c(h, in.bgr ? n * sizeof(core::Vec3b) : 0), o_i(h, n * sizeof(int32_t)), xyz(o_xyz.as<float>()),
+        normals(in.normals ? o_n.as<float>() : nullptr), bgr(in.bgr ? o_c.as<uint8_t>() : nullptr), index(o_i.as<int32_t>()) {}
+  void Download(PointCloud* pc) {
+    pc->xyz.resize(n);
+    pc->index.resize(n);
+    o_xyz.Download(pc->xyz.data(), n * sizeof(core::Vec3f));
+    o_i.Download(pc->index.data(), n * sizeof(int32_t));
+    if (normals) {
+      pc->normals.resize(n);
+      o_n.Download(pc->normals.data(), n * sizeof(core::Vec3f));
+    }
+    if (bgr) {
+      pc->bgr.resize(n);
+      o_c.Download(pc->bgr.data(), n * sizeof(core::Vec3b));
+    }
+  }
+  const size_t n;
+  DeviceBuffer o_xyz, o_n, o_c, o_i;
+  float* const xyz;
+  float* const normals;
+  uint8_t* const bgr;
+  int32_t* const index;
+};
+
+}  // namespace
+
 PointCloud MakePointCloud(const core::Image<float>& disp, const StereoModel& model, const CloudFilter& filter,
                           const core::Image<core::Vec3f>* normals, const core::Image<core::Vec3b>* bgr) {
-  if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("MakePointCloud: empty map");
-  if (normals) SameSize(disp.rows, disp.cols, normals->rows, normals->cols, "MakePointCloud (normals)");
-  if (bgr) SameSize(disp.rows, disp.cols, bgr->rows, bgr->cols, "MakePointCloud (bgr)");
+  CheckCloudSizes("MakePointCloud", disp, normals, bgr);
   std::lock_guard<std::mutex> lock(g_mutex);
   pm_handle* h = Context();
-  DeviceBuffer d_in(h, Bytes(disp)), d_n(h, normals ? Bytes(*normals) : 0), d_c(h, bgr ? Bytes(*bgr) : 0);
-  d_in.Upload(disp.data(), Bytes(disp));
-  if (normals) d_n.Upload(normals->data(), Bytes(*normals));
-  if (bgr) d_c.Upload(bgr->data(), Bytes(*bgr));
-  const pm_cloud_camera cam = CloudCamera(model);
-  const pm_cloud_filter flt = {filter.min_disp, filter.max_range, filter.stride};
+  CloudInputs in(h, disp, model, filter, normals, bgr);
   // count first (capacity 0), then outputs of exactly that size
   int count = 0;
-  Check(pm_point_cloud(h, &cam, &flt, d_in.as<float>(), nullptr, nullptr, disp.rows, disp.cols, 0, nullptr, nullptr, nullptr,
+  Check(pm_point_cloud(h, &in.cam, &in.flt, in.disp, nullptr, nullptr, disp.rows, disp.cols, 0, nullptr, nullptr, nullptr,
                        nullptr, nullptr, &count),
         "pm_point_cloud");
   PointCloud pc;
   if (count <= 0) return pc;
-  const size_t n = (size_t)count;
-  DeviceBuffer o_xyz(h, n * sizeof(core::Vec3f)), o_n(h, normals ? n * sizeof(core::Vec3f) : 0),
-      o_c(h, bgr ? n * sizeof(core::Vec3b) : 0), o_i(h, n * sizeof(int32_t));
+  VertexStreams out(h, (size_t)count, in);
   int again = 0;
-  Check(pm_point_cloud(h, &cam, &flt, d_in.as<float>(), normals ? d_n.as<float>() : nullptr, bgr ? d_c.as<uint8_t>() : nullptr,
-                       disp.rows, disp.cols, count, o_xyz.as<float>(), normals ? o_n.as<float>() : nullptr,
-                       bgr ? o_c.as<uint8_t>() : nullptr, o_i.as<int32_t>(), nullptr, &again),
+  Check(pm_point_cloud(h, &in.cam, &in.flt, in.disp, in.normals, in.bgr, disp.rows, disp.cols, count, out.xyz, out.normals,
+                       out.bgr, out.index, nullptr, &again),
         "pm_point_cloud");
   if (again != count) throw std::runtime_error("MakePointCloud: the count changed between two passes over one map");
-  pc.xyz.resize(n);
-  pc.index.resize(n);
-  o_xyz.Download(pc.xyz.data(), n * sizeof(core::Vec3f));
-  o_i.Download(pc.index.data(), n * sizeof(int32_t));
-  if (normals) {
-    pc.normals.resize(n);
-    o_n.Download(pc.normals.data(), n * sizeof(core::Vec3f));
-  }
-  if (bgr) {
-    pc.bgr.resize(n);
-    o_c.Download(pc.bgr.data(), n * sizeof(core::Vec3b));
-  }
+  out.Download(&pc);
   return pc;
 }
 
 TriangleMesh MakeGridMesh(const core::Image<float>& disp, const StereoModel& model, const CloudFilter& filter,
                           const MeshOptions& options, const core::Image<core::Vec3f>* normals,
                           const core::Image<core::Vec3b>* bgr) {
-  if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("MakeGridMesh: empty map");
-  if (normals) SameSize(disp.rows, disp.cols, normals->rows, normals->cols, "MakeGridMesh (normals)");
-  if (bgr) SameSize(disp.rows, disp.cols, bgr->rows, bgr->cols, "MakeGridMesh (bgr)");
+  CheckCloudSizes("MakeGridMesh", disp, normals, bgr);
   std::lock_guard<std::mutex> lock(g_mutex);
   pm_handle* h = Context();
-  DeviceBuffer d_in(h, Bytes(disp)), d_n(h, normals ? Bytes(*normals) : 0), d_c(h, bgr ? Bytes(*bgr) : 0);
-  d_in.Upload(disp.data(), Bytes(disp));
-  if (normals) d_n.Upload(normals->data(), Bytes(*normals));
-  if (bgr) d_c.Upload(bgr->data(), Bytes(*bgr));
-  const pm_cloud_camera cam = CloudCamera(model);
-  const pm_cloud_filter flt = {filter.min_disp, filter.max_range, filter.stride};
+  CloudInputs in(h, disp, model, filter, normals, bgr);
   const pm_mesh_options opt = {options.max_diff, options.referenced_vertices ? PM_MESH_VERTICES_REFERENCED : PM_MESH_VERTICES_ALL};
   // count first (both capacities 0), then outputs of exactly that size
   int counts[2] = {0, 0};
-  Check(pm_grid_mesh(h, &cam, &flt, &opt, d_in.as<float>(), nullptr, nullptr, disp.rows, disp.cols, 0, 0, nullptr, nullptr,
+  Check(pm_grid_mesh(h, &in.cam, &in.flt, &opt, in.disp, nullptr, nullptr, disp.rows, disp.cols, 0, 0, nullptr, nullptr,
                      nullptr, nullptr, nullptr, nullptr, counts),
         "pm_grid_mesh");
   TriangleMesh mesh;
   if (counts[0] <= 0) return mesh;
-  const size_t n = (size_t)counts[0], t = (size_t)(counts[1] > 0 ? counts[1] : 0);
-  DeviceBuffer o_xyz(h, n * sizeof(core::Vec3f)), o_n(h, normals ? n * sizeof(core::Vec3f) : 0),
-      o_c(h, bgr ? n * sizeof(core::Vec3b) : 0), o_i(h, n * sizeof(int32_t)), o_t(h, t * 3 * sizeof(int32_t));
+  const size_t t = (size_t)(counts[1] > 0 ? counts[1] : 0);
+  VertexStreams out(h, (size_t)counts[0], in);
+  DeviceBuffer o_t(h, t * 3 * sizeof(int32_t));
   int again[2] = {0, 0};
-  Check(pm_grid_mesh(h, &cam, &flt, &opt, d_in.as<float>(), normals ? d_n.as<float>() : nullptr,
-                     bgr ? d_c.as<uint8_t>() : nullptr, disp.rows, disp.cols, counts[0], counts[1], o_xyz.as<float>(),
-                     normals ? o_n.as<float>() : nullptr, bgr ? o_c.as<uint8_t>() : nullptr, o_i.as<int32_t>(),
-                     t ? o_t.as<int32_t>() : nullptr, nullptr, again),
+  Check(pm_grid_mesh(h, &in.cam, &in.flt, &opt, in.disp, in.normals, in.bgr, disp.rows, disp.cols, counts[0], counts[1],
+                     out.xyz, out.normals, out.bgr, out.index, t ? o_t.as<int32_t>() : nullptr, nullptr, again),
         "pm_grid_mesh");
   if (again[0] != counts[0] || again[1] != counts[1])
     throw std::runtime_error("MakeGridMesh: the counts changed between two passes over one map");
-  PointCloud& pc = mesh.vertices;
-  pc.xyz.resize(n);
-  pc.index.resize(n);
-  o_xyz.Download(pc.xyz.data(), n * sizeof(core::Vec3f));
-  o_i.Download(pc.index.data(), n * sizeof(int32_t));
-  if (normals) {
-    pc.normals.resize(n);
-    o_n.Download(pc.normals.data(), n * sizeof(core::Vec3f));
-  }
-  if (bgr) {
-    pc.bgr.resize(n);
-    o_c.Download(pc.bgr.data(), n * sizeof(core::Vec3b));
-  }
+  out.Download(&mesh.vertices);
   mesh.triangles.resize(t);
   if (t) o_t.Download(mesh.triangles.data(), t * 3 * sizeof(int32_t));
   return mesh;
@@ -479,10 +499,7 @@ core::Image<core::Vec3f> DisparityNormals(const core::Image<float>& disp, const 
                              support ? d_sup.as<uint8_t>() : nullptr),
         "pm_disparity_normals");
   d_out.Download(out.data(), Bytes(out));
-  if (support) {
-    if (support->rows != disp.rows || support->cols != disp.cols) support->create(disp.rows, disp.cols);
-    d_sup.Download(support->data(), px);
-  }
+  if (support) DownloadInto(d_sup, support, disp.rows, disp.cols);
   return out;
 }
 
@@ -500,10 +517,7 @@ core::Image<float> FilterSpeckles(const core::Image<float>& disp, const SpeckleF
                            labels ? d_lab.as<int32_t>() : nullptr, nullptr, nullptr, removed),
         "pm_filter_speckles");
   d_map.Download(out.data(), Bytes(out));
-  if (labels) {
-    if (labels->rows != disp.rows || labels->cols != disp.cols) labels->create(disp.rows, disp.cols);
-    d_lab.Download(labels->data(), sizeof(int32_t) * px);
-  }
+  if (labels) DownloadInto(d_lab, labels, disp.rows, disp.cols);
   return out;
 }
 

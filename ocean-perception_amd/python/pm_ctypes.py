@@ -570,6 +570,11 @@ def _f32(a):
     return a, a.ctypes.data_as(C.c_void_p)
 
 
+def _ref(struct):
+    """An optional struct argument: a reference to it, or the null pointer for None."""
+    return C.byref(struct) if struct is not None else None
+
+
 class Engine:
     """One pm_handle.  Methods mirror the C entry points; numpy arrays in, numpy arrays out."""
 
@@ -830,22 +835,20 @@ class Engine:
                    stream=None):
         """n raw images -> n undistorted, rectified images (raw device addresses); view: 22 doubles or a PmRectifyView."""
         v = rectify_view(view)
-        self._check(self.lib.pm_rectify_u8(self.h, C.byref(v) if v is not None else None, d_src, n, src_rows, src_cols,
+        self._check(self.lib.pm_rectify_u8(self.h, _ref(v), d_src, n, src_rows, src_cols,
                                            src_step, rows, cols, border_value, d_dst, d_valid, stream), "pm_rectify_u8")
 
     def rectify_map(self, view, rows, cols, d_xy):
         """The Q5 source coordinates pm_rectify_u8 uses: int32 [rows][cols][2] at the device address d_xy."""
         v = rectify_view(view)
-        self._check(self.lib.pm_rectify_map(self.h, C.byref(v) if v is not None else None, rows, cols, d_xy),
-                    "pm_rectify_map")
+        self._check(self.lib.pm_rectify_map(self.h, _ref(v), rows, cols, d_xy), "pm_rectify_map")
 
     def match_raw_device(self, n, left_view, right_view, d_left_raw, d_right_raw, src_rows, src_cols, src_step, rows, cols,
                          d_seed_l, d_seed_r, d_disp_l, d_disp_r):
         """pm_rectify_u8 of both raw images followed by pm_match_device (raw device addresses)."""
         self._pl_shape = (rows, cols)
         vl, vr = rectify_view(left_view), rectify_view(right_view)
-        self._check(self.lib.pm_match_raw_device(self.h, n, C.byref(vl) if vl is not None else None,
-                                                 C.byref(vr) if vr is not None else None, d_left_raw, d_right_raw, src_rows,
+        self._check(self.lib.pm_match_raw_device(self.h, n, _ref(vl), _ref(vr), d_left_raw, d_right_raw, src_rows,
                                                  src_cols, src_step, rows, cols, d_seed_l, d_seed_r, d_disp_l, d_disp_r),
                     "pm_match_raw_device")
 
@@ -854,7 +857,7 @@ class Engine:
         """n raw interleaved BGR images -> n undistorted, rectified ones (raw device addresses): 8-bit (d_dst) and / or
         float x 1/255 (d_dst_f), one mask per image (d_valid).  src_step in bytes, 0 = 3 * src_cols."""
         v = rectify_view(view)
-        self._check(self.lib.pm_rectify_bgr8(self.h, C.byref(v) if v is not None else None, d_src, n, src_rows, src_cols,
+        self._check(self.lib.pm_rectify_bgr8(self.h, _ref(v), d_src, n, src_rows, src_cols,
                                              src_step, rows, cols, border_value, d_dst, d_dst_f, d_valid, stream),
                     "pm_rectify_bgr8")
 
@@ -864,22 +867,19 @@ class Engine:
         d_right_rect: optional outputs that receive the rectified images."""
         self._pl_shape = (rows, cols)
         vl, vr = rectify_view(left_view), rectify_view(right_view)
-        self._check(self.lib.pm_match_raw_bgr_device(self.h, n, C.byref(vl) if vl is not None else None,
-                                                     C.byref(vr) if vr is not None else None, d_left_raw, d_right_raw,
+        self._check(self.lib.pm_match_raw_bgr_device(self.h, n, _ref(vl), _ref(vr), d_left_raw, d_right_raw,
                                                      src_rows, src_cols, src_step, rows, cols, d_seed_l, d_seed_r, d_disp_l,
                                                      d_disp_r, d_left_rect, d_right_rect), "pm_match_raw_bgr_device")
 
     def backproject(self, camera, d_disp, rows, cols, d_xyz):
         """pm_backproject (raw device addresses); camera: (fx, fy, cx, cy, baseline) or a PmCloudCamera."""
         c = cloud_camera(camera)
-        self._check(self.lib.pm_backproject(self.h, C.byref(c) if c is not None else None, d_disp, rows, cols, d_xyz),
-                    "pm_backproject")
+        self._check(self.lib.pm_backproject(self.h, _ref(c), d_disp, rows, cols, d_xyz), "pm_backproject")
 
     def planes_normals(self, pair, camera, d_disp_l, rows, cols, d_normals):
         """pm_planes_normals: the left view's unit normals from the resident plane state of the last match."""
         c = cloud_camera(camera)
-        self._check(self.lib.pm_planes_normals(self.h, pair, C.byref(c) if c is not None else None, d_disp_l, rows, cols,
-                                               d_normals), "pm_planes_normals")
+        self._check(self.lib.pm_planes_normals(self.h, pair, _ref(c), d_disp_l, rows, cols, d_normals), "pm_planes_normals")
 
     def point_cloud(self, camera, d_disp, rows, cols, capacity, min_disp=0.0, max_range=0.0, stride=1, d_normals=None,
                     d_bgr8=None, d_xyz_out=None, d_normals_out=None, d_bgr8_out=None, d_index_out=None, d_count=None,
@@ -889,7 +889,7 @@ class Engine:
         c = cloud_camera(camera)
         f = PmCloudFilter(min_disp, max_range, stride)
         n = C.c_int(-1)
-        self._check(self.lib.pm_point_cloud(self.h, C.byref(c) if c is not None else None, C.byref(f), d_disp, d_normals,
+        self._check(self.lib.pm_point_cloud(self.h, _ref(c), C.byref(f), d_disp, d_normals,
                                             d_bgr8, rows, cols, capacity, d_xyz_out, d_normals_out, d_bgr8_out, d_index_out,
                                             d_count, C.byref(n) if host_count else None), "pm_point_cloud")
         return n.value if host_count else None
@@ -901,7 +901,7 @@ class Engine:
         (fx, fy, cx, cy, baseline) or a PmCloudCamera; needed for d_normals only."""
         c = cloud_camera(camera)
         f = PmNormalsFit(radius, max_diff, min_support)
-        self._check(self.lib.pm_disparity_normals(self.h, C.byref(c) if c is not None else None, C.byref(f), d_disp, rows, cols,
+        self._check(self.lib.pm_disparity_normals(self.h, _ref(c), C.byref(f), d_disp, rows, cols,
                                                   d_normals, d_planes, d_support), "pm_disparity_normals")
 
     def filter_speckles(self, d_disp, rows, cols, max_diff=1.0, max_size=100, d_out=None, d_labels=None, d_sizes=None,
@@ -925,7 +925,7 @@ class Engine:
         f = PmCloudFilter(min_disp, max_range, stride)
         o = PmMeshOptions(max_diff, vertices)
         n = (C.c_int * 2)(-1, -1)
-        self._check(self.lib.pm_grid_mesh(self.h, C.byref(c) if c is not None else None, C.byref(f), C.byref(o), d_disp, d_normals,
+        self._check(self.lib.pm_grid_mesh(self.h, _ref(c), C.byref(f), C.byref(o), d_disp, d_normals,
                                           d_bgr8, rows, cols, vertex_capacity, tri_capacity, d_xyz_out, d_normals_out, d_bgr8_out,
                                           d_index_out, d_tri_out, d_counts, n if host_counts else None), "pm_grid_mesh")
         return (n[0], n[1]) if host_counts else None
@@ -939,8 +939,7 @@ class Engine:
         m = as_motion(motion)
         o = PmReprojectOptions(min_disp, max_disp, close_radius)
         n = (C.c_int * 2)(-1, -1)
-        self._check(self.lib.pm_reproject_disparity(self.h, C.byref(c) if c is not None else None,
-                                                    C.byref(m) if m is not None else None, C.byref(o), d_disp, rows, cols,
+        self._check(self.lib.pm_reproject_disparity(self.h, _ref(c), _ref(m), C.byref(o), d_disp, rows, cols,
                                                     d_seed_l, d_seed_r, d_counts, n if want_counts else None),
                     "pm_reproject_disparity")
         return (n[0], n[1]) if want_counts else None

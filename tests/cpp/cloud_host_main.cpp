@@ -18,33 +18,8 @@
 #include <string>
 #include <vector>
 
+#include "host_npy.hpp"
 #include "pm_cloud_body.hpp"
-
-static bool read_npy(const std::string& path, size_t bytes, std::unique_ptr<uint8_t[]>* out) {
-  FILE* f = fopen(path.c_str(), "rb");
-  if (!f) return false;
-  uint8_t head[10];
-  bool ok = fread(head, 1, 10, f) == 10 && !memcmp(head, "\x93NUMPY\x01", 7);
-  const size_t hlen = ok ? (size_t)head[8] | ((size_t)head[9] << 8) : 0;
-  ok = ok && fseek(f, 0, SEEK_END) == 0 && (size_t)ftell(f) == 10 + hlen + bytes && fseek(f, (long)(10 + hlen), SEEK_SET) == 0;
-  if (ok) {
-    out->reset(new uint8_t[bytes ? bytes : 1]);  // exactly sized (one byte where the dump is empty)
-    ok = fread(out->get(), 1, bytes, f) == bytes;
-  }
-  fclose(f);
-  if (!ok) fprintf(stderr, "cannot read %zu payload bytes from %s\n", bytes, path.c_str());
-  return ok;
-}
-
-static int differ(const char* what, const void* got, const void* want, size_t bytes) {
-  if (!memcmp(got, want, bytes)) return 0;
-  const uint8_t* g = (const uint8_t*)got;
-  const uint8_t* w = (const uint8_t*)want;
-  size_t at = 0;
-  while (g[at] == w[at]) ++at;
-  fprintf(stderr, "%s differs from the definition at byte %zu of %zu\n", what, at, bytes);
-  return 1;
-}
 
 int main(int argc, char** argv) {
   if (argc != 2) return 2;
@@ -98,8 +73,7 @@ int main(int argc, char** argv) {
   std::unique_ptr<float[]> cxyz(new float[3 * m ? 3 * m : 1]), cn(new float[3 * m ? 3 * m : 1]);
   std::unique_ptr<uint8_t[]> cbgr(new uint8_t[3 * m ? 3 * m : 1]);
   std::unique_ptr<int32_t[]> cidx(new int32_t[m ? m : 1]);
-  const int sub_rows = (rows + stride - 1) / stride, sub_cols = (cols + stride - 1) / stride;
-  const pm::CloudArgs ca = {cam, filter, disp, rows, cols, sub_cols, (long long)sub_rows * sub_cols};
+  const pm::CloudArgs ca = pm::cloud_args(camera, filter, disp, rows, cols);
   const pm::CloudStreams cs = {normals.get(), bgr_b.get(), cxyz.get(), cn.get(), cbgr.get(), cidx.get(), capacity};
   long long slot = 0;
   for (long long item = 0; item < ca.items; ++item) {

@@ -4,26 +4,13 @@
 // for it to check against the oracle.  usage: imaging_main <dir> <rows> <cols>
 #include <cstdio>
 #include <cstdlib>
-#include <fstream>
 #include <iostream>
 #include <string>
 
 #include "imaging.hpp"
+#include "raw_io.hpp"
 
 using namespace bm::imaging;
-
-template <typename T>
-static bool read_raw(const std::string& path, bm::core::Image<T>& im) {
-  std::ifstream f(path, std::ios::binary);
-  if (!f) return false;
-  f.read(reinterpret_cast<char*>(im.data()), sizeof(T) * (size_t)im.rows * im.cols);
-  return (bool)f;
-}
-template <typename T>
-static void write_raw(const std::string& path, const bm::core::Image<T>& im) {
-  std::ofstream f(path, std::ios::binary);
-  f.write(reinterpret_cast<const char*>(im.data()), sizeof(T) * (size_t)im.rows * im.cols);
-}
 
 int main(int argc, char** argv) {
   if (argc < 4) return 2;

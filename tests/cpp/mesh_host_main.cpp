@@ -20,33 +20,8 @@
 #include <string>
 #include <vector>
 
+#include "host_npy.hpp"
 #include "pm_mesh_body.hpp"
-
-static bool read_npy(const std::string& path, size_t bytes, std::unique_ptr<uint8_t[]>* out) {
-  FILE* f = fopen(path.c_str(), "rb");
-  if (!f) return false;
-  uint8_t head[10];
-  bool ok = fread(head, 1, 10, f) == 10 && !memcmp(head, "\x93NUMPY\x01", 7);
-  const size_t hlen = ok ? (size_t)head[8] | ((size_t)head[9] << 8) : 0;
-  ok = ok && fseek(f, 0, SEEK_END) == 0 && (size_t)ftell(f) == 10 + hlen + bytes && fseek(f, (long)(10 + hlen), SEEK_SET) == 0;
-  if (ok) {
-    out->reset(new uint8_t[bytes ? bytes : 1]);  // exactly sized (one byte where the dump is empty)
-    ok = fread(out->get(), 1, bytes, f) == bytes;
-  }
-  fclose(f);
-  if (!ok) fprintf(stderr, "cannot read %zu payload bytes from %s\n", bytes, path.c_str());
-  return ok;
-}
-
-static int differ(const char* what, const void* got, const void* want, size_t bytes) {
-  if (!memcmp(got, want, bytes)) return 0;
-  const uint8_t* g = (const uint8_t*)got;
-  const uint8_t* w = (const uint8_t*)want;
-  size_t at = 0;
-  while (g[at] == w[at]) ++at;
-  fprintf(stderr, "%s differs from the definition at byte %zu of %zu\n", what, at, bytes);
-  return 1;
-}
 
 // what a thread of block (ys, xs0 + k) computes in the count and in the scatter launches
 static bool thread_vertex(const pm::MeshArgs& a, int xs, int ys) {
@@ -88,10 +63,9 @@ int main(int argc, char** argv) {
       !read_npy(dir + "want_tris.npy", 12 * t, &want_tris))
     return 2;
 
-  const int sub_rows = (rows + stride - 1) / stride, sub_cols = (cols + stride - 1) / stride;
-  const pm::MeshArgs a = {{pm::cloud_cam(camera), filter, (const float*)disp_b.get(), rows, cols, sub_cols,
-                           (long long)sub_rows * sub_cols},
-                          sub_rows, (float)p[10], vertices};
+  const int sub_rows = pm::cloud_grid(rows, stride);
+  const pm::MeshArgs a = {pm::cloud_args(camera, filter, (const float*)disp_b.get(), rows, cols), sub_rows, (float)p[10], vertices};
+  const int sub_cols = a.c.sub_cols;
   const int segments = (sub_cols + block - 1) / block, blocks = sub_rows * segments;
   std::vector<int> order(blocks);
   for (int b = 0; b < blocks; ++b) order[b] = reverse ? blocks - 1 - b : b;

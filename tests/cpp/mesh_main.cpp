@@ -9,27 +9,14 @@
 //                                       all_{xyz.f32, index.i32, tris.i32}: every vertex, stride 1, nothing else
 #include <cstdio>
 #include <cstdlib>
-#include <fstream>
 #include <iostream>
 #include <string>
 #include <vector>
 
 #include "imaging.hpp"
+#include "raw_io.hpp"
 
 using namespace bm::imaging;
-
-template <typename T>
-static bool read_raw(const std::string& path, bm::core::Image<T>& im) {
-  std::ifstream f(path, std::ios::binary);
-  if (!f) return false;
-  f.read(reinterpret_cast<char*>(im.data()), sizeof(T) * (size_t)im.rows * im.cols);
-  return (bool)f;
-}
-template <typename T>
-static void write_raw(const std::string& path, const T* data, size_t count) {
-  std::ofstream f(path, std::ios::binary);
-  f.write(reinterpret_cast<const char*>(data), sizeof(T) * count);
-}
 
 static int ply_only(const std::string& dir) {
   TriangleMesh mesh;

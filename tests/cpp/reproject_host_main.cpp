@@ -17,32 +17,12 @@
 #include <memory>
 #include <string>
 
+#include "host_npy.hpp"
 #include "pm_reproject_body.hpp"
 
-static bool read_npy(const std::string& path, size_t bytes, std::unique_ptr<uint8_t[]>* out) {
-  FILE* f = fopen(path.c_str(), "rb");
-  if (!f) return false;
-  uint8_t head[10];
-  bool ok = fread(head, 1, 10, f) == 10 && !memcmp(head, "\x93NUMPY\x01", 7);
-  const size_t hlen = ok ? (size_t)head[8] | ((size_t)head[9] << 8) : 0;
-  ok = ok && fseek(f, 0, SEEK_END) == 0 && (size_t)ftell(f) == 10 + hlen + bytes && fseek(f, (long)(10 + hlen), SEEK_SET) == 0;
-  if (ok) {
-    out->reset(new uint8_t[bytes ? bytes : 1]);
-    ok = fread(out->get(), 1, bytes, f) == bytes;
-  }
-  fclose(f);
-  if (!ok) fprintf(stderr, "cannot read %zu payload bytes from %s\n", bytes, path.c_str());
-  return ok;
-}
-
-static int differ(const char* what, bool backwards, const void* got, const void* want, size_t bytes) {
-  if (!memcmp(got, want, bytes)) return 0;
-  const uint8_t* g = (const uint8_t*)got;
-  const uint8_t* w = (const uint8_t*)want;
-  size_t at = 0;
-  while (g[at] == w[at]) ++at;
-  fprintf(stderr, "%s differs from the definition at byte %zu of %zu (%s)\n", what, at, bytes, backwards ? "backwards" : "forwards");
-  return 1;
+// a mismatch names the pass it happened in
+static int differ_pass(const char* what, bool backwards, const void* got, const void* want, size_t bytes) {
+  return differ(what, got, want, bytes, backwards ? "backwards" : "forwards");
 }
 
 // i-th of n, counted from the front or from the back
@@ -118,15 +98,15 @@ int main(int argc, char** argv) {
     const pm::ReprojectRightArgs ra = {reinterpret_cast<const float*>(seed_l.get() + shift), rows, cols, splat_r.get()};
     run_splat(ra, rows, cols, backwards, pm::reproject_right_lane);
     run_finish(pm::ReprojectFinishArgs{splat_r.get(), seed_r.get() + shift, rows, cols, r, &counts[1]}, backwards);
-    bad |= differ("seed_l", backwards, seed_l.get() + shift, want_l.get(), 4 * px);
-    bad |= differ("seed_r", backwards, seed_r.get() + shift, want_r.get(), 4 * px);
-    bad |= differ("counts", backwards, counts, want_counts.get(), 8);
+    bad |= differ_pass("seed_l", backwards, seed_l.get() + shift, want_l.get(), 4 * px);
+    bad |= differ_pass("seed_r", backwards, seed_r.get() + shift, want_r.get(), 4 * px);
+    bad |= differ_pass("counts", backwards, counts, want_counts.get(), 8);
     for (int k = 0; k < shift; ++k) bad |= seed_l[k] != 0xA5A5A5A5u || seed_r[k] != 0xA5A5A5A5u;
     // counting alone (no output map) reaches the same counts
     int only[2] = {0, 0};
     run_finish(pm::ReprojectFinishArgs{splat_l.get(), nullptr, rows, cols, r, &only[0]}, backwards);
     run_finish(pm::ReprojectFinishArgs{splat_r.get(), nullptr, rows, cols, r, &only[1]}, backwards);
-    bad |= differ("counts without a map", backwards, only, want_counts.get(), 8);
+    bad |= differ_pass("counts without a map", backwards, only, want_counts.get(), 8);
   }
   return bad ? 1 : 0;
 }

@@ -8,27 +8,14 @@
 //                                                  right_only_counts.i32 of a call without d_seed_l that only enqueues
 #include <cstdio>
 #include <cstdlib>
-#include <fstream>
 #include <iostream>
 #include <string>
 #include <vector>
 
 #include "imaging.hpp"
+#include "raw_io.hpp"
 
 using namespace bm::imaging;
-
-template <typename T>
-static bool read_raw(const std::string& path, T* data, size_t count) {
-  std::ifstream f(path, std::ios::binary);
-  if (!f) return false;
-  f.read(reinterpret_cast<char*>(data), (std::streamsize)(sizeof(T) * count));
-  return (bool)f;
-}
-template <typename T>
-static void write_raw(const std::string& path, const T* data, size_t count) {
-  std::ofstream f(path, std::ios::binary);
-  f.write(reinterpret_cast<const char*>(data), (std::streamsize)(sizeof(T) * count));
-}
 
 // device memory of the matcher's handle, freed on scope exit
 struct Device {

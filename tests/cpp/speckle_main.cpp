@@ -12,14 +12,9 @@
 #include <string>
 
 #include "imaging.hpp"
+#include "raw_io.hpp"
 
 using namespace bm::imaging;
-
-template <typename T>
-static void write_raw(const std::string& path, const T* data, size_t count) {
-  std::ofstream f(path, std::ios::binary);
-  f.write(reinterpret_cast<const char*>(data), sizeof(T) * count);
-}
 
 int main(int argc, char** argv) {
   if (argc < 4) return 2;

@@ -7,29 +7,16 @@
 //                                          and print its topology, or the exception: the multi-device constructor path
 #include <cstdio>
 #include <cstdlib>
-#include <fstream>
 #include <iostream>
 #include <string>
 #include <vector>
 
 #include "patchmatch_gpu.hpp"
+#include "raw_io.hpp"
 
 using namespace bm::pm;
 using bm::core::Image1b;
 using bm::core::Image1f;
-
-template <typename T>
-static bool read_raw(const std::string& path, bm::core::Image<T>& im) {
-  std::ifstream f(path, std::ios::binary);
-  if (!f) return false;
-  f.read(reinterpret_cast<char*>(im.data()), sizeof(T) * (size_t)im.rows * im.cols);
-  return (bool)f;
-}
-template <typename T>
-static void write_raw(const std::string& path, const bm::core::Image<T>& im) {
-  std::ofstream f(path, std::ios::binary);
-  f.write(reinterpret_cast<const char*>(im.data()), sizeof(T) * (size_t)im.rows * im.cols);
-}
 
 int main(int argc, char** argv) {
   if (argc == 3 && std::string(argv[1]) == "devices") {

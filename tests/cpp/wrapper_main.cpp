@@ -5,7 +5,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
 #include <iostream>
 #include <string>
 
@@ -14,23 +13,11 @@
 
 #include "patchmatch_gpu.hpp"
 #include "pm/imaging.h"
+#include "raw_io.hpp"
 
 using namespace bm::pm;
 using bm::core::Image1b;
 using bm::core::Image1f;
-
-template <typename T>
-static bool read_raw(const std::string& path, bm::core::Image<T>& im) {
-  std::ifstream f(path, std::ios::binary);
-  if (!f) return false;
-  f.read(reinterpret_cast<char*>(im.data()), sizeof(T) * (size_t)im.rows * im.cols);
-  return (bool)f;
-}
-template <typename T>
-static void write_raw(const std::string& path, const bm::core::Image<T>& im) {
-  std::ofstream f(path, std::ios::binary);
-  f.write(reinterpret_cast<const char*>(im.data()), sizeof(T) * (size_t)im.rows * im.cols);
-}
 
 int main(int argc, char** argv) {
   if (argc < 7) return 2;

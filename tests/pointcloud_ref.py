@@ -17,6 +17,11 @@ camera: (fx, fy, cx, cy, baseline) of the rectified left view, binary64.
 import numpy as np
 
 
+def camera_for(rows, cols):
+    """The camera the tests of the map stages use at rows x cols: fx != fy, a principal point off the pixel grid."""
+    return (412.7, 398.3, cols / 2 - 0.3, rows / 2 + 0.4, 0.12)
+
+
 def backproject(disp, camera):
     """[rows][cols] float32 -> [rows][cols][3] float32."""
     fx, fy, cx, cy, baseline = (np.float64(v) for v in camera)

@@ -8,23 +8,14 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from conftest import ROOT
+from cpp_build import build_caller
 from test_enhance import color_image
 from test_imaging import B0, BETA_B0, X0, RTOL, ATOL
-
-PKG = os.path.join(ROOT, "ocean-perception_amd")
-LIBDIR = os.path.join(PKG, "lib")
 
 
 @pytest.fixture(scope="module")
 def imaging_exe(tmp_path_factory):
-    out = tmp_path_factory.mktemp("cppimg") / "imaging_main"
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(PKG, "host"), os.path.join(ROOT, "tests", "cpp", "imaging_main.cpp"), "-L" + LIBDIR,
-           "-lvehicle_pm_gpu", "-Wl,-rpath," + LIBDIR, "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(out)
+    return build_caller(tmp_path_factory.mktemp("cppimg") / "imaging_main", "imaging_main.cpp")
 
 
 def _has_gpu():

@@ -11,25 +11,18 @@ import pytest
 
 import pointcloud_ref as PR
 from conftest import ROOT
+from cpp_build import build_caller
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import fuzz_cloud as FC  # noqa: E402
 
-PKG = os.path.join(ROOT, "ocean-perception_amd")
-LIBDIR = os.path.join(PKG, "lib")
 ROWS, COLS = 64, 96
 CAMERA = (412.7, 398.3, COLS // 2 - 0.3, ROWS // 2 + 0.4, 0.12)  # what pointcloud_main.cpp sets
 
 
 @pytest.fixture(scope="module")
 def cloud_exe(tmp_path_factory):
-    out = tmp_path_factory.mktemp("cppcloud") / "pointcloud_main"
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(PKG, "host"), os.path.join(ROOT, "tests", "cpp", "pointcloud_main.cpp"), "-L" + LIBDIR,
-           "-lvehicle_pm_gpu", "-Wl,-rpath," + LIBDIR, "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(out)
+    return build_caller(tmp_path_factory.mktemp("cppcloud") / "pointcloud_main", "pointcloud_main.cpp")
 
 
 def _inputs(tmp_path, synth):

@@ -7,22 +7,15 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
+from cpp_build import build_caller
 
-PKG = os.path.join(ROOT, "ocean-perception_amd")
-LIBDIR = os.path.join(PKG, "lib")
 FIXTURE = os.path.join(GOLDEN, "rectify_bgr_41x59.npz")
 
 
 @pytest.fixture(scope="module")
 def rectify_exe(tmp_path_factory):
-    out = tmp_path_factory.mktemp("cpprectbgr") / "rectify_bgr_main"
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(PKG, "host"), os.path.join(ROOT, "tests", "cpp", "rectify_bgr_main.cpp"), "-L" + LIBDIR,
-           "-lvehicle_pm_gpu", "-Wl,-rpath," + LIBDIR, "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(out)
+    return build_caller(tmp_path_factory.mktemp("cpprectbgr") / "rectify_bgr_main", "rectify_bgr_main.cpp")
 
 
 def _run(exe, tmp_path):

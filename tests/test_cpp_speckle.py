@@ -10,25 +10,18 @@ import pytest
 
 import speckle_ref as SR
 from conftest import ROOT
+from cpp_build import build_caller
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import fuzz_cloud as FC  # noqa: E402
 import fuzz_normals as FN  # noqa: E402
 
-PKG = os.path.join(ROOT, "ocean-perception_amd")
-LIBDIR = os.path.join(PKG, "lib")
 ROWS, COLS = 37, 153  # three tiles wide and three high, none of them whole
 
 
 @pytest.fixture(scope="module")
 def speckle_exe(tmp_path_factory):
-    out = tmp_path_factory.mktemp("cppspeckle") / "speckle_main"
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(PKG, "host"), os.path.join(ROOT, "tests", "cpp", "speckle_main.cpp"), "-L" + LIBDIR,
-           "-lvehicle_pm_gpu", "-Wl,-rpath," + LIBDIR, "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(out)
+    return build_caller(tmp_path_factory.mktemp("cppspeckle") / "speckle_main", "speckle_main.cpp")
 
 
 def _input(tmp_path):

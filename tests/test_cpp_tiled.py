@@ -8,21 +8,13 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import ROOT, assert_same, small_pair
-
-PKG = os.path.join(ROOT, "ocean-perception_amd")
-LIBDIR = os.path.join(PKG, "lib")
+from conftest import assert_same, small_pair
+from cpp_build import build_caller
 
 
 @pytest.fixture(scope="module")
 def tiled_exe(tmp_path_factory):
-    out = tmp_path_factory.mktemp("cpp") / "tiled_main"
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(PKG, "host"), os.path.join(ROOT, "tests", "cpp", "tiled_main.cpp"), "-L" + LIBDIR,
-           "-lvehicle_pm_gpu", "-Wl,-rpath," + LIBDIR, "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(out)
+    return build_caller(tmp_path_factory.mktemp("cpp") / "tiled_main", "tiled_main.cpp")
 
 
 def run(exe, tmp_path, l, r, sl, sr, sem, patch, iters, bands, rounds):

@@ -8,20 +8,14 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, assert_same, small_pair
+from cpp_build import build_caller
 
-PKG = os.path.join(ROOT, "ocean-perception_amd")
-LIBDIR = os.path.join(PKG, "lib")
+FAKE_OPENCV = os.path.join(ROOT, "tests", "cpp", "fake_opencv")  # a stand-in for <opencv2/core.hpp>
 
 
 @pytest.fixture(scope="module")
 def wrapper_exe(tmp_path_factory):
-    out = tmp_path_factory.mktemp("cpp") / "wrapper_main"
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(PKG, "host"), os.path.join(ROOT, "tests", "cpp", "wrapper_main.cpp"), "-L" + LIBDIR,
-           "-lvehicle_pm_gpu", "-Wl,-rpath," + LIBDIR, "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(out)
+    return build_caller(tmp_path_factory.mktemp("cpp") / "wrapper_main", "wrapper_main.cpp")
 
 
 def _has_gpu():
@@ -88,14 +82,8 @@ def opencv_caller_exe(tmp_path_factory):
     """tests/cpp/opencv_caller_main.cpp: the reference's include line, using-directives, image types and the call
     sequence of test/stereo_matching/patchmatch_gpu_test.cpp:68-88, compiled against this build's header with a stand-in
     for <opencv2/core.hpp> on the include path (OpenCV itself is not in the image)."""
-    out = tmp_path_factory.mktemp("cpp") / "opencv_caller_main"
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "tests", "cpp", "fake_opencv"),
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "host"),
-           os.path.join(ROOT, "tests", "cpp", "opencv_caller_main.cpp"), "-L" + LIBDIR, "-lvehicle_pm_gpu",
-           "-Wl,-rpath," + LIBDIR, "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(out)
+    return build_caller(tmp_path_factory.mktemp("cpp") / "opencv_caller_main", "opencv_caller_main.cpp",
+                        flags=("-Wall", "-Wextra", "-Werror"), include_first=(FAKE_OPENCV,))
 
 
 def test_reference_caller_with_cv_mat_types_builds_unchanged(opencv_caller_exe):
@@ -106,13 +94,7 @@ def test_reference_caller_with_cv_mat_types_builds_unchanged(opencv_caller_exe):
 
 def test_own_image_class_still_builds_with_opencv_switched_off(tmp_path):
     """PM_NO_OPENCV_TYPES keeps bm::core::Image<T> as Image1b / Image1f even with an opencv2/core.hpp in reach."""
-    out = tmp_path / "wrapper_no_cv"
-    cmd = ["g++", "-std=c++17", "-O1", "-DPM_NO_OPENCV_TYPES", "-I" + os.path.join(ROOT, "tests", "cpp", "fake_opencv"),
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "host"),
-           os.path.join(ROOT, "tests", "cpp", "wrapper_main.cpp"), "-L" + LIBDIR, "-lvehicle_pm_gpu", "-Wl,-rpath," + LIBDIR,
-           "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    build_caller(tmp_path / "wrapper_no_cv", "wrapper_main.cpp", flags=("-DPM_NO_OPENCV_TYPES",), include_first=(FAKE_OPENCV,))
 
 
 @pytest.mark.gpu

@@ -10,9 +10,9 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, assert_same, small_pair
+from cpp_build import build_caller
 
 PKG = os.path.join(ROOT, "ocean-perception_amd")
-LIBDIR = os.path.join(PKG, "lib")
 
 
 def write_png(path, img, filters=(0, 1, 2, 3, 4)):
@@ -60,13 +60,7 @@ def write_png(path, img, filters=(0, 1, 2, 3, 4)):
 
 @pytest.fixture(scope="module")
 def dataset_exe(tmp_path_factory):
-    out = tmp_path_factory.mktemp("cppds") / "dataset_main"
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(PKG, "host"), os.path.join(ROOT, "tests", "cpp", "dataset_main.cpp"), "-L" + LIBDIR,
-           "-lvehicle_pm_gpu", "-Wl,-rpath," + LIBDIR, "-pthread", "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(out)
+    return build_caller(tmp_path_factory.mktemp("cppds") / "dataset_main", "dataset_main.cpp", link=("-pthread",))
 
 
 def _read(exe, path, tmp_path):

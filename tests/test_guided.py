@@ -13,7 +13,8 @@ import pytest
 
 import guided_ref as G
 import oracle_lib as O
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
+from cpp_build import build_caller
 from test_imaging import B0, BETA_B0, X0, RTOL, ATOL, scene
 
 FIXTURE = os.path.join(GOLDEN, "guided_61x99.npz")
@@ -456,15 +457,7 @@ def test_enhance_chain_with_every_image_on_the_device(pm, oracle, synth):
 # ---- 9. the C++ mirror ----------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def guided_exe(tmp_path_factory):
-    pkg = os.path.join(ROOT, "ocean-perception_amd")
-    libdir = os.path.join(pkg, "lib")
-    out = tmp_path_factory.mktemp("cppguided") / "guided_main"
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(pkg, "host"), os.path.join(ROOT, "tests", "cpp", "guided_main.cpp"), "-L" + libdir,
-           "-lvehicle_pm_gpu", "-Wl,-rpath," + libdir, "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(out)
+    return build_caller(tmp_path_factory.mktemp("cppguided") / "guided_main", "guided_main.cpp")
 
 
 def test_guided_mirror_builds_with_gxx(guided_exe):

@@ -20,6 +20,8 @@ import normals_fit_ref as NR
 import pointcloud_ref as PR
 import speckle_ref as SR
 from conftest import GOLDEN, ROOT
+from cpp_build import build_host_kernel
+from pointcloud_ref import camera_for
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import fuzz_cloud as FC  # noqa: E402
@@ -27,11 +29,6 @@ import fuzz_mesh as FM  # noqa: E402  (check_mesh: the device-against-definition
 
 gpu = pytest.mark.gpu
 MODES = (MR.VERTICES_ALL, MR.VERTICES_REFERENCED)
-
-
-def camera_for(rows, cols):
-    """fx != fy, a principal point off the pixel grid."""
-    return (412.7, 398.3, cols / 2 - 0.3, rows / 2 + 0.4, 0.12)
 
 
 # ---- 1. the definition ------------------------------------------------------------------------------------------------
@@ -120,15 +117,7 @@ def test_definition_specials_never_join():
 @pytest.fixture(scope="module")
 def host_mesh_exe(tmp_path_factory):
     """tests/cpp/mesh_host_main.cpp: csrc/pm_mesh_body.hpp compiled for the host alone, with the sanitizers."""
-    out = tmp_path_factory.mktemp("meshhost") / "mesh_host_main"
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "-x", "hip", "--cuda-host-only", "-O1", "-std=c++17", "-ffp-contract=off",
-           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(ROOT, "ocean-perception_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "mesh_host_main.cpp"),
-           "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(out)
+    return build_host_kernel(tmp_path_factory.mktemp("meshhost") / "mesh_host_main", "mesh_host_main.cpp")
 
 
 def _dump_case(path, rng, block, rows, cols, stride, mode, vcap, tcap, reverse):

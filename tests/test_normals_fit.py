@@ -19,6 +19,8 @@ import pytest
 import normals_fit_ref as NR
 import pointcloud_ref as PR
 from conftest import GOLDEN, ROOT
+from cpp_build import build_host_kernel
+from pointcloud_ref import camera_for
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import fuzz_cloud as FC  # noqa: E402
@@ -27,11 +29,6 @@ import fuzz_normals as FN  # noqa: E402  (check_normals_fit: the device-against-
 gpu = pytest.mark.gpu
 RADII = (1, 2, 5, 7)
 SUBSETS = [s for n in (1, 2, 3) for s in itertools.combinations(FN.OUTPUTS, n)]  # every non-empty subset of the outputs
-
-
-def camera_for(rows, cols):
-    """fx != fy, a principal point off the pixel grid."""
-    return (412.7, 398.3, cols / 2 - 0.3, rows / 2 + 0.4, 0.12)
 
 
 # ---- 1. the definition ------------------------------------------------------------------------------------------------
@@ -187,15 +184,7 @@ def test_edge_rules_special_values():
 @pytest.fixture(scope="module")
 def host_fit_exe(tmp_path_factory):
     """tests/cpp/normals_fit_host_main.cpp: csrc/pm_normals_fit_body.hpp compiled for the host alone, with the sanitizers."""
-    out = tmp_path_factory.mktemp("fithost") / "normals_fit_host_main"
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "-x", "hip", "--cuda-host-only", "-O1", "-std=c++17", "-ffp-contract=off",
-           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(ROOT, "ocean-perception_amd", "csrc"),
-           os.path.join(ROOT, "tests", "cpp", "normals_fit_host_main.cpp"), "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(out)
+    return build_host_kernel(tmp_path_factory.mktemp("fithost") / "normals_fit_host_main", "normals_fit_host_main.cpp")
 
 
 def _dump_case(path, disp, cam, radius, max_diff, min_support, shift):

@@ -17,16 +17,13 @@ import pytest
 
 import pointcloud_ref as PR
 from conftest import GOLDEN, ROOT
+from cpp_build import build_host_kernel
+from pointcloud_ref import camera_for
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import fuzz_cloud as FC  # noqa: E402  (check_backproject / check_cloud: the device-against-definition comparisons)
 
 gpu = pytest.mark.gpu
-
-
-def camera_for(rows, cols):
-    """fx != fy, a principal point off the pixel grid."""
-    return (412.7, 398.3, cols / 2 - 0.3, rows / 2 + 0.4, 0.12)
 
 
 # ---- 1. the definition ------------------------------------------------------------------------------------------------
@@ -89,15 +86,7 @@ def test_definition_z_is_the_range_of_disp_to_range():
 @pytest.fixture(scope="module")
 def host_cloud_exe(tmp_path_factory):
     """tests/cpp/cloud_host_main.cpp: csrc/pm_cloud_body.hpp compiled for the host alone, with the sanitizers."""
-    out = tmp_path_factory.mktemp("cloudhost") / "cloud_host_main"
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "-x", "hip", "--cuda-host-only", "-O1", "-std=c++17", "-ffp-contract=off",
-           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(ROOT, "ocean-perception_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "cloud_host_main.cpp"),
-           "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(out)
+    return build_host_kernel(tmp_path_factory.mktemp("cloudhost") / "cloud_host_main", "cloud_host_main.cpp")
 
 
 def _dump_case(path, rng, rows, cols, shift, min_disp, max_range, stride, capacity):

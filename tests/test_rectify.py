@@ -15,6 +15,7 @@ import pytest
 
 import rectify_ref as RR
 from conftest import GOLDEN, ROOT
+from cpp_build import build_host_kernel
 
 FIXTURE = os.path.join(GOLDEN, "rectify_37x53.npz")
 DIST = (-0.28, 0.07, 2e-4, 2e-5, 0.0)  # k1, k2, p1, p2, k3
@@ -266,15 +267,7 @@ def test_stereo_rectify_puts_points_on_equal_rows_with_the_pinhole_disparity(pm)
 @pytest.fixture(scope="module")
 def host_kernel_exe(tmp_path_factory):
     """tests/cpp/rectify_host_main.cpp: csrc/pm_rectify.hpp compiled for the host alone, with the sanitizers."""
-    out = tmp_path_factory.mktemp("rectifyhost") / "rectify_host_main"
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "-x", "hip", "--cuda-host-only", "-O1", "-std=c++17", "-ffp-contract=off",
-           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(ROOT, "ocean-perception_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "rectify_host_main.cpp"),
-           "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(out)
+    return build_host_kernel(tmp_path_factory.mktemp("rectifyhost") / "rectify_host_main", "rectify_host_main.cpp")
 
 
 def test_kernel_code_on_the_host_equals_the_definition(host_kernel_exe, tmp_path):

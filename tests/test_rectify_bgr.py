@@ -16,6 +16,7 @@ import pytest
 import rectify_bgr_ref as RB
 import rectify_ref as RR
 from conftest import GOLDEN, ROOT
+from cpp_build import build_host_kernel
 from test_rectify import _match_pair, image, radtan_view, rot
 
 FIXTURE = os.path.join(GOLDEN, "rectify_bgr_41x59.npz")
@@ -84,15 +85,7 @@ def test_definition_reproduces_its_fixture():
 def host_kernel_exe(tmp_path_factory):
     """tests/cpp/rectify_host_main.cpp (the program of tests/test_rectify.py, run here in its bgr mode): csrc/pm_rectify.hpp
     compiled for the host alone, with the sanitizers."""
-    out = tmp_path_factory.mktemp("rectifybgrhost") / "rectify_bgr_host_main"
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "-x", "hip", "--cuda-host-only", "-O1", "-std=c++17", "-ffp-contract=off",
-           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(ROOT, "ocean-perception_amd", "csrc"),
-           os.path.join(ROOT, "tests", "cpp", "rectify_host_main.cpp"), "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(out)
+    return build_host_kernel(tmp_path_factory.mktemp("rectifybgrhost") / "rectify_bgr_host_main", "rectify_host_main.cpp")
 
 
 def test_kernel_code_on_the_host_equals_the_definition(host_kernel_exe, tmp_path):

@@ -18,6 +18,8 @@ import pytest
 
 import reproject_ref as RR
 from conftest import ROOT
+from cpp_build import build_host_kernel
+from pointcloud_ref import camera_for
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import fuzz_reproject as FR  # noqa: E402  (check_reproject: the device-against-definition comparison)
@@ -26,11 +28,6 @@ gpu = pytest.mark.gpu
 
 CAM = (412.7, 398.3, 39.7, 24.4, 0.12)  # the camera of the analytic cases, for a 48x80 map
 FXB = np.float64(CAM[0]) * np.float64(CAM[4])
-
-
-def camera_for(rows, cols):
-    """fx != fy, a principal point off the pixel grid."""
-    return (412.7, 398.3, cols / 2 - 0.3, rows / 2 + 0.4, 0.12)
 
 
 def two_level(rows, cols, seed=0, far=6.0, near=14.0, zeros=0.08, very_near=False):
@@ -136,15 +133,7 @@ def test_relative_motion_of_the_definition():
 @pytest.fixture(scope="module")
 def host_reproject_exe(tmp_path_factory):
     """tests/cpp/reproject_host_main.cpp: csrc/pm_reproject_body.hpp compiled for the host alone, with the sanitizers."""
-    out = tmp_path_factory.mktemp("reprojecthost") / "reproject_host_main"
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "-x", "hip", "--cuda-host-only", "-O1", "-std=c++17", "-ffp-contract=off",
-           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
-           "-I" + os.path.join(ROOT, "ocean-perception_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "reproject_host_main.cpp"),
-           "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return str(out)
+    return build_host_kernel(tmp_path_factory.mktemp("reprojecthost") / "reproject_host_main", "reproject_host_main.cpp")
 
 
 def _dump_case(path, disp, cam, motion, min_disp, max_disp, r, shift):

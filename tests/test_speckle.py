@@ -18,6 +18,7 @@ import pytest
 
 import speckle_ref as SR
 from conftest import ROOT
+from cpp_build import CSRC, SANITIZE, build_host_kernel
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import fuzz_cloud as FC  # noqa: E402
@@ -124,12 +125,8 @@ def test_kernel_code_on_the_host_equals_a_flood_fill_under_sanitizers(tmp_path):
     run in forward, reverse and shuffled order; labels, sizes, output and the removed count equal a flood fill written in
     that file every time.  This covers indexing and SEQUENTIAL order-independence; it does not cover concurrent
     interleavings, which rest on the argument next to speckle_union and on the GPU tests below."""
-    exe = str(tmp_path / "speckle_host_main")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-ffp-contract=off", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "ocean-perception_amd", "csrc"),
-           os.path.join(ROOT, "tests", "cpp", "speckle_host_main.cpp"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_host_kernel(tmp_path / "speckle_host_main", "speckle_host_main.cpp", compiler=("g++",),
+                            flags=("-std=c++17", "-O1", "-Wall", "-Wextra", "-ffp-contract=off") + SANITIZE, include=(CSRC,))
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and "64 maps x 3 orders, 0 mismatches" in r.stdout, r.stdout + r.stderr[-3000:]
     # the program does compare: one flipped bit in an expectation is a mismatch, not a pass

@@ -192,15 +192,10 @@ def test_invalid_arguments_are_refused(pm):
 def test_the_plan_compiles_without_hip_and_walks_its_grid_clean_under_the_sanitizers(tmp_path):
     """tests/cpp/sweep_plan_main.cpp: csrc/pm_sweep_plan.hpp through g++ (no HIP header in reach) with AddressSanitizer and
     UBSan, over shapes, windows, amplitudes, engines and slot counts, degenerate ones included."""
-    import os
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = str(tmp_path / "sweep_plan_main")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-           "-fno-sanitize-recover=all", "-I" + os.path.join(root, "include"),
-           "-I" + os.path.join(root, "ocean-perception_amd", "csrc"), os.path.join(root, "tests", "cpp", "sweep_plan_main.cpp"),
-           "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    from cpp_build import build_host_kernel
+    exe = build_host_kernel(tmp_path / "sweep_plan_main", "sweep_plan_main.cpp", compiler=("g++",),
+                            flags=("-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                                   "-fno-sanitize-recover=all"))
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and r.stderr == "" and r.stdout.endswith(" 0 broken\n"), (r.stdout, r.stderr)
