@@ -442,6 +442,55 @@ int pm_reproject_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm
                            float* d_seed_l /* may be NULL */, float* d_seed_r /* may be NULL */,
                            int* d_counts /* device int[2], may be NULL */, int* counts /* host int[2], may be NULL */);
 
+/* ---- geometric consistency: keep of a map what earlier frames of the sequence confirm ------------------------------------
+ * What it is for: the judgement a sequence can pass on a map.  PatchMatch's mistakes follow per-frame noise, so a wrong island
+ * of frame k is usually elsewhere in frame k - 1.  Every pixel of the CURRENT left map is carried into n earlier left maps of
+ * the same size and rectified camera through the known motions (the geometric consistency check of multi-view PatchMatch with
+ * visibility-based fusion): it is kept iff enough of them saw the same surface and not too many saw through it.  The depth is
+ * known in the current frame, so every lookup is a gather; nothing is averaged or filled.
+ * Held to its CPU definition (tests/consistency_ref.py) BIT FOR BIT:
+ *   motions    motions[k]: X_src_k = R X_cur + t between the LEFT camera frames, R row-major: with pm_reproject_disparity's
+ *              convention, the motion from the current pose (as "old") to source k's pose (as "new").
+ *   valid      a current pixel is valid iff d = D(y, x) > 0 (binary32): not for 0, -0.0, negatives and NaN; +inf is valid.
+ *   project    into source k: EXACTLY pm_reproject_disparity's `splat` arithmetic with min_disp = 0 and max_disp = 0 (Z, X, Y;
+ *              Xn, Yn, Zn, dropped unless Zn > 0; dp = (float)(fxB / Zn), dropped unless dp > 0 and finite; u, v, the 2^30
+ *              guard, rint half to even, dropped outside the image) -> (iu, iv) and dp.  A dropped pixel has class UNSEEN.
+ *   tap        the window dy = -radius..radius, dx = -radius..radius around (iu, iv) in row-major order; a tap COUNTS iff it
+ *              lies inside the image and ds = D_k(iv + dy, iu + dx) > 0; e = (double)ds - (double)dp in binary64.  The chosen
+ *              tap is the FIRST one with the smallest fabs(e): a later tap replaces it only with a strictly smaller value (a
+ *              ds of +inf gives e = +inf and loses against any finite one).  No counting tap: class UNSEEN.
+ *   class      with md = (double)max_diff:  fabs(e) <= md  CONSISTENT (1);  e > md  OCCLUDED (2): the source saw something
+ *              nearer there and says nothing about this pixel;  e < -md  CONFLICT (3): the source saw through the point;
+ *              UNSEEN is 0.
+ *   per pixel  n_cons, n_conf: the sources of class 1 and of class 3.  S: a binary64 sum from +0.0 over k = 0 .. n - 1 in
+ *              order, S = S + fabs(e_k) for the CONSISTENT sources.  KEPT iff valid, n_cons >= min_consistent and
+ *              n_conf <= max_conflicts.
+ *   d_out      a valid pixel that is not KEPT becomes +0.0f; every other pixel, invalid ones included, keeps its input bits
+ *              (pm_filter_speckles' rule).  May equal d_disp unless d_disp is itself a source.
+ *   d_classes  uint16 per pixel: the class of source k in bits 2k and 2k + 1; 0 for an invalid pixel.
+ *   d_residual (float)(S / (double)n_cons), +0.0 where n_cons == 0 or the pixel is invalid.
+ *   counts     counts[0] / d_counts[0] = valid pixels, [1] = kept pixels.
+ * Every output is optional, but at least one must be given.  A source may be d_disp itself.  Valid in every mode of the
+ * handle: it reads maps, not the handle's state.  It enqueues on the handle's stream; a non-NULL `counts` synchronises it like
+ * pm_point_cloud's `count`, otherwise the call only enqueues.  d_sources and motions are HOST arrays of n_sources entries,
+ * read before the call returns.  One launch behind a 16-byte memset; only integer addition crosses workgroups, so every output
+ * is a pure function of the inputs.  Scratch is the 16 bytes of the counts, allocated on first use, reused, and released with
+ * the handle.
+ * PM_ERR_INVALID_ARG, with pm_last_error naming the argument and nothing enqueued: a null camera, options, d_disp, d_sources,
+ * motions or d_sources[k]; a camera pm_backproject refuses; n_sources outside 1..PM_CONSISTENCY_MAX_SOURCES; a non-finite
+ * entry of motions[k] (named with k); a max_diff that is not finite or < 0; radius outside 0..2; min_consistent outside
+ * 0..n_sources; max_conflicts outside 0..8; rows or cols < 1; no output at all; d_out equal to a source (this covers
+ * d_out == d_disp where d_disp is itself a source).  PM_ERR_SIZE as for pm_backproject. */
+#define PM_CONSISTENCY_MAX_SOURCES 8
+enum { PM_CONSISTENCY_UNSEEN = 0, PM_CONSISTENCY_CONSISTENT = 1, PM_CONSISTENCY_OCCLUDED = 2, PM_CONSISTENCY_CONFLICT = 3 };
+typedef struct pm_consistency_options { float max_diff; int radius; int min_consistent; int max_conflicts; } pm_consistency_options;
+int pm_filter_consistency(pm_handle* h, const pm_cloud_camera* camera, const pm_consistency_options* options,
+                          const float* d_disp, int n_sources, const float* const* d_sources /* host array of device maps */,
+                          const pm_motion* motions /* host array */, int rows, int cols,
+                          float* d_out /* may be NULL, may equal d_disp */, uint16_t* d_classes /* may be NULL */,
+                          float* d_residual /* may be NULL */, int* d_counts /* device int[2], may be NULL */,
+                          int* counts /* host int[2], may be NULL: non-NULL synchronises like pm_point_cloud's count */);
+
 /* ---- device buffers for host code that does not include HIP (host/imaging.hpp uses them) ------------------
  * pm_device_malloc / pm_device_free wrap hipMalloc / hipFree on the handle's device; pm_upload / pm_download are
  * stream-ordered copies on the handle's stream from / to pageable host memory (pm_download returns after the

@@ -18,6 +18,7 @@
 //     pm_mesh.hpp        the three kernels of pm_grid_mesh (k_mesh_count / _vertices / _triangles)
 //     pm_reproject.hpp   the three kernels of pm_reproject_disparity (k_reproject_splat / _splat_right / _finish); their
 //                        bodies are pm_reproject_body.hpp's
+//     pm_consistency.hpp the kernel of pm_filter_consistency (k_consistency<RADIUS>); its body is pm_consistency_body.hpp's
 // Every __global__ kernel lives in exactly one unit; the others reach it through the launch functions declared here.
 #pragma once
 

@@ -47,6 +47,8 @@ struct ImagingState {
   // pm_reproject_disparity: kReprojectHeader words ([0], [1]: the counts), the left and the right splat map, one word per
   // pixel each (the memset of a call clears up to here), then the closed left seed of a call without d_seed_l
   DevBuf<unsigned> reproject_buf;
+  // pm_filter_consistency: kConsistencyHeader words ([0] valid pixels, [1] kept pixels), cleared per call
+  DevBuf<int> consistency_counts;
 };
 
 #define PM_HIP(h, call)                                                                                     \

@@ -51,30 +51,48 @@ struct ReprojectArgs {
   unsigned* splat;  // [rows][cols], zeroed
 };
 
-// Where source pixel (x, y) with disparity d lands and with which value; false where it is dropped.
-__host__ __device__ __forceinline__ bool reproject_pixel(const ReprojectArgs& a, float d, int x, int y, int* iu, int* iv,
-                                                         float* dn) {
-  const CloudCam& c = a.cam;
-  bool ok = d > 0.f && d >= a.min_disp;
+// The two halves of carrying a pixel through a motion, shared with pm_filter_consistency (pm_consistency_body.hpp), which
+// keeps the first half's point across its sources.  First half: the point P = (X, Y, Z) of pixel (x, y) with disparity d in
+// binary64 (pm_backproject's values before their rounding); false where the pixel takes no part.
+__host__ __device__ __forceinline__ bool reproject_point(const CloudCam& c, float min_disp, float d, int x, int y, double P[3]) {
+  const bool ok = d > 0.f && d >= min_disp;
   const double Z = c.fxb / (double)(ok ? d : 1.f);
-  const double X = (((double)x - c.cx) * Z) / c.fx;
-  const double Y = (((double)y - c.cy) * Z) / c.fy;
-  const double Xn = (((a.R[0] * X) + (a.R[1] * Y)) + (a.R[2] * Z)) + a.t[0];
-  const double Yn = (((a.R[3] * X) + (a.R[4] * Y)) + (a.R[5] * Z)) + a.t[1];
-  const double Zn = (((a.R[6] * X) + (a.R[7] * Y)) + (a.R[8] * Z)) + a.t[2];
+  P[0] = (((double)x - c.cx) * Z) / c.fx;
+  P[1] = (((double)y - c.cy) * Z) / c.fy;
+  P[2] = Z;
+  return ok;
+}
+
+// Second half: P through X_new = R X + t and into the rows x cols image of the same camera: the pixel it lands on and the
+// disparity it has there.  `ok`: the first half's answer; false where the point is dropped, and (iu, iv) is then (0, 0).
+__host__ __device__ __forceinline__ bool reproject_project(const CloudCam& c, const double R[9], const double t[3],
+                                                           float max_disp, int rows, int cols, bool ok, const double P[3],
+                                                           int* iu, int* iv, float* dn) {
+  const double X = P[0], Y = P[1], Z = P[2];
+  const double Xn = (((R[0] * X) + (R[1] * Y)) + (R[2] * Z)) + t[0];
+  const double Yn = (((R[3] * X) + (R[4] * Y)) + (R[5] * Z)) + t[1];
+  const double Zn = (((R[6] * X) + (R[7] * Y)) + (R[8] * Z)) + t[2];
   ok = ok && Zn > 0.0;
   const float v = (float)(c.fxb / Zn);
-  ok = ok && v > 0.f && v < __builtin_inff() && (a.max_disp == 0.f || v <= a.max_disp);
+  ok = ok && v > 0.f && v < __builtin_inff() && (max_disp == 0.f || v <= max_disp);
   const double u = (c.fx * (Xn / Zn)) + c.cx;
   const double w = (c.fy * (Yn / Zn)) + c.cy;
   const double lim = 1073741824.0;  // 2^30: what follows fits an int
   ok = ok && __builtin_fabs(u) < lim && __builtin_fabs(w) < lim;
   const double ru = __builtin_rint(u), rw = __builtin_rint(w);  // half to even
-  ok = ok && ru >= 0.0 && ru < (double)a.cols && rw >= 0.0 && rw < (double)a.rows;
+  ok = ok && ru >= 0.0 && ru < (double)cols && rw >= 0.0 && rw < (double)rows;
   *iu = ok ? (int)ru : 0;
   *iv = ok ? (int)rw : 0;
   *dn = v;
   return ok;
+}
+
+// Where source pixel (x, y) with disparity d lands and with which value; false where it is dropped.
+__host__ __device__ __forceinline__ bool reproject_pixel(const ReprojectArgs& a, float d, int x, int y, int* iu, int* iv,
+                                                         float* dn) {
+  double P[3];
+  const bool ok = reproject_point(a.cam, a.min_disp, d, x, y, P);
+  return reproject_project(a.cam, a.R, a.t, a.max_disp, a.rows, a.cols, ok, P, iu, iv, dn);
 }
 
 // The work of one thread of k_reproject_splat: source pixels x, x + 64, x + 128, x + 192 of row y.  The lanes of a wavefront

@@ -1,8 +1,8 @@
 // pm_stages.hip -- C-ABI implementation of the stages of include/pm/imaging.h that read a finished disparity map: points,
-// plane-mode normals and the compacted cloud, the windowed plane fit, the speckle filter, the grid mesh and the temporal
-// seeds.  Like pm_imaging.hip it reaches the handle only through pm_internal.hpp, and it shares that unit's one state
-// object (pm_imaging_state.hpp).  Every entry point: its argument checks in a fixed order (the first fault is the one
-// reported), then the device, then its launches on the handle's stream.
+// plane-mode normals and the compacted cloud, the windowed plane fit, the speckle filter, the grid mesh, the temporal
+// seeds and the consistency filter.  Like pm_imaging.hip it reaches the handle only through pm_internal.hpp, and it shares
+// that unit's one state object (pm_imaging_state.hpp).  Every entry point: its argument checks in a fixed order (the first
+// fault is the one reported), then the device, then its launches on the handle's stream.
 #include "pm/imaging.h"
 #include "pm/testing.h"
 
@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "pm_cloud.hpp"
+#include "pm_consistency.hpp"
 #include "pm_imaging_state.hpp"
 #include "pm_mesh.hpp"
 #include "pm_normals_fit.hpp"
@@ -449,4 +450,89 @@ int pm_reproject_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm
 void pm_debug_reproject_constants(int* tile_w, int* tile_h) {
   if (tile_w) *tile_w = kReprojectTileW;
   if (tile_h) *tile_h = kReprojectTileH;
+}
+
+// ---- geometric consistency: a map judged by earlier maps of its sequence (pm_consistency.hpp) -------------------------------
+namespace {
+constexpr size_t kConsistencyHeader = 4;  // the two counts, padded to 16 bytes
+
+template <int RADIUS>
+void launch_consistency(const ConsistencyArgs& a, dim3 grid, hipStream_t stream) {
+  hipLaunchKernelGGL(k_consistency<RADIUS>, grid, dim3(kConsistencyBlockX, kConsistencyBlockY), 0, stream, a);
+}
+}  // namespace
+
+int pm_filter_consistency(pm_handle* h, const pm_cloud_camera* camera, const pm_consistency_options* options,
+                          const float* d_disp, int n_sources, const float* const* d_sources, const pm_motion* motions, int rows,
+                          int cols, float* d_out, uint16_t* d_classes, float* d_residual, int* d_counts, int* counts) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_filter_consistency";
+  if (int rc = check_cloud_camera(h, what, camera)) return rc;
+  if (!options || !d_disp || !d_sources || !motions) {
+    set_err(h, "%s: null %s", what, !options ? "options" : !d_disp ? "d_disp" : !d_sources ? "d_sources" : "motions");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (n_sources < 1 || n_sources > kConsistencyMaxSources) {
+    set_err(h, "%s: n_sources %d outside 1..%d", what, n_sources, kConsistencyMaxSources);
+    return PM_ERR_INVALID_ARG;
+  }
+  for (int k = 0; k < n_sources; ++k) {
+    if (!d_sources[k]) {
+      set_err(h, "%s: null d_sources[%d]", what, k);
+      return PM_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < 12; ++i)
+      if (!std::isfinite(i < 9 ? motions[k].R[i] : motions[k].t[i - 9])) {
+        set_err(h, "%s: %s[%d] of motions[%d] is not finite", what, i < 9 ? "R" : "t", i < 9 ? i : i - 9, k);
+        return PM_ERR_INVALID_ARG;
+      }
+  }
+  if (int rc = check_max_diff(h, what, options->max_diff)) return rc;
+  if (options->radius < 0 || options->radius > kConsistencyMaxRadius) {
+    set_err(h, "%s: radius %d outside 0..%d", what, options->radius, kConsistencyMaxRadius);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (options->min_consistent < 0 || options->min_consistent > n_sources) {
+    set_err(h, "%s: min_consistent %d outside 0..n_sources (%d)", what, options->min_consistent, n_sources);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (options->max_conflicts < 0 || options->max_conflicts > kConsistencyMaxSources) {
+    set_err(h, "%s: max_conflicts %d outside 0..%d", what, options->max_conflicts, kConsistencyMaxSources);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
+  if (!d_out && !d_classes && !d_residual && !d_counts && !counts) {
+    set_err(h, "%s: no output: d_out, d_classes, d_residual, d_counts and counts are all null", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  for (int k = 0; d_out && k < n_sources; ++k)
+    if (d_out == d_sources[k]) {  // a pixel of a source is read by other pixels' lookups
+      set_err(h, "%s: d_out must not alias d_sources[%d]", what, k);
+      return PM_ERR_INVALID_ARG;
+    }
+  ImagingState* st = nullptr;
+  hipStream_t stream = nullptr;
+  if (int rc = stage_begin(h, what, &st, &stream)) return rc;
+  PM_HIP(h, st->consistency_counts.reserve(sizeof(int) * kConsistencyHeader, stream));
+  int* d_totals = st->consistency_counts.get();
+  ConsistencyArgs a = {};
+  a.cam = cloud_cam(*camera);
+  a.disp = d_disp, a.rows = rows, a.cols = cols, a.n = n_sources;
+  a.max_diff = options->max_diff, a.min_consistent = options->min_consistent, a.max_conflicts = options->max_conflicts;
+  a.out = d_out, a.classes = d_classes, a.residual = d_residual, a.counts = d_totals;
+  for (int k = 0; k < n_sources; ++k) {
+    for (int i = 0; i < 9; ++i) a.src[k].R[i] = motions[k].R[i];
+    for (int i = 0; i < 3; ++i) a.src[k].t[i] = motions[k].t[i];
+    a.src[k].map = d_sources[k];
+  }
+  PM_HIP(h, hipMemsetAsync(d_totals, 0, sizeof(int) * kConsistencyHeader, stream));
+  const dim3 grid((unsigned)((cols + kConsistencySpan - 1) / kConsistencySpan),
+                  (unsigned)((rows + kConsistencyBlockY - 1) / kConsistencyBlockY));
+  switch (options->radius) {
+    case 0: launch_consistency<0>(a, grid, stream); break;
+    case 1: launch_consistency<1>(a, grid, stream); break;
+    default: launch_consistency<2>(a, grid, stream); break;
+  }
+  if (int rc = launch_check(h, "consistency filter")) return rc;
+  return stage_counts(h, stream, d_totals, 2, d_counts, counts);
 }

@@ -484,6 +484,62 @@ std::array<int, 2> ReprojectDisparity(pm::PatchmatchGpu& matcher, const StereoMo
   return {{counts[0], counts[1]}};
 }
 
+std::array<int, 2> FilterConsistency(pm::PatchmatchGpu& matcher, const StereoModel& model,
+                                     const std::vector<core::Image<float>>& sources, const std::vector<Motion>& motions,
+                                     const ConsistencyOptions& options, const core::Image<float>& disp,
+                                     core::Image<float>* out, core::Image<uint16_t>* classes, core::Image<float>* residual) {
+  pm_handle* h = matcher.handle();
+  if (!h) throw std::runtime_error("FilterConsistency: the matcher has no handle yet (plan it or match once)");
+  if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("FilterConsistency: empty map");
+  if (sources.size() != motions.size()) throw std::invalid_argument("FilterConsistency: one motion per source");
+  for (const core::Image<float>& s : sources) SameSize(disp.rows, disp.cols, s.rows, s.cols, "FilterConsistency");
+  // the matcher's handle, not the imaging context's: every buffer is freed on every way out
+  struct Buffers {
+    pm_handle* h;
+    std::vector<void*> p;
+    ~Buffers() {
+      for (void* q : p) pm_device_free(h, q);
+    }
+    void Check(int status, const char* what) const {
+      if (status != PM_OK) throw std::runtime_error(std::string(what) + ": " + pm_status_string(status) + " -- " + pm_last_error(h));
+    }
+    void* Get(size_t bytes) {
+      void* q = nullptr;
+      Check(pm_device_malloc(h, bytes, &q), "pm_device_malloc");
+      p.push_back(q);
+      return q;
+    }
+  } dev{h, {}};
+  const size_t px = (size_t)disp.rows * disp.cols;
+  float* d_disp = static_cast<float*>(dev.Get(4 * px));
+  dev.Check(pm_upload(h, d_disp, disp.data(), 4 * px), "pm_upload");
+  std::vector<const float*> d_sources;
+  std::vector<pm_motion> m(motions.size());
+  for (size_t k = 0; k < sources.size(); ++k) {
+    void* q = dev.Get(4 * px);
+    dev.Check(pm_upload(h, q, sources[k].data(), 4 * px), "pm_upload");
+    d_sources.push_back(static_cast<const float*>(q));
+    for (size_t i = 0; i < 9; ++i) m[k].R[i] = motions[k].R[i];
+    for (size_t i = 0; i < 3; ++i) m[k].t[i] = motions[k].t[i];
+  }
+  uint16_t* d_classes = classes ? static_cast<uint16_t*>(dev.Get(2 * px)) : nullptr;
+  float* d_residual = residual ? static_cast<float*>(dev.Get(4 * px)) : nullptr;
+  const pm_cloud_camera cam = CloudCamera(model);
+  const pm_consistency_options opt = {options.max_diff, options.radius, options.min_consistent, options.max_conflicts};
+  int counts[2] = {-1, -1};
+  dev.Check(pm_filter_consistency(h, &cam, &opt, d_disp, (int)sources.size(), d_sources.data(), m.data(), disp.rows, disp.cols,
+                                  out ? d_disp : nullptr /* in place on the device */, d_classes, d_residual, nullptr, counts),
+            "pm_filter_consistency");
+  auto fetch = [&](auto* image, const void* d_src, size_t bytes) {
+    if (image->rows != disp.rows || image->cols != disp.cols) image->create(disp.rows, disp.cols);
+    dev.Check(pm_download(h, image->data(), d_src, bytes), "pm_download");
+  };
+  if (out) fetch(out, d_disp, 4 * px);
+  if (classes) fetch(classes, d_classes, 2 * px);
+  if (residual) fetch(residual, d_residual, 4 * px);
+  return {{counts[0], counts[1]}};
+}
+
 core::Image<core::Vec3f> DisparityNormals(const core::Image<float>& disp, const StereoModel& model, const NormalsFit& fit,
                                           core::Image<uint8_t>* support) {
   if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("DisparityNormals: empty map");

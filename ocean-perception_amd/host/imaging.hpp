@@ -179,5 +179,26 @@ std::array<int, 2> ReprojectDisparity(pm::PatchmatchGpu& matcher, const StereoMo
                                       const float* d_disp, int rows, int cols, float* d_seed_l, float* d_seed_r,
                                       const ReprojectOptions& options = ReprojectOptions(), bool want_counts = true);
 
+// Along a sequence: the CURRENT left map judged by earlier left maps of the same size and camera, each reached through the
+// motion X_src = R X_cur + t between the left camera frames -- RelativeMotion(T_world_cur, T_world_src) (pm/imaging.h:
+// pm_filter_consistency; definition: tests/consistency_ref.py).  A pixel > 0 is kept iff at least min_consistent sources saw
+// the same surface (within max_diff, nearest of a (2 radius + 1)^2 window) and at most max_conflicts saw through it.
+struct ConsistencyOptions {  // pm_consistency_options
+  float max_diff = 1.f;    // finite, >= 0
+  int radius = 1;          // 0..2
+  int min_consistent = 1;  // 0..sources.size()
+  int max_conflicts = 0;   // 0..8
+};
+// Host images in, host images out, on the matcher's own handle and stream (pm_device_malloc / pm_upload / pm_download):
+// out: disp with every pixel > 0 that is not kept set to 0; classes: the class of source k (0 unseen, 1 consistent,
+// 2 occluded, 3 conflict) in bits 2k, 2k + 1; residual: the mean |difference| over the consistent sources; each where it
+// is asked for.  Returns {pixels > 0, kept pixels}.  The matcher must have planned its handle.  Throws
+// std::invalid_argument where the sizes differ and std::runtime_error where pm_filter_consistency refuses.
+std::array<int, 2> FilterConsistency(pm::PatchmatchGpu& matcher, const StereoModel& model,
+                                     const std::vector<core::Image<float>>& sources, const std::vector<Motion>& motions,
+                                     const ConsistencyOptions& options, const core::Image<float>& disp,
+                                     core::Image<float>* out, core::Image<uint16_t>* classes = nullptr,
+                                     core::Image<float>* residual = nullptr);
+
 }  // namespace imaging
 }  // namespace bm

@@ -48,6 +48,7 @@ EXPORTS = [
     "pm_filter_speckles", "pm_debug_speckle_constants",
     "pm_grid_mesh", "pm_debug_mesh_constants",
     "pm_reproject_disparity", "pm_debug_reproject_constants",
+    "pm_filter_consistency",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
     "pm_debug_sweep_plan", "pm_debug_noise_cost_constants", "pm_debug_noise_cost", "pm_debug_remove_background",
     "pm_remove_background", "pm_mask_occlusions", "pm_foreground_texture_mask", "pm_sparse_init", "pm_corner_subpix", "pm_profile_enable", "pm_profile_read",
@@ -212,6 +213,14 @@ def as_motion(values):
     m.R[:] = [float(v) for v in np.asarray(R, np.float64).ravel()]
     m.t[:] = [float(v) for v in np.asarray(t, np.float64).ravel()]
     return m
+
+
+PM_CONSISTENCY_MAX_SOURCES = 8
+PM_CONSISTENCY_UNSEEN, PM_CONSISTENCY_CONSISTENT, PM_CONSISTENCY_OCCLUDED, PM_CONSISTENCY_CONFLICT = 0, 1, 2, 3
+
+
+class PmConsistencyOptions(C.Structure):  # pm_filter_consistency
+    _fields_ = [("max_diff", C.c_float), ("radius", C.c_int), ("min_consistent", C.c_int), ("max_conflicts", C.c_int)]
 
 
 def reproject_constants():
@@ -400,6 +409,10 @@ def load():
     lib.pm_reproject_disparity.restype = C.c_int
     lib.pm_debug_reproject_constants.argtypes = [C.POINTER(C.c_int)] * 2
     lib.pm_debug_reproject_constants.restype = None
+    lib.pm_filter_consistency.argtypes = [vp, C.POINTER(PmCloudCamera), C.POINTER(PmConsistencyOptions), vp, C.c_int,
+                                          C.POINTER(vp), C.POINTER(PmMotion), C.c_int, C.c_int, vp, vp, vp, vp,
+                                          C.POINTER(C.c_int)]
+    lib.pm_filter_consistency.restype = C.c_int
     lib.pm_device_malloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     lib.pm_device_free.argtypes = [vp, vp]
     lib.pm_upload.argtypes = [vp, vp, vp, C.c_size_t]
@@ -942,6 +955,22 @@ class Engine:
         self._check(self.lib.pm_reproject_disparity(self.h, _ref(c), _ref(m), C.byref(o), d_disp, rows, cols,
                                                     d_seed_l, d_seed_r, d_counts, n if want_counts else None),
                     "pm_reproject_disparity")
+        return (n[0], n[1]) if want_counts else None
+
+    def filter_consistency(self, camera, d_disp, d_sources, motions, rows, cols, max_diff=1.0, radius=1, min_consistent=1,
+                           max_conflicts=0, d_out=None, d_classes=None, d_residual=None, d_counts=None, want_counts=False):
+        """pm_filter_consistency (raw device addresses): the current left map judged by the earlier maps d_sources (a
+        sequence of device addresses) under motions (a sequence of (R, t) or PmMotion, X_src = R X_cur + t), on the handle's
+        stream.  d_out [rows][cols] float32 (may be d_disp), d_classes uint16, d_residual float32, d_counts two device ints,
+        each where given.  -> (valid pixels, kept pixels) with want_counts (the call then synchronises), else None."""
+        c = cloud_camera(camera)
+        o = PmConsistencyOptions(max_diff, radius, min_consistent, max_conflicts)
+        src = (C.c_void_p * len(d_sources))(*d_sources)
+        mot = (PmMotion * len(motions))(*[as_motion(m) for m in motions])
+        n = (C.c_int * 2)(-1, -1)
+        self._check(self.lib.pm_filter_consistency(self.h, _ref(c), C.byref(o), d_disp, len(d_sources), src, mot, rows, cols,
+                                                   d_out, d_classes, d_residual, d_counts, n if want_counts else None),
+                    "pm_filter_consistency")
         return (n[0], n[1]) if want_counts else None
 
     def normalize(self, d_bgr, rows, cols, d_out):
