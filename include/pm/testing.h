@@ -54,6 +54,34 @@ int pm_debug_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, 
 int pm_debug_sweep_plan(const pm_params* params, int rows, int cols, int patch_h, int patch_w, int pass, int slots,
                         float amp, pm_debug_sweep_variant* out);
 
+/* ---- where the run engine cuts a chain into segments (csrc/pm_seg_bounds.hpp) ------------------------------------------
+ * k_runblk3 (PM_SEM_CPU) cuts every chain into (64 / group) * waves segments that run in parallel.  The boundaries are the
+ * equal split, or balanced by a prediction of where the chain's runs will stop; they change the work, never the result.
+ * pm_debug_segment_bounds: the rule itself, csrc/pm_seg_bounds.hpp::segment_bounds with the kernel's minimum segment length
+ * (8 positions): flags = null or n bytes (non-zero = predicted stop), nd = positions per run step; bounds receives
+ * nseg + 1 values.  No handle, no device.  PM_ERR_INVALID_ARG: null bounds, n, nseg or nd below 1.
+ * pm_debug_propagate_hinted: pm_debug_propagate with a hint source per pass, hint_modes[4] indexed like `ran`:
+ *   0 = none (the equal split; what pm_propagate and pm_debug_propagate launch),
+ *   1 = the run boundaries of the map the pass starts from,
+ *   2 = the stop-bit plane (row +1 only; any other pass takes it for 0).
+ * stops: null, or rows x cols bytes, in and out: copied into view 0's stop-bit plane before the first pass and read back
+ * after the last one; every row +1 pass of this call writes the plane (1 where it left a pixel with another value than its
+ * left neighbour, interior pixels only).  bounds: null, or room for 65 values: receives the boundaries chain `bounds_chain`
+ * (the image row of a row pass, the image column of a column pass) of pass `bounds_pass` used, *n_bounds of them
+ * (segments + 1; 0 where that pass did not run on the run engine).  PM_SEM_GPU handles ignore the hints.
+ * pm_debug_match_sweep_hint: the hint Match() gives sweep `pass` of iteration `it` for images of rows x cols, from the host
+ * function it launches from (csrc/pm_sweep_plan.hpp::match_sweep_hint): *mode as above, *write_stops = 1 where the sweep
+ * stores its stop bits for the next iteration.  No handle, no device.  A hint is given only to chains of at least 400
+ * positions, to the row +1 pass, from iteration 1 on and where the window is the previous iteration's.
+ * pm_debug_read_stops: view 0 / 1's stop-bit plane of pair 0 as the last call left it, rows x cols bytes (view 1 in its
+ * own, mirrored, coordinates). */
+int pm_debug_match_sweep_hint(const pm_params* params, int rows, int cols, int it, int pass, int* mode, int* write_stops);
+int pm_debug_read_stops(pm_handle* h, int view, int rows, int cols, uint8_t* stops);
+int pm_debug_segment_bounds(const uint8_t* flags, int n, int nseg, int nd, int* bounds);
+int pm_debug_propagate_hinted(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
+                              int patch_h, int patch_w, int pass_mask, float amp, const int* hint_modes, uint8_t* stops,
+                              int bounds_pass, int bounds_chain, int* bounds, int* n_bounds, pm_debug_sweep_variant* ran);
+
 /* ---- the noise + clamp + cost stage of a scalar-mode iteration, on its own and with its cost plane -----------------------
  * (k_noise_cost / k_noise_cost_tiled<W, W> of csrc/pm_kernels.hpp, chosen by launch_noise_cost.)
  * pm_debug_noise_cost_constants: the pixels one workgroup of the tiled kernel owns (tile_cols x tile_rows) and the target

@@ -63,6 +63,10 @@ struct PlaneSet {
   // stretch (round 4: DESIGN.md 6, "what a launch costs besides its steps").  Every access goes through state_at() / chain_at().
   float* disp;         // [B][2][rows4][pitch][4]   view 0 = left, view 1 = right (mirrored coordinates)
   float* cost;         // [B][2][rows4][pitch][4]   cost of disp under the current window
+  // STOP-BIT plane of the row +1 sweeps (pm_run3.hpp, pm_seg_bounds.hpp): 1 where the sweep left a pixel with another
+  // value than its left neighbour.  Written by the sweep of one iteration, read by the same sweep of the next as a
+  // prediction of where its runs end; row-major, so a row chain reads and writes it coalesced.  nullptr: none (no hint).
+  uint8_t* stops;      // [B][2][rows][pitch]
   const float* noise;  // [rows][pitch]         cv::RNG(seed) uniform [-1,1), shared by all slots
   unsigned long long* counters;  // [8] work counters (see pm_debug_counters), one atomic per wavefront
   // Row-tiled mode: chains a sweep launch works on, [n_views][cols] (chain index = plane column), nullptr = all.
@@ -116,6 +120,7 @@ struct View {
   const float* cpg;
   float* disp;
   float* cost;
+  uint8_t* stops;  // this view's stop-bit plane (PlaneSet::stops), or nullptr
 };
 
 // view index of a launch slot (the same rule make_view applies)
@@ -153,6 +158,7 @@ __device__ __forceinline__ View make_view(const PlaneSet& ps, int slot) {
   const size_t dofs = ((size_t)b * 2 + v) * ps.splane;
   w.disp = ps.disp + dofs;
   w.cost = ps.cost + dofs;
+  w.stops = ps.stops ? ps.stops + pv * ps.plane : nullptr;
   return w;
 }
 

@@ -162,6 +162,7 @@ PlaneSet plane_set(const pm_handle* h, int rows, int cols, int n_views) {
   ps.ncl = cols + kTransPad + 2;
   ps.disp = h->disp;
   ps.cost = h->cost;
+  ps.stops = h->stops;
   ps.noise = h->noise;
   ps.counters = h->counters_on ? h->counters : nullptr;
   ps.chain_mask = nullptr;
@@ -368,7 +369,12 @@ int view_op(pm_handle* h, const PlaneSet& ps, int idx, int slots, hipStream_t st
   if (it < p.patchmatch_iters) {
     const CostParams cp = cost_params(p, p.patch_w[it], p.patch_h[it]);
     const Interior in = interior(p, ps.rows, ps.cols, cp.pw, cp.ph);
-    if (k > 0) return run_sweep(h, ps, cp, sweep_geom(p, in, k - 1), slots, p.noise_amp[it], stream);
+    if (k > 0) {
+      // segment boundaries balanced by predicted stops where that pays (pm_sweep_plan.hpp::match_sweep_hint)
+      const SweepGeom g = sweep_geom(p, in, k - 1);
+      const SweepHint hint = match_sweep_hint(p, it, k - 1, (g.s_last - g.s_first) * g.dir + 1);
+      return run_sweep(h, ps, cp, g, slots, p.noise_amp[it], stream, nullptr, hint);
+    }
     {
       Launch l(h, PM_K_NOISE, stream);
       // from the second iteration on the cost plane is valid for this window if the window is unchanged
@@ -606,6 +612,7 @@ PlaneSet plane_set_of_pair(const PlaneSet& ps, int b) {
   if (q.cpg) q.cpg += b2 * (size_t)ps.ncl * ps.pitch_t * 4;
   q.disp += b2 * ps.splane;
   q.cost += b2 * ps.splane;
+  if (q.stops) q.stops += b2 * ps.plane;
   return q;
 }
 
@@ -1086,6 +1093,8 @@ int pm_create(const pm_params* params, int device, int max_rows, int max_cols, i
   // never see uninitialised memory
   PM_HIP(h, h->disp.alloc_zeroed(sizeof(float) * (B * 2 * splane + kSlackElems), h->stream));
   PM_HIP(h, h->cost.alloc_zeroed(sizeof(float) * (B * 2 * splane + kSlackElems), h->stream));
+  // the row +1 sweeps' stop bits (pm_device.hpp): read only where the previous iteration of the same call wrote them
+  if (params->semantics == PM_SEM_CPU) PM_HIP(h, h->stops.alloc_zeroed(B * 2 * plane, h->stream));
   PM_HIP(h, h->noise.alloc(sizeof(float) * (plane + kSlackElems)));
   PM_HIP(h, h->counters.alloc_zeroed(sizeof(unsigned long long) * 16, h->stream));  // [8..13]: timing builds only
   if (int rc = alloc_seed_scratch(h, h->seeds[0], h->stream)) return rc;

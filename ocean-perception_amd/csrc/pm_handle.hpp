@@ -77,6 +77,7 @@ struct pm_handle {
   pm::DevBuf<float> cpg;
   pm::DevBuf<float> disp;
   pm::DevBuf<float> cost;
+  pm::DevBuf<uint8_t> stops;  // stop bits of the row +1 sweeps (pm::PlaneSet::stops); PM_SEM_CPU handles only
   pm::DevBuf<float> noise;    // grows with the largest table asked for (pm_engine.hip::ensure_noise)
   pm::DevBuf<unsigned long long> counters;  // device, 8 words
   bool counters_on = false;                // same-address atomics serialise: opt-in only
@@ -350,8 +351,9 @@ void launch_background(pm_handle* h, const PlaneSet& ps, const CostParams& cp, c
                        int cached, int slots, hipStream_t stream);
 // amp: the iteration's noise amplitude (1e30f: none); ran (may be null): the variant launched (pm_sweep_plan.hpp), left
 // as it is where the geometry has nothing to sweep
+// hint: the segment boundaries of the run engine (pm_sweep_defs.hpp); the default is the equal split
 int run_sweep(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, float amp,
-              hipStream_t stream, SweepVariant* ran = nullptr);
+              hipStream_t stream, SweepVariant* ran = nullptr, const SweepHint& hint = SweepHint());
 void launch_finalize(pm_handle* h, const PlaneSet& ps, float* d_disp_l, float* d_disp_r, int n, hipStream_t stream);
 void launch_mask_occlusions(pm_handle* h, float* d_disp_l, const float* d_disp_r, int rows, int cols,
                             hipStream_t stream);

@@ -776,7 +776,8 @@ namespace {
 // pm_propagate and pm_debug_propagate: `who` names the entry point in error messages, ran (may be null) receives the
 // variant each pass launched, indexed by the pass
 int propagate_impl(pm_handle* h, const char* who, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
-                   int patch_h, int patch_w, int pass_mask, float amp, pm::SweepVariant* ran) {
+                   int patch_h, int patch_w, int pass_mask, float amp, pm::SweepVariant* ran,
+                   const pm::SweepHint* hints = nullptr, uint8_t* stops = nullptr) {
   if (int rc = refuse_while_capturing(h, who)) return rc;
   if (!left || !right || !disp) {
     set_err(h, "%s: null pointer", who);
@@ -799,10 +800,20 @@ int propagate_impl(pm_handle* h, const char* who, const uint8_t* left, const uin
   const Interior in = interior(h->params, rows, cols, cp.pw, cp.ph);
   launch_noise_cost(h, ps, cp, in, -1.f, 1, 0, h->stream);
   if (int rc = launch_check(h, "cost")) return rc;
+  // hints (pm_debug_propagate_hinted): per pass, with the caller's stop-bit plane in view 0's and that plane handed back
+  if (stops && ps.stops)
+    PM_HIP(h, hipMemcpy2DAsync(ps.stops, (size_t)ps.pitch, stops, (size_t)cols, (size_t)cols, (size_t)rows,
+                               hipMemcpyHostToDevice, h->stream));
   for (int k = 0; k < 4; ++k)
     if (pass_mask & (1 << k))
-      if (int rc = run_sweep(h, ps, cp, sweep_geom(h->params, in, k), 1, amp, h->stream, ran ? ran + k : nullptr))
+      if (int rc = run_sweep(h, ps, cp, sweep_geom(h->params, in, k), 1, amp, h->stream, ran ? ran + k : nullptr,
+                             hints ? hints[k] : pm::SweepHint()))
         return rc;
+  if (stops && ps.stops) {
+    PM_HIP(h, hipMemcpy2DAsync(stops, (size_t)cols, ps.stops, (size_t)ps.pitch, (size_t)cols, (size_t)rows,
+                               hipMemcpyDeviceToHost, h->stream));
+    PM_HIP(h, hipStreamSynchronize(h->stream));
+  }
   return stage_out(h, ps, disp, 0);
 }
 }  // namespace
@@ -834,6 +845,91 @@ int pm_debug_propagate(pm_handle* h, const uint8_t* left, const uint8_t* right, 
   if (ran)
     for (int k = 0; k < 4; ++k) ran[k] = debug_record(v[k]);
   return rc;
+}
+
+// pm_debug_propagate with a segment-boundary hint per pass (include/pm/testing.h)
+int pm_debug_propagate_hinted(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
+                              int patch_h, int patch_w, int pass_mask, float amp, const int* hint_modes, uint8_t* stops,
+                              int bounds_pass, int bounds_chain, int* bounds, int* n_bounds, pm_debug_sweep_variant* ran) {
+  if (ran) memset(ran, 0, 4 * sizeof(*ran));
+  if (n_bounds) *n_bounds = 0;
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (!(amp >= 0.f) || !hint_modes || (bounds && (bounds_pass < 0 || bounds_pass > 3 || !n_bounds))) {
+    set_err(h, "pm_debug_propagate_hinted: negative or NaN noise amplitude, no hint modes, or a boundary pass outside 0 .. 3");
+    return PM_ERR_INVALID_ARG;
+  }
+  for (int k = 0; k < 4; ++k)
+    if (hint_modes[k] < pm::kSegHintNone || hint_modes[k] > pm::kSegHintPlane) {
+      set_err(h, "pm_debug_propagate_hinted: unknown hint mode");
+      return PM_ERR_INVALID_ARG;
+    }
+  PM_HIP(h, hipSetDevice(h->device));
+  constexpr int kWords = 2 * pm::kSegHintMaxSeg + 1;  // every segment count a launch can have (64 / 16 * kMaxSegWaves)
+  pm::DevBuf<int> d_bounds;
+  if (bounds) {
+    PM_HIP(h, d_bounds.alloc(sizeof(int) * kWords));
+    PM_HIP(h, hipMemsetAsync(d_bounds.get(), 0xff, sizeof(int) * kWords, h->stream));
+  }
+  pm::SweepHint hints[4];
+  for (int k = 0; k < 4; ++k) {
+    hints[k].mode = hint_modes[k];
+    hints[k].write_stops = k == 0 ? 1 : 0;
+    if (bounds && k == bounds_pass) {
+      hints[k].dbg_bounds = d_bounds.get();
+      hints[k].dbg_chain = bounds_chain;
+    }
+  }
+  pm::SweepVariant v[4];
+  const int rc = propagate_impl(h, "pm_debug_propagate_hinted", left, right, rows, cols, disp, patch_h, patch_w, pass_mask,
+                                amp, v, hints, stops);
+  if (ran)
+    for (int k = 0; k < 4; ++k) ran[k] = debug_record(v[k]);
+  if (rc == PM_OK && bounds && v[bounds_pass].group > 0 && v[bounds_pass].engine == PM_ENGINE_RUNBLK2 &&
+      h->params.semantics == PM_SEM_CPU) {
+    const int nseg = (pm::kWave / v[bounds_pass].group) * v[bounds_pass].waves;
+    if (nseg + 1 <= kWords) {
+      PM_HIP(h, hipMemcpy(bounds, d_bounds.get(), sizeof(int) * (nseg + 1), hipMemcpyDeviceToHost));
+      *n_bounds = nseg + 1;
+    }
+  }
+  return rc;
+}
+
+// pm_seg_bounds.hpp::segment_bounds as k_runblk3 calls it (include/pm/testing.h): no handle, no device
+int pm_debug_segment_bounds(const uint8_t* flags, int n, int nseg, int nd, int* bounds) {
+  if (!bounds || n < 1 || nseg < 1 || nd < 1) return PM_ERR_INVALID_ARG;
+  pm::segment_bounds(flags, n, nseg, nd, pm::kMinSegLen, bounds);
+  return PM_OK;
+}
+
+// the hint Match() gives sweep `pass` of iteration `it` (include/pm/testing.h): no handle, no device
+int pm_debug_match_sweep_hint(const pm_params* params, int rows, int cols, int it, int pass, int* mode, int* write_stops) {
+  if (!params || !mode || !write_stops || pass < 0 || pass > 3 || it < 0 || it >= params->patchmatch_iters ||
+      it >= PM_MAX_ITERS)
+    return PM_ERR_INVALID_ARG;
+  const CostParams cp = cost_params(*params, params->patch_w[it], params->patch_h[it]);
+  const SweepGeom g = sweep_geom(*params, interior(*params, rows, cols, cp.pw, cp.ph), pass);
+  const pm::SweepHint hint = pm::match_sweep_hint(*params, it, pass, (g.s_last - g.s_first) * g.dir + 1);
+  *mode = hint.mode;
+  *write_stops = hint.write_stops;
+  return PM_OK;
+}
+
+// view `view`'s stop-bit plane of pair 0 as the last call left it (include/pm/testing.h)
+int pm_debug_read_stops(pm_handle* h, int view, int rows, int cols, uint8_t* stops) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (int rc = refuse_while_capturing(h, "pm_debug_read_stops")) return rc;
+  if (!stops || view < 0 || view > 1 || !h->stops) {
+    set_err(h, "pm_debug_read_stops: null pointer, a view outside 0 .. 1, or a handle without a stop-bit plane");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_size(h, rows, cols, 1)) return rc;
+  PM_HIP(h, hipSetDevice(h->device));
+  if (int rc = pm_synchronize(h)) return rc;
+  const PlaneSet ps = plane_set(h, rows, cols, 2);
+  PM_HIP(h, hipMemcpy2D(stops, (size_t)cols, ps.stops + (size_t)view * ps.plane, (size_t)ps.pitch, (size_t)cols, (size_t)rows,
+                        hipMemcpyDeviceToHost));
+  return PM_OK;
 }
 
 // what pm_debug_propagate's pass would launch, from the plan alone: no handle, no device

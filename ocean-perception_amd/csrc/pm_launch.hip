@@ -75,11 +75,11 @@ void launch_seed(pm_handle* h, const PlaneSet& ps, const float* d_seed_l, const 
 }
 
 int run_sweep(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, float amp,
-              hipStream_t stream, SweepVariant* ran) {
+              hipStream_t stream, SweepVariant* ran, const SweepHint& hint) {
   const int chains = g.c_hi - g.c_lo + 1;
   if (chains <= 0 || (g.s_last - g.s_first) * g.dir < 0) return PM_OK;
   Launch l(h, g.axis == 0 ? PM_K_SWEEP_ROW : PM_K_SWEEP_COL, stream);
-  const SweepVariant v = launch_sweep(ps, cp, g, slots, h->params.engine, amp, stream);  // pm_sweeps.hip
+  const SweepVariant v = launch_sweep(ps, cp, g, slots, h->params.engine, amp, stream, hint);  // pm_sweeps.hip
   if (ran) *ran = v;
   return launch_check(h, "sweep");
 }

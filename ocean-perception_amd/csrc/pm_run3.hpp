@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "pm_run2.hpp"
+#include "pm_seg_bounds.hpp"
 
 namespace pm {
 
@@ -499,10 +500,97 @@ __device__ __forceinline__ void run3_step(const View& v, const PlaneSet& ps, con
   }
 }
 
+// The kernel's side of pm_seg_bounds.hpp::segment_bounds, for a chain seg_hint_applies() to.  ONE wavefront computes the
+// boundaries and leaves them in LDS (s_bound[0 .. nseg]); the workgroup meets at a barrier behind it.  (Every wavefront
+// computing them for itself needs no barrier but was measured at 4-6 us per chain on a full chip: the chip is bound by
+// vector issue, and four copies of ~800 instructions are five run steps' worth per chain.)
+// Stop flags by blocks of 64 LDS indices of st4 (bit i of block b: index 64 b + i = chain position 64 b + i - 1; index 0 and
+// indices beyond n: 0): lane b keeps block b's mask.  Block weights and running sums are wave-uniform (scalar registers);
+// lane s finds boundary s: the block its target falls into from the running sums, the crossing inside the block by a
+// binary search over popcounts of the block's mask; the minimum length is applied in segment order on the scalar unit.
+// mode: kSegHintRuns (flags from st4) or kSegHintPlane (stopmask: the blocks' masks, staged with the chain state).
+__device__ __forceinline__ void run3_bounds(const float4* st4, const unsigned long long* stopmask, int mode, int n, int nseg,
+                                            int stop_w, int seg_len, int lane, int* s_bound) {
+  const int nblk = (n + 64) >> 6;
+  unsigned m_lo = 0u, m_hi = 0u;
+  int tot = 0;  // flags set
+  if (mode == kSegHintRuns) {
+    float carry = 0.f;  // the value in front of the block: the previous block's last
+    for (int b = 0; b < nblk; ++b) {
+      const int j = 64 * b + lane;
+      const float cur = st4[min(j, n)].x;
+      const float left = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, cur), 0x138, 0xF, 0xF, true));
+      const float prev = lane == 0 ? carry : left;  // wave_shr:1: lane i reads lane i - 1
+      carry = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cur), 63));
+      const unsigned long long m = mask_of(j >= 1 && j <= n && cur != prev);
+      tot += __builtin_popcountll(m);
+      if (lane == b) {
+        m_lo = (unsigned)m;
+        m_hi = (unsigned)(m >> 32);
+      }
+    }
+  } else {
+    if (lane < nblk) {
+      const unsigned long long m = stopmask[lane];
+      m_lo = (unsigned)m;
+      m_hi = (unsigned)(m >> 32);
+    }
+    for (int b = 0; b < nblk; ++b)
+      tot += __builtin_popcount((unsigned)__builtin_amdgcn_readlane((int)m_lo, b)) +
+             __builtin_popcount((unsigned)__builtin_amdgcn_readlane((int)m_hi, b));
+  }
+  if (tot == 0) {  // nothing predicted: the equal split, as the header function says
+    if (lane <= nseg) s_bound[lane] = lane == nseg ? n : min(n, lane * seg_len);
+    return;
+  }
+  const int W = n + (stop_w - 1) * tot;
+  const int blo = max(64 * lane, 1), bhi = min(64 * lane + 63, n);
+  const int wb = max(bhi - blo + 1, 0) + (stop_w - 1) * (__builtin_popcount(m_lo) + __builtin_popcount(m_hi));
+  // lane s: ceil(s W / nseg); the segment counts plan_sweep gives are powers of two (uniform branch)
+  const int num = lane * W + nseg - 1;
+  const int quo = (nseg & (nseg - 1)) == 0 ? num >> __builtin_ctz(nseg) : num / nseg;
+  const int T = (lane >= 1 && lane < nseg) ? quo : W;
+  // the block the target falls into = the blocks that end below it; e_b = the weight in front of that block
+  int run = 0, e_b = 0, blk = 0;
+  for (int b = 0; b < nblk; ++b) {
+    run += __builtin_amdgcn_readlane(wb, b);
+    const bool below = run < T;
+    blk += below ? 1 : 0;
+    e_b = below ? run : e_b;
+  }
+  const unsigned long long m_b = (unsigned long long)(unsigned)__builtin_amdgcn_ds_bpermute(blk << 2, (int)m_lo) |
+                                 ((unsigned long long)(unsigned)__builtin_amdgcn_ds_bpermute(blk << 2, (int)m_hi) << 32);
+  // the first index 64 blk + kk of the block at which the weight up to and including it reaches T
+  const int z = blk == 0 ? 1 : 0;  // (index 0 is the pixel before the chain: no position, no weight)
+  int kk = 0;
+#pragma unroll
+  for (int step = 32; step; step >>= 1) {
+    const int t = kk + step - 1;
+    const int P = e_b + (t + 1 - z) + (stop_w - 1) * __builtin_popcountll(m_b & (~0ull >> (63 - t)));
+    if (P < T) kk += step;
+  }
+  const int raw = 64 * blk + kk;  // positions in front of boundary `lane`
+  // the minimum length from both ends, in segment order
+  int mine = lane == 0 ? 0 : n, cur = 0;
+  for (int s = 1; s < nseg; ++s) {
+    cur = max(__builtin_amdgcn_readlane(raw, s), cur + kMinSegLen);
+    cur = min(cur, n - (nseg - s) * kMinSegLen);
+    if (lane == s) mine = cur;
+  }
+  if (lane <= nseg) s_bound[lane] = mine;
+}
+
 // One workgroup per chain; a wavefront carries 64 / GS segments.  grid = (chains, 1, slots), block = 64 * nw,
 // dynamic LDS = run3_lds_bytes() (pm_sweep_plan.hpp).
+// hint: bits 0-1 = SegHint, where the segment boundaries come from (pm_seg_bounds.hpp; kSegHintPlane: row +1 sweeps only,
+// the others take it for kSegHintNone); bit 2 (kRun3WriteStops, row +1 sweeps): the write-back stores every position's stop
+// bit into PlaneSet::stops for the same sweep of the next iteration; bits 8-21: 0, or what a predicted stop weighs instead
+// of the step's positions (tuning).  dbg_bounds: null, or [nseg + 1] words that receive the
+// boundaries chain dbg_chain of slot 0 used (pm_debug_propagate_hinted).
+constexpr int kRun3WriteStops = 4;
 template <int GS, int AXIS, int TP, int DIR, bool LREF>
-__global__ void __launch_bounds__(64 * kMaxSegWaves) k_runblk3(PlaneSet ps, CostParams cp, SweepGeom g, int seg_len
+__global__ void __launch_bounds__(64 * kMaxSegWaves) k_runblk3(PlaneSet ps, CostParams cp, SweepGeom g, int seg_len,
+                                                               int hint, int* dbg_bounds, int dbg_chain
 #ifdef PM_RUN3_STATS
                                                                , unsigned* chain_log  // [workgroup][8], this launch's
 #endif
@@ -612,35 +700,78 @@ __global__ void __launch_bounds__(64 * kMaxSegWaves) k_runblk3(PlaneSet ps, Cost
   k.dmposf = (float)(DIR * k.mpos);
   k.rofs = DIR > 0 ? k.gl : pw - k.gl;
   const int sidx = kPerWave * w + lane / GS;
+  // row +1 sweeps: the stop bits of the chain's row, 64 positions per LDS word pair (run3_bounds' blocks); static, so that
+  // only these instantiations pay for it
+  constexpr bool kStopPlane = AXIS == 0 && DIR > 0;
+  __shared__ unsigned long long s_stopmask[kStopPlane ? kRun3StaticLds / sizeof(unsigned long long) : 1];  // (pm_sweep_plan.hpp)
+  const int hint_mode = (kStopPlane || (hint & 3) != kSegHintPlane) ? (hint & 3) : kSegHintNone;
+  const bool hinted = hint_mode != kSegHintNone && seg_hint_applies(n, nseg, kMinSegLen);  // uniform
 
   {
     // the chain's state into LDS, four positions per thread in flight (the latency of one load, not of four in a row;
     // four consecutive positions of a column chain share a 16-byte piece of the state planes, pm_device.hpp::state_at)
     constexpr int U = 4;
     const int bd = blockDim.x;
+    const bool load_stops = kStopPlane && hinted && hint_mode == kSegHintPlane;  // uniform
     for (int j0 = threadIdx.x; j0 <= n; j0 += U * bd) {
       float dd[U], cc[U];
+      unsigned char sb[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int j = j0 + u * bd;
         dd[u] = cc[u] = 0.f;
+        sb[u] = 0;
         if (j <= n) {
           const size_t o = chain_at(AXIS, chain, g.s_first + DIR * (j - 1), ps.pitch);
           dd[u] = v.disp[o];
           if (j > 0) cc[u] = v.cost[o];
+          if constexpr (kStopPlane)
+            if (load_stops && j > 0) sb[u] = v.stops[(size_t)chain * ps.pitch + (g.s_first + (j - 1))];
         }
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int j = j0 + u * bd;
         if (j <= n) st4[j] = make_float4(dd[u], cc[u], dd[u], cc[u]);
+        if constexpr (kStopPlane)
+          if (load_stops) {
+            // a wavefront's lanes hold 64 consecutive indices from a multiple of 64 on: one block of run3_bounds
+            const unsigned long long m = mask_of(sb[u] != 0);
+            if (lane == 0 && j <= n) s_stopmask[j >> 6] = m;
+          }
       }
     }
   }
   __syncthreads();
 
-  const int i0 = sidx * seg_len;
-  const int i1 = min(n, i0 + seg_len);
+  // ---- the segment of this lane's group: equal split, or boundaries balanced by predicted stops (pm_seg_bounds.hpp) ----
+#ifdef PM_RUN3_STATS
+  const long long t_pre0 = clock64();
+#endif
+  int i0 = sidx * seg_len;
+  int i1 = min(n, i0 + seg_len);
+#ifndef PM_RUN3_NO_SEG_HINT  // (A/B switch of tools/build_variant.sh)
+  if (hinted) {  // uniform for the workgroup
+    // the boundaries pass through the words of s_last, which nobody touches before round 1 has ended (a barrier below
+    // keeps the first of those writes behind the last of these reads)
+    int* s_bound = (int*)s_last;
+    if (w == 0) {
+      // (PM_SEG_STOP_W: the tuning build's override, at most kRun3MaxStopWeight: the sums below are 32-bit)
+      const int stop_w = (hint >> 8) != 0 ? (hint >> 8) & 0x3fff : nd;
+      run3_bounds(st4, kStopPlane ? s_stopmask : nullptr, hint_mode, n, nseg, stop_w, seg_len, lane, s_bound);
+    }
+    __syncthreads();
+    i0 = s_bound[sidx];
+    i1 = s_bound[sidx + 1];
+  }
+#endif
+#ifdef PM_RUN3_STATS
+  const long long t_pre1 = clock64();
+#endif
+  if (dbg_bounds && chain == dbg_chain && blockIdx.z == 0 && k.gl == 0) {
+    dbg_bounds[sidx] = min(i0, n);
+    if (sidx == nseg - 1) dbg_bounds[nseg] = i1;  // (the end the last segment runs to, not the n it should be)
+  }
   const bool active = i0 < n;
   k.lim = (active && k.mpos >= 0 && k.mpos < nd) ? i1 : (int)0x80000000;
 #ifdef PM_TUNING
@@ -676,6 +807,9 @@ __global__ void __launch_bounds__(64 * kMaxSegWaves) k_runblk3(PlaneSet ps, Cost
   const long long t_r1 = clock64();
 #endif
   float lastv = *cand_slot;
+#ifndef PM_RUN3_NO_SEG_HINT
+  if (hinted) __syncthreads();  // s_last held the segment boundaries: every wavefront has read its own by now
+#endif
   if (active && k.gl == 0) s_last[sidx + 1] = lastv;
   if (threadIdx.x == 0) s_last[0] = in_used;
 
@@ -775,6 +909,7 @@ __global__ void __launch_bounds__(64 * kMaxSegWaves) k_runblk3(PlaneSet ps, Cost
       atomicAdd(&ps.counters[12], (unsigned long long)(t_r1 - t_start));
       atomicAdd(&ps.counters[13], (unsigned long long)(t_end - t_r1));
       atomicAdd(&ps.counters[14], (unsigned long long)nseg);
+      atomicAdd(&ps.counters[15], (unsigned long long)(t_pre1 - t_pre0));  // the boundary pre-pass, wavefront 0's clocks
     }
   }
   if (chain_log && blockIdx.z == 0) {  // per chain: what its slowest wavefront did, and when (tools/chain_tail.py)
@@ -814,6 +949,7 @@ __global__ void __launch_bounds__(64 * kMaxSegWaves) k_runblk3(PlaneSet ps, Cost
     if (w == 0) atomicAdd(&ps.counters[base + 3], (unsigned long long)n);
   }
 
+  const bool write_stops = kStopPlane && (hint & kRun3WriteStops) != 0;  // uniform
   for (int j = threadIdx.x + 1; j <= n; j += blockDim.x) {
     const float4 t = st4[j];
     if (t.z != t.x) {
@@ -821,6 +957,8 @@ __global__ void __launch_bounds__(64 * kMaxSegWaves) k_runblk3(PlaneSet ps, Cost
       v.disp[o] = t.z;
       v.cost[o] = t.w;
     }
+    if constexpr (kStopPlane)
+      if (write_stops) v.stops[(size_t)chain * ps.pitch + (g.s_first + (j - 1))] = t.z != st4[j - 1].z ? 1 : 0;
   }
 }
 

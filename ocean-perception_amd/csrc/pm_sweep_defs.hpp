@@ -26,4 +26,14 @@ struct SweepGeom {
   int s_first, s_last;  // first and last visited position along the chain (inclusive)
 };
 
+// What a caller tells k_runblk3 about its segment boundaries (pm_seg_bounds.hpp).  The default is the equal split, which
+// is what every caller outside Match()'s iterations launches.  Other engines ignore it.
+struct SweepHint {
+  int mode = 0;             // SegHint: where the predicted stops come from
+  int write_stops = 0;      // 1: a row +1 sweep stores its stop bits into PlaneSet::stops for the next iteration
+  int stop_w = 0;           // 0: a predicted stop weighs the positions of a run step (the rule); else this many (tuning)
+  int* dbg_bounds = nullptr;  // device, [segments + 1]: the boundaries chain dbg_chain of slot 0 used (test hook)
+  int dbg_chain = -1;
+};
+
 }  // namespace pm

@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "pm/patchmatch.h"
+#include "pm_seg_bounds.hpp"
 #include "pm_sweep_defs.hpp"
 #include "pm_tune.hpp"
 
@@ -80,12 +81,69 @@ inline const SweepKnobs& sweep_knobs() {
   return k;
 }
 
+// Which hint source each sweep class of a Match() iteration gives k_runblk3 for its segment boundaries
+// (pm_seg_bounds.hpp), indexed by the pass: 0 = row +1, 1 = column +1, 2 = row -1, 3 = column -1.  Shipped: the row +1
+// sweep reads the stop bits its predecessor of the previous iteration wrote; every other class keeps the equal split.
+// Measured (profiles/segment_balance_ab.txt): with the run boundaries of the state they start from the
+// row -1 launches do not get shorter and the column -1 launches get longer, the pre-pass costing more than the balance
+// wins; the column +1 sweep loses already in the simulation (tools/segment_balance.py).
+// PM_SEG_HINT (tuning build): a bit per pass, 1 = that class takes its source (row +1: the plane, the others: run
+// boundaries).  -DPM_RUN3_NO_SEG_HINT compiles the pre-pass out of the kernel and all classes keep the equal split.
+
+// the largest stop weight the kernel's 32-bit sums hold: lane * W with lane < 32, W <= 4095 * weight
+constexpr int kRun3MaxStopWeight = 16383;
+static_assert((long long)(kSegHintMaxSeg - 1) * ((long long)kSegHintMaxLen * (kRun3MaxStopWeight + 1)) + kSegHintMaxSeg < 0x7fffffffLL,
+              "k_runblk3's boundary targets overflow");
+struct SegHintModes {
+  int pass[4];
+  int stop_w;  // PM_SEG_STOP_W: 0 = a predicted stop weighs the positions of a run step (the rule), else this many
+  SegHintModes() {
+    const int w = SweepKnobs::env_int("PM_SEG_STOP_W", 0);
+    stop_w = w < 0 ? 0 : (w > kRun3MaxStopWeight ? kRun3MaxStopWeight : w);
+#ifdef PM_RUN3_NO_SEG_HINT
+    const int bits = 0;
+#else
+    const int bits = SweepKnobs::env_int("PM_SEG_HINT", 1);
+#endif
+    const int source[4] = {kSegHintPlane, kSegHintRuns, kSegHintRuns, kSegHintRuns};
+    for (int k = 0; k < 4; ++k) pass[k] = ((bits >> k) & 1) ? source[k] : kSegHintNone;
+  }
+};
+inline const SegHintModes& seg_hint_modes() {
+  static const SegHintModes m;
+  return m;
+}
+
+// The hint of sweep `pass` of iteration `it` of a Match() (pm_engine.hip::view_op launches from it; pm_debug_match_sweep_hint
+// returns it without a device).  A class takes its source (seg_hint_modes) only where the chains are long enough to pay
+// for the pre-pass (seg_hint_pays).  The row +1 sweep reads the stop bits the same sweep of the previous iteration of the
+// same call wrote for the same interior, i.e. the same window -- iteration 0 and a window change take the equal split --
+// and writes them where the next iteration will read them.
+inline SweepHint match_sweep_hint(const pm_params& p, int it, int pass, int chain_len) {
+  SweepHint hint;
+  const int mode = seg_hint_modes().pass[pass];
+  if (mode == kSegHintNone || !seg_hint_pays(chain_len)) return hint;
+  hint.stop_w = seg_hint_modes().stop_w;
+  if (mode != kSegHintPlane) {
+    hint.mode = mode;
+    return hint;
+  }
+  const auto same_window = [&](int a, int b) { return p.patch_w[a] == p.patch_w[b] && p.patch_h[a] == p.patch_h[b]; };
+  hint.mode = (it > 0 && same_window(it - 1, it)) ? kSegHintPlane : kSegHintNone;
+  hint.write_stops = (it + 1 < p.patchmatch_iters && same_window(it + 1, it)) ? 1 : 0;
+  return hint;
+}
+
 // ---- dynamic LDS of the chain kernels, one formula each -------------------------------------------------------------
 // (chain_lds_bytes(n, 4 * kMaxSegWaves + 4, planes), the serial fallback's estimate in plan_sweep, is deliberately
 // conservative: it bounds all of them for any segment count.)
 // k_runblk3: one float4 per position and the pixel before the chain, [nseg + 1] last values, [nseg] candidates, 2 flags
 inline size_t run3_lds_bytes(int n, int nseg) { return sizeof(float) * (4 * (size_t)(n + 1) + 2 * (size_t)nseg + 3); }
 // ... plus its staged reference lines (LREF): kLref4Stride dwords per image row (column sweeps) / column (row sweeps)
+// ... and, outside this formula, kRun3StaticLds (pm_seg_bounds.hpp) bytes of STATIC LDS in the row +1 variants (the staged stop masks of
+// pm_run3.hpp: one 64-bit word per 64 positions of the longest hinted chain).  kChainLdsMax leaves 1 KB below the CU's
+// 160 KB for it; launch_planned counts it when it raises a kernel's LDS limit.
+static_assert(kChainLdsMax + kRun3StaticLds <= 160 * 1024, "k_runblk3's static LDS does not fit beside the longest chain");
 inline size_t run3_lref_bytes(int lines) { return sizeof(unsigned) * (size_t)kLref4Stride * lines; }
 // k_runblk2: five planes (the fifth: what a position does with its predecessor's old value), [nseg + 1] last values, 2 flags
 inline size_t run2_lds_bytes(int n, int nseg) { return chain_lds_bytes(n, nseg + 3, 5); }

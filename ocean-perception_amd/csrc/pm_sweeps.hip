@@ -34,7 +34,7 @@ constexpr int variant_key(int group, int axis, int window, int dir, bool lref) {
   case variant_key(GS, AXIS, 0, 1, false): launch(k_runblk2<GS, AXIS>); break;
 
 void launch_planned(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, const SweepVariant& v,
-                    hipStream_t stream) {
+                    hipStream_t stream, const SweepHint& hint) {
   if (v.engine == PM_ENGINE_SERIAL) {
     hipLaunchKernelGGL(k_sweep_serial, dim3((unsigned)((v.chains + 63) / 64), 1, (unsigned)slots), dim3(v.block), 0, stream,
                        ps, cp, g);
@@ -46,7 +46,8 @@ void launch_planned(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g
   }
   // the run engines: one workgroup per chain; arg: the kernel's arguments behind (ps, cp, g)
   auto launch_chain = [&](auto kernel, auto... arg) {
-    allow_big_lds(kernel, v.lds_bytes);
+    // (static LDS counts against the same limit as the dynamic part: the row +1 variants of k_runblk3 have some)
+    allow_big_lds(kernel, v.lds_bytes + kRun3StaticLds);
     hipLaunchKernelGGL(kernel, dim3((unsigned)v.chains, 1, (unsigned)slots), dim3((unsigned)v.block), v.lds_bytes, stream,
                        ps, cp, g, arg...);
   };
@@ -60,7 +61,12 @@ void launch_planned(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g
   }
   auto launch = [&](auto kernel) {
     const int seg_len = v.seg_len | (sweep_knobs().run3_dbg << 24);  // (PM_RUN3_DBG: the tuning build's timing switches)
-    launch_chain(kernel, seg_len
+    // the stop-bit plane is a row +1 sweep's alone, and only of a plane set that has one
+    const bool row_fwd = v.axis == 0 && v.dir > 0 && ps.stops;
+    const int mode = (hint.mode == kSegHintPlane && !row_fwd) ? kSegHintNone : hint.mode;
+    const int hint_bits = (mode & 3) | ((hint.write_stops && row_fwd) ? kRun3WriteStops : 0) |
+                          ((hint.stop_w < 0 ? 0 : (hint.stop_w > kRun3MaxStopWeight ? kRun3MaxStopWeight : hint.stop_w)) << 8);
+    launch_chain(kernel, seg_len, hint_bits, hint.dbg_bounds, hint.dbg_chain
 #ifdef PM_RUN3_STATS  // (its kernels take one more argument: the launch's slot of the per-chain log)
                  , run3_stats_slot(stream, v.axis, v.dir, v.group, v.chain_len, v.chains, v.waves)
 #endif
@@ -79,9 +85,9 @@ void launch_planned(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g
 }  // namespace
 
 SweepVariant launch_sweep(const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, int engine, float amp,
-                          hipStream_t stream) {
+                          hipStream_t stream, const SweepHint& hint) {
   const SweepVariant v = plan_sweep(cp.semantics, cp.pw, cp.ph, ps.rows, ps.cols, g, slots, engine, amp);
-  launch_planned(ps, cp, g, slots, v, stream);
+  launch_planned(ps, cp, g, slots, v, stream, hint);
   return v;
 }
 

@@ -50,7 +50,7 @@ EXPORTS = [
     "pm_reproject_disparity", "pm_debug_reproject_constants",
     "pm_filter_consistency",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
-    "pm_debug_sweep_plan", "pm_debug_noise_cost_constants", "pm_debug_noise_cost", "pm_debug_remove_background",
+    "pm_debug_sweep_plan", "pm_debug_segment_bounds", "pm_debug_propagate_hinted", "pm_debug_match_sweep_hint", "pm_debug_read_stops", "pm_debug_noise_cost_constants", "pm_debug_noise_cost", "pm_debug_remove_background",
     "pm_remove_background", "pm_mask_occlusions", "pm_foreground_texture_mask", "pm_sparse_init", "pm_corner_subpix", "pm_profile_enable", "pm_profile_read",
     "pm_kernel_name", "pm_debug_counters", "pm_debug_counters_enable",
     "pm_tile_begin", "pm_tile_noise", "pm_tile_sweep", "pm_tile_snapshot", "pm_tile_restore", "pm_tile_get_row",
@@ -443,6 +443,17 @@ def load():
     lib.pm_debug_sweep_plan.argtypes = [C.POINTER(PmParams), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_float, C.POINTER(PmDebugSweepVariant)]
     lib.pm_debug_sweep_plan.restype = C.c_int
+    lib.pm_debug_segment_bounds.argtypes = [u8p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    lib.pm_debug_segment_bounds.restype = C.c_int
+    lib.pm_debug_propagate_hinted.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                              C.POINTER(C.c_int), u8p, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                              C.POINTER(C.c_int), C.POINTER(PmDebugSweepVariant)]
+    lib.pm_debug_propagate_hinted.restype = C.c_int
+    lib.pm_debug_match_sweep_hint.argtypes = [C.POINTER(PmParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                              C.POINTER(C.c_int)]
+    lib.pm_debug_match_sweep_hint.restype = C.c_int
+    lib.pm_debug_read_stops.argtypes = [vp, C.c_int, C.c_int, C.c_int, u8p]
+    lib.pm_debug_read_stops.restype = C.c_int
     lib.pm_remove_background.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, f32p, C.c_int, C.c_int, C.c_float]
     lib.pm_remove_background.restype = C.c_int
     lib.pm_debug_noise_cost_constants.argtypes = [C.POINTER(C.c_int)] * 3
@@ -571,6 +582,37 @@ def sweep_plan(params, rows, cols, patch_h, patch_w, pass_index, slots=1, amp=1e
     if rc != PM_OK:
         raise PmError(rc, "pm_debug_sweep_plan")
     return {n: getattr(out, n) for n, _ in PmDebugSweepVariant._fields_}
+
+
+SEG_HINT_NONE, SEG_HINT_RUNS, SEG_HINT_PLANE = 0, 1, 2   # csrc/pm_seg_bounds.hpp::SegHint
+MIN_SEG_LEN = 8                                          # csrc/pm_seg_bounds.hpp::kMinSegLen
+
+
+def segment_bounds(flags, n, nseg, nd):
+    """pm_debug_segment_bounds: the boundaries k_runblk3 gives a chain of n positions cut into nseg segments, nd positions
+    per run step, with the stop prediction `flags` (None, or n values; non-zero = stop) -> list of nseg + 1 (no device)."""
+    out = (C.c_int * (nseg + 1))()
+    ptr = None
+    if flags is not None:
+        f = np.ascontiguousarray(flags, dtype=np.uint8)
+        assert f.shape == (n,)
+        ptr = f.ctypes.data_as(C.c_void_p)
+    rc = load().pm_debug_segment_bounds(ptr, n, nseg, nd, out)
+    if rc != PM_OK:
+        raise PmError(rc, "pm_debug_segment_bounds")
+    return list(out)
+
+
+SEG_HINT_MIN_CHAIN = 400                                 # csrc/pm_seg_bounds.hpp::kSegHintMinChain
+
+
+def match_sweep_hint(params, rows, cols, it, pass_index):
+    """pm_debug_match_sweep_hint: (hint mode, write_stops) Match() gives that sweep of that iteration (no device)."""
+    mode, write = C.c_int(-1), C.c_int(-1)
+    rc = load().pm_debug_match_sweep_hint(C.byref(params), rows, cols, it, pass_index, C.byref(mode), C.byref(write))
+    if rc != PM_OK:
+        raise PmError(rc, "pm_debug_match_sweep_hint")
+    return mode.value, write.value
 
 
 def _u8(a):
@@ -1050,6 +1092,35 @@ class Engine:
                                                 patch_h, patch_w, pass_mask, amp, ran), "pm_debug_propagate")
         return d, [{n: getattr(ran[k], n) for n, _ in PmDebugSweepVariant._fields_} for k in range(4)
                    if pass_mask & (1 << k)]
+
+    def debug_propagate_hinted(self, left, right, disp, patch_h, patch_w, pass_mask=15, amp=1e30, hints=(0, 0, 0, 0),
+                               stops=None, bounds_of=None):
+        """debug_propagate() with a segment-boundary hint per pass (pm_debug_propagate_hinted, include/pm/testing.h).
+        stops: None or a rows x cols uint8 plane handed to the row +1 pass; bounds_of: None or (pass, chain)
+        -> (map, variants, the stop-bit plane after the call or None, the boundaries that chain used or None)."""
+        left, pl = _u8(left)
+        right, pr = _u8(right)
+        d = np.array(disp, dtype=np.float32, order="C", copy=True)
+        ran = (PmDebugSweepVariant * 4)()
+        modes = (C.c_int * 4)(*hints)
+        st = None if stops is None else np.array(stops, dtype=np.uint8, order="C", copy=True)
+        assert st is None or st.shape == d.shape
+        bounds, nb = (C.c_int * 65)(), C.c_int(0)
+        bp, bc = bounds_of if bounds_of is not None else (0, -1)
+        self._check(self.lib.pm_debug_propagate_hinted(
+            self.h, pl, pr, d.shape[0], d.shape[1], d.ctypes.data_as(C.c_void_p), patch_h, patch_w, pass_mask, amp, modes,
+            None if st is None else st.ctypes.data_as(C.c_void_p), bp, bc, bounds if bounds_of is not None else None,
+            C.byref(nb), ran), "pm_debug_propagate_hinted")
+        recs = [{n: getattr(ran[k], n) for n, _ in PmDebugSweepVariant._fields_} for k in range(4)
+                if pass_mask & (1 << k)]
+        return d, recs, st, (list(bounds[:nb.value]) if bounds_of is not None else None)
+
+    def debug_read_stops(self, view, rows, cols):
+        """pm_debug_read_stops: the stop-bit plane of that view of pair 0 as the last call left it."""
+        out = np.zeros((rows, cols), np.uint8)
+        self._check(self.lib.pm_debug_read_stops(self.h, view, rows, cols, out.ctypes.data_as(C.c_void_p)),
+                    "pm_debug_read_stops")
+        return out
 
     def remove_background(self, left, right, disp, patch_h, patch_w, factor):
         left, pl = _u8(left)
