@@ -362,7 +362,11 @@ int pm_mask_occlusions(pm_handle* h, float* disp_l, const float* disp_r, int row
  * across the tile boundary: the caller moves that ROW of disparities between neighbouring tiles with
  * pm_tile_get_row / pm_tile_set_row (hipMemcpyPeer, RCCL send/recv, ...) and repeats the sweep from
  * pm_tile_snapshot's state until no tile's incoming row changes; the fixpoint is the untiled result
- * (driver: ocean-perception_amd/python/tiled.py).  All pointers are DEVICE memory; n = 1 pair. */
+ * (driver: ocean-perception_amd/python/tiled.py).  All pointers are DEVICE memory; n = 1 pair.
+ * A stage is the whole-image stage restricted to the OWNED rows: it writes the disparity and the cost of those rows only.
+ * The halo rows of the state belong to the neighbours -- pm_tile_set_row / pm_tile_presweep / pm_tile_exchange_round store
+ * there what a neighbour delivers -- and hold values >= 0; a band takes its slice of the whole-image noise table at
+ * pm_tile_begin.  Bands of one owned row and more are supported (tests/test_tile_stages.py). */
 typedef struct pm_tile {
   int global_rows; /* rows of the whole image                     */
   int band_row0;   /* image row of the band's first row           */

@@ -105,6 +105,19 @@ int pm_debug_noise_cost(pm_handle* h, const uint8_t* left, const uint8_t* right,
 int pm_debug_remove_background(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
                                const float* cost, int patch_h, int patch_w, float factor);
 
+/* ---- the state of a row-tiled band between its stages (pm_tile_*, csrc/pm_tile.hip) -------------------------------------
+ * pm_debug_tile_state: the disparity and cost plane of one view of the OPEN band, every band row, halo included.
+ * which: 0 = the live state planes, 1 = the snapshot planes (pm_tile_snapshot / pm_tile_presweep); view: 0 or 1, view 1 in
+ * its own mirrored coordinates, as pm_tile_get_row delivers it; disp / cost: host planes of band_rows x cols floats, either
+ * may be null; write = 0 copies out after synchronising the handle's stream, write = 1 copies in (and synchronises).
+ * PM_ERR_INVALID_ARG: no open band, a snapshot that does not exist, a view the handle does not have, writing the snapshot.
+ * pm_debug_tile_last_sweep: the record of what the last pm_tile_sweep / pm_tile_sweep_masked / pm_tile_exchange_round of
+ * this handle launched, all zero when that call swept nothing (or was refused).  chain_len / chains are the band's: a
+ * column sweep's chains are as long as the owned rows the whole-image sweep visits.  Written on the host, as in
+ * pm_debug_propagate; no kernel differs for it. */
+int pm_debug_tile_state(pm_handle* h, int which, int view, float* disp, float* cost, int write);
+int pm_debug_tile_last_sweep(pm_handle* h, pm_debug_sweep_variant* ran);
+
 /* ---- pm_point_cloud's launch constants (csrc/pm_cloud.hpp) ------------------------------------------------------------
  * items_per_block: the considered pixels one block of the count / scatter launches takes; blocks_per_scan_pass: the block
  * counts the offsets kernel turns into offsets per pass.  A map with more than items_per_block * blocks_per_scan_pass

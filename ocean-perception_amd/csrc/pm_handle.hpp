@@ -99,6 +99,8 @@ struct pm_handle {
   int tile_band_rows = 0, tile_cols = 0;
   pm::DevBuf<float> snap_disp;  // snapshot of the disparity / cost planes (2 views)
   pm::DevBuf<float> snap_cost;
+  pm::DevBuf<float> tile_noise;  // the band's noise table: owned rows of the whole-image table, halo rows zero
+  pm::SweepVariant tile_last_sweep;  // what the last sweep stage launched (pm_debug_tile_last_sweep); all zero: nothing
 
   // staging for the host-buffer entry points: tightly packed [B][rows][cols]
   pm::DevBuf<uint8_t> st_left;  // one block: left, then right

@@ -2,6 +2,7 @@
 // larger image and runs the phases of a Match one by one, so a driver (pm_tiled.hip in one process, or
 // python/tiled.py over RCCL) can exchange boundary rows between the phases.  Host logic only: geometry of the band
 // inside the whole image, snapshots, row copies; kernels through the launch functions of pm_handle.hpp.
+#include "pm/testing.h"
 #include "pm_handle.hpp"
 
 using namespace pm;
@@ -9,12 +10,26 @@ using namespace pm::eng;
 
 namespace {
 
-// PlaneSet of the band with the noise pointer moved to the band's slice of the whole-image table.
+// PlaneSet of the band with the noise pointer on the band's own table (tile_noise_table).
 PlaneSet tile_plane_set(pm_handle* h) {
   const int n_views = h->params.left_right_check ? 2 : 1;
   PlaneSet ps = plane_set(h, h->tile_band_rows, h->tile_cols, n_views);
-  ps.noise = h->noise + (size_t)h->tile.band_row0 * ps.pitch;
+  ps.noise = h->tile_noise;
   return ps;
+}
+
+// The band's noise table: its OWNED rows hold their slice of the whole-image table (ensure_noise), its halo rows zeros.
+// The noise + cost kernels add noise to every row of the plane set they are given; a unit noise of zero leaves a value
+// >= 0 bit for bit as it is, so pm_tile_noise changes owned rows only -- the halo rows of the state planes belong to the
+// neighbour bands (pm_tile_set_row), no stage of this band writes them.
+int tile_noise_table(pm_handle* h) {
+  const pm_tile& t = h->tile;
+  const size_t pitch = (size_t)align_up(h->tile_cols, 64);
+  if (!h->tile_noise) PM_HIP(h, h->tile_noise.alloc(sizeof(float) * ((size_t)h->max_rows * h->max_pitch + kSlackElems)));
+  PM_HIP(h, hipMemsetAsync(h->tile_noise, 0, sizeof(float) * ((size_t)h->tile_band_rows * pitch + kSlackElems), h->stream));
+  PM_HIP(h, hipMemcpyAsync(h->tile_noise + (size_t)(t.own_row0 - t.band_row0) * pitch, h->noise + (size_t)t.own_row0 * pitch,
+                           sizeof(float) * (size_t)t.own_rows * pitch, hipMemcpyDeviceToDevice, h->stream));
+  return PM_OK;
 }
 
 // Rows this tile sweeps: owned rows that the sweeps of the whole image visit, in band coordinates.
@@ -71,6 +86,7 @@ int pm_tile_begin(pm_handle* h, const pm_tile* tile, const uint8_t* d_left_band,
   h->tile_band_rows = band_rows;
   h->tile_cols = cols;
   h->tile_on = true;
+  if (int rc = tile_noise_table(h)) return rc;
   const PlaneSet ps = tile_plane_set(h);
   launch_prep(h, ps, d_left_band, d_right_band, 1, (size_t)cols, -1, nullptr, h->stream);
   if (int rc = launch_check(h, "prep")) return rc;
@@ -97,6 +113,7 @@ static int tile_sweep(pm_handle* h, int it, int k, const int* d_mask);
 int pm_tile_sweep(pm_handle* h, int it, int k) { return tile_sweep(h, it, k, nullptr); }
 int pm_tile_sweep_masked(pm_handle* h, int it, int k, const int* d_mask) {
   if (!h) return PM_ERR_INVALID_ARG;
+  h->tile_last_sweep = SweepVariant();
   if (!d_mask) {
     set_err(h, "pm_tile_sweep_masked: null mask");
     return PM_ERR_INVALID_ARG;
@@ -105,6 +122,7 @@ int pm_tile_sweep_masked(pm_handle* h, int it, int k, const int* d_mask) {
 }
 
 static int tile_sweep(pm_handle* h, int it, int k, const int* d_mask) {
+  if (h) h->tile_last_sweep = SweepVariant();  // (pm_debug_tile_last_sweep: a call that sweeps nothing leaves zeros)
   if (int rc = tile_check(h, "pm_tile_sweep")) return rc;
   const pm_params& p = h->params;
   if (it < 0 || it >= p.patchmatch_iters || k < 0 || k > 3) {
@@ -140,7 +158,7 @@ static int tile_sweep(pm_handle* h, int it, int k, const int* d_mask) {
     g.s_first -= t.band_row0;
     g.s_last -= t.band_row0;
   }
-  return run_sweep(h, ps, cp, g, ps.n_views, p.noise_amp[it], h->stream);
+  return run_sweep(h, ps, cp, g, ps.n_views, p.noise_amp[it], h->stream, &h->tile_last_sweep);
 }
 
 // the snapshot planes of the plan's two views, on first use
@@ -206,6 +224,7 @@ int pm_tile_restore_cols(pm_handle* h, const int* d_mask) {
 // pm_tile_restore_cols(mask of incoming != used) + pm_tile_set_row + pm_tile_sweep_masked.
 int pm_tile_exchange_round(pm_handle* h, int it, int k, int pred_image_row, const float* d_incoming, const float* d_used,
                            float* d_used_next, int* d_mask) {
+  if (h) h->tile_last_sweep = SweepVariant();
   if (int rc = tile_check(h, "pm_tile_exchange_round")) return rc;
   const int r = pred_image_row - h->tile.band_row0;
   if (!h->snap_disp || !d_incoming || !d_used || !d_used_next || d_used_next == d_used || !d_mask || r < 0 ||
@@ -290,6 +309,48 @@ int pm_tile_finish(pm_handle* h, float* d_disp_l_own, float* d_disp_r_own) {
   if (ps.n_views > 1)
     PM_HIP(h, hipMemcpyAsync(d_disp_r_own, h->st_disp_r + ofs, bytes, hipMemcpyDeviceToDevice, h->stream));
   h->tile_on = false;
+  return PM_OK;
+}
+
+// ---- test hooks (include/pm/testing.h) ----------------------------------------------------------------------------------
+// The state planes of one view of the open band, live or snapshot, to or from tight band_rows x cols host planes: the
+// copy kernels of the single stages on a plane set whose state pointers are moved to that view's planes.
+int pm_debug_tile_state(pm_handle* h, int which, int view, float* disp, float* cost, int write) {
+  if (int rc = tile_check(h, "pm_debug_tile_state")) return rc;
+  PlaneSet ps = tile_plane_set(h);
+  if (which < 0 || which > 1 || view < 0 || view >= ps.n_views || write < 0 || write > 1 || (which == 1 && write) ||
+      (which == 1 && !h->snap_disp)) {
+    set_err(h, "pm_debug_tile_state: planes %d / view %d of %d / write %d: no such planes, or the snapshot is read-only",
+            which, view, ps.n_views, write);
+    return PM_ERR_INVALID_ARG;
+  }
+  const size_t ofs = (size_t)view * ps.splane, px = (size_t)ps.rows * ps.cols;
+  ps.disp = (which ? h->snap_disp.get() : h->disp.get()) + ofs;
+  ps.cost = (which ? h->snap_cost.get() : h->cost.get()) + ofs;
+  float* const host[2] = {disp, cost};
+  const int plane_id[2] = {0, 3};  // the numbers of k_copy_in / k_copy_out
+  for (int i = 0; i < 2; ++i) {
+    if (!host[i]) continue;
+    if (write) {
+      PM_HIP(h, hipMemcpyAsync(h->st_disp_l, host[i], sizeof(float) * px, hipMemcpyHostToDevice, h->stream));
+      launch_copy_in(h, ps, h->st_disp_l, plane_id[i], h->stream);
+      if (int rc = launch_check(h, "copy_in")) return rc;
+    } else {
+      launch_copy_out(h, ps, h->st_disp_l, plane_id[i], h->stream);
+      if (int rc = launch_check(h, "copy_out")) return rc;
+      PM_HIP(h, hipMemcpyAsync(host[i], h->st_disp_l, sizeof(float) * px, hipMemcpyDeviceToHost, h->stream));
+    }
+    PM_HIP(h, hipStreamSynchronize(h->stream));  // (pageable host memory, and the staging plane is used twice)
+  }
+  if (!write) PM_HIP(h, hipStreamSynchronize(h->stream));  // (with two null planes a read is this synchronisation alone)
+  return PM_OK;
+}
+
+// what the last pm_tile_sweep / pm_tile_sweep_masked / pm_tile_exchange_round of this handle launched; host side only
+int pm_debug_tile_last_sweep(pm_handle* h, pm_debug_sweep_variant* ran) {
+  if (!h || !ran) return PM_ERR_INVALID_ARG;
+  const SweepVariant& v = h->tile_last_sweep;
+  *ran = pm_debug_sweep_variant{v.engine, v.axis, v.dir, v.group, v.waves, v.window, v.lref, v.chain_len, v.chains};
   return PM_OK;
 }
 

@@ -56,6 +56,7 @@ EXPORTS = [
     "pm_tile_begin", "pm_tile_noise", "pm_tile_sweep", "pm_tile_snapshot", "pm_tile_restore", "pm_tile_get_row",
     "pm_tile_set_row", "pm_tile_background", "pm_tile_finish", "pm_tile_restore_cols", "pm_tile_sweep_masked",
     "pm_tile_exchange_round", "pm_tile_row_moved", "pm_tile_presweep",
+    "pm_debug_tile_state", "pm_debug_tile_last_sweep",
     "pm_match_view_device", "pm_set_unit_noise", "pm_initialize",
     "pm_planes_begin", "pm_planes_step", "pm_planes_read", "pm_planes_write", "pm_planes_finish",
     "pm_tiled_band_rows", "pm_tiled_create", "pm_tiled_destroy", "pm_tiled_match_u8", "pm_tiled_last_error",
@@ -521,6 +522,10 @@ def load():
     lib.pm_tile_row_moved.restype = C.c_int
     lib.pm_tile_presweep.argtypes = [vp, C.c_int, f32p]
     lib.pm_tile_presweep.restype = C.c_int
+    lib.pm_debug_tile_state.argtypes = [vp, C.c_int, C.c_int, vp, vp, C.c_int]
+    lib.pm_debug_tile_state.restype = C.c_int
+    lib.pm_debug_tile_last_sweep.argtypes = [vp, C.POINTER(PmDebugSweepVariant)]
+    lib.pm_debug_tile_last_sweep.restype = C.c_int
     for name in ("pm_tile_begin", "pm_tile_noise", "pm_tile_sweep", "pm_tile_snapshot", "pm_tile_restore",
                  "pm_tile_get_row", "pm_tile_set_row", "pm_tile_background", "pm_tile_finish", "pm_tile_restore_cols",
                  "pm_tile_sweep_masked"):
@@ -1235,6 +1240,26 @@ class Engine:
 
     def tile_finish(self, d_out_l, d_out_r):
         self._check(self.lib.pm_tile_finish(self.h, d_out_l, d_out_r), "pm_tile_finish")
+
+    def debug_tile_state(self, shape, which=0, view=0):
+        """pm_debug_tile_state, reading: (disp, cost) of that view of the open band, `shape` = (band_rows, cols);
+        which: 0 = the live planes, 1 = the snapshot."""
+        d, c = np.empty(shape, np.float32), np.empty(shape, np.float32)
+        self._check(self.lib.pm_debug_tile_state(self.h, which, view, d.ctypes.data_as(C.c_void_p),
+                                                 c.ctypes.data_as(C.c_void_p), 0), "pm_debug_tile_state")
+        return d, c
+
+    def debug_tile_state_write(self, view, disp=None, cost=None, which=0):
+        """pm_debug_tile_state, writing the live planes of that view (either plane may be None)."""
+        d, pd = _f32(disp) if disp is not None else (None, None)
+        c, pc = _f32(cost) if cost is not None else (None, None)
+        self._check(self.lib.pm_debug_tile_state(self.h, which, view, pd, pc, 1), "pm_debug_tile_state")
+
+    def debug_tile_last_sweep(self):
+        """pm_debug_tile_last_sweep -> a dict of the fields of pm_debug_sweep_variant (all zero: nothing was swept)."""
+        out = PmDebugSweepVariant()
+        self._check(self.lib.pm_debug_tile_last_sweep(self.h, C.byref(out)), "pm_debug_tile_last_sweep")
+        return {n: getattr(out, n) for n, _ in PmDebugSweepVariant._fields_}
 
     # --- PM_MODE_PLANES stage by stage (device addresses as ints) ---------------------------------------
     def planes_begin(self, n, d_left, d_right, rows, cols, d_seed_l=None, d_seed_r=None):
