@@ -489,7 +489,9 @@ int pm_tiled_set_schedule(pm_tiled_plan* plan, int schedule);
  *   followed by v's refinement (one fused launch); finish
  * when params.mode == PM_MODE_PLANES.  These entry points run one stage each (tests, tools). */
 enum { PM_PL_SPATIAL = 1, PM_PL_VIEW = 2, PM_PL_REFINE = 3, PM_PL_VIEW_REFINE = 4 };
-/* prep + random plane initialisation (+ its cost) of n pairs; seeds as in pm_match_device */
+/* prep + random plane initialisation (+ its cost) of n pairs; seeds as in pm_match_device.  Images are at least 8x8, as
+ * for every Match entry point: a smaller one is refused with PM_ERR_INVALID_ARG (the error names pm_planes_begin), the
+ * handle stays usable, and no state is left to step on.  An image may be smaller than the window and than a tile. */
 int pm_planes_begin(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
                     const float* d_seed_l, const float* d_seed_r);
 /* stage = PM_PL_SPATIAL: arg = colour + 2 * iteration (colour 0 red: x + y even, 1 black), both views; the iteration

@@ -118,6 +118,44 @@ int pm_debug_remove_background(pm_handle* h, const uint8_t* left, const uint8_t*
 int pm_debug_tile_state(pm_handle* h, int which, int view, float* disp, float* cost, int write);
 int pm_debug_tile_last_sweep(pm_handle* h, pm_debug_sweep_variant* ran);
 
+/* ---- what a stage of PM_MODE_PLANES launches (csrc/pm_planes_plan.hpp::plan_planes) -------------------------------------
+ * One kernel template, k_planes, runs every stage of the mode, instantiated per stage, window P (3 .. 15), state type and
+ * window shape; a launch's grid and dynamic LDS, and the paths the kernel takes for the launch as a whole, follow from the
+ * parameters and the image size alone.  plan_planes computes them on the host, the launch is made from its result, and
+ * these hooks show it.  No kernel and no result differs for them.
+ * stage: 0 = the initialisation pm_planes_begin launches, or PM_PL_SPATIAL / _VIEW / _REFINE / _VIEW_REFINE as
+ * pm_planes_step takes them.  In a record `stage` is the instantiation that runs: PM_PL_VIEW_REFINE on a handle with one
+ * view (left_right_check = 0) runs PM_PL_REFINE, and PM_PL_VIEW with one view launches nothing -- the all-zero record.
+ * pm_debug_planes_constants: tile_w[5] / tile_h[5], indexed by the stage: the pixels one workgroup owns;
+ * fast_fill_entries: a launch whose target tile rows hold more than fast_fill_entries - 1 entries (`rw`) fills them entry
+ * by entry.  Any pointer may be null.  No handle, no device.
+ * pm_debug_planes_plan: the record for params (mode PM_MODE_PLANES), that stage and images of rows x cols; no handle, no
+ * device.  PM_ERR_INVALID_ARG (and an all-zero record): a null pointer, another mode, a window the mode does not hold, a
+ * stage outside 0 .. 4, rows or cols below 1.
+ * pm_debug_planes_last: the record of what the last pm_planes_begin / pm_planes_step of this handle launched, written on
+ * the host from the plan the launch was made from; all zero when that call launched nothing or was refused.  (After a
+ * Match() it holds the last launch of the schedule.) */
+typedef struct pm_debug_planes_variant {
+  int launched;       /* 1 = a kernel runs; 0 = nothing does, and every other field is 0                                */
+  int stage;          /* the instantiation: 0 = initialisation, else PM_PL_*                                            */
+  int patch;          /* window P                                                                                       */
+  int window;         /* PM_PL_WINDOW_FULL / PM_PL_WINDOW_CHECKER                                                       */
+  int state_f16;      /* 0 = f32 state, 1 = f16                                                                         */
+  int tile_w, tile_h; /* pixels per workgroup                                                                           */
+  int grid_x, grid_y; /* workgroups of one slot                                                                         */
+  int lds_bytes;      /* dynamic LDS                                                                                    */
+  int rw;             /* entries of a target tile row: tile_w + 2 (P / 2) + max_disp + 2 margin + 2                    */
+  int margin;         /* columns a slanted window reaches beyond the fronto-parallel one, per side                      */
+  int fast_fill;      /* 1 = the target tile is filled a dword (two pixels) per lane: even cols, rw + 1 <= fast_fill_entries */
+  int ref_regs;       /* 1 = the spatial stage keeps the reference window in registers (checkerboard 3 and 11)          */
+  int tap_class;      /* one id per grouping of the window's leftover taps: checkerboard 4 * (taps an even row leaves beyond
+                         whole groups of four) + (taps an odd row leaves) -- 9 for P = 3 and 11, 14 for 5 and 13, 3 for 7 and
+                         15, 4 for 9 --, full window 16 + P % 4                                                          */
+} pm_debug_planes_variant;
+void pm_debug_planes_constants(int* tile_w, int* tile_h, int* fast_fill_entries);
+int pm_debug_planes_plan(const pm_params* params, int stage, int rows, int cols, pm_debug_planes_variant* out);
+int pm_debug_planes_last(pm_handle* h, pm_debug_planes_variant* out);
+
 /* ---- pm_point_cloud's launch constants (csrc/pm_cloud.hpp) ------------------------------------------------------------
  * items_per_block: the considered pixels one block of the count / scatter launches takes; blocks_per_scan_pass: the block
  * counts the offsets kernel turns into offsets per pass.  A map with more than items_per_block * blocks_per_scan_pass

@@ -34,6 +34,7 @@
 #include "pm_device.hpp"
 #include "pm_hipres.hpp"
 #include "pm_hostcopy.hpp"
+#include "pm_planes_plan.hpp"
 #include "pm_seed_api.hpp"
 #include "pm_sweep_plan.hpp"
 #include "pm_tune.hpp"
@@ -87,6 +88,7 @@ struct pm_handle {
   pm::DevBuf<void> planes_state;
   int pl_rows = 0, pl_cols = 0, pl_n = 0;  // what pm_planes_begin last prepared
   bool pl_on = false;
+  pm::PlanesVariant pl_last;  // what the last pm_planes_begin / pm_planes_step launched (pm_debug_planes_last); all zero: nothing
 
   // scratch of the device seeder (pm_seed.hpp), one set per (lane, view): index lane * 2 + view.  Set 0 exists from
   // pm_create on, the others are allocated on first use (seeders of different views / lanes run side by side).

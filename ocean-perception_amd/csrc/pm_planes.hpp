@@ -25,39 +25,13 @@
 
 #include "pm_cloud_body.hpp"
 #include "pm_device.hpp"
+#include "pm_planes_plan.hpp"
 #include "pm_sweep_defs.hpp"
 
 namespace pm {
 
-enum { PL_INIT = 0, PL_SPATIAL = 1, PL_VIEW = 2, PL_REFINE = 3, PL_VIEW_REFINE = 4 };  // 4 = 2 then 3, one tile fill
+// (the stage ids PL_*, the tile sizes per stage and PlanesParams: pm_planes_plan.hpp)
 enum { PL_RAND_INIT = 0, PL_RAND_REFINE = 1 };  // `stage` of the random key (oracle: ST_INIT / ST_REFINE)
-
-// Tile height (rows = wavefronts of a block) per stage.  Results do not depend on it; what it trades is the halo (P - 1
-// extra rows of reference and target tile per block), the wavefronts a CU holds, and how evenly a launch's blocks fill
-// the chip's block slots (a 1280x720 view is 1800 blocks of 8 rows: 2.3 rounds on the 768 slots three blocks per CU give).
-// -DPL_TILE_H_SPATIAL / -DPL_TILE_H_OTHER: A/B builds (profiles/r06_planes_tile_height.txt).
-#ifndef PL_TILE_H_SPATIAL
-#define PL_TILE_H_SPATIAL 8
-#endif
-#ifndef PL_TILE_H_OTHER
-#define PL_TILE_H_OTHER 8
-#endif
-#ifndef PL_SPATIAL_REF_REGS
-#define PL_SPATIAL_REF_REGS 1
-#endif
-__host__ __device__ constexpr int pl_tile_h(int stage) { return stage == 1 /* PL_SPATIAL */ ? PL_TILE_H_SPATIAL : PL_TILE_H_OTHER; }
-
-struct PlanesParams {
-  int patch, max_disp, refine_steps, margin;
-  float slope_max;  // effective bound (f16-representable in f16 mode)
-  float slope_init, slope_per_disp;
-  float alpha, one_minus_alpha, tau_color, tau_grad, inv_n;
-  float lr_tol;
-  unsigned long long seed;
-  int n_views;
-  int window;  // PM_PL_WINDOW_FULL / PM_PL_WINDOW_CHECKER (pm/patchmatch.h): which taps of the P x P window count
-  int neighbours;  // PM_PL_NEIGH_FOUR / PM_PL_NEIGH_TWO: the spatial stage's candidates
-};
 
 // State of all slots: slot (pair, view) holds 4 arrays of `plane` elements: a, b, z, cost.
 // An array is split by COLOUR of the red-black stage: the pixels with x + y even first ([rows][pitch / 2], element
@@ -313,35 +287,7 @@ __device__ __forceinline__ void pl_row_taps(int xrow, const int (&xoff)[P], cons
     sg = __builtin_amdgcn_sad_u8(lgw[q] & mask, pgs, sg);
   }
 }
-// Two window rows of the checkerboard at once (round 6): an even row has NE = (P + 1) / 2 taps, the odd row behind it
-// NO = P / 2 -- 6 and 5 for P = 11 -- so both end in a partial group of four (2 taps and 1 tap), and a partial group costs
-// what a full one does (byte gathers, two v_sad_u8, masks).  Where the two leftovers fit ONE group they share it: the
-// samples are taken in the order [even full groups | odd full groups | even leftover, odd leftover], the reference bytes of
-// the shared group come from one v_perm_b32 of the two rows' last dwords (zero where the group is short: no masks).
-// P = 11: 3 groups per row pair instead of 4, 20 vector instructions for gathers and SADs instead of 26.
-template <int P>
-struct PlPairOrder {
-  static constexpr int NE = (P + 1) / 2, NO = P / 2, QE = NE / 4, QO = NO / 4, RE = NE % 4, RO = NO % 4, NT = NE + NO;
-  static constexpr bool shared = RE > 0 && RO > 0 && RE + RO <= 4;
-  int odd[NT], idx[NT];
-  constexpr PlPairOrder() : odd{}, idx{} {
-    int k = 0;
-    for (int j = 0; j < 4 * QE; ++j, ++k) { odd[k] = 0; idx[k] = j; }
-    for (int j = 0; j < 4 * QO; ++j, ++k) { odd[k] = 1; idx[k] = j; }
-    for (int j = 4 * QE; j < NE; ++j, ++k) { odd[k] = 0; idx[k] = j; }
-    for (int j = 4 * QO; j < NO; ++j, ++k) { odd[k] = 1; idx[k] = j; }
-  }
-  // v_perm_b32 selector of the shared group's reference bytes: RE bytes of the even row's last dword (source 1: bytes
-  // 0..3), then RO bytes of the odd row's (source 0: bytes 4..7), then zeros (0x0c)
-  static constexpr unsigned sel() {
-    unsigned v = 0;
-    for (int b = 0; b < 4; ++b) {
-      const unsigned s = b < RE ? (unsigned)b : (b < RE + RO ? (unsigned)(4 + b - RE) : 0x0cu);
-      v |= s << (8 * b);
-    }
-    return v;
-  }
-};
+// (two window rows of the checkerboard at once, PlPairOrder<P>: pm_planes_plan.hpp)
 template <int P, int LWW>
 __device__ __forceinline__ void pl_rowpair_taps(int xrow_e, int xrow_o, const int (&xoff)[P], const unsigned* ple,
                                                 const unsigned* plo, unsigned& sc, unsigned& sg) {
@@ -650,21 +596,8 @@ struct PlArgs {
   int dbg;  // tuning build only (PM_PLANES_DBG): bit 0 no window evaluation, bit 1 no tile fill -- timing experiments
 };
 
-// grid = (ceil(cols / TW), ceil(rows / tile height), slots), block = 64 x tile height, dynamic LDS = pl_lds_bytes().
-// Tile width.  The spatial stage updates one colour: 64 active lanes per row of a 128-wide tile.  The other stages update
-// every pixel: 64-wide tiles, one pixel per lane.  -DPL_WIDE_TW=128 gives them 128-wide tiles whose lanes take two pixels
-// of a row one after the other (half as many blocks per launch, the 164 extra target columns of a tile row amortised
-// over 128 pixels); tried for the last, partly filled round of blocks of a launch (900 blocks on 512 slots instead of
-// 1800 on 768) and dropped: 241 -> 231 pairs/s -- two blocks per CU instead of three leave 4 wavefronts per SIMD
-// instead of 6, which costs more than the tail gains (bit-identical either way).
-#ifndef PL_WIDE_TW
-#define PL_WIDE_TW 64
-#endif
-__host__ __device__ constexpr int pl_tile_w(int stage) { return stage == PL_SPATIAL ? 128 : PL_WIDE_TW; }
-__host__ __device__ constexpr int pl_ref_row_dwords(int LW, int win) {
-  // dwords per reference row (+1: a shifted copy reads 3 bytes further); checkerboard: per column-parity half
-  return win == 1 ? ((LW + 1) / 2 + 3) / 4 + 1 : (LW + 3) / 4 + 1;
-}
+// grid = (ceil(cols / TW), ceil(rows / tile height), slots), block = 64 x tile height, dynamic LDS: all from plan_planes().
+// (tile widths pl_tile_w and pl_ref_row_dwords: pm_planes_plan.hpp)
 template <int P, int STAGE, typename ST, int WIN>
 // (second launch bound = wavefronts per SIMD the register budget must allow: two of the red-black stage's 78 KB blocks fit
 // a CU's LDS -- four wavefronts per SIMD, 128 VGPRs -- and its register-resident reference window uses them)
@@ -679,7 +612,7 @@ __global__ void __launch_bounds__(64 * pl_tile_h(STAGE), STAGE == PL_SPATIAL ? 4
   constexpr int COPYW = TR * 2 * LWW;            // dwords per shifted copy: rows of LWW colour + LWW gradient dwords
   constexpr int NREF = (WIN == 1 ? 8 : 4) * (COPYW / 2);  // per channel (COPYW / 2 = TR * LWW); 2 NREF is even
   extern __shared__ __attribute__((aligned(16))) unsigned pl_lds[];
-  const int rw = TW + 2 * h + pp.max_disp + 2 * pp.margin + 2;
+  const int rw = pl_target_row_entries(TW, P, pp.max_disp, pp.margin);
   unsigned* s_rc = pl_lds;
   pl_u2* s_tgt = (pl_u2*)(pl_lds + 2 * NREF);  // 2 NREF is even: 8-byte aligned
   float* s_pl = (float*)(s_tgt + TR * rw);     // SPATIAL only: [3][kPlTileH + 2][TW + 2]
@@ -751,9 +684,8 @@ __global__ void __launch_bounds__(64 * pl_tile_h(STAGE), STAGE == PL_SPATIAL ? 4
         }
       };
       // target entry of column x = {pixel x, pixel x + 1}, each as colour | gradient << 16
-      const bool tfast = (cols & 1) == 0 && (reinterpret_cast<uintptr_t>(tgtpk) & 3u) == 0;  // uniform
-      constexpr int MAXT = 4;  // 128-column strips of the target tile whose loads are all in flight together
-      if (tfast && rw + 1 <= 128 * MAXT) {
+      constexpr int MAXT = kPlFillStrips;  // 128-column strips of the target tile whose loads are all in flight together
+      if (pl_fast_fill(cols, rw, (reinterpret_cast<uintptr_t>(tgtpk) & 3u) == 0)) {  // uniform
         // one dword (two pixels) per lane, row and strip: the entries of both its columns; the pixel behind them comes
         // from the next lane (lane 63: one more u16).  Columns outside the image repeat the border pixel, as the clamp did.
         const int xs_e = xs_lo & ~1, eoff = xs_lo - xs_e;  // even start column; entry index of column c = c - xs_lo
@@ -992,58 +924,52 @@ __global__ void __launch_bounds__(64 * pl_tile_h(STAGE), STAGE == PL_SPATIAL ? 4
   }  // sub
 }
 
-template <int STAGE>
-inline size_t pl_lds_bytes(int P, const PlanesParams& pp) {
-  const int h = P / 2;
-  const int TW = pl_tile_w(STAGE), kPlTileH = pl_tile_h(STAGE);
-  const int TR = kPlTileH + P - 1, LW = TW + P - 1;
-  const int nref = ((pp.window == 1 ? 8 : 4) * TR * pl_ref_row_dwords(LW, pp.window) + 1) & ~1;
-  const int rw = TW + 2 * h + pp.max_disp + 2 * pp.margin + 2;
-  size_t words = 2 * (size_t)nref + 2 * (size_t)TR * rw + 4;
-  if (STAGE == PL_SPATIAL) words += 3 * (size_t)(kPlTileH + 2) * (TW + 2);
-  return words * 4;
-}
-
+// ran (may be null): receives the plan the launch was made from (pm_debug_planes_last)
 template <int P, int STAGE, typename ST, int WIN>
 inline hipError_t pl_launch_w(const PlaneSet& ps, void* state, const PlanesParams& pp, const PlArgs& ar, int slots,
-                              hipStream_t stream) {
-  const int TW = pl_tile_w(STAGE), kPlTileH = pl_tile_h(STAGE);
-  const size_t lds = pl_lds_bytes<STAGE>(P, pp);
+                              hipStream_t stream, PlanesVariant* ran) {
+  // the target planes of every slot of the launch: plane 1 (view 0) and 2 (view 1) of the pair's four packed planes.
+  // `plane` is even (the pitch is a multiple of 64), so one start on a 4-byte boundary means all of them are.
+  const bool aligned4 = (reinterpret_cast<uintptr_t>(ps.pk16) & 3u) == 0 && (ps.plane & 1u) == 0;
+  const PlanesVariant v = plan_planes(pp, sizeof(ST) == 2, STAGE, ps.rows, ps.cols, aligned4);
+  if (!v.launched || v.stage != STAGE || v.patch != P || v.window != WIN) return hipErrorInvalidValue;
+  const size_t lds = (size_t)v.lds_bytes;
   if (lds > kChainLdsMax) return hipErrorInvalidValue;
   allow_big_lds(k_planes<P, STAGE, ST, WIN>, lds);
   PlaneState<ST> st;
   st.base = (ST*)state;
   st.plane = ps.plane;
   st.half_pitch = ps.pitch / 2;
-  const dim3 grid((unsigned)((ps.cols + TW - 1) / TW), (unsigned)((ps.rows + kPlTileH - 1) / kPlTileH), (unsigned)slots);
-  hipLaunchKernelGGL((k_planes<P, STAGE, ST, WIN>), grid, dim3(64 * kPlTileH), lds, stream, ps, st, pp, ar);
+  const dim3 grid((unsigned)v.grid_x, (unsigned)v.grid_y, (unsigned)slots);
+  hipLaunchKernelGGL((k_planes<P, STAGE, ST, WIN>), grid, dim3(64 * v.tile_h), lds, stream, ps, st, pp, ar);
+  if (ran) *ran = v;
   return hipGetLastError();
 }
 template <int P, int STAGE, typename ST>
 inline hipError_t pl_launch_t(const PlaneSet& ps, void* state, const PlanesParams& pp, const PlArgs& ar, int slots,
-                              hipStream_t stream) {
-  return pp.window == 1 ? pl_launch_w<P, STAGE, ST, 1>(ps, state, pp, ar, slots, stream)
-                        : pl_launch_w<P, STAGE, ST, 0>(ps, state, pp, ar, slots, stream);
+                              hipStream_t stream, PlanesVariant* ran) {
+  return pp.window == 1 ? pl_launch_w<P, STAGE, ST, 1>(ps, state, pp, ar, slots, stream, ran)
+                        : pl_launch_w<P, STAGE, ST, 0>(ps, state, pp, ar, slots, stream, ran);
 }
 
 template <int P, int STAGE>
 inline hipError_t pl_launch_p(const PlaneSet& ps, void* state, bool f16, const PlanesParams& pp, const PlArgs& ar,
-                              int slots, hipStream_t stream) {
-  return f16 ? pl_launch_t<P, STAGE, _Float16>(ps, state, pp, ar, slots, stream)
-             : pl_launch_t<P, STAGE, float>(ps, state, pp, ar, slots, stream);
+                              int slots, hipStream_t stream, PlanesVariant* ran) {
+  return f16 ? pl_launch_t<P, STAGE, _Float16>(ps, state, pp, ar, slots, stream, ran)
+             : pl_launch_t<P, STAGE, float>(ps, state, pp, ar, slots, stream, ran);
 }
 
 template <int STAGE>
 inline hipError_t pl_launch(const PlaneSet& ps, void* state, bool f16, const PlanesParams& pp, const PlArgs& ar,
-                            int slots, hipStream_t stream) {
+                            int slots, hipStream_t stream, PlanesVariant* ran = nullptr) {
   switch (pp.patch) {
-    case 3: return pl_launch_p<3, STAGE>(ps, state, f16, pp, ar, slots, stream);
-    case 5: return pl_launch_p<5, STAGE>(ps, state, f16, pp, ar, slots, stream);
-    case 7: return pl_launch_p<7, STAGE>(ps, state, f16, pp, ar, slots, stream);
-    case 9: return pl_launch_p<9, STAGE>(ps, state, f16, pp, ar, slots, stream);
-    case 11: return pl_launch_p<11, STAGE>(ps, state, f16, pp, ar, slots, stream);
-    case 13: return pl_launch_p<13, STAGE>(ps, state, f16, pp, ar, slots, stream);
-    case 15: return pl_launch_p<15, STAGE>(ps, state, f16, pp, ar, slots, stream);
+    case 3: return pl_launch_p<3, STAGE>(ps, state, f16, pp, ar, slots, stream, ran);
+    case 5: return pl_launch_p<5, STAGE>(ps, state, f16, pp, ar, slots, stream, ran);
+    case 7: return pl_launch_p<7, STAGE>(ps, state, f16, pp, ar, slots, stream, ran);
+    case 9: return pl_launch_p<9, STAGE>(ps, state, f16, pp, ar, slots, stream, ran);
+    case 11: return pl_launch_p<11, STAGE>(ps, state, f16, pp, ar, slots, stream, ran);
+    case 13: return pl_launch_p<13, STAGE>(ps, state, f16, pp, ar, slots, stream, ran);
+    case 15: return pl_launch_p<15, STAGE>(ps, state, f16, pp, ar, slots, stream, ran);
     default: return hipErrorInvalidValue;
   }
 }

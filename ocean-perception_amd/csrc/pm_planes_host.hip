@@ -5,6 +5,7 @@
 
 #include "pm_handle.hpp"
 #include "pm_internal.hpp"
+#include "pm/testing.h"
 #include "pm_planes.hpp"
 #include "pm_tune.hpp"
 
@@ -57,7 +58,8 @@ int planes_alloc(pm_handle* h, hipStream_t stream) {
   if (h->planes_state) return PM_OK;
   {  // the tile of the widest stage must fit the CU's LDS: (128 + P-1 + max_disp + slope margin) x (8 + P-1) entries
     const PlanesParams pp = planes_params(h->params);
-    const size_t need = pl_lds_bytes<PL_SPATIAL>(pp.patch, pp);
+    const size_t need = pl_lds_bytes(PL_SPATIAL, pp.patch, pp.window == 1 ? 1 : 0,
+                                     pl_target_row_entries(pl_tile_w(PL_SPATIAL), pp.patch, pp.max_disp, pp.margin));
     if (need > kChainLdsMax) {
       set_err(h, "PM_MODE_PLANES: window %d, max_disp %d and slope_max %.2f need %zu KB of LDS per tile (limit %zu KB): "
                  "lower max_disp or the window", pp.patch, pp.max_disp, (double)pp.slope_max, need / 1024,
@@ -93,7 +95,8 @@ int planes_stage(pm_handle* h, const PlaneSet& ps0, const PlArgs& ar, int slots,
   const PlaneSet ps = pair0 ? plane_set_of_pair(ps0, pair0) : ps0;
   // PlaneState::arr: a pair holds 2 views x 4 arrays of `plane` elements
   char* state = (char*)h->planes_state.get() + (size_t)pair0 * 8 * ps0.plane * (f16 ? sizeof(_Float16) : sizeof(float));
-  const hipError_t e = pl_launch<STAGE>(ps, state, f16, planes_params(h->params), ar, slots, stream);
+  // (the record of what was launched: pm_debug_planes_last; written on the host, the launch is made from it)
+  const hipError_t e = pl_launch<STAGE>(ps, state, f16, planes_params(h->params), ar, slots, stream, &h->pl_last);
   if (e != hipSuccess) {
     set_err(h, "launch of planes %s failed: %s", what, hipGetErrorString(e));
     return PM_ERR_HIP;
@@ -284,9 +287,14 @@ extern "C" {
 
 int pm_planes_begin(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
                     const float* d_seed_l, const float* d_seed_r) {
+  if (h) h->pl_last = PlanesVariant();
   if (int rc = planes_check(h, "pm_planes_begin", false)) return rc;
   if (!d_left || !d_right) {
     set_err(h, "pm_planes_begin: null image pointer");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (rows < 8 || cols < 8) {  // (the rule of every plane-mode entry point, Match() included: include/pm/patchmatch.h)
+    set_err(h, "pm_planes_begin: image %dx%d too small (plane mode takes 8x8 and more)", cols, rows);
     return PM_ERR_INVALID_ARG;
   }
   if (int rc = check_size(h, rows, cols, n)) return rc;
@@ -294,6 +302,7 @@ int pm_planes_begin(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d
 }
 
 int pm_planes_step(pm_handle* h, int stage, int arg) {
+  if (h) h->pl_last = PlanesVariant();  // (a step that launches nothing, or is refused, leaves zeros)
   if (int rc = planes_check(h, "pm_planes_step", true)) return rc;
   const int nv = h->params.left_right_check ? 2 : 1;
   const bool ok = (stage == PM_PL_SPATIAL && arg >= 0 && arg < 2 * PM_MAX_ITERS) ||
@@ -356,6 +365,49 @@ int pm_planes_finish(pm_handle* h, float* d_disp_l, float* d_disp_r) {
     return PM_ERR_INVALID_ARG;
   }
   return planes_finish(h, d_disp_l, d_disp_r, h->stream);
+}
+
+// ---- test hooks (include/pm/testing.h) ------------------------------------------------------------------------------
+static void planes_variant_out(const PlanesVariant& v, pm_debug_planes_variant* out) {
+  out->launched = v.launched;
+  out->stage = v.stage;
+  out->patch = v.patch;
+  out->window = v.window;
+  out->state_f16 = v.state_f16;
+  out->tile_w = v.tile_w;
+  out->tile_h = v.tile_h;
+  out->grid_x = v.grid_x;
+  out->grid_y = v.grid_y;
+  out->lds_bytes = v.lds_bytes;
+  out->rw = v.rw;
+  out->margin = v.margin;
+  out->fast_fill = v.fast_fill;
+  out->ref_regs = v.ref_regs;
+  out->tap_class = v.tap_class;
+}
+
+void pm_debug_planes_constants(int* tile_w, int* tile_h, int* fast_fill_entries) {
+  for (int s = PL_INIT; s <= PL_VIEW_REFINE; ++s) {
+    if (tile_w) tile_w[s] = pl_tile_w(s);
+    if (tile_h) tile_h[s] = pl_tile_h(s);
+  }
+  if (fast_fill_entries) *fast_fill_entries = 128 * kPlFillStrips;
+}
+
+int pm_debug_planes_plan(const pm_params* params, int stage, int rows, int cols, pm_debug_planes_variant* out) {
+  if (out) *out = pm_debug_planes_variant{};
+  if (!params || !out || stage < PL_INIT || stage > PL_VIEW_REFINE || rows < 1 || cols < 1) return PM_ERR_INVALID_ARG;
+  const PlanesParams pp = planes_params(*params);
+  if (params->mode != PM_MODE_PLANES || !pl_window_held(pp.patch)) return PM_ERR_INVALID_ARG;
+  // (device allocations start on 256-byte boundaries: the launch finds its target planes aligned)
+  planes_variant_out(plan_planes(pp, params->state_dtype == PM_STATE_F16, stage, rows, cols, true), out);
+  return PM_OK;
+}
+
+int pm_debug_planes_last(pm_handle* h, pm_debug_planes_variant* out) {
+  if (!h || !out) return PM_ERR_INVALID_ARG;
+  planes_variant_out(h->pl_last, out);
+  return PM_OK;
 }
 
 }  // extern "C"

@@ -59,6 +59,7 @@ EXPORTS = [
     "pm_debug_tile_state", "pm_debug_tile_last_sweep",
     "pm_match_view_device", "pm_set_unit_noise", "pm_initialize",
     "pm_planes_begin", "pm_planes_step", "pm_planes_read", "pm_planes_write", "pm_planes_finish",
+    "pm_debug_planes_constants", "pm_debug_planes_plan", "pm_debug_planes_last",
     "pm_tiled_band_rows", "pm_tiled_create", "pm_tiled_destroy", "pm_tiled_match_u8", "pm_tiled_last_error",
     "pm_tiled_upload_u8", "pm_tiled_run", "pm_tiled_download", "pm_tiled_topology", "pm_tiled_set_exchange",
     "pm_tiled_set_schedule",
@@ -137,6 +138,12 @@ class PmDebugSweepVariant(C.Structure):  # include/pm/testing.h
                                              "chains")]
 
 
+class PmDebugPlanesVariant(C.Structure):  # include/pm/testing.h
+    _fields_ = [(name, C.c_int) for name in ("launched", "stage", "patch", "window", "state_f16", "tile_w", "tile_h",
+                                             "grid_x", "grid_y", "lds_bytes", "rw", "margin", "fast_fill", "ref_regs",
+                                             "tap_class")]
+
+
 class PmCamera(C.Structure):  # include/pm/imaging.h: the radial-tangential model
     _fields_ = [(name, C.c_double) for name in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
 
@@ -195,6 +202,24 @@ def noise_cost_constants():
     a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
     load().pm_debug_noise_cost_constants(C.byref(a), C.byref(b), C.byref(c))
     return a.value, b.value, c.value
+
+
+def planes_constants():
+    """pm_debug_planes_constants: (tile widths, tile heights) of k_planes, each a tuple indexed by the stage (0 = the
+    initialisation, then PM_PL_*), and the entries of a target tile row from which on the tile is filled entry by entry."""
+    w, h, n = (C.c_int * 5)(), (C.c_int * 5)(), C.c_int(0)
+    load().pm_debug_planes_constants(w, h, C.byref(n))
+    return tuple(w), tuple(h), n.value
+
+
+def planes_plan(params, stage, rows, cols):
+    """pm_debug_planes_plan: what that stage (0 = initialisation, else PM_PL_*) launches on images of rows x cols, from the
+    host-side plan alone (no handle, no device) -> a dict of the fields of pm_debug_planes_variant."""
+    out = PmDebugPlanesVariant()
+    rc = load().pm_debug_planes_plan(C.byref(params), stage, rows, cols, C.byref(out))
+    if rc != PM_OK:
+        raise PmError(rc, "pm_debug_planes_plan")
+    return {n: getattr(out, n) for n, _ in PmDebugPlanesVariant._fields_}
 
 
 class PmMotion(C.Structure):  # pm_reproject_disparity: X_new = R X_old + t between the left camera frames
@@ -539,6 +564,12 @@ def load():
     lib.pm_planes_read.argtypes = [vp, C.c_int, C.c_int, f32p]
     lib.pm_planes_write.argtypes = [vp, C.c_int, C.c_int, f32p]
     lib.pm_planes_finish.argtypes = [vp, f32p, f32p]
+    lib.pm_debug_planes_constants.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.pm_debug_planes_constants.restype = None
+    lib.pm_debug_planes_plan.argtypes = [C.POINTER(PmParams), C.c_int, C.c_int, C.c_int, C.POINTER(PmDebugPlanesVariant)]
+    lib.pm_debug_planes_plan.restype = C.c_int
+    lib.pm_debug_planes_last.argtypes = [vp, C.POINTER(PmDebugPlanesVariant)]
+    lib.pm_debug_planes_last.restype = C.c_int
     for name in ("pm_planes_begin", "pm_planes_step", "pm_planes_read", "pm_planes_write", "pm_planes_finish"):
         getattr(lib, name).restype = C.c_int
     lib.pm_profile_enable.argtypes = [vp, C.c_int]
@@ -1280,6 +1311,12 @@ class Engine:
     def planes_write(self, pair, view, planes):
         a, p = _f32(planes)
         self._check(self.lib.pm_planes_write(self.h, pair, view, p), "pm_planes_write")
+
+    def debug_planes_last(self):
+        """pm_debug_planes_last -> a dict of the fields of pm_debug_planes_variant (all zero: nothing was launched)."""
+        out = PmDebugPlanesVariant()
+        self._check(self.lib.pm_debug_planes_last(self.h, C.byref(out)), "pm_debug_planes_last")
+        return {n: getattr(out, n) for n, _ in PmDebugPlanesVariant._fields_}
 
     def planes_finish(self, d_disp_l, d_disp_r):
         self._check(self.lib.pm_planes_finish(self.h, d_disp_l, d_disp_r), "pm_planes_finish")

@@ -303,6 +303,26 @@ void pmo_planes_prepare(const uint8_t* left, const uint8_t* right, int rows, int
   free(g);
 }
 
+/* disparity maps; consistency mask on the left map only, as MaskOcclusions does (patchmatch_gpu.cu:273-295) */
+void pmo_planes_finish(const pmo_planes_params* p, int rows, int cols, const pmo_planes_state* st0,
+                       const pmo_planes_state* st1, float* disp_l, float* disp_r) {
+  const int nv = p->left_right_check ? 2 : 1;
+  for (int y = 0; y < rows; ++y)
+    for (int x = 0; x < cols; ++x) {
+      const size_t o = (size_t)y * cols + x;
+      float dl = st0->z[o];
+      if (nv == 2) {
+        const float fx = (float)x - dl;
+        const int xt = clampi((int)rintf(fx), 0, cols - 1);
+        const float dr = st1->z[(size_t)y * cols + (cols - 1 - xt)];
+        const float df = dl - dr;
+        if (fabsf(df) > p->lr_tol) dl = 0.0f;
+        if (disp_r) disp_r[o] = st1->z[(size_t)y * cols + (cols - 1 - x)];
+      }
+      disp_l[o] = dl;
+    }
+}
+
 void pmo_planes_match(const pmo_planes_params* p, const uint8_t* left, const uint8_t* right, int rows, int cols,
                       const float* seed_l, const float* seed_r, float* disp_l, float* disp_r, float* planes_out) {
   const size_t n = (size_t)rows * cols;
@@ -341,21 +361,7 @@ void pmo_planes_match(const pmo_planes_params* p, const uint8_t* left, const uin
       pmo_planes_refine(p, &im[v], v, it, &st[v]);
     }
   }
-  /* disparity maps; consistency mask on the left map only, as MaskOcclusions does (patchmatch_gpu.cu:273-295) */
-  for (int y = 0; y < rows; ++y)
-    for (int x = 0; x < cols; ++x) {
-      const size_t o = (size_t)y * cols + x;
-      float dl = st[0].z[o];
-      if (nv == 2) {
-        const float fx = (float)x - dl;
-        const int xt = clampi((int)rintf(fx), 0, cols - 1);
-        const float dr = st[1].z[(size_t)y * cols + (cols - 1 - xt)];
-        const float df = dl - dr;
-        if (fabsf(df) > p->lr_tol) dl = 0.0f;
-        if (disp_r) disp_r[o] = st[1].z[(size_t)y * cols + (cols - 1 - x)];
-      }
-      disp_l[o] = dl;
-    }
+  pmo_planes_finish(p, rows, cols, &st[0], &st[1], disp_l, disp_r);
   if (planes_out) memcpy(planes_out, stf, sizeof(float) * 4 * n * nv);
   free(seed_rm);
   free(stf);

@@ -113,6 +113,12 @@ void pmo_planes_view_prop(const pmo_planes_params* p, const pmo_planes_view* im,
                           const pmo_planes_state* other);
 void pmo_planes_refine(const pmo_planes_params* p, const pmo_planes_view* im, int view, int it, pmo_planes_state* st);
 
+/* The last step of a Match(): the disparity maps of the states.  disp_l = z of view 0, set to 0 where the right view
+ * disagrees (|dl - dr| > lr_tol at the column rint(x - dl), clamped to the row; only with left_right_check); disp_r (may be
+ * NULL) = z of view 1 in right-image coordinates.  st1 is not read when left_right_check == 0. */
+void pmo_planes_finish(const pmo_planes_params* p, int rows, int cols, const pmo_planes_state* st0,
+                       const pmo_planes_state* st1, float* disp_l, float* disp_r);
+
 /* Whole Match(): both views, I iterations, disparity maps out (right map in right-image coordinates).
  * seed_l / seed_r in left / right image coordinates or NULL.  planes_out (optional): 8 planes of rows*cols
  * floats: view 0 a, b, z, cost, view 1 (mirrored coordinates) a, b, z, cost. */

@@ -576,6 +576,8 @@ def _planes_lib():
         lib.pmo_planes_refine.argtypes = [PP, PV, C.c_int, C.c_int, PS]
         lib.pmo_planes_match.argtypes = [PP, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
         lib.pmo_planes_prepare.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
+        lib.pmo_planes_finish.argtypes = [PP, C.c_int, C.c_int, PS, PS, vp, vp]
+        lib.pmo_planes_finish.restype = None
         _planes_ready = True
     return lib
 
@@ -649,10 +651,23 @@ class PlanesViews:
     def refine(self, p, view, it):
         _planes_lib().pmo_planes_refine(C.byref(p), C.byref(self.view[view]), view, it, C.byref(self.state[view]))
 
+    def finish(self, p):
+        """pmo_planes_finish on the current states -> (left map, right map in right-image coordinates)."""
+        dl = np.zeros((self.rows, self.cols), np.float32)
+        dr = np.zeros((self.rows, self.cols), np.float32)
+        _planes_lib().pmo_planes_finish(C.byref(p), self.rows, self.cols, C.byref(self.state[0]), C.byref(self.state[1]),
+                                        _p(dl), _p(dr))
+        return dl, dr
+
+
+PLANES_MIN_SIZE = 8   # the engine's rule (include/pm/patchmatch.h): plane mode takes images of 8x8 and more
+
 
 def planes_match(p, left, right, seed_l=None, seed_r=None, want_planes=False):
     left, right = c_u8(left), c_u8(right)
     rows, cols = left.shape
+    if rows < PLANES_MIN_SIZE or cols < PLANES_MIN_SIZE:   # refused by the same rule as pm_planes_begin / Match()
+        raise ValueError(f"planes_match: image {cols}x{rows} too small (plane mode takes 8x8 and more)")
     sl = c_f32(seed_l) if seed_l is not None else None
     sr = c_f32(seed_r) if seed_r is not None else None
     dl = np.zeros((rows, cols), np.float32)

@@ -13,7 +13,9 @@ import pytest
 
 from conftest import assert_same
 
-ROWS, COLS = 72, 200  # not multiples of the 8 x 32 / 8 x 64 tiles
+# 72 rows are nine whole 8-row tiles; 200 columns are an even width (the fast target-tile fill) that is no multiple of the
+# 64- and 128-column tiles.  Partial tiles in y, odd widths, tile edges and the smallest images: tests/test_plane_stages.py.
+ROWS, COLS = 72, 200
 
 
 def okw(pm_params):
