@@ -27,6 +27,26 @@ long long pm_debug_live_host_buffers(void);
 long long pm_debug_live_host_bytes(void);
 long long pm_debug_live_graph_execs(void);
 
+/* ---- the route of a Match() call ---------------------------------------------------------------------------------------
+ * What csrc/pm_match_plan.hpp::plan_match, the host function every Match() enqueues from, decides for a call on n pairs
+ * with these parameters -- seed_l_given / seed_r_given: the view's seed maps are given; bgr: the input is BGR
+ * (pm_match_bgr_device) -- with the knobs of this build: no handle, no device.
+ * PM_ERR_INVALID_ARG: a null pointer, n < 1. */
+typedef struct pm_debug_match_route {
+  int route;              /* 0 plane mode; 1 head and views on the handle's stream; 2 the head once for both views, then
+                             the views on two streams; 3 per-view heads on two streams; 4 chunks                      */
+  int n_views;
+  int self_seed[2];       /* 1: that view's seed map is computed on the device                                       */
+  int pair_chunk;         /* pairs per chunk                                                                         */
+  int head_aside;         /* 1: a chunk's head runs on the upload stream                                             */
+  int lane_pairs[2];      /* plane mode: pairs on the handle's stream / on the second stream                         */
+  int seq_chunks;         /* frame sequences: 1 = frames run as chunks over the view streams                         */
+  int seq_hold;           /* ... 1 = a frame may be held for a partner while the device is busy                      */
+  int need_view_events, need_slot_events, need_second_seed_scratch; /* what pm_capture_begin creates ahead of a capture */
+} pm_debug_match_route;
+int pm_debug_match_plan(const pm_params* params, int n, int seed_l_given, int seed_r_given, int bgr,
+                        pm_debug_match_route* out);
+
 /* ---- the directional sweeps as ONE iteration of Match() launches them ------------------------------------------------
  * pm_propagate (include/pm/patchmatch.h) with the iteration's noise amplitude as an argument, and a record of the kernel
  * variant every pass ran.  The amplitude changes no result: with the window, the axis and the direction it selects the

@@ -44,23 +44,23 @@ hipError_t create_stream(hipStream_t* s, int kind, int prio_class) {
   // high: eight band handles 49 -> 117 ms and pm_match_u8 314 -> 218 pairs/s as soon as a single-pair handle lived in
   // the same process).  Measured with every handle kind alive in one process (tools/stream_matrix.py,
   // profiles/r04_stream_matrix.txt): single 384, batch 429, pm_match_u8 310-323, eight bands 47.6 ms -- each within
-  // 1 % of the same leg in a process of its own.  The tuning build reads PM_STREAM_PRIO = "main,view,copy,lane"
-  // (1 high, 0 default, -1 low; one number = all four).
+  // 1 % of the same leg in a process of its own.  The tuning build reads PM_STREAM_PRIO = "main,view,copy"
+  // (1 high, 0 default, -1 low; one number = all three).
   static const struct Prio {
-    int v[4];
+    int v[3];
     Prio() {
-      v[0] = v[1] = v[2] = v[3] = 1;
+      v[0] = v[1] = v[2] = 1;
       const char* e = pm::tune_env("PM_STREAM_PRIO");
       if (e) {
-        int a = 1, b = 1, c = 1, d = 1;
-        const int n = sscanf(e, "%d,%d,%d,%d", &a, &b, &c, &d);
-        if (n == 1) b = c = d = a;
-        v[0] = a; v[1] = b; v[2] = c; v[3] = d;
+        int a = 1, b = 1, c = 1;
+        const int n = sscanf(e, "%d,%d,%d", &a, &b, &c);
+        if (n == 1) b = c = a;
+        v[0] = a; v[1] = b; v[2] = c;
       }
     }
   } prio;
   // pm_params.stream_priority selects the class of a handle's streams; the tuning build's PM_STREAM_PRIO overrides it
-  const int p = pm::tune_env("PM_STREAM_PRIO") ? prio.v[kind & 3] : prio_class;
+  const int p = pm::tune_env("PM_STREAM_PRIO") ? prio.v[kind] : prio_class;
   if (p == 0) return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
   if (p == 2) {
     // a stream with a CU mask never shares its hardware queue (the runtime keeps such queues out of the shared pools);
@@ -375,14 +375,11 @@ int view_op(pm_handle* h, const PlaneSet& ps, int idx, int slots, hipStream_t st
       const SweepHint hint = match_sweep_hint(p, it, k - 1, (g.s_last - g.s_first) * g.dir + 1);
       return run_sweep(h, ps, cp, g, slots, p.noise_amp[it], stream, nullptr, hint);
     }
-    {
-      Launch l(h, PM_K_NOISE, stream);
-      // from the second iteration on the cost plane is valid for this window if the window is unchanged
-      const CostParams prev = it > 0 ? cost_params(p, p.patch_w[it - 1], p.patch_h[it - 1]) : cp;
-      const int keep_zero = (it > 0 && cp.pw == prev.pw && cp.ph == prev.ph) ? 1 : 0;
-      launch_noise_cost(h, ps, cp, in, p.noise_amp[it], slots, keep_zero, stream);
-    }
-    return launch_check(h, "noise_cost");
+    Launch l(h, PM_K_NOISE, stream);
+    // from the second iteration on the cost plane is valid for this window if the window is unchanged
+    const CostParams prev = it > 0 ? cost_params(p, p.patch_w[it - 1], p.patch_h[it - 1]) : cp;
+    const int keep_zero = (it > 0 && cp.pw == prev.pw && cp.ph == prev.ph) ? 1 : 0;
+    return launch_noise_cost(h, ps, cp, in, p.noise_amp[it], slots, keep_zero, stream);
   }
   const CostParams bcp = cost_params(p, p.bg_patch_w, p.bg_patch_h);
   const Interior in = interior(p, ps.rows, ps.cols, bcp.pw, bcp.ph);
@@ -392,11 +389,8 @@ int view_op(pm_handle* h, const PlaneSet& ps, int idx, int slots, hipStream_t st
     cached = (bcp.pw == last.pw && bcp.ph == last.ph) ? 1 : 0;
   }
   const float factor = p.semantics == PM_SEM_CPU ? p.win_by_factor : p.cost_improve_factor;
-  {
-    Launch l(h, PM_K_BACKGROUND, stream);
-    launch_background(h, ps, bcp, in, factor, cached, slots, stream);
-  }
-  return launch_check(h, "background");
+  Launch l(h, PM_K_BACKGROUND, stream);
+  return launch_background(h, ps, bcp, in, factor, cached, slots, stream);
 }
 
 // `sets` plane sets are advanced side by side, each on its own stream (one set on the handle's stream, or the two
@@ -411,33 +405,17 @@ int run_view_sets(pm_handle* h, const PlaneSet* pss, const hipStream_t* streams,
   return PM_OK;
 }
 
-bool view_streams_enabled() {
-  static bool v = [] {
-    const char* e = pm::tune_env("PM_VIEW_STREAMS");
-    return e ? atoi(e) != 0 : true;
+// the knobs of plan_match: the defaults, or -- tuning build -- PM_VIEW_STREAMS, PM_PAIR_CHUNK, PM_PLANES_LANES, read once
+const MatchKnobs& match_knobs() {
+  static const MatchKnobs knobs = [] {
+    MatchKnobs k;
+    if (const char* e = pm::tune_env("PM_VIEW_STREAMS")) k.view_streams = atoi(e) != 0;
+    if (const char* e = pm::tune_env("PM_PAIR_CHUNK")) k.pair_chunk = atoi(e);
+    if (const char* e = pm::tune_env("PM_PLANES_LANES")) k.plane_lanes = atoi(e) != 1;
+    return k;
   }();
-  return v;
+  return knobs;
 }
-
-int seed_views(pm_handle* h, const PlaneSet& ps, int n_pairs, int view, int scratch, hipStream_t stream) {
-  if (!h->need_seed[view]) return PM_OK;
-  Launch l(h, PM_K_SEED, stream);
-  for (int b = 0; b < n_pairs; ++b)
-    if (int rc = run_sparse_init(h, ps, b, view, scratch, kSeedAllStages, stream)) return rc;
-  return PM_OK;
-}
-
-// What a view stream needs to prepare its own planes (match_device_impl): with the views on their own streams the
-// prep / transpose / line-plane / seed kernels of a view run at the head of that view's stream, so the two halves of
-// the setup run side by side and neither view waits for the other's (round 2: eight launches in a row on the main
-// stream, then a cross-stream event in front of each view).
-struct ViewSetup {
-  const uint8_t* d_left;
-  const uint8_t* d_right;
-  const float* d_seed_l;
-  const float* d_seed_r;
-  int n;
-};
 
 // Fork / join bookkeeping.  While a capture is open, every stream work was forked onto is remembered until the
 // handle's stream has waited for an event recorded behind that work: hipStreamEndCapture on a capture with an unjoined
@@ -463,6 +441,33 @@ hipEvent_t join_event(const pm_handle* h, hipStream_t s) {
 }
 
 }  // namespace
+
+MatchPlan match_plan(const pm_handle* h, const MatchCall& c) {
+  return plan_match(h->params, c.n, c.seed_l != nullptr, c.seed_r != nullptr, c.bgr != nullptr, match_knobs());
+}
+
+int enqueue_head(pm_handle* h, const PlaneSet& ps, const MatchCall& c, int view, unsigned steps, hipStream_t stream,
+                 int scratch, int pair0, int n_pairs) {
+  const bool timed = !(steps & kHeadUntimed);
+  if (steps & kHeadPrep) {
+    Launch l(h, PM_K_PREP, stream, timed);
+    if (int rc = launch_prep(h, ps, c, view, (steps & kHeadRideSeeds) != 0, stream)) return rc;
+  }
+  if (steps & kHeadLines) {
+    Launch l(h, PM_K_PREP, stream, timed);
+    if (int rc = run_transpose(h, ps, c.n, view, stream)) return rc;
+  }
+  if (steps & kHeadSeedCopy) {
+    Launch l(h, PM_K_SEED, stream, timed);
+    if (int rc = launch_seed(h, ps, c.seed_l, c.seed_r, c.n, view, stream)) return rc;
+  }
+  if (const unsigned stages = steps & kSeedAllStages) {
+    Launch l(h, PM_K_SEED, stream, timed);
+    for (int b = pair0, end = pair0 + (n_pairs < 0 ? c.n : n_pairs); b < end; ++b)
+      if (int rc = run_sparse_init(h, ps, b, view, scratch, stages, stream)) return rc;
+  }
+  return PM_OK;
+}
 
 // `onto` waits for `ev`, recorded here behind everything `from` holds (from null: `ev` as recorded before; ev null:
 // nothing to wait for), and counts as forked.  What `from` held is then behind `onto`: joining `onto` joins it too.
@@ -521,9 +526,14 @@ int seq_events_create(pm_handle* h) {
 
 namespace {
 
-// Both views of the pairs of `ps` on vstream[0] / vstream[1], each stream already forked; view v seeds with scratch
-// set v.  Enqueue only; the caller joins.
-int run_views_on(pm_handle* h, const PlaneSet& ps, int slots, const ViewSetup* setup, const hipStream_t vstream[2]) {
+// Both views of c's pairs (plane set `ps`) on vstream[0] / vstream[1], each stream already forked.  `head`: the steps
+// each view still has to run at the head of its own stream (enqueue_head) -- everything, the seeder alone (the rest ran
+// once for both views), or nothing (a chunk whose head ran aside); view v seeds with scratch set v.  With the views on
+// their own streams the two halves of the setup run side by side and neither view waits for the other's.  Enqueue only;
+// the caller joins.
+constexpr unsigned kHeadOfView = kHeadPrep | kHeadRideSeeds | kHeadLines | kSeedAllStages;
+int run_views_on(pm_handle* h, const PlaneSet& ps, const MatchCall& c, const MatchPlan& plan, unsigned head,
+                 const hipStream_t vstream[2]) {
   int rc = PM_OK;
   PlaneSet pv[2] = {ps, ps};
   for (int v = 0; v < 2; ++v) pv[v].view_fixed = v;
@@ -531,35 +541,25 @@ int run_views_on(pm_handle* h, const PlaneSet& ps, int slots, const ViewSetup* s
   // launch k of BOTH views before launch k + 1 of either.  (One view's whole head first left the other view's stream
   // empty for the ~55 us the host needs for nine launches, and the second view then ends that much later: a tenth of
   // the reference's own 376x240 call, profiles/r06_reference_call_timeline.txt.)
-  for (int op = 0; op < 2 && setup && rc == PM_OK; ++op)
-    for (int v = 0; v < 2 && rc == PM_OK; ++v) {
-      Launch l(h, PM_K_PREP, vstream[v]);
-      if (op == 0) {
-        const PrepSeedMaps seeds{setup->d_seed_l, setup->d_seed_r};  // the seed copy rides along (one launch less)
-        launch_prep(h, ps, setup->d_left, setup->d_right, setup->n, (size_t)ps.cols, v, &seeds, vstream[v]);
-        rc = launch_check(h, "prep");
-      } else {
-        rc = run_transpose(h, ps, setup->n, v, vstream[v]);
-      }
-    }
-  for (int b = 0; b < slots / 2 && rc == PM_OK; ++b)  // a view's pairs share its scratch: pair by pair
+  for (unsigned step : {head & (kHeadPrep | kHeadRideSeeds), head & kHeadLines})
+    for (int v = 0; v < 2 && step && rc == PM_OK; ++v) rc = enqueue_head(h, ps, c, v, step, vstream[v]);
+  for (int b = 0; b < c.n && rc == PM_OK; ++b)  // a view's pairs share its scratch: pair by pair
     for (int st = 0; st < kSeedStages && rc == PM_OK; ++st)
-      for (int v = 0; v < 2 && rc == PM_OK; ++v) {
-        if (!h->need_seed[v]) continue;
-        Launch l(h, PM_K_SEED, vstream[v]);
-        rc = run_sparse_init(h, ps, b, v, v, 1u << st, vstream[v]);
-      }
-  if (rc == PM_OK) rc = run_view_sets(h, pv, vstream, 2, slots / 2);
+      for (int v = 0; v < 2 && rc == PM_OK; ++v)
+        if (plan.self_seed[v] && (head & (1u << st))) rc = enqueue_head(h, ps, c, v, 1u << st, vstream[v], v, b, 1);
+  if (rc == PM_OK) rc = run_view_sets(h, pv, vstream, 2, c.n);
   if (rc == PM_ERR_HIP && !h->err[0]) set_err(h, "per-view stream setup failed");
   return rc;
 }
 
-int run_views(pm_handle* h, const PlaneSet& ps, int slots, const ViewSetup* setup = nullptr) {
-  if (ps.n_views != 2 || !view_streams_enabled()) {
-    for (int v = 0; v < ps.n_views; ++v)
-      if (int rc = seed_views(h, ps, slots / ps.n_views, v, 0, h->stream)) return rc;
+// The views of c's pairs behind whatever head the route leaves to them (match_device_impl).
+int run_views(pm_handle* h, const PlaneSet& ps, const MatchCall& c, const MatchPlan& plan) {
+  if (plan.route == kRouteOneStream) {
+    for (int v = 0; v < plan.n_views; ++v)
+      if (plan.self_seed[v])
+        if (int rc = enqueue_head(h, ps, c, v, kSeedAllStages, h->stream)) return rc;
     const hipStream_t own = h->stream;
-    return run_view_sets(h, &ps, &own, 1, slots);
+    return run_view_sets(h, &ps, &own, 1, c.n * plan.n_views);
   }
   // one view stays on the caller's stream, the other forks off
   if (int rc = view_streams_create(h)) return rc;
@@ -580,7 +580,7 @@ int run_views(pm_handle* h, const PlaneSet& ps, int slots, const ViewSetup* setu
   vs[h->late_view] = h->stream;
   vs[1 - h->late_view] = h->view1_stream;
   auto views = [&]() -> int {
-    if (int rc = run_views_on(h, ps, slots, setup, vs)) return rc;
+    if (int rc = run_views_on(h, ps, c, plan, plan.route == kRouteViewHeads ? kHeadOfView : kSeedAllStages, vs)) return rc;
     // sampled: a timed event is a command of its own on the stream, in front of the join of every call it is recorded in
     if (!h->capturing && !h->view_end_recorded && (h->view_calls++ % pm_handle::kViewEndEvery) == 0) {
       for (int v = 0; v < 2; ++v) PM_HIP(h, hipEventRecord(h->view_end[v], vs[v]));
@@ -616,22 +616,6 @@ PlaneSet plane_set_of_pair(const PlaneSet& ps, int b) {
   return q;
 }
 
-// pairs per chunk (PM_PAIR_CHUNK in the tuning build).  Two pairs advanced through every launch together run at 408
-// pairs/s where one runs at 373 -- a single pair leaves SIMDs short of wavefronts -- while 4 or 32 in lockstep fall back
-// to 368 / 357 (working sets): profiles/r03_pair_lanes.txt.
-int pair_chunk() {
-  static const int v = [] {
-    const char* e = pm::tune_env("PM_PAIR_CHUNK");
-    const int x = e ? atoi(e) : 2;
-    return x < 1 ? 1 : x;
-  }();
-  return v;
-}
-
-bool seq_pipelined(const pm_handle* h) {
-  return h->params.mode == PM_MODE_SCALAR && h->params.left_right_check != 0 && view_streams_enabled() && !h->bgr;
-}
-
 // One CHUNK of a batch or of a frame sequence: pairs [b, b + c) of the plan.
 //   the HEAD of the chunk, behind the non-null events `ready` (the chunk's inputs are in device memory) and `ready2`
 //                 (those of its second frame, in a chunk of two device-resident frames): images, gradients, transposes
@@ -644,76 +628,48 @@ bool seq_pipelined(const pm_handle* h) {
 //                 ([c][rows][cols]).
 // Chunks enqueued one after the other run back to back on the two view streams, nothing forks or joins in between.
 // Enqueue only; the caller orders what follows behind s_out.
-int seq_enqueue_chunk(pm_handle* h, int b, int c, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
-                      const float* d_seed_l, const float* d_seed_r, float* d_disp_l, float* d_disp_r, hipEvent_t ready,
-                      hipEvent_t ready2, const Event v_done[2], hipEvent_t head_done) {
+int seq_enqueue_chunk(pm_handle* h, int b, const MatchCall& c, const MatchPlan& plan, float* d_disp_l, float* d_disp_r,
+                      const ChunkEvents& ev) {
   if (int rc = view_streams_create(h)) return rc;
-  const PlaneSet ps = plane_set(h, rows, cols, 2);
-  const PlaneSet pb = plane_set_of_pair(ps, b);
-  h->need_seed[0] = h->params.sparse_init && !d_seed_l;
-  h->need_seed[1] = h->params.sparse_init && !d_seed_r;
-  // ---- head: on s_in when a view seeds itself (measured, frame sequence at 720p: self-seeded 396 -> 401 pairs/s with the
-  // head aside, seeded 410 -> 402 -- without the seeder the head is too short to pay for one more cross-queue wait)
-  const bool head_aside = h->need_seed[0] || h->need_seed[1];
+  const PlaneSet pb = plane_set_of_pair(plane_set(h, c.rows, c.cols, 2), b);
   const hipStream_t vs[2] = {h->stream, h->view1_stream};
-  if (head_aside) {
-    for (hipEvent_t e : {ready, ready2})
+  if (plan.head_aside) {  // on s_in (MatchPlan::head_aside): the view streams then start with the first noise + cost
+    for (hipEvent_t e : {ev.ready, ev.ready2})
       if (int rc = fork_stream(h, e, nullptr, h->s_in)) return rc;
-    for (int v = 0; v < 2; ++v) {
-      {
-        Launch l(h, PM_K_PREP, h->s_in);
-        const PrepSeedMaps seeds{d_seed_l, d_seed_r};  // the seed copy rides along (one launch less)
-        launch_prep(h, pb, d_left, d_right, c, (size_t)cols, v, &seeds, h->s_in);
-        if (int rc = launch_check(h, "prep")) return rc;
-      }
-      {
-        Launch l(h, PM_K_PREP, h->s_in);
-        if (int rc = run_transpose(h, pb, c, v, h->s_in)) return rc;
-      }
-    }
-    for (int v = 0; v < 2; ++v) {
-      PlaneSet pv = pb;
-      pv.view_fixed = v;
-      if (int rc = seed_views(h, pv, c, v, v, h->s_in)) return rc;
-    }
-    h->need_seed[0] = h->need_seed[1] = false;  // done in the head: the view streams start with the first noise + cost
+    for (int v = 0; v < 2; ++v)
+      if (int rc = enqueue_head(h, pb, c, v, kHeadPrep | kHeadRideSeeds | kHeadLines, h->s_in)) return rc;
+    for (int v = 0; v < 2; ++v)
+      if (plan.self_seed[v])
+        if (int rc = enqueue_head(h, pb, c, v, kSeedAllStages, h->s_in, v)) return rc;
     for (int v = 0; v < 2; ++v)  // (the first fork records head_done on s_in, the second waits for the same record)
-      if (int rc = fork_stream(h, head_done, v == 0 ? h->s_in : nullptr, vs[v])) return rc;
-    if (int rc = run_views_on(h, pb, 2 * c, nullptr, vs)) return rc;
+      if (int rc = fork_stream(h, ev.head_done, v == 0 ? h->s_in : nullptr, vs[v])) return rc;
   } else {
     for (int v = 0; v < 2; ++v)
-      for (hipEvent_t e : {ready, ready2})
+      for (hipEvent_t e : {ev.ready, ev.ready2})
         if (int rc = fork_stream(h, e, nullptr, vs[v])) return rc;
-    const ViewSetup sb{d_left, d_right, d_seed_l, d_seed_r, c};
-    if (int rc = run_views_on(h, pb, 2 * c, &sb, vs)) return rc;
   }
+  if (int rc = run_views_on(h, pb, c, plan, plan.head_aside ? 0u : kHeadOfView, vs)) return rc;
   for (int v = 0; v < 2; ++v)
-    if (int rc = fork_stream(h, v_done[v], vs[v], h->s_out)) return rc;
-  {
-    Launch l(h, PM_K_FINALIZE, h->s_out);
-    launch_finalize(h, pb, d_disp_l, d_disp_r, c, h->s_out);
-    if (int rc = launch_check(h, "finalize")) return rc;
-  }
-  return PM_OK;
+    if (int rc = fork_stream(h, ev.v_done[v], vs[v], h->s_out)) return rc;
+  Launch l(h, PM_K_FINALIZE, h->s_out);
+  return launch_finalize(h, pb, d_disp_l, d_disp_r, c.n, h->s_out);
 }
 
 namespace {
 
-// A batch of pairs as chunks of pair_chunk() pairs, one after the other on the two view streams, every chunk's
+// A batch of pairs as chunks of plan.pair_chunk pairs, one after the other on the two view streams, every chunk's
 // cross-check on s_out as soon as its two views are through; the handle's stream joins s_out at the end of the call.
-int run_pairs_as_chunks(pm_handle* h, int n, const ViewSetup& vs, int rows, int cols, float* d_disp_l, float* d_disp_r) {
-  const int chunk = pair_chunk();
+int run_pairs_as_chunks(pm_handle* h, const MatchCall& c, const MatchPlan& plan, float* d_disp_l, float* d_disp_r) {
   if (int rc = view_streams_create(h)) return rc;
   if (int rc = seq_events_create(h)) return rc;
   PM_HIP(h, hipEventRecord(h->view_fork, h->stream));
-  const size_t px = (size_t)rows * cols;
+  const size_t px = (size_t)c.rows * c.cols;
   int rc = PM_OK;
-  for (int b = 0; b < n && rc == PM_OK; b += chunk) {
-    const int c = n - b < chunk ? n - b : chunk;
-    rc = seq_enqueue_chunk(h, b, c, vs.d_left + b * px, vs.d_right + b * px, rows, cols,
-                           vs.d_seed_l ? vs.d_seed_l + b * px : nullptr, vs.d_seed_r ? vs.d_seed_r + b * px : nullptr,
-                           d_disp_l + b * px, d_disp_r ? d_disp_r + b * px : nullptr, b == 0 ? h->view_fork : nullptr,
-                           nullptr, h->pipe[(size_t)b].v_done, h->pipe[(size_t)b].head_done);
+  for (int b = 0; b < c.n && rc == PM_OK; b += plan.pair_chunk) {
+    const int k = c.n - b < plan.pair_chunk ? c.n - b : plan.pair_chunk;
+    const pm_handle::PipeSlot& sl = h->pipe[(size_t)b];
+    rc = seq_enqueue_chunk(h, b, c.pairs(b, k), plan, d_disp_l + b * px, d_disp_r ? d_disp_r + b * px : nullptr,
+                           ChunkEvents{b == 0 ? h->view_fork.get() : nullptr, nullptr, sl.v_done, sl.head_done});
   }
   if (rc == PM_OK) return join_stream(h, h->s_out, h->out_join, h->stream);
   // a chunk failed part way: the handle's stream waits for whatever the side streams hold (a capture's forks are
@@ -842,14 +798,13 @@ int refuse_while_capturing(pm_handle* h, const char* what) {
 // Opens a capture on the handle's stream (thread-local mode).  Lazily created resources must exist before it starts:
 // creating streams, events or device memory is not capturable.
 int capture_open(pm_handle* h) {
-  if (h->params.left_right_check && h->params.mode == PM_MODE_SCALAR) {
+  const MatchPlan plan = match_plan(h, MatchCall());  // (what a capture needs depends on the handle's parameters only)
+  if (plan.need_view_events)
     if (int rc = view_streams_create(h)) return rc;
+  if (plan.need_slot_events)
     if (int rc = seq_events_create(h)) return rc;
-  }
-  if (h->params.sparse_init)
-    for (int i = 1; i < 2; ++i)
-      if (!h->seeds[i].eig)
-        if (int rc = alloc_seed_scratch(h, h->seeds[i], h->stream)) return rc;
+  if (plan.need_second_seed_scratch && !h->seeds[1].eig)
+    if (int rc = alloc_seed_scratch(h, h->seeds[1], h->stream)) return rc;
   h->cap_unjoined.clear();
   PM_HIP(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
   h->capturing = true;
@@ -880,60 +835,42 @@ int capture_close(pm_handle* h, GraphExec* exec, const char* what) {
   return PM_OK;
 }
 
-int match_device_impl(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
-                      const float* d_seed_l, const float* d_seed_r, float* d_disp_l, float* d_disp_r) {
-  if (!d_left || !d_right || !d_disp_l) {
+int match_device_impl(pm_handle* h, const MatchCall& c, float* d_disp_l, float* d_disp_r) {
+  if (!c.left || !c.right || !d_disp_l) {
     set_err(h, "pm_match_device: null image or output pointer");
     return PM_ERR_INVALID_ARG;
   }
-  if (int rc = check_size(h, rows, cols, n, /*match=*/!h->bgr)) return rc;
+  if (int rc = check_size(h, c.rows, c.cols, c.n, /*match=*/!c.bgr)) return rc;
   PM_HIP(h, hipSetDevice(h->device));
   prof_break_all(h);  // whatever sits between two calls on the streams is not a kernel's time
-  const int n_views = h->params.left_right_check ? 2 : 1;
-  if (n_views == 2 && !d_disp_r) {
+  const MatchPlan plan = match_plan(h, c);  // once per call: everything below enqueues what it says
+  if (plan.n_views == 2 && !d_disp_r) {
     set_err(h, "pm_match_device: disp_r required when left_right_check is set");
     return PM_ERR_INVALID_ARG;
   }
-  if (h->params.mode == PM_MODE_PLANES)
-    return planes_match(h, n, d_left, d_right, rows, cols, d_seed_l, d_seed_r, d_disp_l, d_disp_r);
-  if (int rc = ensure_noise(h, rows, cols)) return rc;
-  PlaneSet ps = plane_set(h, rows, cols, n_views);
-  // a missing seed map is computed on the device, as the reference's Match() does (inside run_views, so that
-  // the two views' seeders overlap on their own streams)
-  h->need_seed[0] = h->params.sparse_init && !d_seed_l;
-  h->need_seed[1] = h->params.sparse_init && !d_seed_r && n_views > 1;
-  // two views on their own streams: each stream prepares its own planes (run_views); otherwise here
-  const bool per_view_setup = n_views == 2 && view_streams_enabled() && !h->bgr;
-  if (per_view_setup && n > pair_chunk()) {
-    // chunks of pairs, each with its own cross-check launch (run_pairs_as_chunks)
-    const ViewSetup vs{d_left, d_right, d_seed_l, d_seed_r, n};
-    return run_pairs_as_chunks(h, n, vs, rows, cols, d_disp_l, d_disp_r);
+  if (plan.route == kRoutePlanes) return planes_match(h, c, plan, d_disp_l, d_disp_r);
+  if (int rc = ensure_noise(h, c.rows, c.cols)) return rc;
+  // chunks of pairs, each with its own cross-check launch
+  if (plan.route == kRouteChunks) return run_pairs_as_chunks(h, c, plan, d_disp_l, d_disp_r);
+  const PlaneSet ps = plane_set(h, c.rows, c.cols, plan.n_views);
+  // two views of gray images on their own streams: each stream runs its own head (run_views); otherwise once, here.  A
+  // missing seed map is computed on the device, as the reference's Match() does, behind the seed copy
+  if (plan.route != kRouteViewHeads)
+    if (int rc = enqueue_head(h, ps, c, -1, kHeadPrep | kHeadLines | kHeadSeedCopy, h->stream)) return rc;
+  if (int rc = run_views(h, ps, c, plan)) return rc;
+  Launch l(h, PM_K_FINALIZE, h->stream);
+  return launch_finalize(h, ps, d_disp_l, d_disp_r, c.n, h->stream);
+}
+
+// pm_match_device and pm_match_bgr_device behind their null-handle checks
+static int match_device_entry(pm_handle* h, const MatchCall& c, float* d_disp_l, float* d_disp_r) {
+  if (h->pipe_count > 0) {  // the frames of a sequence live in the same plane slots
+    set_err(h, "pm_match_device: pairs are in flight (pm_collect them first)");
+    return PM_ERR_BUSY;
   }
-  if (per_view_setup) {
-    const ViewSetup vs{d_left, d_right, d_seed_l, d_seed_r, n};
-    if (int rc = run_views(h, ps, n * n_views, &vs)) return rc;
-  } else {
-    {
-      Launch l(h, PM_K_PREP, h->stream);
-      launch_prep(h, ps, d_left, d_right, n, (size_t)cols, -1, nullptr, h->stream);
-    }
-    if (int rc = launch_check(h, "prep")) return rc;
-    {
-      Launch l(h, PM_K_PREP, h->stream);
-      if (int rc = run_transpose(h, ps, n, -1, h->stream)) return rc;
-    }
-    {
-      Launch l(h, PM_K_SEED, h->stream);
-      launch_seed(h, ps, d_seed_l, d_seed_r, n, -1, h->stream);
-    }
-    if (int rc = launch_check(h, "seed")) return rc;
-    if (int rc = run_views(h, ps, n * n_views)) return rc;
-  }
-  {
-    Launch l(h, PM_K_FINALIZE, h->stream);
-    launch_finalize(h, ps, d_disp_l, d_disp_r, n, h->stream);
-  }
-  return launch_check(h, "finalize");
+  const int rc = match_device_impl(h, c, d_disp_l, d_disp_r);
+  if (rc != PM_OK) abort_capture(h);  // a failed call must not leave the stream in capture mode
+  return rc;
 }
 
 }  // namespace eng
@@ -1188,13 +1125,17 @@ int pm_replay(pm_handle* h) {
 int pm_match_device(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
                     const float* d_seed_l, const float* d_seed_r, float* d_disp_l, float* d_disp_r) {
   if (!h) return PM_ERR_INVALID_ARG;
-  if (h->pipe_count > 0) {  // the frames of a sequence live in the same plane slots
-    set_err(h, "pm_match_device: pairs are in flight (pm_collect them first)");
-    return PM_ERR_BUSY;
-  }
-  const int rc = match_device_impl(h, n, d_left, d_right, rows, cols, d_seed_l, d_seed_r, d_disp_l, d_disp_r);
-  if (rc != PM_OK) abort_capture(h);  // a failed call must not leave the stream in capture mode
-  return rc;
+  return match_device_entry(h, MatchCall{d_left, d_right, d_seed_l, d_seed_r, n, rows, cols, nullptr}, d_disp_l, d_disp_r);
+}
+
+// the route of such a call, from the plan alone: no handle, no device (include/pm/testing.h)
+int pm_debug_match_plan(const pm_params* params, int n, int seed_l_given, int seed_r_given, int bgr, pm_debug_match_route* out) {
+  if (!params || !out || n < 1) return PM_ERR_INVALID_ARG;
+  const MatchPlan m = plan_match(*params, n, seed_l_given != 0, seed_r_given != 0, bgr != 0, match_knobs());
+  *out = pm_debug_match_route{m.route, m.n_views, {m.self_seed[0], m.self_seed[1]}, m.pair_chunk, m.head_aside,
+                              {m.lane_pairs[0], m.lane_pairs[1]}, m.seq_chunks, m.seq_hold, m.need_view_events,
+                              m.need_slot_events, m.need_second_seed_scratch};
+  return PM_OK;
 }
 
 int pm_match_view_device(pm_handle* h, const float* d_iml, const float* d_imr, const float* d_Gl, const float* d_Gr,
@@ -1234,26 +1175,20 @@ int pm_match_view_device(pm_handle* h, const float* d_iml, const float* d_imr, c
   PlaneSet ps = plane_set(h, rows, cols, 1);
   {
     Launch l(h, PM_K_PREP, h->stream);
-    launch_prep_view(h, ps, d_iml, d_imr, d_Gl, d_Gr, step / sizeof(float), h->stream);
+    if (int rc = launch_prep_view(h, ps, d_iml, d_imr, d_Gl, d_Gr, step / sizeof(float), h->stream)) return rc;
   }
-  if (int rc = launch_check(h, "prep_view")) return rc;
-  {
-    Launch l(h, PM_K_PREP, h->stream);
-    if (int rc = run_transpose(h, ps, 1, -1, h->stream)) return rc;
-  }
+  const MatchCall one{nullptr, nullptr, nullptr, nullptr, 1, rows, cols, nullptr};  // (the caller's float images went in above)
+  if (int rc = enqueue_head(h, ps, one, -1, kHeadLines, h->stream)) return rc;
   {
     Launch l(h, PM_K_SEED, h->stream);
-    launch_copy_disp_strided(h, ps, d_disp, disp_step / sizeof(float), 0, h->stream);
+    if (int rc = launch_copy_disp_strided(h, ps, d_disp, disp_step / sizeof(float), 0, h->stream)) return rc;
   }
-  if (int rc = launch_check(h, "seed")) return rc;
-  h->need_seed[0] = h->need_seed[1] = false;
   const hipStream_t own = h->stream;
   if (int rc = run_view_sets(h, &ps, &own, 1, 1)) return rc;
   {
     Launch l(h, PM_K_FINALIZE, h->stream);
-    launch_copy_disp_strided(h, ps, d_disp, disp_step / sizeof(float), 1, h->stream);
+    if (int rc = launch_copy_disp_strided(h, ps, d_disp, disp_step / sizeof(float), 1, h->stream)) return rc;
   }
-  if (int rc = launch_check(h, "copy out")) return rc;
   if (foreign) {
     PM_HIP(h, hipEventRecord(h->ext_join, h->stream));
     PM_HIP(h, hipStreamWaitEvent(user, h->ext_join, 0));
@@ -1352,7 +1287,11 @@ void plan_size(const pm_handle* h, int* max_rows, int* max_cols) {
   *max_cols = h->max_cols;
 }
 void** imaging_slot(pm_handle* h) { return &h->imaging_state; }
-void set_bgr_source(pm_handle* h, const pm::BgrSource* src) { h->bgr = src; }
+int match_bgr(pm_handle* h, int n, const pm::BgrSource& src, int rows, int cols, const float* d_seed_l,
+              const float* d_seed_r, float* d_disp_l, float* d_disp_r) {
+  return pm::eng::match_device_entry(h, pm::eng::MatchCall{src.left, src.right, d_seed_l, d_seed_r, n, rows, cols, &src},
+                                     d_disp_l, d_disp_r);
+}
 void set_error(pm_handle* h, const char* fmt, ...) {
   if (!h) return;
   va_list ap;

@@ -1,6 +1,7 @@
 // pm_handle.hpp -- the engine handle and the host-side helpers its translation units share.  Not part of the ABI.
 //
 //   pm_engine.hip        handle lifecycle, parameter checks, Match() on device buffers, capture / replay, profiling
+//     pm_match_plan.hpp  plan_match: the route of a Match() call -- which launches go onto which stream (no HIP, no handle)
 //   pm_launch.hip        the ONLY unit that includes the scalar-mode kernels (pm_kernels.hpp): one launch function each
 //   pm_sweeps.hip        the directional sweep kernels (pm_run3.hpp, pm_run2.hpp, pm_wave.hpp, pm_serial.hpp)
 //   pm_seed.hip          the device seeder (pm_seed.hpp)
@@ -34,6 +35,7 @@
 #include "pm_device.hpp"
 #include "pm_hipres.hpp"
 #include "pm_hostcopy.hpp"
+#include "pm_match_plan.hpp"
 #include "pm_planes_plan.hpp"
 #include "pm_seed_api.hpp"
 #include "pm_sweep_plan.hpp"
@@ -50,9 +52,22 @@ struct EventRec {
   int start_ref = -1;  // >= 0: the stop event of that record is this one's start (the launch before it on the same stream)
 };
 
+// One Match() call's inputs, as every level of the schedule takes them.
+struct MatchCall {
+  const uint8_t* left = nullptr;   // [n][rows][cols], tight (BGR input: only non-null; the prep stage reads `bgr`)
+  const uint8_t* right = nullptr;
+  const float* seed_l = nullptr;   // [n][rows][cols], or null: no seed maps for that view
+  const float* seed_r = nullptr;
+  int n = 0, rows = 0, cols = 0;
+  const BgrSource* bgr = nullptr;  // pm_match_bgr_device's source (k_prep_bgr), or null: 8-bit gray images
+  MatchCall pairs(int b, int c) const {  // pairs [b, b + c) of a gray call
+    const size_t o = (size_t)b * rows * cols;
+    return MatchCall{left + o, right + o, seed_l ? seed_l + o : nullptr, seed_r ? seed_r + o : nullptr, c, rows, cols, bgr};
+  }
+};
+
 }  // namespace eng
 }  // namespace pm
-
 
 struct pm_handle {
   pm_params params;
@@ -90,10 +105,9 @@ struct pm_handle {
   bool pl_on = false;
   pm::PlanesVariant pl_last;  // what the last pm_planes_begin / pm_planes_step launched (pm_debug_planes_last); all zero: nothing
 
-  // scratch of the device seeder (pm_seed.hpp), one set per (lane, view): index lane * 2 + view.  Set 0 exists from
-  // pm_create on, the others are allocated on first use (seeders of different views / lanes run side by side).
-  pm::SeedScratch seeds[8];
-  bool need_seed[2] = {false, false};  // set by pm_match_device: views whose seed map the device computes
+  // scratch of the device seeder (pm_seed.hpp), one set per view.  Set 0 exists from pm_create on, set 1 is allocated
+  // on first use (the seeders of the two views run side by side on their streams).
+  pm::SeedScratch seeds[2];
 
   // row-tiled mode (pm_tile_*)
   bool tile_on = false;
@@ -124,11 +138,8 @@ struct pm_handle {
     pm::Event v_done[2];  // view stream v: the chunk that STARTS at this slot has run
     pm::Event out_done;   // s_out: the slot's maps have arrived on the host
     uint64_t tag = 0;
-    int rows = 0, cols = 0;
     int state = 0;                  // 0 free, 1 uploaded and held for a partner, 2 enqueued
-    bool has_sl = false, has_sr = false;
-    const uint8_t *d_left = nullptr, *d_right = nullptr;  // where the chunk reads this frame (staging or caller memory)
-    const float *d_seed_l = nullptr, *d_seed_r = nullptr;
+    pm::eng::MatchCall in;          // where the chunk reads this frame (staging or caller memory), n = 1
     float *d_out_l = nullptr, *d_out_r = nullptr;         // where the cross-check writes (staging or caller memory)
     bool device_io = false;         // pm_submit_device: no copies at all
     bool ready_in = false;          // pm_submit_device_after: in_done stands for the caller's "inputs are complete" event
@@ -160,8 +171,6 @@ struct pm_handle {
   pm::Event in_join;   // s_in -> the handle's stream (only when a capture is ended with the head stream unjoined)
   void* imaging_state = nullptr;  // pm_imaging_state.hpp's, released by pm_imaging.hip (pm_internal.hpp)
   pm::DevBuf<void> texmask_scratch;  // pm_foreground_texture_mask: four byte planes, allocated on first use
-  // pm_match_bgr_device: the next Match reads enhanced BGR inputs through k_prep_bgr instead of 8-bit gray images
-  const pm::BgrSource* bgr = nullptr;
   pm::GraphExec graph_exec;  // pm_capture_* / pm_replay
   bool capturing = false;
   bool no_tiled = false;        // PM_NO_TILED (experiment knob), read once by pm_create
@@ -213,19 +222,8 @@ constexpr size_t kSlackPk16 = 128;   // packed 16-bit planes
 // not that slack: spare bytes behind the tight u8 staging block (left, right) -- a guard, never cleared, nothing reads it
 constexpr size_t kStagingPadBytes = 64;
 
-// Every stream of the engine is created through this.  PM_STREAM_PRIO = "main,view,copy,lane" (read once; one number
-// = all four): the priority class of the handle's stream, the second view's stream, the upload / download streams and
-// the lanes' streams -- 1 high, 0 default, -1 low.  Default "0,1,0,1": the streams the views of a pair and the
-// pipelines of a batch run on are HIGH, not for the priority but because streams of different classes never share a
-// hardware queue and a class of their own keeps them off the queues of whatever else the process creates (with
-// default-priority streams, where a stream lands depends on the process's other queue-owning streams, and some
-// constellations put both views of a pair on ONE queue: 384 -> 275 pairs/s; taking the queues in a fixed order in
-// pm_create does not prevent that -- the runtime reassigns).  The handle's own stream and the copy streams stay
-// default: copies on streams of a non-default class are slower (pm_match_u8 x 4: 12.3 -> 14.4 ms).  The price:
-// default-priority streams that work side by side slow down while a stream of another class exists in the process
-// (pm_submit_u8's upload / download streams beside the compute stream: 343 -> 280-300 pairs/s; eight band handles on
-// one device 49 -> 117 ms); "0" restores one class for everything (tools/multi_handle.py, batch_after.py, pipe_timing.py).
-enum StreamKind { kStreamMain = 0, kStreamView = 1, kStreamCopy = 2, kStreamLane = 3 };
+// Every stream of the engine is created through this; the policy and its measurements: pm_engine.hip::create_stream.
+enum StreamKind { kStreamMain = 0, kStreamView = 1, kStreamCopy = 2 };
 hipError_t create_stream(hipStream_t* s, int kind, int prio_class);
 int create_handle_streams(pm_handle* h);  // the handle's four streams, together (pm_engine.hip)
 
@@ -240,7 +238,6 @@ inline hipError_t create_event_pair(Event& a, Event& b) {
   return hipSuccess;
 }
 
-// Brackets the launches of one kernel class with a pair of events while the handle is profiling.
 // While the handle is profiling, the launches of one kernel class are bracketed by events on the stream they go to.  An
 // in-stream event before a launch fires when the launch in front of it has finished: the stop event of the previous
 // bracket on the same stream IS the start of the next one, so a chain of launches costs one event per launch, not two
@@ -261,7 +258,7 @@ struct Launch {
   hipStream_t stream;
   bool timed;
   int rec = -1;
-  Launch(pm_handle* h_, int k, hipStream_t s) : h(h_), klass(k), stream(s), timed(h_->profiling) {
+  Launch(pm_handle* h_, int k, hipStream_t s, bool on = true) : h(h_), klass(k), stream(s), timed(on && h_->profiling) {
     if (!timed) return;
     if (h->ev_used == (int)h->ev_pool.size()) {
       if ((int)h->ev_pool.size() >= kMaxEvents) {
@@ -311,81 +308,91 @@ int capture_open(pm_handle* h);                                             // p
 int capture_close(pm_handle* h, GraphExec* exec, const char* what);  // *exec: empty
 bool pair_planes_wanted(const pm_handle* h);
 int pair_planes_alloc(pm_handle* h, hipStream_t stream);
-int match_device_impl(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
-                      const float* d_seed_l, const float* d_seed_r, float* d_disp_l, float* d_disp_r);
+MatchPlan match_plan(const pm_handle* h, const MatchCall& c);  // plan_match with the build's knobs (pm_match_plan.hpp)
+int match_device_impl(pm_handle* h, const MatchCall& c, float* d_disp_l, float* d_disp_r);
+// The HEAD of a view: what runs in front of its first noise + cost.  `steps` selects, in the order they are enqueued:
+enum : unsigned {
+  kHeadPrep = 1u << 8,       // images + gradients (k_prep / k_prep_bgr) of c's pairs
+  kHeadRideSeeds = 1u << 9,  // with kHeadPrep: the seed copy rides along (one launch less)
+  kHeadLines = 1u << 10,     // transposed copies + line planes (run_transpose)
+  kHeadSeedCopy = 1u << 11,  // the seed maps (null: zeros) into the disparity planes, a launch of its own
+  kHeadUntimed = 1u << 12,   // no profiling brackets (the stage entry points, pm_tile_begin)
+};
+// ... and, in the low bits, the seeder stages (1 << stage; kSeedAllStages: the whole seeder in ONE bracket) of pairs
+// [pair0, pair0 + n_pairs) (n_pairs < 0: all of c's) with scratch set `scratch`.  view >= 0: that view only; -1: both
+// (not the seeder).  Every step sits in its own bracket; enqueue only.
+int enqueue_head(pm_handle* h, const PlaneSet& ps, const MatchCall& c, int view, unsigned steps, hipStream_t stream,
+                 int scratch = 0, int pair0 = 0, int n_pairs = -1);
 // view streams, chunk events, fork / join, and one chunk of a batch / frame sequence (pm_engine.hip)
 int view_streams_create(pm_handle* h);
 PlaneSet plane_set_of_pair(const PlaneSet& ps, int b);  // the plane set of the pairs from b on
 int fork_stream(pm_handle* h, hipEvent_t ev, hipStream_t from, hipStream_t onto);
 int join_stream(pm_handle* h, hipStream_t from, hipEvent_t ev, hipStream_t onto);
 int seq_events_create(pm_handle* h);
-int pair_chunk();
-bool seq_pipelined(const pm_handle* h);
-int seq_enqueue_chunk(pm_handle* h, int b, int c, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
-                      const float* d_seed_l, const float* d_seed_r, float* d_disp_l, float* d_disp_r, hipEvent_t ready,
-                      hipEvent_t ready2, const Event v_done[2], hipEvent_t head_done);
+// the events of one chunk: `ready` / `ready2` (null: none) stand for its inputs, v_done[2] and head_done are recorded
+struct ChunkEvents {
+  hipEvent_t ready, ready2;
+  const Event* v_done;
+  hipEvent_t head_done;
+};
+int seq_enqueue_chunk(pm_handle* h, int b, const MatchCall& c, const MatchPlan& plan, float* d_disp_l, float* d_disp_r,
+                      const ChunkEvents& ev);
 SeedParams seed_params(const pm_params& p);
 int alloc_seed_scratch(pm_handle* h, SeedScratch& sc, hipStream_t stream);
 // SparseInit (or Patchmatch::Initialize(.., 1)) for view `view` of pair `b` straight into its disparity plane
 int run_sparse_init(pm_handle* h, const PlaneSet& ps, int b, int view, int scratch, unsigned stages, hipStream_t stream);
 
 // ---- pm_launch.hip: one function per scalar-mode kernel, enqueued on `stream` (the last parameter) ---------------
-// k_prep, or k_prep_bgr when the call came in through pm_match_bgr_device (the gray images are then never stored)
-// seeds != null: the launch also copies the seed maps (null members = all background) into the disparity planes of its
-// view(s), i.e. what launch_seed does
-struct PrepSeedMaps {
-  const float* l;
-  const float* r;
-};
+// Every launch function returns the status of its launch (launch_check).
+// k_prep on c's images, or k_prep_bgr on c.bgr (the gray images are then never stored); ride_seeds: the launch also
+// copies c's seed maps (null = all background) into the disparity planes of its view(s), i.e. what launch_seed does
 // view >= 0: that view only; view -1: both
-void launch_prep(pm_handle* h, const PlaneSet& ps, const uint8_t* d_left, const uint8_t* d_right, int n, size_t stride,
-                 int view, const PrepSeedMaps* seeds, hipStream_t stream);
-void launch_prep_view(pm_handle* h, const PlaneSet& ps, const float* d_iml, const float* d_imr, const float* d_Gl,
-                      const float* d_Gr, size_t stride, hipStream_t stream);
+int launch_prep(pm_handle* h, const PlaneSet& ps, const MatchCall& c, int view, bool ride_seeds, hipStream_t stream);
+int launch_prep_view(pm_handle* h, const PlaneSet& ps, const float* d_iml, const float* d_imr, const float* d_Gl,
+                    const float* d_Gr, size_t stride, hipStream_t stream);
 // transposed copies + line-triple / quad planes of n pairs (run by every path that ran a prep kernel);
 // view >= 0: the planes of that view only (per-view streams: each stream derives its own planes)
 int run_transpose(pm_handle* h, const PlaneSet& ps, int n, int view, hipStream_t stream);
-void launch_seed(pm_handle* h, const PlaneSet& ps, const float* d_seed_l, const float* d_seed_r, int n, int view,
-                 hipStream_t stream);
+int launch_seed(pm_handle* h, const PlaneSet& ps, const float* d_seed_l, const float* d_seed_r, int n, int view,
+                hipStream_t stream);
 // noise + clamp + cost of the current disparity (amount < 0: cost only); RemoveBackground / MaskBackground
-void launch_noise_cost(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const Interior& in, float amount,
-                       int slots, int keep_zero, hipStream_t stream);
-void launch_noise_only(pm_handle* h, const PlaneSet& ps, const CostParams& cp, float amount, hipStream_t stream);
-void launch_background(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const Interior& in, float factor,
-                       int cached, int slots, hipStream_t stream);
+int launch_noise_cost(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const Interior& in, float amount,
+                      int slots, int keep_zero, hipStream_t stream);
+int launch_noise_only(pm_handle* h, const PlaneSet& ps, const CostParams& cp, float amount, hipStream_t stream);
+int launch_background(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const Interior& in, float factor,
+                      int cached, int slots, hipStream_t stream);
 // amp: the iteration's noise amplitude (1e30f: none); ran (may be null): the variant launched (pm_sweep_plan.hpp), left
 // as it is where the geometry has nothing to sweep
 // hint: the segment boundaries of the run engine (pm_sweep_defs.hpp); the default is the equal split
 int run_sweep(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, float amp,
               hipStream_t stream, SweepVariant* ran = nullptr, const SweepHint& hint = SweepHint());
-void launch_finalize(pm_handle* h, const PlaneSet& ps, float* d_disp_l, float* d_disp_r, int n, hipStream_t stream);
-void launch_mask_occlusions(pm_handle* h, float* d_disp_l, const float* d_disp_r, int rows, int cols,
-                            hipStream_t stream);
-void launch_state_row(pm_handle* h, const PlaneSet& ps, int r, float* d_buf, int to_buf, hipStream_t stream);
-void launch_restore_cols(pm_handle* h, const PlaneSet& ps, const float* snap_disp, const float* snap_cost,
-                         const int* d_mask, hipStream_t stream);
-void launch_tile_round(pm_handle* h, const PlaneSet& ps, const float* snap_disp, const float* snap_cost,
-                       const float* d_incoming, const float* d_used, float* d_used_next, int* d_mask, int pred_r,
-                       int y_lo, int y_hi, hipStream_t stream);
-void launch_state_row_moved(pm_handle* h, const PlaneSet& ps, int r, const float* d_ref, int* d_flag,
-                            hipStream_t stream);
-void launch_tile_presweep(pm_handle* h, const PlaneSet& ps, float* snap_disp, float* snap_cost, const float* d_row,
-                          int pred_r, hipStream_t stream);
+int launch_finalize(pm_handle* h, const PlaneSet& ps, float* d_disp_l, float* d_disp_r, int n, hipStream_t stream);
+int launch_mask_occlusions(pm_handle* h, float* d_disp_l, const float* d_disp_r, int rows, int cols,
+                           hipStream_t stream);
+int launch_state_row(pm_handle* h, const PlaneSet& ps, int r, float* d_buf, int to_buf, hipStream_t stream);
+int launch_restore_cols(pm_handle* h, const PlaneSet& ps, const float* snap_disp, const float* snap_cost,
+                        const int* d_mask, hipStream_t stream);
+int launch_tile_round(pm_handle* h, const PlaneSet& ps, const float* snap_disp, const float* snap_cost,
+                      const float* d_incoming, const float* d_used, float* d_used_next, int* d_mask, int pred_r,
+                      int y_lo, int y_hi, hipStream_t stream);
+int launch_state_row_moved(pm_handle* h, const PlaneSet& ps, int r, const float* d_ref, int* d_flag,
+                           hipStream_t stream);
+int launch_tile_presweep(pm_handle* h, const PlaneSet& ps, float* snap_disp, float* snap_cost, const float* d_row,
+                         int pred_r, hipStream_t stream);
 // rows x cols floats from tight device memory into page-locked host memory (its DEVICE address), row stride in floats
-void launch_download(pm_handle* h, float* dst_dev, size_t dst_step_floats, const float* d_src, int rows, int cols,
-                     hipStream_t stream);
-void launch_upload(pm_handle* h, float* d_dst, const float* src_dev, int words, hipStream_t stream);
+int launch_download(pm_handle* h, float* dst_dev, size_t dst_step_floats, const float* d_src, int rows, int cols,
+                    hipStream_t stream);
+int launch_upload(pm_handle* h, float* d_dst, const float* src_dev, int words, hipStream_t stream);
 // tight caller planes <-> the planes of view 0; which: 0 = disparity, 1 = gradient magnitude, 2 = unit noise, 3 = cost
 // (copy_in: 0 and 3 only)
-void launch_copy_in(pm_handle* h, const PlaneSet& ps, const float* d_src, int which, hipStream_t stream);
-void launch_copy_out(pm_handle* h, const PlaneSet& ps, float* d_dst, int which, hipStream_t stream);
-void launch_copy_disp_strided(pm_handle* h, const PlaneSet& ps, float* d_buf, size_t stride, int to_buf,
-                              hipStream_t stream);
+int launch_copy_in(pm_handle* h, const PlaneSet& ps, const float* d_src, int which, hipStream_t stream);
+int launch_copy_out(pm_handle* h, const PlaneSet& ps, float* d_dst, int which, hipStream_t stream);
+int launch_copy_disp_strided(pm_handle* h, const PlaneSet& ps, float* d_buf, size_t stride, int to_buf,
+                             hipStream_t stream);
 
 // ---- pm_planes_host.hip ------------------------------------------------------------------------------------------
 int planes_alloc(pm_handle* h, hipStream_t stream);
-int planes_match(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
-                 const float* d_seed_l, const float* d_seed_r, float* d_disp_l, float* d_disp_r);
+int planes_match(pm_handle* h, const MatchCall& c, const MatchPlan& plan, float* d_disp_l, float* d_disp_r);
 
 }  // namespace eng
 }  // namespace pm

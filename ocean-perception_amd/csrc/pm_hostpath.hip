@@ -56,8 +56,7 @@ int download_plane(pm_handle* h, void* dst, size_t step, const void* d_src, size
   const size_t tstep = *direct ? step : row_bytes;
   char* dev = (tstep % sizeof(float)) == 0 ? host_dev_address(h, target, span_bytes(rows, tstep, row_bytes)) : nullptr;
   if (dev) {
-    launch_download(h, (float*)dev, tstep / sizeof(float), (const float*)d_src, rows, (int)(row_bytes / sizeof(float)), stream);
-    return launch_check(h, "download");
+    return launch_download(h, (float*)dev, tstep / sizeof(float), (const float*)d_src, rows, (int)(row_bytes / sizeof(float)), stream);
   }
   if (tstep == row_bytes)
     PM_HIP(h, hipMemcpyAsync(target, d_src, row_bytes * (size_t)rows, hipMemcpyDeviceToHost, stream));
@@ -88,7 +87,7 @@ PinnedSlot pinned_slot(pm_handle* h, int slot, size_t px) {
 int pipe_init(pm_handle* h) {
   if (!h->copy_pool) h->copy_pool.reset(new pm::CopyPool());
   if (int rc = seq_events_create(h)) return rc;
-  if (seq_pipelined(h))
+  if (match_plan(h, MatchCall()).seq_chunks)
     if (int rc = view_streams_create(h)) return rc;
   return PM_OK;
 }
@@ -99,7 +98,7 @@ int pipe_init(pm_handle* h) {
 int enqueue_frames(pm_handle* h, int b, int c) {
   pm_handle::PipeSlot& f0 = h->pipe[(size_t)b];
   const pm_handle::PipeSlot& fl = h->pipe[(size_t)(b + c - 1)];
-  const int rows = f0.rows, cols = f0.cols;
+  const int rows = f0.in.rows, cols = f0.in.cols;
   const size_t px = (size_t)rows * cols;
   const bool lr = h->params.left_right_check != 0;
   // host frames: the later frame's upload (s_in runs in order).  Device-resident frames: the caller's "inputs are
@@ -107,9 +106,11 @@ int enqueue_frames(pm_handle* h, int b, int c) {
   // of both views and the head
   hipEvent_t ready = !f0.device_io ? fl.in_done : f0.ready_in ? f0.in_done : nullptr;
   hipEvent_t ready2 = (f0.device_io && c > 1 && fl.ready_in) ? fl.in_done : nullptr;
-  if (seq_pipelined(h)) {
-    if (int rc = seq_enqueue_chunk(h, b, c, f0.d_left, f0.d_right, rows, cols, f0.d_seed_l, f0.d_seed_r, f0.d_out_l,
-                                   f0.d_out_r, ready, ready2, f0.v_done, f0.head_done))
+  MatchCall call = f0.in;  // the chunk's frames are neighbours in memory (can_gang): one call on c pairs
+  call.n = c;
+  const MatchPlan plan = match_plan(h, call);
+  if (plan.seq_chunks) {
+    if (int rc = seq_enqueue_chunk(h, b, call, plan, f0.d_out_l, f0.d_out_r, ChunkEvents{ready, ready2, f0.v_done, f0.head_done}))
       return rc;
   } else {
     if (ready) PM_HIP(h, hipStreamWaitEvent(h->stream, ready, 0));
@@ -117,11 +118,9 @@ int enqueue_frames(pm_handle* h, int b, int c) {
     // All frames of the chunk through every launch together (plane mode: two lanes on two streams, each filling the
     // other's launch tails, pm_planes_host.hip::planes_match).  They are neighbours in memory: a chunk of more than one
     // frame is either all pairs of pm_match_batch_u8 (ring slots 0 .. n - 1) or a held frame and the partner can_gang
-    // accepted -- and enqueue_or_hold holds a frame only if seq_pipelined(h) or in plane mode without bgr, so a scalar
-    // sequence reaches this branch one frame at a time.
-    if (int rc = match_device_impl(h, c, f0.d_left, f0.d_right, rows, cols, f0.d_seed_l, f0.d_seed_r, f0.d_out_l,
-                                   lr ? f0.d_out_r : nullptr))
-      return rc;
+    // accepted -- and enqueue_or_hold holds a frame only where the plan says so (MatchPlan::seq_hold: chunks, or plane
+    // mode), so a scalar sequence reaches this branch one frame at a time.
+    if (int rc = match_device_impl(h, call, f0.d_out_l, lr ? f0.d_out_r : nullptr)) return rc;
     PM_HIP(h, hipEventRecord(f0.v_done[0], h->stream));
     PM_HIP(h, hipStreamWaitEvent(h->s_out, f0.v_done[0], 0));
   }
@@ -160,12 +159,13 @@ int held_slot(const pm_handle* h) {
 
 // two frames can be advanced through every launch together if they are neighbours in device memory
 bool can_gang(const pm_handle* h, const pm_handle::PipeSlot& a, const pm_handle::PipeSlot& b, int sa, int sb) {
-  if (sb != sa + 1 || a.rows != b.rows || a.cols != b.cols || a.has_sl != b.has_sl || a.has_sr != b.has_sr ||
+  const MatchCall &fa = a.in, &fb = b.in;
+  if (sb != sa + 1 || fa.rows != fb.rows || fa.cols != fb.cols || !fa.seed_l != !fb.seed_l || !fa.seed_r != !fb.seed_r ||
       a.device_io != b.device_io)
     return false;
-  const size_t px = (size_t)a.rows * a.cols;
-  return b.d_left == a.d_left + px && b.d_right == a.d_right + px && (!a.has_sl || b.d_seed_l == a.d_seed_l + px) &&
-         (!a.has_sr || b.d_seed_r == a.d_seed_r + px) && b.d_out_l == a.d_out_l + px &&
+  const size_t px = (size_t)fa.rows * fa.cols;
+  return fb.left == fa.left + px && fb.right == fa.right + px && (!fa.seed_l || fb.seed_l == fa.seed_l + px) &&
+         (!fa.seed_r || fb.seed_r == fa.seed_r + px) && b.d_out_l == a.d_out_l + px &&
          (!h->params.left_right_check || b.d_out_r == a.d_out_r + px);
 }
 
@@ -173,8 +173,7 @@ bool can_gang(const pm_handle* h, const pm_handle::PipeSlot& a, const pm_handle:
 // anyway and a neighbour slot exists
 int enqueue_or_hold(pm_handle* h, int slot) {
   // (plane mode is not pipelined over the view streams, but two of its frames make a batch of two lanes)
-  const bool gangs = seq_pipelined(h) || (h->params.mode == PM_MODE_PLANES && !h->bgr);
-  const bool hold = gangs && pair_chunk() >= 2 && slot + 1 < h->max_batch && device_busy(h);
+  const bool hold = match_plan(h, MatchCall()).seq_hold && slot + 1 < h->max_batch && device_busy(h);
   return hold ? PM_OK : enqueue_frames(h, slot, 1);
 }
 
@@ -233,16 +232,11 @@ int stage_frame(pm_handle* h, int slot, const SubmitArgs& a, bool zero_l, bool z
   const size_t px = (size_t)rows * cols;
   const size_t frow = sizeof(float) * (size_t)cols;
   sl.tag = a.tag;
-  sl.rows = rows;
-  sl.cols = cols;
   sl.device_io = a.device_io;
   sl.ready_in = a.ready != nullptr;
   sl.direct_l = sl.direct_r = false;
   if (a.device_io) {
-    sl.d_left = a.left;
-    sl.d_right = a.right;
-    sl.d_seed_l = a.seed_l;
-    sl.d_seed_r = a.seed_r;
+    sl.in = MatchCall{a.left, a.right, a.seed_l, a.seed_r, 1, rows, cols, nullptr};
     sl.d_out_l = a.out_l;
     sl.d_out_r = a.out_r;
     sl.out_l = sl.out_r = nullptr;
@@ -273,17 +267,12 @@ int stage_frame(pm_handle* h, int slot, const SubmitArgs& a, bool zero_l, bool z
       PM_HIP(h, hipMemsetAsync(dsr, 0, sizeof(float) * px, h->s_in));
     }
     PM_HIP(h, hipEventRecord(sl.in_done, h->s_in));
-    sl.d_left = dl8;
-    sl.d_right = dr8;
-    sl.d_seed_l = a.seed_l || zero_l ? dsl : nullptr;
-    sl.d_seed_r = a.seed_r || zero_r ? dsr : nullptr;
+    sl.in = MatchCall{dl8, dr8, a.seed_l || zero_l ? dsl : nullptr, a.seed_r || zero_r ? dsr : nullptr, 1, rows, cols, nullptr};
     sl.d_out_l = h->st_disp_l + (size_t)slot * px;
     sl.d_out_r = h->st_disp_r + (size_t)slot * px;
     sl.out_l = a.out_l;
     sl.out_r = a.out_r;
   }
-  sl.has_sl = sl.d_seed_l != nullptr;
-  sl.has_sr = sl.d_seed_r != nullptr;
   sl.out_step = sl.out_l ? a.out_step : 0;
   sl.state = 1;
   return PM_OK;
@@ -296,10 +285,11 @@ int finish_frame(pm_handle* h, int slot, float* out_l, float* out_r, size_t out_
   f.state = 0;
   PM_HIP(h, hipEventSynchronize(f.out_done));
   if (!f.device_io) {
-    const size_t frow = sizeof(float) * (size_t)f.cols;
-    const PinnedSlot ps = pinned_slot(h, slot, (size_t)f.rows * f.cols);
-    if (!f.direct_l) h->copy_pool->Copy2D(out_l, out_step, ps.dl, frow, frow, f.rows);
-    if (h->params.left_right_check && !f.direct_r) h->copy_pool->Copy2D(out_r, out_step, ps.dr, frow, frow, f.rows);
+    const int rows = f.in.rows, cols = f.in.cols;
+    const size_t frow = sizeof(float) * (size_t)cols;
+    const PinnedSlot ps = pinned_slot(h, slot, (size_t)rows * cols);
+    if (!f.direct_l) h->copy_pool->Copy2D(out_l, out_step, ps.dl, frow, frow, rows);
+    if (h->params.left_right_check && !f.direct_r) h->copy_pool->Copy2D(out_r, out_step, ps.dr, frow, frow, rows);
   }
   return PM_OK;
 }
@@ -331,7 +321,7 @@ int submit_impl(pm_handle* h, SubmitArgs a, const char* what) {
   }
   if (h->pipe_count > 0) {
     const pm_handle::PipeSlot& first = h->pipe[(size_t)h->pipe_head];
-    if (first.rows != a.rows || first.cols != a.cols) {  // the frames in flight share the noise table and the slot layout
+    if (first.in.rows != a.rows || first.in.cols != a.cols) {  // the frames in flight share the noise table and the slot layout
       set_err(h, "%s: image size changed with pairs in flight; collect them first", what);
       return PM_ERR_BUSY;
     }
@@ -442,7 +432,8 @@ int pm_match_batch_u8(pm_handle* h, int n, const uint8_t* const* left, const uin
     if (int rc = ensure_noise(h, rows, cols)) return rc;
   const size_t frow = sizeof(float) * (size_t)cols;
   // handles that cannot run as chunks (plane mode, one view only) take all pairs as one
-  const int chunk = seq_pipelined(h) ? pair_chunk() : n;
+  const MatchPlan plan = match_plan(h, MatchCall());
+  const int chunk = plan.seq_chunks ? plan.pair_chunk : n;
   h->pipe_head = 0;
   int rc = PM_OK;
   for (int b = 0; b < n && rc == PM_OK; b += chunk) {
@@ -535,8 +526,7 @@ int pm_match_u8(pm_handle* h, const uint8_t* left, const uint8_t* right, int row
     h->copy_pool->Copy2D(ps.r, (size_t)cols, right, image_step, (size_t)cols, rows);
     d_right = h->st_left + px;
     const int words = (int)(2 * px / sizeof(float));
-    launch_upload(h, (float*)h->st_left.get(), (const float*)slab_dev, words, h->stream);
-    if (int rc = launch_check(h, "upload")) return rc;
+    if (int rc = launch_upload(h, (float*)h->st_left.get(), (const float*)slab_dev, words, h->stream)) return rc;
   } else {
     if (int rc = upload_plane(h, h->st_left, left, image_step, (size_t)cols, rows, ps.l, h->stream)) return rc;
     if (int rc = upload_plane(h, h->st_right, right, image_step, (size_t)cols, rows, ps.r, h->stream)) return rc;
@@ -546,9 +536,9 @@ int pm_match_u8(pm_handle* h, const uint8_t* left, const uint8_t* right, int row
   if (seed_r)
     if (int rc = upload_plane(h, h->st_seed_r, seed_r, seed_step, frow, rows, ps.sr, h->stream)) return rc;
   HP(mark(2));
-  if (int rc = match_device_impl(h, 1, h->st_left, d_right, rows, cols, seed_l ? h->st_seed_l : nullptr,
-                               seed_r ? h->st_seed_r : nullptr, h->st_disp_l, lr ? h->st_disp_r : nullptr))
-    return rc;
+  const MatchCall call{h->st_left, d_right, seed_l ? h->st_seed_l.get() : nullptr, seed_r ? h->st_seed_r.get() : nullptr, 1, rows,
+                       cols, nullptr};
+  if (int rc = match_device_impl(h, call, h->st_disp_l, lr ? h->st_disp_r.get() : nullptr)) return rc;
   HP(mark(3));
   // the left map is unpacked into the caller's buffer while the right one is still on the bus
   if (!h->left_out) PM_HIP(h, create_event_pair(h->left_out, h->right_out));
@@ -630,7 +620,7 @@ int pm_collect(pm_handle* h, float* disp_l, float* disp_r, size_t disp_step, uin
   }
   const bool lr = h->params.left_right_check != 0;
   pm_handle::PipeSlot& sl = h->pipe[(size_t)h->pipe_head];
-  const size_t frow = sizeof(float) * (size_t)sl.cols;
+  const size_t frow = sizeof(float) * (size_t)sl.in.cols;
   // where the maps go: the buffers bound at submit, else the ones given here (a device-resident frame has neither)
   float* out_l = sl.out_l ? sl.out_l : disp_l;
   float* out_r = sl.out_l ? sl.out_r : disp_r;
@@ -686,9 +676,8 @@ int stage_prep(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows
   PM_HIP(h, hipMemcpyAsync(h->st_left, left, px, hipMemcpyHostToDevice, h->stream));
   PM_HIP(h, hipMemcpyAsync(h->st_right, right ? right : left, px, hipMemcpyHostToDevice, h->stream));
   const PlaneSet ps = plane_set(h, rows, cols, 1);
-  launch_prep(h, ps, h->st_left, h->st_right, 1, (size_t)cols, -1, nullptr, h->stream);
-  if (int rc = launch_check(h, "prep")) return rc;
-  if (int rc = run_transpose(h, ps, 1, -1, h->stream)) return rc;
+  const MatchCall call{h->st_left, h->st_right, nullptr, nullptr, 1, rows, cols, nullptr};
+  if (int rc = enqueue_head(h, ps, call, -1, kHeadPrep | kHeadLines | kHeadUntimed, h->stream)) return rc;
   *ps_out = ps;
   return PM_OK;
 }
@@ -698,14 +687,12 @@ int stage_disp_in(pm_handle* h, const PlaneSet& ps, const float* disp, int which
   const size_t px = (size_t)ps.rows * ps.cols;
   float* st = which == 3 ? h->st_disp_r.get() : h->st_disp_l.get();
   PM_HIP(h, hipMemcpyAsync(st, disp, sizeof(float) * px, hipMemcpyHostToDevice, h->stream));
-  launch_copy_in(h, ps, st, which, h->stream);
-  return launch_check(h, "copy_in");
+  return launch_copy_in(h, ps, st, which, h->stream);
 }
 
 int stage_out(pm_handle* h, const PlaneSet& ps, float* dst, int which) {
   const size_t px = (size_t)ps.rows * ps.cols;
-  launch_copy_out(h, ps, h->st_disp_l, which, h->stream);
-  if (int rc = launch_check(h, "copy_out")) return rc;
+  if (int rc = launch_copy_out(h, ps, h->st_disp_l, which, h->stream)) return rc;
   PM_HIP(h, hipMemcpyAsync(dst, h->st_disp_l, sizeof(float) * px, hipMemcpyDeviceToHost, h->stream));
   PM_HIP(h, hipStreamSynchronize(h->stream));
   return PM_OK;
@@ -767,8 +754,7 @@ int pm_add_noise(pm_handle* h, float* disp, int rows, int cols, float amount) {
   const PlaneSet ps = plane_set(h, rows, cols, 1);
   if (int rc = stage_disp_in(h, ps, disp)) return rc;
   CostParams cp = cost_params(h->params, 3, 3);
-  launch_noise_only(h, ps, cp, amount, h->stream);
-  if (int rc = launch_check(h, "noise")) return rc;
+  if (int rc = launch_noise_only(h, ps, cp, amount, h->stream)) return rc;
   return stage_out(h, ps, disp, 0);
 }
 
@@ -798,8 +784,7 @@ int propagate_impl(pm_handle* h, const char* who, const uint8_t* left, const uin
   if (int rc = stage_disp_in(h, ps, disp)) return rc;
   const CostParams cp = cost_params(h->params, patch_w, patch_h);
   const Interior in = interior(h->params, rows, cols, cp.pw, cp.ph);
-  launch_noise_cost(h, ps, cp, in, -1.f, 1, 0, h->stream);
-  if (int rc = launch_check(h, "cost")) return rc;
+  if (int rc = launch_noise_cost(h, ps, cp, in, -1.f, 1, 0, h->stream)) return rc;
   // hints (pm_debug_propagate_hinted): per pass, with the caller's stop-bit plane in view 0's and that plane handed back
   if (stops && ps.stops)
     PM_HIP(h, hipMemcpy2DAsync(ps.stops, (size_t)ps.pitch, stops, (size_t)cols, (size_t)cols, (size_t)rows,
@@ -970,8 +955,7 @@ int remove_background_impl(pm_handle* h, const char* who, const uint8_t* left, c
     if (int rc = stage_disp_in(h, ps, cost, 3)) return rc;
   const CostParams cp = cost_params(h->params, patch_w, patch_h);
   const Interior in = interior(h->params, rows, cols, cp.pw, cp.ph);
-  launch_background(h, ps, cp, in, factor, cost ? 1 : 0, 1, h->stream);
-  if (int rc = launch_check(h, "background")) return rc;
+  if (int rc = launch_background(h, ps, cp, in, factor, cost ? 1 : 0, 1, h->stream)) return rc;
   return stage_out(h, ps, disp, 0);
 }
 }  // namespace
@@ -1018,8 +1002,8 @@ int pm_debug_noise_cost(pm_handle* h, const uint8_t* left, const uint8_t* right,
   if (cost)
     if (int rc = stage_disp_in(h, ps, cost, 3)) return rc;
   const CostParams cp = cost_params(h->params, patch_w, patch_h);
-  launch_noise_cost(h, ps, cp, interior(h->params, rows, cols, cp.pw, cp.ph), amount, 1, keep_zero, h->stream);
-  if (int rc = launch_check(h, "noise_cost")) return rc;
+  if (int rc = launch_noise_cost(h, ps, cp, interior(h->params, rows, cols, cp.pw, cp.ph), amount, 1, keep_zero, h->stream))
+    return rc;
   if (cost)
     if (int rc = stage_out(h, ps, cost, 3)) return rc;
   return stage_out(h, ps, disp, 0);
@@ -1114,8 +1098,7 @@ int pm_mask_occlusions(pm_handle* h, float* disp_l, const float* disp_r, int row
   const size_t px = (size_t)rows * cols;
   PM_HIP(h, hipMemcpyAsync(h->st_disp_l, disp_l, sizeof(float) * px, hipMemcpyHostToDevice, h->stream));
   PM_HIP(h, hipMemcpyAsync(h->st_disp_r, disp_r, sizeof(float) * px, hipMemcpyHostToDevice, h->stream));
-  launch_mask_occlusions(h, h->st_disp_l, h->st_disp_r, rows, cols, h->stream);
-  if (int rc = launch_check(h, "mask_occlusions")) return rc;
+  if (int rc = launch_mask_occlusions(h, h->st_disp_l, h->st_disp_r, rows, cols, h->stream)) return rc;
   PM_HIP(h, hipMemcpyAsync(disp_l, h->st_disp_l, sizeof(float) * px, hipMemcpyDeviceToHost, h->stream));
   PM_HIP(h, hipStreamSynchronize(h->stream));
   return PM_OK;

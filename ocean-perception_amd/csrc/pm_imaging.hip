@@ -376,10 +376,10 @@ int pm_match_bgr_device(pm_handle* h, int n, const uint8_t* d_left_bgr8, const u
     set_err(h, "pm_match_bgr_device: n >= 1 pairs of at least 8x8 pixels");
     return PM_ERR_INVALID_ARG;
   }
-  ImagingState* st = state_of(h);
+  ImagingState& st = *state_of(h);
   const size_t ipx = (size_t)rows * cols, values = ipx * 3;
-  PM_HIP(h, st->bgr_blur.reserve(sizeof(float) * values * 2 * (size_t)n, pm_internal::stream(h)));
-  PM_HIP(h, st->bgr_mm.reserve(sizeof(unsigned) * 8 * (size_t)n, pm_internal::stream(h)));
+  PM_HIP(h, st.bgr_blur.reserve(sizeof(float) * values * 2 * (size_t)n, pm_internal::stream(h)));
+  PM_HIP(h, st.bgr_mm.reserve(sizeof(unsigned) * 8 * (size_t)n, pm_internal::stream(h)));
   // NormalizeColorIlluminant (normalization.cpp:178-185): ksize = NextOddInt(cols / 3), sigma = (float)ksize / 4
   const int third = cols / 3;
   const int ksize = third + (1 - third % 2);
@@ -389,9 +389,9 @@ int pm_match_bgr_device(pm_handle* h, int n, const uint8_t* d_left_bgr8, const u
     init[i] = kValueMinInit;
     init[i + 1] = kValueMaxInit;
   }
-  PM_HIP(h, hipMemcpyAsync(st->bgr_mm, init.data(), sizeof(unsigned) * init.size(), hipMemcpyHostToDevice, pm_internal::stream(h)));
-  float* blur_l = st->bgr_blur;
-  float* blur_r = st->bgr_blur + values * (size_t)n;
+  PM_HIP(h, hipMemcpyAsync(st.bgr_mm, init.data(), sizeof(unsigned) * init.size(), hipMemcpyHostToDevice, pm_internal::stream(h)));
+  float* blur_l = st.bgr_blur;
+  float* blur_r = st.bgr_blur + values * (size_t)n;
   const size_t small = (size_t)(rows / 8) * (cols / 8);
   // image z = b * 2 + i (pair b, left / right); up to kBlurBatch images per launch of each pass
   for (int z0 = 0; z0 < 2 * n; z0 += kBlurBatch) {
@@ -409,7 +409,7 @@ int pm_match_bgr_device(pm_handle* h, int n, const uint8_t* d_left_bgr8, const u
     if (int rc = run_gaussian_batch<true>(h, srcs, dsts, count, rows, cols, 3, ksize, sigma, false)) return rc;
     dim3 mgrid = reduce_grid(small);
     mgrid.y = (unsigned)count;
-    unsigned* mm = st->bgr_mm + (size_t)z0 * 4;
+    unsigned* mm = st.bgr_mm + (size_t)z0 * 4;
     hipLaunchKernelGGL((k_value_minmax_fused<1>), mgrid, dim3(256), 0, pm_internal::stream(h), bb, rows, cols, mm);
     hipLaunchKernelGGL((k_value_minmax_fused<2>), mgrid, dim3(256), 0, pm_internal::stream(h), bb, rows, cols, mm);
   }
@@ -419,12 +419,8 @@ int pm_match_bgr_device(pm_handle* h, int n, const uint8_t* d_left_bgr8, const u
   src.right = d_right_bgr8;
   src.blur_l = blur_l;
   src.blur_r = blur_r;
-  src.mm = st->bgr_mm;
-  pm_internal::set_bgr_source(h, &src);
-  // the image pointers below only have to be non-null: the prep stage reads `src`
-  const int rc = pm_match_device(h, n, d_left_bgr8, d_right_bgr8, rows, cols, d_seed_l, d_seed_r, d_disp_l, d_disp_r);
-  pm_internal::set_bgr_source(h, nullptr);
-  return rc;
+  src.mm = st.bgr_mm;
+  return pm_internal::match_bgr(h, n, src, rows, cols, d_seed_l, d_seed_r, d_disp_l, d_disp_r);
 }
 
 int pm_normalize_color_illuminant(pm_handle* h, const float* d_bgr, int rows, int cols, float* d_out) {

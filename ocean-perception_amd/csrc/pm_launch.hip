@@ -34,23 +34,24 @@ static SetupGrid setup_grid(pm_handle* h, const PlaneSet& ps, int n, int view) {
   return sg;
 }
 
-void launch_prep(pm_handle* h, const PlaneSet& ps, const uint8_t* d_left, const uint8_t* d_right, int n, size_t stride,
-                 int view, const PrepSeedMaps* seeds, hipStream_t stream) {
-  if (h->bgr) {
-    hipLaunchKernelGGL(k_prep_bgr, dim3((unsigned)((ps.cols + 63) / 64), (unsigned)((ps.rows + kPrepBgrTileH - 1) / kPrepBgrTileH), (unsigned)n),
-                       dim3(256), 0, stream, ps, *h->bgr);
-    if (seeds) launch_seed(h, ps, seeds->l, seeds->r, n, view, stream);
-    return;
+int launch_prep(pm_handle* h, const PlaneSet& ps, const MatchCall& c, int view, bool ride_seeds, hipStream_t stream) {
+  if (c.bgr) {
+    hipLaunchKernelGGL(k_prep_bgr, dim3((unsigned)((ps.cols + 63) / 64), (unsigned)((ps.rows + kPrepBgrTileH - 1) / kPrepBgrTileH), (unsigned)c.n),
+                       dim3(256), 0, stream, ps, *c.bgr);
+    if (ride_seeds) return launch_seed(h, ps, c.seed_l, c.seed_r, c.n, view, stream);
+    return launch_check(h, "prep");
   }
-  const PrepSeeds sd{seeds ? seeds->l : nullptr, seeds ? seeds->r : nullptr, seeds ? 1 : 0};
-  hipLaunchKernelGGL(k_prep, pixel_grid(ps.cols, ps.rows, n), dim3(256), 0, stream, ps, d_left, d_right, stride, view,
-                     sd);
+  const PrepSeeds sd{ride_seeds ? c.seed_l : nullptr, ride_seeds ? c.seed_r : nullptr, ride_seeds ? 1 : 0};
+  hipLaunchKernelGGL(k_prep, pixel_grid(ps.cols, ps.rows, c.n), dim3(256), 0, stream, ps, c.left, c.right, (size_t)c.cols,
+                     view, sd);
+  return launch_check(h, "prep");
 }
 
-void launch_prep_view(pm_handle* h, const PlaneSet& ps, const float* d_iml, const float* d_imr, const float* d_Gl,
-                      const float* d_Gr, size_t stride, hipStream_t stream) {
+int launch_prep_view(pm_handle* h, const PlaneSet& ps, const float* d_iml, const float* d_imr, const float* d_Gl,
+                     const float* d_Gr, size_t stride, hipStream_t stream) {
   hipLaunchKernelGGL(k_prep_view, pixel_grid(ps.cols, ps.rows, 1), dim3(256), 0, stream, ps, d_iml, d_imr, d_Gl, d_Gr,
                      stride);
+  return launch_check(h, "prep_view");
 }
 
 
@@ -68,10 +69,11 @@ int run_transpose(pm_handle* h, const PlaneSet& ps, int n, int view, hipStream_t
 }
 
 // seed maps (tightly packed [n][rows][cols], null = zeros) into the disparity planes; view 1 mirrored
-void launch_seed(pm_handle* h, const PlaneSet& ps, const float* d_seed_l, const float* d_seed_r, int n, int view,
-                 hipStream_t stream) {
+int launch_seed(pm_handle* h, const PlaneSet& ps, const float* d_seed_l, const float* d_seed_r, int n, int view,
+                hipStream_t stream) {
   hipLaunchKernelGGL(k_seed, pixel_grid(ps.cols, ps.rows, n), dim3(256), 0, stream, ps, d_seed_l, d_seed_r,
                      (size_t)ps.cols, view);
+  return launch_check(h, "seed");
 }
 
 int run_sweep(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const SweepGeom& g, int slots, float amp,
@@ -85,8 +87,8 @@ int run_sweep(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const Swee
 }
 
 // noise + clamp + cost of the current disparity; PM_SEM_CPU square windows use the LDS-tiled kernel
-void launch_noise_cost(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const Interior& in, float amount,
-                       int slots, int keep_zero, hipStream_t stream) {
+int launch_noise_cost(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const Interior& in, float amount,
+                      int slots, int keep_zero, hipStream_t stream) {
   const bool tiled = cp.semantics == PM_SEM_CPU && cp.pw == cp.ph && !h->no_tiled;
   const dim3 tgrid((unsigned)((ps.cols + kTileW - 1) / kTileW), (unsigned)((ps.rows + kTileH - 1) / kTileH),
                    (unsigned)slots);
@@ -100,7 +102,7 @@ void launch_noise_cost(pm_handle* h, const PlaneSet& ps, const CostParams& cp, c
 #define PM_NC_CASE(W)                                                                                                 \
   case W:                                                                                                             \
     hipLaunchKernelGGL((k_noise_cost_tiled<W, W>), tgrid, dim3(256), 0, stream, ps, cp, in, amount, keep_zero);       \
-    return;
+    return launch_check(h, "noise_cost");
   if (tiled) {
     switch (cp.pw) {
       PM_NC_CASE(3)
@@ -113,18 +115,19 @@ void launch_noise_cost(pm_handle* h, const PlaneSet& ps, const CostParams& cp, c
   }
 #undef PM_NC_CASE
   hipLaunchKernelGGL(k_noise_cost, pixel_grid(ps.cols, ps.rows, slots), dim3(256), 0, stream, ps, cp, in, amount);
+  return launch_check(h, "noise_cost");
 }
 
 // RemoveBackground / MaskBackground; PM_SEM_CPU square windows use the LDS-tiled kernel
-void launch_background(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const Interior& in, float factor,
-                       int cached, int slots, hipStream_t stream) {
+int launch_background(pm_handle* h, const PlaneSet& ps, const CostParams& cp, const Interior& in, float factor,
+                      int cached, int slots, hipStream_t stream) {
   const bool tiled = cp.semantics == PM_SEM_CPU && cp.pw == cp.ph && !h->no_tiled;
   const dim3 tgrid((unsigned)((ps.cols + kTileW - 1) / kTileW), (unsigned)((ps.rows + kTileH - 1) / kTileH),
                    (unsigned)slots);
 #define PM_BG_CASE(W)                                                                                        \
   case W:                                                                                                    \
     hipLaunchKernelGGL((k_background_tiled<W, W>), tgrid, dim3(256), 0, stream, ps, cp, in, factor, cached); \
-    return;
+    return launch_check(h, "background");
   if (tiled) {
     switch (cp.pw) {
       PM_BG_CASE(3)
@@ -138,82 +141,96 @@ void launch_background(pm_handle* h, const PlaneSet& ps, const CostParams& cp, c
 #undef PM_BG_CASE
   hipLaunchKernelGGL(k_background, pixel_grid(ps.cols, ps.rows, slots), dim3(256), 0, stream, ps, cp, in, factor,
                      cached);
+  return launch_check(h, "background");
 }
 
 // the noise step alone (pm_add_noise): an empty interior skips the clamp and the cost
-void launch_noise_only(pm_handle* h, const PlaneSet& ps, const CostParams& cp, float amount, hipStream_t stream) {
+int launch_noise_only(pm_handle* h, const PlaneSet& ps, const CostParams& cp, float amount, hipStream_t stream) {
   const Interior none{1, 0, 1, 0};
   hipLaunchKernelGGL(k_noise_cost, pixel_grid(ps.cols, ps.rows, 1), dim3(256), 0, stream, ps, cp, none, amount);
+  return launch_check(h, "noise");
 }
 
 // cross-check (when two views ran) + un-mirroring + tight [n][rows][cols] output
-void launch_finalize(pm_handle* h, const PlaneSet& ps, float* d_disp_l, float* d_disp_r, int n, hipStream_t stream) {
+int launch_finalize(pm_handle* h, const PlaneSet& ps, float* d_disp_l, float* d_disp_r, int n, hipStream_t stream) {
   hipLaunchKernelGGL(k_finalize, pixel_grid(ps.cols, ps.rows, n), dim3(256), 0, stream, ps, d_disp_l, d_disp_r,
                      (size_t)ps.cols);
+  return launch_check(h, "finalize");
 }
 
-void launch_mask_occlusions(pm_handle* h, float* d_disp_l, const float* d_disp_r, int rows, int cols,
-                            hipStream_t stream) {
+int launch_mask_occlusions(pm_handle* h, float* d_disp_l, const float* d_disp_r, int rows, int cols,
+                           hipStream_t stream) {
   hipLaunchKernelGGL(k_mask_occlusions, pixel_grid(cols, rows, 1), dim3(256), 0, stream, d_disp_l, d_disp_r, rows,
                      cols);
+  return launch_check(h, "mask_occlusions");
 }
 
-void launch_state_row(pm_handle* h, const PlaneSet& ps, int r, float* d_buf, int to_buf, hipStream_t stream) {
+int launch_state_row(pm_handle* h, const PlaneSet& ps, int r, float* d_buf, int to_buf, hipStream_t stream) {
   hipLaunchKernelGGL(k_state_row, dim3((unsigned)((ps.cols + 255) / 256), (unsigned)ps.n_views), dim3(256), 0, stream, ps, r,
                      d_buf, to_buf);
+  return launch_check(h, "state_row");
 }
 
-void launch_tile_round(pm_handle* h, const PlaneSet& ps, const float* snap_disp, const float* snap_cost,
-                       const float* d_incoming, const float* d_used, float* d_used_next, int* d_mask, int pred_r, int y_lo,
-                       int y_hi, hipStream_t stream) {
+int launch_tile_round(pm_handle* h, const PlaneSet& ps, const float* snap_disp, const float* snap_cost,
+                      const float* d_incoming, const float* d_used, float* d_used_next, int* d_mask, int pred_r, int y_lo,
+                      int y_hi, hipStream_t stream) {
   const int chunks = (y_hi - y_lo + kTileRoundRows) / kTileRoundRows;
   hipLaunchKernelGGL(k_tile_round, dim3((unsigned)((ps.cols + 255) / 256), (unsigned)chunks, (unsigned)ps.n_views), dim3(256),
                      0, stream, ps, snap_disp, snap_cost, d_incoming, d_used, d_used_next, d_mask, pred_r, y_lo, y_hi);
+  return launch_check(h, "tile_round");
 }
 
-void launch_tile_presweep(pm_handle* h, const PlaneSet& ps, float* snap_disp, float* snap_cost, const float* d_row,
-                          int pred_r, hipStream_t stream) {
+int launch_tile_presweep(pm_handle* h, const PlaneSet& ps, float* snap_disp, float* snap_cost, const float* d_row,
+                         int pred_r, hipStream_t stream) {
   const int rows4 = (ps.rows + 3) / 4;  // 16-byte pieces per column (pm_device.hpp::state_at)
   hipLaunchKernelGGL(k_tile_presweep, dim3((unsigned)((ps.pitch + 255) / 256), (unsigned)rows4, (unsigned)ps.n_views), dim3(256),
                      0, stream, ps, snap_disp, snap_cost, d_row, pred_r);
+  return launch_check(h, "tile_presweep");
 }
 
-void launch_state_row_moved(pm_handle* h, const PlaneSet& ps, int r, const float* d_ref, int* d_flag,
-                            hipStream_t stream) {
+int launch_state_row_moved(pm_handle* h, const PlaneSet& ps, int r, const float* d_ref, int* d_flag,
+                           hipStream_t stream) {
   hipLaunchKernelGGL(k_state_row_moved, dim3((unsigned)((ps.cols + 255) / 256), (unsigned)ps.n_views), dim3(256), 0,
                      stream, ps, r, d_ref, d_flag);
+  return launch_check(h, "state_row_moved");
 }
 
-void launch_restore_cols(pm_handle* h, const PlaneSet& ps, const float* snap_disp, const float* snap_cost,
-                         const int* d_mask, hipStream_t stream) {
+int launch_restore_cols(pm_handle* h, const PlaneSet& ps, const float* snap_disp, const float* snap_cost,
+                        const int* d_mask, hipStream_t stream) {
   hipLaunchKernelGGL(k_restore_cols, pixel_grid(ps.cols, ps.rows, ps.n_views), dim3(256), 0, stream, ps, snap_disp,
                      snap_cost, d_mask);
+  return launch_check(h, "restore_cols");
 }
 
-void launch_download(pm_handle* h, float* dst_dev, size_t dst_step_floats, const float* d_src, int rows, int cols,
-                     hipStream_t stream) {
+int launch_download(pm_handle* h, float* dst_dev, size_t dst_step_floats, const float* d_src, int rows, int cols,
+                    hipStream_t stream) {
   hipLaunchKernelGGL(k_download, dim3(kDownloadBlocks), dim3(256), 0, stream, dst_dev, dst_step_floats, d_src, rows, cols);
+  return launch_check(h, "download");
 }
 
 // the same copy kernel the other way: `words` floats from page-locked host memory (device address) into device memory, one
 // 16-byte load per lane where the grid allows (every load is a round trip over the bus)
-void launch_upload(pm_handle* h, float* d_dst, const float* src_dev, int words, hipStream_t stream) {
+int launch_upload(pm_handle* h, float* d_dst, const float* src_dev, int words, hipStream_t stream) {
   const int blocks = std::min(64, std::max(1, (words / 4 + 255) / 256));
   hipLaunchKernelGGL(k_download, dim3((unsigned)blocks), dim3(256), 0, stream, d_dst, (size_t)words, src_dev, 1, words);
+  return launch_check(h, "upload");
 }
 
-void launch_copy_in(pm_handle* h, const PlaneSet& ps, const float* d_src, int which, hipStream_t stream) {
+int launch_copy_in(pm_handle* h, const PlaneSet& ps, const float* d_src, int which, hipStream_t stream) {
   hipLaunchKernelGGL(k_copy_in, pixel_grid(ps.cols, ps.rows, 1), dim3(256), 0, stream, ps, d_src, which);
+  return launch_check(h, "copy_in");
 }
 
-void launch_copy_out(pm_handle* h, const PlaneSet& ps, float* d_dst, int which, hipStream_t stream) {
+int launch_copy_out(pm_handle* h, const PlaneSet& ps, float* d_dst, int which, hipStream_t stream) {
   hipLaunchKernelGGL(k_copy_out, pixel_grid(ps.cols, ps.rows, 1), dim3(256), 0, stream, ps, d_dst, which);
+  return launch_check(h, "copy_out");
 }
 
-void launch_copy_disp_strided(pm_handle* h, const PlaneSet& ps, float* d_buf, size_t stride, int to_buf,
-                              hipStream_t stream) {
+int launch_copy_disp_strided(pm_handle* h, const PlaneSet& ps, float* d_buf, size_t stride, int to_buf,
+                             hipStream_t stream) {
   hipLaunchKernelGGL(k_copy_disp_strided, pixel_grid(ps.cols, ps.rows, 1), dim3(256), 0, stream, ps, d_buf, stride,
                      to_buf);
+  return launch_check(h, "copy_disp_strided");
 }
 
 }  // namespace eng

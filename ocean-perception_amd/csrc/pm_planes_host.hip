@@ -77,15 +77,6 @@ int planes_alloc(pm_handle* h, hipStream_t stream) {
 
 namespace {
 
-// PM_PLANES_LANES=1 (tuning builds): the whole batch through every launch on one stream, as until round 6
-bool planes_two_lanes() {
-  static const bool on = [] {
-    const char* e = pm::tune_env("PM_PLANES_LANES");
-    return !(e && atoi(e) == 1);
-  }();
-  return on;
-}
-
 // pair0: the launch covers the pairs from pair0 on (`ps` is the plan's plane set; slots counts from that pair)
 template <int STAGE>
 int planes_stage(pm_handle* h, const PlaneSet& ps0, const PlArgs& ar, int slots, int klass, const char* what, int pair0,
@@ -137,36 +128,26 @@ int planes_step(pm_handle* h, const PlaneSet& ps, int n, int stage, int arg, int
   }
 }
 
-// prep (images, gradients, packed planes) + seeds + random initialisation of n pairs
-int planes_begin(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
-                 const float* d_seed_l, const float* d_seed_r, hipStream_t stream) {
+// prep (images, gradients, packed planes) + seeds + random initialisation of c's pairs: the head of a plane-mode call
+// (no transposed planes in this mode)
+int planes_begin(pm_handle* h, const MatchCall& c, const MatchPlan& plan, hipStream_t stream) {
   if (int rc = planes_alloc(h, stream)) return rc;
-  const int nv = h->params.left_right_check ? 2 : 1;
+  const int n = c.n, rows = c.rows, cols = c.cols, nv = plan.n_views;
   PlaneSet ps = plane_set(h, rows, cols, nv);
-  {
-    Launch l(h, PM_K_PREP, stream);
-    launch_prep(h, ps, d_left, d_right, n, (size_t)cols, -1, nullptr, stream);
-  }
-  if (int rc = launch_check(h, "prep")) return rc;
-  const float* sl = d_seed_l;
-  const float* sr = d_seed_r;
+  if (int rc = enqueue_head(h, ps, c, -1, kHeadPrep, stream)) return rc;
   PlArgs ar{};
   ar.dbg = planes_dbg();
-  if (h->params.sparse_init) {
-    // SparseInit on the device (patchmatch_gpu.cu:414-442) into the scalar engine's disparity planes, from
-    // which the initialisation kernel takes the seeds (view 1's plane is already in mirrored coordinates)
-    for (int v = 0; v < nv; ++v) {
-      if (v == 0 ? sl != nullptr : sr != nullptr) continue;
-      Launch l(h, PM_K_SEED, stream);
-      for (int b = 0; b < n; ++b)
-        if (int rc = run_sparse_init(h, ps, b, v, 0, kSeedAllStages, stream)) return rc;
-      ar.seed_in_disp |= 1 << v;
-    }
+  // SparseInit on the device (patchmatch_gpu.cu:414-442) into the scalar engine's disparity planes, from
+  // which the initialisation kernel takes the seeds (view 1's plane is already in mirrored coordinates)
+  for (int v = 0; v < nv; ++v) {
+    if (!plan.self_seed[v]) continue;
+    if (int rc = enqueue_head(h, ps, c, v, kSeedAllStages, stream)) return rc;
+    ar.seed_in_disp |= 1 << v;
   }
   ar.stage = PL_INIT;
   ar.view_fixed = -1;
-  ar.seed_l = sl;
-  ar.seed_r = sr;
+  ar.seed_l = c.seed_l;
+  ar.seed_r = c.seed_r;
   if (int rc = planes_stage<PL_INIT>(h, ps, ar, n * nv, PM_K_PL_INIT, "initialisation", 0, stream)) return rc;
   h->pl_rows = rows;
   h->pl_cols = cols;
@@ -213,16 +194,15 @@ namespace pm {
 namespace eng {
 
 // The whole schedule of oracle/pm_planes_oracle.c::pmo_planes_match.
-int planes_match(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols,
-                 const float* d_seed_l, const float* d_seed_r, float* d_disp_l, float* d_disp_r) {
-  if (int rc = planes_begin(h, n, d_left, d_right, rows, cols, d_seed_l, d_seed_r, h->stream)) return rc;
-  const int nv = h->params.left_right_check ? 2 : 1;
-  const PlaneSet ps = plane_set(h, rows, cols, nv);
-  // A batch runs as TWO LANES: the first half of its pairs through the iterations on the handle's stream, the second
-  // half on view1_stream, launch k of both before launch k + 1 of either.  The 33 launches of a pair's iterations each end
-  // with a tail in which a few tiles hold the chip; the other lane's launch fills it (two handles side by side matched
-  // 560 pairs/s where one matched 469 / 521 / 552 with 1 / 2 / 4 pairs per launch: tools/multi_handle.py, round 6).
-  const int n_lane[2] = {planes_two_lanes() && n >= 2 ? (n + 1) / 2 : n, planes_two_lanes() && n >= 2 ? n / 2 : 0};
+int planes_match(pm_handle* h, const MatchCall& c, const MatchPlan& plan, float* d_disp_l, float* d_disp_r) {
+  if (int rc = planes_begin(h, c, plan, h->stream)) return rc;
+  const int nv = plan.n_views;
+  const PlaneSet ps = plane_set(h, c.rows, c.cols, nv);
+  // A batch runs as TWO LANES (MatchPlan::lane_pairs): the first half of its pairs through the iterations on the handle's
+  // stream, the second half on view1_stream, launch k of both before launch k + 1 of either.  The 33 launches of a pair's
+  // iterations each end with a tail in which a few tiles hold the chip; the other lane's launch fills it (two handles side
+  // by side matched 560 pairs/s where one matched 469 / 521 / 552 with 1 / 2 / 4 pairs per launch: tools/multi_handle.py).
+  const int* n_lane = plan.lane_pairs;
   const hipStream_t lane_stream[2] = {h->stream, h->view1_stream};
   if (n_lane[1]) {
     if (int rc = view_streams_create(h)) return rc;
@@ -298,7 +278,8 @@ int pm_planes_begin(pm_handle* h, int n, const uint8_t* d_left, const uint8_t* d
     return PM_ERR_INVALID_ARG;
   }
   if (int rc = check_size(h, rows, cols, n)) return rc;
-  return planes_begin(h, n, d_left, d_right, rows, cols, d_seed_l, d_seed_r, h->stream);
+  const MatchCall c{d_left, d_right, d_seed_l, d_seed_r, n, rows, cols, nullptr};
+  return planes_begin(h, c, match_plan(h, c), h->stream);
 }
 
 int pm_planes_step(pm_handle* h, int stage, int arg) {

@@ -88,11 +88,8 @@ int pm_tile_begin(pm_handle* h, const pm_tile* tile, const uint8_t* d_left_band,
   h->tile_on = true;
   if (int rc = tile_noise_table(h)) return rc;
   const PlaneSet ps = tile_plane_set(h);
-  launch_prep(h, ps, d_left_band, d_right_band, 1, (size_t)cols, -1, nullptr, h->stream);
-  if (int rc = launch_check(h, "prep")) return rc;
-  if (int rc = run_transpose(h, ps, 1, -1, h->stream)) return rc;
-  launch_seed(h, ps, d_seed_l_band, d_seed_r_band, 1, -1, h->stream);
-  return launch_check(h, "seed");
+  const MatchCall band{d_left_band, d_right_band, d_seed_l_band, d_seed_r_band, 1, band_rows, cols, nullptr};
+  return enqueue_head(h, ps, band, -1, kHeadPrep | kHeadLines | kHeadSeedCopy | kHeadUntimed, h->stream);
 }
 
 int pm_tile_noise(pm_handle* h, int it) {
@@ -105,8 +102,7 @@ int pm_tile_noise(pm_handle* h, int it) {
   const PlaneSet ps = tile_plane_set(h);
   const CostParams cp = cost_params(p, p.patch_w[it], p.patch_h[it]);
   const Interior in = tile_interior(h, cp.pw, cp.ph);
-  launch_noise_cost(h, ps, cp, in, p.noise_amp[it], ps.n_views, 0, h->stream);
-  return launch_check(h, "noise_cost");
+  return launch_noise_cost(h, ps, cp, in, p.noise_amp[it], ps.n_views, 0, h->stream);
 }
 
 static int tile_sweep(pm_handle* h, int it, int k, const int* d_mask);
@@ -190,8 +186,7 @@ int pm_tile_presweep(pm_handle* h, int pred_image_row, const float* d_row) {
   }
   if (int rc = snapshot_alloc(h)) return rc;
   const PlaneSet ps = tile_plane_set(h);
-  launch_tile_presweep(h, ps, h->snap_disp, h->snap_cost, d_row, d_row ? r : -4, h->stream);
-  return launch_check(h, "tile_presweep");
+  return launch_tile_presweep(h, ps, h->snap_disp, h->snap_cost, d_row, d_row ? r : -4, h->stream);
 }
 
 int pm_tile_restore(pm_handle* h) {
@@ -214,8 +209,7 @@ int pm_tile_restore_cols(pm_handle* h, const int* d_mask) {
     return PM_ERR_INVALID_ARG;
   }
   const PlaneSet ps = tile_plane_set(h);
-  launch_restore_cols(h, ps, h->snap_disp, h->snap_cost, d_mask, h->stream);
-  return launch_check(h, "restore_cols");
+  return launch_restore_cols(h, ps, h->snap_disp, h->snap_cost, d_mask, h->stream);
 }
 
 // One exchange round of vertical sweep k in two launches: k_tile_round (compare the incoming boundary row with the one
@@ -243,8 +237,9 @@ int pm_tile_exchange_round(pm_handle* h, int it, int k, int pred_image_row, cons
     set_err(h, "pm_tile_exchange_round: row %d is one of the band's own rows, not a neighbour's", pred_image_row);
     return PM_ERR_INVALID_ARG;
   }
-  launch_tile_round(h, ps, h->snap_disp, h->snap_cost, d_incoming, d_used, d_used_next, d_mask, r, y_lo, y_hi, h->stream);
-  if (int rc = launch_check(h, "tile_round")) return rc;
+  if (int rc = launch_tile_round(h, ps, h->snap_disp, h->snap_cost, d_incoming, d_used, d_used_next, d_mask, r, y_lo, y_hi,
+                                 h->stream))
+    return rc;
   return tile_sweep(h, it, k, d_mask);
 }
 
@@ -256,8 +251,7 @@ int pm_tile_row_moved(pm_handle* h, int image_row, const float* d_ref_row, int* 
     return PM_ERR_INVALID_ARG;
   }
   const PlaneSet ps = tile_plane_set(h);
-  launch_state_row_moved(h, ps, r, d_ref_row, d_flag, h->stream);
-  return launch_check(h, "state_row_moved");
+  return launch_state_row_moved(h, ps, r, d_ref_row, d_flag, h->stream);
 }
 
 static int tile_row_copy(pm_handle* h, int image_row, float* d_dst, const float* d_src, const char* what) {
@@ -269,8 +263,7 @@ static int tile_row_copy(pm_handle* h, int image_row, float* d_dst, const float*
   }
   const PlaneSet ps = tile_plane_set(h);
   // (the state planes keep four rows interleaved: a row is every fourth word of a stretch -- a small kernel, not a copy)
-  launch_state_row(h, ps, r, d_dst ? d_dst : const_cast<float*>(d_src), d_dst ? 1 : 0, h->stream);
-  return launch_check(h, what);
+  return launch_state_row(h, ps, r, d_dst ? d_dst : const_cast<float*>(d_src), d_dst ? 1 : 0, h->stream);
 }
 
 int pm_tile_get_row(pm_handle* h, int image_row, float* d_dst) {
@@ -290,8 +283,7 @@ int pm_tile_background(pm_handle* h) {
   const int cached = (last >= 0 && bcp.pw == (p.semantics == PM_SEM_CPU ? p.patch_w[last] : 3) &&
                       bcp.ph == (p.semantics == PM_SEM_CPU ? p.patch_h[last] : 3)) ? 1 : 0;
   const float factor = p.semantics == PM_SEM_CPU ? p.win_by_factor : p.cost_improve_factor;
-  launch_background(h, ps, bcp, in, factor, cached, ps.n_views, h->stream);
-  return launch_check(h, "background");
+  return launch_background(h, ps, bcp, in, factor, cached, ps.n_views, h->stream);
 }
 
 int pm_tile_finish(pm_handle* h, float* d_disp_l_own, float* d_disp_r_own) {
@@ -301,8 +293,7 @@ int pm_tile_finish(pm_handle* h, float* d_disp_l_own, float* d_disp_r_own) {
     set_err(h, "pm_tile_finish: null output");
     return PM_ERR_INVALID_ARG;
   }
-  launch_finalize(h, ps, h->st_disp_l, ps.n_views > 1 ? h->st_disp_r : nullptr, 1, h->stream);
-  if (int rc = launch_check(h, "finalize")) return rc;
+  if (int rc = launch_finalize(h, ps, h->st_disp_l, ps.n_views > 1 ? h->st_disp_r : nullptr, 1, h->stream)) return rc;
   const size_t ofs = (size_t)(h->tile.own_row0 - h->tile.band_row0) * ps.cols;
   const size_t bytes = sizeof(float) * (size_t)h->tile.own_rows * ps.cols;
   PM_HIP(h, hipMemcpyAsync(d_disp_l_own, h->st_disp_l + ofs, bytes, hipMemcpyDeviceToDevice, h->stream));
@@ -333,11 +324,9 @@ int pm_debug_tile_state(pm_handle* h, int which, int view, float* disp, float* c
     if (!host[i]) continue;
     if (write) {
       PM_HIP(h, hipMemcpyAsync(h->st_disp_l, host[i], sizeof(float) * px, hipMemcpyHostToDevice, h->stream));
-      launch_copy_in(h, ps, h->st_disp_l, plane_id[i], h->stream);
-      if (int rc = launch_check(h, "copy_in")) return rc;
+      if (int rc = launch_copy_in(h, ps, h->st_disp_l, plane_id[i], h->stream)) return rc;
     } else {
-      launch_copy_out(h, ps, h->st_disp_l, plane_id[i], h->stream);
-      if (int rc = launch_check(h, "copy_out")) return rc;
+      if (int rc = launch_copy_out(h, ps, h->st_disp_l, plane_id[i], h->stream)) return rc;
       PM_HIP(h, hipMemcpyAsync(host[i], h->st_disp_l, sizeof(float) * px, hipMemcpyDeviceToHost, h->stream));
     }
     PM_HIP(h, hipStreamSynchronize(h->stream));  // (pageable host memory, and the staging plane is used twice)

@@ -1,7 +1,7 @@
 // pm_tune.hpp -- the A/B knobs of the tuning build.  The shipped library reads NO environment variable: every
 // schedule and LDS-budget choice is fixed by the code (results never depended on them).  `make tuning` builds
 // lib/libvehicle_pm_gpu_tuning.so with -DPM_TUNING, in which the knobs named at the call sites (PM_STREAM_PRIO,
-// PM_PAIR_LANES, PM_RUNBLK_*, PM_G16_*, ...) are read once per process; tools/ select that build through PM_LIB.
+// PM_PAIR_CHUNK, PM_RUNBLK_*, PM_G16_*, ...) are read once per process; tools/ select that build through PM_LIB.
 #pragma once
 
 #include <cstdlib>

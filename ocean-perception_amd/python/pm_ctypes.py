@@ -50,6 +50,7 @@ EXPORTS = [
     "pm_reproject_disparity", "pm_debug_reproject_constants",
     "pm_filter_consistency",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
+    "pm_debug_match_plan",
     "pm_debug_sweep_plan", "pm_debug_segment_bounds", "pm_debug_propagate_hinted", "pm_debug_match_sweep_hint", "pm_debug_read_stops", "pm_debug_noise_cost_constants", "pm_debug_noise_cost", "pm_debug_remove_background",
     "pm_remove_background", "pm_mask_occlusions", "pm_foreground_texture_mask", "pm_sparse_init", "pm_corner_subpix", "pm_profile_enable", "pm_profile_read",
     "pm_kernel_name", "pm_debug_counters", "pm_debug_counters_enable",
@@ -136,6 +137,16 @@ class PmTiledAuditRecord(C.Structure):  # include/pm/testing.h
 class PmDebugSweepVariant(C.Structure):  # include/pm/testing.h
     _fields_ = [(name, C.c_int) for name in ("engine", "axis", "dir", "group", "waves", "window", "lref", "chain_len",
                                              "chains")]
+
+
+class PmDebugMatchRoute(C.Structure):  # include/pm/testing.h
+    _fields_ = [("route", C.c_int), ("n_views", C.c_int), ("self_seed", C.c_int * 2), ("pair_chunk", C.c_int),
+                ("head_aside", C.c_int), ("lane_pairs", C.c_int * 2), ("seq_chunks", C.c_int), ("seq_hold", C.c_int),
+                ("need_view_events", C.c_int), ("need_slot_events", C.c_int), ("need_second_seed_scratch", C.c_int)]
+
+
+# pm_debug_match_route.route (csrc/pm_match_plan.hpp::MatchRoute)
+ROUTE_PLANES, ROUTE_ONE_STREAM, ROUTE_SHARED_HEAD, ROUTE_VIEW_HEADS, ROUTE_CHUNKS = 0, 1, 2, 3, 4
 
 
 class PmDebugPlanesVariant(C.Structure):  # include/pm/testing.h
@@ -608,6 +619,21 @@ def default_params(semantics=PM_SEM_CPU, **kw):
                 raise AttributeError(k)
             setattr(p, k, v)
     return p
+
+
+def match_plan(params, n=1, seed_l=False, seed_r=False, bgr=False):
+    """pm_debug_match_plan: the route of a Match() on n pairs -- seed_l / seed_r: that view's seed maps are given; bgr: BGR
+    input -- from the host-side plan alone (no handle, no device) -> a dict of the fields of pm_debug_match_route (the
+    two-element ones as tuples)."""
+    fn = load().pm_debug_match_plan
+    fn.argtypes = [C.POINTER(PmParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PmDebugMatchRoute)]
+    fn.restype = C.c_int
+    out = PmDebugMatchRoute()
+    rc = fn(C.byref(params), n, int(bool(seed_l)), int(bool(seed_r)), int(bool(bgr)), C.byref(out))
+    if rc != PM_OK:
+        raise PmError(rc, "pm_debug_match_plan")
+    rec = {name: getattr(out, name) for name, _ in PmDebugMatchRoute._fields_}
+    return {k: tuple(v) if not isinstance(v, int) else v for k, v in rec.items()}
 
 
 def sweep_plan(params, rows, cols, patch_h, patch_w, pass_index, slots=1, amp=1e30):
