@@ -359,10 +359,10 @@ int pm_mask_occlusions(pm_handle* h, float* disp_l, const float* disp_r, int row
  * data (at least patch_h/2 + 1 where the image continues, so that windows and Sobel gradients of the
  * owned rows see true neighbours).  Everything except the two vertical sweeps of an iteration is local
  * to a tile (rectified stereo only looks along rows).  A vertical sweep carries one value per column
- * across the tile boundary: the caller moves that ROW of disparities between neighbouring tiles with
- * pm_tile_get_row / pm_tile_set_row (hipMemcpyPeer, RCCL send/recv, ...) and repeats the sweep from
- * pm_tile_snapshot's state until no tile's incoming row changes; the fixpoint is the untiled result
- * (driver: ocean-perception_amd/python/tiled.py).  All pointers are DEVICE memory; n = 1 pair.
+ * across the tile boundary: the caller moves that ROW of disparities between neighbouring tiles
+ * (hipMemcpyPeer, RCCL send/recv, ...) in the order pm_tiled_steps below lists, stage by stage; the
+ * result is the untiled one (drivers: pm_tiled_* below in one process, ocean-perception_amd/python/tiled.py
+ * over several).  All pointers are DEVICE memory; n = 1 pair.
  * A stage is the whole-image stage restricted to the OWNED rows: it writes the disparity and the cost of those rows only.
  * The halo rows of the state belong to the neighbours -- pm_tile_set_row / pm_tile_presweep / pm_tile_exchange_round store
  * there what a neighbour delivers -- and hold values >= 0; a band takes its slice of the whole-image noise table at
@@ -407,21 +407,53 @@ int pm_tile_row_moved(pm_handle* h, int image_row, const float* d_ref_row, int* 
 int pm_tile_background(pm_handle* h);
 /* cross-check + un-mirror; writes the owned rows only: [own_rows][cols] each */
 int pm_tile_finish(pm_handle* h, float* d_disp_l_own, float* d_disp_r_own);
+/* The order of those stages and of the rows between them: one attempt of a Match() over n_bands bands as a flat list of
+ * steps, in the order a single-threaded driver enqueues them (a driver with one process per band does the steps of its
+ * band in this order).  No handle, no device; the one place the protocol is written down (csrc/pm_tiled_steps.hpp) --
+ * pm_tiled_run below and python/tiled.py execute this list and decide nothing themselves.
+ *   schedule   pm_tiled_schedule (below).  PIPELINED: in a vertical pass the bands take turns along the sweep direction,
+ *              SET_ROW (the predecessor's final row), SWEEP, PUBLISH.  SPECULATIVE: every band PUBLISHes, takes its
+ *              predecessor's row as a guess (PRESWEEP) and SWEEPs; then `rounds` rounds of PUBLISH / EXCHANGE_ROUND, which
+ *              the band at position pos of the sweep direction leaves after round pos - 1 (it is final); then ROW_MOVED.
+ *   rounds     SPECULATIVE only: exchange rounds per vertical pass; negative or > n_bands - 1 = n_bands - 1, always enough.
+ * The values of pm_tiled_op are the stage ids of the audit log (include/pm/testing.h). */
+typedef enum pm_tiled_op {
+  PM_TILED_OP_BEGIN = 1,          /* pm_tile_begin                                                                  */
+  PM_TILED_OP_NOISE = 2,          /* pm_tile_noise(iteration)                                                       */
+  PM_TILED_OP_SWEEP = 3,          /* pm_tile_sweep(iteration, pass)                                                 */
+  PM_TILED_OP_PUBLISH = 4,        /* pm_tile_get_row: the band's boundary row into its buffer `buffer`, for `peer`   */
+  PM_TILED_OP_PRESWEEP = 5,       /* pm_tile_presweep on the row taken from `peer` (none: peer = -1)                 */
+  PM_TILED_OP_EXCHANGE_ROUND = 6, /* pm_tile_exchange_round on the row taken from `peer`                             */
+  PM_TILED_OP_ROW_MOVED = 7,      /* pm_tile_row_moved against the row the band published last (in `buffer`)         */
+  PM_TILED_OP_BACKGROUND = 8,     /* pm_tile_background                                                             */
+  PM_TILED_OP_FINISH = 9,         /* pm_tile_finish                                                                 */
+  PM_TILED_OP_SET_ROW = 10        /* pm_tile_set_row of the row taken from `peer`                                    */
+} pm_tiled_op;
+typedef struct pm_tiled_step {
+  int op;        /* pm_tiled_op                                                                                        */
+  int band;
+  int iteration; /* -1: BEGIN, BACKGROUND, FINISH                                                                      */
+  int pass;      /* pm_tile_sweep's k; -1 outside the sweeps.  1 runs down (a band's predecessor is band - 1), 3 up     */
+  int round;     /* the exchange round; -1: the guess phase, the pipelined schedule, outside a vertical pass.  ROW_MOVED
+                    carries the pass's last round                                                                      */
+  int peer;      /* a step that takes a row: the band it comes from; PUBLISH: the band that will take it; -1: none      */
+  int buffer;    /* which of a band's two published-row buffers: taking a row, `peer`'s; PUBLISH, ROW_MOVED: the band's */
+  /* taking a row across to another band's stream (a peer copy, or the consuming stage reading it in place): */
+  int copy;             /* 1: the row is compared with a later one, so it must be COPIED into the band's own memory    */
+  int done_behind_copy; /* 1: a copied row counts as consumed behind the copy, in front of the stage that uses the copy;
+                           0: behind the stage.  A row read in place is consumed behind the stage that reads it.        */
+} pm_tiled_step;
+/* copies the first `capacity` steps (steps may be NULL), *total = the steps of the attempt */
+int pm_tiled_steps(int n_bands, int iterations, int schedule, int rounds, pm_tiled_step* steps, int capacity, int* total);
 
 /* ---- the row-tiled driver over the pm_tile_* stages: ONE process, n band handles on up to n devices ----------------
  * The C / C++ caller's form of BASELINE config 4 (the multi-process variant over torch.distributed / RCCL is
- * ocean-perception_amd/python/tiled.py; both run the same protocol).  Band k owns rows split as evenly as possible and
- * works on its rows plus patch_h/2 + 1 halo rows of image data.  Noise / cost, the horizontal sweeps, the background
- * mask and the cross-check are local to a band.  A vertical sweep carries one value per column across a band boundary
- * (one row of disparities, read by the receiving band behind an event of the sender's stream -- no host synchronisation,
- * no RCCL inside one process).  Two schedules give the same maps (pm_tiled_set_schedule below):
- *   PIPELINED (default)  the bands sweep in order along the sweep direction, each continuing from its predecessor's final
- *                        row: exact by construction, `rounds` is ignored;
- *   SPECULATIVE          every band sweeps with the neighbour's OLD boundary row, the new boundary rows travel one hop,
- *                        and a band re-sweeps exactly the columns whose incoming value changed, `rounds` times per sweep
- *                        (band k is final after round k + 1).  Whether that sufficed is one device flag per band ("my
- *                        boundary row still moved after the last row I sent"), read once per Match; only if it is set is
- *                        the Match repeated with n_bands - 1 rounds, which is always enough.
+ * ocean-perception_amd/python/tiled.py; both execute the steps of pm_tiled_steps above).  Band k owns rows split as evenly
+ * as possible and works on its rows plus patch_h/2 + 1 halo rows of image data.  A row that a step takes from another band
+ * is read by the receiving band behind an event of the sender's stream -- no host synchronisation, no RCCL inside one
+ * process.  Two schedules give the same maps (pm_tiled_set_schedule below): PIPELINED (default) is exact by construction
+ * and ignores `rounds`; whether SPECULATIVE's `rounds` sufficed is one device flag per band (ROW_MOVED), read once per
+ * Match; only if it is set is the Match repeated with n_bands - 1 rounds, which is always enough.
  * The result equals the untiled Match() bit for bit (tests/test_cpp_tiled.py, 4096x2160).
  * Replaces, for one large image, PatchmatchGpu::Match(const Image1b&, const Image1b&, Image1f&, Image1f&)
  * (src/vehicle/patchmatch_gpu/patchmatch_gpu.h:99-102). */

@@ -56,7 +56,7 @@ EXPORTS = [
     "pm_kernel_name", "pm_debug_counters", "pm_debug_counters_enable",
     "pm_tile_begin", "pm_tile_noise", "pm_tile_sweep", "pm_tile_snapshot", "pm_tile_restore", "pm_tile_get_row",
     "pm_tile_set_row", "pm_tile_background", "pm_tile_finish", "pm_tile_restore_cols", "pm_tile_sweep_masked",
-    "pm_tile_exchange_round", "pm_tile_row_moved", "pm_tile_presweep",
+    "pm_tile_exchange_round", "pm_tile_row_moved", "pm_tile_presweep", "pm_tiled_steps",
     "pm_debug_tile_state", "pm_debug_tile_last_sweep",
     "pm_match_view_device", "pm_set_unit_noise", "pm_initialize",
     "pm_planes_begin", "pm_planes_step", "pm_planes_read", "pm_planes_write", "pm_planes_finish",
@@ -126,6 +126,11 @@ class PmTile(C.Structure):
 
 class PmTiledInfo(C.Structure):
     _fields_ = [("rounds_used", C.c_int), ("repeated", C.c_int), ("exchanges", C.c_int)]
+
+
+class PmTiledStep(C.Structure):  # pm_tiled_steps
+    _fields_ = [(name, C.c_int) for name in ("op", "band", "iteration", "sweep", "round", "peer", "buffer", "copy",
+                                             "done_behind_copy")]   # `sweep` is the header's `pass`
 
 
 class PmTiledAuditRecord(C.Structure):  # include/pm/testing.h
@@ -518,6 +523,8 @@ def load():
     lib.pm_tile_set_row.argtypes = [vp, C.c_int, f32p]
     lib.pm_tile_background.argtypes = [vp]
     lib.pm_tile_finish.argtypes = [vp, f32p, f32p]
+    lib.pm_tiled_steps.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PmTiledStep), C.c_int, C.POINTER(C.c_int)]
+    lib.pm_tiled_steps.restype = C.c_int
     lib.pm_tiled_band_rows.argtypes = [C.POINTER(PmParams), C.c_int, C.c_int]
     lib.pm_tiled_band_rows.restype = C.c_int
     lib.pm_tiled_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
@@ -1374,6 +1381,20 @@ TILED_CALLS = {1: "set_device", 2: "malloc", 3: "event_create", 4: "event_record
                6: "stream_sync", 7: "memset", 8: "copy_h2d", 9: "copy_d2h", 10: "copy_peer", 11: "stage", 12: "stage_arg"}
 TILED_STAGES = {1: "begin", 2: "noise", 3: "sweep", 4: "get_row", 5: "presweep", 6: "exchange_round", 7: "row_moved",
                 8: "background", 9: "finish", 10: "set_row"}
+# pm_tiled_op: the same numbers (PUBLISH is the get_row stage)
+(TILED_BEGIN, TILED_NOISE, TILED_SWEEP, TILED_PUBLISH, TILED_PRESWEEP, TILED_EXCHANGE_ROUND, TILED_ROW_MOVED,
+ TILED_BACKGROUND, TILED_FINISH, TILED_SET_ROW) = range(1, 11)
+
+
+def tiled_steps(n_bands, iterations, schedule, rounds=-1):
+    """pm_tiled_steps: one attempt of a row-tiled Match() as the list of PmTiledStep a driver executes.  No handle, no device."""
+    lib, total = load(), C.c_int(0)
+    rc = lib.pm_tiled_steps(n_bands, iterations, schedule, rounds, None, 0, C.byref(total))
+    steps = (PmTiledStep * max(total.value, 1))()
+    rc = rc or lib.pm_tiled_steps(n_bands, iterations, schedule, rounds, steps, total.value, C.byref(total))
+    if rc != PM_OK:
+        raise PmError(rc, "pm_tiled_steps")
+    return list(steps[:total.value])
 
 
 class TiledEngine:

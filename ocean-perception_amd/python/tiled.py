@@ -7,29 +7,22 @@ own rows see their true neighbours.  Only the two vertical sweeps of an iteratio
 column, the first row of a band continues from the value the last row of the band above ended on
 (src/vehicle/stereo_matching/patchmatch.cpp:276-285, :301-310 read in pass order).
 
-Exact semantics without serialising the GPUs: speculate and fix up at band granularity (the scheme
-the kernels use inside a chain, pm_run.hpp).  Each rank sweeps with the neighbour's OLD boundary row,
-the new boundary rows travel one hop (one row of disparities per view: 16 KB at 4096 columns), and a rank
-re-sweeps exactly the COLUMNS whose incoming value changed (columns of a vertical sweep are independent
-chains) from the snapshot it took before the sweep.  Band k is final after round k+1; the fixpoint is the
-untiled sweep.
+Who takes whose boundary row, when and in which order is pm_tiled_steps (include/pm/patchmatch.h): match_band does the
+steps of its rank and decides nothing itself.  Two schedules, same maps (`pipelined=` of match_band).  PIPELINED, the
+default: in a vertical sweep the ranks take turns along the sweep direction, each continuing from its predecessor's FINAL
+row -- nothing is guessed, everything that does not cross a boundary still overlaps between the ranks.  SPECULATIVE: every
+rank sweeps with the neighbour's OLD row, the new rows travel one hop per round (one row of disparities per view: 16 KB at
+4096 columns) and a rank re-sweeps exactly the COLUMNS whose incoming value changed from the snapshot it took before the
+sweep.  Measured with eight bands on one device through the C driver: 28.5 ms per 4096x2160 frame pipelined, 35.7
+speculative, 29.5 untiled.
 
-Everything stays on the device timeline: the exchange is RCCL send/recv (torch.distributed P2P over xGMI)
-enqueued on the engine's own stream, "which columns changed" is a device mask handed to
-pm_tile_restore_cols / pm_tile_sweep_masked, and the number of rounds per sweep is FIXED (2 by default; a round
-in which nothing changed costs three empty launches), so no rank ever waits on the host inside a Match().
-Whether the fixed rounds sufficed is one device flag per rank -- "my boundary row still changed after the
-last round" -- reduced over the ranks ONCE, after the Match; only if it is set (a value crossed more than
-`rounds` band boundaries in one sweep) is the Match repeated with world - 1 rounds, which always suffices.
-`LocalComm` runs the same protocol with the ranks as threads of one process (tests on a single GPU).
-
-Two schedules, same maps (pm_tiled_schedule of include/pm/patchmatch.h; `pipelined=` of match_band): the one above is the
-SPECULATIVE one.  The default since round 6 is PIPELINED: in a vertical sweep the ranks take turns along the sweep
-direction -- a rank receives its predecessor's FINAL boundary row, stores it in front of its chains, sweeps once and sends
-its own last row on.  Nothing is guessed, so there is no snapshot, no mask, no re-sweep, no flag and no repeat; everything
-that does not cross a boundary (noise / cost, horizontal sweeps) still overlaps between the ranks.  Measured with eight
-bands on one device through the C driver: 28.5 ms per 4096x2160 frame against 35.7 speculative and 29.5 untiled.
+Everything stays on the device timeline: the exchange is RCCL send/recv (torch.distributed P2P over xGMI) enqueued on the
+engine's own stream and the number of rounds per sweep is FIXED, so no rank ever waits on the host inside a Match().
+Whether the rounds sufficed is one device flag per rank, reduced over the ranks ONCE, after the Match; only if it is set
+is the Match repeated with world - 1 rounds, which always suffices.  `LocalComm` runs the same protocol with the ranks as
+threads of one process (tests on a single GPU).
 """
+import itertools
 import threading
 
 import numpy as np
@@ -224,77 +217,77 @@ def match_band(engine, comm, params, left_band, right_band, seed_l_band, seed_r_
     """Enqueues this rank's part of Match() for device tensors of its band on the engine's stream and returns
     (disp_l, disp_r, flag): the maps of the owned rows and a one-element device tensor that is non-zero if this rank's
     boundary row still changed after the last exchange round of some sweep (then `rounds` was too small).
-    Nothing in here waits on the host."""
+    Nothing in here waits on the host.
+
+    The steps of band comm.rank of pm_tiled_steps, through `comm` and the engine.  The pipelined schedule hands a row over
+    where its step stands (comm.send / comm.recv).  The speculative one moves the rows of one exchange -- the steps of one
+    (iteration, pass, round) -- in ONE comm.shift per rank, behind the rank's PUBLISH and in front of its other steps:
+    LocalComm.shift meets at a barrier, so a rank calls it in every exchange, also where it neither sends nor receives."""
     band_rows, cols = left_band.shape
     n_views = 2 if params.left_right_check else 1
     dev = left_band.device
     tile = pm.PmTile(global_rows, band_row0, own_row0, own_rows)
     ptr = lambda t: t.data_ptr() if t is not None else None
+    schedule = pm.PM_TILED_SCHEDULE_PIPELINED if pipelined else pm.PM_TILED_SCHEDULE_SPECULATIVE
+    steps = pm.tiled_steps(comm.world, params.patchmatch_iters, schedule, max(rounds, 0))  # (a negative count runs no round here)
     ext = torch.cuda.ExternalStream(engine.stream(), device=dev)
     ext.wait_stream(torch.cuda.current_stream(dev))  # the inputs were produced on the caller's stream
     with torch.cuda.stream(ext):
-        engine.tile_begin(tile, ptr(left_band), ptr(right_band), band_rows, cols, ptr(seed_l_band), ptr(seed_r_band))
-        own_end = own_row0 + own_rows
         flag = torch.zeros(1, dtype=torch.int32, device=dev)
         mask = torch.zeros((n_views, cols), dtype=torch.int32, device=dev)
-
-        def get_row(r):
-            t = torch.empty((n_views, cols), dtype=torch.float32, device=dev)
-            engine.tile_get_row(r, t.data_ptr())
-            return t
-
-        for it in range(params.patchmatch_iters):
-            engine.tile_noise(it)
-            for k in range(4):
-                if k in (0, 2):  # horizontal sweeps never leave the band
-                    engine.tile_sweep(it, k)
-                    continue
-                down = k == 1
-                out_row = own_end - 1 if down else own_row0
-                pred_row = own_row0 - 1 if down else own_end
-                if pipelined:
-                    # the ranks take turns along the sweep direction: my predecessor's final row in front of my chains,
-                    # one sweep, my last row on to my successor
-                    pos = comm.rank if down else comm.world - 1 - comm.rank
-                    pred = comm.rank - 1 if down else comm.rank + 1
-                    succ = comm.rank + 1 if down else comm.rank - 1
-                    if pos > 0:
-                        row = comm.recv((n_views, cols), dev, pred, down)
-                        engine.tile_set_row(pred_row, row.data_ptr())
-                    engine.tile_sweep(it, k)
-                    if pos < comm.world - 1:
-                        comm.send(get_row(out_row), succ, down)
-                    continue
-                sent = get_row(out_row)
-                used = comm.shift(sent, down)  # the neighbour's value before the sweep: the guess
-                # the guess into the planes and the snapshot in one launch
-                engine.tile_presweep(pred_row, used.data_ptr() if used is not None else None)
-                engine.tile_sweep(it, k)
-                # The band at position pos of the sweep direction (0 = the band without a predecessor) is final after
-                # round pos - 1: from round pos on it would receive the row it already has.  It skips those rounds and
-                # its predecessor does not send: world (world - 1) / 2 band-rounds instead of (world - 1)^2.
-                pos = comm.rank if down else comm.world - 1 - comm.rank
-                for r in range(rounds):
-                    recv = pos > r            # my predecessor's row can still have changed
-                    send = pos + 1 > r and 0 <= (comm.rank + 1 if down else comm.rank - 1) < comm.world
-                    if send:
-                        sent = get_row(out_row)
-                    new_in = comm.shift(sent, down, send=send, recv=recv)
-                    if new_in is not None:
-                        # columns whose incoming value changed: flagged, put back to the snapshot, the incoming row
-                        # stored -- one launch -- then the masked sweep (pm_tile_exchange_round)
-                        engine.tile_exchange_round(it, k, pred_row, new_in.data_ptr(), used.data_ptr(), new_in.data_ptr(), mask.data_ptr())
-                        used = new_in
-                # did my boundary row move after the last row I sent?  then my successor is stale.  Only a rank
-                # that HAS a successor in this sweep's direction asks: the last band's row is an image border
-                # nobody consumes, and a change there must not make every rank repeat the Match.
-                succ = comm.rank + 1 if down else comm.rank - 1
-                if 0 <= succ < comm.world:
-                    engine.tile_row_moved(out_row, sent.data_ptr(), flag.data_ptr())
-        engine.tile_background()
         out_l = torch.empty((own_rows, cols), dtype=torch.float32, device=dev)
         out_r = torch.empty_like(out_l) if n_views > 1 else None
-        engine.tile_finish(out_l.data_ptr(), ptr(out_r))
+        sent = [None, None]   # the rows this band published, by buffer
+        used = None           # the predecessor's row the last vertical sweep of this band started from
+
+        def do(s, row):  # step s of this band on `row`, if it takes one
+            nonlocal used
+            own_end = own_row0 + own_rows   # (boundary_rows of csrc/pm_tiled_steps.hpp)
+            out_row, pred_row = (own_end - 1, own_row0 - 1) if s.sweep == 1 else (own_row0, own_end)
+            if s.op == pm.TILED_BEGIN:
+                engine.tile_begin(tile, ptr(left_band), ptr(right_band), band_rows, cols, ptr(seed_l_band), ptr(seed_r_band))
+            elif s.op == pm.TILED_NOISE:
+                engine.tile_noise(s.iteration)
+            elif s.op == pm.TILED_SWEEP:
+                engine.tile_sweep(s.iteration, s.sweep)
+            elif s.op == pm.TILED_PUBLISH:
+                sent[s.buffer] = torch.empty((n_views, cols), dtype=torch.float32, device=dev)
+                engine.tile_get_row(out_row, ptr(sent[s.buffer]))
+            elif s.op == pm.TILED_PRESWEEP:   # the guess into the planes and the snapshot in one launch
+                engine.tile_presweep(pred_row, ptr(row))
+            elif s.op == pm.TILED_EXCHANGE_ROUND:   # compare, restore and row store in one launch, then the masked sweep
+                engine.tile_exchange_round(s.iteration, s.sweep, pred_row, ptr(row), ptr(used), ptr(row), ptr(mask))
+            elif s.op == pm.TILED_SET_ROW:
+                engine.tile_set_row(pred_row, ptr(row))
+            elif s.op == pm.TILED_ROW_MOVED:
+                engine.tile_row_moved(out_row, ptr(sent[s.buffer]), ptr(flag))
+            elif s.op == pm.TILED_BACKGROUND:
+                engine.tile_background()
+            elif s.op == pm.TILED_FINISH:
+                engine.tile_finish(ptr(out_l), ptr(out_r))
+            used = row if s.op in takes else used
+
+        takes = (pm.TILED_PRESWEEP, pm.TILED_EXCHANGE_ROUND, pm.TILED_SET_ROW)
+        mine = lambda some: [s for s in some if s.band == comm.rank]
+        if pipelined:
+            for s in mine(steps):
+                do(s, comm.recv((n_views, cols), dev, s.peer, s.sweep == 1) if s.op in takes else None)
+                if s.op == pm.TILED_PUBLISH:
+                    comm.send(sent[s.buffer], s.peer, s.sweep == 1)
+        else:
+            last = None   # the row this band published last
+            for _, group in itertools.groupby(steps, key=lambda s: (s.iteration, s.sweep, s.round)):
+                group = list(group)
+                publish = [s for s in mine(group) if s.op == pm.TILED_PUBLISH]
+                rest = [s for s in mine(group) if s.op != pm.TILED_PUBLISH]
+                for s in publish:
+                    do(s, None)
+                    last = sent[s.buffer]
+                row = None
+                if any(s.op == pm.TILED_PUBLISH for s in group):   # an exchange: some band hands a row on
+                    row = comm.shift(last, group[0].sweep == 1, send=bool(publish), recv=any(s.op in takes for s in rest))
+                for s in rest:
+                    do(s, row if s.op in takes else None)
     torch.cuda.current_stream(dev).wait_stream(ext)
     return out_l, out_r, flag
 
