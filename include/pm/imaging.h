@@ -491,6 +491,64 @@ int pm_filter_consistency(pm_handle* h, const pm_cloud_camera* camera, const pm_
                           float* d_residual /* may be NULL */, int* d_counts /* device int[2], may be NULL */,
                           int* counts /* host int[2], may be NULL: non-NULL synchronises like pm_point_cloud's count */);
 
+/* ---- matching confidence: how well each disparity of a map matched ----------------------------------------------------------
+ * What it is for: every stage behind Match() treats each positive disparity as equally good.  PatchMatch keeps no cost volume,
+ * so this stage evaluates the matching functor again around the answer -- at d, one pixel either side of d, and at the
+ * background hypothesis d = 0 (the comparison RemoveBackground makes) -- and, where the right map is given, reads the
+ * left-right residual.  It returns the four measures, a flag byte per pixel and the map with the failing pixels zeroed; a
+ * consumer thresholds a cloud, weights a fusion or keeps only trustworthy temporal seeds.  It sits behind Match() and in front
+ * of pm_filter_speckles.
+ * Held to its CPU definition (tests/confidence_ref.py) BIT FOR BIT.  G_l, G_r are the Sobel magnitudes of the two images
+ * (pm_gradient_magnitude); cost(x, y, d) is the PM_SEM_CPU cost of the patch_w x patch_h window at (x, y) under the handle's
+ * functor_alpha, functor_tau_color, functor_tau_grad -- always that functor, whatever the handle's semantics or mode.  Every
+ * operation is one binary32 rounding unless it says binary64:
+ *   interior   pw / 2 <= x <= cols - pw / 2 - 1 and ph / 2 <= y <= rows - ph / 2 - 1 (empty where the window does not fit).
+ *   valid      d = D_l(y, x) > 0: not for 0, -0.0, negatives and NaN.
+ *   MEASURED   valid, interior and d <= hi with hi = (float)x - (float)(pw / 2): the domain in which the window stays in the
+ *              image; every interior value Match() returns lies in it.  +inf and values beyond hi are valid but not measured;
+ *              nothing is clamped.
+ *   costs      c0 = cost(d); c_bg = cost(+0.0f); dm = d - 1.0f, side M exists iff dm >= 0, cm = cost(dm); dp = d + 1.0f, side P
+ *              exists iff dp <= hi, cp = cost(dp).
+ *   margin     both sides: (cp < cm ? cp : cm) - c0; one side: that side's cost - c0; none: +0.0f.  Negative: d is not even a
+ *              local minimum.
+ *   bg_margin  c_bg - c0.
+ *   lr         with d_disp_r: q = (int)fmaxf((float)x - d, 0.f) (pm_mask_occlusions' index), r = D_r(y, q); r > 0:
+ *              (float)fabs((double)r - (double)d) in binary64, otherwise +inf.  Without d_disp_r: +inf.
+ *   flags      a measured pixel: PM_CONF_MEASURED plus one PM_CONF_FAIL_* bit per threshold it does not PASS (see the struct;
+ *              a +inf lr passes only max_lr_diff = +inf; FAIL_LR only ever with d_disp_r).  Not measured: 0.  KEPT iff
+ *              flags == PM_CONF_MEASURED.
+ *   d_out      a measured pixel that is not KEPT becomes +0.0f; with drop_unmeasured = 1 so does a valid pixel that is not
+ *              measured; every other pixel, invalid ones included, keeps its input bits (pm_filter_speckles' rule).  May equal
+ *              d_disp_l.
+ *   d_measures four planes c0, margin, bg_margin, lr; a pixel that is not measured gets -1.0f, +0.0f, +0.0f, +inf.
+ *   counts     [0] valid, [1] measured, [2] kept pixels.
+ * Every output is optional, but at least one must be given.  Valid in every mode of the handle: it reads images and maps, not
+ * the handle's state.  It enqueues on the handle's stream; a non-NULL `counts` synchronises it like pm_point_cloud's `count`.
+ * Two launches behind a 16-byte memset; only integer addition crosses workgroups.  Scratch is one allocation (16 bytes of counts,
+ * a byte and a float per pixel for the gradients), made on first use, reused, grown under a stream synchronisation and
+ * released with the handle.
+ * PM_ERR_INVALID_ARG, with pm_last_error naming the argument and nothing enqueued: null options, d_left, d_right or d_disp_l;
+ * no output at all; patch_w or patch_h even or outside 3..PM_MAX_PATCH; a NaN threshold; drop_unmeasured outside {0, 1}; rows
+ * or cols < 1; d_out equal to d_disp_r.  PM_ERR_SIZE as for pm_backproject. */
+typedef struct pm_confidence_options {
+  int   patch_w, patch_h;   /* odd, 3 .. PM_MAX_PATCH each; need not be square                    */
+  float max_cost;           /* PASS iff c0 <= max_cost;              +inf: every pixel passes      */
+  float min_margin;         /* PASS iff margin >= min_margin;        -inf: every pixel passes      */
+  float min_bg_margin;      /* PASS iff bg_margin >= min_bg_margin;  -inf: every pixel passes      */
+  float max_lr_diff;        /* PASS iff lr <= max_lr_diff;           +inf: every pixel passes;
+                               read only when d_disp_r is given                                   */
+  int   drop_unmeasured;    /* 0 / 1, see d_out                                                    */
+} pm_confidence_options;
+enum { PM_CONF_MEASURED = 1, PM_CONF_FAIL_COST = 2, PM_CONF_FAIL_MARGIN = 4, PM_CONF_FAIL_BG = 8, PM_CONF_FAIL_LR = 16 };
+int pm_disparity_confidence(pm_handle* h, const pm_confidence_options* options,
+                            const uint8_t* d_left, const uint8_t* d_right,      /* rectified, [rows][cols], packed */
+                            const float* d_disp_l, const float* d_disp_r /* may be NULL */, int rows, int cols,
+                            float* d_out      /* may be NULL, may equal d_disp_l */,
+                            float* d_measures /* [4][rows][cols]: c0, margin, bg_margin, lr; may be NULL */,
+                            uint8_t* d_flags  /* [rows][cols], may be NULL */,
+                            int* d_counts     /* device int[3], may be NULL */,
+                            int* counts       /* host int[3], may be NULL: non-NULL synchronises like pm_point_cloud's count */);
+
 /* ---- device buffers for host code that does not include HIP (host/imaging.hpp uses them) ------------------
  * pm_device_malloc / pm_device_free wrap hipMalloc / hipFree on the handle's device; pm_upload / pm_download are
  * stream-ordered copies on the handle's stream from / to pageable host memory (pm_download returns after the

@@ -205,6 +205,13 @@ void pm_debug_mesh_constants(int* items_per_block, int* blocks_per_scan_pass);
  * Tests place holes on tile borders and corners with them.  No handle, no device. */
 void pm_debug_reproject_constants(int* tile_w, int* tile_h);
 
+/* ---- pm_disparity_confidence's launch constants (csrc/pm_confidence_body.hpp) -------------------------------------------------
+ * tile_w x tile_h: the pixels one block owns; target_cols: the columns of the target rows its LDS tile holds.  A block takes
+ * the global-memory path iff lo4 + target_cols < hi + patch_w + 1, with lo4 the multiple of four at or below the smallest
+ * floor(x - d' - (patch_w - 1) / 2) of its measured pixels (d' = d + 1 where that side exists, else d) and hi their largest
+ * x - patch_w / 2.  Tests build a map that reaches that path with them.  No handle, no device. */
+void pm_debug_confidence_constants(int* tile_w, int* tile_h, int* target_cols);
+
 /* ---- the row-tiled driver's device discipline, provable on ONE GPU ------------------------------------------------
  * pm_tiled_create with the bands accounted to LOGICAL devices: band k lives on logical_devices[k] (>= 0; several bands
  * may share one) while every HIP call still goes to the physical device of the band's handle.  Such a plan logs every

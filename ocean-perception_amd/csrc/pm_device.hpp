@@ -10,8 +10,49 @@
 
 namespace pm {
 
+// Two device instructions with what a CPU build of a *_body.hpp header computes in their place, so that the arithmetic
+// below is ONE statement for the kernels and for a host that walks them (tests/cpp/confidence_host_main.cpp).
+// rint_i: round to nearest, ties to even, as int (v_cvt_i32_f32 after v_rndne; the host's default rounding mode).
+__host__ __device__ __forceinline__ int rint_i(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __float2int_rn(v);
+#else
+  return (int)__builtin_rintf(v);
+#endif
+}
+// mul_u24: the product of two values below 2^24 (v_mul_u32_u24, full rate)
+__host__ __device__ __forceinline__ unsigned mul_u24(unsigned a, unsigned b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __umul24(a, b);
+#else
+  return a * b;
+#endif
+}
+
+// sad_u8: acc + the absolute differences of the four bytes of a and b (v_sad_u8)
+__host__ __device__ __forceinline__ unsigned sad_u8(unsigned a, unsigned b, unsigned acc) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_sad_u8(a, b, acc);
+#else
+  for (int k = 0; k < 32; k += 8) {
+    const unsigned x = (a >> k) & 0xffu, y = (b >> k) & 0xffu;
+    acc += x > y ? x - y : y - x;
+  }
+  return acc;
+#endif
+}
+// sat_u8_pk: saturate_cast<uchar>(s) in byte 0 of a zero dword (v_cvt_pk_u8_f32; see cpu_acc_grad)
+__host__ __device__ __forceinline__ unsigned sat_u8_pk(float s) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_cvt_pk_u8_f32(s, 0, 0u);
+#else
+  const int iv = (int)__builtin_rintf(s < -1.f ? -1.f : s > 256.f ? 256.f : s);
+  return (unsigned)(iv < 0 ? 0 : iv > 255 ? 255 : iv);
+#endif
+}
+
 // BORDER_REFLECT_101 index (one reflection: |overshoot| < len)
-__device__ __forceinline__ int reflect101(int p, int len) {
+__host__ __device__ __forceinline__ int reflect101(int p, int len) {
   if (len == 1) return 0;
   if (p < 0) p = -p;
   if (p >= len) p = 2 * (len - 1) - p;
@@ -175,9 +216,24 @@ struct CostParams {
 };
 
 // saturate_cast<uchar>(float) = clamp(cvRound(v), 0, 255); cvRound rounds half to even.
-__device__ __forceinline__ int sat_u8(float v) {
-  const int iv = __float2int_rn(v);
-  return min(max(iv, 0), 255);
+__host__ __device__ __forceinline__ int sat_u8(float v) {
+  const int iv = rint_i(v);
+  return iv < 0 ? 0 : iv > 255 ? 255 : iv;
+}
+
+// Sobel magnitude of pixel (x, y) of an 8-bit image: kernels [-1 0 1]x[1 2 1]^T, unnormalised, BORDER_REFLECT_101 (OpenCV
+// default); every intermediate is an integer < 2^24, the only rounding is the correctly rounded sqrt.  What k_prep
+// (pm_kernels.hpp) and pm_disparity_confidence's gradient launch (pm_confidence.hpp) write.
+__host__ __device__ __forceinline__ float sobel_mag(const uint8_t* im, size_t stride, int rows, int cols, int x, int y) {
+  const uint8_t* r0 = im + (size_t)reflect101(y - 1, rows) * stride;
+  const uint8_t* r1 = im + (size_t)y * stride;
+  const uint8_t* r2 = im + (size_t)reflect101(y + 1, rows) * stride;
+  const int xm = reflect101(x - 1, cols), xp = reflect101(x + 1, cols);
+  const int dx = ((int)r0[xp] - (int)r0[xm]) + 2 * ((int)r1[xp] - (int)r1[xm]) + ((int)r2[xp] - (int)r2[xm]);
+  const int dy = ((int)r2[xm] - (int)r0[xm]) + 2 * ((int)r2[x] - (int)r0[x]) + ((int)r2[xp] - (int)r0[xp]);
+  const float fx = (float)dx, fy = (float)dy;
+  const float sx = fx * fx, sy = fy * fy;
+  return sqrtf(sx + sy);  // correctly rounded (-fhip-fp32-correctly-rounded-divide-sqrt); __fsqrt_rn is the 1-ulp native form
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -194,7 +250,7 @@ struct CpuLerp {
   float a, ia;
 };
 
-__device__ __forceinline__ CpuLerp cpu_lerp(int x, float d, int pw) {
+__host__ __device__ __forceinline__ CpuLerp cpu_lerp(int x, float d, int pw) {
   float cx = (float)x - d;
   cx = cx - (float)(pw - 1) * 0.5f;
   CpuLerp l;
@@ -202,19 +258,19 @@ __device__ __forceinline__ CpuLerp cpu_lerp(int x, float d, int pw) {
   l.ipx = (int)fl;
   l.a = cx - fl;
   l.ia = 1.f - l.a;
-  l.a11 = __float2int_rn(l.ia * 65536.f);
-  l.a12 = __float2int_rn(l.a * 65536.f);
+  l.a11 = rint_i(l.ia * 65536.f);
+  l.a12 = rint_i(l.a * 65536.f);
   return l;
 }
 
 // r0, r1 <= 255 and a11, a12 <= 65536 fit 24 bits: v_mad_u32_u24 (full rate) instead of v_mul_lo_u32.
-__device__ __forceinline__ int cpu_tap_color(int left, int r0, int r1, const CpuLerp& l) {
-  unsigned t = __umul24((unsigned)r1, (unsigned)l.a12) + (1u << 15);
-  t = __umul24((unsigned)r0, (unsigned)l.a11) + t;
+__host__ __device__ __forceinline__ int cpu_tap_color(int left, int r0, int r1, const CpuLerp& l) {
+  unsigned t = mul_u24((unsigned)r1, (unsigned)l.a12) + (1u << 15);
+  t = mul_u24((unsigned)r0, (unsigned)l.a11) + t;
   const int v = (int)(t >> 16);
   return abs(left - v);
 }
-__device__ __forceinline__ int cpu_tap_grad(int left_g8, float g0, float g1, const CpuLerp& l) {
+__host__ __device__ __forceinline__ int cpu_tap_grad(int left_g8, float g0, float g1, const CpuLerp& l) {
   float s = g0 * l.ia;
   s = s + g1 * l.a;
   return abs(left_g8 - sat_u8(s));
@@ -240,19 +296,19 @@ __device__ __forceinline__ unsigned cpu_color_sum(int r0, int r1, const CpuLerp&
   const unsigned t = __umul24((unsigned)r1, (unsigned)l.a12) + (1u << 15);
   return __umul24((unsigned)r0, (unsigned)l.a11) + t;
 }
-__device__ __forceinline__ unsigned cpu_acc_color(unsigned acc, int left, int r0, int r1, const CpuLerp& l) {
-  unsigned t = __umul24((unsigned)r1, (unsigned)l.a12) + (1u << 15);
-  t = __umul24((unsigned)r0, (unsigned)l.a11) + t;
-  return __builtin_amdgcn_sad_u8((unsigned)left, t >> 16, acc);
+__host__ __device__ __forceinline__ unsigned cpu_acc_color(unsigned acc, int left, int r0, int r1, const CpuLerp& l) {
+  unsigned t = mul_u24((unsigned)r1, (unsigned)l.a12) + (1u << 15);
+  t = mul_u24((unsigned)r0, (unsigned)l.a11) + t;
+  return sad_u8((unsigned)left, t >> 16, acc);
 }
 // saturate_cast<uchar>(s) = clamp(rint(s), 0, 255), ties to even: exactly what v_cvt_pk_u8_f32 computes
 // (checked on the device for every multiple of 1/16 in [-0.5, 260), the floats next to every .5 tie and
 // +-1e30: tools/probe/cvt_pk_u8.hip), and it drops the byte into a chosen lane of a dword -- one
 // instruction instead of clamp + magic add (+ v_perm when four taps are packed).
-__device__ __forceinline__ unsigned cpu_acc_grad(unsigned acc, int left_g8, float g0, float g1, const CpuLerp& l) {
+__host__ __device__ __forceinline__ unsigned cpu_acc_grad(unsigned acc, int left_g8, float g0, float g1, const CpuLerp& l) {
   float s = g0 * l.ia;
   s = s + g1 * l.a;
-  return __builtin_amdgcn_sad_u8((unsigned)left_g8, __builtin_amdgcn_cvt_pk_u8_f32(s, 0, 0u), acc);
+  return sad_u8((unsigned)left_g8, sat_u8_pk(s), acc);
 }
 // The same with the lerp sum already formed (packed-f32 products, pm_run2.hpp / k_noise_cost_tiled).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -286,7 +342,7 @@ __device__ __forceinline__ void load_pair_f32(const float* base, unsigned byte_o
 // (float)((double)sum * inv_n) without f64 conversions: sum * (hi + lo) with the rounding error of the leading
 // product recovered by one FMA.  Equal to the double form for EVERY window 3..15 x 3..15 and every sum
 // 0 .. 255 * pw * ph (exhaustive check: tests/test_oracle_primitives.py::test_mean_from_sum_is_exact).
-__device__ __forceinline__ float mean_from_sum(int sum, const CostParams& cp) {
+__host__ __device__ __forceinline__ float mean_from_sum(int sum, const CostParams& cp) {
   const float sf = (float)sum;
   const float p = sf * cp.inv_n_hi;
   const float e1 = __builtin_fmaf(sf, cp.inv_n_hi, -p);
@@ -295,7 +351,7 @@ __device__ __forceinline__ float mean_from_sum(int sum, const CostParams& cp) {
 }
 
 // mean = (float)(sum * (1./N)); cost = alpha*min(mean_c, tau_c) + (1-alpha)*min(mean_g, tau_g).
-__device__ __forceinline__ float cpu_cost_from_sums(int sc, int sg, const CostParams& cp) {
+__host__ __device__ __forceinline__ float cpu_cost_from_sums(int sc, int sg, const CostParams& cp) {
   const float mc = mean_from_sum(sc, cp);
   const float mg = mean_from_sum(sg, cp);
   const float ec = fminf(mc, cp.tau_color);

@@ -49,6 +49,9 @@ struct ImagingState {
   DevBuf<unsigned> reproject_buf;
   // pm_filter_consistency: kConsistencyHeader words ([0] valid pixels, [1] kept pixels), cleared per call
   DevBuf<int> consistency_counts;
+  // pm_disparity_confidence: kConfidenceHeader words ([0] valid, [1] measured, [2] kept pixels; cleared per call), then the
+  // right image's gradient (one float per pixel), then the left image's saturated gradient (one byte per pixel)
+  DevBuf<int> confidence_buf;
 };
 
 #define PM_HIP(h, call)                                                                                     \

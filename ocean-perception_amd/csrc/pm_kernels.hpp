@@ -13,20 +13,8 @@ namespace pm {
 // Replaces upload+convertTo (patchmatch_gpu.cu:346-349), GradientMagnitude x2 (:351-352,
 // :307-319: Sobel x, Sobel y, magnitude = 3 passes per image) and the four cu::flip (:357-360)
 // with one pass: 2 B/px read, 4*(1+4+1) B/px written.
-// Sobel: kernels [-1 0 1]x[1 2 1]^T, unnormalised, BORDER_REFLECT_101 (OpenCV default); every
-// intermediate is an integer < 2^24, the only rounding is the correctly rounded sqrt.
+// Sobel: sobel_mag (pm_device.hpp).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sobel_mag(const uint8_t* im, size_t stride, int rows, int cols, int x, int y) {
-  const uint8_t* r0 = im + (size_t)reflect101(y - 1, rows) * stride;
-  const uint8_t* r1 = im + (size_t)y * stride;
-  const uint8_t* r2 = im + (size_t)reflect101(y + 1, rows) * stride;
-  const int xm = reflect101(x - 1, cols), xp = reflect101(x + 1, cols);
-  const int dx = ((int)r0[xp] - (int)r0[xm]) + 2 * ((int)r1[xp] - (int)r1[xm]) + ((int)r2[xp] - (int)r2[xm]);
-  const int dy = ((int)r2[xm] - (int)r0[xm]) + 2 * ((int)r2[x] - (int)r0[x]) + ((int)r2[xp] - (int)r0[xp]);
-  const float fx = (float)dx, fy = (float)dy;
-  const float sx = fx * fx, sy = fy * fy;
-  return sqrtf(sx + sy);  // correctly rounded (-fhip-fp32-correctly-rounded-divide-sqrt); __fsqrt_rn is the 1-ulp native form
-}
 
 // in_left / in_right: [B][rows][in_stride] u8.  grid = (ceil(cols/256), rows, B).
 // view_sel: -1 = all four planes; 0 = the direct copies only (what view 0 works on), 1 = the mirrored copies only (view 1):

@@ -1,6 +1,6 @@
 // pm_stages.hip -- C-ABI implementation of the stages of include/pm/imaging.h that read a finished disparity map: points,
 // plane-mode normals and the compacted cloud, the windowed plane fit, the speckle filter, the grid mesh, the temporal
-// seeds and the consistency filter.  Like pm_imaging.hip it reaches the handle only through pm_internal.hpp, and it shares
+// seeds, the consistency filter and the matching confidence.  Like pm_imaging.hip it reaches the handle only through pm_internal.hpp, and it shares
 // that unit's one state object (pm_imaging_state.hpp).  Every entry point: its argument checks in a fixed order (the first
 // fault is the one reported), then the device, then its launches on the handle's stream.
 #include "pm/imaging.h"
@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "pm_cloud.hpp"
+#include "pm_confidence.hpp"
 #include "pm_consistency.hpp"
 #include "pm_imaging_state.hpp"
 #include "pm_mesh.hpp"
@@ -105,7 +106,7 @@ int stage_begin(pm_handle* h, const char* what, ImagingState** st, hipStream_t* 
   return PM_OK;
 }
 
-// Behind the launches of a stage that counts: the `n` (1 or 2) device totals go to the device destination and to the
+// Behind the launches of a stage that counts: the `n` (1 to 3) device totals go to the device destination and to the
 // host destination where given; the host copy has landed when this returns.
 int stage_counts(pm_handle* h, hipStream_t stream, const int* d_totals, int n, int* d_dst, int* dst) {
   if (d_dst) PM_HIP(h, hipMemcpyAsync(d_dst, d_totals, n * sizeof(int), hipMemcpyDeviceToDevice, stream));
@@ -535,4 +536,89 @@ int pm_filter_consistency(pm_handle* h, const pm_cloud_camera* camera, const pm_
   }
   if (int rc = launch_check(h, "consistency filter")) return rc;
   return stage_counts(h, stream, d_totals, 2, d_counts, counts);
+}
+
+// ---- matching confidence: the functor evaluated again around a map's answer (pm_confidence.hpp) -----------------------------
+namespace {
+constexpr size_t kConfidenceHeader = 4;  // the three counts, padded to 16 bytes
+
+template <int PW, int PH>
+void launch_confidence(const ConfidenceArgs& a, dim3 grid, hipStream_t stream) {
+  hipLaunchKernelGGL((k_confidence<PW, PH>), grid, dim3(kConfThreads), 0, stream, a);
+}
+}  // namespace
+
+int pm_disparity_confidence(pm_handle* h, const pm_confidence_options* options, const uint8_t* d_left, const uint8_t* d_right,
+                            const float* d_disp_l, const float* d_disp_r, int rows, int cols, float* d_out, float* d_measures,
+                            uint8_t* d_flags, int* d_counts, int* counts) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_disparity_confidence";
+  if (!options || !d_left || !d_right || !d_disp_l) {
+    set_err(h, "%s: null %s", what, !options ? "options" : !d_left ? "d_left" : !d_right ? "d_right" : "d_disp_l");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (!d_out && !d_measures && !d_flags && !d_counts && !counts) {
+    set_err(h, "%s: no output: d_out, d_measures, d_flags, d_counts and counts are all null", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  const int pw = options->patch_w, ph = options->patch_h;
+  if (pw < 3 || pw > PM_MAX_PATCH || pw % 2 == 0 || ph < 3 || ph > PM_MAX_PATCH || ph % 2 == 0) {
+    const bool w_bad = pw < 3 || pw > PM_MAX_PATCH || pw % 2 == 0;
+    set_err(h, "%s: %s %d must be odd and within 3..%d", what, w_bad ? "patch_w" : "patch_h", w_bad ? pw : ph, PM_MAX_PATCH);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (std::isnan(options->max_cost) || std::isnan(options->min_margin) || std::isnan(options->min_bg_margin) ||
+      std::isnan(options->max_lr_diff)) {
+    set_err(h, "%s: %s must not be NaN", what,
+            std::isnan(options->max_cost) ? "max_cost" : std::isnan(options->min_margin) ? "min_margin"
+            : std::isnan(options->min_bg_margin) ? "min_bg_margin" : "max_lr_diff");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (options->drop_unmeasured != 0 && options->drop_unmeasured != 1) {
+    set_err(h, "%s: drop_unmeasured %d must be 0 or 1", what, options->drop_unmeasured);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
+  if (d_out && d_out == d_disp_r) {  // a pixel of the right map is read by other pixels' lookups
+    set_err(h, "%s: d_out must not alias d_disp_r", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  ImagingState* st = nullptr;
+  hipStream_t stream = nullptr;
+  if (int rc = stage_begin(h, what, &st, &stream)) return rc;
+  const size_t px = (size_t)rows * cols;
+  PM_HIP(h, st->confidence_buf.reserve(sizeof(int) * (kConfidenceHeader + px + (px + 3) / 4), stream));
+  int* d_totals = st->confidence_buf.get();
+  float* d_gr = reinterpret_cast<float*>(d_totals + kConfidenceHeader);
+  uint8_t* d_gl8 = reinterpret_cast<uint8_t*>(d_gr + px);
+  const pm_params& p = pm_internal::params(h);
+  ConfidenceArgs a = {};
+  a.left = d_left, a.right = d_right, a.gl8 = d_gl8, a.gr = d_gr, a.disp_l = d_disp_l, a.disp_r = d_disp_r;
+  a.rows = rows, a.cols = cols, a.pw = pw, a.ph = ph;
+  a.max_cost = options->max_cost, a.min_margin = options->min_margin, a.min_bg_margin = options->min_bg_margin;
+  a.max_lr_diff = options->max_lr_diff, a.drop_unmeasured = options->drop_unmeasured;
+  a.cp = confidence_cost_params(p.functor_alpha, p.functor_tau_color, p.functor_tau_grad, pw, ph);
+  a.out = d_out, a.measures = d_measures, a.flags = d_flags, a.counts = d_totals;
+  PM_HIP(h, hipMemsetAsync(d_totals, 0, sizeof(int) * kConfidenceHeader, stream));
+  static_assert(kConfGradBlockY == kCloudBlockY && kConfTileH >= kCloudBlockY, "check_cloud_shape bounds both grids");
+  hipLaunchKernelGGL(k_confidence_grad,
+                     dim3((unsigned)((cols + kConfGradBlockX - 1) / kConfGradBlockX), (unsigned)((rows + kConfGradBlockY - 1) / kConfGradBlockY)),
+                     dim3(kConfGradBlockX, kConfGradBlockY), 0, stream, d_left, d_right, rows, cols, d_gl8, d_gr);
+  const dim3 grid((unsigned)((cols + kConfTileW - 1) / kConfTileW), (unsigned)((rows + kConfTileH - 1) / kConfTileH));
+  switch (pw == ph ? pw : 0) {
+    case 3: launch_confidence<3, 3>(a, grid, stream); break;
+    case 5: launch_confidence<5, 5>(a, grid, stream); break;
+    case 7: launch_confidence<7, 7>(a, grid, stream); break;
+    case 9: launch_confidence<9, 9>(a, grid, stream); break;
+    case 11: launch_confidence<11, 11>(a, grid, stream); break;
+    default: launch_confidence<0, 0>(a, grid, stream); break;
+  }
+  if (int rc = launch_check(h, "disparity confidence")) return rc;
+  return stage_counts(h, stream, d_totals, 3, d_counts, counts);
+}
+
+void pm_debug_confidence_constants(int* tile_w, int* tile_h, int* target_cols) {
+  if (tile_w) *tile_w = kConfTileW;
+  if (tile_h) *tile_h = kConfTileH;
+  if (target_cols) *target_cols = kConfTileRW;
 }

@@ -540,6 +540,64 @@ std::array<int, 2> FilterConsistency(pm::PatchmatchGpu& matcher, const StereoMod
   return {{counts[0], counts[1]}};
 }
 
+std::array<int, 3> DisparityConfidence(pm::PatchmatchGpu& matcher, const core::Image<uint8_t>& left,
+                                       const core::Image<uint8_t>& right, const ConfidenceOptions& options,
+                                       const core::Image<float>& disp_l, const core::Image<float>* disp_r,
+                                       core::Image<float>* out, ConfidenceMeasures* measures, core::Image<uint8_t>* flags) {
+  pm_handle* h = matcher.handle();
+  if (!h) throw std::runtime_error("DisparityConfidence: the matcher has no handle yet (plan it or match once)");
+  const int rows = disp_l.rows, cols = disp_l.cols;
+  if (rows <= 0 || cols <= 0) throw std::invalid_argument("DisparityConfidence: empty map");
+  SameSize(rows, cols, left.rows, left.cols, "DisparityConfidence");
+  SameSize(rows, cols, right.rows, right.cols, "DisparityConfidence");
+  if (disp_r) SameSize(rows, cols, disp_r->rows, disp_r->cols, "DisparityConfidence");
+  if (left.step != (size_t)cols || right.step != (size_t)cols) throw std::invalid_argument("DisparityConfidence: the images must be packed");
+  // the matcher's handle, not the imaging context's: every buffer is freed on every way out
+  struct Buffers {
+    pm_handle* h;
+    std::vector<void*> p;
+    ~Buffers() {
+      for (void* q : p) pm_device_free(h, q);
+    }
+    void Check(int status, const char* what) const {
+      if (status != PM_OK) throw std::runtime_error(std::string(what) + ": " + pm_status_string(status) + " -- " + pm_last_error(h));
+    }
+    void* Put(const void* src, size_t bytes) {
+      void* q = nullptr;
+      Check(pm_device_malloc(h, bytes, &q), "pm_device_malloc");
+      p.push_back(q);
+      if (src) Check(pm_upload(h, q, src, bytes), "pm_upload");
+      return q;
+    }
+  } dev{h, {}};
+  const size_t px = (size_t)rows * cols;
+  const uint8_t* d_left = static_cast<const uint8_t*>(dev.Put(left.data(), px));
+  const uint8_t* d_right = static_cast<const uint8_t*>(dev.Put(right.data(), px));
+  float* d_disp = static_cast<float*>(dev.Put(disp_l.data(), 4 * px));
+  const float* d_disp_r = disp_r ? static_cast<const float*>(dev.Put(disp_r->data(), 4 * px)) : nullptr;
+  float* d_measures = measures ? static_cast<float*>(dev.Put(nullptr, 16 * px)) : nullptr;
+  uint8_t* d_flags = flags ? static_cast<uint8_t*>(dev.Put(nullptr, px)) : nullptr;
+  const pm_confidence_options opt = {options.patch_w,    options.patch_h,     options.max_cost,           options.min_margin,
+                                     options.min_bg_margin, options.max_lr_diff, options.drop_unmeasured ? 1 : 0};
+  int counts[3] = {-1, -1, -1};
+  dev.Check(pm_disparity_confidence(h, &opt, d_left, d_right, d_disp, d_disp_r, rows, cols,
+                                    out ? d_disp : nullptr /* in place on the device */, d_measures, d_flags, nullptr, counts),
+            "pm_disparity_confidence");
+  auto fetch = [&](auto* image, const void* d_src, size_t bytes) {
+    if (image->rows != rows || image->cols != cols) image->create(rows, cols);
+    dev.Check(pm_download(h, image->data(), d_src, bytes), "pm_download");
+  };
+  if (out) fetch(out, d_disp, 4 * px);
+  if (measures) {
+    fetch(&measures->cost, d_measures, 4 * px);
+    fetch(&measures->margin, d_measures + px, 4 * px);
+    fetch(&measures->bg_margin, d_measures + 2 * px, 4 * px);
+    fetch(&measures->lr, d_measures + 3 * px, 4 * px);
+  }
+  if (flags) fetch(flags, d_flags, px);
+  return {{counts[0], counts[1], counts[2]}};
+}
+
 core::Image<core::Vec3f> DisparityNormals(const core::Image<float>& disp, const StereoModel& model, const NormalsFit& fit,
                                           core::Image<uint8_t>* support) {
   if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("DisparityNormals: empty map");

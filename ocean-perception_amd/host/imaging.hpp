@@ -15,6 +15,7 @@
 #pragma once
 
 #include <array>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -199,6 +200,31 @@ std::array<int, 2> FilterConsistency(pm::PatchmatchGpu& matcher, const StereoMod
                                      const ConsistencyOptions& options, const core::Image<float>& disp,
                                      core::Image<float>* out, core::Image<uint16_t>* classes = nullptr,
                                      core::Image<float>* residual = nullptr);
+
+// Matching confidence of a left disparity map over its rectified 8-bit pair (pm/imaging.h: pm_disparity_confidence;
+// definition: tests/confidence_ref.py).  The matching functor of the matcher's handle is evaluated again at d, at d - 1 and
+// d + 1 and at the background hypothesis 0 over a patch_w x patch_h window; with disp_r the left-right residual is read too.
+// A measured pixel (d > 0, the window inside the image, d <= x - patch_w / 2) is kept iff it passes every threshold.
+struct ConfidenceOptions {  // pm_confidence_options
+  int patch_w = 7, patch_h = 7;                 // odd, 3 .. PM_MAX_PATCH
+  float max_cost = HUGE_VALF;                   // cost(d) <= max_cost
+  float min_margin = -HUGE_VALF;                // min(cost(d - 1), cost(d + 1)) - cost(d) >= min_margin
+  float min_bg_margin = -HUGE_VALF;             // cost(0) - cost(d) >= min_bg_margin
+  float max_lr_diff = HUGE_VALF;                // |disp_r(y, x - d) - d| <= max_lr_diff, read only with disp_r
+  bool drop_unmeasured = false;                 // also zero the pixels > 0 that are not measured
+};
+struct ConfidenceMeasures {  // the four planes of d_measures; a pixel that is not measured holds -1, 0, 0, +inf
+  core::Image<float> cost, margin, bg_margin, lr;
+};
+// out: the map with the measured pixels that fail zeroed (may be &disp_l); measures: the four measures; flags: PM_CONF_* bits
+// per pixel; each where it is asked for.  disp_r may be null.  Returns {pixels > 0, measured pixels, kept pixels}.  The matcher
+// must have planned its handle.  Throws std::invalid_argument where the sizes differ or an image is not packed and
+// std::runtime_error where pm_disparity_confidence refuses.
+std::array<int, 3> DisparityConfidence(pm::PatchmatchGpu& matcher, const core::Image<uint8_t>& left,
+                                       const core::Image<uint8_t>& right, const ConfidenceOptions& options,
+                                       const core::Image<float>& disp_l, const core::Image<float>* disp_r,
+                                       core::Image<float>* out, ConfidenceMeasures* measures = nullptr,
+                                       core::Image<uint8_t>* flags = nullptr);
 
 }  // namespace imaging
 }  // namespace bm

@@ -49,6 +49,7 @@ EXPORTS = [
     "pm_grid_mesh", "pm_debug_mesh_constants",
     "pm_reproject_disparity", "pm_debug_reproject_constants",
     "pm_filter_consistency",
+    "pm_disparity_confidence", "pm_debug_confidence_constants",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
     "pm_debug_match_plan",
     "pm_debug_sweep_plan", "pm_debug_segment_bounds", "pm_debug_propagate_hinted", "pm_debug_match_sweep_hint", "pm_debug_read_stops", "pm_debug_noise_cost_constants", "pm_debug_noise_cost", "pm_debug_remove_background",
@@ -265,6 +266,21 @@ class PmConsistencyOptions(C.Structure):  # pm_filter_consistency
     _fields_ = [("max_diff", C.c_float), ("radius", C.c_int), ("min_consistent", C.c_int), ("max_conflicts", C.c_int)]
 
 
+PM_CONF_MEASURED, PM_CONF_FAIL_COST, PM_CONF_FAIL_MARGIN, PM_CONF_FAIL_BG, PM_CONF_FAIL_LR = 1, 2, 4, 8, 16
+
+
+class PmConfidenceOptions(C.Structure):  # pm_disparity_confidence
+    _fields_ = [("patch_w", C.c_int), ("patch_h", C.c_int), ("max_cost", C.c_float), ("min_margin", C.c_float),
+                ("min_bg_margin", C.c_float), ("max_lr_diff", C.c_float), ("drop_unmeasured", C.c_int)]
+
+
+def confidence_constants():
+    """pm_debug_confidence_constants: (tile columns, tile rows, target columns held in LDS) of k_confidence."""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    load().pm_debug_confidence_constants(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
 def reproject_constants():
     """pm_debug_reproject_constants: (tile_w, tile_h) of the close + count launch."""
     a, b = C.c_int(0), C.c_int(0)
@@ -455,6 +471,11 @@ def load():
                                           C.POINTER(vp), C.POINTER(PmMotion), C.c_int, C.c_int, vp, vp, vp, vp,
                                           C.POINTER(C.c_int)]
     lib.pm_filter_consistency.restype = C.c_int
+    lib.pm_disparity_confidence.argtypes = [vp, C.POINTER(PmConfidenceOptions), vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp,
+                                            C.POINTER(C.c_int)]
+    lib.pm_disparity_confidence.restype = C.c_int
+    lib.pm_debug_confidence_constants.argtypes = [C.POINTER(C.c_int)] * 3
+    lib.pm_debug_confidence_constants.restype = None
     lib.pm_device_malloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     lib.pm_device_free.argtypes = [vp, vp]
     lib.pm_upload.argtypes = [vp, vp, vp, C.c_size_t]
@@ -1083,6 +1104,22 @@ class Engine:
                                                    d_out, d_classes, d_residual, d_counts, n if want_counts else None),
                     "pm_filter_consistency")
         return (n[0], n[1]) if want_counts else None
+
+    def disparity_confidence(self, d_left, d_right, d_disp_l, d_disp_r, rows, cols, patch_w=5, patch_h=None,
+                             max_cost=float("inf"), min_margin=float("-inf"), min_bg_margin=float("-inf"),
+                             max_lr_diff=float("inf"), drop_unmeasured=0, d_out=None, d_measures=None, d_flags=None,
+                             d_counts=None, want_counts=False):
+        """pm_disparity_confidence (raw device addresses): the matching confidence of the left map d_disp_l over the rectified
+        8-bit pair d_left / d_right, with the right map d_disp_r where given, on the handle's stream.  d_out [rows][cols]
+        float32 (may be d_disp_l), d_measures [4][rows][cols] float32 (c0, margin, bg_margin, lr), d_flags uint8, d_counts
+        three device ints, each where given.  -> (valid, measured, kept) with want_counts (the call then synchronises)."""
+        o = PmConfidenceOptions(patch_w, patch_w if patch_h is None else patch_h, max_cost, min_margin, min_bg_margin,
+                                max_lr_diff, drop_unmeasured)
+        n = (C.c_int * 3)(-1, -1, -1)
+        self._check(self.lib.pm_disparity_confidence(self.h, C.byref(o), d_left, d_right, d_disp_l, d_disp_r, rows, cols, d_out,
+                                                     d_measures, d_flags, d_counts, n if want_counts else None),
+                    "pm_disparity_confidence")
+        return (n[0], n[1], n[2]) if want_counts else None
 
     def normalize(self, d_bgr, rows, cols, d_out):
         self._check(self.lib.pm_normalize(self.h, d_bgr, rows, cols, d_out), "pm_normalize")
