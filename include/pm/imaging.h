@@ -549,6 +549,75 @@ int pm_disparity_confidence(pm_handle* h, const pm_confidence_options* options,
                             int* d_counts     /* device int[3], may be NULL */,
                             int* counts       /* host int[3], may be NULL: non-NULL synchronises like pm_point_cloud's count */);
 
+/* ---- sequence fusion: the newest left map refined by, and filled from, earlier maps of the sequence ---------------------------
+ * What it is for: pm_reproject_disparity carries a map forward and pm_filter_consistency removes what earlier frames
+ * contradict; neither improves a value or recovers a lost one.  The per-frame noise of a PatchMatch map is independent between
+ * frames, so this stage averages, per pixel of the CURRENT left map, the observations the n earlier left maps made of the same
+ * surface (visibility-based fusion of multi-view PatchMatch), and gives a pixel that lost its value in this frame (cross-check,
+ * background mask, confidence filter) the value the earlier frames agree on.  It sits behind pm_disparity_confidence and in
+ * front of pm_filter_speckles / pm_point_cloud / pm_grid_mesh.
+ * Held to its CPU definition (tests/fuse_ref.py) BIT FOR BIT.  Binary64 unless it says binary32, one rounding per operation,
+ * parentheses as written; fxB = fx * baseline formed once:
+ *   motions    pm_filter_consistency's: motions[k] is X_src_k = R X_cur + t between the LEFT camera frames.
+ *   refine     every valid pixel (d = D(y, x) > 0) is carried into each source with EXACTLY pm_filter_consistency's project, tap
+ *              and class (max_diff, radius).  Z = fxB / (double)d and Zn are the values `project` formed.  A CONSISTENT source
+ *              k, with ds the chosen tap's value, observes   Zs = fxB / (double)ds;  g = Zn - t2;  Zo = ((Zs - t2) * Z) / g;
+ *              o_k = fxB / Zo   -- Zo is the depth along the pixel's own ray at which source k would have measured ds (Zn is
+ *              affine in Z along a ray; no inverse motion is needed).  It TAKES PART iff g > 0, Zo > 0, o_k is finite and its
+ *              weight is > 0; otherwise the source counts for its class and contributes nothing.
+ *   weights    optional float planes, d_weight for the current map and d_source_weights[k] per source, the latter read at the
+ *              chosen tap; a NULL plane (or a NULL d_source_weights) is 1.0 everywhere.  w counts as (double)w iff it is
+ *              finite and > 0; 0, negatives, NaN and +-inf are 0 and that observation does not take part -- the margin plane
+ *              of pm_disparity_confidence's d_measures can be passed as it is.
+ *   sums       num = w0 * (double)d, den = w0; then over k = 0 .. n - 1 in order, the sources that take part:
+ *              num = num + (w_k * o_k), den = den + w_k.  omin / omax over (double)d where w0 > 0 and the o_k that take part.
+ *   KEPT       pm_filter_consistency's rule: valid, n_cons >= min_consistent, n_conf <= max_conflicts (min_consistent = 0
+ *              with max_conflicts = 8 removes nothing).
+ *   d_out      valid, not KEPT: +0.0f, and it is never filled;  KEPT and den > 0: (float)(num / den);  KEPT otherwise: the
+ *              input bits.  May equal d_disp unless d_disp is itself a source.
+ *   d_count    uint8: the observations that took part, the pixel's own included where w0 > 0: 0 .. 9.
+ *   d_spread   (float)(omax - omin), +0.0 where d_count is 0.
+ *   NaN        a quotient or difference that is NaN (only a valid pixel that is +inf makes one) is stored as 0x7FC00000.
+ *   fill       only with fill_min_sources >= 1; with 0 an invalid pixel keeps its input bits and no splat runs.  The inverse
+ *              of motions[k] is formed on the host:  Rinv[3i+j] = R[3j+i];  tinv_i = -(((R[i]*t0) + (R[3+i]*t1)) + (R[6+i]*t2))
+ *              (R is still not checked).  S_k is EXACTLY pm_reproject_disparity's `splat` of source k through (Rinv, tinv) with
+ *              min_disp = max_disp = 0 and no close: the nearest surface wins.  At an invalid pixel (d not > 0: 0, -0.0,
+ *              negatives, NaN):  c_k = S_k(y, x) is a candidate iff c_k > 0;  m = the binary32 maximum of the candidates;
+ *              source k SUPPORTS iff c_k > 0 and fabs((double)c_k - (double)m) <= (double)fill_max_diff;  FILLED iff the
+ *              number of supporters n_sup >= fill_min_sources;  then acc from +0.0 in k order over the supporters,
+ *              acc = acc + (double)c_k;  d_out = (float)(acc / (double)n_sup);  d_count = n_sup;
+ *              d_spread = (float)((double)m - (double)(the smallest supporter)).  An invalid pixel that is not filled keeps its
+ *              input bits (pm_filter_speckles' rule), with d_count 0 and d_spread +0.0.  Weights play no part in a fill: a
+ *              caller who distrusts a source's pixels passes that source already filtered.
+ *   d_flags    uint8: PM_FUSE_VALID, PM_FUSE_KEPT, PM_FUSE_FUSED (kept, and at least one SOURCE observation took part),
+ *              PM_FUSE_FILLED.
+ *   counts     [0] valid, [1] kept, [2] fused, [3] filled pixels.
+ * Every output is optional, but at least one must be given.  A source may be d_disp itself.  Valid in every mode of the
+ * handle: it reads maps, not the handle's state.  It enqueues on the handle's stream; a non-NULL `counts` synchronises it like
+ * pm_point_cloud's `count`, otherwise the call only enqueues.  d_sources, motions and d_source_weights are HOST arrays of
+ * n_sources entries, read before the call returns.  One memset and one launch, two launches when filling; only integer maximum
+ * and integer addition cross workgroups, so every output is a pure function of the inputs.  Scratch (16 bytes of counts and,
+ * when filling, n_sources maps of 4 bytes per pixel) is ONE allocation, made on first use, reused, grown under a stream
+ * synchronisation and released with the handle, so a size must have run once before it is captured.
+ * PM_ERR_INVALID_ARG, with pm_last_error naming the argument and nothing enqueued: everything pm_filter_consistency refuses;
+ * fill_min_sources outside 0..n_sources; a fill_max_diff that is not finite or < 0; d_out, d_count, d_spread or d_flags equal
+ * to a source or to a source's weight plane.  PM_ERR_SIZE as for pm_backproject. */
+enum { PM_FUSE_VALID = 1, PM_FUSE_KEPT = 2, PM_FUSE_FUSED = 4, PM_FUSE_FILLED = 8 };
+typedef struct pm_fuse_options {
+  float max_diff; int radius; int min_consistent; int max_conflicts;   /* pm_consistency_options' four          */
+  int   fill_min_sources;                                              /* 0: no fill; else 1 .. n_sources       */
+  float fill_max_diff;                                                 /* finite, >= 0                          */
+} pm_fuse_options;
+int pm_fuse_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_fuse_options* options,
+                      const float* d_disp, const float* d_weight /* may be NULL */, int n_sources,
+                      const float* const* d_sources /* host array of device maps */, const pm_motion* motions /* host array */,
+                      const float* const* d_source_weights /* host array, may be NULL, entries may be NULL */,
+                      int rows, int cols,
+                      float* d_out /* may be NULL, may equal d_disp */, uint8_t* d_count /* may be NULL */,
+                      float* d_spread /* may be NULL */, uint8_t* d_flags /* may be NULL */,
+                      int* d_counts /* device int[4], may be NULL */,
+                      int* counts /* host int[4], may be NULL: non-NULL synchronises like pm_point_cloud's count */);
+
 /* ---- device buffers for host code that does not include HIP (host/imaging.hpp uses them) ------------------
  * pm_device_malloc / pm_device_free wrap hipMalloc / hipFree on the handle's device; pm_upload / pm_download are
  * stream-ordered copies on the handle's stream from / to pageable host memory (pm_download returns after the

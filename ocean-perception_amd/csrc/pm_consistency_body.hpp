@@ -46,9 +46,12 @@ struct ConsistencyArgs {
 
 // The class of a pixel that lands on (iu, iv) of `map` with disparity dp there (`seen`: it does land), and |e| of the
 // chosen tap in *abs_e: the first tap of the (2 RADIUS + 1)^2 window, row-major, with the smallest |ds - dp| in binary64.
+// Where asked for (pm_fuse_disparity, pm_fuse_body.hpp), the chosen tap's ds in *tap_ds and its index in `map` in *tap_at; 0.f
+// and 0 where the class is UNSEEN.
 template <int RADIUS>
 __host__ __device__ __forceinline__ unsigned consistency_class(const float* map, int rows, int cols, bool seen, int iu, int iv,
-                                                               float dp, double md, double* abs_e) {
+                                                               float dp, double md, double* abs_e, float* tap_ds = nullptr,
+                                                               size_t* tap_at = nullptr) {
   constexpr int W = 2 * RADIUS + 1;
   float ds[W * W];
 #pragma unroll
@@ -62,6 +65,8 @@ __host__ __device__ __forceinline__ unsigned consistency_class(const float* map,
     }
   bool found = false;
   double e = 0.0, best = 0.0;
+  float chosen = 0.f;
+  int at = 0;
 #pragma unroll
   for (int i = 0; i < W * W; ++i) {  // then the choice, in row-major order
     const double ek = (double)ds[i] - (double)dp;
@@ -69,9 +74,13 @@ __host__ __device__ __forceinline__ unsigned consistency_class(const float* map,
     const bool take = ds[i] > 0.f && (!found || ak < best);  // a later tap replaces only with a strictly smaller |e|
     e = take ? ek : e;
     best = take ? ak : best;
+    chosen = take ? ds[i] : chosen;
+    at = take ? i : at;
     found = found || take;
   }
   *abs_e = best;
+  if (tap_ds) *tap_ds = chosen;  // a counting tap lies inside the image: the index below is one of `map`
+  if (tap_at) *tap_at = found ? (size_t)(iv + at / W - RADIUS) * cols + (iu + at % W - RADIUS) : (size_t)0;
   if (!found) return kConsistencyUnseen;
   return best <= md ? kConsistencyConsistent : e > md ? kConsistencyOccluded : kConsistencyConflict;
 }

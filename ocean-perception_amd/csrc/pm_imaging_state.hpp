@@ -52,6 +52,9 @@ struct ImagingState {
   // pm_disparity_confidence: kConfidenceHeader words ([0] valid, [1] measured, [2] kept pixels; cleared per call), then the
   // right image's gradient (one float per pixel), then the left image's saturated gradient (one byte per pixel)
   DevBuf<int> confidence_buf;
+  // pm_fuse_disparity: kFuseHeader words ([0] valid, [1] kept, [2] fused, [3] filled pixels), then, for a call that fills,
+  // one splat map of one word per pixel for each source; the memset of a call clears all of it
+  DevBuf<unsigned> fuse_buf;
 };
 
 #define PM_HIP(h, call)                                                                                     \

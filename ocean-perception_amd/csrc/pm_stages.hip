@@ -1,6 +1,6 @@
 // pm_stages.hip -- C-ABI implementation of the stages of include/pm/imaging.h that read a finished disparity map: points,
 // plane-mode normals and the compacted cloud, the windowed plane fit, the speckle filter, the grid mesh, the temporal
-// seeds, the consistency filter and the matching confidence.  Like pm_imaging.hip it reaches the handle only through pm_internal.hpp, and it shares
+// seeds, the consistency filter, the matching confidence and the sequence fusion.  Like pm_imaging.hip it reaches the handle only through pm_internal.hpp, and it shares
 // that unit's one state object (pm_imaging_state.hpp).  Every entry point: its argument checks in a fixed order (the first
 // fault is the one reported), then the device, then its launches on the handle's stream.
 #include "pm/imaging.h"
@@ -14,6 +14,7 @@
 #include "pm_cloud.hpp"
 #include "pm_confidence.hpp"
 #include "pm_consistency.hpp"
+#include "pm_fuse.hpp"
 #include "pm_imaging_state.hpp"
 #include "pm_mesh.hpp"
 #include "pm_normals_fit.hpp"
@@ -106,7 +107,7 @@ int stage_begin(pm_handle* h, const char* what, ImagingState** st, hipStream_t* 
   return PM_OK;
 }
 
-// Behind the launches of a stage that counts: the `n` (1 to 3) device totals go to the device destination and to the
+// Behind the launches of a stage that counts: the `n` (1 to 4) device totals go to the device destination and to the
 // host destination where given; the host copy has landed when this returns.
 int stage_counts(pm_handle* h, hipStream_t stream, const int* d_totals, int n, int* d_dst, int* dst) {
   if (d_dst) PM_HIP(h, hipMemcpyAsync(d_dst, d_totals, n * sizeof(int), hipMemcpyDeviceToDevice, stream));
@@ -621,4 +622,120 @@ void pm_debug_confidence_constants(int* tile_w, int* tile_h, int* target_cols) {
   if (tile_w) *tile_w = kConfTileW;
   if (tile_h) *tile_h = kConfTileH;
   if (target_cols) *target_cols = kConfTileRW;
+}
+
+// ---- sequence fusion: a map refined by, and filled from, earlier maps of its sequence (pm_fuse.hpp) ---------------------------
+namespace {
+constexpr size_t kFuseHeader = 4;  // the four counts: 16 bytes in front of the splat maps
+
+template <int RADIUS>
+void launch_fuse(const FuseArgs& a, dim3 grid, hipStream_t stream) {
+  hipLaunchKernelGGL(k_fuse<RADIUS>, grid, dim3(kFuseBlockX, kFuseBlockY), 0, stream, a);
+}
+}  // namespace
+
+int pm_fuse_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_fuse_options* options, const float* d_disp,
+                      const float* d_weight, int n_sources, const float* const* d_sources, const pm_motion* motions,
+                      const float* const* d_source_weights, int rows, int cols, float* d_out, uint8_t* d_count,
+                      float* d_spread, uint8_t* d_flags, int* d_counts, int* counts) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_fuse_disparity";
+  if (int rc = check_cloud_camera(h, what, camera)) return rc;
+  if (!options || !d_disp || !d_sources || !motions) {
+    set_err(h, "%s: null %s", what, !options ? "options" : !d_disp ? "d_disp" : !d_sources ? "d_sources" : "motions");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (n_sources < 1 || n_sources > kFuseMaxSources) {
+    set_err(h, "%s: n_sources %d outside 1..%d", what, n_sources, kFuseMaxSources);
+    return PM_ERR_INVALID_ARG;
+  }
+  for (int k = 0; k < n_sources; ++k) {
+    if (!d_sources[k]) {
+      set_err(h, "%s: null d_sources[%d]", what, k);
+      return PM_ERR_INVALID_ARG;
+    }
+    for (int i = 0; i < 12; ++i)
+      if (!std::isfinite(i < 9 ? motions[k].R[i] : motions[k].t[i - 9])) {
+        set_err(h, "%s: %s[%d] of motions[%d] is not finite", what, i < 9 ? "R" : "t", i < 9 ? i : i - 9, k);
+        return PM_ERR_INVALID_ARG;
+      }
+  }
+  if (int rc = check_max_diff(h, what, options->max_diff)) return rc;
+  if (options->radius < 0 || options->radius > kFuseMaxRadius) {
+    set_err(h, "%s: radius %d outside 0..%d", what, options->radius, kFuseMaxRadius);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (options->min_consistent < 0 || options->min_consistent > n_sources) {
+    set_err(h, "%s: min_consistent %d outside 0..n_sources (%d)", what, options->min_consistent, n_sources);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (options->max_conflicts < 0 || options->max_conflicts > kFuseMaxSources) {
+    set_err(h, "%s: max_conflicts %d outside 0..%d", what, options->max_conflicts, kFuseMaxSources);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (options->fill_min_sources < 0 || options->fill_min_sources > n_sources) {
+    set_err(h, "%s: fill_min_sources %d outside 0..n_sources (%d)", what, options->fill_min_sources, n_sources);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (!std::isfinite(options->fill_max_diff) || options->fill_max_diff < 0.f) {
+    set_err(h, "%s: fill_max_diff must be finite and >= 0", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
+  if (!d_out && !d_count && !d_spread && !d_flags && !d_counts && !counts) {
+    set_err(h, "%s: no output: d_out, d_count, d_spread, d_flags, d_counts and counts are all null", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  const void* const outs[4] = {d_out, d_count, d_spread, d_flags};
+  static const char* const out_names[4] = {"d_out", "d_count", "d_spread", "d_flags"};
+  for (int o = 0; o < 4; ++o)
+    for (int k = 0; outs[o] && k < n_sources; ++k) {  // a pixel of a source is read by other pixels' lookups
+      const bool map = outs[o] == d_sources[k];
+      if (map || (d_source_weights && outs[o] == d_source_weights[k])) {
+        set_err(h, "%s: %s must not alias %s[%d]", what, out_names[o], map ? "d_sources" : "d_source_weights", k);
+        return PM_ERR_INVALID_ARG;
+      }
+    }
+  ImagingState* st = nullptr;
+  hipStream_t stream = nullptr;
+  if (int rc = stage_begin(h, what, &st, &stream)) return rc;
+  const bool fill = options->fill_min_sources >= 1;
+  const size_t px = (size_t)rows * cols;
+  const size_t words = kFuseHeader + (fill ? (size_t)n_sources * px : 0);
+  PM_HIP(h, st->fuse_buf.reserve(sizeof(unsigned) * words, stream));
+  unsigned* base = st->fuse_buf.get();
+  unsigned* d_splat = base + kFuseHeader;
+  FuseArgs a = {};
+  a.cam = cloud_cam(*camera);
+  a.disp = d_disp, a.weight = d_weight, a.rows = rows, a.cols = cols, a.n = n_sources;
+  a.max_diff = options->max_diff, a.min_consistent = options->min_consistent, a.max_conflicts = options->max_conflicts;
+  a.fill_min_sources = options->fill_min_sources, a.fill_max_diff = options->fill_max_diff;
+  a.splat = d_splat, a.px = px;
+  a.out = d_out, a.count = d_count, a.spread = d_spread, a.flags = d_flags, a.counts = reinterpret_cast<int*>(base);
+  FuseSplatArgs sa = {};
+  sa.cam = a.cam, sa.rows = rows, sa.cols = cols, sa.splat = d_splat, sa.px = px;
+  for (int k = 0; k < n_sources; ++k) {
+    const double* R = motions[k].R;
+    const double* t = motions[k].t;
+    for (int i = 0; i < 9; ++i) a.src[k].R[i] = R[i];
+    for (int i = 0; i < 3; ++i) a.src[k].t[i] = t[i];
+    a.src[k].map = d_sources[k];
+    a.src[k].weight = d_source_weights ? d_source_weights[k] : nullptr;
+    for (int i = 0; i < 3; ++i) {  // the inverse of a rigid motion, in binary64 (not contracted: -ffp-contract=off)
+      for (int j = 0; j < 3; ++j) sa.src[k].R[3 * i + j] = R[3 * j + i];
+      sa.src[k].t[i] = -(((R[i] * t[0]) + (R[3 + i] * t[1])) + (R[6 + i] * t[2]));
+    }
+    sa.src[k].map = d_sources[k];
+  }
+  PM_HIP(h, hipMemsetAsync(base, 0, sizeof(unsigned) * words, stream));
+  const dim3 block(kFuseBlockX, kFuseBlockY);
+  const dim3 grid((unsigned)((cols + kFuseSpan - 1) / kFuseSpan), (unsigned)((rows + kFuseBlockY - 1) / kFuseBlockY));
+  if (fill) hipLaunchKernelGGL(k_fuse_splat, dim3(grid.x, grid.y, (unsigned)n_sources), block, 0, stream, sa);
+  switch (options->radius) {
+    case 0: launch_fuse<0>(a, grid, stream); break;
+    case 1: launch_fuse<1>(a, grid, stream); break;
+    default: launch_fuse<2>(a, grid, stream); break;
+  }
+  if (int rc = launch_check(h, "fuse disparity")) return rc;
+  return stage_counts(h, stream, reinterpret_cast<const int*>(base), 4, d_counts, counts);
 }

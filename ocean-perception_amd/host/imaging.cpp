@@ -598,6 +598,74 @@ std::array<int, 3> DisparityConfidence(pm::PatchmatchGpu& matcher, const core::I
   return {{counts[0], counts[1], counts[2]}};
 }
 
+std::array<int, 4> FuseDisparity(pm::PatchmatchGpu& matcher, const StereoModel& model,
+                                 const std::vector<core::Image<float>>& sources, const std::vector<Motion>& motions,
+                                 const FuseOptions& options, const core::Image<float>& disp, const core::Image<float>* weight,
+                                 const std::vector<core::Image<float>>& source_weights, core::Image<float>* out,
+                                 core::Image<uint8_t>* count, core::Image<float>* spread, core::Image<uint8_t>* flags) {
+  pm_handle* h = matcher.handle();
+  if (!h) throw std::runtime_error("FuseDisparity: the matcher has no handle yet (plan it or match once)");
+  const int rows = disp.rows, cols = disp.cols;
+  if (rows <= 0 || cols <= 0) throw std::invalid_argument("FuseDisparity: empty map");
+  if (sources.size() != motions.size()) throw std::invalid_argument("FuseDisparity: one motion per source");
+  if (!source_weights.empty() && source_weights.size() != sources.size())
+    throw std::invalid_argument("FuseDisparity: source_weights is empty or has one entry per source");
+  for (const core::Image<float>& s : sources) SameSize(rows, cols, s.rows, s.cols, "FuseDisparity");
+  if (weight) SameSize(rows, cols, weight->rows, weight->cols, "FuseDisparity");
+  for (const core::Image<float>& w : source_weights)
+    if (w.rows != 0 || w.cols != 0) SameSize(rows, cols, w.rows, w.cols, "FuseDisparity");
+  // the matcher's handle, not the imaging context's: every buffer is freed on every way out
+  struct Buffers {
+    pm_handle* h;
+    std::vector<void*> p;
+    ~Buffers() {
+      for (void* q : p) pm_device_free(h, q);
+    }
+    void Check(int status, const char* what) const {
+      if (status != PM_OK) throw std::runtime_error(std::string(what) + ": " + pm_status_string(status) + " -- " + pm_last_error(h));
+    }
+    void* Put(const void* src, size_t bytes) {
+      void* q = nullptr;
+      Check(pm_device_malloc(h, bytes, &q), "pm_device_malloc");
+      p.push_back(q);
+      if (src) Check(pm_upload(h, q, src, bytes), "pm_upload");
+      return q;
+    }
+  } dev{h, {}};
+  const size_t px = (size_t)rows * cols;
+  float* d_disp = static_cast<float*>(dev.Put(disp.data(), 4 * px));
+  const float* d_weight = weight ? static_cast<const float*>(dev.Put(weight->data(), 4 * px)) : nullptr;
+  std::vector<const float*> d_sources, d_weights;
+  std::vector<pm_motion> m(motions.size());
+  for (size_t k = 0; k < sources.size(); ++k) {
+    d_sources.push_back(static_cast<const float*>(dev.Put(sources[k].data(), 4 * px)));
+    const bool has = !source_weights.empty() && source_weights[k].rows != 0;
+    d_weights.push_back(has ? static_cast<const float*>(dev.Put(source_weights[k].data(), 4 * px)) : nullptr);
+    for (size_t i = 0; i < 9; ++i) m[k].R[i] = motions[k].R[i];
+    for (size_t i = 0; i < 3; ++i) m[k].t[i] = motions[k].t[i];
+  }
+  uint8_t* d_count = count ? static_cast<uint8_t*>(dev.Put(nullptr, px)) : nullptr;
+  float* d_spread = spread ? static_cast<float*>(dev.Put(nullptr, 4 * px)) : nullptr;
+  uint8_t* d_flags = flags ? static_cast<uint8_t*>(dev.Put(nullptr, px)) : nullptr;
+  const pm_cloud_camera cam = CloudCamera(model);
+  const pm_fuse_options opt = {options.max_diff,      options.radius,           options.min_consistent,
+                               options.max_conflicts, options.fill_min_sources, options.fill_max_diff};
+  int counts[4] = {-1, -1, -1, -1};
+  dev.Check(pm_fuse_disparity(h, &cam, &opt, d_disp, d_weight, (int)sources.size(), d_sources.data(), m.data(),
+                              source_weights.empty() ? nullptr : d_weights.data(), rows, cols,
+                              out ? d_disp : nullptr /* in place on the device */, d_count, d_spread, d_flags, nullptr, counts),
+            "pm_fuse_disparity");
+  auto fetch = [&](auto* image, const void* d_src, size_t bytes) {
+    if (image->rows != rows || image->cols != cols) image->create(rows, cols);
+    dev.Check(pm_download(h, image->data(), d_src, bytes), "pm_download");
+  };
+  if (out) fetch(out, d_disp, 4 * px);
+  if (count) fetch(count, d_count, px);
+  if (spread) fetch(spread, d_spread, 4 * px);
+  if (flags) fetch(flags, d_flags, px);
+  return {{counts[0], counts[1], counts[2], counts[3]}};
+}
+
 core::Image<core::Vec3f> DisparityNormals(const core::Image<float>& disp, const StereoModel& model, const NormalsFit& fit,
                                           core::Image<uint8_t>* support) {
   if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("DisparityNormals: empty map");

@@ -226,5 +226,30 @@ std::array<int, 3> DisparityConfidence(pm::PatchmatchGpu& matcher, const core::I
                                        core::Image<float>* out, ConfidenceMeasures* measures = nullptr,
                                        core::Image<uint8_t>* flags = nullptr);
 
+// Along a sequence: the CURRENT left map refined by, and filled from, earlier left maps of the same size and camera, each
+// reached through the motion X_src = R X_cur + t -- RelativeMotion(T_world_cur, T_world_src) (pm/imaging.h:
+// pm_fuse_disparity; definition: tests/fuse_ref.py).  A kept pixel > 0 becomes the weighted mean of itself and of what the
+// consistent sources observed along its ray; with fill_min_sources >= 1 a pixel without a value takes the mean of the sources
+// that agree, within fill_max_diff, with the nearest surface they carry to it.
+struct FuseOptions {  // pm_fuse_options
+  float max_diff = 1.f;      // finite, >= 0
+  int radius = 1;            // 0..2
+  int min_consistent = 1;    // 0..sources.size()
+  int max_conflicts = 0;     // 0..8
+  int fill_min_sources = 0;  // 0: no fill; else 1..sources.size()
+  float fill_max_diff = 1.f;  // finite, >= 0
+};
+// Host images in, host images out, on the matcher's own handle and stream.  weight: the current map's weight plane, may be
+// null; source_weights: empty, or one entry per source, an empty image standing for "no plane" (1.0 everywhere).  out: the
+// fused map; count: the observations per pixel; spread: their range; flags: PM_FUSE_* bits; each where it is asked for.
+// Returns {pixels > 0, kept, fused, filled}.  The matcher must have planned its handle.  Throws std::invalid_argument where
+// the sizes differ and std::runtime_error where pm_fuse_disparity refuses.
+std::array<int, 4> FuseDisparity(pm::PatchmatchGpu& matcher, const StereoModel& model,
+                                 const std::vector<core::Image<float>>& sources, const std::vector<Motion>& motions,
+                                 const FuseOptions& options, const core::Image<float>& disp, const core::Image<float>* weight,
+                                 const std::vector<core::Image<float>>& source_weights, core::Image<float>* out,
+                                 core::Image<uint8_t>* count = nullptr, core::Image<float>* spread = nullptr,
+                                 core::Image<uint8_t>* flags = nullptr);
+
 }  // namespace imaging
 }  // namespace bm

@@ -50,6 +50,7 @@ EXPORTS = [
     "pm_reproject_disparity", "pm_debug_reproject_constants",
     "pm_filter_consistency",
     "pm_disparity_confidence", "pm_debug_confidence_constants",
+    "pm_fuse_disparity",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
     "pm_debug_match_plan",
     "pm_debug_sweep_plan", "pm_debug_segment_bounds", "pm_debug_propagate_hinted", "pm_debug_match_sweep_hint", "pm_debug_read_stops", "pm_debug_noise_cost_constants", "pm_debug_noise_cost", "pm_debug_remove_background",
@@ -274,6 +275,14 @@ class PmConfidenceOptions(C.Structure):  # pm_disparity_confidence
                 ("min_bg_margin", C.c_float), ("max_lr_diff", C.c_float), ("drop_unmeasured", C.c_int)]
 
 
+PM_FUSE_VALID, PM_FUSE_KEPT, PM_FUSE_FUSED, PM_FUSE_FILLED = 1, 2, 4, 8
+
+
+class PmFuseOptions(C.Structure):  # pm_fuse_disparity
+    _fields_ = [("max_diff", C.c_float), ("radius", C.c_int), ("min_consistent", C.c_int), ("max_conflicts", C.c_int),
+                ("fill_min_sources", C.c_int), ("fill_max_diff", C.c_float)]
+
+
 def confidence_constants():
     """pm_debug_confidence_constants: (tile columns, tile rows, target columns held in LDS) of k_confidence."""
     a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
@@ -474,6 +483,10 @@ def load():
     lib.pm_disparity_confidence.argtypes = [vp, C.POINTER(PmConfidenceOptions), vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp,
                                             C.POINTER(C.c_int)]
     lib.pm_disparity_confidence.restype = C.c_int
+    lib.pm_fuse_disparity.argtypes = [vp, C.POINTER(PmCloudCamera), C.POINTER(PmFuseOptions), vp, vp, C.c_int, C.POINTER(vp),
+                                      C.POINTER(PmMotion), C.POINTER(vp), C.c_int, C.c_int, vp, vp, vp, vp, vp,
+                                      C.POINTER(C.c_int)]
+    lib.pm_fuse_disparity.restype = C.c_int
     lib.pm_debug_confidence_constants.argtypes = [C.POINTER(C.c_int)] * 3
     lib.pm_debug_confidence_constants.restype = None
     lib.pm_device_malloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
@@ -1120,6 +1133,26 @@ class Engine:
                                                      d_measures, d_flags, d_counts, n if want_counts else None),
                     "pm_disparity_confidence")
         return (n[0], n[1], n[2]) if want_counts else None
+
+    def fuse_disparity(self, camera, d_disp, d_sources, motions, rows, cols, max_diff=1.0, radius=1, min_consistent=1,
+                       max_conflicts=0, fill_min_sources=0, fill_max_diff=1.0, d_weight=None, d_source_weights=None, d_out=None,
+                       d_count=None, d_spread=None, d_flags=None, d_counts=None, want_counts=False):
+        """pm_fuse_disparity (raw device addresses): the current left map refined by, and with fill_min_sources >= 1 filled
+        from, the earlier maps d_sources (a sequence of device addresses) under motions (a sequence of (R, t) or PmMotion,
+        X_src = R X_cur + t), on the handle's stream.  d_weight and d_source_weights (a sequence whose entries may be None):
+        float32 weight planes, None = 1.0.  d_out [rows][cols] float32 (may be d_disp), d_count uint8, d_spread float32,
+        d_flags uint8 (PM_FUSE_*), d_counts four device ints, each where given.  -> (valid, kept, fused, filled) with
+        want_counts (the call then synchronises), else None."""
+        c = cloud_camera(camera)
+        o = PmFuseOptions(max_diff, radius, min_consistent, max_conflicts, fill_min_sources, fill_max_diff)
+        src = (C.c_void_p * len(d_sources))(*d_sources)
+        mot = (PmMotion * len(motions))(*[as_motion(m) for m in motions])
+        wts = (C.c_void_p * len(d_source_weights))(*d_source_weights) if d_source_weights is not None else None
+        n = (C.c_int * 4)(-1, -1, -1, -1)
+        self._check(self.lib.pm_fuse_disparity(self.h, _ref(c), C.byref(o), d_disp, d_weight, len(d_sources), src, mot, wts,
+                                               rows, cols, d_out, d_count, d_spread, d_flags, d_counts,
+                                               n if want_counts else None), "pm_fuse_disparity")
+        return tuple(n) if want_counts else None
 
     def normalize(self, d_bgr, rows, cols, d_out):
         self._check(self.lib.pm_normalize(self.h, d_bgr, rows, cols, d_out), "pm_normalize")
