@@ -618,6 +618,87 @@ int pm_fuse_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_fuse
                       int* d_counts /* device int[4], may be NULL */,
                       int* counts /* host int[4], may be NULL: non-NULL synchronises like pm_point_cloud's count */);
 
+/* ---- camera motion between two frames of a sequence ---------------------------------------------------------------------------
+ * What it is for: pm_reproject_disparity, pm_filter_consistency and pm_fuse_disparity take the rigid motion of the left camera
+ * as an input.  When frame k + 1 arrives, everything an estimate of it needs is on the device: the left image of frame k, its
+ * disparity map (a 3-D point per pixel) and the left image of frame k + 1.  pm_track_features picks one corner per cell of the
+ * old image, predicts where each lands in the new image under a guess of the motion, and finds it there by block matching;
+ * pm_solve_motion (host, binary64) fits the motion to the tracks by Gauss-Newton on the reprojection error with Huber weights;
+ * pm_estimate_motion runs both.  The motion is pm_reproject_disparity's: X_new = R X_old + t between the left camera frames,
+ * and can be handed to that stage unchanged.
+ * Held to its CPU definition (tests/motion_ref.py) BIT FOR BIT; the kernels select and match in exact integer arithmetic:
+ *   score      gx, gy: the 3x3 Sobel responses of the old image; Sxx, Syy, Sxy: sums of gx gx, gy gy, gx gy over the 7x7 window;
+ *              score = 16 (Sxx Syy - Sxy Sxy) - (Sxx + Syy)^2 in int64 (Harris with k = 1/16).
+ *   eligible   m = max(p, 4); m <= x <= cols - 1 - m, m <= y <= rows - 1 - m; d = D_old(y, x) finite, > 0, >= min_disp, and
+ *              <= max_disp where max_disp != 0; score >= min_score.
+ *   select     cell (cx, cy) covers x in [cx cell, min(cols, (cx + 1) cell)), y likewise; its feature is the eligible pixel of
+ *              the largest score, a tie going to the smallest y cols + x.  Features are numbered by cell, row-major: the k-th
+ *              feature is record k.
+ *   predict    pm_reproject_disparity's `splat` arithmetic through the guess: Z, X, Y; Xn, Yn, Zn; u, v; PREDICTED iff Zn > 0
+ *              and |u|, |v| < 2^30; (iu, iv) = rint, half to even, and may lie outside the image.  A record that is not
+ *              predicted has x_new = y_new = 0, sad = second = INT32_MAX and no flag.
+ *   match      candidates (qx, qy) = (iu + ex, iv + ey), ey and ex in -s .. s, row-major; a candidate COUNTS iff its (2p+1)^2
+ *              patch lies inside the new image; SAD over the patch; the best is the first of the smallest SAD; MATCHED iff a
+ *              candidate counts; `second`: the smallest SAD of a counting candidate at Chebyshev distance >= 2 from the best.
+ *              A predicted record without a counting candidate has x_new = (float)iu, y_new = (float)iv, sad = second =
+ *              INT32_MAX and PREDICTED alone.
+ *   sub-pixel  in x: iff (qx - 1, qy) and (qx + 1, qy) are candidates of the window that count, den = cm - 2 c0 + cp > 0 and
+ *              c0 > 0 (a perfect match stays on its pixel): x_new = (float)((double)qx + (double)(cm - cp) / (double)(2 den))
+ *              and SUBPIX_X; otherwise (float)qx.  Same in y.
+ *   OK         flags & (PREDICTED | MATCHED | FAIL_SAD | FAIL_GAP) == PREDICTED | MATCHED: the tracks the solve uses.
+ *   solve      binary64, one rounding per operation, in the order tests/motion_ref.py writes out.  P_i: pm_backproject's point of
+ *              (x, y, disp) before its rounding.  Per iteration, over the OK tracks in order from +0.0: Q = R P + t, skipped
+ *              unless Qz > 0; iz = 1 / Qz; a = Qx iz; b = Qy iz; ru = ((fx a) + cx) - x_new; rv likewise; e = sqrt(ru ru + rv rv);
+ *              w = 1 if e <= huber_px, else huber_px / e; J for the left perturbation Q' = Q + omega x Q + upsilon, delta =
+ *              (omega, upsilon); H += w J^T J, g += w J^T r; H delta = -g by LDL^T without pivoting, which fails iff a pivot is
+ *              not > 0; the Cayley update with a = omega / 2: dR = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a), R <- dR R,
+ *              t <- dR t + upsilon; it stops after the update when max |delta_i| < epsilon, or after `iterations`.  Under the
+ *              motion reached: n_used (Qz > 0), the inliers (e <= inlier_px) and their root-mean-square e.  info->iterations:
+ *              the updates made; info->n_tracks: the OK tracks.  valid iff no factorisation failed and n_inliers >= min_inliers.
+ * No new status code: a solve that cannot be trusted returns PM_OK with info->valid == 0 and *out equal to the guess.
+ * pm_track_features enqueues on the handle's stream and is valid in every mode of the handle.  count, d_count and capacity
+ * behave as pm_point_cloud's: the count (the number of features) is reported beyond the capacity, exactly the first `capacity`
+ * records are written, capacity == 0 only counts, a non-NULL `count` synchronises the stream.  pm_estimate_motion tracks into
+ * scratch of the handle, downloads the records and solves; it always synchronises.  pm_solve_motion needs no handle, and its
+ * status alone reports a refusal.  Scratch (16 bytes, two words per cell and, for pm_estimate_motion, one record per cell) is
+ * ONE allocation, made on first use, reused, grown under a stream synchronisation and released with the handle.
+ * PM_ERR_INVALID_ARG, with pm_last_error naming the argument and nothing enqueued: a null required pointer; a camera that
+ * pm_backproject refuses; a non-finite entry of the guess; an option outside its range below, NaN thresholds included; rows or
+ * cols < 1; no output at all; capacity < 0.  PM_ERR_SIZE as for pm_backproject. */
+typedef struct pm_track {            /* 32 bytes */
+  int32_t x, y;                      /* the feature's pixel in the OLD left image          */
+  float   disp;                      /* D_old(y, x)                                        */
+  float   x_new, y_new;              /* its position in the NEW left image, sub-pixel      */
+  int32_t sad, second;               /* best SAD; best SAD at Chebyshev distance >= 2 from it, INT32_MAX if none */
+  uint32_t flags;                    /* PM_TRACK_* */
+} pm_track;
+enum { PM_TRACK_PREDICTED = 1, PM_TRACK_MATCHED = 2, PM_TRACK_SUBPIX_X = 4, PM_TRACK_SUBPIX_Y = 8,
+       PM_TRACK_FAIL_SAD = 16, PM_TRACK_FAIL_GAP = 32 };
+typedef struct pm_track_options {
+  int cell;            /* 8..64: one feature per cell x cell pixels                         */
+  int patch_radius;    /* p, 1..7                                                           */
+  int search_radius;   /* s, 0..24                                                          */
+  int64_t min_score;   /* >= 1                                                              */
+  float min_disp, max_disp;  /* as pm_reproject_options; max_disp 0 = no limit             */
+  int max_sad;         /* >= 0, 0 = no limit: FAIL_SAD iff sad > max_sad                    */
+  int min_gap;         /* >= 0: FAIL_GAP iff second - sad < min_gap (second = INT32_MAX never fails) */
+} pm_track_options;
+typedef struct pm_solve_options { int iterations /*1..50*/; double huber_px /*>0*/; double epsilon /*>=0*/;
+                                  double inlier_px /*>0*/; int min_inliers /*>=6*/; } pm_solve_options;
+typedef struct pm_motion_info { int valid, n_tracks, n_used, n_inliers, iterations; double rms_px; } pm_motion_info;
+
+int pm_track_features(pm_handle* h, const pm_cloud_camera* camera, const pm_track_options* options,
+                      const pm_motion* guess /* NULL = identity */, const uint8_t* d_left_old, const float* d_disp_old,
+                      const uint8_t* d_left_new, int rows, int cols, int capacity, pm_track* d_tracks /* may be NULL */,
+                      int* d_count /* may be NULL */, int* count /* host, may be NULL: non-NULL synchronises */);
+int pm_solve_motion(const pm_cloud_camera* camera, const pm_solve_options* options, const pm_track* tracks /* host */, int n,
+                    const pm_motion* guess /* NULL = identity */, pm_motion* out /* may be NULL */,
+                    pm_motion_info* info /* may be NULL */);      /* host only, no handle */
+int pm_estimate_motion(pm_handle* h, const pm_cloud_camera* camera, const pm_track_options* track_options,
+                       const pm_solve_options* solve_options, const pm_motion* guess /* NULL = identity */,
+                       const uint8_t* d_left_old, const float* d_disp_old, const uint8_t* d_left_new, int rows, int cols,
+                       pm_motion* out /* may be NULL */, pm_motion_info* info /* may be NULL */);
+
 /* ---- device buffers for host code that does not include HIP (host/imaging.hpp uses them) ------------------
  * pm_device_malloc / pm_device_free wrap hipMalloc / hipFree on the handle's device; pm_upload / pm_download are
  * stream-ordered copies on the handle's stream from / to pageable host memory (pm_download returns after the

@@ -55,6 +55,9 @@ struct ImagingState {
   // pm_fuse_disparity: kFuseHeader words ([0] valid, [1] kept, [2] fused, [3] filled pixels), then, for a call that fills,
   // one splat map of one word per pixel for each source; the memset of a call clears all of it
   DevBuf<unsigned> fuse_buf;
+  // pm_track_features / pm_estimate_motion: kTrackHeader words ([0] the number of features), one word per cell (its feature's
+  // pixel index or -1), one word per cell (the feature list) and, for pm_estimate_motion, one pm_track per cell
+  DevBuf<int> track_buf;
 };
 
 #define PM_HIP(h, call)                                                                                     \

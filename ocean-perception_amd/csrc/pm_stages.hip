@@ -1,6 +1,6 @@
 // pm_stages.hip -- C-ABI implementation of the stages of include/pm/imaging.h that read a finished disparity map: points,
 // plane-mode normals and the compacted cloud, the windowed plane fit, the speckle filter, the grid mesh, the temporal
-// seeds, the consistency filter, the matching confidence and the sequence fusion.  Like pm_imaging.hip it reaches the handle only through pm_internal.hpp, and it shares
+// seeds, the consistency filter, the matching confidence, the sequence fusion and the feature tracks of the motion estimate.  Like pm_imaging.hip it reaches the handle only through pm_internal.hpp, and it shares
 // that unit's one state object (pm_imaging_state.hpp).  Every entry point: its argument checks in a fixed order (the first
 // fault is the one reported), then the device, then its launches on the handle's stream.
 #include "pm/imaging.h"
@@ -10,6 +10,8 @@
 
 #include <cmath>
 #include <cstdint>
+#include <new>
+#include <vector>
 
 #include "pm_cloud.hpp"
 #include "pm_confidence.hpp"
@@ -20,6 +22,7 @@
 #include "pm_normals_fit.hpp"
 #include "pm_reproject.hpp"
 #include "pm_speckle.hpp"
+#include "pm_track.hpp"
 #include "pm_tune.hpp"
 
 using namespace pm;
@@ -738,4 +741,187 @@ int pm_fuse_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_fuse
   }
   if (int rc = launch_check(h, "fuse disparity")) return rc;
   return stage_counts(h, stream, reinterpret_cast<const int*>(base), 4, d_counts, counts);
+}
+
+// ---- camera motion between two frames: features of the old left image tracked into the new one (pm_track.hpp) ----------------
+namespace {
+constexpr size_t kTrackHeader = 4;  // words in front of the per-cell arrays: [0] the number of features, padded to 16 bytes
+
+// what pm_track_features and pm_estimate_motion are both given
+struct TrackInputs {
+  const pm_cloud_camera* camera;
+  const pm_track_options* options;
+  const pm_motion* guess;  // null: the identity
+  const uint8_t* left_old;
+  const float* disp_old;
+  const uint8_t* left_new;
+  int rows, cols;
+};
+
+// what run_track leaves behind: where the records and the number of features are on the device, and the stream
+struct TrackRun {
+  pm_track* records;
+  const int* d_total;
+  hipStream_t stream;
+};
+
+// The checks of everything but the outputs, in a fixed order.
+int check_track(pm_handle* h, const char* what, const TrackInputs& in) {
+  const pm_track_options* o = in.options;
+  const pm_motion* guess = in.guess;
+  if (int rc = check_cloud_camera(h, what, in.camera)) return rc;
+  if (!o || !in.left_old || !in.disp_old || !in.left_new) {
+    set_err(h, "%s: null %s", what, !o ? "options" : !in.left_old ? "d_left_old" : !in.disp_old ? "d_disp_old" : "d_left_new");
+    return PM_ERR_INVALID_ARG;
+  }
+  for (int i = 0; guess && i < 12; ++i)
+    if (!std::isfinite(i < 9 ? guess->R[i] : guess->t[i - 9])) {
+      set_err(h, "%s: %s[%d] of the guess is not finite", what, i < 9 ? "R" : "t", i < 9 ? i : i - 9);
+      return PM_ERR_INVALID_ARG;
+    }
+  if (o->cell < kTrackMinCell || o->cell > kTrackMaxCell) {
+    set_err(h, "%s: cell %d outside %d..%d", what, o->cell, kTrackMinCell, kTrackMaxCell);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (o->patch_radius < 1 || o->patch_radius > kTrackMaxPatch) {
+    set_err(h, "%s: patch_radius %d outside 1..%d", what, o->patch_radius, kTrackMaxPatch);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (o->search_radius < 0 || o->search_radius > kTrackMaxSearch) {
+    set_err(h, "%s: search_radius %d outside 0..%d", what, o->search_radius, kTrackMaxSearch);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (o->min_score < 1) {
+    set_err(h, "%s: min_score %lld must be >= 1", what, (long long)o->min_score);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (!(o->min_disp >= 0.f) || !(o->max_disp >= 0.f)) {
+    set_err(h, "%s: %s must be >= 0 and not NaN%s", what, !(o->min_disp >= 0.f) ? "min_disp" : "max_disp",
+            !(o->min_disp >= 0.f) ? "" : " (0 = no limit)");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (o->max_sad < 0 || o->min_gap < 0) {
+    set_err(h, "%s: %s must be >= 0", what, o->max_sad < 0 ? "max_sad" : "min_gap");
+    return PM_ERR_INVALID_ARG;
+  }
+  return check_cloud_shape(h, what, in.rows, in.cols);
+}
+
+int track_cells(int n, int cell) { return (n + cell - 1) / cell; }
+
+// The three launches.  Scratch: kTrackHeader words, the per-cell results, the feature list and, with `own_records`, one
+// record per cell behind them, which then take the place of d_tracks and capacity.
+int run_track(pm_handle* h, const char* what, const TrackInputs& in, int capacity, pm_track* d_tracks, int* d_count,
+              bool own_records, TrackRun* run) {
+  const pm_track_options* o = in.options;
+  const pm_motion* guess = in.guess;
+  const int rows = in.rows, cols = in.cols;
+  ImagingState* st = nullptr;
+  hipStream_t stream = nullptr;
+  if (int rc = stage_begin(h, what, &st, &stream)) return rc;
+  const int ncx = track_cells(cols, o->cell), ncy = track_cells(rows, o->cell);
+  const size_t cells = (size_t)ncx * ncy;  // <= rows * cols / 64 + ...: far below 2^31 (check_cloud_shape)
+  const size_t words = kTrackHeader + 2 * cells;
+  PM_HIP(h, st->track_buf.reserve(sizeof(int) * words + (own_records ? sizeof(pm_track) * cells : 0), stream));
+  int* base = st->track_buf.get();
+  int* cell_best = base + kTrackHeader;
+  int* feat = cell_best + cells;
+  if (own_records) {
+    d_tracks = reinterpret_cast<pm_track*>(base + words);
+    capacity = (int)cells;
+  }
+  const TrackOpt opt = {o->cell, o->patch_radius, o->search_radius, (long long)o->min_score, o->min_disp, o->max_disp,
+                        o->max_sad,  o->min_gap};
+  hipLaunchKernelGGL(k_track_select, dim3((unsigned)ncx, (unsigned)ncy), dim3(kTrackBlock), 0, stream,
+                     TrackSelectArgs{opt, in.left_old, in.disp_old, rows, cols, cell_best});
+  hipLaunchKernelGGL(k_track_compact, dim3(1), dim3(kTrackCompactThreads), 0, stream, (const int*)cell_best, (int)cells, feat,
+                     base, d_count);
+  const size_t blocks = cells < (size_t)capacity ? cells : (size_t)capacity;
+  if (blocks > 0 && d_tracks) {
+    TrackMatchArgs a = {};
+    a.opt = opt, a.cam = cloud_cam(*in.camera);
+    for (int i = 0; i < 9; ++i) a.R[i] = guess ? guess->R[i] : (i % 4 == 0 ? 1.0 : 0.0);
+    for (int i = 0; i < 3; ++i) a.t[i] = guess ? guess->t[i] : 0.0;
+    a.old = in.left_old, a.disp = in.disp_old, a.img = in.left_new, a.rows = rows, a.cols = cols;
+    a.feat = feat, a.total = base, a.tracks = d_tracks;
+    hipLaunchKernelGGL(k_track_match, dim3((unsigned)blocks), dim3(kTrackBlock), 0, stream, a);
+  }
+  if (int rc = launch_check(h, "track features")) return rc;
+  *run = TrackRun{d_tracks, base, stream};
+  return PM_OK;
+}
+}  // namespace
+
+int pm_track_features(pm_handle* h, const pm_cloud_camera* camera, const pm_track_options* options, const pm_motion* guess,
+                      const uint8_t* d_left_old, const float* d_disp_old, const uint8_t* d_left_new, int rows, int cols,
+                      int capacity, pm_track* d_tracks, int* d_count, int* count) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_track_features";
+  const TrackInputs in = {camera, options, guess, d_left_old, d_disp_old, d_left_new, rows, cols};
+  if (int rc = check_track(h, what, in)) return rc;
+  if (capacity < 0) {
+    set_err(h, "%s: capacity %d must be >= 0", what, capacity);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (capacity > 0 && !d_tracks) {
+    set_err(h, "%s: null d_tracks with capacity %d", what, capacity);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (capacity == 0 && !d_count && !count) {
+    set_err(h, "%s: no output: capacity is 0, d_count and count are null", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  TrackRun run = {};
+  if (int rc = run_track(h, what, in, capacity, d_tracks, d_count, false, &run)) return rc;
+  return stage_counts(h, run.stream, run.d_total, 1, nullptr, count);  // k_track_compact wrote d_count
+}
+
+int pm_estimate_motion(pm_handle* h, const pm_cloud_camera* camera, const pm_track_options* track_options,
+                       const pm_solve_options* solve_options, const pm_motion* guess, const uint8_t* d_left_old,
+                       const float* d_disp_old, const uint8_t* d_left_new, int rows, int cols, pm_motion* out,
+                       pm_motion_info* info) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_estimate_motion";
+  const TrackInputs in = {camera, track_options, guess, d_left_old, d_disp_old, d_left_new, rows, cols};
+  if (int rc = check_track(h, what, in)) return rc;
+  const pm_solve_options* s = solve_options;
+  if (!s) {
+    set_err(h, "%s: null solve_options", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (s->iterations < 1 || s->iterations > 50) {
+    set_err(h, "%s: iterations %d outside 1..50", what, s->iterations);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (!(s->huber_px > 0.0) || !(s->epsilon >= 0.0) || !(s->inlier_px > 0.0)) {
+    set_err(h, "%s: %s and not NaN", what,
+            !(s->huber_px > 0.0) ? "huber_px must be > 0" : !(s->epsilon >= 0.0) ? "epsilon must be >= 0" : "inlier_px must be > 0");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (s->min_inliers < 6) {
+    set_err(h, "%s: min_inliers %d must be >= 6", what, s->min_inliers);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (!out && !info) {
+    set_err(h, "%s: no output: out and info are null", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  TrackRun run = {};
+  if (int rc = run_track(h, what, in, 0, nullptr, nullptr, true, &run)) return rc;
+  int n = 0;
+  if (int rc = stage_counts(h, run.stream, run.d_total, 1, nullptr, &n)) return rc;
+  std::vector<pm_track> tracks;
+  try {
+    tracks.resize((size_t)n);
+  } catch (const std::bad_alloc&) {
+    set_err(h, "%s: out of host memory for %d records", what, n);
+    return PM_ERR_NOMEM;
+  }
+  if (n > 0) {
+    PM_HIP(h, hipMemcpyAsync(tracks.data(), run.records, sizeof(pm_track) * (size_t)n, hipMemcpyDeviceToHost, run.stream));
+    PM_HIP(h, hipStreamSynchronize(run.stream));
+  }
+  const int rc = pm_solve_motion(camera, s, tracks.data(), n, guess, out, info);
+  if (rc != PM_OK) set_err(h, "%s: pm_solve_motion refused its arguments", what);
+  return rc;
 }

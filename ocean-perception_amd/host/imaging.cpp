@@ -666,6 +666,101 @@ std::array<int, 4> FuseDisparity(pm::PatchmatchGpu& matcher, const StereoModel& 
   return {{counts[0], counts[1], counts[2], counts[3]}};
 }
 
+namespace {
+// The two frames of a motion estimate on the matcher's handle (not the imaging context's); every buffer is freed on every way
+// out.
+struct MotionFrames {
+  pm_handle* h;
+  std::vector<void*> p;
+  const uint8_t *old = nullptr, *img = nullptr;
+  const float* disp = nullptr;
+  pm_cloud_camera cam;
+  pm_track_options opt;
+  pm_motion guess;
+  MotionFrames(pm::PatchmatchGpu& matcher, const char* who, const StereoModel& model, const TrackOptions& o, const Motion* g,
+               const core::Image<uint8_t>& left_old, const core::Image<float>& disp_old, const core::Image<uint8_t>& left_new)
+      : h(matcher.handle()), cam(CloudCamera(model)),
+        opt{o.cell, o.patch_radius, o.search_radius, o.min_score, o.min_disp, o.max_disp, o.max_sad, o.min_gap} {
+    if (!h) throw std::runtime_error(std::string(who) + ": the matcher has no handle yet (plan it or match once)");
+    SameSize(left_old.rows, left_old.cols, disp_old.rows, disp_old.cols, who);
+    SameSize(left_old.rows, left_old.cols, left_new.rows, left_new.cols, who);
+    const Motion start = g ? *g : Motion();
+    for (size_t i = 0; i < 9; ++i) guess.R[i] = start.R[i];
+    for (size_t i = 0; i < 3; ++i) guess.t[i] = start.t[i];
+    old = static_cast<const uint8_t*>(Put(left_old.data(), Bytes(left_old)));
+    disp = static_cast<const float*>(Put(disp_old.data(), Bytes(disp_old)));
+    img = static_cast<const uint8_t*>(Put(left_new.data(), Bytes(left_new)));
+  }
+  ~MotionFrames() {
+    for (void* q : p) pm_device_free(h, q);
+  }
+  MotionFrames(const MotionFrames&) = delete;
+  MotionFrames& operator=(const MotionFrames&) = delete;
+  void Check(int status, const char* what) const {
+    if (status != PM_OK) throw std::runtime_error(std::string(what) + ": " + pm_status_string(status) + " -- " + pm_last_error(h));
+  }
+  void* Put(const void* src, size_t bytes) {
+    void* q = nullptr;
+    Check(pm_device_malloc(h, bytes, &q), "pm_device_malloc");
+    p.push_back(q);
+    if (src) Check(pm_upload(h, q, src, bytes), "pm_upload");
+    return q;
+  }
+};
+
+Motion FromC(const pm_motion& m) {
+  Motion out;
+  for (size_t i = 0; i < 9; ++i) out.R[i] = m.R[i];
+  for (size_t i = 0; i < 3; ++i) out.t[i] = m.t[i];
+  return out;
+}
+}  // namespace
+
+std::vector<pm_track> TrackFeatures(pm::PatchmatchGpu& matcher, const StereoModel& model, const TrackOptions& options,
+                                    const Motion* guess, const core::Image<uint8_t>& left_old, const core::Image<float>& disp_old,
+                                    const core::Image<uint8_t>& left_new) {
+  MotionFrames f(matcher, "TrackFeatures", model, options, guess, left_old, disp_old, left_new);
+  const int rows = left_old.rows, cols = left_old.cols;
+  // at most one feature per cell: room for all of them without a counting call in front
+  const int cell = options.cell > 0 ? options.cell : 1;
+  const int capacity = ((rows + cell - 1) / cell) * ((cols + cell - 1) / cell);
+  pm_track* d_tracks = static_cast<pm_track*>(f.Put(nullptr, sizeof(pm_track) * (size_t)capacity));
+  int count = -1;
+  f.Check(pm_track_features(f.h, &f.cam, &f.opt, &f.guess, f.old, f.disp, f.img, rows, cols, capacity, d_tracks, nullptr, &count),
+          "pm_track_features");
+  std::vector<pm_track> tracks((size_t)count);
+  if (count > 0) f.Check(pm_download(f.h, tracks.data(), d_tracks, sizeof(pm_track) * tracks.size()), "pm_download");
+  return tracks;
+}
+
+Motion SolveMotion(const StereoModel& model, const SolveOptions& options, const std::vector<pm_track>& tracks, const Motion* guess,
+                   pm_motion_info* info) {
+  const pm_cloud_camera cam = CloudCamera(model);
+  const pm_solve_options opt = {options.iterations, options.huber_px, options.epsilon, options.inlier_px, options.min_inliers};
+  const Motion start = guess ? *guess : Motion();
+  pm_motion g, out;
+  for (size_t i = 0; i < 9; ++i) g.R[i] = start.R[i];
+  for (size_t i = 0; i < 3; ++i) g.t[i] = start.t[i];
+  pm_motion_info local;
+  const int rc = pm_solve_motion(&cam, &opt, tracks.data(), (int)tracks.size(), &g, &out, info ? info : &local);
+  if (rc != PM_OK) throw std::runtime_error(std::string("pm_solve_motion: ") + pm_status_string(rc));
+  return FromC(out);
+}
+
+Motion EstimateMotion(pm::PatchmatchGpu& matcher, const StereoModel& model, const TrackOptions& track_options,
+                      const SolveOptions& solve_options, const Motion* guess, const core::Image<uint8_t>& left_old,
+                      const core::Image<float>& disp_old, const core::Image<uint8_t>& left_new, pm_motion_info* info) {
+  MotionFrames f(matcher, "EstimateMotion", model, track_options, guess, left_old, disp_old, left_new);
+  const pm_solve_options opt = {solve_options.iterations, solve_options.huber_px, solve_options.epsilon, solve_options.inlier_px,
+                                solve_options.min_inliers};
+  pm_motion out;
+  pm_motion_info local;
+  f.Check(pm_estimate_motion(f.h, &f.cam, &f.opt, &opt, &f.guess, f.old, f.disp, f.img, left_old.rows, left_old.cols, &out,
+                             info ? info : &local),
+          "pm_estimate_motion");
+  return FromC(out);
+}
+
 core::Image<core::Vec3f> DisparityNormals(const core::Image<float>& disp, const StereoModel& model, const NormalsFit& fit,
                                           core::Image<uint8_t>* support) {
   if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("DisparityNormals: empty map");

@@ -251,5 +251,40 @@ std::array<int, 4> FuseDisparity(pm::PatchmatchGpu& matcher, const StereoModel& 
                                  core::Image<uint8_t>* count = nullptr, core::Image<float>* spread = nullptr,
                                  core::Image<uint8_t>* flags = nullptr);
 
+// The motion of the left camera between two frames, X_new = R X_old + t: what ReprojectDisparity takes, and, the other way
+// round, what FilterConsistency and FuseDisparity take (pm/imaging.h: pm_track_features, pm_solve_motion, pm_estimate_motion;
+// definition: tests/motion_ref.py).  One corner per cell of the old left image with a value in its disparity map is predicted
+// through the guess and block-matched in the new left image; the motion is fitted to the tracks on the host in binary64.
+struct TrackOptions {  // pm_track_options
+  int cell = 16;             // 8..64
+  int patch_radius = 3;      // 1..7
+  int search_radius = 5;     // 0..24
+  int64_t min_score = 1;     // >= 1
+  float min_disp = 0.f, max_disp = 0.f;  // >= 0; max_disp 0 = no limit
+  int max_sad = 0;           // >= 0, 0 = no limit
+  int min_gap = 0;           // >= 0
+};
+struct SolveOptions {  // pm_solve_options
+  int iterations = 10;      // 1..50
+  double huber_px = 1.0;    // > 0
+  double epsilon = 1e-9;    // >= 0
+  double inlier_px = 1.0;   // > 0
+  int min_inliers = 12;     // >= 6
+};
+// Host images in, the records out (all of them), on the matcher's own handle and stream; guess: null = the identity.  The
+// matcher must have planned its handle.  Throws std::invalid_argument where the sizes differ and std::runtime_error where
+// pm_track_features refuses.
+std::vector<pm_track> TrackFeatures(pm::PatchmatchGpu& matcher, const StereoModel& model, const TrackOptions& options,
+                                    const Motion* guess, const core::Image<uint8_t>& left_old, const core::Image<float>& disp_old,
+                                    const core::Image<uint8_t>& left_new);
+// No device takes part.  info->valid == 0: the result is not to be trusted and the returned motion is the guess.  Throws
+// std::runtime_error where pm_solve_motion refuses.
+Motion SolveMotion(const StereoModel& model, const SolveOptions& options, const std::vector<pm_track>& tracks, const Motion* guess,
+                   pm_motion_info* info = nullptr);
+// TrackFeatures, then SolveMotion, in one call of the C ABI (pm_estimate_motion).
+Motion EstimateMotion(pm::PatchmatchGpu& matcher, const StereoModel& model, const TrackOptions& track_options,
+                      const SolveOptions& solve_options, const Motion* guess, const core::Image<uint8_t>& left_old,
+                      const core::Image<float>& disp_old, const core::Image<uint8_t>& left_new, pm_motion_info* info = nullptr);
+
 }  // namespace imaging
 }  // namespace bm

@@ -51,6 +51,7 @@ EXPORTS = [
     "pm_filter_consistency",
     "pm_disparity_confidence", "pm_debug_confidence_constants",
     "pm_fuse_disparity",
+    "pm_track_features", "pm_solve_motion", "pm_estimate_motion",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
     "pm_debug_match_plan",
     "pm_debug_sweep_plan", "pm_debug_segment_bounds", "pm_debug_propagate_hinted", "pm_debug_match_sweep_hint", "pm_debug_read_stops", "pm_debug_noise_cost_constants", "pm_debug_noise_cost", "pm_debug_remove_background",
@@ -283,6 +284,51 @@ class PmFuseOptions(C.Structure):  # pm_fuse_disparity
                 ("fill_min_sources", C.c_int), ("fill_max_diff", C.c_float)]
 
 
+PM_TRACK_PREDICTED, PM_TRACK_MATCHED, PM_TRACK_SUBPIX_X, PM_TRACK_SUBPIX_Y, PM_TRACK_FAIL_SAD, PM_TRACK_FAIL_GAP = 1, 2, 4, 8, 16, 32
+# pm_track as a numpy record: 32 bytes
+TRACK_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("disp", "<f4"), ("x_new", "<f4"), ("y_new", "<f4"), ("sad", "<i4"),
+                        ("second", "<i4"), ("flags", "<u4")])
+
+
+class PmTrack(C.Structure):  # one record of pm_track_features
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("disp", C.c_float), ("x_new", C.c_float), ("y_new", C.c_float),
+                ("sad", C.c_int32), ("second", C.c_int32), ("flags", C.c_uint32)]
+
+
+class PmTrackOptions(C.Structure):  # pm_track_features
+    _fields_ = [("cell", C.c_int), ("patch_radius", C.c_int), ("search_radius", C.c_int), ("min_score", C.c_int64),
+                ("min_disp", C.c_float), ("max_disp", C.c_float), ("max_sad", C.c_int), ("min_gap", C.c_int)]
+
+
+class PmSolveOptions(C.Structure):  # pm_solve_motion
+    _fields_ = [("iterations", C.c_int), ("huber_px", C.c_double), ("epsilon", C.c_double), ("inlier_px", C.c_double),
+                ("min_inliers", C.c_int)]
+
+
+class PmMotionInfo(C.Structure):
+    _fields_ = [("valid", C.c_int), ("n_tracks", C.c_int), ("n_used", C.c_int), ("n_inliers", C.c_int), ("iterations", C.c_int),
+                ("rms_px", C.c_double)]
+
+    def as_dict(self):
+        return dict(valid=self.valid, n_tracks=self.n_tracks, n_used=self.n_used, n_inliers=self.n_inliers,
+                    iterations=self.iterations, rms_px=self.rms_px)
+
+
+def solve_motion(camera, tracks, guess=None, iterations=10, huber_px=1.0, epsilon=1e-9, inlier_px=1.0, min_inliers=12):
+    """pm_solve_motion (host only, no handle): tracks, a TRACK_DTYPE array -> (R[9], t[3], info dict).  Raises PmError where
+    the arguments are refused."""
+    lib = load()
+    c = cloud_camera(camera)
+    o = PmSolveOptions(iterations, huber_px, epsilon, inlier_px, min_inliers)
+    tr = np.ascontiguousarray(tracks, TRACK_DTYPE)
+    out, info = PmMotion(), PmMotionInfo()
+    rc = lib.pm_solve_motion(_ref(c), C.byref(o), tr.ctypes.data_as(C.c_void_p) if tr.size else None, int(tr.size),
+                             _ref(as_motion(guess)), C.byref(out), C.byref(info))
+    if rc != PM_OK:
+        raise PmError(rc, "pm_solve_motion", "refused its arguments")
+    return np.array(out.R[:]), np.array(out.t[:]), info.as_dict()
+
+
 def confidence_constants():
     """pm_debug_confidence_constants: (tile columns, tile rows, target columns held in LDS) of k_confidence."""
     a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
@@ -487,6 +533,16 @@ def load():
                                       C.POINTER(PmMotion), C.POINTER(vp), C.c_int, C.c_int, vp, vp, vp, vp, vp,
                                       C.POINTER(C.c_int)]
     lib.pm_fuse_disparity.restype = C.c_int
+    lib.pm_track_features.argtypes = [vp, C.POINTER(PmCloudCamera), C.POINTER(PmTrackOptions), C.POINTER(PmMotion), vp, vp, vp,
+                                      C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int)]
+    lib.pm_track_features.restype = C.c_int
+    lib.pm_solve_motion.argtypes = [C.POINTER(PmCloudCamera), C.POINTER(PmSolveOptions), vp, C.c_int, C.POINTER(PmMotion),
+                                    C.POINTER(PmMotion), C.POINTER(PmMotionInfo)]
+    lib.pm_solve_motion.restype = C.c_int
+    lib.pm_estimate_motion.argtypes = [vp, C.POINTER(PmCloudCamera), C.POINTER(PmTrackOptions), C.POINTER(PmSolveOptions),
+                                       C.POINTER(PmMotion), vp, vp, vp, C.c_int, C.c_int, C.POINTER(PmMotion),
+                                       C.POINTER(PmMotionInfo)]
+    lib.pm_estimate_motion.restype = C.c_int
     lib.pm_debug_confidence_constants.argtypes = [C.POINTER(C.c_int)] * 3
     lib.pm_debug_confidence_constants.restype = None
     lib.pm_device_malloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
@@ -1153,6 +1209,38 @@ class Engine:
                                                rows, cols, d_out, d_count, d_spread, d_flags, d_counts,
                                                n if want_counts else None), "pm_fuse_disparity")
         return tuple(n) if want_counts else None
+
+    def track_features(self, camera, d_left_old, d_disp_old, d_left_new, rows, cols, guess=None, cell=16, patch_radius=3,
+                       search_radius=5, min_score=1, min_disp=0.0, max_disp=0.0, max_sad=0, min_gap=0, capacity=0, d_tracks=None,
+                       d_count=None, want_count=False):
+        """pm_track_features (raw device addresses): one corner per cell of the old left image (uint8) with a value in its
+        disparity map, predicted through guess ((R, t) or PmMotion, None = identity) and matched in the new left image, on the
+        handle's stream.  d_tracks: room for `capacity` 32-byte records (TRACK_DTYPE); d_count: one device int.  -> the number
+        of features with want_count (the call then synchronises), else None."""
+        c = cloud_camera(camera)
+        o = PmTrackOptions(cell, patch_radius, search_radius, min_score, min_disp, max_disp, max_sad, min_gap)
+        n = C.c_int(-1)
+        self._check(self.lib.pm_track_features(self.h, _ref(c), C.byref(o), _ref(as_motion(guess)), d_left_old, d_disp_old,
+                                               d_left_new, rows, cols, capacity, d_tracks, d_count,
+                                               C.byref(n) if want_count else None), "pm_track_features")
+        return n.value if want_count else None
+
+    def estimate_motion(self, camera, d_left_old, d_disp_old, d_left_new, rows, cols, guess=None, track_options=None,
+                        solve_options=None):
+        """pm_estimate_motion (raw device addresses): track, download, solve -> (R[9], t[3], info dict); X_new = R X_old + t,
+        what reproject_disparity takes.  track_options / solve_options: dicts of PmTrackOptions' / PmSolveOptions' fields over
+        the defaults of track_features / solve_motion.  Synchronises."""
+        c = cloud_camera(camera)
+        to = dict(cell=16, patch_radius=3, search_radius=5, min_score=1, min_disp=0.0, max_disp=0.0, max_sad=0, min_gap=0)
+        so = dict(iterations=10, huber_px=1.0, epsilon=1e-9, inlier_px=1.0, min_inliers=12)
+        to.update(track_options or {})
+        so.update(solve_options or {})
+        o, s = PmTrackOptions(**to), PmSolveOptions(**so)
+        out, info = PmMotion(), PmMotionInfo()
+        self._check(self.lib.pm_estimate_motion(self.h, _ref(c), C.byref(o), C.byref(s), _ref(as_motion(guess)), d_left_old,
+                                                d_disp_old, d_left_new, rows, cols, C.byref(out), C.byref(info)),
+                    "pm_estimate_motion")
+        return np.array(out.R[:]), np.array(out.t[:]), info.as_dict()
 
     def normalize(self, d_bgr, rows, cols, d_out):
         self._check(self.lib.pm_normalize(self.h, d_bgr, rows, cols, d_out), "pm_normalize")
