@@ -699,6 +699,91 @@ int pm_estimate_motion(pm_handle* h, const pm_cloud_camera* camera, const pm_tra
                        const uint8_t* d_left_old, const float* d_disp_old, const uint8_t* d_left_new, int rows, int cols,
                        pm_motion* out /* may be NULL */, pm_motion_info* info /* may be NULL */);
 
+/* ---- a persistent world-frame model: a truncated signed distance volume, integrated from maps and raycast back -----------------
+ * What it is for: the sequence stages above work on a sliding window of at most PM_CONSISTENCY_MAX_SOURCES earlier maps, and
+ * every output lives in one camera frame.  A TSDF volume holds what the whole sequence saw, in the WORLD frame: pm_tsdf_integrate
+ * folds one disparity map and its camera pose into it, pm_tsdf_raycast renders it back as an ordinary LEFT disparity map (and
+ * normals) at any pose.  Every stage above consumes that map unchanged: pm_point_cloud / pm_grid_mesh make the fused surface,
+ * pm_reproject_disparity with the identity motion makes the right seed, pm_submit_device_after takes the pair as seeds without
+ * cracks, pm_filter_consistency / pm_fuse_disparity take it as ONE source that stands for the whole history.
+ * The caller owns the volume: nx * ny * nz records of 8 bytes {float tsdf; float weight}, x fastest, in device memory
+ * (pm_device_malloc, pm_tsdf_bytes); weight == 0 means never observed.  pose: X_cam = R X_world + t (a pm_motion from the world
+ * frame into the left camera's).
+ * Held to its CPU definition (tests/tsdf_ref.py) BIT FOR BIT.  Binary64 unless it says binary32, one rounding per operation,
+ * parentheses as written; fxB = fx * baseline formed once:
+ *   integrate, per voxel (i, j, k), independent of every other voxel:
+ *     point    Xw = origin[0] + ((double)i * voxel); Yw, Zw likewise with j, k.
+ *     project  EXACTLY pm_reproject_disparity's `splat` arithmetic from its motion line on, with max_disp = 0:
+ *              Xc = (((R0*Xw) + (R1*Yw)) + (R2*Zw)) + t0; Yc, Zc likewise; dropped unless Zc > 0; dropped unless
+ *              (float)(fxB / Zc) is > 0 and finite; u = (fx * (Xc / Zc)) + cx; v likewise; the 2^30 guard; rint half to even;
+ *              dropped outside the rows x cols image -> (iu, iv).  A voxel that gets this far is IN VIEW.
+ *     measure  d = D(iv, iu) counts iff d > 0 and d >= min_disp (binary32; never NaN).  Zm = fxB / (double)d; dropped if
+ *              max_range != 0 and (float)Zm > max_range.  sdf = Zm - Zc, the projective distance along the optical axis;
+ *              dropped if sdf < -trunc.  f = (float)fmin(1.0, sdf / trunc): free space in front of the surface is carved with 1.
+ *     weight   wn = 1.0f, or W(iv, iu) where d_weight is given, under pm_fuse_disparity's rule: with 0, -0.0, negatives, NaN
+ *              and +-inf the observation does not take part.
+ *     update   binary32:  tsdf' = ((tsdf * w) + (f * wn)) / (w + wn);  w' = fminf(w + wn, max_weight).  A voxel that was
+ *              dropped keeps its bits and is neither read nor written.
+ *     counts   [0] voxels in view, [1] voxels updated.
+ *   raycast, per pixel (x, y):
+ *     inverse  formed on the host, as pm_fuse_disparity forms its inverse motions:  Ri[3i+j] = R[3j+i];
+ *              c_i = -(((R[i]*t0) + (R[3+i]*t1)) + (R[6+i]*t2))  (R is not checked for being a rotation).
+ *     ray      dx = ((double)x - cx) / fx; dy = ((double)y - cy) / fy; the direction in the camera frame is (dx, dy, 1), so the
+ *              ray parameter s is the camera depth Z.  In the world frame wd_i = ((Ri[3i]*dx) + (Ri[3i+1]*dy)) + Ri[3i+2].
+ *     samples  ds = (double)step * trunc; s_n = (double)min_range + ((double)n * ds), never accumulated, for n = 0, 1, ... while
+ *              s_n <= (double)max_range.  Grid coordinates q_i = ((c_i + (s * wd_i)) - origin[i]) / voxel.
+ *     sample   b_i = floor(q_i); fr_i = (float)(q_i - b_i).  VALID iff 0 <= b_i and b_i + 1 <= n_i - 1 on every axis and each
+ *              of the eight corners takes part: weight > 0 and weight >= min_weight.  With lerp(a, b, t) = a + (t * (b - a)) in
+ *              binary32 and T(i, j, k) the corner's tsdf:  x00 = lerp(T(b0, b1, b2), T(b0+1, b1, b2), fr0);  x10: row b1 + 1;
+ *              x01: slice b2 + 1;  x11: both;  y0 = lerp(x00, x10, fr1);  y1 = lerp(x01, x11, fr1);  value = lerp(y0, y1, fr2).
+ *     hit      the first n with sample n - 1 VALID and f_prev > 0, and sample n VALID and f_cur <= 0:
+ *              s* = s_(n-1) + (ds * ((double)f_prev / ((double)f_prev - (double)f_cur))).  A VALID f_prev < 0 followed by a
+ *              VALID f_cur > 0 is a back face and ends the ray without a hit.  A sample that is not VALID forgets f_prev.
+ *     d_disp_out     (float)(fxB / s*), +0.0f without a hit.
+ *     d_normals_out  q* = the grid coordinates at s*.  Along each grid axis i the sample at q* + e_i and at q* - e_i (one
+ *              voxel either side); G_i = v_plus - v_minus in binary32; (0, 0, 0) where one of the six is not VALID or there is
+ *              no hit.  m_i = ((R[3i]*(double)G0) + (R[3i+1]*(double)G1)) + (R[3i+2]*(double)G2); n_i = (float)m_i;
+ *              normalised as pm_planes_normals does (binary32 sum of squares, sqrtf, (0, 0, 0) unless the length is finite and
+ *              > 0), and negated iff ((m0*dx) + (m1*dy)) + m2 > 0, so that it faces the camera.
+ *     counts   [0] pixels hit.
+ * pm_tsdf_bytes needs no handle.  The other three enqueue on the handle's stream and are valid in every mode of the handle; a
+ * non-NULL host `counts` synchronises like pm_point_cloud's `count`.  pm_tsdf_clear is one memset; integrate and raycast are one
+ * launch each behind a 16-byte memset; no voxel is touched by two threads and only integer addition crosses workgroups, so every
+ * output is a pure function of the inputs.  Scratch is the 16 bytes of the counts, allocated on first use, reused, and released
+ * with the handle.
+ * PM_ERR_INVALID_ARG, with pm_last_error naming the argument and nothing enqueued: a null camera, volume, pose, options, d_disp
+ * or d_voxels; a camera pm_backproject refuses; a non-finite entry of the pose; nx, ny, nz, rows or cols < 1; a voxel, trunc or
+ * max_weight that is not finite or not > 0; a non-finite origin; integrate: a min_disp that is NaN or < 0, a max_range that is
+ * not >= 0 (0 = no limit); raycast: a step outside (0, 1], ranges that are not finite or not 0 < min_range < max_range, a
+ * min_weight that is NaN or < 0, no output at all (d_disp_out, d_normals_out, d_counts and counts all NULL).  PM_ERR_SIZE:
+ * nx * ny * nz > 2^31 - 1; more pixels than pm_backproject takes; raycast: more than 65536 samples along a ray. */
+typedef struct pm_tsdf_volume {
+  int nx, ny, nz;          /* voxels; x fastest in memory                                    */
+  double origin[3];        /* world position of the centre of voxel (0, 0, 0)                */
+  double voxel;            /* edge length, > 0                                               */
+  double trunc;            /* truncation distance, > 0 (typically 3..5 voxels)               */
+  float  max_weight;       /* > 0: the weight saturates here, so the model can follow change */
+} pm_tsdf_volume;
+typedef struct pm_tsdf_integrate_options { float min_disp; float max_range; } pm_tsdf_integrate_options;
+typedef struct pm_tsdf_raycast_options {
+  float min_range, max_range;
+  float step;              /* fraction of trunc, in (0, 1]                                   */
+  float min_weight;        /* a voxel takes part iff weight > 0 and >= min_weight            */
+} pm_tsdf_raycast_options;
+
+size_t pm_tsdf_bytes(const pm_tsdf_volume* volume);   /* 0 if invalid or too large */
+int pm_tsdf_clear(pm_handle* h, const pm_tsdf_volume* volume, void* d_voxels);
+int pm_tsdf_integrate(pm_handle* h, const pm_cloud_camera* camera, const pm_tsdf_volume* volume,
+                      const pm_motion* pose /* X_cam = R X_world + t */, const pm_tsdf_integrate_options* options,
+                      const float* d_disp, const float* d_weight /* may be NULL */, int rows, int cols, void* d_voxels,
+                      int* d_counts /* device int[2]: voxels in view, voxels updated; may be NULL */,
+                      int* counts /* host int[2], may be NULL: non-NULL synchronises like pm_point_cloud's count */);
+int pm_tsdf_raycast(pm_handle* h, const pm_cloud_camera* camera, const pm_tsdf_volume* volume, const pm_motion* pose,
+                    const pm_tsdf_raycast_options* options, const void* d_voxels, int rows, int cols,
+                    float* d_disp_out /* may be NULL */, float* d_normals_out /* [rows][cols][3], may be NULL */,
+                    int* d_counts /* device int[1]: pixels hit; may be NULL */,
+                    int* counts /* host int[1], may be NULL: non-NULL synchronises */);
+
 /* ---- device buffers for host code that does not include HIP (host/imaging.hpp uses them) ------------------
  * pm_device_malloc / pm_device_free wrap hipMalloc / hipFree on the handle's device; pm_upload / pm_download are
  * stream-ordered copies on the handle's stream from / to pageable host memory (pm_download returns after the

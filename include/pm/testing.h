@@ -212,6 +212,12 @@ void pm_debug_reproject_constants(int* tile_w, int* tile_h);
  * x - patch_w / 2.  Tests build a map that reaches that path with them.  No handle, no device. */
 void pm_debug_confidence_constants(int* tile_w, int* tile_h, int* target_cols);
 
+/* ---- the launch constants of pm_tsdf_integrate and pm_tsdf_raycast (csrc/pm_tsdf_body.hpp) --------------------------------------
+ * lanes: the consecutive voxels along x one wavefront of k_tsdf_integrate owns, and the consecutive pixels of a row one
+ * wavefront of k_tsdf_raycast owns; waves: the wavefronts of a block of either.  Tests choose volumes and maps that cross a
+ * span and leave a tail with them.  No handle, no device. */
+void pm_debug_tsdf_constants(int* lanes, int* waves);
+
 /* ---- the row-tiled driver's device discipline, provable on ONE GPU ------------------------------------------------
  * pm_tiled_create with the bands accounted to LOGICAL devices: band k lives on logical_devices[k] (>= 0; several bands
  * may share one) while every HIP call still goes to the physical device of the band's handle.  Such a plan logs every

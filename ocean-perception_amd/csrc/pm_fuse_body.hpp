@@ -79,6 +79,15 @@ __host__ __device__ __forceinline__ double fuse_weight(float w) { return w > 0.f
 // The sign of a generated NaN differs between processors: a NaN result is the canonical quiet NaN.
 __host__ __device__ __forceinline__ float fuse_canonical(float v) { return v != v ? __builtin_bit_cast(float, 0x7FC00000u) : v; }
 
+// The inverse of the rigid motion X' = R X + t, formed on the host in binary64 with the parentheses as written (the build does
+// not contract): what the fill splats of pm_fuse_disparity and the rays of pm_tsdf_raycast go through.
+inline void motion_inverse(const double R[9], const double t[3], double Ri[9], double ti[3]) {
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) Ri[3 * i + j] = R[3 * j + i];
+    ti[i] = -(((R[i] * t[0]) + (R[3 + i] * t[1])) + (R[6 + i] * t[2]));
+  }
+}
+
 // The vote of the splat maps at pixel `at`, which has no value of its own: whether it is filled, and with what.
 __host__ __device__ __forceinline__ bool fuse_fill(const FuseArgs& a, size_t at, float* value, int* n_sup, float* spread) {
   unsigned m = 0u;  // the maps hold the bits of +0.0 or of a finite binary32 > 0: unsigned order is float order

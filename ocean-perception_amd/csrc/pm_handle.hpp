@@ -22,6 +22,8 @@
 //     pm_consistency.hpp the kernel of pm_filter_consistency (k_consistency<RADIUS>); its body is pm_consistency_body.hpp's
 //     pm_fuse.hpp        the two kernels of pm_fuse_disparity (k_fuse_splat, k_fuse<RADIUS>); their bodies are
 //                        pm_fuse_body.hpp's
+//     pm_tsdf.hpp        the two kernels of pm_tsdf_integrate and pm_tsdf_raycast (k_tsdf_integrate, k_tsdf_raycast); their
+//                        bodies are pm_tsdf_body.hpp's
 //     pm_track.hpp       the three kernels of pm_track_features (k_track_select, k_track_compact, k_track_match); their
 //                        scalar pieces are pm_track_body.hpp's
 // Every __global__ kernel lives in exactly one unit; the others reach it through the launch functions declared here.

@@ -58,6 +58,8 @@ struct ImagingState {
   // pm_track_features / pm_estimate_motion: kTrackHeader words ([0] the number of features), one word per cell (its feature's
   // pixel index or -1), one word per cell (the feature list) and, for pm_estimate_motion, one pm_track per cell
   DevBuf<int> track_buf;
+  // pm_tsdf_integrate / pm_tsdf_raycast: kTsdfHeader words ([0], [1]: the counts of the call), cleared per call
+  DevBuf<int> tsdf_counts;
 };
 
 #define PM_HIP(h, call)                                                                                     \

@@ -1,6 +1,6 @@
 // pm_stages.hip -- C-ABI implementation of the stages of include/pm/imaging.h that read a finished disparity map: points,
 // plane-mode normals and the compacted cloud, the windowed plane fit, the speckle filter, the grid mesh, the temporal
-// seeds, the consistency filter, the matching confidence, the sequence fusion and the feature tracks of the motion estimate.  Like pm_imaging.hip it reaches the handle only through pm_internal.hpp, and it shares
+// seeds, the consistency filter, the matching confidence, the sequence fusion, the feature tracks of the motion estimate and the TSDF volume.  Like pm_imaging.hip it reaches the handle only through pm_internal.hpp, and it shares
 // that unit's one state object (pm_imaging_state.hpp).  Every entry point: its argument checks in a fixed order (the first
 // fault is the one reported), then the device, then its launches on the handle's stream.
 #include "pm/imaging.h"
@@ -23,6 +23,7 @@
 #include "pm_reproject.hpp"
 #include "pm_speckle.hpp"
 #include "pm_track.hpp"
+#include "pm_tsdf.hpp"
 #include "pm_tune.hpp"
 
 using namespace pm;
@@ -724,10 +725,7 @@ int pm_fuse_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_fuse
     for (int i = 0; i < 3; ++i) a.src[k].t[i] = t[i];
     a.src[k].map = d_sources[k];
     a.src[k].weight = d_source_weights ? d_source_weights[k] : nullptr;
-    for (int i = 0; i < 3; ++i) {  // the inverse of a rigid motion, in binary64 (not contracted: -ffp-contract=off)
-      for (int j = 0; j < 3; ++j) sa.src[k].R[3 * i + j] = R[3 * j + i];
-      sa.src[k].t[i] = -(((R[i] * t[0]) + (R[3 + i] * t[1])) + (R[6 + i] * t[2]));
-    }
+    motion_inverse(R, t, sa.src[k].R, sa.src[k].t);  // in binary64 (not contracted: -ffp-contract=off)
     sa.src[k].map = d_sources[k];
   }
   PM_HIP(h, hipMemsetAsync(base, 0, sizeof(unsigned) * words, stream));
@@ -741,6 +739,179 @@ int pm_fuse_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_fuse
   }
   if (int rc = launch_check(h, "fuse disparity")) return rc;
   return stage_counts(h, stream, reinterpret_cast<const int*>(base), 4, d_counts, counts);
+}
+
+// ---- a persistent world-frame model: a TSDF volume integrated from maps and raycast back (pm_tsdf.hpp) ------------------------
+namespace {
+constexpr size_t kTsdfHeader = 4;            // the counts of a call, padded to 16 bytes
+
+// the volume's voxels, or 0 where a dimension is < 1 or they exceed 2^31 - 1
+size_t tsdf_voxels(const pm_tsdf_volume& v) {
+  if (v.nx < 1 || v.ny < 1 || v.nz < 1) return 0;
+  const size_t xy = (size_t)v.nx * (size_t)v.ny;
+  if (xy > (size_t)INT32_MAX || xy * (size_t)v.nz > (size_t)INT32_MAX) return 0;
+  return xy * (size_t)v.nz;
+}
+
+const char* tsdf_volume_fault(const pm_tsdf_volume& v) {
+  if (v.nx < 1 || v.ny < 1 || v.nz < 1) return "nx, ny and nz of the volume must be >= 1";
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite(v.origin[i])) return "origin of the volume is not finite";
+  if (!std::isfinite(v.voxel) || !(v.voxel > 0.0)) return "voxel of the volume must be finite and > 0";
+  if (!std::isfinite(v.trunc) || !(v.trunc > 0.0)) return "trunc of the volume must be finite and > 0";
+  if (!std::isfinite(v.max_weight) || !(v.max_weight > 0.f)) return "max_weight of the volume must be finite and > 0";
+  return nullptr;
+}
+
+// what pm_tsdf_integrate and pm_tsdf_raycast check in the same order: camera, the null pointers, the volume, the pose
+int check_tsdf_common(pm_handle* h, const char* what, const pm_cloud_camera* camera, const pm_tsdf_volume* volume,
+                      const pm_motion* pose, const void* options, const void* d_voxels) {
+  if (int rc = check_cloud_camera(h, what, camera)) return rc;
+  if (!volume || !pose || !options || !d_voxels) {
+    set_err(h, "%s: null %s", what, !volume ? "volume" : !pose ? "pose" : !options ? "options" : "d_voxels");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (const char* fault = tsdf_volume_fault(*volume)) {
+    set_err(h, "%s: %s", what, fault);
+    return PM_ERR_INVALID_ARG;
+  }
+  for (int i = 0; i < 12; ++i)
+    if (!std::isfinite(i < 9 ? pose->R[i] : pose->t[i - 9])) {
+      set_err(h, "%s: %s[%d] of the pose is not finite", what, i < 9 ? "R" : "t", i < 9 ? i : i - 9);
+      return PM_ERR_INVALID_ARG;
+    }
+  return PM_OK;
+}
+
+int check_tsdf_size(pm_handle* h, const char* what, const pm_tsdf_volume& v) {
+  if (tsdf_voxels(v) == 0) {
+    set_err(h, "%s: %dx%dx%d voxels exceed 2^31 - 1", what, v.nx, v.ny, v.nz);
+    return PM_ERR_SIZE;
+  }
+  return PM_OK;
+}
+}  // namespace
+
+size_t pm_tsdf_bytes(const pm_tsdf_volume* volume) {
+  if (!volume || tsdf_volume_fault(*volume)) return 0;
+  return tsdf_voxels(*volume) * sizeof(TsdfVoxel);
+}
+
+int pm_tsdf_clear(pm_handle* h, const pm_tsdf_volume* volume, void* d_voxels) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_tsdf_clear";
+  if (!volume || !d_voxels) {
+    set_err(h, "%s: null %s", what, !volume ? "volume" : "d_voxels");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (const char* fault = tsdf_volume_fault(*volume)) {
+    set_err(h, "%s: %s", what, fault);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_tsdf_size(h, what, *volume)) return rc;
+  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
+  PM_HIP(h, hipMemsetAsync(d_voxels, 0, tsdf_voxels(*volume) * sizeof(TsdfVoxel), pm_internal::stream(h)));  // {+0.0f, +0.0f}
+  return PM_OK;
+}
+
+int pm_tsdf_integrate(pm_handle* h, const pm_cloud_camera* camera, const pm_tsdf_volume* volume, const pm_motion* pose,
+                      const pm_tsdf_integrate_options* options, const float* d_disp, const float* d_weight, int rows, int cols,
+                      void* d_voxels, int* d_counts, int* counts) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_tsdf_integrate";
+  if (int rc = check_tsdf_common(h, what, camera, volume, pose, options, d_voxels)) return rc;
+  if (!d_disp) {
+    set_err(h, "%s: null d_disp", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (std::isnan(options->min_disp) || options->min_disp < 0.f) {
+    set_err(h, "%s: min_disp must not be NaN or negative", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (!(options->max_range >= 0.f)) {
+    set_err(h, "%s: max_range must be >= 0 (0 = no limit)", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
+  if (int rc = check_tsdf_size(h, what, *volume)) return rc;
+  ImagingState* st = nullptr;
+  hipStream_t stream = nullptr;
+  if (int rc = stage_begin(h, what, &st, &stream)) return rc;
+  PM_HIP(h, st->tsdf_counts.reserve(sizeof(int) * kTsdfHeader, stream));
+  int* d_totals = st->tsdf_counts.get();
+  TsdfIntegrateArgs a = {};
+  a.cam = cloud_cam(*camera);
+  a.grid = tsdf_grid(*volume);
+  for (int i = 0; i < 9; ++i) a.R[i] = pose->R[i];
+  for (int i = 0; i < 3; ++i) a.t[i] = pose->t[i];
+  a.min_disp = options->min_disp, a.max_range = options->max_range;
+  a.disp = d_disp, a.weight = d_weight, a.rows = rows, a.cols = cols;
+  a.voxels = static_cast<TsdfVoxel*>(d_voxels), a.counts = d_totals;
+  PM_HIP(h, hipMemsetAsync(d_totals, 0, sizeof(int) * kTsdfHeader, stream));
+  const size_t spans = (((size_t)volume->nx + kTsdfLanes - 1) / kTsdfLanes) * (size_t)volume->ny * (size_t)volume->nz;
+  const size_t blocks = (spans + kTsdfBlockY - 1) / kTsdfBlockY;
+  const dim3 grid((unsigned)(blocks < kTsdfMaxBlocks ? blocks : kTsdfMaxBlocks));
+  hipLaunchKernelGGL(k_tsdf_integrate, grid, dim3(kTsdfBlockX, kTsdfBlockY), 0, stream, a);
+  if (int rc = launch_check(h, "tsdf integrate")) return rc;
+  return stage_counts(h, stream, d_totals, 2, d_counts, counts);
+}
+
+int pm_tsdf_raycast(pm_handle* h, const pm_cloud_camera* camera, const pm_tsdf_volume* volume, const pm_motion* pose,
+                    const pm_tsdf_raycast_options* options, const void* d_voxels, int rows, int cols, float* d_disp_out,
+                    float* d_normals_out, int* d_counts, int* counts) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_tsdf_raycast";
+  if (int rc = check_tsdf_common(h, what, camera, volume, pose, options, d_voxels)) return rc;
+  if (!(options->step > 0.f && options->step <= 1.f)) {
+    set_err(h, "%s: step must lie in (0, 1]", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (!std::isfinite(options->min_range) || !std::isfinite(options->max_range) || !(options->min_range > 0.f) ||
+      !(options->min_range < options->max_range)) {
+    set_err(h, "%s: min_range and max_range must be finite with 0 < min_range < max_range", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (std::isnan(options->min_weight) || options->min_weight < 0.f) {
+    set_err(h, "%s: min_weight must not be NaN or negative", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
+  if (!d_disp_out && !d_normals_out && !d_counts && !counts) {
+    set_err(h, "%s: no output: d_disp_out, d_normals_out, d_counts and counts are all null", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_tsdf_size(h, what, *volume)) return rc;
+  TsdfRaycastArgs a = {};
+  a.cam = cloud_cam(*camera);
+  a.grid = tsdf_grid(*volume);
+  for (int i = 0; i < 9; ++i) a.R[i] = pose->R[i];
+  motion_inverse(pose->R, pose->t, a.Ri, a.c);  // in binary64 (not contracted: -ffp-contract=off)
+  a.min_range = (double)options->min_range, a.max_range = (double)options->max_range;
+  a.ds = (double)options->step * volume->trunc;
+  a.min_weight = options->min_weight;
+  a.n_samples = tsdf_sample_count(a.min_range, a.max_range, a.ds);
+  if (a.n_samples < 0) {
+    set_err(h, "%s: step * trunc puts more than 65536 samples between min_range and max_range", what);
+    return PM_ERR_SIZE;
+  }
+  a.voxels = static_cast<const TsdfVoxel*>(d_voxels), a.rows = rows, a.cols = cols;
+  a.disp_out = d_disp_out, a.normals_out = d_normals_out;
+  ImagingState* st = nullptr;
+  hipStream_t stream = nullptr;
+  if (int rc = stage_begin(h, what, &st, &stream)) return rc;
+  PM_HIP(h, st->tsdf_counts.reserve(sizeof(int) * kTsdfHeader, stream));
+  int* d_totals = st->tsdf_counts.get();
+  a.counts = d_totals;
+  PM_HIP(h, hipMemsetAsync(d_totals, 0, sizeof(int) * kTsdfHeader, stream));
+  const dim3 grid((unsigned)((cols + kTsdfLanes - 1) / kTsdfLanes), (unsigned)((rows + kTsdfBlockY - 1) / kTsdfBlockY));
+  hipLaunchKernelGGL(k_tsdf_raycast, grid, dim3(kTsdfBlockX, kTsdfBlockY), 0, stream, a);
+  if (int rc = launch_check(h, "tsdf raycast")) return rc;
+  return stage_counts(h, stream, d_totals, 1, d_counts, counts);
+}
+
+void pm_debug_tsdf_constants(int* lanes, int* waves) {
+  if (lanes) *lanes = kTsdfLanes;
+  if (waves) *waves = kTsdfWaves;
 }
 
 // ---- camera motion between two frames: features of the old left image tracked into the new one (pm_track.hpp) ----------------

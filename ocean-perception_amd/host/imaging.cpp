@@ -830,5 +830,108 @@ core::Image<core::Vec3f> PlaneNormals(pm::PatchmatchGpu& matcher, const StereoMo
   return out;
 }
 
+// ---- TsdfVolume: the device memory is a DeviceBuffer on the matcher's handle ---------------------------------------------------
+struct TsdfVolume::Impl {
+  pm_handle* h;
+  pm_tsdf_volume volume;
+  DeviceBuffer voxels;
+  Impl(pm_handle* handle, const pm_tsdf_volume& v, size_t bytes) : h(handle), volume(v), voxels(handle, bytes) {}
+  void Check(int status, const char* what) const {  // the matcher's handle, not the imaging context's
+    if (status != PM_OK) throw std::runtime_error(std::string(what) + ": " + pm_status_string(status) + " -- " + pm_last_error(h));
+  }
+};
+
+namespace {
+pm_motion ToMotion(const Motion& m) {
+  pm_motion out;
+  for (size_t i = 0; i < 9; ++i) out.R[i] = m.R[i];
+  for (size_t i = 0; i < 3; ++i) out.t[i] = m.t[i];
+  return out;
+}
+}  // namespace
+
+TsdfVolume::TsdfVolume(pm::PatchmatchGpu& matcher, const TsdfGrid& grid) : grid_(grid) {
+  pm_handle* h = matcher.handle();
+  if (!h) throw std::runtime_error("TsdfVolume: the matcher has no handle yet (plan it or match once)");
+  const pm_tsdf_volume v = {grid.nx, grid.ny, grid.nz, {grid.origin[0], grid.origin[1], grid.origin[2]}, grid.voxel, grid.trunc,
+                            grid.max_weight};
+  const size_t bytes = pm_tsdf_bytes(&v);
+  if (bytes == 0) throw std::invalid_argument("TsdfVolume: the grid is invalid or exceeds 2^31 - 1 voxels");
+  impl_.reset(new Impl(h, v, bytes));
+  Clear();
+}
+
+TsdfVolume::~TsdfVolume() = default;
+
+void* TsdfVolume::device() { return impl_->voxels.as<void>(); }
+
+void TsdfVolume::Clear() { impl_->Check(pm_tsdf_clear(impl_->h, &impl_->volume, device()), "pm_tsdf_clear"); }
+
+std::array<int, 2> TsdfVolume::IntegrateDevice(const StereoModel& model, const Motion& pose, const float* d_disp,
+                                               const float* d_weight, int rows, int cols, const TsdfIntegrateOptions& options,
+                                               bool want_counts) {
+  const pm_cloud_camera cam = CloudCamera(model);
+  const pm_motion m = ToMotion(pose);
+  const pm_tsdf_integrate_options opt = {options.min_disp, options.max_range};
+  int counts[2] = {-1, -1};
+  impl_->Check(pm_tsdf_integrate(impl_->h, &cam, &impl_->volume, &m, &opt, d_disp, d_weight, rows, cols, device(), nullptr,
+                                 want_counts ? counts : nullptr),
+               "pm_tsdf_integrate");
+  return {{counts[0], counts[1]}};
+}
+
+std::array<int, 2> TsdfVolume::Integrate(const StereoModel& model, const Motion& pose, const core::Image<float>& disp,
+                                         const core::Image<float>* weight, const TsdfIntegrateOptions& options) {
+  if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("TsdfVolume::Integrate: empty map");
+  if (weight) SameSize(disp.rows, disp.cols, weight->rows, weight->cols, "TsdfVolume::Integrate");
+  DeviceBuffer d_disp(impl_->h, Bytes(disp));
+  impl_->Check(pm_upload(impl_->h, d_disp.as<void>(), disp.data(), Bytes(disp)), "pm_upload");
+  std::unique_ptr<DeviceBuffer> d_weight;
+  if (weight) {
+    d_weight.reset(new DeviceBuffer(impl_->h, Bytes(*weight)));
+    impl_->Check(pm_upload(impl_->h, d_weight->as<void>(), weight->data(), Bytes(*weight)), "pm_upload");
+  }
+  return IntegrateDevice(model, pose, d_disp.as<float>(), d_weight ? d_weight->as<float>() : nullptr, disp.rows, disp.cols, options,
+                         /*want_counts=*/true);  // synchronises: the buffers may go
+}
+
+int TsdfVolume::RaycastDevice(const StereoModel& model, const Motion& pose, int rows, int cols, float* d_disp_out,
+                              float* d_normals_out, const TsdfRaycastOptions& options, bool want_counts) {
+  const pm_cloud_camera cam = CloudCamera(model);
+  const pm_motion m = ToMotion(pose);
+  const pm_tsdf_raycast_options opt = {options.min_range, options.max_range, options.step, options.min_weight};
+  int hits = -1;
+  impl_->Check(pm_tsdf_raycast(impl_->h, &cam, &impl_->volume, &m, &opt, device(), rows, cols, d_disp_out, d_normals_out, nullptr,
+                               want_counts ? &hits : nullptr),
+               "pm_tsdf_raycast");
+  return hits;
+}
+
+int TsdfVolume::Raycast(const StereoModel& model, const Motion& pose, int rows, int cols, core::Image<float>* disp,
+                        core::Image<core::Vec3f>* normals, const TsdfRaycastOptions& options) {
+  if (rows <= 0 || cols <= 0) throw std::invalid_argument("TsdfVolume::Raycast: empty size");
+  const size_t px = (size_t)rows * cols;
+  std::unique_ptr<DeviceBuffer> d_disp, d_normals;
+  if (disp) d_disp.reset(new DeviceBuffer(impl_->h, 4 * px));
+  if (normals) d_normals.reset(new DeviceBuffer(impl_->h, 12 * px));
+  const int hits = RaycastDevice(model, pose, rows, cols, d_disp ? d_disp->as<float>() : nullptr,
+                                 d_normals ? d_normals->as<float>() : nullptr, options, /*want_counts=*/true);
+  if (disp) {
+    if (disp->rows != rows || disp->cols != cols) disp->create(rows, cols);
+    impl_->Check(pm_download(impl_->h, disp->data(), d_disp->as<void>(), 4 * px), "pm_download");
+  }
+  if (normals) {
+    if (normals->rows != rows || normals->cols != cols) normals->create(rows, cols);
+    impl_->Check(pm_download(impl_->h, normals->data(), d_normals->as<void>(), 12 * px), "pm_download");
+  }
+  return hits;
+}
+
+std::vector<float> TsdfVolume::Download() {
+  std::vector<float> out(2 * voxels());
+  impl_->Check(pm_download(impl_->h, out.data(), device(), sizeof(float) * out.size()), "pm_download");
+  return out;
+}
+
 }  // namespace imaging
 }  // namespace bm

@@ -16,6 +16,7 @@
 
 #include <array>
 #include <cmath>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -285,6 +286,64 @@ Motion SolveMotion(const StereoModel& model, const SolveOptions& options, const 
 Motion EstimateMotion(pm::PatchmatchGpu& matcher, const StereoModel& model, const TrackOptions& track_options,
                       const SolveOptions& solve_options, const Motion* guess, const core::Image<uint8_t>& left_old,
                       const core::Image<float>& disp_old, const core::Image<uint8_t>& left_new, pm_motion_info* info = nullptr);
+
+// A persistent world-frame model of a sequence: a truncated signed distance volume that Integrate folds left disparity maps
+// and their camera poses into and Raycast renders back, at any pose, as an ordinary left disparity map with normals -- what
+// MakePointCloud, MakeGridMesh, ReprojectDisparity (with the identity motion, for the right seed), FilterConsistency and
+// FuseDisparity take (pm/imaging.h: pm_tsdf_clear, pm_tsdf_integrate, pm_tsdf_raycast; definition: tests/tsdf_ref.py).  A pose is
+// a Motion from the WORLD frame into the left camera's: X_cam = R X_world + t.
+struct TsdfGrid {  // pm_tsdf_volume
+  int nx = 0, ny = 0, nz = 0;               // voxels, x fastest
+  std::array<double, 3> origin{{0, 0, 0}};  // the world position of the centre of voxel (0, 0, 0)
+  double voxel = 0.01;                      // edge length, > 0
+  double trunc = 0.04;                      // truncation distance, > 0 (typically 3..5 voxels)
+  float max_weight = 64.f;                  // > 0: the weight saturates here
+};
+struct TsdfIntegrateOptions {  // pm_tsdf_integrate_options
+  float min_disp = 0.f;   // a pixel measures iff disp > 0 and disp >= min_disp
+  float max_range = 0.f;  // > 0: a measured range above it is dropped; 0 = no limit
+};
+struct TsdfRaycastOptions {  // pm_tsdf_raycast_options
+  float min_range = 0.1f, max_range = 10.f;  // finite, 0 < min_range < max_range
+  float step = 0.5f;                         // the march's step as a fraction of trunc, in (0, 1]
+  float min_weight = 0.f;                    // a voxel takes part iff weight > 0 and weight >= min_weight
+};
+// Owns the volume's device memory (8 bytes per voxel) on the matcher's handle, which must be planned and must outlive the
+// volume; everything runs on that handle's stream.  Throws std::invalid_argument for a grid pm_tsdf_bytes refuses and where
+// image sizes differ, std::runtime_error where the C call refuses.
+class TsdfVolume {
+ public:
+  TsdfVolume(pm::PatchmatchGpu& matcher, const TsdfGrid& grid);  // allocated and cleared
+  ~TsdfVolume();
+  TsdfVolume(const TsdfVolume&) = delete;
+  TsdfVolume& operator=(const TsdfVolume&) = delete;
+  const TsdfGrid& grid() const { return grid_; }
+  size_t voxels() const { return (size_t)grid_.nx * grid_.ny * grid_.nz; }
+  void* device();  // nx * ny * nz records {float tsdf; float weight}
+  void Clear();
+  // Host map in; weight: a plane of the map's size, null = 1.0.  Returns {voxels in view, voxels updated}.
+  std::array<int, 2> Integrate(const StereoModel& model, const Motion& pose, const core::Image<float>& disp,
+                               const core::Image<float>* weight = nullptr,
+                               const TsdfIntegrateOptions& options = TsdfIntegrateOptions());
+  // Device maps in (those a device Match() left behind); with want_counts = false it only enqueues and returns {-1, -1}.
+  std::array<int, 2> IntegrateDevice(const StereoModel& model, const Motion& pose, const float* d_disp, const float* d_weight,
+                                     int rows, int cols, const TsdfIntegrateOptions& options = TsdfIntegrateOptions(),
+                                     bool want_counts = true);
+  // Host images out, each where it is asked for (at least one).  Returns the pixels hit.
+  int Raycast(const StereoModel& model, const Motion& pose, int rows, int cols, core::Image<float>* disp,
+              core::Image<core::Vec3f>* normals = nullptr, const TsdfRaycastOptions& options = TsdfRaycastOptions());
+  // Device maps out: d_disp_out rows x cols floats, d_normals_out rows x cols x 3 floats, either may be null; with
+  // want_counts = false it only enqueues and returns -1.
+  int RaycastDevice(const StereoModel& model, const Motion& pose, int rows, int cols, float* d_disp_out, float* d_normals_out,
+                    const TsdfRaycastOptions& options = TsdfRaycastOptions(), bool want_counts = true);
+  // The records, 2 floats per voxel (tsdf, weight), x fastest; synchronises.
+  std::vector<float> Download();
+
+ private:
+  struct Impl;
+  std::unique_ptr<Impl> impl_;
+  TsdfGrid grid_;
+};
 
 }  // namespace imaging
 }  // namespace bm

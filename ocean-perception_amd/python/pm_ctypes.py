@@ -51,6 +51,7 @@ EXPORTS = [
     "pm_filter_consistency",
     "pm_disparity_confidence", "pm_debug_confidence_constants",
     "pm_fuse_disparity",
+    "pm_tsdf_bytes", "pm_tsdf_clear", "pm_tsdf_integrate", "pm_tsdf_raycast", "pm_debug_tsdf_constants",
     "pm_track_features", "pm_solve_motion", "pm_estimate_motion",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
     "pm_debug_match_plan",
@@ -282,6 +283,43 @@ PM_FUSE_VALID, PM_FUSE_KEPT, PM_FUSE_FUSED, PM_FUSE_FILLED = 1, 2, 4, 8
 class PmFuseOptions(C.Structure):  # pm_fuse_disparity
     _fields_ = [("max_diff", C.c_float), ("radius", C.c_int), ("min_consistent", C.c_int), ("max_conflicts", C.c_int),
                 ("fill_min_sources", C.c_int), ("fill_max_diff", C.c_float)]
+
+
+class PmTsdfVolume(C.Structure):  # pm_tsdf_*: the caller-owned volume, nx * ny * nz records {float tsdf; float weight}
+    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("origin", C.c_double * 3), ("voxel", C.c_double),
+                ("trunc", C.c_double), ("max_weight", C.c_float)]
+
+
+class PmTsdfIntegrateOptions(C.Structure):
+    _fields_ = [("min_disp", C.c_float), ("max_range", C.c_float)]
+
+
+class PmTsdfRaycastOptions(C.Structure):
+    _fields_ = [("min_range", C.c_float), ("max_range", C.c_float), ("step", C.c_float), ("min_weight", C.c_float)]
+
+
+def tsdf_volume(values):
+    """A PmTsdfVolume from a dict (nx, ny, nz, origin, voxel, trunc, max_weight) or those seven values in that order; a
+    PmTsdfVolume or None passes through."""
+    if values is None or isinstance(values, PmTsdfVolume):
+        return values
+    if isinstance(values, dict):
+        values = [values[k] for k in ("nx", "ny", "nz", "origin", "voxel", "trunc", "max_weight")]
+    nx, ny, nz, origin, voxel, trunc, max_weight = values
+    return PmTsdfVolume(int(nx), int(ny), int(nz), (C.c_double * 3)(*[float(v) for v in origin]), float(voxel), float(trunc),
+                        float(max_weight))
+
+
+def tsdf_bytes(volume):
+    """pm_tsdf_bytes: the bytes of the volume's device buffer, 0 if it is invalid or too large."""
+    return int(load().pm_tsdf_bytes(_ref(tsdf_volume(volume))))
+
+
+def tsdf_constants():
+    """pm_debug_tsdf_constants: (voxels along x / pixels of a row one wavefront owns, wavefronts per block)."""
+    a, b = C.c_int(0), C.c_int(0)
+    load().pm_debug_tsdf_constants(C.byref(a), C.byref(b))
+    return a.value, b.value
 
 
 PM_TRACK_PREDICTED, PM_TRACK_MATCHED, PM_TRACK_SUBPIX_X, PM_TRACK_SUBPIX_Y, PM_TRACK_FAIL_SAD, PM_TRACK_FAIL_GAP = 1, 2, 4, 8, 16, 32
@@ -533,6 +571,18 @@ def load():
                                       C.POINTER(PmMotion), C.POINTER(vp), C.c_int, C.c_int, vp, vp, vp, vp, vp,
                                       C.POINTER(C.c_int)]
     lib.pm_fuse_disparity.restype = C.c_int
+    lib.pm_tsdf_bytes.argtypes = [C.POINTER(PmTsdfVolume)]
+    lib.pm_tsdf_bytes.restype = C.c_size_t
+    lib.pm_tsdf_clear.argtypes = [vp, C.POINTER(PmTsdfVolume), vp]
+    lib.pm_tsdf_clear.restype = C.c_int
+    lib.pm_tsdf_integrate.argtypes = [vp, C.POINTER(PmCloudCamera), C.POINTER(PmTsdfVolume), C.POINTER(PmMotion),
+                                      C.POINTER(PmTsdfIntegrateOptions), vp, vp, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int)]
+    lib.pm_tsdf_integrate.restype = C.c_int
+    lib.pm_tsdf_raycast.argtypes = [vp, C.POINTER(PmCloudCamera), C.POINTER(PmTsdfVolume), C.POINTER(PmMotion),
+                                    C.POINTER(PmTsdfRaycastOptions), vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(C.c_int)]
+    lib.pm_tsdf_raycast.restype = C.c_int
+    lib.pm_debug_tsdf_constants.argtypes = [C.POINTER(C.c_int)] * 2
+    lib.pm_debug_tsdf_constants.restype = None
     lib.pm_track_features.argtypes = [vp, C.POINTER(PmCloudCamera), C.POINTER(PmTrackOptions), C.POINTER(PmMotion), vp, vp, vp,
                                       C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int)]
     lib.pm_track_features.restype = C.c_int
@@ -1209,6 +1259,36 @@ class Engine:
                                                rows, cols, d_out, d_count, d_spread, d_flags, d_counts,
                                                n if want_counts else None), "pm_fuse_disparity")
         return tuple(n) if want_counts else None
+
+    def tsdf_clear(self, volume, d_voxels):
+        """pm_tsdf_clear (raw device address): every record of the volume becomes (+0.0, +0.0), on the handle's stream."""
+        self._check(self.lib.pm_tsdf_clear(self.h, _ref(tsdf_volume(volume)), d_voxels), "pm_tsdf_clear")
+
+    def tsdf_integrate(self, camera, volume, pose, d_disp, rows, cols, d_voxels, min_disp=0.0, max_range=0.0, d_weight=None,
+                       d_counts=None, want_counts=False):
+        """pm_tsdf_integrate (raw device addresses): the left map d_disp, seen from pose ((R, t) or PmMotion, X_cam = R X_world
+        + t), folded into the volume at d_voxels, on the handle's stream.  d_weight: a float32 weight plane, None = 1.0;
+        d_counts: two device ints.  -> (voxels in view, voxels updated) with want_counts (the call then synchronises)."""
+        c = cloud_camera(camera)
+        o = PmTsdfIntegrateOptions(min_disp, max_range)
+        n = (C.c_int * 2)(-1, -1)
+        self._check(self.lib.pm_tsdf_integrate(self.h, _ref(c), _ref(tsdf_volume(volume)), _ref(as_motion(pose)), C.byref(o),
+                                               d_disp, d_weight, rows, cols, d_voxels, d_counts, n if want_counts else None),
+                    "pm_tsdf_integrate")
+        return (n[0], n[1]) if want_counts else None
+
+    def tsdf_raycast(self, camera, volume, pose, d_voxels, rows, cols, min_range=0.1, max_range=10.0, step=0.5, min_weight=0.0,
+                     d_disp_out=None, d_normals_out=None, d_counts=None, want_counts=False):
+        """pm_tsdf_raycast (raw device addresses): the volume rendered at pose into a left disparity map d_disp_out
+        [rows][cols] float32 and camera-frame normals d_normals_out [rows][cols][3] float32, each where given, on the handle's
+        stream.  d_counts: one device int.  -> the pixels hit with want_counts (the call then synchronises), else None."""
+        c = cloud_camera(camera)
+        o = PmTsdfRaycastOptions(min_range, max_range, step, min_weight)
+        n = (C.c_int * 1)(-1)
+        self._check(self.lib.pm_tsdf_raycast(self.h, _ref(c), _ref(tsdf_volume(volume)), _ref(as_motion(pose)), C.byref(o),
+                                             d_voxels, rows, cols, d_disp_out, d_normals_out, d_counts,
+                                             n if want_counts else None), "pm_tsdf_raycast")
+        return n[0] if want_counts else None
 
     def track_features(self, camera, d_left_old, d_disp_old, d_left_new, rows, cols, guess=None, cell=16, patch_radius=3,
                        search_radius=5, min_score=1, min_disp=0.0, max_disp=0.0, max_sad=0, min_gap=0, capacity=0, d_tracks=None,

@@ -1,0 +1,744 @@
+"""A persistent world-frame model: a TSDF volume integrated from disparity maps and raycast back (include/pm/imaging.h:
+pm_tsdf_bytes, pm_tsdf_clear, pm_tsdf_integrate, pm_tsdf_raycast).
+
+CPU tests pin the definition (tests/tsdf_ref.py) against an ANALYTIC scene -- a plane at world Z = Z0 with a box in front of it,
+whose disparity map at any pose is rendered here by exact ray intersection, so the maps of different poses are consistent --
+show ON THE DEFINITION ALONE that a fused model beats a single noisy map, and run the kernels' own per-thread code
+(csrc/pm_tsdf_body.hpp) on the host under ASan / UBSan, spans and blocks forwards and backwards.  GPU tests hold the kernels to
+the definition with tolerance 0 -- every operation of the definition is one IEEE rounding, the build uses -ffp-contract=off, no
+voxel or pixel is touched by two threads and only integer addition crosses workgroups -- with guard bands around every buffer."""
+import ctypes as C
+import functools
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import mesh_ref
+import pointcloud_ref
+import tsdf_ref as TR
+from conftest import ROOT
+from cpp_build import build_host_kernel
+from test_reproject import CAM, FXB
+
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import fuzz_tsdf as FT  # noqa: E402  (check_tsdf: the device-against-definition comparison)
+
+gpu = pytest.mark.gpu
+
+ROWS, COLS = 48, 80
+I3 = np.eye(3).ravel()
+IDENT = (I3, np.zeros(3))
+
+# ---- the analytic scene -------------------------------------------------------------------------------------------------------
+Z0 = 2.0                                                # the plane: world Z = Z0
+BOX = ((-0.07, 0.05), (-0.04, 0.05), (Z0 - 0.12, Z0))   # the box on it: x, y, z extents; its front face is at Z0 - 0.12
+VOXEL, TRUNC = 0.01, 0.06
+GRID = TR.make_grid(52, 34, 40, (-0.255, -0.165, Z0 - 0.3), VOXEL, TRUNC, max_weight=64.0)
+RAY = dict(min_range=1.2, max_range=2.4, step=0.5, min_weight=0.0)
+CENTRE = np.array([0.0, 0.0, Z0 - 0.06])
+
+
+def pose_on_arc(degrees, axis=(0, 1, 0), distance=None):
+    """The pose (R[9], t[3]; X_cam = R X_world + t) of a camera on the circle about CENTRE through the world origin's camera,
+    turned by `degrees` about `axis` and looking at CENTRE."""
+    Rwc = FT.rotation(axis, degrees)  # camera to world
+    c = CENTRE + Rwc @ np.array([0.0, 0.0, -(CENTRE[2] if distance is None else distance)])
+    R = Rwc.T
+    return R.ravel(), -(R @ c)
+
+
+ARC = tuple(pose_on_arc(a) for a in (-2.5, -1.5, -0.5, 0.5, 1.5, 2.5)) + (pose_on_arc(1.0, (1, 0, 0)),)
+
+
+def render(pose, rows=ROWS, cols=COLS, cam=CAM):
+    """The scene's left disparity map at `pose` by exact ray intersection, binary64 until the final rounding: every pixel's
+    ray against the plane and against the box's six faces (slab method); the nearer wins; +0.0 where the ray meets nothing in
+    front of the camera."""
+    fx, fy, cx, cy, baseline = (np.float64(v) for v in cam)
+    R = np.asarray(pose[0], np.float64).reshape(3, 3)
+    t = np.asarray(pose[1], np.float64)
+    c = -(R.T @ t)
+    x = np.arange(cols, dtype=np.float64)[None, :]
+    y = np.arange(rows, dtype=np.float64)[:, None]
+    d_cam = np.stack(np.broadcast_arrays((x - cx) / fx, (y - cy) / fy, np.ones((rows, cols))), -1)
+    wd = d_cam @ R  # R^T d per pixel
+    with np.errstate(divide="ignore", invalid="ignore"):
+        s_plane = (Z0 - c[2]) / wd[..., 2]
+        s_plane = np.where(s_plane > 0, s_plane, np.inf)
+        lo, hi = np.full((rows, cols), -np.inf), np.full((rows, cols), np.inf)
+        for i in range(3):
+            a = (BOX[i][0] - c[i]) / wd[..., i]
+            b = (BOX[i][1] - c[i]) / wd[..., i]
+            par = wd[..., i] == 0
+            inside = (c[i] >= BOX[i][0]) & (c[i] <= BOX[i][1])
+            a = np.where(par, np.where(inside, -np.inf, np.inf), a)
+            b = np.where(par, np.where(inside, np.inf, -np.inf), b)
+            lo, hi = np.maximum(lo, np.minimum(a, b)), np.minimum(hi, np.maximum(a, b))
+        s_box = np.where((lo <= hi) & (lo > 0), lo, np.inf)
+        s = np.minimum(s_plane, s_box)
+        return np.where(np.isfinite(s), (fx * baseline) / s, 0.0).astype(np.float32)
+
+
+def flat_mask(disp, r):
+    """Pixels at least r pixels inside the image whose (2r+1)^2 neighbourhood holds one value: away from every silhouette."""
+    rows, cols = disp.shape
+    m = np.zeros((rows, cols), bool)
+    core = np.ones((rows - 2 * r, cols - 2 * r), bool)
+    for dy in range(2 * r + 1):
+        for dx in range(2 * r + 1):
+            core &= disp[dy:dy + rows - 2 * r, dx:dx + cols - 2 * r] == disp[r:rows - r, r:cols - r]
+    m[r:rows - r, r:cols - r] = core
+    return m
+
+
+def ulps(got, want):
+    return np.abs(got.astype(np.float64) - want.astype(np.float64)) / np.spacing(np.abs(want)).astype(np.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def one_view():
+    """The noiseless map of the identity pose integrated once into the cleared volume."""
+    truth = render(IDENT)
+    return truth, TR.integrate(GRID, TR.clear(GRID), truth, CAM, *IDENT)
+
+
+# ---- 1. the definition ------------------------------------------------------------------------------------------------
+def test_definition_one_noiseless_view_is_returned_within_two_ulps():
+    """Identity pose, one noiseless map, raycast at the same pose.  Where the ray stays inside the volume and every voxel a
+    sample near the surface reads saw ONE constant disparity d (flat_mask with r = 4: a voxel is 0.01 / 1.88 * 412.7 = 2.2
+    pixels wide at the nearest surface, a sample's corners span one voxel, rint adds half a pixel), the stored values are
+    (float)((Zm - Zc) / trunc) with Zm = fxB / d: linear in z, constant in x and y.  The x and y lerps of equal values are exact;
+    the two slice values and the z lerp's subtraction, product and sum round five times, each by at most 2^-25 (|value| <= 1),
+    so a sample is within 5 * 2^-25 of the linear function; the crossing found from two samples ds apart, whose exact values
+    differ by ds / trunc, is within 2 * 5 * 2^-25 * trunc of Zm in depth, a relative error of 10 * 2^-25 * trunc / Zm <=
+    10 * 2^-25 * 0.06 / 1.88 = 0.32 * 2^-25 -- less than a third of a binary32 ulp of the disparity (an ulp is at least 2^-24
+    relative) -- and the final rounding adds half an ulp.  With step 0.5 and trunc = 6 voxels no clamped or unobserved voxel is
+    read at the crossing (|sdf| <= trunc / 2 + voxel < trunc).  Bound: 2 ulps; reached: 0."""
+    truth, out = one_view()
+    assert out["counts"][0] > 0.4 * GRID["nx"] * GRID["ny"] * GRID["nz"] and 0.5 * out["counts"][0] < out["counts"][1] < out["counts"][0]
+    ray = TR.raycast(GRID, out["voxels"], CAM, *IDENT, ROWS, COLS, **RAY)
+    flat = flat_mask(truth, 4)
+    assert flat.sum() > 0.5 * ROWS * COLS and len(np.unique(truth[flat])) == 2  # the plane and the box's front face
+    assert ray["hit"][flat].all() and ray["counts"][0] == ray["hit"].sum() >= flat.sum()
+    worst = ulps(ray["disp"], truth)[flat].max()
+    print("flat pixels %d, hit %d, worst %.2f ulps" % (flat.sum(), ray["hit"].sum(), worst))
+    assert worst <= 2.0
+    assert (ray["disp"][~ray["hit"]] == 0).all() and not np.signbit(ray["disp"][~ray["hit"]]).any()
+    # the normals of both faces look back along the optical axis; no hit, no normal
+    n = ray["normals"]
+    inner = flat_mask(truth, 8)
+    assert inner.sum() > 500 and np.abs(n[inner] - np.array([0, 0, -1], np.float32)).max() < 1e-5
+    assert (n[~ray["hit"]] == 0).all() and (np.abs(np.linalg.norm(n[ray["hit"] & (n != 0).any(-1)], axis=-1) - 1) < 1e-6).all()
+
+
+def test_definition_a_second_integrate_keeps_tsdf_and_raises_the_weight_until_max_weight_holds_it():
+    truth, out = one_view()
+    for max_weight, want_w in ((64.0, (2.0, 3.0)), (2.0, (2.0, 2.0)), (1.0, (1.0, 1.0)), (1.5, (1.5, 1.5))):
+        grid = dict(GRID, max_weight=max_weight)
+        first = TR.integrate(grid, TR.clear(grid), truth, CAM, *IDENT)
+        assert np.array_equal(FT.bits(first["voxels"]), FT.bits(out["voxels"]))  # w = 1 either way
+        second = TR.integrate(grid, first["voxels"], truth, CAM, *IDENT)
+        up = first["updated"]
+        assert np.array_equal(second["counts"], first["counts"]) and np.array_equal(second["updated"], up)
+        assert np.array_equal(FT.bits(second["voxels"][..., 0]), FT.bits(first["voxels"][..., 0]))  # ((f * 1) + (f * 1)) / 2
+        assert (second["voxels"][..., 1][up] == np.float32(want_w[0])).all() and (second["voxels"][..., 1][~up] == 0).all()
+        third = TR.integrate(grid, second["voxels"], truth, CAM, *IDENT)
+        assert (third["voxels"][..., 1][up] == np.float32(want_w[1])).all()
+        if max_weight == 2.0:  # held: (f * 2 + f) / 3 may move the last bit, the weight does not move
+            assert np.abs(third["voxels"][..., 0] - first["voxels"][..., 0]).max() <= 2 ** -23
+
+
+def test_definition_nothing_in_view_changes_nothing():
+    """The camera behind the volume (it looks away from it) and the volume beside the view: both counts 0, every record keeps
+    its bits -- those of a volume with a history, NaN payloads included."""
+    truth, _ = one_view()
+    rng = np.random.default_rng(2)
+    start = rng.uniform(-1, 1, (GRID["nz"], GRID["ny"], GRID["nx"], 2)).astype(np.float32)
+    start.view(np.uint32)[0, 0, :4, 0] = (0x7FC00001, 0xFFC00000, 0x80000000, 0x00000001)
+    behind = (I3, np.array([0.0, 0.0, -(Z0 + 1.0)]))         # the camera's centre at Z0 + 1, looking along +z: all behind it
+    beside = (I3, np.array([40.0, 0.0, 0.0]))                # the volume 40 m to the right of the optical axis
+    away = (FT.rotation((0, 1, 0), 180.0).ravel(), np.zeros(3))
+    for pose in (behind, beside, away):
+        out = TR.integrate(GRID, start, truth, CAM, *pose)
+        assert tuple(out["counts"]) == (0, 0) and np.array_equal(FT.bits(out["voxels"]), FT.bits(start))
+        ray = TR.raycast(GRID, one_view()[1]["voxels"], CAM, *pose, ROWS, COLS, **RAY)
+        assert ray["counts"][0] == 0 and (FT.bits(ray["disp"]) == 0).all() and (FT.bits(ray["normals"]) == 0).all()
+
+
+def test_definition_every_special_weight_and_value():
+    """pm_fuse_disparity's weight rule: 0, -0.0, negatives, NaN and +-inf take no part, a subnormal and ordinary weights do;
+    a disparity of 0, -0.0, a negative, NaN or one below min_disp measures nothing, and a range beyond max_range is dropped."""
+    truth, plain = one_view()
+    w = np.ones((ROWS, COLS), np.float32)
+    w[:, :9 * 8] = np.repeat(FT.WEIGHT_SPECIALS, 8)[None, :]
+    takes = np.isfinite(w) & (w > 0)
+    assert (~takes).sum() == 6 * 8 * ROWS  # 0, -0.0, -1, NaN, +inf, -inf; 1e-45, 0.25 and 3 take part
+    out = TR.integrate(GRID, TR.clear(GRID), truth, CAM, *IDENT, weight=w)
+    X, Y, Z = TR.voxel_centres(GRID)
+    seen, iu, iv, _ = TR.project(X, Y, Z, CAM, *IDENT, ROWS, COLS)
+    iu, iv = np.broadcast_to(iu, seen.shape), np.broadcast_to(iv, seen.shape)
+    assert np.array_equal(out["updated"], plain["updated"] & takes[iv, iu]) and 0 < out["counts"][1] < plain["counts"][1]
+    assert np.array_equal(out["in_view"], plain["in_view"])
+    up = out["updated"]
+    assert np.array_equal(FT.bits(out["voxels"][..., 1][up]), FT.bits(w[iv, iu][up]))  # min(0 + wn, 64)
+    exact = up & np.isin(w[iv, iu], (0.25, 1.0))  # (0 * 0 + f * wn) / wn is f where wn is a power of two
+    assert exact.sum() > 1000 and np.array_equal(FT.bits(out["voxels"][..., 0][exact]), FT.bits(plain["voxels"][..., 0][exact]))
+    normal = up & (w[iv, iu] >= 0.25)  # (1e-45 is subnormal: f * wn has one bit left)
+    assert np.abs(out["voxels"][..., 0][normal] - plain["voxels"][..., 0][normal]).max() <= 2.0 ** -23
+    d = truth.copy()
+    d[:, :FT.SPECIALS.size * 8] = np.repeat(FT.SPECIALS, 8)[None, :]
+    with np.errstate(invalid="ignore"):
+        good = (d > 0) & (d >= 1.0)
+    out = TR.integrate(GRID, TR.clear(GRID), d, CAM, *IDENT, min_disp=1.0)
+    assert not out["updated"][~good[iv, iu]].any() and out["updated"].any() and np.array_equal(out["in_view"], plain["in_view"])
+    assert np.isinf(d).sum() == ROWS * 8 and not out["updated"][np.isinf(d)[iv, iu]].any()  # +inf: range 0, far behind every voxel
+    near_only = TR.integrate(GRID, TR.clear(GRID), truth, CAM, *IDENT, max_range=Z0 - 0.06)
+    assert 0 < near_only["counts"][1] < plain["counts"][1]
+    assert np.array_equal(near_only["updated"], plain["updated"] & (truth > FXB / (Z0 - 0.06))[iv, iu])
+
+
+def _slab(values_by_slice, weight=1.0, grid_n=(4, 4, None)):
+    """A small volume whose tsdf depends on the z slice alone, seen by a camera on its axis."""
+    nz = len(values_by_slice)
+    grid = TR.make_grid(grid_n[0], grid_n[1], nz, (-0.015, -0.015, 1.0), 0.01, 0.04)
+    vol = np.zeros((nz, grid_n[1], grid_n[0], 2), np.float32)
+    vol[..., 0] = np.asarray(values_by_slice, np.float32)[:, None, None]
+    vol[..., 1] = weight
+    return grid, vol
+
+
+SLAB_RAY = dict(min_range=0.9, max_range=1.2, step=0.25, min_weight=0.0)
+SLAB_CAM = (400.0, 400.0, 4.0, 4.0, 0.1)  # cx, cy integers: pixel (4, 4) looks along the axis
+
+
+def test_definition_front_faces_back_faces_and_unobserved_corners():
+    # a front face: + to -, crossing between slice 2 (z = 1.02) and slice 3 (z = 1.03) at 1.025
+    grid, vol = _slab([1.0, 1.0, 0.5, -0.5, -1.0, -1.0])
+    ray = TR.raycast(grid, vol, SLAB_CAM, *IDENT, 9, 9, **SLAB_RAY)
+    assert ray["hit"][4, 4] and abs(40.0 / float(ray["disp"][4, 4]) - 1.025) < 1e-6
+    assert np.abs(ray["normals"][4, 4] - (0, 0, -1)).max() < 1e-6
+    # a back face: - to + ends the ray, although a front face follows it
+    grid, back = _slab([-1.0, -0.5, 0.5, 1.0, 0.5, -0.5, -1.0])
+    ray = TR.raycast(grid, back, SLAB_CAM, *IDENT, 9, 9, **SLAB_RAY)
+    assert ray["counts"][0] == 0 and (FT.bits(ray["disp"]) == 0).all()
+    grid, back = _slab([-1.0, -0.5, 0.5, 1.0, 1.0, 1.0, 1.0])
+    assert TR.raycast(grid, back, SLAB_CAM, *IDENT, 9, 9, **SLAB_RAY)["counts"][0] == 0
+    seen_from_behind = (FT.rotation((0, 1, 0), 180.0).ravel(), np.array([0.0, 0.0, 2.06]))  # the same volume from z = 2.06, looking back
+    ray = TR.raycast(grid, back, SLAB_CAM, *seen_from_behind, 9, 9, **SLAB_RAY)
+    assert ray["hit"][4, 4] and abs(40.0 / float(ray["disp"][4, 4]) - (2.06 - 1.015)) < 1e-6  # the same crossing, now a front face
+    assert np.abs(ray["normals"][4, 4] - (0, 0, -1)).max() < 1e-6  # in the camera's frame
+    # an unobserved corner invalidates every sample that reads it: the samples either side of the crossing forget f_prev
+    grid, vol = _slab([1.0, 1.0, 0.5, -0.5, -1.0, -1.0])
+    full = TR.raycast(grid, vol, SLAB_CAM, *IDENT, 9, 9, **SLAB_RAY)
+    assert full["hit"].sum() >= 9
+    holed = vol.copy()
+    holed[2, 1, 1, 1] = 0.0  # voxel (1, 1, 2): a corner of the cells b = (0..1, 0..1, 1..2)
+    ray = TR.raycast(grid, holed, SLAB_CAM, *IDENT, 9, 9, **SLAB_RAY)
+    lost = full["hit"] & ~ray["hit"]
+    assert lost.any() and (full["hit"] & ray["hit"]).any() and not (ray["hit"] & ~full["hit"]).any()
+    q = [(np.arange(9) - 4.0) / 400.0 * 1.025 / 0.01 + 1.5] * 2  # the grid x (and y) of each pixel's ray at the crossing
+    reads = lambda v: (np.floor(v) <= 1) & (np.floor(v) + 1 >= 1)
+    assert np.array_equal(lost, full["hit"] & (reads(q[1])[:, None] & reads(q[0])[None, :]))
+    keep = full["hit"] & ray["hit"]
+    assert np.array_equal(FT.bits(ray["disp"][keep]), FT.bits(full["disp"][keep]))
+    # min_weight: a voxel takes part iff weight > 0 and weight >= min_weight
+    light = vol.copy()
+    light[..., 1] = 1.0
+    assert TR.raycast(grid, light, SLAB_CAM, *IDENT, 9, 9, **dict(SLAB_RAY, min_weight=2.0))["counts"][0] == 0
+    assert TR.raycast(grid, light, SLAB_CAM, *IDENT, 9, 9, **dict(SLAB_RAY, min_weight=1.0))["counts"][0] == full["counts"][0]
+    # a normal needs its six samples: in a volume two voxels thick along x none of them fits
+    grid, thin = _slab([1.0, 1.0, 0.5, -0.5, -1.0, -1.0], grid_n=(2, 4, None))
+    ray = TR.raycast(grid, thin, SLAB_CAM, *IDENT, 9, 9, **SLAB_RAY)
+    assert ray["hit"].any() and (ray["normals"] == 0).all()
+
+
+# ---- 2. fusion: on the definition alone -----------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def fused_model():
+    """Six poses on a 5-degree arc about the scene, each map with U(-0.3, 0.3) px of noise, integrated in turn."""
+    rng = np.random.default_rng(3)
+    vol, maps = TR.clear(GRID), []
+    for pose in ARC[:6]:
+        d = render(pose)
+        d = (d + rng.uniform(-0.3, 0.3, d.shape).astype(np.float32)).astype(np.float32)
+        maps.append(d)
+        vol = TR.integrate(GRID, vol, d, CAM, *pose)["voxels"]
+    truth = render(ARC[6])
+    noisy = (truth + rng.uniform(-0.3, 0.3, truth.shape).astype(np.float32)).astype(np.float32)
+    return vol, tuple(maps), truth, noisy, TR.raycast(GRID, vol, CAM, *ARC[6], ROWS, COLS, **RAY)
+
+
+def test_conditions_the_fused_model_beats_a_single_noisy_map():
+    """Six noisy maps along the arc, raycast at a seventh pose (off the arc: pitched by one degree).  On the pixels valid in
+    both, the RMS error of the raycast map against the noiseless truth is SMALLER than that of one noisy map rendered at that
+    pose, and at least half of the truth's valid pixels are hit.  Reached: RMS 0.054 px against 0.175 px, 3455 of 3840 pixels
+    hit."""
+    _, _, truth, noisy, ray = fused_model()
+    both = ray["hit"] & (truth > 0)
+    rms = lambda a: float(np.sqrt(np.mean((a[both].astype(np.float64) - truth[both].astype(np.float64)) ** 2)))
+    print("hit %d of %d, RMS raycast %.4f, one noisy map %.4f" % (ray["hit"].sum(), (truth > 0).sum(), rms(ray["disp"]), rms(noisy)))
+    assert rms(ray["disp"]) < rms(noisy)
+    assert ray["hit"].sum() >= 0.5 * (truth > 0).sum()
+
+
+def test_a_raycast_map_is_an_ordinary_left_map_for_the_cloud_and_the_mesh():
+    _, _, _, _, ray = fused_model()
+    cloud = pointcloud_ref.point_cloud(ray["disp"], CAM, 0.0, 0.0, 1, None, ray["normals"], None)
+    assert cloud["count"] == ray["counts"][0] > 0
+    mesh = mesh_ref.grid_mesh(ray["disp"], CAM, max_diff=1.0)
+    assert mesh["vertex_count"] == ray["counts"][0] and mesh["tri_count"] > ray["counts"][0]  # a surface, not a dust of points
+
+
+# ---- the cases the kernels are held to ------------------------------------------------------------------------------------------
+VOLUMES = {"1x1x1": (1, 1, 1), "1x7x3": (1, 7, 3), "70x9x5": (70, 9, 5), "37x21x13": (37, 21, 13)}
+MAPS = {"1x1": (1, 1), "1x7": (1, 7), "37x53": (37, 53), "64x96": (64, 96), "9x300": (9, 300)}
+FACES = ("from -z", "from +z", "from -x", "from +x", "from -y", "from +y")  # the box face through which the rays enter
+SEEING = ("identity", "yaw", "roll", "inside") + FACES
+POSES = SEEING + ("behind", "beside")
+CASE_VOXEL, CASE_TRUNC = 0.02, 0.07
+
+
+def case_grid(volume, max_weight=64.0):
+    """The volume with its centre on the world's z axis, one metre and half its depth away from the world's origin."""
+    nx, ny, nz = VOLUMES[volume]
+    ext = (np.array([nx, ny, nz]) - 1) * CASE_VOXEL
+    return TR.make_grid(nx, ny, nz, (-ext[0] / 2, -ext[1] / 2, 1.0), CASE_VOXEL, CASE_TRUNC, max_weight)
+
+
+def case_pose(grid, name):
+    """-> (pose, the distance of the camera from the volume's centre)."""
+    ext = (np.array([grid["nx"], grid["ny"], grid["nz"]]) - 1) * grid["voxel"]
+    centre = np.array(grid["origin"]) + ext / 2
+    dist = float(centre[2])
+    if name == "identity" or name == "from -z":
+        return IDENT if name == "identity" else (I3, np.array([0.003, -0.002, 0.0])), dist
+    turn = {"yaw": ((0, 1, 0), 12.0), "roll": ((0, 0, 1), 30.0), "inside": ((0, 1, 0), 80.0), "from +z": ((0, 1, 0), 180.0),
+            "from -x": ((0, 1, 0), 90.0), "from +x": ((0, 1, 0), -90.0), "from -y": ((1, 0, 0), -90.0), "from +y": ((1, 0, 0), 90.0),
+            "behind": ((0, 1, 0), 0.0), "beside": ((0, 1, 0), 0.0)}[name]
+    Rwc = FT.rotation(*turn)  # camera to world
+    back = {"inside": 0.0, "behind": -dist}.get(name, dist)
+    c = centre + Rwc @ np.array([0.0, 0.0, -back]) + (np.array([50.0, 0.0, 0.0]) if name == "beside" else 0.0)
+    R = Rwc.T
+    return (R.ravel(), -(R @ c)), dist if name != "inside" else 0.2
+
+
+def case_camera(shape, integer_centre):
+    rows, cols = MAPS[shape]
+    fx, fy = 0.9 * max(cols, 8), 1.17 * max(rows, 8)  # each axis of the map spans the volume, however thin the map
+    return (fx, fy, float(cols // 2), float(rows // 2), 0.12) if integer_centre else (fx, fy, cols / 2 - 0.3, rows / 2 + 0.4, 0.12)
+
+
+def case_map(shape, camera, dist, seed, specials=True):
+    """A surface `dist` in front of the camera with a relief of +-3 %, 5 % of its pixels without a value, special values in
+    its first pixels."""
+    rows, cols = MAPS[shape]
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[:rows, :cols]
+    depth = dist * (1.0 + 0.03 * np.sin(0.37 * x + 0.2) * np.cos(0.29 * y))
+    d = (camera[0] * camera[4] / depth).astype(np.float32)
+    d[rng.random((rows, cols)) < 0.05] = 0.0
+    if specials and d.size > 2 * FT.SPECIALS.size:
+        d.ravel()[:FT.SPECIALS.size] = FT.SPECIALS
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def tsdf_case(volume, shape, names, ray_name=None, weighted=False, step=0.5, min_weight=0.0, max_weight=64.0, min_disp=0.0,
+              max_range=0.0):
+    """One integrate per named pose into the cleared volume, then a raycast at ray_name (default: the first pose) ->
+    (the arguments of FT.check_tsdf as a dict, the definition's results)."""
+    rows, cols = MAPS[shape]
+    grid = case_grid(volume, max_weight)
+    camera = case_camera(shape, "identity" in names)
+    steps = []
+    for k, name in enumerate(names):
+        pose, dist = case_pose(grid, name)
+        w = FT.random_weight(np.random.default_rng(100 + k), rows, cols) if weighted else None
+        steps.append((case_map(shape, camera, dist, seed=rows + cols + k), pose, w))
+    ray_pose, dist = case_pose(grid, ray_name or names[0])
+    far = dist + 1.5 * CASE_VOXEL * max(VOLUMES[volume])
+    ray = dict(min_range=0.05, max_range=far, step=step, min_weight=min_weight)
+    args = dict(grid=grid, start=None, steps=steps, camera=camera, ray_pose=ray_pose, rows=rows, cols=cols, ray=ray,
+                min_disp=min_disp, max_range=max_range)
+    return args, FT.reference(grid, TR.clear(grid), steps, camera, ray_pose, rows, cols, ray, min_disp, max_range)
+
+
+def test_conditions_the_cases_see_update_and_hit():
+    """Every pose that looks at the 37x21x13 volume updates voxels and, raycast from where it integrated, hits; the two that
+    do not look at it see nothing; the 70x9x5 volume is hit through a map wider than a wavefront; the volumes one voxel thick
+    are updated and can never be hit."""
+    for name in POSES:
+        _, want = tsdf_case("37x21x13", "37x53", (name,))
+        print(name, want["counts"][0], want["ray"]["counts"], want["ray"]["samples"])
+        if name in SEEING:
+            assert want["counts"][0][1] > 100 and want["ray"]["counts"][0] > 30, name
+            assert (np.abs(want["ray"]["normals"]).sum(-1) > 0).sum() > 10, name
+        else:
+            assert tuple(want["counts"][0]) == (0, 0) and want["ray"]["counts"][0] == 0, name
+    _, want = tsdf_case("70x9x5", "9x300", ("identity",))
+    assert want["counts"][0][1] > 500 and want["ray"]["counts"][0] > 100
+    hit_cols = np.flatnonzero(want["ray"]["hit"].any(0))
+    assert hit_cols.min() < 128 and hit_cols.max() >= 192  # across wavefronts of the raycast
+    args = tsdf_case("70x9x5", "9x300", ("identity",))[0]
+    up = TR.integrate(args["grid"], TR.clear(args["grid"]), args["steps"][0][0], args["camera"], *IDENT)["updated"]
+    assert up[..., :64].any() and up[..., 64:].any()  # both spans of a row of the grid, the tail included
+    for volume in ("1x1x1", "1x7x3"):
+        _, want = tsdf_case(volume, "37x53", ("identity",))
+        assert want["counts"][0][1] >= 1 and want["ray"]["counts"][0] == 0
+    # a pixel on the axis: two components of its ray are exactly zero in the camera frame and, under the identity, in the world's
+    cam = case_camera("37x53", True)
+    assert (26.0 - cam[2]) / cam[0] == 0.0 and (18.0 - cam[3]) / cam[1] == 0.0
+    assert tsdf_case("37x21x13", "37x53", ("identity",))[1]["ray"]["hit"][18, 26]
+
+
+# ---- 3. the kernels' own per-thread code, run on the host ---------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def host_tsdf_exe(tmp_path_factory):
+    """tests/cpp/tsdf_host_main.cpp: csrc/pm_tsdf_body.hpp compiled for the host alone, with the sanitizers."""
+    return build_host_kernel(tmp_path_factory.mktemp("tsdfhost") / "tsdf_host_main", "tsdf_host_main.cpp")
+
+
+def _dump_case(path, args, want, start=None):
+    os.makedirs(path)
+    grid, steps, ray = args["grid"], args["steps"], args["ray"]
+    save = lambda name, a: np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    poses = np.zeros(12 * 4)
+    for k, (_, pose, _) in enumerate(steps):
+        poses[12 * k:12 * k + 12] = [*np.asarray(pose[0]).ravel(), *np.asarray(pose[1]).ravel()]
+    weighted = steps[0][2] is not None
+    save("params", np.array([grid["nx"], grid["ny"], grid["nz"], *grid["origin"], grid["voxel"], grid["trunc"], grid["max_weight"],
+                             *args["camera"], args["rows"], args["cols"], len(steps), args["min_disp"], args["max_range"], weighted,
+                             ray["min_range"], ray["max_range"], ray["step"], ray["min_weight"],
+                             *np.asarray(args["ray_pose"][0]).ravel(), *np.asarray(args["ray_pose"][1]).ravel(), *poses], np.float64))
+    save("start", TR.clear(grid) if start is None else start)
+    save("disp", np.stack([s[0] for s in steps]).astype(np.float32))
+    save("weights", np.stack([s[2] if weighted else np.full(s[0].shape, 7.0, np.float32) for s in steps]).astype(np.float32))
+    save("want_voxels", np.stack(want["volumes"]))
+    save("want_counts", np.stack(want["counts"]).astype(np.int32))
+    save("want_disp", want["ray"]["disp"])
+    save("want_normals", want["ray"]["normals"])
+    save("want_hits", want["ray"]["counts"])
+
+
+def test_kernel_code_on_the_host_equals_the_definition(host_tsdf_exe, tmp_path):
+    """Every thread of both launches over whole volumes and maps on the CPU, forwards and backwards, the raycast with each
+    output alone and with the count alone: the volume's bytes behind every integrate, the map, the normals and the counts equal
+    the .npy dumps of the definition byte for byte, and AddressSanitizer / UBSan see every access into buffers of exactly the
+    size the stage may touch.  Four volumes x five maps, the poses in turn, one to three integrates, weights given and null,
+    step 0.25 / 0.5 / 1, min_weight 0 / 2, a saturating max_weight, min_disp and max_range, and a volume with a history."""
+    totals, k = np.zeros(3, np.int64), 0
+    for volume in VOLUMES:
+        for shape in MAPS:
+            names = tuple(POSES[(k + j) % len(POSES)] for j in range(1 + k % 3))
+            args, want = tsdf_case(volume, shape, names, ray_name=names[-1] if names[-1] in SEEING else SEEING[k % len(SEEING)], weighted=k % 2 == 1, step=(0.25, 0.5, 1.0)[k % 3],
+                                   min_weight=(0.0, 2.0)[k % 4 == 3], max_weight=(64.0, 1.5)[k % 5 == 4], min_disp=(0.0, 0.25)[k % 7 == 6],
+                                   max_range=(0.0, 1.12)[k % 6 == 5])
+            d = str(tmp_path / ("case%d" % k))
+            _dump_case(d, args, want)
+            r = subprocess.run([host_tsdf_exe, d], capture_output=True, text=True)
+            assert r.returncode == 0, (volume, shape, names, r.stderr[-3000:])
+            totals += (*np.sum(want["counts"], axis=0), want["ray"]["counts"][0])
+            k += 1
+    # a volume with a history: random values and weights, NaN payloads in records that stay untouched
+    args, _ = tsdf_case("37x21x13", "37x53", ("yaw", "roll"), ray_name="identity", weighted=True)
+    rng = np.random.default_rng(8)
+    start = rng.uniform(-1, 1, (13, 21, 37, 2)).astype(np.float32)
+    start[..., 1] = rng.choice([0.0, 1.0, 2.0, 3.5], (13, 21, 37))
+    want = FT.reference(args["grid"], start, args["steps"], args["camera"], args["ray_pose"], 37, 53, args["ray"])
+    d = str(tmp_path / "history")
+    _dump_case(d, args, want, start)
+    r = subprocess.run([host_tsdf_exe, d], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    print("in view, updated, hit:", totals, want["ray"]["counts"])
+    assert totals[1] > 20000 and totals[2] > 500 and want["ray"]["counts"][0] > 100
+    # the program does compare: one flipped bit in an expectation is a mismatch, not a pass
+    for name, dtype, word in (("voxels", np.uint32, "the volume behind integrate 1"), ("counts", np.int32, "counts"),
+                              ("disp", np.uint32, "disp"), ("normals", np.uint32, "normals"), ("hits", np.int32, "hits")):
+        path = os.path.join(d, "want_%s.npy" % name)
+        keep = np.load(path)
+        flipped = keep.copy()
+        flipped.view(dtype).ravel()[-1] ^= 1
+        np.save(path, flipped)
+        r = subprocess.run([host_tsdf_exe, d], capture_output=True, text=True)
+        assert r.returncode == 1 and word + " differs" in r.stderr, (name, r.returncode, r.stderr[-500:])
+        np.save(path, keep)
+    assert subprocess.run([host_tsdf_exe, d], capture_output=True, text=True).returncode == 0
+
+
+def test_headers_declare_and_the_library_exports_the_tsdf_functions(pm):
+    text = open(os.path.join(ROOT, "include", "pm", "imaging.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    lib = pm.load()
+    assert re.search(r"\bsize_t\s+pm_tsdf_bytes\s*\(\s*const\s+pm_tsdf_volume\s*\*", text)
+    for name in ("pm_tsdf_clear", "pm_tsdf_integrate", "pm_tsdf_raycast"):
+        assert re.search(r"\bint\s+%s\s*\(\s*pm_handle\s*\*" % name, text), name
+    for name in ("pm_tsdf_bytes", "pm_tsdf_clear", "pm_tsdf_integrate", "pm_tsdf_raycast", "pm_debug_tsdf_constants"):
+        assert name in pm.EXPORTS and hasattr(lib, name), name
+    for name in ("pm_tsdf_volume", "pm_tsdf_integrate_options", "pm_tsdf_raycast_options"):
+        assert "typedef struct " + name in text, name
+    assert text.index("pm_fuse_disparity") < text.index("pm_tsdf_integrate") < text.index("pm_device_malloc")
+    assert "#define PM_ABI_VERSION 6" in open(os.path.join(ROOT, "include", "pm", "patchmatch.h")).read() and pm.PM_ABI_VERSION == 6
+    assert (C.sizeof(pm.PmTsdfVolume), C.sizeof(pm.PmTsdfIntegrateOptions), C.sizeof(pm.PmTsdfRaycastOptions)) == (64, 8, 16)
+    assert pm.tsdf_constants() == (64, 4)
+    # pm_tsdf_bytes needs no handle and no device: 8 bytes per voxel, 0 for what the stages refuse
+    assert pm.tsdf_bytes(GRID) == 8 * 52 * 34 * 40 and pm.tsdf_bytes(case_grid("1x1x1")) == 8
+    assert lib.pm_tsdf_bytes(None) == 0
+    for bad in (dict(nx=0), dict(ny=-1), dict(nz=0), dict(voxel=0.0), dict(voxel=float("nan")), dict(trunc=-1.0), dict(trunc=float("inf")),
+                dict(max_weight=0.0), dict(max_weight=float("nan")), dict(origin=(0.0, float("inf"), 0.0)), dict(nx=2048, ny=2048, nz=512)):
+        assert pm.tsdf_bytes(dict(GRID, **bad)) == 0, bad
+    assert pm.tsdf_bytes(dict(GRID, nx=2047, ny=2048, nz=512)) == 8 * 2047 * 2048 * 512
+    csrc = os.path.join(ROOT, "ocean-perception_amd", "csrc")
+    assert '#include "pm_tsdf.hpp"' in open(os.path.join(csrc, "pm_stages.hip")).read()  # the kernels live in that unit alone
+    assert "pm_tsdf.hpp" in open(os.path.join(csrc, "pm_handle.hpp")).read()
+    for f in os.listdir(csrc):
+        if f.endswith(".hip") and f != "pm_stages.hip":
+            assert "pm_tsdf" not in open(os.path.join(csrc, f)).read(), f
+
+
+# ---- 4. device parity ----------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def engine(pm):
+    with pm.Engine(pm.default_params(0, patch=5), max_rows=64, max_cols=96) as e:
+        yield e
+
+
+def _check(torch, engine, volume, shape, names, outputs=FT.RAY_OUTPUTS, integrate_counts=("d_counts", "counts"), offset_floats=0, **kw):
+    args, want = tsdf_case(volume, shape, tuple(names), **kw)
+    return FT.check_tsdf(torch, engine, want=want, outputs=outputs, integrate_counts=integrate_counts, offset_floats=offset_floats, **args)
+
+
+@gpu
+@pytest.mark.parametrize("shape", list(MAPS))
+@pytest.mark.parametrize("volume", list(VOLUMES))
+def test_tsdf_equals_the_definition(pm, engine, volume, shape):
+    """Four volumes (one voxel; thinner than a sample's cell; a row of the grid that crosses the 64-voxel span and leaves a tail
+    of 6; several spans, rows and slices, none a multiple of the block) x five maps (one pixel; a row shorter than a wavefront;
+    rows that are no multiple of the block's 4; whole wavefronts; a row of five wavefronts with a ragged tail): pm_tsdf_clear
+    over a patterned buffer, the volume's bytes behind each integrate, the raycast's map, normals, d_counts and host counts at
+    tolerance 0.  The identity pose with an integer principal point (the central ray has two exact-zero components), then a
+    yawed and a rolled view with weights."""
+    import torch
+    _check(torch, engine, volume, shape, ("identity",))
+    _check(torch, engine, volume, shape, ("yaw", "roll"), ray_name="roll", weighted=True, step=0.25)
+
+
+@gpu
+@pytest.mark.parametrize("pose", POSES)
+def test_every_pose(pm, engine, pose):
+    """The camera in front of the volume, yawed, rolled, inside it, behind it, beside it, and outside each of the box's six
+    faces, so that rays enter through every face: integrated from there, raycast from there."""
+    import torch
+    want = _check(torch, engine, "37x21x13", "37x53", (pose,))
+    assert (want["ray"]["counts"][0] > 0) == (pose in SEEING)
+    _check(torch, engine, "70x9x5", "64x96", (pose,), weighted=True, step=1.0)
+
+
+@gpu
+@pytest.mark.parametrize("step", [0.25, 1.0])
+@pytest.mark.parametrize("min_weight", [0.0, 2.0])
+@pytest.mark.parametrize("weighted", [False, True])
+def test_options(pm, engine, weighted, min_weight, step):
+    """With and without d_weight, min_weight 0 and 2 (two integrates from one pose raise the weights to 2 where the weights
+    allow), step 0.25 and 1."""
+    import torch
+    want = _check(torch, engine, "37x21x13", "64x96", ("yaw", "yaw"), weighted=weighted, min_weight=min_weight, step=step)
+    assert want["ray"]["counts"][0] > 0
+    if min_weight == 2.0:
+        assert want["ray"]["counts"][0] <= tsdf_case("37x21x13", "64x96", ("yaw", "yaw"), weighted=weighted, step=step)[1]["ray"]["counts"][0]
+
+
+@gpu
+def test_each_output_alone_unaligned_and_the_other_options(pm, engine):
+    """Each optional output of the raycast absent in turn and each alone; the integrate with either count, both and neither;
+    maps 4, 8 and 12 bytes past a 16-byte boundary; min_disp, max_range and a max_weight that saturates."""
+    import torch
+    four = FT.RAY_OUTPUTS
+    for outputs in [tuple(k for k in four if k != drop) for drop in four] + [(k,) for k in four]:
+        _check(torch, engine, "37x21x13", "37x53", ("roll",), outputs=outputs, weighted=True)
+    for counts in ((), ("d_counts",), ("counts",)):
+        _check(torch, engine, "37x21x13", "37x53", ("roll",), integrate_counts=counts, weighted=True)
+    for off in (1, 2, 3):
+        _check(torch, engine, "70x9x5", "9x300", ("identity",), offset_floats=off, weighted=True)
+    want = _check(torch, engine, "37x21x13", "37x53", ("identity", "identity", "identity"), max_weight=1.5, weighted=True)
+    assert want["volumes"][-1][..., 1].max() == 1.5
+    plain = tsdf_case("37x21x13", "37x53", ("identity",))[1]["counts"][0][1]
+    assert 0 < _check(torch, engine, "37x21x13", "37x53", ("identity",), min_disp=5.1)["counts"][0][1] < plain
+    assert 0 < _check(torch, engine, "37x21x13", "37x53", ("identity",), max_range=1.12)["counts"][0][1] < plain
+
+
+@gpu
+def test_three_integrates_in_sequence_then_a_raycast(pm, engine):
+    """Three views into one volume, the volume's bytes compared behind each, then both raycast outputs and the counts -- from a
+    pose none of them had -- and the same into a volume with a history."""
+    import torch
+    want = _check(torch, engine, "37x21x13", "64x96", ("identity", "yaw", "from -x"), ray_name="roll", weighted=True)
+    assert want["ray"]["counts"][0] > 100 and all(c[1] > 1000 for c in want["counts"])
+    assert not np.array_equal(want["volumes"][0], want["volumes"][1]) and not np.array_equal(want["volumes"][1], want["volumes"][2])
+    args, _ = tsdf_case("37x21x13", "64x96", ("identity", "yaw", "from -x"), ray_name="roll", weighted=True)
+    rng = np.random.default_rng(8)
+    start = rng.uniform(-1, 1, (13, 21, 37, 2)).astype(np.float32)
+    start[..., 1] = rng.choice([0.0, 1.0, 2.0, 3.5], (13, 21, 37))
+    FT.check_tsdf(torch, engine, **dict(args, start=start))
+
+
+@gpu
+@pytest.mark.parametrize("mode", ["scalar", "planes"])
+def test_integrate_directly_behind_a_match_on_the_handles_stream(pm, synth, mode):
+    """A Match() of a synthetic pair into a device buffer, then clear, integrate and raycast on the handle's stream with nothing
+    copied and nothing synchronised in between: the volume and the map equal the definition on the downloaded disparity map (a two-iteration match is rough: 9408 pixels with
+    a value, 15697 voxels updated, 53 pixels hit in scalar mode)."""
+    import torch
+    rows, cols = 96, 128
+    cam = (100.0, 100.0, 64.0, 48.0, 0.02)  # the pair's disparities of 1 .. 21 are ranges of 2 .. 0.1
+    kw = dict(mode=pm.PM_MODE_PLANES) if mode == "planes" else {}
+    p = synth.make_pair(5, rows=rows, cols=cols, n_points=40, dilate_factor=2)
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+    L, R, SL, SR = (up(p[k]) for k in ("left", "right", "seed_l", "seed_r"))
+    D = torch.zeros((2, rows, cols), dtype=torch.float32, device="cuda")
+    grid = TR.make_grid(40, 32, 40, (-0.5, -0.4, 0.05), 0.025, 0.1, 8.0)  # (the true map: 18489 voxels updated, 1579 pixels hit)
+    vol = FT.Guarded(torch, 8 * 40 * 32 * 40)
+    vol.t[vol.lo:vol.lo + vol.n] = 0x5A
+    out = FT.Guarded(torch, 4 * rows * cols)
+    ray = dict(min_range=0.05, max_range=1.1, step=0.5, min_weight=0.0)
+    torch.cuda.synchronize()
+    with pm.Engine(pm.default_params(0, patch=5, patchmatch_iters=2, max_disp=32, **kw), max_rows=rows, max_cols=cols) as e:
+        e.match_device(1, L.data_ptr(), R.data_ptr(), rows, cols, SL.data_ptr(), SR.data_ptr(), D[0].data_ptr(), D[1].data_ptr())
+        e.tsdf_clear(grid, vol.ptr)
+        e.tsdf_integrate(cam, grid, IDENT, D[0].data_ptr(), rows, cols, vol.ptr)
+        n = e.tsdf_raycast(cam, grid, IDENT, vol.ptr, rows, cols, d_disp_out=out.ptr, want_counts=True, **ray)
+        e.synchronize()
+    disp = D[0].cpu().numpy()
+    want = TR.integrate(grid, TR.clear(grid), disp, cam, *IDENT)
+    want_ray = TR.raycast(grid, want["voxels"], cam, *IDENT, rows, cols, **ray)
+    print(mode, "valid pixels", (disp > 0).sum(), "in view, updated", want["counts"], "hit", want_ray["counts"])
+    assert (disp > 0).sum() > 0.25 * rows * cols and want["counts"][1] > 1000 and want_ray["counts"][0] > 20
+    assert np.array_equal(vol.read(np.uint32), FT.bits(want["voxels"]).ravel())
+    assert n == want_ray["counts"][0] and np.array_equal(FT.bits(out.read(np.float32)), FT.bits(want_ray["disp"]).ravel())
+
+
+@gpu
+def test_invalid_arguments_are_named_and_nothing_is_enqueued(pm, engine):
+    """PM_ERR_INVALID_ARG / PM_ERR_SIZE with pm_last_error naming the argument; the volume, the outputs and the counts keep
+    their guard patterns and their payloads."""
+    import torch
+    rows, cols = 16, 24
+    lib, h = engine.lib, engine.h
+    grid = TR.make_grid(8, 6, 5, (-0.07, -0.05, 0.9), 0.02, 0.06, 64.0)
+    cam = (40.0, 40.0, 12.0, 8.0, 0.1)
+    disp = torch.full((rows, cols), 4.25, dtype=torch.float32, device="cuda")  # a surface at range 0.94, inside the volume
+    bufs = {k: FT.Guarded(torch, n) for k, n in (("vol", 8 * 240), ("out", 4 * rows * cols), ("nrm", 12 * rows * cols), ("c", 8))}
+    host = (C.c_int * 2)(-5, -5)
+    UNSET = object()
+    pick = lambda v, default: default if v is UNSET else v
+
+    def volume(**kw):
+        return pm.tsdf_volume(dict(grid, **kw))
+
+    def integrate(camera=cam, vol=UNSET, pose=IDENT, opt=(0.0, 0.0), d=UNSET, shape=(rows, cols), vox=UNSET):
+        v = pick(vol, volume())
+        o = pm.PmTsdfIntegrateOptions(*opt) if opt is not None else None
+        return lib.pm_tsdf_integrate(h, pm._ref(pm.cloud_camera(camera)), pm._ref(v), pm._ref(pm.as_motion(pose)), pm._ref(o),
+                                     pick(d, disp.data_ptr()), None, shape[0], shape[1], pick(vox, bufs["vol"].ptr), bufs["c"].ptr, host)
+
+    def raycast(camera=cam, vol=UNSET, pose=IDENT, opt=(0.5, 1.5, 0.5, 0.0), vox=UNSET, shape=(rows, cols), out=UNSET, nrm=UNSET,
+                c=UNSET, hc=host):
+        v = pick(vol, volume())
+        o = pm.PmTsdfRaycastOptions(*opt) if opt is not None else None
+        return lib.pm_tsdf_raycast(h, pm._ref(pm.cloud_camera(camera)), pm._ref(v), pm._ref(pm.as_motion(pose)), pm._ref(o),
+                                   pick(vox, bufs["vol"].ptr), shape[0], shape[1], pick(out, bufs["out"].ptr),
+                                   pick(nrm, bufs["nrm"].ptr), pick(c, bufs["c"].ptr), hc)
+
+    def refused(rc, word, who, status=pm.PM_ERR_INVALID_ARG):
+        text = lib.pm_last_error(h).decode()
+        assert rc == status and word in text and who in text, (rc, word, text)
+
+    nan, inf = float("nan"), float("inf")
+    for call, who in ((integrate, "pm_tsdf_integrate"), (raycast, "pm_tsdf_raycast")):
+        refused(call(camera=None), "camera", who)
+        refused(call(vol=None), "volume", who)
+        refused(call(pose=None), "pose", who)
+        refused(call(opt=None), "options", who)
+        refused(call(vox=None), "d_voxels", who)
+        for i, name in enumerate(("fx", "fy", "cx", "cy", "baseline")):
+            for bad in (nan, inf, -inf):
+                refused(call(camera=cam[:i] + (bad,) + cam[i + 1:]), name, who)
+        refused(call(camera=(0.0,) + cam[1:]), "fx", who)
+        refused(call(camera=(cam[0], 0.0) + cam[2:]), "fy", who)
+        for i in range(12):
+            for bad in (nan, inf, -inf):
+                R, t = np.eye(3).ravel(), np.zeros(3)
+                (R if i < 9 else t)[i if i < 9 else i - 9] = bad
+                refused(call(pose=(R, t)), ("R[%d]" % i if i < 9 else "t[%d]" % (i - 9)) + " of the pose", who)
+        for key in ("nx", "ny", "nz"):
+            for bad in (0, -3):
+                refused(call(vol=volume(**{key: bad})), "nx, ny and nz", who)
+        for key in ("voxel", "trunc", "max_weight"):
+            for bad in (nan, inf, 0.0, -0.5):
+                refused(call(vol=volume(**{key: bad})), key, who)
+        refused(call(vol=volume(origin=(0.0, nan, 0.0))), "origin", who)
+        for shape in ((0, cols), (rows, 0), (rows, -3)):
+            refused(call(shape=shape), "empty", who)
+        refused(call(shape=(70000, 40000)), "exceed", who, pm.PM_ERR_SIZE)
+        refused(call(vol=volume(nx=2048, ny=2048, nz=512)), "exceed 2^31 - 1", who, pm.PM_ERR_SIZE)
+        refused(call(vol=volume(nx=65536, ny=65536, nz=65536)), "exceed 2^31 - 1", who, pm.PM_ERR_SIZE)
+    refused(integrate(d=None), "d_disp", "pm_tsdf_integrate")
+    for bad in (nan, -1.0):
+        refused(integrate(opt=(bad, 0.0)), "min_disp", "pm_tsdf_integrate")
+        refused(integrate(opt=(0.0, bad)), "max_range", "pm_tsdf_integrate")
+    for bad in (nan, 0.0, -0.5, 1.5, inf):
+        refused(raycast(opt=(0.5, 1.5, bad, 0.0)), "step", "pm_tsdf_raycast")
+    for lo, hi in ((nan, 1.5), (0.5, nan), (inf, 1.5), (0.5, inf), (0.0, 1.5), (-1.0, 1.5), (1.5, 1.5), (1.5, 0.5)):
+        refused(raycast(opt=(lo, hi, 0.5, 0.0)), "min_range", "pm_tsdf_raycast")
+    for bad in (nan, -1.0):
+        refused(raycast(opt=(0.5, 1.5, 0.5, bad)), "min_weight", "pm_tsdf_raycast")
+    refused(raycast(out=None, nrm=None, c=None, hc=None), "no output", "pm_tsdf_raycast")
+    refused(raycast(vol=volume(trunc=1e-9), opt=(0.5, 1.5, 0.25, 0.0)), "samples", "pm_tsdf_raycast", pm.PM_ERR_SIZE)
+    for bad in (dict(nx=0), dict(voxel=nan)):
+        assert lib.pm_tsdf_clear(h, pm._ref(volume(**bad)), bufs["vol"].ptr) == pm.PM_ERR_INVALID_ARG
+        assert "pm_tsdf_clear" in lib.pm_last_error(h).decode()
+    assert lib.pm_tsdf_clear(h, None, bufs["vol"].ptr) == pm.PM_ERR_INVALID_ARG and "volume" in lib.pm_last_error(h).decode()
+    assert lib.pm_tsdf_clear(h, pm._ref(volume()), None) == pm.PM_ERR_INVALID_ARG and "d_voxels" in lib.pm_last_error(h).decode()
+    assert lib.pm_tsdf_clear(h, pm._ref(volume(nx=2048, ny=2048, nz=512)), bufs["vol"].ptr) == pm.PM_ERR_SIZE
+    engine.synchronize()
+    for buf in bufs.values():
+        buf.read(np.uint8, 0)  # the guards and every payload byte still hold the fill
+    assert tuple(host) == (-5, -5) and (disp.cpu().numpy() == 4.25).all()
+    # and the same arguments made good do run
+    assert lib.pm_tsdf_clear(h, pm._ref(volume()), bufs["vol"].ptr) == pm.PM_OK
+    assert integrate() == pm.PM_OK and tuple(host) == (240, 240)
+    assert raycast() == pm.PM_OK and 0 < host[0] <= rows * cols and host[1] == 240
+
+
+@gpu
+def test_tsdf_scratch_is_owned_by_the_handle(pm):
+    """The counts of a call are ONE handle-owned allocation of 16 bytes through csrc/pm_devbuf.hpp, made on first use by either
+    stage, shared by both, gone with the handle; the volume is the caller's."""
+    import torch
+    lib = pm.load()
+    live = lambda: (lib.pm_debug_live_device_allocations(), lib.pm_debug_live_device_bytes())
+    before = live()
+    grid = case_grid("37x21x13")
+    cam = case_camera("37x53", True)
+    vol = torch.zeros(2 * 10101, dtype=torch.float32, device="cuda")
+    d = torch.full((37, 53), float(cam[0] * cam[4] / 1.12), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    with pm.Engine(pm.default_params(0, patch=5), max_rows=64, max_cols=96) as e:
+        base = live()
+        e.tsdf_clear(grid, vol.data_ptr())
+        assert live() == base
+        n = e.tsdf_integrate(cam, grid, IDENT, d.data_ptr(), 37, 53, vol.data_ptr(), want_counts=True)
+        assert n[0] == 10101 and 0 < n[1] < n[0] and live() == (base[0] + 1, base[1] + 16)
+        assert e.tsdf_raycast(cam, grid, IDENT, vol.data_ptr(), 37, 53, 0.05, 2.0, want_counts=True) > 0
+        assert live() == (base[0] + 1, base[1] + 16)
+    assert live() == before
+
+
+@gpu
+def test_fuzz_tsdf_one_short_seeded_run():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_tsdf.py"), "--cases", "12", "--seed", "4"],
+                       capture_output=True, text=True)
+    assert r.returncode == 0 and "bit-identical" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
