@@ -35,30 +35,30 @@ struct ImagingState {
   // pm_match_raw_device: the rectified pairs, [left, right][n][rows][cols] bytes; pm_match_raw_bgr_device: the rectified
   // BGR images the caller did not ask for, [n][rows][cols][3] bytes each
   DevBuf<uint8_t> rect_buf;
-  // ---- pm_stages.hip ----
+  // ---- pm_stages.hip (kCountsHeader: the counts of a call, padded to 16 bytes) ----
   // pm_point_cloud: [0] the count, [1 ..] one word per block of kCloudBlock items: its count, then its offset
   DevBuf<int> cloud_blocks;
-  // pm_filter_speckles: [0] the removed count (kSpeckleHeader words, cleared per call), then the working labels and the
+  // pm_filter_speckles: [0] the removed count (kCountsHeader words, cleared per call), then the working labels and the
   // root sizes, one word per pixel each
   DevBuf<int> speckle_buf;
   // pm_grid_mesh: [0] the vertex count, [1] the triangle count, then one word per block of kMeshBlock items for each of
   // the two (its count, then its offset), then the organised slot map, one word per grid item
   DevBuf<int> mesh_buf;
-  // pm_reproject_disparity: kReprojectHeader words ([0], [1]: the counts), the left and the right splat map, one word per
+  // pm_reproject_disparity: kCountsHeader words ([0], [1]: the counts), the left and the right splat map, one word per
   // pixel each (the memset of a call clears up to here), then the closed left seed of a call without d_seed_l
   DevBuf<unsigned> reproject_buf;
-  // pm_filter_consistency: kConsistencyHeader words ([0] valid pixels, [1] kept pixels), cleared per call
+  // pm_filter_consistency: kCountsHeader words ([0] valid pixels, [1] kept pixels), cleared per call
   DevBuf<int> consistency_counts;
-  // pm_disparity_confidence: kConfidenceHeader words ([0] valid, [1] measured, [2] kept pixels; cleared per call), then the
+  // pm_disparity_confidence: kCountsHeader words ([0] valid, [1] measured, [2] kept pixels; cleared per call), then the
   // right image's gradient (one float per pixel), then the left image's saturated gradient (one byte per pixel)
   DevBuf<int> confidence_buf;
-  // pm_fuse_disparity: kFuseHeader words ([0] valid, [1] kept, [2] fused, [3] filled pixels), then, for a call that fills,
+  // pm_fuse_disparity: kCountsHeader words ([0] valid, [1] kept, [2] fused, [3] filled pixels), then, for a call that fills,
   // one splat map of one word per pixel for each source; the memset of a call clears all of it
   DevBuf<unsigned> fuse_buf;
-  // pm_track_features / pm_estimate_motion: kTrackHeader words ([0] the number of features), one word per cell (its feature's
+  // pm_track_features / pm_estimate_motion: kCountsHeader words ([0] the number of features), one word per cell (its feature's
   // pixel index or -1), one word per cell (the feature list) and, for pm_estimate_motion, one pm_track per cell
   DevBuf<int> track_buf;
-  // pm_tsdf_integrate / pm_tsdf_raycast: kTsdfHeader words ([0], [1]: the counts of the call), cleared per call
+  // pm_tsdf_integrate / pm_tsdf_raycast: kCountsHeader words ([0], [1]: the counts of the call), cleared per call
   DevBuf<int> tsdf_counts;
 };
 

@@ -1,8 +1,9 @@
 // pm_stages.hip -- C-ABI implementation of the stages of include/pm/imaging.h that read a finished disparity map: points,
 // plane-mode normals and the compacted cloud, the windowed plane fit, the speckle filter, the grid mesh, the temporal
-// seeds, the consistency filter, the matching confidence, the sequence fusion, the feature tracks of the motion estimate and the TSDF volume.  Like pm_imaging.hip it reaches the handle only through pm_internal.hpp, and it shares
-// that unit's one state object (pm_imaging_state.hpp).  Every entry point: its argument checks in a fixed order (the first
-// fault is the one reported), then the device, then its launches on the handle's stream.
+// seeds, the consistency filter, the matching confidence, the sequence fusion, the TSDF volume and the feature tracks of the
+// motion estimate.  Like pm_imaging.hip it reaches the handle only through pm_internal.hpp, and it shares that unit's one
+// state object (pm_imaging_state.hpp).  Every entry point: its argument checks in a fixed order (the first fault is the one
+// reported), then the device, then its launches on the handle's stream.
 #include "pm/imaging.h"
 #include "pm/testing.h"
 
@@ -10,6 +11,8 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
+#include <initializer_list>
 #include <new>
 #include <vector>
 
@@ -31,11 +34,32 @@ using namespace pm;
 // ---- what the stages share --------------------------------------------------------------------------------------------
 namespace {
 
+// The first null pointer of a list, by its name.
+struct NamedPointer {
+  const char* name;
+  const void* p;
+};
+
+int check_not_null(pm_handle* h, const char* what, std::initializer_list<NamedPointer> pointers) {
+  for (const NamedPointer& q : pointers)
+    if (!q.p) {
+      set_err(h, "%s: null %s", what, q.name);
+      return PM_ERR_INVALID_ARG;
+    }
+  return PM_OK;
+}
+
+// A call with every output null; `names` as the message lists them, `parenthesised` the form of the older stages.
+int check_any_output(pm_handle* h, const char* what, std::initializer_list<const void*> outputs, const char* names,
+                     bool parenthesised = false) {
+  for (const void* p : outputs)
+    if (p) return PM_OK;
+  set_err(h, parenthesised ? "%s: no output (%s are all null)" : "%s: no output: %s are all null", what, names);
+  return PM_ERR_INVALID_ARG;
+}
+
 int check_cloud_camera(pm_handle* h, const char* what, const pm_cloud_camera* cam) {
-  if (!cam) {
-    set_err(h, "%s: null camera", what);
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_not_null(h, what, {{"camera", cam}})) return rc;
   static const char* const names[5] = {"fx", "fy", "cx", "cy", "baseline"};
   const double* e = reinterpret_cast<const double*>(cam);
   static_assert(sizeof(pm_cloud_camera) == 5 * sizeof(double), "pm_cloud_camera is 5 doubles");
@@ -85,6 +109,80 @@ int check_max_diff(pm_handle* h, const char* what, float max_diff) {
   return PM_OK;
 }
 
+// the seeds and the tracks
+int check_disp_limits(pm_handle* h, const char* what, float min_disp, float max_disp) {
+  if (!(min_disp >= 0.f) || !(max_disp >= 0.f)) {
+    set_err(h, "%s: %s must be >= 0 and not NaN%s", what, !(min_disp >= 0.f) ? "min_disp" : "max_disp",
+            !(min_disp >= 0.f) ? "" : " (0 = no limit)");
+    return PM_ERR_INVALID_ARG;
+  }
+  return PM_OK;
+}
+
+// `whose`: the motion as the message names it ("the motion", "motions[1]", "the pose", "the guess")
+int check_motion(pm_handle* h, const char* what, const pm_motion& m, const char* whose) {
+  for (int i = 0; i < 12; ++i)
+    if (!std::isfinite(i < 9 ? m.R[i] : m.t[i - 9])) {
+      set_err(h, "%s: %s[%d] of %s is not finite", what, i < 9 ? "R" : "t", i < 9 ? i : i - 9, whose);
+      return PM_ERR_INVALID_ARG;
+    }
+  return PM_OK;
+}
+
+// the consistency filter and the fusion: the earlier maps of the sequence with their motions ...
+static_assert(kFuseMaxSources == kConsistencyMaxSources && kFuseMaxRadius == kConsistencyMaxRadius, "one set of limits");
+
+int check_sources(pm_handle* h, const char* what, int n_sources, const float* const* d_sources, const pm_motion* motions) {
+  if (n_sources < 1 || n_sources > kConsistencyMaxSources) {
+    set_err(h, "%s: n_sources %d outside 1..%d", what, n_sources, kConsistencyMaxSources);
+    return PM_ERR_INVALID_ARG;
+  }
+  for (int k = 0; k < n_sources; ++k) {
+    if (!d_sources[k]) {
+      set_err(h, "%s: null d_sources[%d]", what, k);
+      return PM_ERR_INVALID_ARG;
+    }
+    char whose[24];
+    std::snprintf(whose, sizeof whose, "motions[%d]", k);
+    if (int rc = check_motion(h, what, motions[k], whose)) return rc;
+  }
+  return PM_OK;
+}
+
+// ... and the options of the vote
+int check_votes(pm_handle* h, const char* what, float max_diff, int radius, int min_consistent, int max_conflicts,
+                int n_sources) {
+  if (int rc = check_max_diff(h, what, max_diff)) return rc;
+  if (radius < 0 || radius > kConsistencyMaxRadius) {
+    set_err(h, "%s: radius %d outside 0..%d", what, radius, kConsistencyMaxRadius);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (min_consistent < 0 || min_consistent > n_sources) {
+    set_err(h, "%s: min_consistent %d outside 0..n_sources (%d)", what, min_consistent, n_sources);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (max_conflicts < 0 || max_conflicts > kConsistencyMaxSources) {
+    set_err(h, "%s: max_conflicts %d outside 0..%d", what, max_conflicts, kConsistencyMaxSources);
+    return PM_ERR_INVALID_ARG;
+  }
+  return PM_OK;
+}
+
+// A motion into the arrays of a kernel's arguments; null is the identity, and `t` may be null where only R is wanted.
+void set_motion(double R[9], double t[3], const pm_motion* m) {
+  for (int i = 0; i < 9; ++i) R[i] = m ? m->R[i] : (i % 4 == 0 ? 1.0 : 0.0);
+  for (int i = 0; t && i < 3; ++i) t[i] = m ? m->t[i] : 0.0;
+}
+
+// The grid of the three launches that give a block 256 pixels of a row and four rows (the seeds' splats, the consistency
+// filter, the fusion); the kernels keep their own constants.
+static_assert(kReprojectSpan == kConsistencySpan && kConsistencySpan == kFuseSpan && kReprojectBlockY == kConsistencyBlockY &&
+                  kConsistencyBlockY == kFuseBlockY,
+              "one row-span launch shape");
+dim3 span_grid(int rows, int cols) {
+  return dim3((unsigned)((cols + kFuseSpan - 1) / kFuseSpan), (unsigned)((rows + kFuseBlockY - 1) / kFuseBlockY));
+}
+
 // the cloud and the mesh: a compacted stream is gathered from its organised input
 int check_cloud_streams(pm_handle* h, const char* what, const float* d_normals, const float* d_normals_out,
                         const uint8_t* d_bgr8, const uint8_t* d_bgr8_out) {
@@ -111,6 +209,17 @@ int stage_begin(pm_handle* h, const char* what, ImagingState** st, hipStream_t* 
   return PM_OK;
 }
 
+// The counts of a call, padded to 16 bytes: the words in front of a counting stage's scratch, cleared per call.
+constexpr size_t kCountsHeader = 4;
+
+// The scratch of a stage that needs the counts alone: reserved and cleared, `*d_totals` its address.
+int counts_scratch(pm_handle* h, DevBuf<int>& buf, hipStream_t stream, int** d_totals) {
+  PM_HIP(h, buf.reserve(sizeof(int) * kCountsHeader, stream));
+  *d_totals = buf.get();
+  PM_HIP(h, hipMemsetAsync(*d_totals, 0, sizeof(int) * kCountsHeader, stream));
+  return PM_OK;
+}
+
 // Behind the launches of a stage that counts: the `n` (1 to 4) device totals go to the device destination and to the
 // host destination where given; the host copy has landed when this returns.
 int stage_counts(pm_handle* h, hipStream_t stream, const int* d_totals, int n, int* d_dst, int* dst) {
@@ -128,10 +237,7 @@ int stage_counts(pm_handle* h, hipStream_t stream, const int* d_totals, int n, i
 int pm_backproject(pm_handle* h, const pm_cloud_camera* camera, const float* d_disp, int rows, int cols, float* d_xyz) {
   if (!h) return PM_ERR_INVALID_ARG;
   if (int rc = check_cloud_camera(h, "pm_backproject", camera)) return rc;
-  if (!d_disp || !d_xyz) {
-    set_err(h, "pm_backproject: null %s", !d_disp ? "d_disp" : "d_xyz");
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_not_null(h, "pm_backproject", {{"d_disp", d_disp}, {"d_xyz", d_xyz}})) return rc;
   if (int rc = check_cloud_shape(h, "pm_backproject", rows, cols)) return rc;
   PM_HIP(h, hipSetDevice(pm_internal::device(h)));
   const BackprojectArgs a = {cloud_cam(*camera), d_disp, rows, cols, d_xyz};
@@ -159,10 +265,7 @@ int pm_point_cloud(pm_handle* h, const pm_cloud_camera* camera, const pm_cloud_f
   if (!h) return PM_ERR_INVALID_ARG;
   const char* const what = "pm_point_cloud";
   if (int rc = check_cloud_camera(h, what, camera)) return rc;
-  if (!filter || !d_disp) {
-    set_err(h, "%s: null %s", what, !filter ? "filter" : "d_disp");
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_not_null(h, what, {{"filter", filter}, {"d_disp", d_disp}})) return rc;
   if (int rc = check_cloud_filter(h, what, filter)) return rc;
   if (capacity < 0) {
     set_err(h, "%s: capacity %d must be >= 0", what, capacity);
@@ -206,14 +309,8 @@ int pm_disparity_normals(pm_handle* h, const pm_cloud_camera* camera, const pm_n
                          int cols, float* d_normals, float* d_planes, uint8_t* d_support) {
   if (!h) return PM_ERR_INVALID_ARG;
   const char* const what = "pm_disparity_normals";
-  if (!fit || !d_disp) {
-    set_err(h, "%s: null %s", what, !fit ? "fit" : "d_disp");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (!d_normals && !d_planes && !d_support) {
-    set_err(h, "%s: no output (d_normals, d_planes and d_support are all null)", what);
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_not_null(h, what, {{"fit", fit}, {"d_disp", d_disp}})) return rc;
+  if (int rc = check_any_output(h, what, {d_normals, d_planes, d_support}, "d_normals, d_planes and d_support", true)) return rc;
   if (d_normals)  // the camera is read for the normals alone
     if (int rc = check_cloud_camera(h, what, camera)) return rc;
   if (fit->radius < 1 || fit->radius > kNormalsFitMaxRadius) {
@@ -259,22 +356,14 @@ void pm_debug_normals_fit_constants(int* tile_cols, int* tile_rows, int* pixels_
 }
 
 // ---- speckle filter: connected components of similar disparity (pm_speckle.hpp) ------------------------------------------
-namespace {
-constexpr size_t kSpeckleHeader = 4;  // words in front of the labels: the counter's 16 bytes, cleared whole
-}
-
 int pm_filter_speckles(pm_handle* h, const pm_speckle_filter* filter, const float* d_disp, int rows, int cols, float* d_out,
                        int32_t* d_labels, int32_t* d_sizes, int* d_removed, int* removed) {
   if (!h) return PM_ERR_INVALID_ARG;
   const char* const what = "pm_filter_speckles";
-  if (!filter || !d_disp) {
-    set_err(h, "%s: null %s", what, !filter ? "filter" : "d_disp");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (!d_out && !d_labels && !d_sizes && !d_removed && !removed) {
-    set_err(h, "%s: no output (d_out, d_labels, d_sizes, d_removed and removed are all null)", what);
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_not_null(h, what, {{"filter", filter}, {"d_disp", d_disp}})) return rc;
+  if (int rc = check_any_output(h, what, {d_out, d_labels, d_sizes, d_removed, removed},
+                                "d_out, d_labels, d_sizes, d_removed and removed", true))
+    return rc;
   if (int rc = check_max_diff(h, what, filter->max_diff)) return rc;
   if (filter->max_size < 0) {
     set_err(h, "%s: max_size %d must be >= 0", what, filter->max_size);
@@ -293,14 +382,14 @@ int pm_filter_speckles(pm_handle* h, const pm_speckle_filter* filter, const floa
   hipStream_t stream = nullptr;
   if (int rc = stage_begin(h, what, &st, &stream)) return rc;
   const int pixels = rows * cols;
-  PM_HIP(h, st->speckle_buf.reserve(sizeof(int) * (kSpeckleHeader + 2 * (size_t)pixels), stream));
+  PM_HIP(h, st->speckle_buf.reserve(sizeof(int) * (kCountsHeader + 2 * (size_t)pixels), stream));
   int* d_total = st->speckle_buf.get();
-  const SpeckleArgs a = {d_disp, rows, cols, filter->max_diff, d_total + kSpeckleHeader, d_total + kSpeckleHeader + pixels};
+  const SpeckleArgs a = {d_disp, rows, cols, filter->max_diff, d_total + kCountsHeader, d_total + kCountsHeader + pixels};
   const SpeckleOut o = {d_out, d_labels, d_sizes, filter->max_size};
   const int tiles_x = speckle_tiles_x(cols);
   const long long tiles = (long long)tiles_x * speckle_tiles_y(rows), items = speckle_merge_items(rows, cols);
   const unsigned per_pixel = (unsigned)(((long long)pixels + kSpeckleBlock - 1) / kSpeckleBlock);
-  PM_HIP(h, hipMemsetAsync(d_total, 0, sizeof(int) * kSpeckleHeader, stream));
+  PM_HIP(h, hipMemsetAsync(d_total, 0, sizeof(int) * kCountsHeader, stream));
   hipLaunchKernelGGL(k_speckle_local, dim3((unsigned)tiles), dim3(kSpeckleTileCols, kSpeckleTileRows), 0, stream, a, tiles_x);
   if (items > 0)
     hipLaunchKernelGGL(k_speckle_merge, dim3((unsigned)((items + kSpeckleBlock - 1) / kSpeckleBlock)), dim3(kSpeckleBlock), 0,
@@ -324,10 +413,7 @@ int pm_grid_mesh(pm_handle* h, const pm_cloud_camera* camera, const pm_cloud_fil
   if (!h) return PM_ERR_INVALID_ARG;
   const char* const what = "pm_grid_mesh";
   if (int rc = check_cloud_camera(h, what, camera)) return rc;
-  if (!filter || !options || !d_disp) {
-    set_err(h, "%s: null %s", what, !filter ? "filter" : !options ? "options" : "d_disp");
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_not_null(h, what, {{"filter", filter}, {"options", options}, {"d_disp", d_disp}})) return rc;
   if (int rc = check_cloud_filter(h, what, filter)) return rc;
   if (int rc = check_max_diff(h, what, options->max_diff)) return rc;
   if (options->vertices != PM_MESH_VERTICES_ALL && options->vertices != PM_MESH_VERTICES_REFERENCED) {
@@ -382,39 +468,22 @@ void pm_debug_mesh_constants(int* items_per_block, int* blocks_per_scan_pass) {
 }
 
 // ---- temporal seeds: a map carried into the next frame's two seed maps (pm_reproject.hpp) ------------------------------------
-namespace {
-constexpr size_t kReprojectHeader = 4;  // words in front of the maps: the two counts, padded to 16 bytes
-}
-
 int pm_reproject_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_motion* motion,
                            const pm_reproject_options* options, const float* d_disp, int rows, int cols, float* d_seed_l,
                            float* d_seed_r, int* d_counts, int* counts) {
   if (!h) return PM_ERR_INVALID_ARG;
   const char* const what = "pm_reproject_disparity";
   if (int rc = check_cloud_camera(h, what, camera)) return rc;
-  if (!motion || !options || !d_disp) {
-    set_err(h, "%s: null %s", what, !motion ? "motion" : !options ? "options" : "d_disp");
-    return PM_ERR_INVALID_ARG;
-  }
-  for (int i = 0; i < 12; ++i)
-    if (!std::isfinite(i < 9 ? motion->R[i] : motion->t[i - 9])) {
-      set_err(h, "%s: %s[%d] of the motion is not finite", what, i < 9 ? "R" : "t", i < 9 ? i : i - 9);
-      return PM_ERR_INVALID_ARG;
-    }
-  if (!(options->min_disp >= 0.f) || !(options->max_disp >= 0.f)) {
-    set_err(h, "%s: %s must be >= 0 and not NaN%s", what, !(options->min_disp >= 0.f) ? "min_disp" : "max_disp",
-            !(options->min_disp >= 0.f) ? "" : " (0 = no limit)");
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_not_null(h, what, {{"motion", motion}, {"options", options}, {"d_disp", d_disp}})) return rc;
+  if (int rc = check_motion(h, what, *motion, "the motion")) return rc;
+  if (int rc = check_disp_limits(h, what, options->min_disp, options->max_disp)) return rc;
   if (options->close_radius < 0 || options->close_radius > kReprojectMaxRadius) {
     set_err(h, "%s: close_radius %d must be 0 .. %d", what, options->close_radius, kReprojectMaxRadius);
     return PM_ERR_INVALID_ARG;
   }
   if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
-  if (!d_seed_l && !d_seed_r && !d_counts && !counts) {
-    set_err(h, "%s: no output: d_seed_l, d_seed_r, d_counts and counts are all null", what);
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_any_output(h, what, {d_seed_l, d_seed_r, d_counts, counts}, "d_seed_l, d_seed_r, d_counts and counts"))
+    return rc;
   if (d_seed_l == d_disp || d_seed_r == d_disp) {
     set_err(h, "%s: %s must not alias d_disp", what, d_seed_l == d_disp ? "d_seed_l" : "d_seed_r");
     return PM_ERR_INVALID_ARG;
@@ -423,20 +492,18 @@ int pm_reproject_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm
   hipStream_t stream = nullptr;
   if (int rc = stage_begin(h, what, &st, &stream)) return rc;
   const size_t px = (size_t)rows * cols;
-  const size_t cleared = kReprojectHeader + 2 * px;
+  const size_t cleared = kCountsHeader + 2 * px;
   PM_HIP(h, st->reproject_buf.reserve(sizeof(unsigned) * (cleared + (d_seed_l ? 0 : px)), stream));
   unsigned* base = st->reproject_buf.get();
   int* d_totals = reinterpret_cast<int*>(base);
-  unsigned* splat_l = base + kReprojectHeader;
+  unsigned* splat_l = base + kCountsHeader;
   unsigned* splat_r = splat_l + px;
   unsigned* closed_l = d_seed_l ? reinterpret_cast<unsigned*>(d_seed_l) : splat_r + px;
   PM_HIP(h, hipMemsetAsync(base, 0, sizeof(unsigned) * cleared, stream));
   ReprojectArgs a = {cloud_cam(*camera), {}, {}, options->min_disp, options->max_disp, d_disp, rows, cols, splat_l};
-  for (int i = 0; i < 9; ++i) a.R[i] = motion->R[i];
-  for (int i = 0; i < 3; ++i) a.t[i] = motion->t[i];
-  const int span = kReprojectSpan;
+  set_motion(a.R, a.t, motion);
   const dim3 block(kReprojectBlockX, kReprojectBlockY);
-  const dim3 splat_grid((unsigned)((cols + span - 1) / span), (unsigned)((rows + kReprojectBlockY - 1) / kReprojectBlockY));
+  const dim3 splat_grid = span_grid(rows, cols);
   const dim3 tile_grid((unsigned)((cols + kReprojectTileW - 1) / kReprojectTileW),
                        (unsigned)((rows + kReprojectTileH - 1) / kReprojectTileH));
   const int r = options->close_radius;
@@ -460,8 +527,6 @@ void pm_debug_reproject_constants(int* tile_w, int* tile_h) {
 
 // ---- geometric consistency: a map judged by earlier maps of its sequence (pm_consistency.hpp) -------------------------------
 namespace {
-constexpr size_t kConsistencyHeader = 4;  // the two counts, padded to 16 bytes
-
 template <int RADIUS>
 void launch_consistency(const ConsistencyArgs& a, dim3 grid, hipStream_t stream) {
   hipLaunchKernelGGL(k_consistency<RADIUS>, grid, dim3(kConsistencyBlockX, kConsistencyBlockY), 0, stream, a);
@@ -474,43 +539,15 @@ int pm_filter_consistency(pm_handle* h, const pm_cloud_camera* camera, const pm_
   if (!h) return PM_ERR_INVALID_ARG;
   const char* const what = "pm_filter_consistency";
   if (int rc = check_cloud_camera(h, what, camera)) return rc;
-  if (!options || !d_disp || !d_sources || !motions) {
-    set_err(h, "%s: null %s", what, !options ? "options" : !d_disp ? "d_disp" : !d_sources ? "d_sources" : "motions");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (n_sources < 1 || n_sources > kConsistencyMaxSources) {
-    set_err(h, "%s: n_sources %d outside 1..%d", what, n_sources, kConsistencyMaxSources);
-    return PM_ERR_INVALID_ARG;
-  }
-  for (int k = 0; k < n_sources; ++k) {
-    if (!d_sources[k]) {
-      set_err(h, "%s: null d_sources[%d]", what, k);
-      return PM_ERR_INVALID_ARG;
-    }
-    for (int i = 0; i < 12; ++i)
-      if (!std::isfinite(i < 9 ? motions[k].R[i] : motions[k].t[i - 9])) {
-        set_err(h, "%s: %s[%d] of motions[%d] is not finite", what, i < 9 ? "R" : "t", i < 9 ? i : i - 9, k);
-        return PM_ERR_INVALID_ARG;
-      }
-  }
-  if (int rc = check_max_diff(h, what, options->max_diff)) return rc;
-  if (options->radius < 0 || options->radius > kConsistencyMaxRadius) {
-    set_err(h, "%s: radius %d outside 0..%d", what, options->radius, kConsistencyMaxRadius);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (options->min_consistent < 0 || options->min_consistent > n_sources) {
-    set_err(h, "%s: min_consistent %d outside 0..n_sources (%d)", what, options->min_consistent, n_sources);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (options->max_conflicts < 0 || options->max_conflicts > kConsistencyMaxSources) {
-    set_err(h, "%s: max_conflicts %d outside 0..%d", what, options->max_conflicts, kConsistencyMaxSources);
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_not_null(h, what, {{"options", options}, {"d_disp", d_disp}, {"d_sources", d_sources}, {"motions", motions}}))
+    return rc;
+  if (int rc = check_sources(h, what, n_sources, d_sources, motions)) return rc;
+  if (int rc = check_votes(h, what, options->max_diff, options->radius, options->min_consistent, options->max_conflicts, n_sources))
+    return rc;
   if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
-  if (!d_out && !d_classes && !d_residual && !d_counts && !counts) {
-    set_err(h, "%s: no output: d_out, d_classes, d_residual, d_counts and counts are all null", what);
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_any_output(h, what, {d_out, d_classes, d_residual, d_counts, counts},
+                                "d_out, d_classes, d_residual, d_counts and counts"))
+    return rc;
   for (int k = 0; d_out && k < n_sources; ++k)
     if (d_out == d_sources[k]) {  // a pixel of a source is read by other pixels' lookups
       set_err(h, "%s: d_out must not alias d_sources[%d]", what, k);
@@ -519,21 +556,18 @@ int pm_filter_consistency(pm_handle* h, const pm_cloud_camera* camera, const pm_
   ImagingState* st = nullptr;
   hipStream_t stream = nullptr;
   if (int rc = stage_begin(h, what, &st, &stream)) return rc;
-  PM_HIP(h, st->consistency_counts.reserve(sizeof(int) * kConsistencyHeader, stream));
-  int* d_totals = st->consistency_counts.get();
+  int* d_totals = nullptr;
+  if (int rc = counts_scratch(h, st->consistency_counts, stream, &d_totals)) return rc;
   ConsistencyArgs a = {};
   a.cam = cloud_cam(*camera);
   a.disp = d_disp, a.rows = rows, a.cols = cols, a.n = n_sources;
   a.max_diff = options->max_diff, a.min_consistent = options->min_consistent, a.max_conflicts = options->max_conflicts;
   a.out = d_out, a.classes = d_classes, a.residual = d_residual, a.counts = d_totals;
   for (int k = 0; k < n_sources; ++k) {
-    for (int i = 0; i < 9; ++i) a.src[k].R[i] = motions[k].R[i];
-    for (int i = 0; i < 3; ++i) a.src[k].t[i] = motions[k].t[i];
+    set_motion(a.src[k].R, a.src[k].t, &motions[k]);
     a.src[k].map = d_sources[k];
   }
-  PM_HIP(h, hipMemsetAsync(d_totals, 0, sizeof(int) * kConsistencyHeader, stream));
-  const dim3 grid((unsigned)((cols + kConsistencySpan - 1) / kConsistencySpan),
-                  (unsigned)((rows + kConsistencyBlockY - 1) / kConsistencyBlockY));
+  const dim3 grid = span_grid(rows, cols);
   switch (options->radius) {
     case 0: launch_consistency<0>(a, grid, stream); break;
     case 1: launch_consistency<1>(a, grid, stream); break;
@@ -545,8 +579,6 @@ int pm_filter_consistency(pm_handle* h, const pm_cloud_camera* camera, const pm_
 
 // ---- matching confidence: the functor evaluated again around a map's answer (pm_confidence.hpp) -----------------------------
 namespace {
-constexpr size_t kConfidenceHeader = 4;  // the three counts, padded to 16 bytes
-
 template <int PW, int PH>
 void launch_confidence(const ConfidenceArgs& a, dim3 grid, hipStream_t stream) {
   hipLaunchKernelGGL((k_confidence<PW, PH>), grid, dim3(kConfThreads), 0, stream, a);
@@ -558,14 +590,11 @@ int pm_disparity_confidence(pm_handle* h, const pm_confidence_options* options, 
                             uint8_t* d_flags, int* d_counts, int* counts) {
   if (!h) return PM_ERR_INVALID_ARG;
   const char* const what = "pm_disparity_confidence";
-  if (!options || !d_left || !d_right || !d_disp_l) {
-    set_err(h, "%s: null %s", what, !options ? "options" : !d_left ? "d_left" : !d_right ? "d_right" : "d_disp_l");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (!d_out && !d_measures && !d_flags && !d_counts && !counts) {
-    set_err(h, "%s: no output: d_out, d_measures, d_flags, d_counts and counts are all null", what);
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_not_null(h, what, {{"options", options}, {"d_left", d_left}, {"d_right", d_right}, {"d_disp_l", d_disp_l}}))
+    return rc;
+  if (int rc = check_any_output(h, what, {d_out, d_measures, d_flags, d_counts, counts},
+                                "d_out, d_measures, d_flags, d_counts and counts"))
+    return rc;
   const int pw = options->patch_w, ph = options->patch_h;
   if (pw < 3 || pw > PM_MAX_PATCH || pw % 2 == 0 || ph < 3 || ph > PM_MAX_PATCH || ph % 2 == 0) {
     const bool w_bad = pw < 3 || pw > PM_MAX_PATCH || pw % 2 == 0;
@@ -592,9 +621,9 @@ int pm_disparity_confidence(pm_handle* h, const pm_confidence_options* options, 
   hipStream_t stream = nullptr;
   if (int rc = stage_begin(h, what, &st, &stream)) return rc;
   const size_t px = (size_t)rows * cols;
-  PM_HIP(h, st->confidence_buf.reserve(sizeof(int) * (kConfidenceHeader + px + (px + 3) / 4), stream));
+  PM_HIP(h, st->confidence_buf.reserve(sizeof(int) * (kCountsHeader + px + (px + 3) / 4), stream));
   int* d_totals = st->confidence_buf.get();
-  float* d_gr = reinterpret_cast<float*>(d_totals + kConfidenceHeader);
+  float* d_gr = reinterpret_cast<float*>(d_totals + kCountsHeader);
   uint8_t* d_gl8 = reinterpret_cast<uint8_t*>(d_gr + px);
   const pm_params& p = pm_internal::params(h);
   ConfidenceArgs a = {};
@@ -604,7 +633,7 @@ int pm_disparity_confidence(pm_handle* h, const pm_confidence_options* options, 
   a.max_lr_diff = options->max_lr_diff, a.drop_unmeasured = options->drop_unmeasured;
   a.cp = confidence_cost_params(p.functor_alpha, p.functor_tau_color, p.functor_tau_grad, pw, ph);
   a.out = d_out, a.measures = d_measures, a.flags = d_flags, a.counts = d_totals;
-  PM_HIP(h, hipMemsetAsync(d_totals, 0, sizeof(int) * kConfidenceHeader, stream));
+  PM_HIP(h, hipMemsetAsync(d_totals, 0, sizeof(int) * kCountsHeader, stream));
   static_assert(kConfGradBlockY == kCloudBlockY && kConfTileH >= kCloudBlockY, "check_cloud_shape bounds both grids");
   hipLaunchKernelGGL(k_confidence_grad,
                      dim3((unsigned)((cols + kConfGradBlockX - 1) / kConfGradBlockX), (unsigned)((rows + kConfGradBlockY - 1) / kConfGradBlockY)),
@@ -630,8 +659,6 @@ void pm_debug_confidence_constants(int* tile_w, int* tile_h, int* target_cols) {
 
 // ---- sequence fusion: a map refined by, and filled from, earlier maps of its sequence (pm_fuse.hpp) ---------------------------
 namespace {
-constexpr size_t kFuseHeader = 4;  // the four counts: 16 bytes in front of the splat maps
-
 template <int RADIUS>
 void launch_fuse(const FuseArgs& a, dim3 grid, hipStream_t stream) {
   hipLaunchKernelGGL(k_fuse<RADIUS>, grid, dim3(kFuseBlockX, kFuseBlockY), 0, stream, a);
@@ -645,38 +672,11 @@ int pm_fuse_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_fuse
   if (!h) return PM_ERR_INVALID_ARG;
   const char* const what = "pm_fuse_disparity";
   if (int rc = check_cloud_camera(h, what, camera)) return rc;
-  if (!options || !d_disp || !d_sources || !motions) {
-    set_err(h, "%s: null %s", what, !options ? "options" : !d_disp ? "d_disp" : !d_sources ? "d_sources" : "motions");
-    return PM_ERR_INVALID_ARG;
-  }
-  if (n_sources < 1 || n_sources > kFuseMaxSources) {
-    set_err(h, "%s: n_sources %d outside 1..%d", what, n_sources, kFuseMaxSources);
-    return PM_ERR_INVALID_ARG;
-  }
-  for (int k = 0; k < n_sources; ++k) {
-    if (!d_sources[k]) {
-      set_err(h, "%s: null d_sources[%d]", what, k);
-      return PM_ERR_INVALID_ARG;
-    }
-    for (int i = 0; i < 12; ++i)
-      if (!std::isfinite(i < 9 ? motions[k].R[i] : motions[k].t[i - 9])) {
-        set_err(h, "%s: %s[%d] of motions[%d] is not finite", what, i < 9 ? "R" : "t", i < 9 ? i : i - 9, k);
-        return PM_ERR_INVALID_ARG;
-      }
-  }
-  if (int rc = check_max_diff(h, what, options->max_diff)) return rc;
-  if (options->radius < 0 || options->radius > kFuseMaxRadius) {
-    set_err(h, "%s: radius %d outside 0..%d", what, options->radius, kFuseMaxRadius);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (options->min_consistent < 0 || options->min_consistent > n_sources) {
-    set_err(h, "%s: min_consistent %d outside 0..n_sources (%d)", what, options->min_consistent, n_sources);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (options->max_conflicts < 0 || options->max_conflicts > kFuseMaxSources) {
-    set_err(h, "%s: max_conflicts %d outside 0..%d", what, options->max_conflicts, kFuseMaxSources);
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_not_null(h, what, {{"options", options}, {"d_disp", d_disp}, {"d_sources", d_sources}, {"motions", motions}}))
+    return rc;
+  if (int rc = check_sources(h, what, n_sources, d_sources, motions)) return rc;
+  if (int rc = check_votes(h, what, options->max_diff, options->radius, options->min_consistent, options->max_conflicts, n_sources))
+    return rc;
   if (options->fill_min_sources < 0 || options->fill_min_sources > n_sources) {
     set_err(h, "%s: fill_min_sources %d outside 0..n_sources (%d)", what, options->fill_min_sources, n_sources);
     return PM_ERR_INVALID_ARG;
@@ -686,10 +686,9 @@ int pm_fuse_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_fuse
     return PM_ERR_INVALID_ARG;
   }
   if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
-  if (!d_out && !d_count && !d_spread && !d_flags && !d_counts && !counts) {
-    set_err(h, "%s: no output: d_out, d_count, d_spread, d_flags, d_counts and counts are all null", what);
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_any_output(h, what, {d_out, d_count, d_spread, d_flags, d_counts, counts},
+                                "d_out, d_count, d_spread, d_flags, d_counts and counts"))
+    return rc;
   const void* const outs[4] = {d_out, d_count, d_spread, d_flags};
   static const char* const out_names[4] = {"d_out", "d_count", "d_spread", "d_flags"};
   for (int o = 0; o < 4; ++o)
@@ -705,10 +704,10 @@ int pm_fuse_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_fuse
   if (int rc = stage_begin(h, what, &st, &stream)) return rc;
   const bool fill = options->fill_min_sources >= 1;
   const size_t px = (size_t)rows * cols;
-  const size_t words = kFuseHeader + (fill ? (size_t)n_sources * px : 0);
+  const size_t words = kCountsHeader + (fill ? (size_t)n_sources * px : 0);
   PM_HIP(h, st->fuse_buf.reserve(sizeof(unsigned) * words, stream));
   unsigned* base = st->fuse_buf.get();
-  unsigned* d_splat = base + kFuseHeader;
+  unsigned* d_splat = base + kCountsHeader;
   FuseArgs a = {};
   a.cam = cloud_cam(*camera);
   a.disp = d_disp, a.weight = d_weight, a.rows = rows, a.cols = cols, a.n = n_sources;
@@ -719,18 +718,15 @@ int pm_fuse_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_fuse
   FuseSplatArgs sa = {};
   sa.cam = a.cam, sa.rows = rows, sa.cols = cols, sa.splat = d_splat, sa.px = px;
   for (int k = 0; k < n_sources; ++k) {
-    const double* R = motions[k].R;
-    const double* t = motions[k].t;
-    for (int i = 0; i < 9; ++i) a.src[k].R[i] = R[i];
-    for (int i = 0; i < 3; ++i) a.src[k].t[i] = t[i];
+    set_motion(a.src[k].R, a.src[k].t, &motions[k]);
     a.src[k].map = d_sources[k];
     a.src[k].weight = d_source_weights ? d_source_weights[k] : nullptr;
-    motion_inverse(R, t, sa.src[k].R, sa.src[k].t);  // in binary64 (not contracted: -ffp-contract=off)
+    motion_inverse(motions[k].R, motions[k].t, sa.src[k].R, sa.src[k].t);  // in binary64 (not contracted: -ffp-contract=off)
     sa.src[k].map = d_sources[k];
   }
   PM_HIP(h, hipMemsetAsync(base, 0, sizeof(unsigned) * words, stream));
   const dim3 block(kFuseBlockX, kFuseBlockY);
-  const dim3 grid((unsigned)((cols + kFuseSpan - 1) / kFuseSpan), (unsigned)((rows + kFuseBlockY - 1) / kFuseBlockY));
+  const dim3 grid = span_grid(rows, cols);
   if (fill) hipLaunchKernelGGL(k_fuse_splat, dim3(grid.x, grid.y, (unsigned)n_sources), block, 0, stream, sa);
   switch (options->radius) {
     case 0: launch_fuse<0>(a, grid, stream); break;
@@ -743,8 +739,6 @@ int pm_fuse_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_fuse
 
 // ---- a persistent world-frame model: a TSDF volume integrated from maps and raycast back (pm_tsdf.hpp) ------------------------
 namespace {
-constexpr size_t kTsdfHeader = 4;            // the counts of a call, padded to 16 bytes
-
 // the volume's voxels, or 0 where a dimension is < 1 or they exceed 2^31 - 1
 size_t tsdf_voxels(const pm_tsdf_volume& v) {
   if (v.nx < 1 || v.ny < 1 || v.nz < 1) return 0;
@@ -767,20 +761,13 @@ const char* tsdf_volume_fault(const pm_tsdf_volume& v) {
 int check_tsdf_common(pm_handle* h, const char* what, const pm_cloud_camera* camera, const pm_tsdf_volume* volume,
                       const pm_motion* pose, const void* options, const void* d_voxels) {
   if (int rc = check_cloud_camera(h, what, camera)) return rc;
-  if (!volume || !pose || !options || !d_voxels) {
-    set_err(h, "%s: null %s", what, !volume ? "volume" : !pose ? "pose" : !options ? "options" : "d_voxels");
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_not_null(h, what, {{"volume", volume}, {"pose", pose}, {"options", options}, {"d_voxels", d_voxels}}))
+    return rc;
   if (const char* fault = tsdf_volume_fault(*volume)) {
     set_err(h, "%s: %s", what, fault);
     return PM_ERR_INVALID_ARG;
   }
-  for (int i = 0; i < 12; ++i)
-    if (!std::isfinite(i < 9 ? pose->R[i] : pose->t[i - 9])) {
-      set_err(h, "%s: %s[%d] of the pose is not finite", what, i < 9 ? "R" : "t", i < 9 ? i : i - 9);
-      return PM_ERR_INVALID_ARG;
-    }
-  return PM_OK;
+  return check_motion(h, what, *pose, "the pose");
 }
 
 int check_tsdf_size(pm_handle* h, const char* what, const pm_tsdf_volume& v) {
@@ -800,10 +787,7 @@ size_t pm_tsdf_bytes(const pm_tsdf_volume* volume) {
 int pm_tsdf_clear(pm_handle* h, const pm_tsdf_volume* volume, void* d_voxels) {
   if (!h) return PM_ERR_INVALID_ARG;
   const char* const what = "pm_tsdf_clear";
-  if (!volume || !d_voxels) {
-    set_err(h, "%s: null %s", what, !volume ? "volume" : "d_voxels");
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_not_null(h, what, {{"volume", volume}, {"d_voxels", d_voxels}})) return rc;
   if (const char* fault = tsdf_volume_fault(*volume)) {
     set_err(h, "%s: %s", what, fault);
     return PM_ERR_INVALID_ARG;
@@ -820,10 +804,7 @@ int pm_tsdf_integrate(pm_handle* h, const pm_cloud_camera* camera, const pm_tsdf
   if (!h) return PM_ERR_INVALID_ARG;
   const char* const what = "pm_tsdf_integrate";
   if (int rc = check_tsdf_common(h, what, camera, volume, pose, options, d_voxels)) return rc;
-  if (!d_disp) {
-    set_err(h, "%s: null d_disp", what);
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_not_null(h, what, {{"d_disp", d_disp}})) return rc;
   if (std::isnan(options->min_disp) || options->min_disp < 0.f) {
     set_err(h, "%s: min_disp must not be NaN or negative", what);
     return PM_ERR_INVALID_ARG;
@@ -837,17 +818,15 @@ int pm_tsdf_integrate(pm_handle* h, const pm_cloud_camera* camera, const pm_tsdf
   ImagingState* st = nullptr;
   hipStream_t stream = nullptr;
   if (int rc = stage_begin(h, what, &st, &stream)) return rc;
-  PM_HIP(h, st->tsdf_counts.reserve(sizeof(int) * kTsdfHeader, stream));
-  int* d_totals = st->tsdf_counts.get();
+  int* d_totals = nullptr;
+  if (int rc = counts_scratch(h, st->tsdf_counts, stream, &d_totals)) return rc;
   TsdfIntegrateArgs a = {};
   a.cam = cloud_cam(*camera);
   a.grid = tsdf_grid(*volume);
-  for (int i = 0; i < 9; ++i) a.R[i] = pose->R[i];
-  for (int i = 0; i < 3; ++i) a.t[i] = pose->t[i];
+  set_motion(a.R, a.t, pose);
   a.min_disp = options->min_disp, a.max_range = options->max_range;
   a.disp = d_disp, a.weight = d_weight, a.rows = rows, a.cols = cols;
   a.voxels = static_cast<TsdfVoxel*>(d_voxels), a.counts = d_totals;
-  PM_HIP(h, hipMemsetAsync(d_totals, 0, sizeof(int) * kTsdfHeader, stream));
   const size_t spans = (((size_t)volume->nx + kTsdfLanes - 1) / kTsdfLanes) * (size_t)volume->ny * (size_t)volume->nz;
   const size_t blocks = (spans + kTsdfBlockY - 1) / kTsdfBlockY;
   const dim3 grid((unsigned)(blocks < kTsdfMaxBlocks ? blocks : kTsdfMaxBlocks));
@@ -876,15 +855,14 @@ int pm_tsdf_raycast(pm_handle* h, const pm_cloud_camera* camera, const pm_tsdf_v
     return PM_ERR_INVALID_ARG;
   }
   if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
-  if (!d_disp_out && !d_normals_out && !d_counts && !counts) {
-    set_err(h, "%s: no output: d_disp_out, d_normals_out, d_counts and counts are all null", what);
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_any_output(h, what, {d_disp_out, d_normals_out, d_counts, counts},
+                                "d_disp_out, d_normals_out, d_counts and counts"))
+    return rc;
   if (int rc = check_tsdf_size(h, what, *volume)) return rc;
   TsdfRaycastArgs a = {};
   a.cam = cloud_cam(*camera);
   a.grid = tsdf_grid(*volume);
-  for (int i = 0; i < 9; ++i) a.R[i] = pose->R[i];
+  set_motion(a.R, nullptr, pose);
   motion_inverse(pose->R, pose->t, a.Ri, a.c);  // in binary64 (not contracted: -ffp-contract=off)
   a.min_range = (double)options->min_range, a.max_range = (double)options->max_range;
   a.ds = (double)options->step * volume->trunc;
@@ -899,10 +877,9 @@ int pm_tsdf_raycast(pm_handle* h, const pm_cloud_camera* camera, const pm_tsdf_v
   ImagingState* st = nullptr;
   hipStream_t stream = nullptr;
   if (int rc = stage_begin(h, what, &st, &stream)) return rc;
-  PM_HIP(h, st->tsdf_counts.reserve(sizeof(int) * kTsdfHeader, stream));
-  int* d_totals = st->tsdf_counts.get();
+  int* d_totals = nullptr;
+  if (int rc = counts_scratch(h, st->tsdf_counts, stream, &d_totals)) return rc;
   a.counts = d_totals;
-  PM_HIP(h, hipMemsetAsync(d_totals, 0, sizeof(int) * kTsdfHeader, stream));
   const dim3 grid((unsigned)((cols + kTsdfLanes - 1) / kTsdfLanes), (unsigned)((rows + kTsdfBlockY - 1) / kTsdfBlockY));
   hipLaunchKernelGGL(k_tsdf_raycast, grid, dim3(kTsdfBlockX, kTsdfBlockY), 0, stream, a);
   if (int rc = launch_check(h, "tsdf raycast")) return rc;
@@ -916,8 +893,6 @@ void pm_debug_tsdf_constants(int* lanes, int* waves) {
 
 // ---- camera motion between two frames: features of the old left image tracked into the new one (pm_track.hpp) ----------------
 namespace {
-constexpr size_t kTrackHeader = 4;  // words in front of the per-cell arrays: [0] the number of features, padded to 16 bytes
-
 // what pm_track_features and pm_estimate_motion are both given
 struct TrackInputs {
   const pm_cloud_camera* camera;
@@ -939,17 +914,12 @@ struct TrackRun {
 // The checks of everything but the outputs, in a fixed order.
 int check_track(pm_handle* h, const char* what, const TrackInputs& in) {
   const pm_track_options* o = in.options;
-  const pm_motion* guess = in.guess;
   if (int rc = check_cloud_camera(h, what, in.camera)) return rc;
-  if (!o || !in.left_old || !in.disp_old || !in.left_new) {
-    set_err(h, "%s: null %s", what, !o ? "options" : !in.left_old ? "d_left_old" : !in.disp_old ? "d_disp_old" : "d_left_new");
-    return PM_ERR_INVALID_ARG;
-  }
-  for (int i = 0; guess && i < 12; ++i)
-    if (!std::isfinite(i < 9 ? guess->R[i] : guess->t[i - 9])) {
-      set_err(h, "%s: %s[%d] of the guess is not finite", what, i < 9 ? "R" : "t", i < 9 ? i : i - 9);
-      return PM_ERR_INVALID_ARG;
-    }
+  if (int rc = check_not_null(h, what, {{"options", o}, {"d_left_old", in.left_old}, {"d_disp_old", in.disp_old},
+                                        {"d_left_new", in.left_new}}))
+    return rc;
+  if (in.guess)
+    if (int rc = check_motion(h, what, *in.guess, "the guess")) return rc;
   if (o->cell < kTrackMinCell || o->cell > kTrackMaxCell) {
     set_err(h, "%s: cell %d outside %d..%d", what, o->cell, kTrackMinCell, kTrackMaxCell);
     return PM_ERR_INVALID_ARG;
@@ -966,11 +936,7 @@ int check_track(pm_handle* h, const char* what, const TrackInputs& in) {
     set_err(h, "%s: min_score %lld must be >= 1", what, (long long)o->min_score);
     return PM_ERR_INVALID_ARG;
   }
-  if (!(o->min_disp >= 0.f) || !(o->max_disp >= 0.f)) {
-    set_err(h, "%s: %s must be >= 0 and not NaN%s", what, !(o->min_disp >= 0.f) ? "min_disp" : "max_disp",
-            !(o->min_disp >= 0.f) ? "" : " (0 = no limit)");
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_disp_limits(h, what, o->min_disp, o->max_disp)) return rc;
   if (o->max_sad < 0 || o->min_gap < 0) {
     set_err(h, "%s: %s must be >= 0", what, o->max_sad < 0 ? "max_sad" : "min_gap");
     return PM_ERR_INVALID_ARG;
@@ -980,22 +946,21 @@ int check_track(pm_handle* h, const char* what, const TrackInputs& in) {
 
 int track_cells(int n, int cell) { return (n + cell - 1) / cell; }
 
-// The three launches.  Scratch: kTrackHeader words, the per-cell results, the feature list and, with `own_records`, one
+// The three launches.  Scratch: kCountsHeader words, the per-cell results, the feature list and, with `own_records`, one
 // record per cell behind them, which then take the place of d_tracks and capacity.
 int run_track(pm_handle* h, const char* what, const TrackInputs& in, int capacity, pm_track* d_tracks, int* d_count,
               bool own_records, TrackRun* run) {
   const pm_track_options* o = in.options;
-  const pm_motion* guess = in.guess;
   const int rows = in.rows, cols = in.cols;
   ImagingState* st = nullptr;
   hipStream_t stream = nullptr;
   if (int rc = stage_begin(h, what, &st, &stream)) return rc;
   const int ncx = track_cells(cols, o->cell), ncy = track_cells(rows, o->cell);
   const size_t cells = (size_t)ncx * ncy;  // <= rows * cols / 64 + ...: far below 2^31 (check_cloud_shape)
-  const size_t words = kTrackHeader + 2 * cells;
+  const size_t words = kCountsHeader + 2 * cells;
   PM_HIP(h, st->track_buf.reserve(sizeof(int) * words + (own_records ? sizeof(pm_track) * cells : 0), stream));
   int* base = st->track_buf.get();
-  int* cell_best = base + kTrackHeader;
+  int* cell_best = base + kCountsHeader;
   int* feat = cell_best + cells;
   if (own_records) {
     d_tracks = reinterpret_cast<pm_track*>(base + words);
@@ -1011,8 +976,7 @@ int run_track(pm_handle* h, const char* what, const TrackInputs& in, int capacit
   if (blocks > 0 && d_tracks) {
     TrackMatchArgs a = {};
     a.opt = opt, a.cam = cloud_cam(*in.camera);
-    for (int i = 0; i < 9; ++i) a.R[i] = guess ? guess->R[i] : (i % 4 == 0 ? 1.0 : 0.0);
-    for (int i = 0; i < 3; ++i) a.t[i] = guess ? guess->t[i] : 0.0;
+    set_motion(a.R, a.t, in.guess);
     a.old = in.left_old, a.disp = in.disp_old, a.img = in.left_new, a.rows = rows, a.cols = cols;
     a.feat = feat, a.total = base, a.tracks = d_tracks;
     hipLaunchKernelGGL(k_track_match, dim3((unsigned)blocks), dim3(kTrackBlock), 0, stream, a);
@@ -1056,10 +1020,7 @@ int pm_estimate_motion(pm_handle* h, const pm_cloud_camera* camera, const pm_tra
   const TrackInputs in = {camera, track_options, guess, d_left_old, d_disp_old, d_left_new, rows, cols};
   if (int rc = check_track(h, what, in)) return rc;
   const pm_solve_options* s = solve_options;
-  if (!s) {
-    set_err(h, "%s: null solve_options", what);
-    return PM_ERR_INVALID_ARG;
-  }
+  if (int rc = check_not_null(h, what, {{"solve_options", s}})) return rc;
   if (s->iterations < 1 || s->iterations > 50) {
     set_err(h, "%s: iterations %d outside 1..50", what, s->iterations);
     return PM_ERR_INVALID_ARG;

@@ -15,12 +15,15 @@ int g_device = 0;
 pm_handle* g_handle = nullptr;
 std::mutex g_mutex;
 
-void Check(int status, const char* what) {
+// A failed call throws with the error text of the handle it ran on.
+void CheckOn(pm_handle* h, int status, const char* what) {
   if (status == PM_OK) return;
   std::string msg = std::string(what) + ": " + pm_status_string(status);
-  if (g_handle) msg += std::string(" -- ") + pm_last_error(g_handle);
+  if (h) msg += std::string(" -- ") + pm_last_error(h);
   throw std::runtime_error(msg);
 }
+
+void Check(int status, const char* what) { CheckOn(g_handle, status, what); }  // the imaging context's calls
 
 pm_handle* Context() {
   if (g_handle) return g_handle;
@@ -38,31 +41,79 @@ pm_handle* Context() {
   return g_handle;
 }
 
-// A device buffer freed on scope exit.
-class DeviceBuffer {
- public:
-  DeviceBuffer(pm_handle* h, size_t bytes) : h_(h) { Check(pm_device_malloc(h, bytes, &p_), "pm_device_malloc"); }
-  ~DeviceBuffer() { pm_device_free(h_, p_); }
-  DeviceBuffer(const DeviceBuffer&) = delete;
-  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
-  template <typename T>
-  T* as() { return static_cast<T*>(p_); }
-  void Upload(const void* src, size_t bytes) { Check(pm_upload(h_, p_, src, bytes), "pm_upload"); }
-  void Download(void* dst, size_t bytes) { Check(pm_download(h_, dst, p_, bytes), "pm_download"); }
-
- private:
-  pm_handle* h_;
-  void* p_ = nullptr;
-};
-
 template <typename T>
 size_t Bytes(const Image<T>& im) { return sizeof(T) * (size_t)im.rows * im.cols; }
 
-// The download into an optional output image, which takes the result's size first.
-template <typename T>
-void DownloadInto(DeviceBuffer& d, Image<T>* out, int rows, int cols) {
-  if (out->rows != rows || out->cols != cols) out->create(rows, cols);
-  d.Download(out->data(), Bytes(*out));
+// Any number of device buffers on one handle -- the imaging context's or a matcher's --, freed on every way out.  Check
+// reports with that handle's error text.
+class DeviceBuffers {
+ public:
+  explicit DeviceBuffers(pm_handle* h) : h_(h) {}
+  ~DeviceBuffers() {
+    for (void* q : p_) pm_device_free(h_, q);
+  }
+  DeviceBuffers(const DeviceBuffers&) = delete;
+  DeviceBuffers& operator=(const DeviceBuffers&) = delete;
+  pm_handle* handle() const { return h_; }
+  void Check(int status, const char* what) const { CheckOn(h_, status, what); }
+  template <typename T = void>
+  T* Get(size_t bytes) {
+    p_.push_back(nullptr);  // its place first: the buffer is owned from the moment it exists
+    Check(pm_device_malloc(h_, bytes, &p_.back()), "pm_device_malloc");
+    return static_cast<T*>(p_.back());
+  }
+  template <typename T>
+  T* Put(const void* src, size_t bytes) {
+    T* q = Get<T>(bytes);
+    Check(pm_upload(h_, q, src, bytes), "pm_upload");
+    return q;
+  }
+  // The download into an optional output image, which takes the result's size first.
+  template <typename T>
+  void Fetch(Image<T>* out, const void* d_src, int rows, int cols) const {
+    if (out->rows != rows || out->cols != cols) out->create(rows, cols);
+    Check(pm_download(h_, out->data(), d_src, Bytes(*out)), "pm_download");
+  }
+
+ private:
+  pm_handle* h_;
+  std::vector<void*> p_;
+};
+
+// One of them.
+class DeviceBuffer : private DeviceBuffers {
+ public:
+  DeviceBuffer(pm_handle* h, size_t bytes) : DeviceBuffers(h), p_(Get(bytes)) {}
+  template <typename T>
+  T* as() { return static_cast<T*>(p_); }
+  void Upload(const void* src, size_t bytes) { Check(pm_upload(handle(), p_, src, bytes), "pm_upload"); }
+  void Download(void* dst, size_t bytes) { Check(pm_download(handle(), dst, p_, bytes), "pm_download"); }
+  template <typename T>
+  void DownloadInto(Image<T>* out, int rows, int cols) { Fetch(out, p_, rows, cols); }
+
+ private:
+  void* p_;
+};
+
+pm_motion ToC(const Motion& m) {
+  pm_motion out;
+  for (size_t i = 0; i < 9; ++i) out.R[i] = m.R[i];
+  for (size_t i = 0; i < 3; ++i) out.t[i] = m.t[i];
+  return out;
+}
+
+Motion FromC(const pm_motion& m) {
+  Motion out;
+  for (size_t i = 0; i < 9; ++i) out.R[i] = m.R[i];
+  for (size_t i = 0; i < 3; ++i) out.t[i] = m.t[i];
+  return out;
+}
+
+// The handle of the sequence stages: the matcher's, not the imaging context's.
+pm_handle* MatcherHandle(pm::PatchmatchGpu& matcher, const char* who) {
+  pm_handle* h = matcher.handle();
+  if (!h) throw std::runtime_error(std::string(who) + ": the matcher has no handle yet (plan it or match once)");
+  return h;
 }
 
 void SameSize(int r0, int c0, int r1, int c1, const char* what) {
@@ -183,7 +234,7 @@ float FindDarkFast(const Image1f& intensity, const Image1f& range, float percent
   Check(pm_find_dark(h, d_i.as<float>(), d_r.as<float>(), intensity.rows, intensity.cols, percentile,
                      d_m.as<uint8_t>(), &thr),
         "pm_find_dark");
-  DownloadInto(d_m, &mask, intensity.rows, intensity.cols);
+  d_m.DownloadInto(&mask, intensity.rows, intensity.cols);
   return thr;
 }
 
@@ -272,7 +323,7 @@ Image<Pixel> RectifyImage(const Image<Pixel>& raw, const RectifyView& view, int 
                           d_mask, nullptr),
           "pm_rectify_bgr8");
   d_out.Download(out.data(), Bytes(out));
-  if (valid) DownloadInto(d_valid, valid, rows, cols);
+  if (valid) d_valid.DownloadInto(valid, rows, cols);
   return out;
 }
 
@@ -469,18 +520,13 @@ Motion RelativeMotion(const double T_world_old[16], const double T_world_new[16]
 std::array<int, 2> ReprojectDisparity(pm::PatchmatchGpu& matcher, const StereoModel& model, const Motion& motion,
                                       const float* d_disp, int rows, int cols, float* d_seed_l, float* d_seed_r,
                                       const ReprojectOptions& options, bool want_counts) {
-  pm_handle* h = matcher.handle();
-  if (!h) throw std::runtime_error("ReprojectDisparity: the matcher has no handle yet (plan it or match once)");
+  pm_handle* h = MatcherHandle(matcher, "ReprojectDisparity");
   const pm_cloud_camera cam = CloudCamera(model);
-  pm_motion m;
-  for (size_t i = 0; i < 9; ++i) m.R[i] = motion.R[i];
-  for (size_t i = 0; i < 3; ++i) m.t[i] = motion.t[i];
+  const pm_motion m = ToC(motion);
   const pm_reproject_options opt = {options.min_disp, options.max_disp, options.close_radius};
   int counts[2] = {-1, -1};
-  const int rc = pm_reproject_disparity(h, &cam, &m, &opt, d_disp, rows, cols, d_seed_l, d_seed_r, nullptr,
-                                        want_counts ? counts : nullptr);
-  if (rc != PM_OK)  // the matcher's handle, not the imaging context's
-    throw std::runtime_error(std::string("pm_reproject_disparity: ") + pm_status_string(rc) + " -- " + pm_last_error(h));
+  CheckOn(h, pm_reproject_disparity(h, &cam, &m, &opt, d_disp, rows, cols, d_seed_l, d_seed_r, nullptr, want_counts ? counts : nullptr),
+          "pm_reproject_disparity");
   return {{counts[0], counts[1]}};
 }
 
@@ -488,55 +534,30 @@ std::array<int, 2> FilterConsistency(pm::PatchmatchGpu& matcher, const StereoMod
                                      const std::vector<core::Image<float>>& sources, const std::vector<Motion>& motions,
                                      const ConsistencyOptions& options, const core::Image<float>& disp,
                                      core::Image<float>* out, core::Image<uint16_t>* classes, core::Image<float>* residual) {
-  pm_handle* h = matcher.handle();
-  if (!h) throw std::runtime_error("FilterConsistency: the matcher has no handle yet (plan it or match once)");
-  if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("FilterConsistency: empty map");
+  DeviceBuffers dev(MatcherHandle(matcher, "FilterConsistency"));
+  const int rows = disp.rows, cols = disp.cols;
+  if (rows <= 0 || cols <= 0) throw std::invalid_argument("FilterConsistency: empty map");
   if (sources.size() != motions.size()) throw std::invalid_argument("FilterConsistency: one motion per source");
-  for (const core::Image<float>& s : sources) SameSize(disp.rows, disp.cols, s.rows, s.cols, "FilterConsistency");
-  // the matcher's handle, not the imaging context's: every buffer is freed on every way out
-  struct Buffers {
-    pm_handle* h;
-    std::vector<void*> p;
-    ~Buffers() {
-      for (void* q : p) pm_device_free(h, q);
-    }
-    void Check(int status, const char* what) const {
-      if (status != PM_OK) throw std::runtime_error(std::string(what) + ": " + pm_status_string(status) + " -- " + pm_last_error(h));
-    }
-    void* Get(size_t bytes) {
-      void* q = nullptr;
-      Check(pm_device_malloc(h, bytes, &q), "pm_device_malloc");
-      p.push_back(q);
-      return q;
-    }
-  } dev{h, {}};
-  const size_t px = (size_t)disp.rows * disp.cols;
-  float* d_disp = static_cast<float*>(dev.Get(4 * px));
-  dev.Check(pm_upload(h, d_disp, disp.data(), 4 * px), "pm_upload");
+  for (const core::Image<float>& s : sources) SameSize(rows, cols, s.rows, s.cols, "FilterConsistency");
+  const size_t px = (size_t)rows * cols;
+  float* d_disp = dev.Put<float>(disp.data(), 4 * px);
   std::vector<const float*> d_sources;
-  std::vector<pm_motion> m(motions.size());
+  std::vector<pm_motion> m;
   for (size_t k = 0; k < sources.size(); ++k) {
-    void* q = dev.Get(4 * px);
-    dev.Check(pm_upload(h, q, sources[k].data(), 4 * px), "pm_upload");
-    d_sources.push_back(static_cast<const float*>(q));
-    for (size_t i = 0; i < 9; ++i) m[k].R[i] = motions[k].R[i];
-    for (size_t i = 0; i < 3; ++i) m[k].t[i] = motions[k].t[i];
+    d_sources.push_back(dev.Put<float>(sources[k].data(), 4 * px));
+    m.push_back(ToC(motions[k]));
   }
-  uint16_t* d_classes = classes ? static_cast<uint16_t*>(dev.Get(2 * px)) : nullptr;
-  float* d_residual = residual ? static_cast<float*>(dev.Get(4 * px)) : nullptr;
+  uint16_t* d_classes = classes ? dev.Get<uint16_t>(2 * px) : nullptr;
+  float* d_residual = residual ? dev.Get<float>(4 * px) : nullptr;
   const pm_cloud_camera cam = CloudCamera(model);
   const pm_consistency_options opt = {options.max_diff, options.radius, options.min_consistent, options.max_conflicts};
   int counts[2] = {-1, -1};
-  dev.Check(pm_filter_consistency(h, &cam, &opt, d_disp, (int)sources.size(), d_sources.data(), m.data(), disp.rows, disp.cols,
+  dev.Check(pm_filter_consistency(dev.handle(), &cam, &opt, d_disp, (int)sources.size(), d_sources.data(), m.data(), rows, cols,
                                   out ? d_disp : nullptr /* in place on the device */, d_classes, d_residual, nullptr, counts),
             "pm_filter_consistency");
-  auto fetch = [&](auto* image, const void* d_src, size_t bytes) {
-    if (image->rows != disp.rows || image->cols != disp.cols) image->create(disp.rows, disp.cols);
-    dev.Check(pm_download(h, image->data(), d_src, bytes), "pm_download");
-  };
-  if (out) fetch(out, d_disp, 4 * px);
-  if (classes) fetch(classes, d_classes, 2 * px);
-  if (residual) fetch(residual, d_residual, 4 * px);
+  if (out) dev.Fetch(out, d_disp, rows, cols);
+  if (classes) dev.Fetch(classes, d_classes, rows, cols);
+  if (residual) dev.Fetch(residual, d_residual, rows, cols);
   return {{counts[0], counts[1]}};
 }
 
@@ -544,57 +565,34 @@ std::array<int, 3> DisparityConfidence(pm::PatchmatchGpu& matcher, const core::I
                                        const core::Image<uint8_t>& right, const ConfidenceOptions& options,
                                        const core::Image<float>& disp_l, const core::Image<float>* disp_r,
                                        core::Image<float>* out, ConfidenceMeasures* measures, core::Image<uint8_t>* flags) {
-  pm_handle* h = matcher.handle();
-  if (!h) throw std::runtime_error("DisparityConfidence: the matcher has no handle yet (plan it or match once)");
+  DeviceBuffers dev(MatcherHandle(matcher, "DisparityConfidence"));
   const int rows = disp_l.rows, cols = disp_l.cols;
   if (rows <= 0 || cols <= 0) throw std::invalid_argument("DisparityConfidence: empty map");
   SameSize(rows, cols, left.rows, left.cols, "DisparityConfidence");
   SameSize(rows, cols, right.rows, right.cols, "DisparityConfidence");
   if (disp_r) SameSize(rows, cols, disp_r->rows, disp_r->cols, "DisparityConfidence");
   if (left.step != (size_t)cols || right.step != (size_t)cols) throw std::invalid_argument("DisparityConfidence: the images must be packed");
-  // the matcher's handle, not the imaging context's: every buffer is freed on every way out
-  struct Buffers {
-    pm_handle* h;
-    std::vector<void*> p;
-    ~Buffers() {
-      for (void* q : p) pm_device_free(h, q);
-    }
-    void Check(int status, const char* what) const {
-      if (status != PM_OK) throw std::runtime_error(std::string(what) + ": " + pm_status_string(status) + " -- " + pm_last_error(h));
-    }
-    void* Put(const void* src, size_t bytes) {
-      void* q = nullptr;
-      Check(pm_device_malloc(h, bytes, &q), "pm_device_malloc");
-      p.push_back(q);
-      if (src) Check(pm_upload(h, q, src, bytes), "pm_upload");
-      return q;
-    }
-  } dev{h, {}};
   const size_t px = (size_t)rows * cols;
-  const uint8_t* d_left = static_cast<const uint8_t*>(dev.Put(left.data(), px));
-  const uint8_t* d_right = static_cast<const uint8_t*>(dev.Put(right.data(), px));
-  float* d_disp = static_cast<float*>(dev.Put(disp_l.data(), 4 * px));
-  const float* d_disp_r = disp_r ? static_cast<const float*>(dev.Put(disp_r->data(), 4 * px)) : nullptr;
-  float* d_measures = measures ? static_cast<float*>(dev.Put(nullptr, 16 * px)) : nullptr;
-  uint8_t* d_flags = flags ? static_cast<uint8_t*>(dev.Put(nullptr, px)) : nullptr;
+  const uint8_t* d_left = dev.Put<uint8_t>(left.data(), px);
+  const uint8_t* d_right = dev.Put<uint8_t>(right.data(), px);
+  float* d_disp = dev.Put<float>(disp_l.data(), 4 * px);
+  const float* d_disp_r = disp_r ? dev.Put<float>(disp_r->data(), 4 * px) : nullptr;
+  float* d_measures = measures ? dev.Get<float>(16 * px) : nullptr;
+  uint8_t* d_flags = flags ? dev.Get<uint8_t>(px) : nullptr;
   const pm_confidence_options opt = {options.patch_w,    options.patch_h,     options.max_cost,           options.min_margin,
                                      options.min_bg_margin, options.max_lr_diff, options.drop_unmeasured ? 1 : 0};
   int counts[3] = {-1, -1, -1};
-  dev.Check(pm_disparity_confidence(h, &opt, d_left, d_right, d_disp, d_disp_r, rows, cols,
+  dev.Check(pm_disparity_confidence(dev.handle(), &opt, d_left, d_right, d_disp, d_disp_r, rows, cols,
                                     out ? d_disp : nullptr /* in place on the device */, d_measures, d_flags, nullptr, counts),
             "pm_disparity_confidence");
-  auto fetch = [&](auto* image, const void* d_src, size_t bytes) {
-    if (image->rows != rows || image->cols != cols) image->create(rows, cols);
-    dev.Check(pm_download(h, image->data(), d_src, bytes), "pm_download");
-  };
-  if (out) fetch(out, d_disp, 4 * px);
+  if (out) dev.Fetch(out, d_disp, rows, cols);
   if (measures) {
-    fetch(&measures->cost, d_measures, 4 * px);
-    fetch(&measures->margin, d_measures + px, 4 * px);
-    fetch(&measures->bg_margin, d_measures + 2 * px, 4 * px);
-    fetch(&measures->lr, d_measures + 3 * px, 4 * px);
+    dev.Fetch(&measures->cost, d_measures, rows, cols);
+    dev.Fetch(&measures->margin, d_measures + px, rows, cols);
+    dev.Fetch(&measures->bg_margin, d_measures + 2 * px, rows, cols);
+    dev.Fetch(&measures->lr, d_measures + 3 * px, rows, cols);
   }
-  if (flags) fetch(flags, d_flags, px);
+  if (flags) dev.Fetch(flags, d_flags, rows, cols);
   return {{counts[0], counts[1], counts[2]}};
 }
 
@@ -603,8 +601,7 @@ std::array<int, 4> FuseDisparity(pm::PatchmatchGpu& matcher, const StereoModel& 
                                  const FuseOptions& options, const core::Image<float>& disp, const core::Image<float>* weight,
                                  const std::vector<core::Image<float>>& source_weights, core::Image<float>* out,
                                  core::Image<uint8_t>* count, core::Image<float>* spread, core::Image<uint8_t>* flags) {
-  pm_handle* h = matcher.handle();
-  if (!h) throw std::runtime_error("FuseDisparity: the matcher has no handle yet (plan it or match once)");
+  DeviceBuffers dev(MatcherHandle(matcher, "FuseDisparity"));
   const int rows = disp.rows, cols = disp.cols;
   if (rows <= 0 || cols <= 0) throw std::invalid_argument("FuseDisparity: empty map");
   if (sources.size() != motions.size()) throw std::invalid_argument("FuseDisparity: one motion per source");
@@ -614,55 +611,32 @@ std::array<int, 4> FuseDisparity(pm::PatchmatchGpu& matcher, const StereoModel& 
   if (weight) SameSize(rows, cols, weight->rows, weight->cols, "FuseDisparity");
   for (const core::Image<float>& w : source_weights)
     if (w.rows != 0 || w.cols != 0) SameSize(rows, cols, w.rows, w.cols, "FuseDisparity");
-  // the matcher's handle, not the imaging context's: every buffer is freed on every way out
-  struct Buffers {
-    pm_handle* h;
-    std::vector<void*> p;
-    ~Buffers() {
-      for (void* q : p) pm_device_free(h, q);
-    }
-    void Check(int status, const char* what) const {
-      if (status != PM_OK) throw std::runtime_error(std::string(what) + ": " + pm_status_string(status) + " -- " + pm_last_error(h));
-    }
-    void* Put(const void* src, size_t bytes) {
-      void* q = nullptr;
-      Check(pm_device_malloc(h, bytes, &q), "pm_device_malloc");
-      p.push_back(q);
-      if (src) Check(pm_upload(h, q, src, bytes), "pm_upload");
-      return q;
-    }
-  } dev{h, {}};
   const size_t px = (size_t)rows * cols;
-  float* d_disp = static_cast<float*>(dev.Put(disp.data(), 4 * px));
-  const float* d_weight = weight ? static_cast<const float*>(dev.Put(weight->data(), 4 * px)) : nullptr;
+  float* d_disp = dev.Put<float>(disp.data(), 4 * px);
+  const float* d_weight = weight ? dev.Put<float>(weight->data(), 4 * px) : nullptr;
   std::vector<const float*> d_sources, d_weights;
-  std::vector<pm_motion> m(motions.size());
+  std::vector<pm_motion> m;
   for (size_t k = 0; k < sources.size(); ++k) {
-    d_sources.push_back(static_cast<const float*>(dev.Put(sources[k].data(), 4 * px)));
+    d_sources.push_back(dev.Put<float>(sources[k].data(), 4 * px));
     const bool has = !source_weights.empty() && source_weights[k].rows != 0;
-    d_weights.push_back(has ? static_cast<const float*>(dev.Put(source_weights[k].data(), 4 * px)) : nullptr);
-    for (size_t i = 0; i < 9; ++i) m[k].R[i] = motions[k].R[i];
-    for (size_t i = 0; i < 3; ++i) m[k].t[i] = motions[k].t[i];
+    d_weights.push_back(has ? dev.Put<float>(source_weights[k].data(), 4 * px) : nullptr);
+    m.push_back(ToC(motions[k]));
   }
-  uint8_t* d_count = count ? static_cast<uint8_t*>(dev.Put(nullptr, px)) : nullptr;
-  float* d_spread = spread ? static_cast<float*>(dev.Put(nullptr, 4 * px)) : nullptr;
-  uint8_t* d_flags = flags ? static_cast<uint8_t*>(dev.Put(nullptr, px)) : nullptr;
+  uint8_t* d_count = count ? dev.Get<uint8_t>(px) : nullptr;
+  float* d_spread = spread ? dev.Get<float>(4 * px) : nullptr;
+  uint8_t* d_flags = flags ? dev.Get<uint8_t>(px) : nullptr;
   const pm_cloud_camera cam = CloudCamera(model);
   const pm_fuse_options opt = {options.max_diff,      options.radius,           options.min_consistent,
                                options.max_conflicts, options.fill_min_sources, options.fill_max_diff};
   int counts[4] = {-1, -1, -1, -1};
-  dev.Check(pm_fuse_disparity(h, &cam, &opt, d_disp, d_weight, (int)sources.size(), d_sources.data(), m.data(),
+  dev.Check(pm_fuse_disparity(dev.handle(), &cam, &opt, d_disp, d_weight, (int)sources.size(), d_sources.data(), m.data(),
                               source_weights.empty() ? nullptr : d_weights.data(), rows, cols,
                               out ? d_disp : nullptr /* in place on the device */, d_count, d_spread, d_flags, nullptr, counts),
             "pm_fuse_disparity");
-  auto fetch = [&](auto* image, const void* d_src, size_t bytes) {
-    if (image->rows != rows || image->cols != cols) image->create(rows, cols);
-    dev.Check(pm_download(h, image->data(), d_src, bytes), "pm_download");
-  };
-  if (out) fetch(out, d_disp, 4 * px);
-  if (count) fetch(count, d_count, px);
-  if (spread) fetch(spread, d_spread, 4 * px);
-  if (flags) fetch(flags, d_flags, px);
+  if (out) dev.Fetch(out, d_disp, rows, cols);
+  if (count) dev.Fetch(count, d_count, rows, cols);
+  if (spread) dev.Fetch(spread, d_spread, rows, cols);
+  if (flags) dev.Fetch(flags, d_flags, rows, cols);
   return {{counts[0], counts[1], counts[2], counts[3]}};
 }
 
@@ -670,50 +644,25 @@ namespace {
 // The two frames of a motion estimate on the matcher's handle (not the imaging context's); every buffer is freed on every way
 // out.
 struct MotionFrames {
-  pm_handle* h;
-  std::vector<void*> p;
+  DeviceBuffers dev;
+  pm_handle* const h;
   const uint8_t *old = nullptr, *img = nullptr;
   const float* disp = nullptr;
-  pm_cloud_camera cam;
-  pm_track_options opt;
-  pm_motion guess;
+  const pm_cloud_camera cam;
+  const pm_track_options opt;
+  const pm_motion guess;
   MotionFrames(pm::PatchmatchGpu& matcher, const char* who, const StereoModel& model, const TrackOptions& o, const Motion* g,
                const core::Image<uint8_t>& left_old, const core::Image<float>& disp_old, const core::Image<uint8_t>& left_new)
-      : h(matcher.handle()), cam(CloudCamera(model)),
-        opt{o.cell, o.patch_radius, o.search_radius, o.min_score, o.min_disp, o.max_disp, o.max_sad, o.min_gap} {
-    if (!h) throw std::runtime_error(std::string(who) + ": the matcher has no handle yet (plan it or match once)");
+      : dev(MatcherHandle(matcher, who)), h(dev.handle()), cam(CloudCamera(model)),
+        opt{o.cell, o.patch_radius, o.search_radius, o.min_score, o.min_disp, o.max_disp, o.max_sad, o.min_gap},
+        guess(ToC(g ? *g : Motion())) {
     SameSize(left_old.rows, left_old.cols, disp_old.rows, disp_old.cols, who);
     SameSize(left_old.rows, left_old.cols, left_new.rows, left_new.cols, who);
-    const Motion start = g ? *g : Motion();
-    for (size_t i = 0; i < 9; ++i) guess.R[i] = start.R[i];
-    for (size_t i = 0; i < 3; ++i) guess.t[i] = start.t[i];
-    old = static_cast<const uint8_t*>(Put(left_old.data(), Bytes(left_old)));
-    disp = static_cast<const float*>(Put(disp_old.data(), Bytes(disp_old)));
-    img = static_cast<const uint8_t*>(Put(left_new.data(), Bytes(left_new)));
-  }
-  ~MotionFrames() {
-    for (void* q : p) pm_device_free(h, q);
-  }
-  MotionFrames(const MotionFrames&) = delete;
-  MotionFrames& operator=(const MotionFrames&) = delete;
-  void Check(int status, const char* what) const {
-    if (status != PM_OK) throw std::runtime_error(std::string(what) + ": " + pm_status_string(status) + " -- " + pm_last_error(h));
-  }
-  void* Put(const void* src, size_t bytes) {
-    void* q = nullptr;
-    Check(pm_device_malloc(h, bytes, &q), "pm_device_malloc");
-    p.push_back(q);
-    if (src) Check(pm_upload(h, q, src, bytes), "pm_upload");
-    return q;
+    old = dev.Put<uint8_t>(left_old.data(), Bytes(left_old));
+    disp = dev.Put<float>(disp_old.data(), Bytes(disp_old));
+    img = dev.Put<uint8_t>(left_new.data(), Bytes(left_new));
   }
 };
-
-Motion FromC(const pm_motion& m) {
-  Motion out;
-  for (size_t i = 0; i < 9; ++i) out.R[i] = m.R[i];
-  for (size_t i = 0; i < 3; ++i) out.t[i] = m.t[i];
-  return out;
-}
 }  // namespace
 
 std::vector<pm_track> TrackFeatures(pm::PatchmatchGpu& matcher, const StereoModel& model, const TrackOptions& options,
@@ -724,12 +673,12 @@ std::vector<pm_track> TrackFeatures(pm::PatchmatchGpu& matcher, const StereoMode
   // at most one feature per cell: room for all of them without a counting call in front
   const int cell = options.cell > 0 ? options.cell : 1;
   const int capacity = ((rows + cell - 1) / cell) * ((cols + cell - 1) / cell);
-  pm_track* d_tracks = static_cast<pm_track*>(f.Put(nullptr, sizeof(pm_track) * (size_t)capacity));
+  pm_track* d_tracks = f.dev.Get<pm_track>(sizeof(pm_track) * (size_t)capacity);
   int count = -1;
-  f.Check(pm_track_features(f.h, &f.cam, &f.opt, &f.guess, f.old, f.disp, f.img, rows, cols, capacity, d_tracks, nullptr, &count),
-          "pm_track_features");
+  f.dev.Check(pm_track_features(f.h, &f.cam, &f.opt, &f.guess, f.old, f.disp, f.img, rows, cols, capacity, d_tracks, nullptr, &count),
+              "pm_track_features");
   std::vector<pm_track> tracks((size_t)count);
-  if (count > 0) f.Check(pm_download(f.h, tracks.data(), d_tracks, sizeof(pm_track) * tracks.size()), "pm_download");
+  if (count > 0) f.dev.Check(pm_download(f.h, tracks.data(), d_tracks, sizeof(pm_track) * tracks.size()), "pm_download");
   return tracks;
 }
 
@@ -737,10 +686,8 @@ Motion SolveMotion(const StereoModel& model, const SolveOptions& options, const 
                    pm_motion_info* info) {
   const pm_cloud_camera cam = CloudCamera(model);
   const pm_solve_options opt = {options.iterations, options.huber_px, options.epsilon, options.inlier_px, options.min_inliers};
-  const Motion start = guess ? *guess : Motion();
-  pm_motion g, out;
-  for (size_t i = 0; i < 9; ++i) g.R[i] = start.R[i];
-  for (size_t i = 0; i < 3; ++i) g.t[i] = start.t[i];
+  const pm_motion g = ToC(guess ? *guess : Motion());
+  pm_motion out;
   pm_motion_info local;
   const int rc = pm_solve_motion(&cam, &opt, tracks.data(), (int)tracks.size(), &g, &out, info ? info : &local);
   if (rc != PM_OK) throw std::runtime_error(std::string("pm_solve_motion: ") + pm_status_string(rc));
@@ -755,9 +702,9 @@ Motion EstimateMotion(pm::PatchmatchGpu& matcher, const StereoModel& model, cons
                                 solve_options.min_inliers};
   pm_motion out;
   pm_motion_info local;
-  f.Check(pm_estimate_motion(f.h, &f.cam, &f.opt, &opt, &f.guess, f.old, f.disp, f.img, left_old.rows, left_old.cols, &out,
-                             info ? info : &local),
-          "pm_estimate_motion");
+  f.dev.Check(pm_estimate_motion(f.h, &f.cam, &f.opt, &opt, &f.guess, f.old, f.disp, f.img, left_old.rows, left_old.cols, &out,
+                                 info ? info : &local),
+              "pm_estimate_motion");
   return FromC(out);
 }
 
@@ -776,7 +723,7 @@ core::Image<core::Vec3f> DisparityNormals(const core::Image<float>& disp, const 
                              support ? d_sup.as<uint8_t>() : nullptr),
         "pm_disparity_normals");
   d_out.Download(out.data(), Bytes(out));
-  if (support) DownloadInto(d_sup, support, disp.rows, disp.cols);
+  if (support) d_sup.DownloadInto(support, disp.rows, disp.cols);
   return out;
 }
 
@@ -794,7 +741,7 @@ core::Image<float> FilterSpeckles(const core::Image<float>& disp, const SpeckleF
                            labels ? d_lab.as<int32_t>() : nullptr, nullptr, nullptr, removed),
         "pm_filter_speckles");
   d_map.Download(out.data(), Bytes(out));
-  if (labels) DownloadInto(d_lab, labels, disp.rows, disp.cols);
+  if (labels) d_lab.DownloadInto(labels, disp.rows, disp.cols);
   return out;
 }
 
@@ -804,55 +751,27 @@ core::Image<core::Vec3f> PlaneNormals(pm::PatchmatchGpu& matcher, const StereoMo
   if (!h) throw std::runtime_error("PlaneNormals: the matcher has not matched yet");
   if (rows <= 0 || cols <= 0) throw std::invalid_argument("PlaneNormals: empty size");
   if (disp_l) SameSize(rows, cols, disp_l->rows, disp_l->cols, "PlaneNormals");
-  auto check = [h](int status, const char* what) {  // the matcher's handle, not the imaging context's
-    if (status != PM_OK) throw std::runtime_error(std::string(what) + ": " + pm_status_string(status) + " -- " + pm_last_error(h));
-  };
+  DeviceBuffers dev(h);  // the matcher's handle, not the imaging context's
   core::Image<core::Vec3f> out(rows, cols);
-  void *d_out = nullptr, *d_mask = nullptr;
-  check(pm_device_malloc(h, Bytes(out), &d_out), "pm_device_malloc");
-  int rc = PM_OK;
-  if (disp_l) {
-    rc = pm_device_malloc(h, Bytes(*disp_l), &d_mask);
-    if (rc == PM_OK) rc = pm_upload(h, d_mask, disp_l->data(), Bytes(*disp_l));
-  }
+  float* d_out = dev.Get<float>(Bytes(out));
+  const float* d_mask = disp_l ? dev.Put<float>(disp_l->data(), Bytes(*disp_l)) : nullptr;
   const pm_cloud_camera cam = CloudCamera(model);
-  const char* what = "pm_planes_normals";
-  if (rc == PM_OK) rc = pm_planes_normals(h, 0, &cam, static_cast<const float*>(d_mask), rows, cols, static_cast<float*>(d_out));
-  if (rc == PM_OK) {
-    rc = pm_download(h, out.data(), d_out, Bytes(out));
-    what = "pm_download";
-  }
-  std::string error;
-  if (rc != PM_OK) error = std::string(what) + ": " + pm_status_string(rc) + " -- " + pm_last_error(h);
-  pm_device_free(h, d_mask);
-  pm_device_free(h, d_out);
-  if (rc != PM_OK) throw std::runtime_error(error);
+  dev.Check(pm_planes_normals(h, 0, &cam, d_mask, rows, cols, d_out), "pm_planes_normals");
+  dev.Fetch(&out, d_out, rows, cols);
   return out;
 }
 
-// ---- TsdfVolume: the device memory is a DeviceBuffer on the matcher's handle ---------------------------------------------------
+// ---- TsdfVolume: the device memory is on the matcher's handle, and so is every call -------------------------------------------
 struct TsdfVolume::Impl {
-  pm_handle* h;
-  pm_tsdf_volume volume;
-  DeviceBuffer voxels;
-  Impl(pm_handle* handle, const pm_tsdf_volume& v, size_t bytes) : h(handle), volume(v), voxels(handle, bytes) {}
-  void Check(int status, const char* what) const {  // the matcher's handle, not the imaging context's
-    if (status != PM_OK) throw std::runtime_error(std::string(what) + ": " + pm_status_string(status) + " -- " + pm_last_error(h));
-  }
+  DeviceBuffers dev;
+  pm_handle* const h;
+  const pm_tsdf_volume volume;
+  void* const voxels;
+  Impl(pm_handle* handle, const pm_tsdf_volume& v, size_t bytes) : dev(handle), h(handle), volume(v), voxels(dev.Get(bytes)) {}
 };
 
-namespace {
-pm_motion ToMotion(const Motion& m) {
-  pm_motion out;
-  for (size_t i = 0; i < 9; ++i) out.R[i] = m.R[i];
-  for (size_t i = 0; i < 3; ++i) out.t[i] = m.t[i];
-  return out;
-}
-}  // namespace
-
 TsdfVolume::TsdfVolume(pm::PatchmatchGpu& matcher, const TsdfGrid& grid) : grid_(grid) {
-  pm_handle* h = matcher.handle();
-  if (!h) throw std::runtime_error("TsdfVolume: the matcher has no handle yet (plan it or match once)");
+  pm_handle* h = MatcherHandle(matcher, "TsdfVolume");
   const pm_tsdf_volume v = {grid.nx, grid.ny, grid.nz, {grid.origin[0], grid.origin[1], grid.origin[2]}, grid.voxel, grid.trunc,
                             grid.max_weight};
   const size_t bytes = pm_tsdf_bytes(&v);
@@ -863,20 +782,20 @@ TsdfVolume::TsdfVolume(pm::PatchmatchGpu& matcher, const TsdfGrid& grid) : grid_
 
 TsdfVolume::~TsdfVolume() = default;
 
-void* TsdfVolume::device() { return impl_->voxels.as<void>(); }
+void* TsdfVolume::device() { return impl_->voxels; }
 
-void TsdfVolume::Clear() { impl_->Check(pm_tsdf_clear(impl_->h, &impl_->volume, device()), "pm_tsdf_clear"); }
+void TsdfVolume::Clear() { impl_->dev.Check(pm_tsdf_clear(impl_->h, &impl_->volume, device()), "pm_tsdf_clear"); }
 
 std::array<int, 2> TsdfVolume::IntegrateDevice(const StereoModel& model, const Motion& pose, const float* d_disp,
                                                const float* d_weight, int rows, int cols, const TsdfIntegrateOptions& options,
                                                bool want_counts) {
   const pm_cloud_camera cam = CloudCamera(model);
-  const pm_motion m = ToMotion(pose);
+  const pm_motion m = ToC(pose);
   const pm_tsdf_integrate_options opt = {options.min_disp, options.max_range};
   int counts[2] = {-1, -1};
-  impl_->Check(pm_tsdf_integrate(impl_->h, &cam, &impl_->volume, &m, &opt, d_disp, d_weight, rows, cols, device(), nullptr,
-                                 want_counts ? counts : nullptr),
-               "pm_tsdf_integrate");
+  impl_->dev.Check(pm_tsdf_integrate(impl_->h, &cam, &impl_->volume, &m, &opt, d_disp, d_weight, rows, cols, device(), nullptr,
+                                     want_counts ? counts : nullptr),
+                   "pm_tsdf_integrate");
   return {{counts[0], counts[1]}};
 }
 
@@ -884,26 +803,22 @@ std::array<int, 2> TsdfVolume::Integrate(const StereoModel& model, const Motion&
                                          const core::Image<float>* weight, const TsdfIntegrateOptions& options) {
   if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("TsdfVolume::Integrate: empty map");
   if (weight) SameSize(disp.rows, disp.cols, weight->rows, weight->cols, "TsdfVolume::Integrate");
-  DeviceBuffer d_disp(impl_->h, Bytes(disp));
-  impl_->Check(pm_upload(impl_->h, d_disp.as<void>(), disp.data(), Bytes(disp)), "pm_upload");
-  std::unique_ptr<DeviceBuffer> d_weight;
-  if (weight) {
-    d_weight.reset(new DeviceBuffer(impl_->h, Bytes(*weight)));
-    impl_->Check(pm_upload(impl_->h, d_weight->as<void>(), weight->data(), Bytes(*weight)), "pm_upload");
-  }
-  return IntegrateDevice(model, pose, d_disp.as<float>(), d_weight ? d_weight->as<float>() : nullptr, disp.rows, disp.cols, options,
+  DeviceBuffers dev(impl_->h);
+  const float* d_disp = dev.Put<float>(disp.data(), Bytes(disp));
+  const float* d_weight = weight ? dev.Put<float>(weight->data(), Bytes(*weight)) : nullptr;
+  return IntegrateDevice(model, pose, d_disp, d_weight, disp.rows, disp.cols, options,
                          /*want_counts=*/true);  // synchronises: the buffers may go
 }
 
 int TsdfVolume::RaycastDevice(const StereoModel& model, const Motion& pose, int rows, int cols, float* d_disp_out,
                               float* d_normals_out, const TsdfRaycastOptions& options, bool want_counts) {
   const pm_cloud_camera cam = CloudCamera(model);
-  const pm_motion m = ToMotion(pose);
+  const pm_motion m = ToC(pose);
   const pm_tsdf_raycast_options opt = {options.min_range, options.max_range, options.step, options.min_weight};
   int hits = -1;
-  impl_->Check(pm_tsdf_raycast(impl_->h, &cam, &impl_->volume, &m, &opt, device(), rows, cols, d_disp_out, d_normals_out, nullptr,
-                               want_counts ? &hits : nullptr),
-               "pm_tsdf_raycast");
+  impl_->dev.Check(pm_tsdf_raycast(impl_->h, &cam, &impl_->volume, &m, &opt, device(), rows, cols, d_disp_out, d_normals_out, nullptr,
+                                   want_counts ? &hits : nullptr),
+                   "pm_tsdf_raycast");
   return hits;
 }
 
@@ -911,25 +826,18 @@ int TsdfVolume::Raycast(const StereoModel& model, const Motion& pose, int rows, 
                         core::Image<core::Vec3f>* normals, const TsdfRaycastOptions& options) {
   if (rows <= 0 || cols <= 0) throw std::invalid_argument("TsdfVolume::Raycast: empty size");
   const size_t px = (size_t)rows * cols;
-  std::unique_ptr<DeviceBuffer> d_disp, d_normals;
-  if (disp) d_disp.reset(new DeviceBuffer(impl_->h, 4 * px));
-  if (normals) d_normals.reset(new DeviceBuffer(impl_->h, 12 * px));
-  const int hits = RaycastDevice(model, pose, rows, cols, d_disp ? d_disp->as<float>() : nullptr,
-                                 d_normals ? d_normals->as<float>() : nullptr, options, /*want_counts=*/true);
-  if (disp) {
-    if (disp->rows != rows || disp->cols != cols) disp->create(rows, cols);
-    impl_->Check(pm_download(impl_->h, disp->data(), d_disp->as<void>(), 4 * px), "pm_download");
-  }
-  if (normals) {
-    if (normals->rows != rows || normals->cols != cols) normals->create(rows, cols);
-    impl_->Check(pm_download(impl_->h, normals->data(), d_normals->as<void>(), 12 * px), "pm_download");
-  }
+  DeviceBuffers dev(impl_->h);
+  float* d_disp = disp ? dev.Get<float>(4 * px) : nullptr;
+  float* d_normals = normals ? dev.Get<float>(12 * px) : nullptr;
+  const int hits = RaycastDevice(model, pose, rows, cols, d_disp, d_normals, options, /*want_counts=*/true);
+  if (disp) dev.Fetch(disp, d_disp, rows, cols);
+  if (normals) dev.Fetch(normals, d_normals, rows, cols);
   return hits;
 }
 
 std::vector<float> TsdfVolume::Download() {
   std::vector<float> out(2 * voxels());
-  impl_->Check(pm_download(impl_->h, out.data(), device(), sizeof(float) * out.size()), "pm_download");
+  impl_->dev.Check(pm_download(impl_->h, out.data(), device(), sizeof(float) * out.size()), "pm_download");
   return out;
 }
 
