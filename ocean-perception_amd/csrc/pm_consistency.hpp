@@ -23,9 +23,7 @@
 
 namespace pm {
 
-constexpr int kConsistencyBlockX = 64;  // one wavefront along a row (256 pixels) ...
-constexpr int kConsistencyBlockY = 4;   // ... and rows per block
-constexpr int kConsistencySpan = kConsistencyLanes * kConsistencyPixelsPerLane;  // pixels of a row per block
+// the launch shape (kConsistencyBlockX / Y, kConsistencySpan) is pm_consistency_body.hpp's, where a CPU build reads it too
 static_assert(kConsistencyBlockX == kConsistencyLanes, "threadIdx.y is the wavefront");
 static_assert(sizeof(ConsistencyArgs) <= 1024, "the by-value argument stays under 1 KB");
 

@@ -19,6 +19,9 @@ constexpr int kConsistencyMaxSources = PM_CONSISTENCY_MAX_SOURCES;
 constexpr int kConsistencyMaxRadius = 2;
 constexpr int kConsistencyLanes = kReprojectLanes;                  // a wavefront takes 64 consecutive pixels of a row ...
 constexpr int kConsistencyPixelsPerLane = kReprojectPixelsPerLane;  // ... four times, 64 pixels apart (k_reproject_splat's shape)
+constexpr int kConsistencyBlockX = kReprojectBlockX;                // k_consistency's block: one wavefront along a row ...
+constexpr int kConsistencyBlockY = kReprojectBlockY;                // ... and rows per block; its grid is span_blocks()
+constexpr int kConsistencySpan = kReprojectSpan;                    // pixels of a row per block
 
 enum : unsigned { kConsistencyUnseen = 0, kConsistencyConsistent = 1, kConsistencyOccluded = 2, kConsistencyConflict = 3 };
 

@@ -25,10 +25,7 @@
 
 namespace pm {
 
-constexpr int kFuseBlockX = 64;  // one wavefront along a row (256 pixels) ...
-constexpr int kFuseBlockY = 4;   // ... and rows per block
-constexpr int kFuseSpan = kFuseLanes * kFusePixelsPerLane;  // pixels of a row per block
-constexpr int kFuseCounters = 4;                            // valid, kept, fused, filled
+// the launch shape (kFuseBlockX / Y, kFuseSpan) and kFuseCounters are pm_fuse_body.hpp's, where a CPU build reads them too
 static_assert(kFuseBlockX == kFuseLanes, "threadIdx.y is the wavefront");
 static_assert(sizeof(FuseArgs) <= 1088 && sizeof(FuseSplatArgs) <= 1024, "the by-value arguments stay near 1 KB");
 

@@ -19,6 +19,10 @@ constexpr int kFuseMaxSources = kConsistencyMaxSources;
 constexpr int kFuseMaxRadius = kConsistencyMaxRadius;
 constexpr int kFuseLanes = kConsistencyLanes;                  // a wavefront takes 64 consecutive pixels of a row ...
 constexpr int kFusePixelsPerLane = kConsistencyPixelsPerLane;  // ... four times, 64 pixels apart (k_consistency's shape)
+constexpr int kFuseBlockX = kConsistencyBlockX;                // the block of both kernels: one wavefront along a row ...
+constexpr int kFuseBlockY = kConsistencyBlockY;                // ... and rows per block; their grid is span_blocks()
+constexpr int kFuseSpan = kConsistencySpan;                    // pixels of a row per block
+constexpr int kFuseCounters = 4;                               // valid, kept, fused, filled: kFusePixelsPerLane bits of fuse_lane's flags each
 
 enum : unsigned { kFuseValid = 1, kFuseKept = 2, kFuseFused = 4, kFuseFilled = 8 };  // PM_FUSE_*
 

@@ -23,9 +23,7 @@
 
 namespace pm {
 
-constexpr int kReprojectBlockX = 64;  // splat launches: one wavefront along a row (256 pixels) ...
-constexpr int kReprojectBlockY = 4;   // ... and rows per block; the finish launch: 64 x 4 threads per 64 x 16 tile
-constexpr int kReprojectSpan = kReprojectLanes * kReprojectPixelsPerLane;  // pixels of a row per splat block
+// the launch shapes (kReprojectBlockX / Y, kReprojectSpan) are pm_reproject_body.hpp's, where a CPU build reads them too
 static_assert(kReprojectBlockX == kReprojectTileW && kReprojectTileH % kReprojectBlockY == 0, "a wavefront per tile row");
 static_assert(kReprojectBlockX == kReprojectLanes, "threadIdx.y is the wavefront");
 

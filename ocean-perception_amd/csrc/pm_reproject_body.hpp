@@ -40,6 +40,19 @@ __host__ __device__ __forceinline__ void reproject_add(int* word, int n) {
 
 constexpr int kReprojectLanes = 64;         // splat launches: a wavefront takes 64 consecutive pixels of a row at a time ...
 constexpr int kReprojectPixelsPerLane = 4;  // ... four times, 64 pixels apart: 256 pixels of a row per wavefront
+constexpr int kReprojectBlockX = 64;        // splat launches: one wavefront along a row (256 pixels) ...
+constexpr int kReprojectBlockY = 4;         // ... and rows per block; the finish launch: 64 x 4 threads per 64 x 16 tile
+constexpr int kReprojectSpan = kReprojectLanes * kReprojectPixelsPerLane;  // pixels of a row per splat block
+
+// The grid of the row-span launches (the seeds' splats here, the consistency filter and the fusion, whose constants are aliases
+// of these): a block takes kReprojectSpan pixels of a row and kReprojectBlockY rows.  The one statement of it, for the launches
+// (pm_stages.hip: span_grid) and for a CPU build that walks them (tests/cpp/host_launch.hpp).
+struct SpanBlocks {
+  unsigned x, y;  // blocks along a row, blocks down the rows
+};
+inline SpanBlocks span_blocks(int rows, int cols) {
+  return SpanBlocks{(unsigned)((cols + kReprojectSpan - 1) / kReprojectSpan), (unsigned)((rows + kReprojectBlockY - 1) / kReprojectBlockY)};
+}
 
 // ---- stage 1: the old left map into the new left view -----------------------------------------------------------------------
 struct ReprojectArgs {

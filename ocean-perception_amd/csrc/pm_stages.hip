@@ -175,12 +175,10 @@ void set_motion(double R[9], double t[3], const pm_motion* m) {
 }
 
 // The grid of the three launches that give a block 256 pixels of a row and four rows (the seeds' splats, the consistency
-// filter, the fusion); the kernels keep their own constants.
-static_assert(kReprojectSpan == kConsistencySpan && kConsistencySpan == kFuseSpan && kReprojectBlockY == kConsistencyBlockY &&
-                  kConsistencyBlockY == kFuseBlockY,
-              "one row-span launch shape");
+// filter, the fusion): pm_reproject_body.hpp states it once, and the other two stages' constants are aliases of it.
 dim3 span_grid(int rows, int cols) {
-  return dim3((unsigned)((cols + kFuseSpan - 1) / kFuseSpan), (unsigned)((rows + kFuseBlockY - 1) / kFuseBlockY));
+  const SpanBlocks blocks = span_blocks(rows, cols);
+  return dim3(blocks.x, blocks.y);
 }
 
 // the cloud and the mesh: a compacted stream is gathered from its organised input

@@ -24,8 +24,7 @@
 
 namespace pm {
 
-constexpr int kTsdfBlockX = kTsdfLanes;  // threadIdx.y is the wavefront
-constexpr int kTsdfBlockY = kTsdfWaves;
+// the block (kTsdfBlockX, kTsdfBlockY) is pm_tsdf_body.hpp's, where a CPU build reads it too
 constexpr unsigned kTsdfMaxBlocks = 1u << 20;  // of k_tsdf_integrate: the stride loop takes the rest
 static_assert(sizeof(TsdfIntegrateArgs) <= 320 && sizeof(TsdfRaycastArgs) <= 384, "the by-value arguments stay small");
 

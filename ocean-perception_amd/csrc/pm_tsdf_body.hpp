@@ -18,6 +18,8 @@ namespace pm {
 
 constexpr int kTsdfLanes = 64;  // k_tsdf_integrate: a wavefront owns 64 consecutive voxels along x; k_tsdf_raycast: 64 pixels of a row
 constexpr int kTsdfWaves = 4;   // wavefronts per block of either kernel
+constexpr int kTsdfBlockX = kTsdfLanes;  // the block of either kernel: threadIdx.y is the wavefront
+constexpr int kTsdfBlockY = kTsdfWaves;
 
 // One voxel: 8 bytes.  weight == 0: never observed.
 struct alignas(8) TsdfVoxel {

@@ -1,45 +1,37 @@
 // cloud_host_main.cpp -- runs the point-cloud stages' own per-thread code (csrc/pm_cloud_body.hpp: backproject_four,
 // cloud_item, cloud_store, cloud_normal -- the bodies of the kernels of csrc/pm_cloud.hpp and of k_planes_normals) on the
 // HOST, so that tests/test_pointcloud.py can hold it to the definition (tests/pointcloud_ref.py) without a GPU and under
-// -fsanitize=address,undefined.  Every buffer is a heap
-// allocation of EXACTLY the bytes the stage may touch: a load past the last disparity, or a store behind slot
-// min(count, capacity) - 1, is reported.  Compiled as HIP source with the host-only switch of hipcc and -ffp-contract=off.
+// -fsanitize=address,undefined.  Every buffer is a heap allocation of EXACTLY the bytes the stage may touch: a load past the
+// last disparity, or a store behind slot min(count, capacity) - 1, is reported.  Compiled as HIP source with the host-only
+// switch of hipcc and -ffp-contract=off.
 //   cloud_host_main <dir>
-// <dir> holds .npy dumps (numpy's format, version 1, C order, little endian; the header is skipped and the payload size
-// checked): params.npy (float64: rows, cols, fx, fy, cx, cy, baseline, min_disp, max_range, stride, capacity, shift),
-// disp.npy (float32 [rows][cols]), planes.npy (float32 [3][rows][cols]: a, b, z), bgr.npy (uint8 [rows][cols][3]) and the
-// definition's results want_xyz.npy, want_normals.npy (masked by disp), want_count.npy (int32 [1]), want_cloud_xyz.npy,
-// want_cloud_normals.npy, want_cloud_bgr.npy, want_cloud_index.npy (each with min(count, capacity) entries).
-// shift: the organised outputs start `shift` floats into their allocation (an unaligned destination for shift % 4 != 0).
+// <dir> holds .npy dumps (host_npy.hpp: Case): params.npy (float64: rows, cols, fx, fy, cx, cy, baseline, min_disp, max_range,
+// stride, capacity, shift), disp.npy (float32 [rows][cols]), planes.npy (float32 [3][rows][cols]: a, b, z), bgr.npy (uint8
+// [rows][cols][3]) and the definition's results want_xyz.npy, want_normals.npy (masked by disp), want_count.npy (int32 [1]),
+// want_cloud_xyz.npy, want_cloud_normals.npy, want_cloud_bgr.npy, want_cloud_index.npy (each with min(count, capacity)
+// entries).  shift: the organised outputs start `shift` floats into their allocation (an unaligned destination for shift % 4 != 0).
 // Exit status 0: every result equals its dump byte for byte; 1: a mismatch (named on stderr); 2: bad input.
-#include <cstdio>
-#include <cstring>
-#include <memory>
-#include <string>
-#include <vector>
 
 #include "host_npy.hpp"
 #include "pm_cloud_body.hpp"
 
+enum { kRows, kCols, kFx, kFy, kCx, kCy, kBaseline, kMinDisp, kMaxRange, kStride, kCapacity, kShift, kParams };
+
 int main(int argc, char** argv) {
   if (argc != 2) return 2;
-  const std::string dir = std::string(argv[1]) + "/";
-  std::unique_ptr<uint8_t[]> raw;
-  if (!read_npy(dir + "params.npy", 12 * sizeof(double), &raw)) return 2;
-  double p[12];
-  memcpy(p, raw.get(), sizeof p);
-  const int rows = (int)p[0], cols = (int)p[1], stride = (int)p[9], capacity = (int)p[10], shift = (int)p[11];
-  const pm_cloud_camera camera = {p[2], p[3], p[4], p[5], p[6]};
-  const pm_cloud_filter filter = {(float)p[7], (float)p[8], stride};
-  if (rows < 1 || cols < 1 || stride < 1 || capacity < 0 || shift < 0) return 2;
+  Case c(argv[1]);
+  const std::vector<double> p = c.params(kParams);
+  const int rows = (int)p[kRows], cols = (int)p[kCols], stride = (int)p[kStride], capacity = (int)p[kCapacity], shift = (int)p[kShift];
+  const pm_cloud_camera camera = {p[kFx], p[kFy], p[kCx], p[kCy], p[kBaseline]};
+  const pm_cloud_filter filter = {(float)p[kMinDisp], (float)p[kMaxRange], stride};
+  if (c.failed || rows < 1 || cols < 1 || stride < 1 || capacity < 0 || shift < 0) return 2;
   const size_t px = (size_t)rows * cols;
-  std::unique_ptr<uint8_t[]> disp_b, planes_b, bgr_b, want_xyz, want_normals, want_count;
-  if (!read_npy(dir + "disp.npy", 4 * px, &disp_b) || !read_npy(dir + "planes.npy", 12 * px, &planes_b) ||
-      !read_npy(dir + "bgr.npy", 3 * px, &bgr_b) || !read_npy(dir + "want_xyz.npy", 12 * px, &want_xyz) ||
-      !read_npy(dir + "want_normals.npy", 12 * px, &want_normals) || !read_npy(dir + "want_count.npy", 4, &want_count))
-    return 2;
-  const float* disp = (const float*)disp_b.get();  // operator new aligns to 16 bytes, like a device allocation
-  const float* planes = (const float*)planes_b.get();
+  const auto disp_p = c.read<float>("disp", px), planes_p = c.read<float>("planes", 3 * px);  // aligned like a device allocation
+  const auto bgr_b = c.raw("bgr", 3 * px);
+  const auto want_xyz = c.raw("want_xyz", 12 * px), want_normals = c.raw("want_normals", 12 * px);
+  const auto want_count = c.read<int32_t>("want_count", 1);
+  if (c.failed) return 2;
+  const float *disp = disp_p.get(), *planes = planes_p.get();
   const pm::CloudCam cam = pm::cloud_cam(camera);
   int bad = 0;
 
@@ -62,14 +54,12 @@ int main(int argc, char** argv) {
   bad |= differ("normals", normals.get(), want_normals.get(), 12 * px);
 
   // pm_point_cloud: the items in order, the slot counted as the three launches compute it
-  int want_n = 0;
-  memcpy(&want_n, want_count.get(), 4);
+  const int want_n = want_count[0];
+  if (want_n < 0) return 2;
   const size_t m = (size_t)(want_n < capacity ? want_n : capacity);
-  std::unique_ptr<uint8_t[]> want_cxyz, want_cn, want_cbgr, want_cidx;
-  if (want_n < 0 || !read_npy(dir + "want_cloud_xyz.npy", 12 * m, &want_cxyz) ||
-      !read_npy(dir + "want_cloud_normals.npy", 12 * m, &want_cn) || !read_npy(dir + "want_cloud_bgr.npy", 3 * m, &want_cbgr) ||
-      !read_npy(dir + "want_cloud_index.npy", 4 * m, &want_cidx))
-    return 2;
+  const auto want_cxyz = c.raw("want_cloud_xyz", 12 * m), want_cn = c.raw("want_cloud_normals", 12 * m);
+  const auto want_cbgr = c.raw("want_cloud_bgr", 3 * m), want_cidx = c.raw("want_cloud_index", 4 * m);
+  if (c.failed) return 2;
   std::unique_ptr<float[]> cxyz(new float[3 * m ? 3 * m : 1]), cn(new float[3 * m ? 3 * m : 1]);
   std::unique_ptr<uint8_t[]> cbgr(new uint8_t[3 * m ? 3 * m : 1]);
   std::unique_ptr<int32_t[]> cidx(new int32_t[m ? m : 1]);

@@ -6,18 +6,16 @@
 // an allocation of exactly its bytes: a tap outside the staged halo, or a store outside the image, is reported.  Compiled
 // as HIP source with the host-only switch of hipcc and -ffp-contract=off.
 //   normals_fit_host_main <dir>
-// <dir> holds .npy dumps (numpy's format, version 1, C order, little endian; the header is skipped and the payload size
-// checked): params.npy (float64: rows, cols, fx, fy, cx, cy, baseline, radius, max_diff, min_support, shift), disp.npy
-// (float32 [rows][cols]) and the definition's want_normals.npy (float32 [rows][cols][3]), want_planes.npy (float32
-// [3][rows][cols]), want_support.npy (uint8 [rows][cols]).  shift: d_normals starts `shift` floats into its allocation.
+// <dir> holds .npy dumps (host_npy.hpp: Case): params.npy (float64: rows, cols, fx, fy, cx, cy, baseline, radius, max_diff,
+// min_support, shift), disp.npy (float32 [rows][cols]) and the definition's want_normals.npy (float32 [rows][cols][3]),
+// want_planes.npy (float32 [3][rows][cols]), want_support.npy (uint8 [rows][cols]).  shift: d_normals starts `shift` floats
+// into its allocation.
 // Exit status 0: every result equals its dump byte for byte; 1: a mismatch (named on stderr); 2: bad input.
-#include <cstdio>
-#include <cstring>
-#include <memory>
-#include <string>
 
 #include "host_npy.hpp"
 #include "pm_normals_fit_body.hpp"
+
+enum { kRows, kCols, kFx, kFy, kCx, kCy, kBaseline, kRadius, kMaxDiff, kMinSupport, kShift, kParams };
 
 // the grid of k_normals_fit<R>, workgroup by workgroup, thread by thread
 template <int R>
@@ -37,25 +35,22 @@ static void run(const pm::NormalsFitArgs& a) {
 
 int main(int argc, char** argv) {
   if (argc != 2) return 2;
-  const std::string dir = std::string(argv[1]) + "/";
-  std::unique_ptr<uint8_t[]> raw;
-  if (!read_npy(dir + "params.npy", 11 * sizeof(double), &raw)) return 2;
-  double p[11];
-  memcpy(p, raw.get(), sizeof p);
-  const int rows = (int)p[0], cols = (int)p[1], radius = (int)p[7], min_support = (int)p[9], shift = (int)p[10];
-  const pm_cloud_camera camera = {p[2], p[3], p[4], p[5], p[6]};
-  const float max_diff = (float)p[8];
-  if (rows < 1 || cols < 1 || radius < 1 || radius > pm::kNormalsFitMaxRadius || shift < 0) return 2;
+  Case c(argv[1]);
+  const std::vector<double> p = c.params(kParams);
+  const int rows = (int)p[kRows], cols = (int)p[kCols], radius = (int)p[kRadius], min_support = (int)p[kMinSupport], shift = (int)p[kShift];
+  const pm_cloud_camera camera = {p[kFx], p[kFy], p[kCx], p[kCy], p[kBaseline]};
+  const float max_diff = (float)p[kMaxDiff];
+  if (c.failed || rows < 1 || cols < 1 || radius < 1 || radius > pm::kNormalsFitMaxRadius || shift < 0) return 2;
   const size_t px = (size_t)rows * cols;
-  std::unique_ptr<uint8_t[]> disp_b, want_normals, want_planes, want_support;
-  if (!read_npy(dir + "disp.npy", 4 * px, &disp_b) || !read_npy(dir + "want_normals.npy", 12 * px, &want_normals) ||
-      !read_npy(dir + "want_planes.npy", 12 * px, &want_planes) || !read_npy(dir + "want_support.npy", px, &want_support))
-    return 2;
+  const auto disp = c.read<float>("disp", px);
+  const auto want_normals = c.raw("want_normals", 12 * px), want_planes = c.raw("want_planes", 12 * px);
+  const auto want_support = c.raw("want_support", px);
+  if (c.failed) return 2;
   std::unique_ptr<float[]> normals(new float[shift + 3 * px]), planes(new float[3 * px]);
   std::unique_ptr<uint8_t[]> support(new uint8_t[px]);
   for (int k = 0; k < shift; ++k) normals[k] = -77.f;
-  const pm::NormalsFitArgs a = {pm::cloud_cam(camera), (const float*)disp_b.get(), rows,         cols,         radius,
-                                max_diff,              min_support,                 normals.get() + shift, planes.get(), support.get()};
+  const pm::NormalsFitArgs a = {pm::cloud_cam(camera), disp.get(), rows, cols, radius, max_diff, min_support, normals.get() + shift,
+                                planes.get(),          support.get()};
   switch (radius) {
     case 1: run<1>(a); break;
     case 2: run<2>(a); break;

@@ -20,6 +20,7 @@ import confidence_ref as CF
 import oracle_lib as O
 from conftest import ROOT
 from cpp_build import build_host_kernel
+from host_run import assert_program_compares, dump_case
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import fuzz_confidence as FC  # noqa: E402  (check_confidence: the device-against-definition comparison; the cases)
@@ -193,20 +194,12 @@ def host_confidence_exe(tmp_path_factory):
 
 
 def _dump_case(path, left, right, dl, dr, pw, ph, with_right, drop, functor=(0.7, 50.0, 20.0), **thresholds):
-    os.makedirs(path)
     want = CF.confidence(left, right, dl, dr if with_right else None, pw, ph, drop_unmeasured=drop, functor=functor, **thresholds)
-    save = lambda name, a: np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
     t = dict(dict(max_cost=INF, min_margin=-INF, min_bg_margin=-INF, max_lr_diff=INF), **thresholds)
-    save("params", np.array([*dl.shape, pw, ph, t["max_cost"], t["min_margin"], t["min_bg_margin"], t["max_lr_diff"], drop,
-                             int(with_right), *(np.float32(v) for v in functor)], np.float64))
-    save("left", left)
-    save("right", right)
-    save("disp_l", dl)
-    save("disp_r", dr)
-    save("want_out", want["out"])
-    save("want_measures", want["measures"])
-    save("want_flags", want["flags"])
-    save("want_counts", want["counts"])
+    dump_case(path, [*dl.shape, pw, ph, t["max_cost"], t["min_margin"], t["min_bg_margin"], t["max_lr_diff"], drop, int(with_right),
+                     *(np.float32(v) for v in functor)],
+              left=left, right=right, disp_l=dl, disp_r=dr, want_out=want["out"], want_measures=want["measures"],
+              want_flags=want["flags"], want_counts=want["counts"])
     return want
 
 
@@ -237,17 +230,9 @@ def test_kernel_code_on_the_host_equals_the_definition(host_confidence_exe, tmp_
     assert r.returncode == 0 and want["counts"][1] > 2000, r.stderr[-3000:]
     assert int(re.search(r"tiled blocks: (\d+)", r.stdout).group(1)) < tiles  # some blocks took the global-memory path unasked
     # the program does compare: one flipped bit in an expectation is a mismatch, not a pass
-    for name, dtype, word in (("want_measures", np.uint32, "measures differs"), ("want_flags", np.uint8, "flags differs"),
-                              ("want_out", np.uint32, "out differs"), ("want_counts", np.int32, "counts differs")):
-        path = os.path.join(last, name + ".npy")
-        keep = np.load(path)
-        flipped = keep.copy()
-        flipped.view(dtype).ravel()[-1] ^= 1
-        np.save(path, flipped)
-        r = subprocess.run([host_confidence_exe, last], capture_output=True, text=True)
-        assert r.returncode == 1 and word in r.stderr, (name, r.returncode, r.stderr[-500:])
-        np.save(path, keep)
-    assert subprocess.run([host_confidence_exe, last], capture_output=True, text=True).returncode == 0
+    assert_program_compares(host_confidence_exe, last,
+                            [("want_measures", np.uint32, "measures differs"), ("want_flags", np.uint8, "flags differs"),
+                             ("want_out", np.uint32, "out differs"), ("want_counts", np.int32, "counts differs")])
 
 
 def test_headers_declare_and_the_library_exports_the_confidence_functions(pm):

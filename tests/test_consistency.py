@@ -20,6 +20,7 @@ import consistency_ref as CR
 import reproject_ref as RR
 from conftest import ROOT
 from cpp_build import build_host_kernel
+from host_run import assert_program_compares, dump_case, flat_motions
 from pointcloud_ref import camera_for
 from test_reproject import CAM, FXB, motions, two_level
 
@@ -243,19 +244,10 @@ def host_consistency_exe(tmp_path_factory):
 
 
 def _dump_case(path, cur, cam, sources, mots, max_diff, radius, min_consistent, max_conflicts):
-    os.makedirs(path)
     want = CR.filter_consistency(cur, sources, cam, mots, max_diff, radius, min_consistent, max_conflicts)
-    save = lambda name, a: np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
-    flat = np.zeros(12 * CR.MAX_SOURCES)
-    for k, (R, t) in enumerate(mots):
-        flat[12 * k:12 * k + 12] = [*np.asarray(R).ravel(), *np.asarray(t).ravel()]
-    save("params", np.array([*cur.shape, *cam, len(sources), radius, max_diff, min_consistent, max_conflicts, *flat], np.float64))
-    save("disp", cur)
-    save("sources", np.stack(sources).astype(np.float32))
-    save("want_out", want["out"])
-    save("want_classes", want["classes"])
-    save("want_residual", want["residual"])
-    save("want_counts", want["counts"])
+    dump_case(path, [*cur.shape, *cam, len(sources), radius, max_diff, min_consistent, max_conflicts, *flat_motions(mots, CR.MAX_SOURCES)],
+              disp=cur, sources=np.stack(sources).astype(np.float32), want_out=want["out"], want_classes=want["classes"],
+              want_residual=want["residual"], want_counts=want["counts"])
     return want
 
 
@@ -281,18 +273,9 @@ def test_kernel_code_on_the_host_equals_the_definition(host_consistency_exe, tmp
                 k += 1
     assert kept > 10000
     # the program does compare: one flipped bit in an expectation is a mismatch, not a pass
-    d = str(tmp_path / "case30")
-    for name, dtype, word in (("want_residual", np.uint32, "residual differs"), ("want_classes", np.uint16, "classes differs"),
-                              ("want_out", np.uint32, "out differs"), ("want_counts", np.int32, "counts differs")):
-        path = os.path.join(d, name + ".npy")
-        keep = np.load(path)
-        flipped = keep.copy()
-        flipped.view(dtype).ravel()[-1] ^= 1
-        np.save(path, flipped)
-        r = subprocess.run([host_consistency_exe, d], capture_output=True, text=True)
-        assert r.returncode == 1 and word in r.stderr, (name, r.returncode, r.stderr[-500:])
-        np.save(path, keep)
-    assert subprocess.run([host_consistency_exe, d], capture_output=True, text=True).returncode == 0
+    assert_program_compares(host_consistency_exe, str(tmp_path / "case30"),
+                            [("want_residual", np.uint32, "residual differs"), ("want_classes", np.uint16, "classes differs"),
+                             ("want_out", np.uint32, "out differs"), ("want_counts", np.int32, "counts differs")])
 
 
 def test_headers_declare_and_the_library_exports_the_consistency_function(pm):

@@ -20,6 +20,7 @@ import consistency_ref as CR
 import fuse_ref as FU
 from conftest import ROOT
 from cpp_build import build_host_kernel
+from host_run import assert_program_compares, dump_case, flat_motions
 from pointcloud_ref import camera_for
 from test_reproject import CAM, FXB, motions, two_level
 
@@ -263,23 +264,15 @@ def host_fuse_exe(tmp_path_factory):
 
 
 def _dump_case(path, cur, cam, sources, mots, weight, source_weights, radius, min_consistent, max_conflicts, fill_min, fill_max_diff):
-    os.makedirs(path)
     n = len(sources)
     want = FU.fuse(cur, sources, cam, mots, weight, source_weights, MAX_DIFF, radius, min_consistent, max_conflicts, fill_min, fill_max_diff)
-    save = lambda name, a: np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
-    flat = np.zeros(12 * FU.MAX_SOURCES)
-    for k, (R, t) in enumerate(mots):
-        flat[12 * k:12 * k + 12] = [*np.asarray(R).ravel(), *np.asarray(t).ravel()]
     has = np.zeros(FU.MAX_SOURCES)
     has[:n] = [w is not None for w in source_weights]
-    save("params", np.array([*cur.shape, *cam, n, radius, MAX_DIFF, min_consistent, max_conflicts, fill_min, fill_max_diff,
-                             weight is not None, *has, *flat], np.float64))
-    save("disp", cur)
-    save("sources", np.stack(sources).astype(np.float32))
-    planes = [weight] + list(source_weights)
-    save("weights", np.stack([np.full(cur.shape, 7.0, np.float32) if w is None else w for w in planes]).astype(np.float32))
-    for name in ("out", "count", "spread", "flags", "counts"):
-        save("want_" + name, want[name])
+    planes = [np.full(cur.shape, 7.0, np.float32) if w is None else w for w in [weight] + list(source_weights)]
+    dump_case(path, [*cur.shape, *cam, n, radius, MAX_DIFF, min_consistent, max_conflicts, fill_min, fill_max_diff, weight is not None,
+                     *has, *flat_motions(mots, FU.MAX_SOURCES)],
+              disp=cur, sources=np.stack(sources).astype(np.float32), weights=np.stack(planes).astype(np.float32),
+              **{"want_" + name: want[name] for name in ("out", "count", "spread", "flags", "counts")})
     return want
 
 
@@ -311,17 +304,9 @@ def test_kernel_code_on_the_host_equals_the_definition(host_fuse_exe, tmp_path):
     print("valid, kept, fused, filled:", totals)
     assert totals[2] > 10000 and totals[3] > 1000 and totals[1] < totals[0]
     # the program does compare: one flipped bit in an expectation is a mismatch, not a pass
-    d = str(tmp_path / "case31")
-    for name, dtype in (("spread", np.uint32), ("count", np.uint8), ("flags", np.uint8), ("out", np.uint32), ("counts", np.int32)):
-        path = os.path.join(d, "want_%s.npy" % name)
-        keep = np.load(path)
-        flipped = keep.copy()
-        flipped.view(dtype).ravel()[-1] ^= 1
-        np.save(path, flipped)
-        r = subprocess.run([host_fuse_exe, d], capture_output=True, text=True)
-        assert r.returncode == 1 and name + " differs" in r.stderr, (name, r.returncode, r.stderr[-500:])
-        np.save(path, keep)
-    assert subprocess.run([host_fuse_exe, d], capture_output=True, text=True).returncode == 0
+    assert_program_compares(host_fuse_exe, str(tmp_path / "case31"),
+                            [("want_" + name, dtype, name + " differs") for name, dtype in
+                             (("spread", np.uint32), ("count", np.uint8), ("flags", np.uint8), ("out", np.uint32), ("counts", np.int32))])
 
 
 def test_headers_declare_and_the_library_exports_the_fuse_function(pm):

@@ -20,6 +20,7 @@ import normals_fit_ref as NR
 import pointcloud_ref as PR
 from conftest import GOLDEN, ROOT
 from cpp_build import build_host_kernel
+from host_run import assert_program_compares, dump_case
 from pointcloud_ref import camera_for
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -188,15 +189,9 @@ def host_fit_exe(tmp_path_factory):
 
 
 def _dump_case(path, disp, cam, radius, max_diff, min_support, shift):
-    os.makedirs(path)
-    rows, cols = disp.shape
     want = NR.disparity_normals(disp, cam, radius, max_diff, min_support)
-    save = lambda name, a: np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
-    save("params", np.array([rows, cols, *cam, radius, np.float32(max_diff), min_support, shift], np.float64))
-    save("disp", disp)
-    save("want_normals", want["normals"])
-    save("want_planes", want["planes"])
-    save("want_support", want["support"])
+    dump_case(path, [*disp.shape, *cam, radius, np.float32(max_diff), min_support, shift], disp=disp,
+              **{"want_" + k: want[k] for k in ("normals", "planes", "support")})
     return int(want["valid"].sum())
 
 
@@ -220,11 +215,7 @@ def test_kernel_code_on_the_host_equals_the_definition(pm, host_fit_exe, tmp_pat
             k += 1
     assert fitted > 3000
     # the program does compare: one flipped bit in an expectation is a mismatch, not a pass
-    want = np.load(os.path.join(d, "want_support.npy"))
-    want[-1, -1] ^= 1
-    np.save(os.path.join(d, "want_support.npy"), want)
-    r = subprocess.run([host_fit_exe, d], capture_output=True, text=True)
-    assert r.returncode == 1 and "support differs" in r.stderr
+    assert_program_compares(host_fit_exe, d, [("want_support", np.uint8, "support differs")])
 
 
 def test_headers_declare_and_the_library_exports_the_fit(pm):

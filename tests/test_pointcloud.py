@@ -18,6 +18,7 @@ import pytest
 import pointcloud_ref as PR
 from conftest import GOLDEN, ROOT
 from cpp_build import build_host_kernel
+from host_run import assert_program_compares, dump_case
 from pointcloud_ref import camera_for
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -90,7 +91,6 @@ def host_cloud_exe(tmp_path_factory):
 
 
 def _dump_case(path, rng, rows, cols, shift, min_disp, max_range, stride, capacity):
-    os.makedirs(path)
     cam = camera_for(rows, cols)
     disp = FC.random_disp(rng, rows, cols, valid=0.7, special=0.15)
     planes = np.stack([rng.choice(np.array([-1.0, 1.0, 0.0, 0.37, -0.004], np.float32), (rows, cols)),
@@ -101,18 +101,9 @@ def _dump_case(path, rng, rows, cols, shift, min_disp, max_range, stride, capaci
     count = PR.point_cloud(disp, cam, min_disp, max_range, stride)["count"]
     cap = 0 if capacity == "zero" else max(count + capacity, 0) if capacity <= 0 else capacity
     pc = PR.point_cloud(disp, cam, min_disp, max_range, stride, cap, nrm, bgr)
-    save = lambda name, a: np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
-    save("params", np.array([rows, cols, *cam, min_disp, max_range, stride, cap, shift], np.float64))
-    save("disp", disp)
-    save("planes", planes)
-    save("bgr", bgr)
-    save("want_xyz", PR.backproject(disp, cam))
-    save("want_normals", nrm)
-    save("want_count", np.array([pc["count"]], np.int32))
-    save("want_cloud_xyz", pc["xyz"])
-    save("want_cloud_normals", pc["normals"])
-    save("want_cloud_bgr", pc["bgr"])
-    save("want_cloud_index", pc["index"])
+    dump_case(path, [rows, cols, *cam, min_disp, max_range, stride, cap, shift], disp=disp, planes=planes, bgr=bgr,
+              want_xyz=PR.backproject(disp, cam), want_normals=nrm, want_count=np.array([pc["count"]], np.int32),
+              **{"want_cloud_" + k: pc[k] for k in ("xyz", "normals", "bgr", "index")})
     return pc["count"], cap
 
 
@@ -136,12 +127,7 @@ def test_kernel_code_on_the_host_equals_the_definition(host_cloud_exe, tmp_path)
         assert r.returncode == 0, (c, r.stderr[-3000:])
     assert counted > 3000
     # the program does compare: one flipped bit in an expectation is a mismatch, not a pass
-    d = str(tmp_path / "case1")
-    want = np.load(os.path.join(d, "want_cloud_index.npy"))
-    want[len(want) // 2] ^= 1
-    np.save(os.path.join(d, "want_cloud_index.npy"), want)
-    r = subprocess.run([host_cloud_exe, d], capture_output=True, text=True)
-    assert r.returncode == 1 and "cloud index differs" in r.stderr
+    assert_program_compares(host_cloud_exe, str(tmp_path / "case1"), [("want_cloud_index", np.int32, "cloud index differs")])
 
 
 def test_headers_declare_and_the_library_exports_the_cloud_functions(pm):

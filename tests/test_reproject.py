@@ -19,6 +19,7 @@ import pytest
 import reproject_ref as RR
 from conftest import ROOT
 from cpp_build import build_host_kernel
+from host_run import assert_program_compares, dump_case, flat_motions
 from pointcloud_ref import camera_for
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -137,14 +138,9 @@ def host_reproject_exe(tmp_path_factory):
 
 
 def _dump_case(path, disp, cam, motion, min_disp, max_disp, r, shift):
-    os.makedirs(path)
     want = RR.reproject(disp, cam, motion[0], motion[1], min_disp, max_disp, r)
-    save = lambda name, a: np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
-    save("params", np.array([*disp.shape, *cam, *np.asarray(motion[0]).ravel(), *motion[1], min_disp, max_disp, r, shift], np.float64))
-    save("disp", disp)
-    save("want_seed_l", want["seed_l"])
-    save("want_seed_r", want["seed_r"])
-    save("want_counts", want["counts"])
+    dump_case(path, [*disp.shape, *cam, *flat_motions([motion], 1), min_disp, max_disp, r, shift],
+              disp=disp, want_seed_l=want["seed_l"], want_seed_r=want["seed_r"], want_counts=want["counts"])
     return want
 
 
@@ -171,12 +167,7 @@ def test_kernel_code_on_the_host_equals_the_definition(host_reproject_exe, tmp_p
         assert r.returncode == 0, (k, r.stderr[-3000:])
     assert seeds > 10000
     # the program does compare: one flipped bit in an expectation is a mismatch, not a pass
-    d = str(tmp_path / "case2")
-    want = np.load(os.path.join(d, "want_seed_r.npy"))
-    want.view(np.uint32)[20, 20] ^= 1
-    np.save(os.path.join(d, "want_seed_r.npy"), want)
-    r = subprocess.run([host_reproject_exe, d], capture_output=True, text=True)
-    assert r.returncode == 1 and "seed_r differs" in r.stderr
+    assert_program_compares(host_reproject_exe, str(tmp_path / "case2"), [("want_seed_r", np.uint32, "seed_r differs")])
 
 
 def test_headers_declare_and_the_library_exports_the_reproject_functions(pm):

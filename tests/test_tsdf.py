@@ -22,6 +22,7 @@ import pointcloud_ref
 import tsdf_ref as TR
 from conftest import ROOT
 from cpp_build import build_host_kernel
+from host_run import assert_program_compares, dump_case, flat_motions
 from test_reproject import CAM, FXB
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -403,25 +404,16 @@ def host_tsdf_exe(tmp_path_factory):
 
 
 def _dump_case(path, args, want, start=None):
-    os.makedirs(path)
     grid, steps, ray = args["grid"], args["steps"], args["ray"]
-    save = lambda name, a: np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
-    poses = np.zeros(12 * 4)
-    for k, (_, pose, _) in enumerate(steps):
-        poses[12 * k:12 * k + 12] = [*np.asarray(pose[0]).ravel(), *np.asarray(pose[1]).ravel()]
     weighted = steps[0][2] is not None
-    save("params", np.array([grid["nx"], grid["ny"], grid["nz"], *grid["origin"], grid["voxel"], grid["trunc"], grid["max_weight"],
-                             *args["camera"], args["rows"], args["cols"], len(steps), args["min_disp"], args["max_range"], weighted,
-                             ray["min_range"], ray["max_range"], ray["step"], ray["min_weight"],
-                             *np.asarray(args["ray_pose"][0]).ravel(), *np.asarray(args["ray_pose"][1]).ravel(), *poses], np.float64))
-    save("start", TR.clear(grid) if start is None else start)
-    save("disp", np.stack([s[0] for s in steps]).astype(np.float32))
-    save("weights", np.stack([s[2] if weighted else np.full(s[0].shape, 7.0, np.float32) for s in steps]).astype(np.float32))
-    save("want_voxels", np.stack(want["volumes"]))
-    save("want_counts", np.stack(want["counts"]).astype(np.int32))
-    save("want_disp", want["ray"]["disp"])
-    save("want_normals", want["ray"]["normals"])
-    save("want_hits", want["ray"]["counts"])
+    dump_case(path, [grid["nx"], grid["ny"], grid["nz"], *grid["origin"], grid["voxel"], grid["trunc"], grid["max_weight"],
+                     *args["camera"], args["rows"], args["cols"], len(steps), args["min_disp"], args["max_range"], weighted,
+                     ray["min_range"], ray["max_range"], ray["step"], ray["min_weight"],
+                     *flat_motions([args["ray_pose"]], 1), *flat_motions([pose for _, pose, _ in steps], 4)],
+              start=TR.clear(grid) if start is None else start, disp=np.stack([s[0] for s in steps]).astype(np.float32),
+              weights=np.stack([s[2] if weighted else np.full(s[0].shape, 7.0, np.float32) for s in steps]).astype(np.float32),
+              want_voxels=np.stack(want["volumes"]), want_counts=np.stack(want["counts"]).astype(np.int32),
+              want_disp=want["ray"]["disp"], want_normals=want["ray"]["normals"], want_hits=want["ray"]["counts"])
 
 
 def test_kernel_code_on_the_host_equals_the_definition(host_tsdf_exe, tmp_path):
@@ -456,17 +448,10 @@ def test_kernel_code_on_the_host_equals_the_definition(host_tsdf_exe, tmp_path):
     print("in view, updated, hit:", totals, want["ray"]["counts"])
     assert totals[1] > 20000 and totals[2] > 500 and want["ray"]["counts"][0] > 100
     # the program does compare: one flipped bit in an expectation is a mismatch, not a pass
-    for name, dtype, word in (("voxels", np.uint32, "the volume behind integrate 1"), ("counts", np.int32, "counts"),
-                              ("disp", np.uint32, "disp"), ("normals", np.uint32, "normals"), ("hits", np.int32, "hits")):
-        path = os.path.join(d, "want_%s.npy" % name)
-        keep = np.load(path)
-        flipped = keep.copy()
-        flipped.view(dtype).ravel()[-1] ^= 1
-        np.save(path, flipped)
-        r = subprocess.run([host_tsdf_exe, d], capture_output=True, text=True)
-        assert r.returncode == 1 and word + " differs" in r.stderr, (name, r.returncode, r.stderr[-500:])
-        np.save(path, keep)
-    assert subprocess.run([host_tsdf_exe, d], capture_output=True, text=True).returncode == 0
+    assert_program_compares(host_tsdf_exe, d,
+                            [("want_" + name, dtype, word + " differs") for name, dtype, word in
+                             (("voxels", np.uint32, "the volume behind integrate 1"), ("counts", np.int32, "counts"),
+                              ("disp", np.uint32, "disp"), ("normals", np.uint32, "normals"), ("hits", np.int32, "hits"))])
 
 
 def test_headers_declare_and_the_library_exports_the_tsdf_functions(pm):
