@@ -784,6 +784,54 @@ int pm_tsdf_raycast(pm_handle* h, const pm_cloud_camera* camera, const pm_tsdf_v
                     int* d_counts /* device int[1]: pixels hit; may be NULL */,
                     int* counts /* host int[1], may be NULL: non-NULL synchronises */);
 
+/* ---- the model taken out of the volume: its zero level set as ONE welded triangle mesh in the world frame ------------------------
+ * pm_tsdf_raycast followed by pm_grid_mesh gives what one pose sees, in that camera's frame.  pm_tsdf_mesh gives the whole surface
+ * the volume holds: an indexed mesh with one vertex per crossed grid edge, shared by every triangle around it, compacted in a fixed
+ * order.  The method is marching tetrahedra over the Kuhn (Freudenthal) split of every cell into six tetrahedra around the
+ * diagonal 000-111 -- the same split in every cell, so faces match between neighbours, the mesh is closed wherever the observed
+ * volume is, and there are no ambiguous cases.
+ * Held to its CPU definition (tests/tsdf_mesh_ref.py) BIT FOR BIT; one rounding per operation, parentheses as written:
+ *   observed  node (i, j, k) is OBSERVED iff weight > 0, weight >= min_weight and tsdf is finite; an observed node is INSIDE iff
+ *             not (tsdf > 0): pm_tsdf_raycast's front crossing.
+ *   cell      (i, j, k), i < nx - 1, j < ny - 1, k < nz - 1, is LIVE iff its eight corner nodes are observed; only live cells emit
+ *             triangles.
+ *   edges     node a owns seven edges a -> a + d, d = (1,0,0), (0,1,0), (0,0,1), (1,1,0), (0,1,1), (1,0,1), (1,1,1) in this
+ *             order.  An edge CROSSES iff both ends are observed and exactly one is inside; it is a VERTEX iff it crosses and lies
+ *             in at least one live cell, so every vertex is named by a triangle.
+ *   vertex    t = (double)f_a / ((double)f_a - (double)f_b), a the owning node;  P_c = origin[c] + (((double)a_c + (d_c ? t : 0.0))
+ *             * voxel);  xyz_c = (float)P_c.
+ *   normal    G_c(n) = T(n + e_c) - T(n - e_c) in binary32, valid iff the six neighbours of n lie inside the grid and are observed;
+ *             g_c = (double)Ga_c + (t * ((double)Gb_c - (double)Ga_c));  n_c = (float)g_c;  l = sqrtf(((n0*n0) + (n1*n1)) +
+ *             (n2*n2));  (0, 0, 0) unless both gradients are valid and l > 0 and finite, else n_c / l.  World frame; it points to
+ *             the positive side, which is free space.
+ *   tetrahedra  for the axis orders p = xyz, xzy, yxz, yzx, zxy, zyx: c0 = 000, c1 = c0 + e_p0, c2 = c1 + e_p1, c3 = 111.  With I
+ *             the inside corners and O the outside ones by corner number:  |I| = 1, I = {a}: the polygon is the edges (a, o), o
+ *             ascending;  |I| = 3, O = {a}: (i, a), i ascending;  |I| = 2, I = {a < b}, O = {c < d}: (a, c), (a, d), (b, d), (b, c).
+ *             With every polygon vertex at its edge's midpoint in doubled integer corner coordinates the polygon is read back to
+ *             front iff ((Q1 - Q0) x (Q2 - Q0)) . (|I| sum(O) - |O| sum(I)) < 0.  Triangles (q0, q1, q2) and, of a quad,
+ *             (q0, q2, q3): (P1 - P0) x (P2 - P0) points to the positive side, pm_grid_mesh's convention.  At most 12 per cell.
+ *   order     vertices by owning node, x fastest, then by edge number; triangles by cell, x fastest, then by tetrahedron, then as
+ *             above.  A triangle is three int32 vertex slots.
+ *   counts    [vertices, triangles], whatever the capacities: exactly the first vertex_capacity vertices and the first
+ *             tri_capacity triangles are written and nothing behind them; the indices always use the untruncated numbering
+ *             (pm_grid_mesh's rules).  Every output is optional; capacities of 0 only count.
+ * An inside node with tsdf == 0 makes its vertices coincide at the node: the ZERO-AREA triangles are emitted, because the topology
+ * stays closed.  A grid thinner than two nodes on any axis is legal and empty.
+ * Runs on the handle's stream, valid in every mode; a non-NULL host `counts` synchronises.  Seven launches at the most, the order
+ * from arithmetic and never from an atomic, so two calls give the same bytes.  Scratch: 5 bytes per node, 8 per 64-node span of
+ * a row and 8 per 1024 spans, ONE handle-owned allocation made on first use, reused, released with the handle; GROWING it
+ * synchronises the stream, as pm_grid_mesh's does.
+ * PM_ERR_INVALID_ARG, with pm_last_error naming the argument and nothing enqueued: a null volume, options or d_voxels; a volume
+ * pm_tsdf_integrate refuses; a min_weight that is NaN or < 0; a negative capacity.  PM_ERR_SIZE: nx * ny * nz > 2^31 - 1, or
+ * 12 x cells or 7 x nodes above 2^31 - 1. */
+typedef struct pm_tsdf_mesh_options { float min_weight; } pm_tsdf_mesh_options;
+int pm_tsdf_mesh(pm_handle* h, const pm_tsdf_volume* volume, const pm_tsdf_mesh_options* options, const void* d_voxels,
+                 int vertex_capacity, int tri_capacity, float* d_xyz_out /* [vertex_capacity][3], may be NULL */,
+                 float* d_normals_out /* [vertex_capacity][3], may be NULL */,
+                 int32_t* d_tri_out /* [tri_capacity][3], may be NULL */,
+                 int* d_counts /* device int[2]: vertices, triangles; may be NULL */,
+                 int* counts /* host int[2], may be NULL: non-NULL synchronises */);
+
 /* ---- device buffers for host code that does not include HIP (host/imaging.hpp uses them) ------------------
  * pm_device_malloc / pm_device_free wrap hipMalloc / hipFree on the handle's device; pm_upload / pm_download are
  * stream-ordered copies on the handle's stream from / to pageable host memory (pm_download returns after the

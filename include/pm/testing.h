@@ -218,6 +218,14 @@ void pm_debug_confidence_constants(int* tile_w, int* tile_h, int* target_cols);
  * span and leave a tail with them.  No handle, no device. */
 void pm_debug_tsdf_constants(int* lanes, int* waves);
 
+/* ---- pm_tsdf_mesh's case table (csrc/pm_tsdf_mesh_body.hpp) and its scratch ------------------------------------------------------
+ * For each of the 256 patterns of a cell's inside bits (bit c: corner c, bit 0 x, bit 1 y, bit 2 z): counts[pattern] triangles
+ * (at most 12) and their vertex codes codes[pattern][3 * triangle + m] = (corner of the owning node) | (edge number << 3), 0xff
+ * behind the last; as the kernels walk it.  Either may be NULL.  pm_debug_tsdf_mesh_scratch_bytes: the bytes of scratch a call on
+ * an nx x ny x nz volume reserves.  No handle, no device. */
+void pm_debug_tsdf_mesh_table(uint8_t* counts /* [256] */, uint8_t* codes /* [256][36] */);
+size_t pm_debug_tsdf_mesh_scratch_bytes(int nx, int ny, int nz);
+
 /* ---- the row-tiled driver's device discipline, provable on ONE GPU ------------------------------------------------
  * pm_tiled_create with the bands accounted to LOGICAL devices: band k lives on logical_devices[k] (>= 0; several bands
  * may share one) while every HIP call still goes to the physical device of the band's handle.  Such a plan logs every

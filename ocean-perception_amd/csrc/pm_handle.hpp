@@ -24,6 +24,8 @@
 //                        pm_fuse_body.hpp's
 //     pm_tsdf.hpp        the two kernels of pm_tsdf_integrate and pm_tsdf_raycast (k_tsdf_integrate, k_tsdf_raycast); their
 //                        bodies are pm_tsdf_body.hpp's
+//     pm_tsdf_mesh.hpp   the five kernels of pm_tsdf_mesh (k_tsdf_mesh_flags / _count / _span_offsets / _vertices /
+//                        _triangles); their bodies and the case table are pm_tsdf_mesh_body.hpp's
 //     pm_track.hpp       the three kernels of pm_track_features (k_track_select, k_track_compact, k_track_match); their
 //                        scalar pieces are pm_track_body.hpp's
 // Every __global__ kernel lives in exactly one unit; the others reach it through the launch functions declared here.

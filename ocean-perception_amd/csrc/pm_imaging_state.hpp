@@ -60,6 +60,10 @@ struct ImagingState {
   DevBuf<int> track_buf;
   // pm_tsdf_integrate / pm_tsdf_raycast: kCountsHeader words ([0], [1]: the counts of the call), cleared per call
   DevBuf<int> tsdf_counts;
+  // pm_tsdf_mesh: kCountsHeader words ([0] the vertex count, [1] the triangle count), one word per group of 1024 spans and one
+  // per 64-node span of a row, for the vertices and for the triangles each (its count, then its offset), one word per node (its vertex mask and its rank in
+  // the span), one byte per node (its crossing edges and whether its cell is live)
+  DevBuf<int> tsdf_mesh_buf;
 };
 
 #define PM_HIP(h, call)                                                                                     \

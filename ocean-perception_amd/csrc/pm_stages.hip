@@ -1,7 +1,7 @@
 // pm_stages.hip -- C-ABI implementation of the stages of include/pm/imaging.h that read a finished disparity map: points,
 // plane-mode normals and the compacted cloud, the windowed plane fit, the speckle filter, the grid mesh, the temporal
-// seeds, the consistency filter, the matching confidence, the sequence fusion, the TSDF volume and the feature tracks of the
-// motion estimate.  Like pm_imaging.hip it reaches the handle only through pm_internal.hpp, and it shares that unit's one
+// seeds, the consistency filter, the matching confidence, the sequence fusion, the TSDF volume with its mesh and the feature
+// tracks of the motion estimate.  Like pm_imaging.hip it reaches the handle only through pm_internal.hpp, and it shares that unit's one
 // state object (pm_imaging_state.hpp).  Every entry point: its argument checks in a fixed order (the first fault is the one
 // reported), then the device, then its launches on the handle's stream.
 #include "pm/imaging.h"
@@ -27,6 +27,7 @@
 #include "pm_speckle.hpp"
 #include "pm_track.hpp"
 #include "pm_tsdf.hpp"
+#include "pm_tsdf_mesh.hpp"
 #include "pm_tune.hpp"
 
 using namespace pm;
@@ -887,6 +888,99 @@ int pm_tsdf_raycast(pm_handle* h, const pm_cloud_camera* camera, const pm_tsdf_v
 void pm_debug_tsdf_constants(int* lanes, int* waves) {
   if (lanes) *lanes = kTsdfLanes;
   if (waves) *waves = kTsdfWaves;
+}
+
+// ---- the volume's zero level set as one welded triangle mesh (pm_tsdf_mesh.hpp) ---------------------------------------------------
+namespace {
+size_t tsdf_mesh_spans(int nx, int ny, int nz) { return (((size_t)nx + kTsdfLanes - 1) / kTsdfLanes) * (size_t)ny * (size_t)nz; }
+
+size_t tsdf_mesh_groups(size_t spans) { return (spans + kTsdfMeshGroup - 1) / kTsdfMeshGroup; }
+
+// the totals, one word per span and one per group of spans for the vertices and for the triangles, one word and one byte per node
+size_t tsdf_mesh_scratch_bytes(int nx, int ny, int nz) {
+  const size_t nodes = (size_t)nx * (size_t)ny * (size_t)nz, spans = tsdf_mesh_spans(nx, ny, nz);
+  return sizeof(int) * (kCountsHeader + 2 * tsdf_mesh_groups(spans) + 2 * spans + nodes) + nodes;
+}
+}  // namespace
+
+int pm_tsdf_mesh(pm_handle* h, const pm_tsdf_volume* volume, const pm_tsdf_mesh_options* options, const void* d_voxels,
+                 int vertex_capacity, int tri_capacity, float* d_xyz_out, float* d_normals_out, int32_t* d_tri_out, int* d_counts,
+                 int* counts) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_tsdf_mesh";
+  if (int rc = check_not_null(h, what, {{"volume", volume}, {"options", options}, {"d_voxels", d_voxels}})) return rc;
+  if (const char* fault = tsdf_volume_fault(*volume)) {
+    set_err(h, "%s: %s", what, fault);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (std::isnan(options->min_weight) || options->min_weight < 0.f) {
+    set_err(h, "%s: min_weight must not be NaN or negative", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (vertex_capacity < 0 || tri_capacity < 0) {
+    set_err(h, "%s: %s %d must be >= 0", what, vertex_capacity < 0 ? "vertex_capacity" : "tri_capacity",
+            vertex_capacity < 0 ? vertex_capacity : tri_capacity);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_tsdf_size(h, what, *volume)) return rc;
+  const int nx = volume->nx, ny = volume->ny, nz = volume->nz;
+  const size_t nodes = tsdf_voxels(*volume);
+  const size_t cells = (size_t)(nx - 1) * (size_t)(ny - 1) * (size_t)(nz - 1);
+  if (7 * nodes > (size_t)INT32_MAX || kTsdfMeshMaxCellTriangles * cells > (size_t)INT32_MAX) {
+    set_err(h, "%s: the %dx%dx%d volume has more than 2^31 - 1 possible vertices or triangles", what, nx, ny, nz);
+    return PM_ERR_SIZE;
+  }
+  ImagingState* st = nullptr;
+  hipStream_t stream = nullptr;
+  if (int rc = stage_begin(h, what, &st, &stream)) return rc;
+  const size_t spans = tsdf_mesh_spans(nx, ny, nz);  // <= nodes: far below 2^31
+  PM_HIP(h, st->tsdf_mesh_buf.reserve(tsdf_mesh_scratch_bytes(nx, ny, nz), stream));
+  int* d_totals = st->tsdf_mesh_buf.get();
+  const bool want_vertices = vertex_capacity > 0 && (d_xyz_out || d_normals_out);
+  const bool want_tris = tri_capacity > 0 && d_tri_out;
+  TsdfMeshArgs a = {};
+  a.grid = tsdf_grid(*volume);
+  a.min_weight = options->min_weight;
+  a.x_spans = (nx + kTsdfLanes - 1) / kTsdfLanes;
+  a.voxels = static_cast<const TsdfVoxel*>(d_voxels);
+  const size_t groups = tsdf_mesh_groups(spans);
+  a.vertex_groups = d_totals + kCountsHeader;
+  a.tri_groups = a.vertex_groups + groups;
+  a.vertex_spans = a.tri_groups + groups;
+  a.tri_spans = a.vertex_spans + spans;
+  a.info = reinterpret_cast<uint32_t*>(a.tri_spans + spans);
+  a.flags = reinterpret_cast<uint8_t*>(a.info + nodes);
+  a.xyz_out = d_xyz_out, a.normals_out = d_normals_out, a.tri_out = d_tri_out;
+  a.vertex_capacity = want_vertices ? vertex_capacity : 0, a.tri_capacity = want_tris ? tri_capacity : 0;
+  const dim3 grid((unsigned)((spans + kTsdfBlockY - 1) / kTsdfBlockY)), block(kTsdfBlockX, kTsdfBlockY);
+  const unsigned n_spans = (unsigned)spans;
+  hipLaunchKernelGGL(k_tsdf_mesh_flags, grid, block, 0, stream, a, n_spans);
+  hipLaunchKernelGGL(k_tsdf_mesh_count, grid, block, 0, stream, a, n_spans);
+  hipLaunchKernelGGL(k_tsdf_mesh_span_offsets, dim3((unsigned)groups), dim3(kTsdfMeshGroup), 0, stream, a, n_spans);
+  hipLaunchKernelGGL(k_cloud_offsets, dim3(1), dim3(kCloudScanThreads), 0, stream, a.vertex_groups, (int)groups, d_totals, d_counts);
+  hipLaunchKernelGGL(k_cloud_offsets, dim3(1), dim3(kCloudScanThreads), 0, stream, a.tri_groups, (int)groups, d_totals + 1,
+                     d_counts ? d_counts + 1 : nullptr);
+  if (want_vertices) hipLaunchKernelGGL(k_tsdf_mesh_vertices, grid, block, 0, stream, a, n_spans);
+  if (want_tris) hipLaunchKernelGGL(k_tsdf_mesh_triangles, grid, block, 0, stream, a, n_spans);
+  if (int rc = launch_check(h, "tsdf mesh")) return rc;
+  return stage_counts(h, stream, d_totals, 2, nullptr, counts);  // k_cloud_offsets wrote d_counts
+}
+
+void pm_debug_tsdf_mesh_table(uint8_t* counts, uint8_t* codes) {
+  for (unsigned pattern = 0; pattern < 256; ++pattern) {
+    int n = 0;
+    uint8_t* row = codes ? codes + 3 * kTsdfMeshMaxCellTriangles * pattern : nullptr;
+    for (int m = 0; row && m < 3 * kTsdfMeshMaxCellTriangles; ++m) row[m] = 0xff;
+    tsdf_mesh_cell_triangles(pattern, [&](unsigned c0, unsigned c1, unsigned c2) {
+      if (row) row[3 * n] = (uint8_t)c0, row[3 * n + 1] = (uint8_t)c1, row[3 * n + 2] = (uint8_t)c2;
+      ++n;
+    });
+    if (counts) counts[pattern] = (uint8_t)n;
+  }
+}
+
+size_t pm_debug_tsdf_mesh_scratch_bytes(int nx, int ny, int nz) {
+  return nx < 1 || ny < 1 || nz < 1 ? 0 : tsdf_mesh_scratch_bytes(nx, ny, nz);
 }
 
 // ---- camera motion between two frames: features of the old left image tracked into the new one (pm_track.hpp) ----------------

@@ -835,6 +835,39 @@ int TsdfVolume::Raycast(const StereoModel& model, const Motion& pose, int rows, 
   return hits;
 }
 
+std::array<int, 2> TsdfVolume::MeshDevice(const TsdfMeshOptions& options, int vertex_capacity, int tri_capacity, float* d_xyz_out,
+                                          float* d_normals_out, int32_t* d_tri_out, int* d_counts, bool want_counts) {
+  const pm_tsdf_mesh_options opt = {options.min_weight};
+  int counts[2] = {-1, -1};
+  impl_->dev.Check(pm_tsdf_mesh(impl_->h, &impl_->volume, &opt, device(), vertex_capacity, tri_capacity, d_xyz_out, d_normals_out,
+                                d_tri_out, d_counts, want_counts ? counts : nullptr),
+                   "pm_tsdf_mesh");
+  return {{counts[0], counts[1]}};
+}
+
+TriangleMesh TsdfVolume::Mesh(const TsdfMeshOptions& options, bool want_normals) {
+  // count first (both capacities 0), then outputs of exactly that size
+  const std::array<int, 2> counts = MeshDevice(options, 0, 0, nullptr, nullptr, nullptr);
+  TriangleMesh mesh;
+  if (counts[0] <= 0) return mesh;
+  const size_t n = (size_t)counts[0], t = (size_t)(counts[1] > 0 ? counts[1] : 0);
+  DeviceBuffers dev(impl_->h);
+  float* d_xyz = dev.Get<float>(n * sizeof(core::Vec3f));
+  float* d_normals = want_normals ? dev.Get<float>(n * sizeof(core::Vec3f)) : nullptr;
+  int32_t* d_tris = t ? dev.Get<int32_t>(t * 3 * sizeof(int32_t)) : nullptr;
+  if (MeshDevice(options, counts[0], counts[1], d_xyz, d_normals, d_tris) != counts)
+    throw std::runtime_error("TsdfVolume::Mesh: the counts changed between two passes over one volume");
+  mesh.vertices.xyz.resize(n);
+  dev.Check(pm_download(impl_->h, mesh.vertices.xyz.data(), d_xyz, n * sizeof(core::Vec3f)), "pm_download");
+  if (want_normals) {
+    mesh.vertices.normals.resize(n);
+    dev.Check(pm_download(impl_->h, mesh.vertices.normals.data(), d_normals, n * sizeof(core::Vec3f)), "pm_download");
+  }
+  mesh.triangles.resize(t);
+  if (t) dev.Check(pm_download(impl_->h, mesh.triangles.data(), d_tris, t * 3 * sizeof(int32_t)), "pm_download");
+  return mesh;
+}
+
 std::vector<float> TsdfVolume::Download() {
   std::vector<float> out(2 * voxels());
   impl_->dev.Check(pm_download(impl_->h, out.data(), device(), sizeof(float) * out.size()), "pm_download");

@@ -290,7 +290,8 @@ Motion EstimateMotion(pm::PatchmatchGpu& matcher, const StereoModel& model, cons
 // A persistent world-frame model of a sequence: a truncated signed distance volume that Integrate folds left disparity maps
 // and their camera poses into and Raycast renders back, at any pose, as an ordinary left disparity map with normals -- what
 // MakePointCloud, MakeGridMesh, ReprojectDisparity (with the identity motion, for the right seed), FilterConsistency and
-// FuseDisparity take (pm/imaging.h: pm_tsdf_clear, pm_tsdf_integrate, pm_tsdf_raycast; definition: tests/tsdf_ref.py).  A pose is
+// FuseDisparity take (pm/imaging.h: pm_tsdf_clear, pm_tsdf_integrate, pm_tsdf_raycast; definition: tests/tsdf_ref.py) -- and that Mesh takes out
+// whole, as one triangle mesh in the world frame (pm_tsdf_mesh).  A pose is
 // a Motion from the WORLD frame into the left camera's: X_cam = R X_world + t.
 struct TsdfGrid {  // pm_tsdf_volume
   int nx = 0, ny = 0, nz = 0;               // voxels, x fastest
@@ -302,6 +303,9 @@ struct TsdfGrid {  // pm_tsdf_volume
 struct TsdfIntegrateOptions {  // pm_tsdf_integrate_options
   float min_disp = 0.f;   // a pixel measures iff disp > 0 and disp >= min_disp
   float max_range = 0.f;  // > 0: a measured range above it is dropped; 0 = no limit
+};
+struct TsdfMeshOptions {  // pm_tsdf_mesh_options
+  float min_weight = 0.f;  // a node is observed iff weight > 0, weight >= min_weight and its value is finite
 };
 struct TsdfRaycastOptions {  // pm_tsdf_raycast_options
   float min_range = 0.1f, max_range = 10.f;  // finite, 0 < min_range < max_range
@@ -336,6 +340,16 @@ class TsdfVolume {
   // want_counts = false it only enqueues and returns -1.
   int RaycastDevice(const StereoModel& model, const Motion& pose, int rows, int cols, float* d_disp_out, float* d_normals_out,
                     const TsdfRaycastOptions& options = TsdfRaycastOptions(), bool want_counts = true);
+  // The model taken out of the volume: its zero level set as ONE welded triangle mesh in the WORLD frame, one vertex per
+  // crossed grid edge (pm/imaging.h: pm_tsdf_mesh; definition: tests/tsdf_mesh_ref.py).  A count call, then one call sized to
+  // fit.  vertices.xyz always, vertices.normals (toward free space; (0, 0, 0) where the volume's gradient is not known) with
+  // want_normals; no colour and no index.  WritePly takes the result unchanged.
+  TriangleMesh Mesh(const TsdfMeshOptions& options = TsdfMeshOptions(), bool want_normals = true);
+  // Device streams out, each may be null: d_xyz_out and d_normals_out vertex_capacity x 3 floats, d_tri_out tri_capacity x 3
+  // int32, d_counts two device ints.  Returns {vertices, triangles}, both counted beyond the capacities; with want_counts =
+  // false it only enqueues and returns {-1, -1}.
+  std::array<int, 2> MeshDevice(const TsdfMeshOptions& options, int vertex_capacity, int tri_capacity, float* d_xyz_out,
+                                float* d_normals_out, int32_t* d_tri_out, int* d_counts = nullptr, bool want_counts = true);
   // The records, 2 floats per voxel (tsdf, weight), x fastest; synchronises.
   std::vector<float> Download();
 

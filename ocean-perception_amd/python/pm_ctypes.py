@@ -52,6 +52,7 @@ EXPORTS = [
     "pm_disparity_confidence", "pm_debug_confidence_constants",
     "pm_fuse_disparity",
     "pm_tsdf_bytes", "pm_tsdf_clear", "pm_tsdf_integrate", "pm_tsdf_raycast", "pm_debug_tsdf_constants",
+    "pm_tsdf_mesh", "pm_debug_tsdf_mesh_table", "pm_debug_tsdf_mesh_scratch_bytes",
     "pm_track_features", "pm_solve_motion", "pm_estimate_motion",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
     "pm_debug_match_plan",
@@ -298,6 +299,10 @@ class PmTsdfRaycastOptions(C.Structure):
     _fields_ = [("min_range", C.c_float), ("max_range", C.c_float), ("step", C.c_float), ("min_weight", C.c_float)]
 
 
+class PmTsdfMeshOptions(C.Structure):
+    _fields_ = [("min_weight", C.c_float)]
+
+
 def tsdf_volume(values):
     """A PmTsdfVolume from a dict (nx, ny, nz, origin, voxel, trunc, max_weight) or those seven values in that order; a
     PmTsdfVolume or None passes through."""
@@ -320,6 +325,20 @@ def tsdf_constants():
     a, b = C.c_int(0), C.c_int(0)
     load().pm_debug_tsdf_constants(C.byref(a), C.byref(b))
     return a.value, b.value
+
+
+def tsdf_mesh_table():
+    """pm_debug_tsdf_mesh_table: (counts uint8 [256], codes uint8 [256][36]) -- per pattern of a cell's inside bits its triangles
+    and their vertex codes (corner of the owning node | edge number << 3), 0xff behind the last."""
+    import numpy as np
+    counts, codes = np.zeros(256, np.uint8), np.zeros((256, 36), np.uint8)
+    load().pm_debug_tsdf_mesh_table(counts.ctypes.data, codes.ctypes.data)
+    return counts, codes
+
+
+def tsdf_mesh_scratch_bytes(nx, ny, nz):
+    """pm_debug_tsdf_mesh_scratch_bytes: the scratch a pm_tsdf_mesh call on an nx x ny x nz volume reserves."""
+    return int(load().pm_debug_tsdf_mesh_scratch_bytes(int(nx), int(ny), int(nz)))
 
 
 PM_TRACK_PREDICTED, PM_TRACK_MATCHED, PM_TRACK_SUBPIX_X, PM_TRACK_SUBPIX_Y, PM_TRACK_FAIL_SAD, PM_TRACK_FAIL_GAP = 1, 2, 4, 8, 16, 32
@@ -583,6 +602,13 @@ def load():
     lib.pm_tsdf_raycast.restype = C.c_int
     lib.pm_debug_tsdf_constants.argtypes = [C.POINTER(C.c_int)] * 2
     lib.pm_debug_tsdf_constants.restype = None
+    lib.pm_tsdf_mesh.argtypes = [vp, C.POINTER(PmTsdfVolume), C.POINTER(PmTsdfMeshOptions), vp, C.c_int, C.c_int, vp, vp, vp, vp,
+                                 C.POINTER(C.c_int)]
+    lib.pm_tsdf_mesh.restype = C.c_int
+    lib.pm_debug_tsdf_mesh_table.argtypes = [vp, vp]
+    lib.pm_debug_tsdf_mesh_table.restype = None
+    lib.pm_debug_tsdf_mesh_scratch_bytes.argtypes = [C.c_int] * 3
+    lib.pm_debug_tsdf_mesh_scratch_bytes.restype = C.c_size_t
     lib.pm_track_features.argtypes = [vp, C.POINTER(PmCloudCamera), C.POINTER(PmTrackOptions), C.POINTER(PmMotion), vp, vp, vp,
                                       C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int)]
     lib.pm_track_features.restype = C.c_int
@@ -1289,6 +1315,18 @@ class Engine:
                                              d_voxels, rows, cols, d_disp_out, d_normals_out, d_counts,
                                              n if want_counts else None), "pm_tsdf_raycast")
         return n[0] if want_counts else None
+
+    def tsdf_mesh(self, volume, d_voxels, vertex_capacity=0, tri_capacity=0, min_weight=0.0, d_xyz_out=None, d_normals_out=None,
+                  d_tri_out=None, d_counts=None, want_counts=True):
+        """pm_tsdf_mesh (raw device addresses): the zero level set of the volume at d_voxels as one welded triangle mesh in the
+        world frame, on the handle's stream.  d_xyz_out, d_normals_out: [vertex_capacity][3] float32; d_tri_out: [tri_capacity][3]
+        int32 vertex slots; d_counts: two device ints; each where given.  -> (vertices, triangles), both reported beyond the
+        capacities, with want_counts (the call then synchronises), else None."""
+        o = PmTsdfMeshOptions(min_weight)
+        n = (C.c_int * 2)(-1, -1)
+        self._check(self.lib.pm_tsdf_mesh(self.h, _ref(tsdf_volume(volume)), C.byref(o), d_voxels, vertex_capacity, tri_capacity,
+                                          d_xyz_out, d_normals_out, d_tri_out, d_counts, n if want_counts else None), "pm_tsdf_mesh")
+        return (n[0], n[1]) if want_counts else None
 
     def track_features(self, camera, d_left_old, d_disp_old, d_left_new, rows, cols, guess=None, cell=16, patch_radius=3,
                        search_radius=5, min_score=1, min_disp=0.0, max_disp=0.0, max_sad=0, min_gap=0, capacity=0, d_tracks=None,
