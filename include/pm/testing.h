@@ -138,6 +138,73 @@ int pm_debug_remove_background(pm_handle* h, const uint8_t* left, const uint8_t*
 int pm_debug_tile_state(pm_handle* h, int which, int view, float* disp, float* cost, int write);
 int pm_debug_tile_last_sweep(pm_handle* h, pm_debug_sweep_variant* ran);
 
+/* ---- the device seeder between its launches (csrc/pm_seed.hpp; plan: csrc/pm_seed_plan.hpp::plan_seed) -------------------
+ * One seed map (pm_sparse_init, pm_initialize, every self-seeded Match()) is five parts on one stream: 0 the corner
+ * response and its maximum, 1 the 3x3 suppression that appends the candidate keys (value bits << 32 | y << 16 | x),
+ * 2 the greedy min-distance selection, 3 the template match of every accepted corner (behind cv::cornerSubPix where
+ * subpixel_corners is on), 4 the splat of the matched corners into the map.  The selection has three routes with one
+ * result; the route, the cell grid, the compiled-in response window and every dynamic LDS size follow from the parameters
+ * and the image size alone.  plan_seed computes them on the host, the launches are made from its result, and these hooks
+ * show it.  No kernel and no result differs for them.  The hooks with a handle run on its first seeder scratch, name
+ * themselves in their errors, return PM_ERR_BUSY between pm_capture_begin and pm_capture_end, and synchronise before
+ * they return.
+ * forced_route: 0 = the route a map takes, PM_SEED_ROUTE_* = that route, or PM_ERR_INVALID_ARG where the parameters cannot
+ * take it (a grid route with a min distance below 1, a grid beyond the LDS, rows or cols above 32768): never a fallback.
+ * pm_debug_seed_plan: the record for params and images of rows x cols; no handle, no device.  PM_ERR_INVALID_ARG (and an
+ * all-zero record): a null pointer, rows or cols below 1, a route that is refused. */
+enum { PM_SEED_ROUTE_FUSED = 1, PM_SEED_ROUTE_SORTED_GRID = 2, PM_SEED_ROUTE_SORTED_LIST = 3 };
+typedef struct pm_debug_seed_plan_record {
+  int route;            /* PM_SEED_ROUTE_*                                                                              */
+  int gx, gy;           /* cells of min_distance pixels over the image; 0 where the min distance is below 1             */
+  int select_lds;       /* dynamic LDS of the selection launch                                                          */
+  int max_features;     /* corners the selection stops at: max_features_per_frame, at most 1024                         */
+  int response_window;  /* the compiled-in box window of the response kernel (3, 5, 7); 0 = the generic loop            */
+  int tiles_x, tiles_y; /* its grid (tiles of 64 x 32 pixels)                                                           */
+  int response_lds;     /* its dynamic LDS                                                                              */
+  int match_lds;        /* dynamic LDS of the matcher: template and search stripe                                       */
+} pm_debug_seed_plan_record;
+int pm_debug_seed_plan(const pm_params* params, int rows, int cols, int forced_route, pm_debug_seed_plan_record* out);
+/* pm_debug_seed_trace: pm_sparse_init part by part; between parts it copies out what the next part reads.  Every pointer of
+ * the record may be null.  The maximum and the candidate count are read behind part 1 (the selection zeroes them).
+ * Images below 8 x 8 (down to 1 x 1), which pm_sparse_init refuses, are uploaded without the engine's preparation.
+ * PM_ERR_INVALID_ARG: a null image or record, dilate_factor outside [0, 8], a negative keys_capacity, a refused route. */
+typedef struct pm_debug_seed_trace_record {
+  float* response;       /* rows x cols, unpitched: the response plane                                                  */
+  unsigned* max_bits;    /* the maximum of the positive responses, as float bits (0: none is positive)                  */
+  int* n_candidates;     /* keys part 1 appended                                                                        */
+  uint64_t* keys;        /* ... the first min(n_candidates, keys_capacity) of them as written: in no order              */
+  int keys_capacity;
+  int* n_accepted;       /* corners the selection accepted                                                              */
+  int* xy;               /* [1024][2] ... x, y in the order of acceptance                                               */
+  float* xy_f;           /* [1024][2] their sub-pixel positions; written where subpixel_corners is on                   */
+  int* xy_rounded;       /* [1024][2] the corners the matcher and the splat read: xy, or the rounded xy_f               */
+  float* d;              /* [1024] the disparity of each corner, -1 = no match                                          */
+  int* overflow;         /* 1 = a cell of the selection's grid took a fifth corner (always 0 on the list route)         */
+  float* seed;           /* rows x cols: the seed map                                                                   */
+} pm_debug_seed_trace_record;
+int pm_debug_seed_trace(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, int dilate_factor,
+                        int forced_route, const pm_debug_seed_trace_record* trace);
+/* pm_debug_seed_select: the selection of the handle's parameters (min distance, max features, quality level) on n caller-given
+ * candidate keys -- distinct positions, any order -- as part 1 would have left them with the maximum max_bits; for the sorted
+ * routes the slots behind them are cleared.  xy: room for 1024 corners; *count of them are written.
+ * PM_ERR_INVALID_ARG: a null pointer, n below 0 or beyond the scratch's capacity (max_rows x pitch + 64), a position
+ * outside rows x cols, a value that is not in (float(max * quality), max] -- what the fused route's descent assumes --,
+ * a refused route. */
+int pm_debug_seed_select(pm_handle* h, const uint64_t* keys, int n, unsigned max_bits, int rows, int cols, int forced_route,
+                         int* xy, int* count, int* overflow);
+/* pm_debug_seed_match: the matcher alone on n <= 1024 caller-given rounded corners xy[n][2] (any integers); xy_f: null, or
+ * their sub-pixel positions [n][2], of which the matcher reads x.  d[n]: the disparity or -1. */
+int pm_debug_seed_match(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, const int* xy,
+                        const float* xy_f, int n, float* d);
+/* pm_debug_seed_splat: the memset, the splat and -- where out_rows x out_cols differs from rows x cols -- the nearest
+ * resize on n <= 1024 caller-given corners xy[n][2] (any integers) with disparities d[n]: half-width k >= 0, values scaled by
+ * inv_scale, dedup = 1: of corners on one pixel the last with d >= 0 counts (0: the largest does).  state_layout = 1: the map
+ * is written as one of the engine's state planes (four rows interleaved) and read back through that layout.  out: out_rows x
+ * out_cols.  PM_ERR_INVALID_ARG: a null pointer, n outside 0 .. 1024, k below 0, dedup or state_layout outside {0, 1}, an
+ * output larger than rows x cols or below 1 x 1, a NaN in d. */
+int pm_debug_seed_splat(pm_handle* h, const int* xy, const float* d, int n, int rows, int cols, int k, float inv_scale,
+                        int dedup, int out_rows, int out_cols, int state_layout, float* out);
+
 /* ---- what a stage of PM_MODE_PLANES launches (csrc/pm_planes_plan.hpp::plan_planes) -------------------------------------
  * One kernel template, k_planes, runs every stage of the mode, instantiated per stage, window P (3 .. 15), state type and
  * window shape; a launch's grid and dynamic LDS, and the paths the kernel takes for the launch as a whole, follow from the

@@ -2,7 +2,10 @@
 // pm_match_batch_u8 (what PatchmatchGpu::Match(cv::Mat...) does, patchmatch_gpu.cu:322-376), the pipelined
 // pm_submit_u8 / pm_collect, and the single-stage functions the parity tests drive one by one.  Staging, copies
 // and synchronisation only: every kernel is reached through the launch functions of pm_handle.hpp.
+#include <algorithm>
+#include <cmath>
 #include <cstring>
+#include <vector>
 
 #include "pm/testing.h"
 #include "pm_handle.hpp"
@@ -1062,6 +1065,232 @@ int pm_initialize(pm_handle* h, const uint8_t* left, const uint8_t* right, int r
   PM_HIP(h, seed_initialize(h->seeds[0], seed_params(h->params), ps.img8, ps.img8 + ps.plane, rows, cols, ps.pitch,
                             downsample_factor, h->st_disp_l, ocols, h->stream));
   PM_HIP(h, hipMemcpyAsync(seed, h->st_disp_l, sizeof(float) * (size_t)orows * ocols, hipMemcpyDeviceToHost, h->stream));
+  PM_HIP(h, hipStreamSynchronize(h->stream));
+  return PM_OK;
+}
+
+// ---- the seeder between its launches (include/pm/testing.h) ---------------------------------------------------------
+
+int pm_debug_seed_plan(const pm_params* params, int rows, int cols, int forced_route, pm_debug_seed_plan_record* out) {
+  if (out) *out = pm_debug_seed_plan_record{};
+  if (!params || !out || rows < 1 || cols < 1) return PM_ERR_INVALID_ARG;
+  const pm::SeedPlan pl = pm::plan_seed(seed_params(*params), rows, cols, forced_route);
+  if (pl.refused) return PM_ERR_INVALID_ARG;
+  *out = pm_debug_seed_plan_record{pl.route,           pl.gx,      pl.gy,      (int)pl.select_lds,   pl.max_features,
+                                   pl.response_window, pl.tiles_x, pl.tiles_y, (int)pl.response_lds, (int)pl.match_lds};
+  return PM_OK;
+}
+
+namespace {
+// the route `who` was asked for, or the plan's refusal as the hook's error
+int seed_route_check(pm_handle* h, const char* who, const SeedParams& sp, int rows, int cols, int forced_route) {
+  const pm::SeedPlan pl = pm::plan_seed(sp, rows, cols, forced_route);
+  if (!pl.refused) return PM_OK;
+  set_err(h, "%s: route %d at %dx%d, min distance %d: %s", who, forced_route, cols, rows, sp.min_distance, pl.refused);
+  return PM_ERR_INVALID_ARG;
+}
+// A pair for a seeder hook: prepared as pm_sparse_init prepares it, or -- below the 8 x 8 the engine's stages take, which
+// only the trace asks for (small_ok) -- copied straight into the image planes the seeder reads.
+int seed_hook_prep(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, bool small_ok, PlaneSet* ps) {
+  if (!small_ok || (rows >= 8 && cols >= 8)) return stage_prep(h, left, right, rows, cols, ps);
+  if (rows < 1 || cols < 1 || rows > h->max_rows || cols > h->max_cols) {
+    set_err(h, "request %dx%d outside 1x1 .. plan %dx%d", cols, rows, h->max_cols, h->max_rows);
+    return PM_ERR_SIZE;
+  }
+  PM_HIP(h, hipSetDevice(h->device));
+  *ps = plane_set(h, rows, cols, 1);
+  PM_HIP(h, hipMemcpy2DAsync(ps->img8, (size_t)ps->pitch, left, (size_t)cols, (size_t)cols, (size_t)rows,
+                             hipMemcpyHostToDevice, h->stream));
+  PM_HIP(h, hipMemcpy2DAsync(ps->img8 + ps->plane, (size_t)ps->pitch, right, (size_t)cols, (size_t)cols, (size_t)rows,
+                             hipMemcpyHostToDevice, h->stream));
+  return PM_OK;
+}
+// a state plane of out_rows rows (pitch elements per interleaved row) -> the caller's row-major map, through state_at
+int seed_read_state_plane(pm_handle* h, const float* d_plane, int out_rows, int out_cols, int pitch, float* out) {
+  std::vector<float> buf((size_t)align_up(out_rows, 4) * (size_t)pitch);
+  PM_HIP(h, hipMemcpyAsync(buf.data(), d_plane, sizeof(float) * buf.size(), hipMemcpyDeviceToHost, h->stream));
+  PM_HIP(h, hipStreamSynchronize(h->stream));
+  for (int y = 0; y < out_rows; ++y)
+    for (int x = 0; x < out_cols; ++x) out[(size_t)y * out_cols + x] = buf[state_at(x, y, pitch)];
+  return PM_OK;
+}
+constexpr int kSeedHookCoordMax = 1 << 20;  // caller-given corner coordinates: any integer within +- this
+}  // namespace
+
+int pm_debug_seed_trace(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, int dilate_factor,
+                        int forced_route, const pm_debug_seed_trace_record* trace) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (int rc = refuse_while_capturing(h, "pm_debug_seed_trace")) return rc;
+  if (!left || !right || !trace || dilate_factor < 0 || dilate_factor > 8 || trace->keys_capacity < 0) {
+    set_err(h, "pm_debug_seed_trace: null pointer, dilate_factor outside [0, 8] or a negative keys_capacity");
+    return PM_ERR_INVALID_ARG;
+  }
+  const SeedParams sp = seed_params(h->params);
+  if (int rc = seed_route_check(h, "pm_debug_seed_trace", sp, rows, cols, forced_route)) return rc;
+  PlaneSet ps;
+  if (int rc = seed_hook_prep(h, left, right, rows, cols, /*small_ok=*/true, &ps)) return rc;
+  const SeedScratch& sc = h->seeds[0];
+  const pm_debug_seed_trace_record& t = *trace;
+  auto part = [&](int i) {
+    return seed_sparse_init(sc, sp, ps.img8, ps.img8 + ps.plane, rows, cols, ps.pitch, dilate_factor, ps.disp, -ps.pitch,
+                            h->stream, 1u << i, forced_route);
+  };
+  unsigned counters[kSeedCounters];
+  auto read_counters = [&] { return hipMemcpyAsync(counters, sc.counters, sizeof(counters), hipMemcpyDeviceToHost, h->stream); };
+  const size_t corners = sizeof(int) * 2 * kSeedMaxFeatures;
+  // part 0: the response plane; part 1: its maximum and the candidates -- read now, the selection zeroes both counters
+  PM_HIP(h, part(0));
+  if (t.response)
+    PM_HIP(h, hipMemcpy2DAsync(t.response, sizeof(float) * cols, sc.eig, sizeof(float) * ps.pitch, sizeof(float) * cols,
+                               (size_t)rows, hipMemcpyDeviceToHost, h->stream));
+  PM_HIP(h, part(1));
+  PM_HIP(h, read_counters());
+  PM_HIP(h, hipStreamSynchronize(h->stream));
+  if (t.max_bits) *t.max_bits = counters[0];
+  if (t.n_candidates) *t.n_candidates = (int)counters[1];
+  if (t.keys) {
+    const size_t n = std::min({(size_t)counters[1], (size_t)t.keys_capacity, (size_t)sc.cap});
+    PM_HIP(h, hipMemcpyAsync(t.keys, sc.keys, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, h->stream));
+  }
+  // part 2: the accepted corners and the overflow flag
+  PM_HIP(h, part(2));
+  PM_HIP(h, read_counters());
+  if (t.xy) PM_HIP(h, hipMemcpyAsync(t.xy, sc.kp_xy, corners, hipMemcpyDeviceToHost, h->stream));
+  PM_HIP(h, hipStreamSynchronize(h->stream));
+  if (t.n_accepted) *t.n_accepted = (int)counters[2];
+  if (t.overflow) *t.overflow = (int)counters[3];
+  // part 3: sub-pixel corners, their roundings, the disparities
+  PM_HIP(h, part(3));
+  if (t.xy_f && sp.subpixel_corners)
+    PM_HIP(h, hipMemcpyAsync(t.xy_f, sc.kp_f, sizeof(float) * 2 * kSeedMaxFeatures, hipMemcpyDeviceToHost, h->stream));
+  if (t.xy_rounded) PM_HIP(h, hipMemcpyAsync(t.xy_rounded, sc.kp_xy, corners, hipMemcpyDeviceToHost, h->stream));
+  if (t.d) PM_HIP(h, hipMemcpyAsync(t.d, sc.kp_d, sizeof(float) * kSeedMaxFeatures, hipMemcpyDeviceToHost, h->stream));
+  PM_HIP(h, hipStreamSynchronize(h->stream));
+  // part 4: the map, in view 0's state plane as in pm_sparse_init
+  PM_HIP(h, part(4));
+  if (t.seed) return seed_read_state_plane(h, ps.disp, rows, cols, ps.pitch, t.seed);
+  PM_HIP(h, hipStreamSynchronize(h->stream));
+  return PM_OK;
+}
+
+int pm_debug_seed_select(pm_handle* h, const uint64_t* keys, int n, unsigned max_bits, int rows, int cols, int forced_route,
+                         int* xy, int* count, int* overflow) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (int rc = refuse_while_capturing(h, "pm_debug_seed_select")) return rc;
+  const SeedScratch& sc = h->seeds[0];
+  if (!xy || !count || !overflow || n < 0 || (n > 0 && !keys) || n > sc.cap) {
+    set_err(h, "pm_debug_seed_select: null pointer, or n = %d outside 0 .. %d (the scratch's capacity)", n, sc.cap);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (rows < 1 || cols < 1 || rows > h->max_rows || cols > h->max_cols) {
+    set_err(h, "pm_debug_seed_select: %dx%d outside 1x1 .. plan %dx%d", cols, rows, h->max_cols, h->max_rows);
+    return PM_ERR_SIZE;
+  }
+  const SeedParams sp = seed_params(h->params);
+  if (int rc = seed_route_check(h, "pm_debug_seed_select", sp, rows, cols, forced_route)) return rc;
+  // what part 1 guarantees: positions inside the image, values in (threshold, maximum] (k_seed_nms)
+  const float maxv = __builtin_bit_cast(float, max_bits);
+  const float thr = (float)((double)maxv * sp.quality_level);
+  for (int i = 0; i < n; ++i) {
+    const int x = (int)(keys[i] & 0xffffu), y = (int)((keys[i] >> 16) & 0xffffu);
+    const float v = __builtin_bit_cast(float, (unsigned)(keys[i] >> 32));
+    if (x >= cols || y >= rows || !(v > thr) || !(v <= maxv)) {
+      set_err(h, "pm_debug_seed_select: keys[%d] = (value %g, y %d, x %d): positions must lie inside %dx%d and values in "
+                 "(%g, %g]", i, (double)v, y, x, cols, rows, (double)thr, (double)maxv);
+      return PM_ERR_INVALID_ARG;
+    }
+  }
+  PM_HIP(h, hipSetDevice(h->device));
+  const unsigned counters[kSeedCounters] = {max_bits, (unsigned)n};
+  PM_HIP(h, hipMemcpyAsync(sc.counters, counters, sizeof(counters), hipMemcpyHostToDevice, h->stream));
+  sc.counters_clean = false;
+  if (n > 0) PM_HIP(h, hipMemcpyAsync(sc.keys, keys, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  // the sort of the sorted routes runs over every slot and takes 0 for "unused"
+  if (pm::plan_seed(sp, rows, cols, forced_route).route != pm::kSeedRouteFused && n < sc.cap)
+    PM_HIP(h, hipMemsetAsync(sc.keys.get() + n, 0, sizeof(uint64_t) * (size_t)(sc.cap - n), h->stream));
+  PM_HIP(h, hipStreamSynchronize(h->stream));  // (the counters above are on this function's stack)
+  PM_HIP(h, seed_sparse_init(sc, sp, nullptr, nullptr, rows, cols, align_up(cols, 64), 0, nullptr, cols, h->stream, 4u,
+                             forced_route));
+  unsigned after[kSeedCounters];
+  PM_HIP(h, hipMemcpyAsync(after, sc.counters, sizeof(after), hipMemcpyDeviceToHost, h->stream));
+  PM_HIP(h, hipMemcpyAsync(xy, sc.kp_xy, sizeof(int) * 2 * kSeedMaxFeatures, hipMemcpyDeviceToHost, h->stream));
+  PM_HIP(h, hipStreamSynchronize(h->stream));
+  *count = (int)after[2];
+  *overflow = (int)after[3];
+  return PM_OK;
+}
+
+int pm_debug_seed_match(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, const int* xy,
+                        const float* xy_f, int n, float* d) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (int rc = refuse_while_capturing(h, "pm_debug_seed_match")) return rc;
+  if (!left || !right || !xy || !d || n < 0 || n > kSeedMaxFeatures) {
+    set_err(h, "pm_debug_seed_match: null pointer, or n = %d outside 0 .. %d", n, kSeedMaxFeatures);
+    return PM_ERR_INVALID_ARG;
+  }
+  for (int i = 0; i < 2 * n; ++i)
+    if (xy[i] < -kSeedHookCoordMax || xy[i] > kSeedHookCoordMax || (xy_f && !(std::fabs(xy_f[i]) <= (float)kSeedHookCoordMax))) {
+      set_err(h, "pm_debug_seed_match: coordinate %d of corner %d beyond +-%d, or not a number", i & 1, i >> 1, kSeedHookCoordMax);
+      return PM_ERR_INVALID_ARG;
+    }
+  PlaneSet ps;
+  if (int rc = seed_hook_prep(h, left, right, rows, cols, /*small_ok=*/false, &ps)) return rc;
+  SeedScratch& sc = h->seeds[0];
+  const SeedParams sp = seed_params(h->params);
+  PM_HIP(h, seed_subpix_prepare(sc, sp, h->stream));
+  const unsigned counters[kSeedCounters] = {0u, 0u, (unsigned)n};
+  PM_HIP(h, hipMemcpyAsync(sc.counters, counters, sizeof(counters), hipMemcpyHostToDevice, h->stream));
+  sc.counters_clean = true;  // [0], [1] and [3] are zero
+  if (n > 0) {
+    PM_HIP(h, hipMemcpyAsync(sc.kp_xy, xy, sizeof(int) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    if (xy_f) PM_HIP(h, hipMemcpyAsync(sc.kp_f, xy_f, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  }
+  PM_HIP(h, hipStreamSynchronize(h->stream));  // (the counters above are on this function's stack)
+  PM_HIP(h, seed_match_corners(sc, sp, ps.img8, ps.img8 + ps.plane, rows, cols, ps.pitch, n, xy_f != nullptr, h->stream));
+  if (n > 0) PM_HIP(h, hipMemcpyAsync(d, sc.kp_d, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  PM_HIP(h, hipStreamSynchronize(h->stream));
+  return PM_OK;
+}
+
+int pm_debug_seed_splat(pm_handle* h, const int* xy, const float* d, int n, int rows, int cols, int k, float inv_scale,
+                        int dedup, int out_rows, int out_cols, int state_layout, float* out) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (int rc = refuse_while_capturing(h, "pm_debug_seed_splat")) return rc;
+  if (!out || n < 0 || n > kSeedMaxFeatures || (n > 0 && (!xy || !d)) || k < 0 || k > kSeedHookCoordMax ||
+      (dedup != 0 && dedup != 1) || (state_layout != 0 && state_layout != 1) || !(inv_scale > 0.f)) {
+    set_err(h, "pm_debug_seed_splat: null pointer, n = %d outside 0 .. %d, k = %d below 0, inv_scale not above 0, or dedup / "
+               "state_layout outside {0, 1}", n, kSeedMaxFeatures, k);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_size(h, rows, cols, 1)) return rc;
+  if (out_rows < 1 || out_cols < 1 || out_rows > rows || out_cols > cols) {
+    set_err(h, "pm_debug_seed_splat: output %dx%d outside 1x1 .. %dx%d", out_cols, out_rows, cols, rows);
+    return PM_ERR_INVALID_ARG;
+  }
+  for (int i = 0; i < n; ++i)
+    if (d[i] != d[i] || xy[2 * i] < -kSeedHookCoordMax || xy[2 * i] > kSeedHookCoordMax ||
+        xy[2 * i + 1] < -kSeedHookCoordMax || xy[2 * i + 1] > kSeedHookCoordMax) {
+      set_err(h, "pm_debug_seed_splat: corner %d: a NaN disparity or a coordinate beyond +-%d", i, kSeedHookCoordMax);
+      return PM_ERR_INVALID_ARG;
+    }
+  PM_HIP(h, hipSetDevice(h->device));
+  const PlaneSet ps = plane_set(h, rows, cols, 1);
+  const SeedScratch& sc = h->seeds[0];
+  const unsigned counters[kSeedCounters] = {0u, 0u, (unsigned)n};
+  PM_HIP(h, hipMemcpyAsync(sc.counters, counters, sizeof(counters), hipMemcpyHostToDevice, h->stream));
+  sc.counters_clean = true;  // [0], [1] and [3] are zero
+  if (n > 0) {
+    PM_HIP(h, hipMemcpyAsync(sc.kp_xy, xy, sizeof(int) * 2 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    PM_HIP(h, hipMemcpyAsync(sc.kp_d, d, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  }
+  PM_HIP(h, hipStreamSynchronize(h->stream));  // (the counters above are on this function's stack)
+  // the map: view 0's state plane (pitch of an image of out_cols columns), or a row-major map in the staging buffer
+  const int out_pitch = state_layout ? -align_up(out_cols, 64) : out_cols;
+  float* d_out = state_layout ? ps.disp : h->st_disp_l.get();
+  PM_HIP(h, seed_splat_corners(sc, n, rows, cols, ps.pitch, k, inv_scale, dedup, out_rows, out_cols, d_out, out_pitch,
+                               h->stream));
+  if (state_layout) return seed_read_state_plane(h, d_out, out_rows, out_cols, -out_pitch, out);
+  PM_HIP(h, hipMemcpyAsync(out, d_out, sizeof(float) * (size_t)out_rows * out_cols, hipMemcpyDeviceToHost, h->stream));
   PM_HIP(h, hipStreamSynchronize(h->stream));
   return PM_OK;
 }

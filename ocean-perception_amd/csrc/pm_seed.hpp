@@ -49,7 +49,7 @@ __device__ __forceinline__ int reflect101n(int p, int len) {
 // BLOCK = 3, 5, 7: compile-time window, every thread owns 8 consecutive rows of its column and forms the
 // horizontal sums of the 8 + BLOCK - 1 rows it touches once (7.5 taps per output instead of 25 for BLOCK = 5);
 // BLOCK = 0: any odd `block` <= 15, plain double loop.
-constexpr int kEigTileW = 64, kEigTileH = 32, kEigRowsPerThread = kEigTileH / 4;
+constexpr int kEigRowsPerThread = kEigTileH / 4;  // (kEigTileW x kEigTileH: pm_seed_plan.hpp)
 template <int BLOCK>
 __global__ void __launch_bounds__(256) k_seed_response(const uint8_t* __restrict__ im, int rows, int cols, int pitch,
                                                        int block_rt, int use_harris, double harris_k,
@@ -158,14 +158,10 @@ __global__ void __launch_bounds__(256) k_seed_response(const uint8_t* __restrict
   }
 }
 
-// ---- constants shared by k_seed_nms and k_seed_select_fused (see the latter)
-constexpr int kSelChunk = 2048;
-constexpr int kSelBins = 2048, kSelDigit = 11, kSelUnroll = 16;
-constexpr int kSelHist = kSelBins + kSelBins / 32;  // bin b lives at b + (b >> 5): 32-bin runs fall on distinct banks
-__host__ __device__ inline size_t seed_select_lds_bytes(int gx, int gy) {
-  return sizeof(unsigned long long) * 2 * kSelChunk + sizeof(unsigned) * (kSelHist + 8) +
-         sizeof(int) * 4 * (size_t)(gx + 2) * (gy + 2);
-}
+// ---- constants of k_seed_select_fused (see there; kSelChunk, kSelBins, kSelHist and the LDS it takes,
+// seed_select_lds_bytes: pm_seed_plan.hpp)
+constexpr int kSelDigit = 11, kSelUnroll = 16;
+static_assert(kSelBins == 1 << kSelDigit, "one bin per digit value");
 // shift of the first digit: the kSelDigit bits ending at the highest bit in which max and threshold differ
 __device__ inline int seed_first_shift(unsigned maxbits, unsigned thrbits) {
   const unsigned diff = maxbits ^ thrbits;
@@ -918,13 +914,36 @@ __global__ void __launch_bounds__(256) k_seed_resize_nearest(const float* __rest
   dst[seed_out_at(xo, yo, dst_pitch)] = src[(size_t)sy * src_pitch + sx];
 }
 
-// PM_SEED_FUSED=0 keeps the radix sort + separate selection (A/B and the fallback's own test); read once.
+// PM_SEED_FUSED=0 (tuning build) keeps the radix sort + separate selection for A/B runs; read once.  Tests reach every
+// route through plan_seed's forced_route instead (pm_debug_seed_select / pm_debug_seed_trace).
 inline bool seed_fused_enabled() {
   static const bool on = [] {
     const char* v = pm::tune_env("PM_SEED_FUSED");
     return !(v && v[0] == '0');
   }();
   return on;
+}
+
+// k_seed_match on `blocks` corners (a block beyond counters[2] returns at once)
+static void launch_seed_match(const SeedScratch& sc, const SeedParams& sp, const SeedPlan& pl, const uint8_t* left,
+                              const uint8_t* right, int rows, int cols, int pitch, int blocks, const float* kp_f,
+                              hipStream_t stream) {
+  hipLaunchKernelGGL(k_seed_match, dim3((unsigned)(blocks > 0 ? blocks : 1)), dim3(256), pl.match_lds, stream, left, right,
+                     rows, cols, pitch, sc.kp_xy, kp_f, sc.counters, sp, sc.kp_d, (const float*)sc.sp_mask, sc.sp_buf);
+}
+// k_seed_splat on `blocks` corners into the zeroed full-size plane, then the resize where the output has another size
+static void launch_seed_splat(const SeedScratch& sc, int blocks, int rows, int cols, int k, float inv_scale, int dedup,
+                              float* full, int full_pitch, bool resized, int out_rows, int out_cols, float* out,
+                              int out_pitch, hipStream_t stream) {
+  hipLaunchKernelGGL(k_seed_splat, dim3((unsigned)(blocks > 0 ? blocks : 1)), dim3(256), 0, stream, (const int*)sc.kp_xy,
+                     (const float*)sc.kp_d, (const unsigned*)sc.counters, rows, cols, k, inv_scale, full, full_pitch, dedup);
+  if (resized)
+    hipLaunchKernelGGL(k_seed_resize_nearest, dim3((unsigned)((out_cols + 255) / 256), (unsigned)out_rows), dim3(256), 0,
+                       stream, (const float*)full, rows, cols, full_pitch, out, out_rows, out_cols, out_pitch);
+}
+// elements of a plane of `rows` rows: row-major with `pitch` elements per row, or a state plane (pitch < 0)
+static size_t seed_plane_elems(int rows, int pitch) {
+  return pitch < 0 ? (size_t)((rows + 3) & ~3) * (size_t)(-pitch) : (size_t)rows * pitch;
 }
 
 // SparseInit / Initialize for one pair of pitched u8 planes: corners of `left` matched into `right`, dilated with
@@ -936,7 +955,10 @@ inline bool seed_fused_enabled() {
 // part i + 1 of either, so neither stream waits for the host to get through the other's whole sequence.
 static hipError_t seed_map(const SeedScratch& sc, const SeedParams& sp, const uint8_t* left, const uint8_t* right,
                            int rows, int cols, int pitch, int k, int out_rows, int out_cols, float inv_scale, float* out,
-                           int out_pitch, hipStream_t stream, unsigned stages) {
+                           int out_pitch, hipStream_t stream, unsigned stages, int forced_route = kSeedRouteAuto) {
+  // every launch below is made from this record (pm_seed_plan.hpp)
+  const SeedPlan pl = plan_seed(sp, rows, cols, forced_route, seed_fused_enabled());
+  if (pl.refused) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((cols + 255) / 256), (unsigned)rows), block(256);
   hipError_t e;
   if (stages & 1u) {
@@ -949,77 +971,82 @@ static hipError_t seed_map(const SeedScratch& sc, const SeedParams& sp, const ui
   const bool resized = out_rows != rows || out_cols != cols;
   float* full = resized ? sc.eig : out;
   const int full_pitch = resized ? pitch : out_pitch;
-  const size_t full_elems = full_pitch < 0 ? (size_t)((rows + 3) & ~3) * (size_t)(-full_pitch) : (size_t)rows * full_pitch;
+  const size_t full_elems = seed_plane_elems(rows, full_pitch);
   const bool zero_in_nms = !resized && full_pitch < 0 && (full_elems % 4) == 0 && ((uintptr_t)full % 16) == 0 &&
                            full_elems / 4 < 0xffffffffull;
-  const int maxf = sp.max_features < kSeedMaxFeatures ? sp.max_features : kSeedMaxFeatures;
-  const int md = sp.min_distance;
-  const int gx = md >= 1 ? (cols + md - 1) / md : 0, gy = md >= 1 ? (rows + md - 1) / md : 0;
-  // x | y << 16 packing, and squared distances (any two candidates of a batch) that fit an int
-  const bool packed_ok = md >= 1 && cols <= 32768 && rows <= 32768;
-  const bool fused = packed_ok && seed_select_lds_bytes(gx, gy) <= 150 * 1024 && seed_fused_enabled();
+  const int maxf = pl.max_features, md = sp.min_distance;
+  const bool fused = pl.route == kSeedRouteFused;
   // the sort treats 0 as "unused slot"; the fused selection only reads the first counters[1] keys
   if ((stages & 1u) && !fused &&
       (e = hipMemsetAsync(sc.keys, 0, sizeof(unsigned long long) * sc.cap, stream)) != hipSuccess)
     return e;
   if (stages & 1u) {
-    const int hb = sp.block_size / 2;
-    const size_t lds = sizeof(unsigned) * (size_t)(kEigTileW + 2 * hb) * (kEigTileH + 2 * hb);
-    const dim3 tiles((unsigned)((cols + kEigTileW - 1) / kEigTileW), (unsigned)((rows + kEigTileH - 1) / kEigTileH));
-    auto kern = sp.block_size == 3   ? k_seed_response<3>
-                : sp.block_size == 5 ? k_seed_response<5>
-                : sp.block_size == 7 ? k_seed_response<7>
-                                     : k_seed_response<0>;
-    hipLaunchKernelGGL(kern, tiles, block, lds, stream, left, rows, cols, pitch, sp.block_size, sp.use_harris,
-                       sp.harris_k, sc.eig, sc.counters);
+    auto kern = pl.response_window == 3   ? k_seed_response<3>
+                : pl.response_window == 5 ? k_seed_response<5>
+                : pl.response_window == 7 ? k_seed_response<7>
+                                          : k_seed_response<0>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)pl.tiles_x, (unsigned)pl.tiles_y), block, pl.response_lds, stream, left, rows,
+                       cols, pitch, sp.block_size, sp.use_harris, sp.harris_k, sc.eig, sc.counters);
   }
   if (stages & 2u)
     hipLaunchKernelGGL(k_seed_nms, dim3(grid.x, (unsigned)((rows + kNmsRows - 1) / kNmsRows)), block, 0, stream, sc.eig,
                        rows, cols, pitch, sp.quality_level, sc.keys, sc.counters, sc.cap,
                        zero_in_nms ? (float4*)full : (float4*)nullptr, (unsigned)(full_elems / 4));
   if ((stages & 4u) && fused) {
-    const size_t lds = seed_select_lds_bytes(gx, gy);
-    if (lds > 64 * 1024)
-      (void)hipFuncSetAttribute((const void*)k_seed_select_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k_seed_select_fused, dim3(1), dim3(1024), lds, stream, (const unsigned long long*)sc.keys,
-                       sc.cap, md, maxf, sp.quality_level, gx, gy, sc.kp_xy, sc.counters);
+    if (pl.select_lds > 64 * 1024)
+      (void)hipFuncSetAttribute((const void*)k_seed_select_fused, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)pl.select_lds);
+    hipLaunchKernelGGL(k_seed_select_fused, dim3(1), dim3(1024), pl.select_lds, stream,
+                       (const unsigned long long*)sc.keys, sc.cap, md, maxf, sp.quality_level, pl.gx, pl.gy, sc.kp_xy,
+                       sc.counters);
   } else if (stages & 4u) {
     size_t tmp_bytes = sc.sort_tmp_bytes;
     if ((e = hipcub::DeviceRadixSort::SortKeysDescending(sc.sort_tmp, tmp_bytes, sc.keys.get(), sc.keys_sorted.get(),
                                                          sc.cap, 0, 64, stream)) != hipSuccess)
       return e;
-    const size_t grid_bytes = (size_t)gx * gy * 4 * sizeof(int);
-    if (packed_ok && grid_bytes <= 150 * 1024) {  // LDS capacity
-      if (grid_bytes > 64 * 1024)
+    if (pl.route == kSeedRouteSortedGrid) {
+      if (pl.select_lds > 64 * 1024)
         (void)hipFuncSetAttribute((const void*)k_seed_select_grid, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)grid_bytes);
-      hipLaunchKernelGGL(k_seed_select_grid, dim3(1), dim3(64), grid_bytes, stream, sc.keys_sorted, sc.cap, cols, md,
-                         maxf, gx, gy, sc.kp_xy, sc.counters);
+                                  (int)pl.select_lds);
+      hipLaunchKernelGGL(k_seed_select_grid, dim3(1), dim3(64), pl.select_lds, stream, sc.keys_sorted, sc.cap, cols, md,
+                         maxf, pl.gx, pl.gy, sc.kp_xy, sc.counters);
     } else {
-      hipLaunchKernelGGL(k_seed_select, dim3(1), dim3(64), 0, stream, sc.keys_sorted, sc.cap, cols, sp.min_distance,
-                         maxf, sc.kp_xy, sc.counters);
+      hipLaunchKernelGGL(k_seed_select, dim3(1), dim3(64), 0, stream, sc.keys_sorted, sc.cap, cols, md, maxf, sc.kp_xy,
+                         sc.counters);
     }
   }
   if (stages & 4u) sc.counters_clean = hipPeekAtLastError() == hipSuccess;
   if (stages & 8u) {
-    const size_t px_bytes = 4 * ((size_t)sp.templ_rows * ((sp.templ_cols + 3) / 4) +
-                                 (size_t)(sp.templ_rows + 2) * ((sp.max_disp + 3) / 4 + 1));
     if (sp.subpixel_corners)
       hipLaunchKernelGGL(k_seed_subpix_corners, dim3((unsigned)((maxf + 63) / 64 > 0 ? (maxf + 63) / 64 : 1)), dim3(64), 0,
                          stream, left, rows, cols, pitch, sc.kp_xy, sc.kp_f, (const unsigned*)sc.counters, sp,
                          (const float*)sc.sp_mask, sc.sp_buf);
-    hipLaunchKernelGGL(k_seed_match, dim3((unsigned)(maxf > 0 ? maxf : 1)), dim3(256), px_bytes, stream, left, right,
-                       rows, cols, pitch, sc.kp_xy, sp.subpixel_corners ? (const float*)sc.kp_f : (const float*)nullptr,
-                       sc.counters, sp, sc.kp_d, (const float*)sc.sp_mask, sc.sp_buf);
+    launch_seed_match(sc, sp, pl, left, right, rows, cols, pitch, maxf,
+                      sp.subpixel_corners ? (const float*)sc.kp_f : (const float*)nullptr, stream);
   }
   if (!(stages & 16u)) return hipGetLastError();
   if (!zero_in_nms && (e = hipMemsetAsync(full, 0, sizeof(float) * full_elems, stream)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_seed_splat, dim3((unsigned)(maxf > 0 ? maxf : 1)), block, 0, stream, (const int*)sc.kp_xy,
-                     (const float*)sc.kp_d, (const unsigned*)sc.counters, rows, cols, k, inv_scale, full, full_pitch,
-                     sp.subpixel_corners);
-  if (resized)
-    hipLaunchKernelGGL(k_seed_resize_nearest, dim3((unsigned)((out_cols + 255) / 256), (unsigned)out_rows), block, 0,
-                       stream, (const float*)full, rows, cols, full_pitch, out, out_rows, out_cols, out_pitch);
+  launch_seed_splat(sc, maxf, rows, cols, k, inv_scale, sp.subpixel_corners, full, full_pitch, resized, out_rows, out_cols,
+                    out, out_pitch, stream);
+  return hipGetLastError();
+}
+hipError_t seed_match_corners(const SeedScratch& sc, const SeedParams& sp, const uint8_t* left, const uint8_t* right,
+                              int rows, int cols, int pitch, int n, bool use_kp_f, hipStream_t stream) {
+  if (n < 0 || n > kSeedMaxFeatures) return hipErrorInvalidValue;
+  // (the matcher's LDS does not depend on the route; the list route is the one no parameters refuse)
+  launch_seed_match(sc, sp, plan_seed(sp, rows, cols, kSeedRouteSortedList), left, right, rows, cols, pitch, n,
+                    use_kp_f ? (const float*)sc.kp_f : (const float*)nullptr, stream);
+  return hipGetLastError();
+}
+hipError_t seed_splat_corners(const SeedScratch& sc, int n, int rows, int cols, int pitch, int k, float inv_scale,
+                              int dedup, int out_rows, int out_cols, float* out, int out_pitch, hipStream_t stream) {
+  if (n < 0 || n > kSeedMaxFeatures) return hipErrorInvalidValue;
+  const bool resized = out_rows != rows || out_cols != cols;
+  float* full = resized ? sc.eig.get() : out;
+  const int full_pitch = resized ? pitch : out_pitch;
+  if (hipError_t e = hipMemsetAsync(full, 0, sizeof(float) * seed_plane_elems(rows, full_pitch), stream)) return e;
+  launch_seed_splat(sc, n, rows, cols, k, inv_scale, dedup, full, full_pitch, resized, out_rows, out_cols, out, out_pitch,
+                    stream);
   return hipGetLastError();
 }
 // pm_corner_subpix: the detector's window of `sp` (sc.sp_mask) on n <= kSeedMaxFeatures device points
@@ -1033,9 +1060,9 @@ hipError_t seed_corner_subpix(const SeedScratch& sc, const SeedParams& sp, const
 }
 hipError_t seed_sparse_init(const SeedScratch& sc, const SeedParams& sp, const uint8_t* left,
                                    const uint8_t* right, int rows, int cols, int pitch, int dilate_factor, float* out,
-                                   int out_pitch, hipStream_t stream, unsigned stages) {
+                                   int out_pitch, hipStream_t stream, unsigned stages, int forced_route) {
   return seed_map(sc, sp, left, right, rows, cols, pitch, (1 << dilate_factor) + 1, rows, cols, 1.0f, out, out_pitch,
-                  stream, stages);
+                  stream, stages, forced_route);
 }
 // downsample_factor >= 1
 hipError_t seed_initialize(const SeedScratch& sc, const SeedParams& sp, const uint8_t* left,

@@ -8,24 +8,13 @@
 #include <cstdint>
 
 #include "pm_devbuf.hpp"
+#include "pm_seed_plan.hpp"  // SeedParams, kSeedMaxFeatures, plan_seed
 
 namespace pm {
 
-struct SeedParams {
-  int max_features, min_distance, block_size;
-  int templ_cols, templ_rows, max_disp;
-  double quality_level, max_matching_cost;
-  int use_harris;   // corner response det(M) - k trace(M)^2 (cv::cornerHarris) instead of the smaller eigenvalue
-  double harris_k;
-  // cv::cornerSubPix on the detected corners (feature_detector.cpp:110-120) / on the match (stereo_matcher.cpp:94-103)
-  int subpixel_corners, subpix_winsize, subpix_zerozone, subpix_maxiters;
-  float subpix_epsilon;
-  int subpixel_refinement;
-};
 constexpr int kSubpixMaxWin = 15;       // largest half window of cornerSubPix the scratch is sized for
 constexpr int kSubpixMatchWin = 10;     // StereoMatcher's fixed window (stereo_matcher.cpp:97)
 
-constexpr int kSeedMaxFeatures = 1024;  // capacity of the accepted-corner list
 constexpr int kSeedCounters = 8;        // SeedScratch::counters
 constexpr int kSeedCapExtra = 64;       // candidate slots beyond one per pixel (SeedScratch::cap; no plane slack)
 constexpr int kSubpixMaskStride = 1024;  // floats between the two masks of SeedScratch::sp_mask (31 * 31 = 961)
@@ -70,13 +59,26 @@ constexpr unsigned kSeedAllStages = (1u << kSeedStages) - 1u;
 // `out`: a row-major map with out_pitch elements per row, or -- out_pitch < 0 -- one of the engine's state planes (four
 // rows interleaved, pm_device.hpp::state_at, pitch -out_pitch).
 // PatchmatchGpu::SparseInit(iml, imr, f)  (patchmatch_gpu.cu:414-442): dilation half-width 2^f + 1, map at image size
+// forced_route (pm_seed_plan.hpp::SeedRoute; the test hooks): the selection route instead of the plan's own choice;
+// hipErrorInvalidValue where the plan refuses it.
 hipError_t seed_sparse_init(const SeedScratch& sc, const SeedParams& sp, const uint8_t* left, const uint8_t* right,
                             int rows, int cols, int pitch, int dilate_factor, float* out, int out_pitch,
-                            hipStream_t stream, unsigned stages = kSeedAllStages);
+                            hipStream_t stream, unsigned stages = kSeedAllStages, int forced_route = kSeedRouteAuto);
 // Patchmatch::Initialize(iml, imr, f)  (patchmatch.cpp:60-84): half-width 2^(f-1) + 1, map of size / f, scaled by 2^-f;
 // downsample_factor >= 1
 hipError_t seed_initialize(const SeedScratch& sc, const SeedParams& sp, const uint8_t* left, const uint8_t* right,
                            int rows, int cols, int pitch, int downsample_factor, float* out, int out_pitch,
                            hipStream_t stream, unsigned stages = kSeedAllStages);
+
+// ---- single launches of the sequence on the scratch as the caller filled it (the test hooks of include/pm/testing.h)
+// k_seed_match alone on the n <= kSeedMaxFeatures corners in sc.kp_xy (use_kp_f: with their sub-pixel positions in
+// sc.kp_f); counters[2] must hold n.  Results in sc.kp_d.
+hipError_t seed_match_corners(const SeedScratch& sc, const SeedParams& sp, const uint8_t* left, const uint8_t* right,
+                              int rows, int cols, int pitch, int n, bool use_kp_f, hipStream_t stream);
+// The memset, k_seed_splat and -- where out_rows x out_cols differs from rows x cols -- k_seed_resize_nearest on the
+// n <= kSeedMaxFeatures corners in sc.kp_xy / sc.kp_d; counters[2] must hold n.  `pitch`: of the full-size plane a
+// resize starts from (sc.eig).
+hipError_t seed_splat_corners(const SeedScratch& sc, int n, int rows, int cols, int pitch, int k, float inv_scale,
+                              int dedup, int out_rows, int out_cols, float* out, int out_pitch, hipStream_t stream);
 
 }  // namespace pm

@@ -58,6 +58,7 @@ EXPORTS = [
     "pm_debug_match_plan",
     "pm_debug_sweep_plan", "pm_debug_segment_bounds", "pm_debug_propagate_hinted", "pm_debug_match_sweep_hint", "pm_debug_read_stops", "pm_debug_noise_cost_constants", "pm_debug_noise_cost", "pm_debug_remove_background",
     "pm_remove_background", "pm_mask_occlusions", "pm_foreground_texture_mask", "pm_sparse_init", "pm_corner_subpix", "pm_profile_enable", "pm_profile_read",
+    "pm_debug_seed_plan", "pm_debug_seed_trace", "pm_debug_seed_select", "pm_debug_seed_match", "pm_debug_seed_splat",
     "pm_kernel_name", "pm_debug_counters", "pm_debug_counters_enable",
     "pm_tile_begin", "pm_tile_noise", "pm_tile_sweep", "pm_tile_snapshot", "pm_tile_restore", "pm_tile_get_row",
     "pm_tile_set_row", "pm_tile_background", "pm_tile_finish", "pm_tile_restore_cols", "pm_tile_sweep_masked",
@@ -153,6 +154,22 @@ class PmDebugMatchRoute(C.Structure):  # include/pm/testing.h
     _fields_ = [("route", C.c_int), ("n_views", C.c_int), ("self_seed", C.c_int * 2), ("pair_chunk", C.c_int),
                 ("head_aside", C.c_int), ("lane_pairs", C.c_int * 2), ("seq_chunks", C.c_int), ("seq_hold", C.c_int),
                 ("need_view_events", C.c_int), ("need_slot_events", C.c_int), ("need_second_seed_scratch", C.c_int)]
+
+
+class PmDebugSeedPlan(C.Structure):  # include/pm/testing.h: pm_debug_seed_plan_record
+    _fields_ = [(name, C.c_int) for name in ("route", "gx", "gy", "select_lds", "max_features", "response_window", "tiles_x",
+                                             "tiles_y", "response_lds", "match_lds")]
+
+
+class PmDebugSeedTrace(C.Structure):  # include/pm/testing.h: pm_debug_seed_trace_record
+    _fields_ = [("response", C.c_void_p), ("max_bits", C.c_void_p), ("n_candidates", C.c_void_p), ("keys", C.c_void_p),
+                ("keys_capacity", C.c_int), ("n_accepted", C.c_void_p), ("xy", C.c_void_p), ("xy_f", C.c_void_p),
+                ("xy_rounded", C.c_void_p), ("d", C.c_void_p), ("overflow", C.c_void_p), ("seed", C.c_void_p)]
+
+
+# the selection routes of the seeder (csrc/pm_seed_plan.hpp::SeedRoute); 0 = the route a map takes
+SEED_ROUTE_AUTO, SEED_ROUTE_FUSED, SEED_ROUTE_SORTED_GRID, SEED_ROUTE_SORTED_LIST = 0, 1, 2, 3
+SEED_MAX_FEATURES = 1024   # csrc/pm_seed_plan.hpp::kSeedMaxFeatures
 
 
 # pm_debug_match_route.route (csrc/pm_match_plan.hpp::MatchRoute)
@@ -678,6 +695,18 @@ def load():
     lib.pm_corner_subpix.restype = C.c_int
     lib.pm_sparse_init.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, C.c_int, f32p]
     lib.pm_sparse_init.restype = C.c_int
+    lib.pm_debug_seed_plan.argtypes = [C.POINTER(PmParams), C.c_int, C.c_int, C.c_int, C.POINTER(PmDebugSeedPlan)]
+    lib.pm_debug_seed_plan.restype = C.c_int
+    lib.pm_debug_seed_trace.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PmDebugSeedTrace)]
+    lib.pm_debug_seed_trace.restype = C.c_int
+    lib.pm_debug_seed_select.argtypes = [vp, vp, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int)]
+    lib.pm_debug_seed_select.restype = C.c_int
+    lib.pm_debug_seed_match.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, vp, vp, C.c_int, vp]
+    lib.pm_debug_seed_match.restype = C.c_int
+    lib.pm_debug_seed_splat.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, vp]
+    lib.pm_debug_seed_splat.restype = C.c_int
     lib.pm_initialize.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, C.c_int, f32p]
     lib.pm_initialize.restype = C.c_int
     lib.pm_tile_begin.argtypes = [vp, C.POINTER(PmTile), u8p, u8p, C.c_int, C.c_int, f32p, f32p]
@@ -807,6 +836,17 @@ def match_plan(params, n=1, seed_l=False, seed_r=False, bgr=False):
         raise PmError(rc, "pm_debug_match_plan")
     rec = {name: getattr(out, name) for name, _ in PmDebugMatchRoute._fields_}
     return {k: tuple(v) if not isinstance(v, int) else v for k, v in rec.items()}
+
+
+def seed_plan(params, rows, cols, forced_route=SEED_ROUTE_AUTO):
+    """pm_debug_seed_plan: what the launches of one seed map look like -- the selection route, its grid and LDS, the response
+    kernel's window, grid and LDS, the matcher's LDS -- from the host-side plan alone (no handle, no device) -> a dict of
+    the fields of pm_debug_seed_plan_record.  A forced route the parameters cannot take raises PmError (INVALID_ARG)."""
+    out = PmDebugSeedPlan()
+    rc = load().pm_debug_seed_plan(C.byref(params), rows, cols, forced_route, C.byref(out))
+    if rc != PM_OK:
+        raise PmError(rc, "pm_debug_seed_plan")
+    return {n: getattr(out, n) for n, _ in PmDebugSeedPlan._fields_}
 
 
 def sweep_plan(params, rows, cols, patch_h, patch_w, pass_index, slots=1, amp=1e30):
@@ -1506,6 +1546,66 @@ class Engine:
         self._check(self.lib.pm_sparse_init(self.h, pl, pr, left.shape[0], left.shape[1], dilate_factor,
                                             seed.ctypes.data_as(C.c_void_p)), "pm_sparse_init")
         return seed
+
+    def debug_seed_trace(self, left, right, dilate_factor=4, forced_route=SEED_ROUTE_AUTO, keys_capacity=None):
+        """pm_sparse_init part by part (pm_debug_seed_trace, include/pm/testing.h) -> a dict: response (rows x cols), max_bits,
+        keys (uint64, as written: unsorted; all of them unless keys_capacity cuts them), n_candidates, xy (accepted corners,
+        [n][2] x, y), xy_f (None unless subpixel_corners), xy_rounded, d, overflow, seed."""
+        left, pl = _u8(left)
+        right, pr = _u8(right)
+        rows, cols = left.shape
+        cap = rows * cols if keys_capacity is None else keys_capacity
+        resp, seed = np.empty((rows, cols), np.float32), np.empty((rows, cols), np.float32)
+        keys = np.zeros(max(cap, 1), np.uint64)
+        xy, xy_r = np.zeros((SEED_MAX_FEATURES, 2), np.int32), np.zeros((SEED_MAX_FEATURES, 2), np.int32)
+        xy_f, d = np.zeros((SEED_MAX_FEATURES, 2), np.float32), np.zeros(SEED_MAX_FEATURES, np.float32)
+        max_bits, ncand, nacc, ovf = C.c_uint(0), C.c_int(-1), C.c_int(-1), C.c_int(-1)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        adr = lambda v: C.cast(C.pointer(v), C.c_void_p)
+        t = PmDebugSeedTrace(ptr(resp), adr(max_bits), adr(ncand), ptr(keys), cap, adr(nacc), ptr(xy), ptr(xy_f), ptr(xy_r),
+                             ptr(d), adr(ovf), ptr(seed))
+        self._check(self.lib.pm_debug_seed_trace(self.h, pl, pr, rows, cols, dilate_factor, forced_route, C.byref(t)),
+                    "pm_debug_seed_trace")
+        n = nacc.value
+        return dict(response=resp, max_bits=max_bits.value, n_candidates=ncand.value, keys=keys[:min(ncand.value, cap)].copy(),
+                    n_accepted=n, xy=xy[:n].copy(), xy_f=xy_f[:n].copy() if self.params.subpixel_corners else None,
+                    xy_rounded=xy_r[:n].copy(), d=d[:n].copy(), overflow=ovf.value, seed=seed)
+
+    def debug_seed_select(self, keys, max_bits, rows, cols, forced_route=SEED_ROUTE_AUTO):
+        """The selection of this handle's parameters on caller-given candidate keys (pm_debug_seed_select) ->
+        (xy [count][2], overflow)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        xy = np.zeros((SEED_MAX_FEATURES, 2), np.int32)
+        count, ovf = C.c_int(-1), C.c_int(-1)
+        self._check(self.lib.pm_debug_seed_select(self.h, keys.ctypes.data_as(C.c_void_p), len(keys), max_bits, rows, cols,
+                                                  forced_route, xy.ctypes.data_as(C.c_void_p), C.byref(count), C.byref(ovf)),
+                    "pm_debug_seed_select")
+        return xy[:count.value].copy(), ovf.value
+
+    def debug_seed_match(self, left, right, xy, xy_f=None):
+        """The matcher alone on caller-given rounded corners xy [n][2] (pm_debug_seed_match); xy_f: their sub-pixel
+        positions or None -> d [n]."""
+        left, pl = _u8(left)
+        right, pr = _u8(right)
+        xy = np.ascontiguousarray(xy, dtype=np.int32).reshape(-1, 2)
+        f = np.ascontiguousarray(xy_f, dtype=np.float32).reshape(-1, 2) if xy_f is not None else None
+        assert f is None or f.shape == xy.shape
+        d = np.zeros(len(xy), np.float32)
+        self._check(self.lib.pm_debug_seed_match(self.h, pl, pr, left.shape[0], left.shape[1], xy.ctypes.data_as(C.c_void_p),
+                                                 f.ctypes.data_as(C.c_void_p) if f is not None else None, len(xy),
+                                                 d.ctypes.data_as(C.c_void_p)), "pm_debug_seed_match")
+        return d
+
+    def debug_seed_splat(self, xy, d, rows, cols, k, inv_scale=1.0, dedup=0, out_shape=None, state_layout=0):
+        """The memset, the splat and the nearest resize on caller-given corners (pm_debug_seed_splat) -> the map."""
+        xy = np.ascontiguousarray(xy, dtype=np.int32).reshape(-1, 2)
+        d = np.ascontiguousarray(d, dtype=np.float32)
+        assert d.shape == (len(xy),)
+        out = np.empty(out_shape or (rows, cols), np.float32)
+        self._check(self.lib.pm_debug_seed_splat(self.h, xy.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), len(xy),
+                                                 rows, cols, k, inv_scale, dedup, out.shape[0], out.shape[1], state_layout,
+                                                 out.ctypes.data_as(C.c_void_p)), "pm_debug_seed_splat")
+        return out
 
     def corner_subpix(self, image, xs, ys):
         image, p = _u8(image)

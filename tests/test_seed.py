@@ -260,8 +260,11 @@ def test_full_size_seeding(pm, oracle, synth):
 @pytest.mark.gpu
 @pytest.mark.parametrize("max_features,min_distance", [(1000, 3), (1024, 1), (300, 40)])
 def test_selection_across_many_chunks(pm, oracle, max_features, min_distance):
-    """The fused sort + selection consumes the candidates in chunks of 2048: white noise gives tens of thousands of
-    candidates, many of them with equal responses, and small min_distance / many features walks several chunks."""
+    """White noise gives tens of thousands of candidates, many of them with equal responses.  At 480 x 752 the case
+    (300, 40) runs the fused sort + selection, which consumes them in chunks of up to 2048 keys (here 1200: four
+    times max_features).  The grids of (1000, 3) and (1024, 1) would take 627 KB and 5.7 MB of LDS: those two run the
+    full radix sort and the LIST selection, through a thousand accepted corners (tests/test_seed_stages.py pins the
+    routes on the plan and walks the fused selection's chunks on synthetic keys)."""
     rows, cols = 480, 752
     rng = np.random.default_rng(99)
     left = rng.integers(0, 256, (rows, cols), dtype=np.uint8)

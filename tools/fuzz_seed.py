@@ -22,6 +22,31 @@ ap.add_argument("--dump", action="store_true", help="with --only: print where th
 a = ap.parse_args()
 pm.load()
 oracle.load()
+
+
+def first_difference(t, left, right, sp, want):
+    """The first part of the device's sequence (Engine.debug_seed_trace) whose result is not the oracle's: the corner
+    list, the sub-pixel corners, the per-corner disparities, the map -- or None."""
+    xs, ys = oracle.gftt_detect(left, sp)
+    if not np.array_equal(t["xy"], np.stack([xs, ys], axis=1).reshape(-1, 2)):
+        return f"detection: {t['n_accepted']} corners of {t['n_candidates']} candidates, the oracle finds {len(xs)}"
+    if t["overflow"]:
+        return "selection: a grid cell overflowed"
+    fx, fy = xs.astype(np.float32), ys.astype(np.float32)
+    if sp.subpixel_corners:
+        fx, fy = oracle.corner_subpix(left, fx, fy, sp.subpix_winsize, sp.subpix_zerozone, sp.subpix_maxiters, sp.subpix_epsilon)
+        if not np.array_equal(t["xy_f"].view(np.uint32), np.stack([fx, fy], axis=1).reshape(-1, 2).view(np.uint32)):
+            return "sub-pixel corners"
+    d = np.array([oracle.match_rectified(left, right, float(x), float(y), sp) for x, y in zip(fx, fy)], np.float32)
+    if not np.array_equal(t["d"].view(np.uint32), d.view(np.uint32)):
+        bad = np.flatnonzero(t["d"] != d)
+        return f"matcher: {bad.size} of {len(d)} disparities, first corner {bad[0]} at ({fx[bad[0]]}, {fy[bad[0]]}): " \
+               f"{t['d'][bad[0]]} vs {d[bad[0]]}"
+    if not np.array_equal(t["seed"], want):
+        return "splat"
+    return None
+
+
 rng = np.random.default_rng(a.seed)
 t0 = time.time()
 for case in range(a.cases):
@@ -75,11 +100,14 @@ for case in range(a.cases):
     want = oracle.sparse_init(left, right, f, sp)
     with pm.Engine(prm, max_rows=rows, max_cols=cols) as e:
         got = e.sparse_init(left, right, f)
-    ok = np.array_equal(got, want)
+        trace = e.debug_seed_trace(left, right, f)
+    stage = first_difference(trace, left, right, sp, want)
+    ok = np.array_equal(got, want) and stage is None
     print(f"case {case:3d}: {cols}x{rows} kind {kind} maxf {maxf} mind {mind} q {q} block {blk} templ {tc}x{tr} "
           f"max_disp {md} f {f} harris {harris} subpix {spc}{spr} win {swin} seeds {(want > 0).mean():.3f} {'ok' if ok else 'MISMATCH'}  [{time.time() - t0:.0f} s]",
           flush=True)
     if not ok:
+        print("first stage that differs:", stage or "none of the trace's -- pm_sparse_init's map alone")
         if a.dump:
             bad = np.argwhere(got != want)
             print(len(bad), "pixels differ; first:", bad[:5].tolist(), got[tuple(bad[0])], want[tuple(bad[0])])
