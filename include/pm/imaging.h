@@ -832,6 +832,86 @@ int pm_tsdf_mesh(pm_handle* h, const pm_tsdf_volume* volume, const pm_tsdf_mesh_
                  int* d_counts /* device int[2]: vertices, triangles; may be NULL */,
                  int* counts /* host int[2], may be NULL: non-NULL synchronises */);
 
+/* ---- dense frame-to-model alignment: the pose of a new map against a render of the model, or against an earlier map ------------
+ * What it is for: pm_tsdf_integrate folds a map into the model at its pose and pm_tsdf_raycast renders the model at any pose; the
+ * pose has to come from somewhere.  pm_estimate_motion tracks sparse texture between two consecutive frames, and chained frame to
+ * frame its errors add up.  pm_align_disparity registers the NEW frame's disparity map against the MODEL's map and camera-facing
+ * normals (pm_tsdf_raycast's outputs, or any earlier map with pm_disparity_normals / pm_planes_normals): point-to-plane
+ * Gauss-Newton with projective association, every pixel a residual, no texture needed.  The motion goes from the MODEL camera frame
+ * into the NEW camera frame, X_new = R X_model + t -- pm_reproject_disparity's convention, so the result goes to that stage
+ * unchanged; the pose of a frame aligned against a render at pose_ref is pm_motion_compose(M, pose_ref).
+ * Held to its CPU definition (tests/align_ref.py) BIT FOR BIT.  Binary64 unless it says binary32, one rounding per operation,
+ * parentheses as written; fxB = fx * baseline formed once.  Per model pixel (x, y), independent of every other pixel:
+ *   model     d = Dm(y, x) counts iff d > 0 && d >= min_disp; n = Nm(y, x, :) counts iff its three components are finite and not
+ *             all zero; P = pm_reproject_disparity's point of (d, x, y).  Otherwise the class is NO_MODEL (0).
+ *   project   EXACTLY pm_reproject_disparity's `splat` arithmetic from its motion line on, with max_disp = 0: Q = (Xn, Yn, Zn),
+ *             dq = (float)(fxB / Zn), (iu, iv).  A dropped pixel has class OUTSIDE (1).
+ *   measure   d2 = Dn(iv, iu) counts iff d2 > 0 && d2 >= min_disp; otherwise UNMEASURED (2).
+ *   gate      fabs((double)dq - (double)d2) <= (double)max_diff; otherwise GATED (3): occlusions and what came into view.
+ *   point     P2 = the point of (d2, iu, iv), in the new frame.
+ *   normal    m_i = ((R[3i]*(double)n0) + (R[3i+1]*(double)n1)) + (R[3i+2]*(double)n2).
+ *   residual  e = ((m0*(Qx-P2x)) + (m1*(Qy-P2y))) + (m2*(Qz-P2z)), metres;  s = (P2z*P2z) / fxB, the metres per pixel of
+ *             disparity at the measurement (stereo depth noise grows with Z^2);  r = e / s, pixels of disparity.
+ *   row       a0 = (P2y*m2) - (P2z*m1); a1 = (P2z*m0) - (P2x*m2); a2 = (P2x*m1) - (P2y*m0);  J = (a0, a1, a2, m0, m1, m2), each
+ *             / s: the derivative of r under pm_solve_motion's left perturbation Q' = Q + omega x Q + upsilon, the normal turning
+ *             with it; delta = (omega, upsilon).
+ *   weight    ar = fabs(r); w = 1.0 if ar <= huber_px, else huber_px / ar.
+ *   terms     28: H_jk = (w*J_j)*J_k for j <= k, row-major upper triangle (21); g_j = (w*J_j)*r (6); r*r (1).  The class is
+ *             USED (4).  A pixel of any other class contributes +0.0 to all 28.
+ *   planes    d_class_out: the class; d_residual_out: (float)r for USED, +0.0f elsewhere.
+ * The sum -- its order is part of the definition, binary64 addition not being associative.  With C = ceil(cols / 64): lane sums
+ * A[y][l] = sum over c ascending from +0.0 of term(y, 64c + l), pixels at or beyond cols being +0.0; the row sum is the balanced
+ * binary tree over l, s[i] = s[2i] + s[2i+1] six times; the total adds the row sums in ascending y from +0.0.  Counts: the model
+ * pixels (class != NO_MODEL), the pixels that reached the gate (GATED + USED) and the USED pixels.
+ * The solve is pm_solve_motion's, shared with it: H delta = -g by LDL^T without pivoting, which fails iff a pivot is not > 0; the
+ * Cayley update; it stops after the update when max |delta_i| < epsilon, or after `iterations` updates.  One more evaluation under
+ * the motion reached gives the counts, rms_px = sqrt(sum_rr / n_used) (0 without a used pixel) and the 21 entries of H -- the
+ * information matrix a caller's pose filter wants.  valid iff no factorisation failed and n_used >= min_used; otherwise the call
+ * returns PM_OK with info->valid == 0 and *out equal to the guess (pm_solve_motion's rule: no new status code).
+ * pm_align_evaluate: one evaluation under `motion`; it only enqueues on the handle's stream (a non-NULL host `sums`
+ * synchronises) and is valid in every mode.  Two launches behind a 16-byte memset; no atomics on floating-point values and no
+ * cross-workgroup waits, so the record is a pure function of the inputs.  pm_align_step (host, no handle): one solve and update
+ * from a record; where the factorisation fails it returns PM_OK with *out = *in, delta all +0.0 and *factorised = 0.
+ * pm_align_disparity loops the two and always synchronises.  pm_motion_compose (host, no handle): X -> a(b(X)),
+ * R_ij = ((a_i0*b_0j) + (a_i1*b_1j)) + (a_i2*b_2j); t_i = (((a_i0*bt0) + (a_i1*bt1)) + (a_i2*bt2)) + at_i; out may alias a or b.
+ * Scratch: `rows` row sums of 28 doubles behind a 256-byte slot for the record, ONE handle-owned allocation made on first use, reused, grown
+ * under a stream synchronisation and released with the handle, and one record of page-locked host memory for the downloads.
+ * PM_ERR_INVALID_ARG, with pm_last_error naming the argument and nothing enqueued: a null required pointer; a camera pm_backproject
+ * refuses; a non-finite entry of the motion; options outside their ranges below, NaN included (min_disp: NaN); rows or cols < 1;
+ * no output at all.  PM_ERR_SIZE as for pm_backproject.  The host-only calls report a refusal by their status alone. */
+enum { PM_ALIGN_NO_MODEL = 0, PM_ALIGN_OUTSIDE = 1, PM_ALIGN_UNMEASURED = 2, PM_ALIGN_GATED = 3, PM_ALIGN_USED = 4 };
+typedef struct pm_align_options {
+  float min_disp;
+  float max_diff;     /* >= 0, finite: the gate, in pixels of disparity */
+  double huber_px;    /* > 0 */
+  int iterations;     /* 1..50 */
+  double epsilon;     /* >= 0 */
+  int min_used;       /* >= 6 */
+} pm_align_options;
+typedef struct pm_align_sums {   /* 240 bytes */
+  double H[21], g[6], rr;
+  int n_model, n_gate, n_used, pad;
+} pm_align_sums;
+typedef struct pm_align_info {
+  int valid, n_model, n_gate, n_used, iterations;
+  double rms_px;
+  double H[21];
+} pm_align_info;
+
+int pm_align_evaluate(pm_handle* h, const pm_cloud_camera* camera, const pm_align_options* options,
+                      const pm_motion* motion /* NULL = identity */, const float* d_disp_model,
+                      const float* d_normals_model /* [rows][cols][3] */, const float* d_disp_new, int rows, int cols,
+                      uint8_t* d_class_out /* may be NULL */, float* d_residual_out /* may be NULL */,
+                      pm_align_sums* d_sums /* device, may be NULL */,
+                      pm_align_sums* sums /* host, may be NULL: non-NULL synchronises */);
+int pm_align_step(const pm_align_sums* sums, const pm_motion* in /* NULL = identity */, pm_motion* out,
+                  double delta[6] /* may be NULL */, int* factorised /* may be NULL */);   /* host only, no handle */
+int pm_align_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_align_options* options,
+                       const pm_motion* guess /* NULL = identity */, const float* d_disp_model, const float* d_normals_model,
+                       const float* d_disp_new, int rows, int cols, pm_motion* out /* may be NULL */,
+                       pm_align_info* info /* may be NULL */);
+int pm_motion_compose(const pm_motion* a, const pm_motion* b, pm_motion* out);           /* host only, no handle */
+
 /* ---- device buffers for host code that does not include HIP (host/imaging.hpp uses them) ------------------
  * pm_device_malloc / pm_device_free wrap hipMalloc / hipFree on the handle's device; pm_upload / pm_download are
  * stream-ordered copies on the handle's stream from / to pageable host memory (pm_download returns after the

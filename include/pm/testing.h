@@ -293,6 +293,12 @@ void pm_debug_tsdf_constants(int* lanes, int* waves);
 void pm_debug_tsdf_mesh_table(uint8_t* counts /* [256] */, uint8_t* codes /* [256][36] */);
 size_t pm_debug_tsdf_mesh_scratch_bytes(int nx, int ny, int nz);
 
+/* ---- the launch constants of pm_align_evaluate (csrc/pm_align_body.hpp) and its scratch -------------------------------------------
+ * lanes: the lane sums of a row, one wavefront per row; waves: the rows of a block.  pm_debug_align_scratch_bytes: the bytes of
+ * device scratch a call on a map of `rows` rows reserves.  No handle, no device. */
+void pm_debug_align_constants(int* lanes, int* waves);
+size_t pm_debug_align_scratch_bytes(int rows);
+
 /* ---- the row-tiled driver's device discipline, provable on ONE GPU ------------------------------------------------
  * pm_tiled_create with the bands accounted to LOGICAL devices: band k lives on logical_devices[k] (>= 0; several bands
  * may share one) while every HIP call still goes to the physical device of the band's handle.  Such a plan logs every

@@ -10,6 +10,7 @@
 #include <new>
 
 #include "pm_devbuf.hpp"
+#include "pm_hipres.hpp"
 #include "pm_internal.hpp"
 
 namespace pm {
@@ -64,6 +65,10 @@ struct ImagingState {
   // per 64-node span of a row, for the vertices and for the triangles each (its count, then its offset), one word per node (its vertex mask and its rank in
   // the span), one byte per node (its crossing edges and whether its cell is live)
   DevBuf<int> tsdf_mesh_buf;
+  // pm_align_evaluate / pm_align_disparity: a 256-byte slot for the record (pm_align_sums; its counts are where the launch adds
+  // them, cleared per call), then one row sum of 28 doubles per row; and the page-locked record the downloads land in
+  DevBuf<char> align_buf;
+  HostBuf align_host;
 };
 
 #define PM_HIP(h, call)                                                                                     \

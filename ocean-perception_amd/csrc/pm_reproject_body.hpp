@@ -78,10 +78,12 @@ __host__ __device__ __forceinline__ bool reproject_point(const CloudCam& c, floa
 
 // Second half: P through X_new = R X + t and into the rows x cols image of the same camera: the pixel it lands on and the
 // disparity it has there.  `ok`: the first half's answer; false where the point is dropped, and (iu, iv) is then (0, 0).
-// Where asked for (pm_fuse_disparity, pm_fuse_body.hpp), the depth Zn in the new frame in *zn.
+// Where asked for (pm_fuse_disparity, pm_fuse_body.hpp), the depth Zn in the new frame in *zn; where asked for
+// (pm_align_disparity, pm_align_body.hpp), the rest of the point in the new frame in *xn and *yn.
 __host__ __device__ __forceinline__ bool reproject_project(const CloudCam& c, const double R[9], const double t[3],
                                                            float max_disp, int rows, int cols, bool ok, const double P[3],
-                                                           int* iu, int* iv, float* dn, double* zn = nullptr) {
+                                                           int* iu, int* iv, float* dn, double* zn = nullptr,
+                                                           double* xn = nullptr, double* yn = nullptr) {
   const double X = P[0], Y = P[1], Z = P[2];
   const double Xn = (((R[0] * X) + (R[1] * Y)) + (R[2] * Z)) + t[0];
   const double Yn = (((R[3] * X) + (R[4] * Y)) + (R[5] * Z)) + t[1];
@@ -99,6 +101,8 @@ __host__ __device__ __forceinline__ bool reproject_project(const CloudCam& c, co
   *iv = ok ? (int)rw : 0;
   *dn = v;
   if (zn) *zn = Zn;
+  if (xn) *xn = Xn;
+  if (yn) *yn = Yn;
   return ok;
 }
 

@@ -1,7 +1,7 @@
 // pm_stages.hip -- C-ABI implementation of the stages of include/pm/imaging.h that read a finished disparity map: points,
 // plane-mode normals and the compacted cloud, the windowed plane fit, the speckle filter, the grid mesh, the temporal
-// seeds, the consistency filter, the matching confidence, the sequence fusion, the TSDF volume with its mesh and the feature
-// tracks of the motion estimate.  Like pm_imaging.hip it reaches the handle only through pm_internal.hpp, and it shares that unit's one
+// seeds, the consistency filter, the matching confidence, the sequence fusion, the TSDF volume with its mesh, the feature
+// tracks of the motion estimate and the dense alignment of a map against a model.  Like pm_imaging.hip it reaches the handle only through pm_internal.hpp, and it shares that unit's one
 // state object (pm_imaging_state.hpp).  Every entry point: its argument checks in a fixed order (the first fault is the one
 // reported), then the device, then its launches on the handle's stream.
 #include "pm/imaging.h"
@@ -12,10 +12,12 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <initializer_list>
 #include <new>
 #include <vector>
 
+#include "pm_align.hpp"
 #include "pm_cloud.hpp"
 #include "pm_confidence.hpp"
 #include "pm_consistency.hpp"
@@ -1149,3 +1151,156 @@ int pm_estimate_motion(pm_handle* h, const pm_cloud_camera* camera, const pm_tra
   if (rc != PM_OK) set_err(h, "%s: pm_solve_motion refused its arguments", what);
   return rc;
 }
+
+// ---- dense alignment: a new map registered against the model's map and normals (pm_align.hpp) ---------------------------------
+namespace {
+constexpr size_t kAlignRecordSlot = 256;  // the record in front of the row sums, which stay 16-byte aligned behind it
+static_assert(sizeof(pm_align_sums) <= kAlignRecordSlot, "the record fits its slot");
+
+size_t align_scratch_bytes(int rows) { return kAlignRecordSlot + sizeof(double) * kAlignTerms * (size_t)rows; }
+
+// what pm_align_evaluate and pm_align_disparity are both given
+struct AlignInputs {
+  const pm_cloud_camera* camera;
+  const pm_align_options* options;
+  const pm_motion* motion;  // null: the identity
+  const float* disp_model;
+  const float* normals_model;
+  const float* disp_new;
+  int rows, cols;
+};
+
+// The checks of everything but the outputs, in a fixed order; `whose`: the motion as the message names it.
+int check_align(pm_handle* h, const char* what, const AlignInputs& in, const char* whose) {
+  const pm_align_options* o = in.options;
+  if (int rc = check_cloud_camera(h, what, in.camera)) return rc;
+  if (int rc = check_not_null(h, what, {{"options", o}, {"d_disp_model", in.disp_model}, {"d_normals_model", in.normals_model},
+                                        {"d_disp_new", in.disp_new}}))
+    return rc;
+  if (in.motion)
+    if (int rc = check_motion(h, what, *in.motion, whose)) return rc;
+  if (std::isnan(o->min_disp)) {
+    set_err(h, "%s: min_disp must not be NaN", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_max_diff(h, what, o->max_diff)) return rc;
+  if (!(o->huber_px > 0.0) || !(o->epsilon >= 0.0)) {
+    set_err(h, "%s: %s and not NaN", what, !(o->huber_px > 0.0) ? "huber_px must be > 0" : "epsilon must be >= 0");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (o->iterations < 1 || o->iterations > 50) {
+    set_err(h, "%s: iterations %d outside 1..50", what, o->iterations);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (o->min_used < 6) {
+    set_err(h, "%s: min_used %d must be >= 6", what, o->min_used);
+    return PM_ERR_INVALID_ARG;
+  }
+  return check_cloud_shape(h, what, in.rows, in.cols);
+}
+
+// One evaluation behind the checks: the 16-byte memset of the counts and the two launches.  *d_record: the handle's record.
+int run_align(pm_handle* h, const char* what, const AlignInputs& in, const pm_motion* motion, uint8_t* d_class_out,
+              float* d_residual_out, pm_align_sums* d_sums, ImagingState** state, hipStream_t* stream_out,
+              pm_align_sums** d_record) {
+  ImagingState* st = nullptr;
+  hipStream_t stream = nullptr;
+  if (int rc = stage_begin(h, what, &st, &stream)) return rc;
+  PM_HIP(h, st->align_buf.reserve(align_scratch_bytes(in.rows), stream));
+  if (!st->align_host.base()) PM_HIP(h, st->align_host.alloc(sizeof(pm_align_sums)));
+  pm_align_sums* record = reinterpret_cast<pm_align_sums*>(st->align_buf.get());
+  AlignArgs a = {};
+  a.cam = cloud_cam(*in.camera);
+  set_motion(a.R, a.t, motion);
+  a.min_disp = in.options->min_disp, a.max_diff = in.options->max_diff, a.huber_px = in.options->huber_px;
+  a.disp_model = in.disp_model, a.normals_model = in.normals_model, a.disp_new = in.disp_new;
+  a.rows = in.rows, a.cols = in.cols;
+  a.class_out = d_class_out, a.residual_out = d_residual_out;
+  a.row_sums = reinterpret_cast<double*>(st->align_buf.get() + kAlignRecordSlot);
+  a.counts = &record->n_model;
+  PM_HIP(h, hipMemsetAsync(a.counts, 0, 4 * sizeof(int), stream));
+  hipLaunchKernelGGL(k_align_rows, dim3(align_row_blocks(in.rows)), dim3(kAlignBlockX, kAlignBlockY), 0, stream, a);
+  hipLaunchKernelGGL(k_align_finish, dim3(1), dim3(kAlignLanes), 0, stream, (const double*)a.row_sums, in.rows,
+                     (const int*)a.counts, record, d_sums);
+  if (int rc = launch_check(h, "align")) return rc;
+  *state = st, *stream_out = stream, *d_record = record;
+  return PM_OK;
+}
+
+// The handle's record through its page-locked memory into *sums; the copy has landed when this returns.
+int align_download(pm_handle* h, ImagingState* st, hipStream_t stream, const pm_align_sums* d_record, pm_align_sums* sums) {
+  PM_HIP(h, hipMemcpyAsync(st->align_host.base(), d_record, sizeof(pm_align_sums), hipMemcpyDeviceToHost, stream));
+  PM_HIP(h, hipStreamSynchronize(stream));
+  std::memcpy(sums, st->align_host.base(), sizeof(pm_align_sums));
+  return PM_OK;
+}
+}  // namespace
+
+int pm_align_evaluate(pm_handle* h, const pm_cloud_camera* camera, const pm_align_options* options, const pm_motion* motion,
+                      const float* d_disp_model, const float* d_normals_model, const float* d_disp_new, int rows, int cols,
+                      uint8_t* d_class_out, float* d_residual_out, pm_align_sums* d_sums, pm_align_sums* sums) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_align_evaluate";
+  const AlignInputs in = {camera, options, motion, d_disp_model, d_normals_model, d_disp_new, rows, cols};
+  if (int rc = check_align(h, what, in, "the motion")) return rc;
+  if (int rc = check_any_output(h, what, {d_class_out, d_residual_out, d_sums, sums}, "d_class_out, d_residual_out, d_sums and sums"))
+    return rc;
+  ImagingState* st = nullptr;
+  hipStream_t stream = nullptr;
+  pm_align_sums* d_record = nullptr;
+  if (int rc = run_align(h, what, in, motion, d_class_out, d_residual_out, d_sums, &st, &stream, &d_record)) return rc;
+  return sums ? align_download(h, st, stream, d_record, sums) : PM_OK;
+}
+
+int pm_align_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_align_options* options, const pm_motion* guess,
+                       const float* d_disp_model, const float* d_normals_model, const float* d_disp_new, int rows, int cols,
+                       pm_motion* out, pm_align_info* info) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_align_disparity";
+  const AlignInputs in = {camera, options, guess, d_disp_model, d_normals_model, d_disp_new, rows, cols};
+  if (int rc = check_align(h, what, in, "the guess")) return rc;
+  if (int rc = check_any_output(h, what, {out, info}, "out and info")) return rc;
+  pm_motion start;
+  set_motion(start.R, start.t, guess);
+  pm_motion m = start;
+  ImagingState* st = nullptr;
+  hipStream_t stream = nullptr;
+  pm_align_sums* d_record = nullptr;
+  pm_align_sums sums;
+  bool failed = false;
+  int done = 0;
+  for (int it = 0; it < options->iterations; ++it) {
+    if (int rc = run_align(h, what, in, &m, nullptr, nullptr, nullptr, &st, &stream, &d_record)) return rc;
+    if (int rc = align_download(h, st, stream, d_record, &sums)) return rc;
+    double delta[6];
+    int factorised = 0;
+    pm_align_step(&sums, &m, &m, delta, &factorised);
+    if (!factorised) {
+      failed = true;
+      break;
+    }
+    ++done;
+    double biggest = 0.0;
+    for (double v : delta) biggest = std::fabs(v) > biggest ? std::fabs(v) : biggest;
+    if (biggest < options->epsilon) break;
+  }
+  if (int rc = run_align(h, what, in, &m, nullptr, nullptr, nullptr, &st, &stream, &d_record)) return rc;
+  if (int rc = align_download(h, st, stream, d_record, &sums)) return rc;
+  const bool valid = !failed && sums.n_used >= options->min_used;
+  if (out) *out = valid ? m : start;
+  if (info) {
+    info->valid = valid ? 1 : 0;
+    info->n_model = sums.n_model, info->n_gate = sums.n_gate, info->n_used = sums.n_used;
+    info->iterations = done;
+    info->rms_px = sums.n_used ? std::sqrt(sums.rr / (double)sums.n_used) : 0.0;
+    for (int i = 0; i < 21; ++i) info->H[i] = sums.H[i];
+  }
+  return PM_OK;
+}
+
+void pm_debug_align_constants(int* lanes, int* waves) {
+  if (lanes) *lanes = kAlignLanes;
+  if (waves) *waves = kAlignWaves;
+}
+
+size_t pm_debug_align_scratch_bytes(int rows) { return rows < 1 ? 0 : align_scratch_bytes(rows); }

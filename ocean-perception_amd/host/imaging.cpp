@@ -708,6 +708,42 @@ Motion EstimateMotion(pm::PatchmatchGpu& matcher, const StereoModel& model, cons
   return FromC(out);
 }
 
+namespace {
+pm_align_options ToC(const AlignOptions& o) {
+  return pm_align_options{o.min_disp, o.max_diff, o.huber_px, o.iterations, o.epsilon, o.min_used};
+}
+}  // namespace
+
+Motion AlignDisparity(pm::PatchmatchGpu& matcher, const StereoModel& model, const AlignOptions& options, const Motion* guess,
+                      const core::Image<float>& disp_model, const core::Image<core::Vec3f>& normals_model,
+                      const core::Image<float>& disp_new, pm_align_info* info) {
+  const char* const who = "AlignDisparity";
+  DeviceBuffers dev(MatcherHandle(matcher, who));
+  if (disp_model.rows <= 0 || disp_model.cols <= 0) throw std::invalid_argument("AlignDisparity: empty map");
+  SameSize(disp_model.rows, disp_model.cols, normals_model.rows, normals_model.cols, who);
+  SameSize(disp_model.rows, disp_model.cols, disp_new.rows, disp_new.cols, who);
+  const float* d_model = dev.Put<float>(disp_model.data(), Bytes(disp_model));
+  const float* d_normals = dev.Put<float>(reinterpret_cast<const float*>(normals_model.data()), Bytes(normals_model));
+  const float* d_new = dev.Put<float>(disp_new.data(), Bytes(disp_new));
+  const pm_cloud_camera cam = CloudCamera(model);
+  const pm_align_options opt = ToC(options);
+  const pm_motion g = ToC(guess ? *guess : Motion());
+  pm_motion out;
+  pm_align_info local;
+  dev.Check(pm_align_disparity(dev.handle(), &cam, &opt, &g, d_model, d_normals, d_new, disp_model.rows, disp_model.cols, &out,
+                               info ? info : &local),
+            "pm_align_disparity");
+  return FromC(out);
+}
+
+Motion ComposeMotion(const Motion& a, const Motion& b) {
+  const pm_motion ca = ToC(a), cb = ToC(b);
+  pm_motion out;
+  const int rc = pm_motion_compose(&ca, &cb, &out);
+  if (rc != PM_OK) throw std::runtime_error(std::string("pm_motion_compose: ") + pm_status_string(rc));
+  return FromC(out);
+}
+
 core::Image<core::Vec3f> DisparityNormals(const core::Image<float>& disp, const StereoModel& model, const NormalsFit& fit,
                                           core::Image<uint8_t>* support) {
   if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("DisparityNormals: empty map");
@@ -767,6 +803,9 @@ struct TsdfVolume::Impl {
   pm_handle* const h;
   const pm_tsdf_volume volume;
   void* const voxels;
+  // Align's render and the new map on the device, kept from call to call and replaced when a larger map arrives
+  float *align_disp = nullptr, *align_normals = nullptr, *align_new = nullptr;
+  size_t align_px = 0;
   Impl(pm_handle* handle, const pm_tsdf_volume& v, size_t bytes) : dev(handle), h(handle), volume(v), voxels(dev.Get(bytes)) {}
 };
 
@@ -833,6 +872,30 @@ int TsdfVolume::Raycast(const StereoModel& model, const Motion& pose, int rows, 
   if (disp) dev.Fetch(disp, d_disp, rows, cols);
   if (normals) dev.Fetch(normals, d_normals, rows, cols);
   return hits;
+}
+
+Motion TsdfVolume::Align(const StereoModel& model, const Motion& pose_guess, const core::Image<float>& disp_new,
+                         const TsdfRaycastOptions& raycast_options, const AlignOptions& align_options, pm_align_info* info) {
+  const int rows = disp_new.rows, cols = disp_new.cols;
+  if (rows <= 0 || cols <= 0) throw std::invalid_argument("TsdfVolume::Align: empty map");
+  const size_t px = (size_t)rows * cols;
+  Impl& m = *impl_;
+  if (px > m.align_px) {
+    m.align_disp = m.dev.Get<float>(4 * px);
+    m.align_normals = m.dev.Get<float>(12 * px);
+    m.align_new = m.dev.Get<float>(4 * px);
+    m.align_px = px;
+  }
+  m.dev.Check(pm_upload(m.h, m.align_new, disp_new.data(), Bytes(disp_new)), "pm_upload");
+  RaycastDevice(model, pose_guess, rows, cols, m.align_disp, m.align_normals, raycast_options, /*want_counts=*/false);
+  const pm_cloud_camera cam = CloudCamera(model);
+  const pm_align_options opt = ToC(align_options);
+  pm_motion out;
+  pm_align_info local;
+  pm_align_info* const report = info ? info : &local;
+  m.dev.Check(pm_align_disparity(m.h, &cam, &opt, nullptr, m.align_disp, m.align_normals, m.align_new, rows, cols, &out, report),
+              "pm_align_disparity");
+  return report->valid ? ComposeMotion(FromC(out), pose_guess) : pose_guess;
 }
 
 std::array<int, 2> TsdfVolume::MeshDevice(const TsdfMeshOptions& options, int vertex_capacity, int tri_capacity, float* d_xyz_out,

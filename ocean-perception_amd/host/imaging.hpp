@@ -287,6 +287,26 @@ Motion EstimateMotion(pm::PatchmatchGpu& matcher, const StereoModel& model, cons
                       const SolveOptions& solve_options, const Motion* guess, const core::Image<uint8_t>& left_old,
                       const core::Image<float>& disp_old, const core::Image<uint8_t>& left_new, pm_motion_info* info = nullptr);
 
+// Dense alignment of a NEW left disparity map against a MODEL's map and camera-facing normals (TsdfVolume::Raycast's outputs,
+// or an earlier map with DisparityNormals / PlaneNormals): point-to-plane Gauss-Newton with projective association
+// (pm/imaging.h: pm_align_disparity; definition: tests/align_ref.py).  The motion goes from the model camera's frame into the new
+// camera's, X_new = R X_model + t: what ReprojectDisparity takes.  info->valid == 0: the result is not to be trusted and the
+// returned motion is the guess.  Runs on the matcher's handle; throws std::runtime_error where the C call refuses.
+struct AlignOptions {  // pm_align_options
+  float min_disp = 0.f;    // a pixel takes part iff disp > 0 and disp >= min_disp
+  float max_diff = 1.f;    // the gate between the carried and the measured disparity, pixels; finite, >= 0
+  double huber_px = 1.0;   // > 0
+  int iterations = 10;     // 1..50
+  double epsilon = 1e-9;   // >= 0: stop when no entry of the update exceeds it
+  int min_used = 100;      // >= 6
+};
+Motion AlignDisparity(pm::PatchmatchGpu& matcher, const StereoModel& model, const AlignOptions& options, const Motion* guess,
+                      const core::Image<float>& disp_model, const core::Image<core::Vec3f>& normals_model,
+                      const core::Image<float>& disp_new, pm_align_info* info = nullptr);
+// Host only: X -> a(b(X)) (pm_motion_compose).  The pose of a frame aligned against a render at pose_ref is
+// ComposeMotion(M, pose_ref).
+Motion ComposeMotion(const Motion& a, const Motion& b);
+
 // A persistent world-frame model of a sequence: a truncated signed distance volume that Integrate folds left disparity maps
 // and their camera poses into and Raycast renders back, at any pose, as an ordinary left disparity map with normals -- what
 // MakePointCloud, MakeGridMesh, ReprojectDisparity (with the identity motion, for the right seed), FilterConsistency and
@@ -350,6 +370,12 @@ class TsdfVolume {
   // false it only enqueues and returns {-1, -1}.
   std::array<int, 2> MeshDevice(const TsdfMeshOptions& options, int vertex_capacity, int tri_capacity, float* d_xyz_out,
                                 float* d_normals_out, int32_t* d_tri_out, int* d_counts = nullptr, bool want_counts = true);
+  // Tracking against the model: raycasts at pose_guess into device buffers the volume owns, aligns disp_new against that render
+  // from the identity (AlignDisparity) and returns ComposeMotion(M, pose_guess), the new frame's pose; pose_guess itself where
+  // info->valid == 0.
+  Motion Align(const StereoModel& model, const Motion& pose_guess, const core::Image<float>& disp_new,
+               const TsdfRaycastOptions& raycast_options = TsdfRaycastOptions(), const AlignOptions& align_options = AlignOptions(),
+               pm_align_info* info = nullptr);
   // The records, 2 floats per voxel (tsdf, weight), x fastest; synchronises.
   std::vector<float> Download();
 

@@ -54,6 +54,8 @@ EXPORTS = [
     "pm_tsdf_bytes", "pm_tsdf_clear", "pm_tsdf_integrate", "pm_tsdf_raycast", "pm_debug_tsdf_constants",
     "pm_tsdf_mesh", "pm_debug_tsdf_mesh_table", "pm_debug_tsdf_mesh_scratch_bytes",
     "pm_track_features", "pm_solve_motion", "pm_estimate_motion",
+    "pm_align_evaluate", "pm_align_step", "pm_align_disparity", "pm_motion_compose", "pm_debug_align_constants",
+    "pm_debug_align_scratch_bytes",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
     "pm_debug_match_plan",
     "pm_debug_sweep_plan", "pm_debug_segment_bounds", "pm_debug_propagate_hinted", "pm_debug_match_sweep_hint", "pm_debug_read_stops", "pm_debug_noise_cost_constants", "pm_debug_noise_cost", "pm_debug_remove_background",
@@ -388,6 +390,83 @@ class PmMotionInfo(C.Structure):
                     iterations=self.iterations, rms_px=self.rms_px)
 
 
+PM_ALIGN_NO_MODEL, PM_ALIGN_OUTSIDE, PM_ALIGN_UNMEASURED, PM_ALIGN_GATED, PM_ALIGN_USED = range(5)
+
+
+class PmAlignOptions(C.Structure):  # pm_align_evaluate / pm_align_disparity
+    _fields_ = [("min_disp", C.c_float), ("max_diff", C.c_float), ("huber_px", C.c_double), ("iterations", C.c_int),
+                ("epsilon", C.c_double), ("min_used", C.c_int)]
+
+
+class PmAlignSums(C.Structure):  # 240 bytes: one evaluation's normal equations and counts
+    _fields_ = [("H", C.c_double * 21), ("g", C.c_double * 6), ("rr", C.c_double), ("n_model", C.c_int), ("n_gate", C.c_int),
+                ("n_used", C.c_int), ("pad", C.c_int)]
+
+    def as_dict(self):
+        return dict(H=np.array(self.H[:]), g=np.array(self.g[:]), rr=self.rr, n_model=self.n_model, n_gate=self.n_gate,
+                    n_used=self.n_used)
+
+
+class PmAlignInfo(C.Structure):
+    _fields_ = [("valid", C.c_int), ("n_model", C.c_int), ("n_gate", C.c_int), ("n_used", C.c_int), ("iterations", C.c_int),
+                ("rms_px", C.c_double), ("H", C.c_double * 21)]
+
+    def as_dict(self):
+        return dict(valid=self.valid, n_model=self.n_model, n_gate=self.n_gate, n_used=self.n_used, iterations=self.iterations,
+                    rms_px=self.rms_px, H=np.array(self.H[:]))
+
+
+ALIGN_DEFAULTS = dict(min_disp=0.0, max_diff=1.0, huber_px=1.0, iterations=10, epsilon=1e-9, min_used=100)
+
+
+def align_options(values=None):
+    """A PmAlignOptions from a dict of its fields over ALIGN_DEFAULTS; a PmAlignOptions passes through."""
+    if isinstance(values, PmAlignOptions):
+        return values
+    o = dict(ALIGN_DEFAULTS)
+    o.update(values or {})
+    return PmAlignOptions(**o)
+
+
+def align_sums(H, g, rr=0.0, n_model=0, n_gate=0, n_used=0):
+    """A PmAlignSums from its parts."""
+    s = PmAlignSums()
+    s.H[:] = [float(v) for v in H]
+    s.g[:] = [float(v) for v in g]
+    s.rr, s.n_model, s.n_gate, s.n_used, s.pad = float(rr), int(n_model), int(n_gate), int(n_used), 0
+    return s
+
+
+def align_step(sums, motion=None):
+    """pm_align_step (host only, no handle): one solve and update from a PmAlignSums -> (factorised, R[9], t[3], delta[6])."""
+    out, delta, ok = PmMotion(), (C.c_double * 6)(), C.c_int(-1)
+    rc = load().pm_align_step(C.byref(sums), _ref(as_motion(motion)), C.byref(out), delta, C.byref(ok))
+    if rc != PM_OK:
+        raise PmError(rc, "pm_align_step", "refused its arguments")
+    return bool(ok.value), np.array(out.R[:]), np.array(out.t[:]), np.array(delta[:])
+
+
+def motion_compose(a, b):
+    """pm_motion_compose (host only, no handle): X -> a(b(X)) -> (R[9], t[3])."""
+    out = PmMotion()
+    rc = load().pm_motion_compose(_ref(as_motion(a)), _ref(as_motion(b)), C.byref(out))
+    if rc != PM_OK:
+        raise PmError(rc, "pm_motion_compose", "refused its arguments")
+    return np.array(out.R[:]), np.array(out.t[:])
+
+
+def align_constants():
+    """pm_debug_align_constants: (lane sums of a row, rows per block)."""
+    a, b = C.c_int(0), C.c_int(0)
+    load().pm_debug_align_constants(C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def align_scratch_bytes(rows):
+    """pm_debug_align_scratch_bytes: the device scratch a pm_align_evaluate call on a map of `rows` rows reserves."""
+    return int(load().pm_debug_align_scratch_bytes(int(rows)))
+
+
 def solve_motion(camera, tracks, guess=None, iterations=10, huber_px=1.0, epsilon=1e-9, inlier_px=1.0, min_inliers=12):
     """pm_solve_motion (host only, no handle): tracks, a TRACK_DTYPE array -> (R[9], t[3], info dict).  Raises PmError where
     the arguments are refused."""
@@ -636,6 +715,21 @@ def load():
                                        C.POINTER(PmMotion), vp, vp, vp, C.c_int, C.c_int, C.POINTER(PmMotion),
                                        C.POINTER(PmMotionInfo)]
     lib.pm_estimate_motion.restype = C.c_int
+    lib.pm_align_evaluate.argtypes = [vp, C.POINTER(PmCloudCamera), C.POINTER(PmAlignOptions), C.POINTER(PmMotion), vp, vp, vp,
+                                      C.c_int, C.c_int, vp, vp, vp, C.POINTER(PmAlignSums)]
+    lib.pm_align_evaluate.restype = C.c_int
+    lib.pm_align_step.argtypes = [C.POINTER(PmAlignSums), C.POINTER(PmMotion), C.POINTER(PmMotion), C.POINTER(C.c_double),
+                                  C.POINTER(C.c_int)]
+    lib.pm_align_step.restype = C.c_int
+    lib.pm_align_disparity.argtypes = [vp, C.POINTER(PmCloudCamera), C.POINTER(PmAlignOptions), C.POINTER(PmMotion), vp, vp, vp,
+                                       C.c_int, C.c_int, C.POINTER(PmMotion), C.POINTER(PmAlignInfo)]
+    lib.pm_align_disparity.restype = C.c_int
+    lib.pm_motion_compose.argtypes = [C.POINTER(PmMotion)] * 3
+    lib.pm_motion_compose.restype = C.c_int
+    lib.pm_debug_align_constants.argtypes = [C.POINTER(C.c_int)] * 2
+    lib.pm_debug_align_constants.restype = None
+    lib.pm_debug_align_scratch_bytes.argtypes = [C.c_int]
+    lib.pm_debug_align_scratch_bytes.restype = C.c_size_t
     lib.pm_debug_confidence_constants.argtypes = [C.POINTER(C.c_int)] * 3
     lib.pm_debug_confidence_constants.restype = None
     lib.pm_device_malloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
@@ -1398,6 +1492,32 @@ class Engine:
         self._check(self.lib.pm_estimate_motion(self.h, _ref(c), C.byref(o), C.byref(s), _ref(as_motion(guess)), d_left_old,
                                                 d_disp_old, d_left_new, rows, cols, C.byref(out), C.byref(info)),
                     "pm_estimate_motion")
+        return np.array(out.R[:]), np.array(out.t[:]), info.as_dict()
+
+    def align_evaluate(self, camera, d_disp_model, d_normals_model, d_disp_new, rows, cols, motion=None, options=None,
+                       d_class_out=None, d_residual_out=None, d_sums=None, want_sums=False):
+        """pm_align_evaluate (raw device addresses): one evaluation of the new map d_disp_new against the model's map and
+        normals under motion ((R, t), PmMotion or None = identity; X_new = R X_model + t), on the handle's stream.  options: a
+        dict of PmAlignOptions' fields over ALIGN_DEFAULTS.  d_class_out uint8 [rows][cols], d_residual_out float32
+        [rows][cols], d_sums one PmAlignSums on the device, each where given.  -> the PmAlignSums with want_sums (the call then
+        synchronises), else None."""
+        c = cloud_camera(camera)
+        o = align_options(options)
+        sums = PmAlignSums()
+        self._check(self.lib.pm_align_evaluate(self.h, _ref(c), C.byref(o), _ref(as_motion(motion)), d_disp_model,
+                                               d_normals_model, d_disp_new, rows, cols, d_class_out, d_residual_out, d_sums,
+                                               C.byref(sums) if want_sums else None), "pm_align_evaluate")
+        return sums if want_sums else None
+
+    def align_disparity(self, camera, d_disp_model, d_normals_model, d_disp_new, rows, cols, guess=None, options=None):
+        """pm_align_disparity (raw device addresses): Gauss-Newton from guess -> (R[9], t[3], info dict); X_new = R X_model + t,
+        what reproject_disparity takes.  Synchronises."""
+        c = cloud_camera(camera)
+        o = align_options(options)
+        out, info = PmMotion(), PmAlignInfo()
+        self._check(self.lib.pm_align_disparity(self.h, _ref(c), C.byref(o), _ref(as_motion(guess)), d_disp_model,
+                                                d_normals_model, d_disp_new, rows, cols, C.byref(out), C.byref(info)),
+                    "pm_align_disparity")
         return np.array(out.R[:]), np.array(out.t[:]), info.as_dict()
 
     def normalize(self, d_bgr, rows, cols, d_out):
