@@ -125,6 +125,49 @@ int pm_debug_noise_cost(pm_handle* h, const uint8_t* left, const uint8_t* right,
 int pm_debug_remove_background(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, float* disp,
                                const float* cost, int patch_h, int patch_w, float factor);
 
+/* ---- the head of a scalar Match plane by plane (csrc/pm_kernels.hpp: k_prep, k_prep_bgr, k_prep_view, k_setup) ---------------
+ * The head is what runs in front of the first noise + cost: the prep kernel writes four image planes per pair (L, R,
+ * mirrored L, mirrored R), each as img8, g32, g8 and pk16, and k_setup -- one launch, planned by
+ * csrc/pm_head_plan.hpp -- derives the four transposes with their replicated pad lines and, for handles with line planes,
+ * the row triples, the reference quads and the column triples.  These hooks add no kernel and change none: they copy and
+ * fill with runtime calls only.  All three return PM_ERR_BUSY between pm_capture_begin and pm_capture_end and while pairs
+ * are in flight, and PM_ERR_INVALID_ARG for a size the handle refuses (Match()'s rule: 5 rows and up on a scalar handle
+ * with caller seeds, else 8) or does not hold.
+ * pm_debug_head_shape: the geometry of the planes for images of rows x cols -- what a kernel's plane set holds --, whether
+ * the handle has line planes, and its pairs.  No device work.
+ * pm_debug_head_read: synchronises every stream of the handle and copies the head planes of pairs 0 .. n - 1 as they lie
+ * in memory, pitch padding included, at the geometry of rows x cols; any pointer may be null.  Read-only: it shows what the
+ * last call on this handle left, whichever entry point that was.  PM_ERR_INVALID_ARG also for a line plane asked of a
+ * handle that has none.
+ * pm_debug_head_poison: fills every head plane of the handle with `byte`, over its whole allocation (all pairs, padding
+ * and slack included) on the handle's stream, and synchronises; the line planes are allocated first where the handle
+ * wants them.  byte: 0 .. 254 -- 255 would make NaNs, and the padding of the planes is read and must stay finite.  What a
+ * call writes afterwards stands out from 0x5A5A5A5A, 1.5e16 as a float: no pixel, gradient or record. */
+typedef struct pm_debug_head_shape_record {
+  int pitch, pitch_t;     /* elements per row of the plain / the transposed planes                                        */
+  int nrl, ncl;           /* lines of the row / column line planes: rows + 2, cols + trans_pad + 2                        */
+  int trans_pad;          /* replicated lines behind the last column of a transposed plane                                */
+  int with_lines;         /* 1 = the handle has the line planes (rpg, rqk, cpg)                                           */
+  int max_batch;
+  size_t plane, plane_t;  /* elements of one plain / transposed plane: rows * pitch, (cols + trans_pad) * pitch_t         */
+} pm_debug_head_shape_record;
+typedef struct pm_debug_head_planes {
+  uint8_t* img8;    /* [n][4][rows][pitch]                 planes 0 = L, 1 = R, 2 = mirrored L, 3 = mirrored R            */
+  float* g32;       /* [n][4][rows][pitch]                                                                              */
+  uint8_t* g8;      /* [n][4][rows][pitch]                                                                              */
+  uint16_t* pk16;   /* [n][4][rows][pitch]                                                                              */
+  uint8_t* timg8;   /* [n][4][cols + trans_pad][pitch_t]                                                                */
+  float* tg32;      /* [n][4][cols + trans_pad][pitch_t]                                                                */
+  uint8_t* tg8;     /* [n][4][cols + trans_pad][pitch_t]                                                                */
+  uint16_t* tpk16;  /* [n][4][cols + trans_pad][pitch_t]                                                                */
+  float* rpg;       /* [n][2][nrl][pitch][4]               slot = view                                                   */
+  uint32_t* rqk;    /* [n][2][nrl][pitch][2]                                                                            */
+  float* cpg;       /* [n][2][ncl][pitch_t][4]                                                                          */
+} pm_debug_head_planes;
+int pm_debug_head_shape(pm_handle* h, int rows, int cols, pm_debug_head_shape_record* out);
+int pm_debug_head_read(pm_handle* h, int n, int rows, int cols, const pm_debug_head_planes* out);
+int pm_debug_head_poison(pm_handle* h, int byte);
+
 /* ---- the state of a row-tiled band between its stages (pm_tile_*, csrc/pm_tile.hip) -------------------------------------
  * pm_debug_tile_state: the disparity and cost plane of one view of the OPEN band, every band row, halo included.
  * which: 0 = the live state planes, 1 = the snapshot planes (pm_tile_snapshot / pm_tile_presweep); view: 0 or 1, view 1 in

@@ -258,7 +258,8 @@ int pair_planes_alloc(pm_handle* h, hipStream_t stream) {
   const size_t pitch_t = (size_t)align_up(h->max_rows, 64);
   const size_t nrp = B * 2 * (size_t)(h->max_rows + 2) * h->max_pitch + kSlackElems;
   const size_t ncp = B * 2 * (size_t)(h->max_cols + kTransPad + 2) * pitch_t + kSlackElems;
-  // zeroed: row padding behind `cols` / `rows` is read (with weight 0 or by lanes out of reach) and must be finite
+  // zeroed: row padding behind `cols` / `rows` is read (with weight 0 or by lanes out of reach) and must be finite; no
+  // result depends on which finite value it holds (tests/test_head_stages.py matches on planes filled with 0x5A)
   PM_HIP(h, h->rpg.alloc_zeroed(sizeof(float) * 4 * nrp, stream));
   PM_HIP(h, h->rqk.alloc_zeroed(sizeof(uint32_t) * 2 * nrp, stream));
   PM_HIP(h, h->cpg.alloc_zeroed(sizeof(float) * 4 * ncp, stream));

@@ -1012,6 +1012,94 @@ int pm_debug_noise_cost(pm_handle* h, const uint8_t* left, const uint8_t* right,
   return stage_out(h, ps, disp, 0);
 }
 
+// ---- the head planes as the last call left them (include/pm/testing.h) -------------------------------------------------
+// what the three hooks refuse alike: an open capture, pairs in flight, and -- rows > 0 -- a size the handle does not take
+static int head_hook_check(pm_handle* h, const char* who, int n, int rows, int cols) {
+  if (int rc = refuse_while_capturing(h, who)) return rc;
+  if (h->pipe_count > 0) {
+    set_err(h, "%s: pairs are in flight (pm_collect them first)", who);
+    return PM_ERR_BUSY;
+  }
+  if (rows > 0 && check_size(h, rows, cols, n, /*match=*/true) != PM_OK) return PM_ERR_INVALID_ARG;  // (check_size says why)
+  return PM_OK;
+}
+
+int pm_debug_head_shape(pm_handle* h, int rows, int cols, pm_debug_head_shape_record* out) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (!out) {
+    set_err(h, "pm_debug_head_shape: null pointer");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = head_hook_check(h, "pm_debug_head_shape", 1, rows < 1 ? 1 : rows, cols)) return rc;
+  const PlaneSet ps = plane_set(h, rows, cols, 1);
+  *out = pm_debug_head_shape_record{ps.pitch, ps.pitch_t, ps.nrl, ps.ncl, kTransPad, pair_planes_wanted(h) ? 1 : 0,
+                                    h->max_batch, ps.plane, ps.plane_t};
+  return PM_OK;
+}
+
+int pm_debug_head_read(pm_handle* h, int n, int rows, int cols, const pm_debug_head_planes* out) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (!out) {
+    set_err(h, "pm_debug_head_read: null pointer");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = head_hook_check(h, "pm_debug_head_read", n, rows < 1 ? 1 : rows, cols)) return rc;
+  if ((out->rpg || out->rqk || out->cpg) && !h->rpg) {
+    set_err(h, "pm_debug_head_read: this handle has no line planes");
+    return PM_ERR_INVALID_ARG;
+  }
+  PM_HIP(h, hipSetDevice(h->device));
+  for (hipStream_t st : {h->stream.get(), h->view1_stream.get(), h->s_in.get(), h->s_out.get()})
+    if (st) PM_HIP(h, hipStreamSynchronize(st));
+  const PlaneSet ps = plane_set(h, rows, cols, 2);
+  const size_t B = (size_t)n;
+  const size_t plain = B * 4 * ps.plane, trans = B * 4 * ps.plane_t;
+  const size_t rows_l = B * 2 * (size_t)ps.nrl * ps.pitch, cols_l = B * 2 * (size_t)ps.ncl * ps.pitch_t;
+  struct {
+    void* dst;
+    const void* src;
+    size_t bytes;
+  } copies[] = {{out->img8, ps.img8, plain},
+                {out->g32, ps.g32, plain * sizeof(float)},
+                {out->g8, ps.g8, plain},
+                {out->pk16, ps.pk16, plain * sizeof(uint16_t)},
+                {out->timg8, ps.timg8, trans},
+                {out->tg32, ps.tg32, trans * sizeof(float)},
+                {out->tg8, ps.tg8, trans},
+                {out->tpk16, ps.tpk16, trans * sizeof(uint16_t)},
+                {out->rpg, ps.rpg, rows_l * 4 * sizeof(float)},
+                {out->rqk, ps.rqk, rows_l * 2 * sizeof(uint32_t)},
+                {out->cpg, ps.cpg, cols_l * 4 * sizeof(float)}};
+  for (const auto& c : copies)
+    if (c.dst) PM_HIP(h, hipMemcpy(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost));
+  return PM_OK;
+}
+
+int pm_debug_head_poison(pm_handle* h, int byte) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  if (int rc = head_hook_check(h, "pm_debug_head_poison", 1, 0, 0)) return rc;
+  if (byte < 0 || byte > 254) {
+    set_err(h, "pm_debug_head_poison: byte %d outside 0 .. 254 (255 would fill the float planes with NaNs)", byte);
+    return PM_ERR_INVALID_ARG;
+  }
+  PM_HIP(h, hipSetDevice(h->device));
+  for (hipStream_t st : {h->view1_stream.get(), h->s_in.get(), h->s_out.get()})
+    if (st) PM_HIP(h, hipStreamSynchronize(st));
+  if (pair_planes_wanted(h))
+    if (int rc = pair_planes_alloc(h, h->stream)) return rc;
+  struct {
+    void* p;
+    size_t bytes;
+  } fills[] = {{h->img8.get(), h->img8.capacity()},   {h->g32.get(), h->g32.capacity()},   {h->g8.get(), h->g8.capacity()},
+               {h->pk16.get(), h->pk16.capacity()},   {h->timg8.get(), h->timg8.capacity()}, {h->tg32.get(), h->tg32.capacity()},
+               {h->tg8.get(), h->tg8.capacity()},     {h->tpk16.get(), h->tpk16.capacity()}, {h->rpg.get(), h->rpg.capacity()},
+               {h->rqk.get(), h->rqk.capacity()},     {h->cpg.get(), h->cpg.capacity()}};
+  for (const auto& f : fills)
+    if (f.p) PM_HIP(h, hipMemsetAsync(f.p, byte, f.bytes, h->stream));
+  PM_HIP(h, hipStreamSynchronize(h->stream));
+  return PM_OK;
+}
+
 int pm_sparse_init(pm_handle* h, const uint8_t* left, const uint8_t* right, int rows, int cols, int dilate_factor,
                    float* seed) {
   if (!h) return PM_ERR_INVALID_ARG;

@@ -4,6 +4,7 @@
 
 #include "pm_color.hpp"
 #include "pm_device.hpp"
+#include "pm_head_plan.hpp"
 #include "pm_sweep_defs.hpp"
 
 namespace pm {
@@ -182,45 +183,41 @@ __device__ __forceinline__ void transpose_block(const T* __restrict__ src, T* __
   }
 }
 
-// Line-triple planes of the run engine (PlaneSet::rpg / cpg): built from the plain and the transposed planes once per
-// Match.  Block (bx, lg, z) of a (ceil(len / 256), ceil(lines / 4), B * 2) grid with z = b * 2 + view (a thread builds
-// the records of four consecutive lines from six loaded ones); `rows_mode` != 0: row triples (len = cols,
-// line = image row, source planes img8 / g32 with pitch), else column triples on the transposed planes (len = rows,
-// line = image column incl. the replicated pad columns, source timg8 / tg32 with pitch_t).
+// Row-triple plane of the run engine (PlaneSet::rpg): built from the plain target planes once per Match.  Block
+// (bx, lg, z) of a (ceil(cols / 256), ceil(nrl / 4), B * 2) grid with z = b * 2 + view (a thread builds the records of four
+// consecutive rows from six loaded ones).  The column triples (PlaneSet::cpg) hold the same records with image columns
+// as lines: col_triples_tile below.
 // Lines beyond the last one repeat it (they are only ever the unused twelfth line of a window).
-constexpr int kLinesPerSetupThread = 4;  // a thread of the row-triple / quad sections builds this many consecutive lines
-__device__ __forceinline__ void triples_block(const PlaneSet& ps, int rows_mode, int bx, int lg, int z) {
+__device__ __forceinline__ void triples_block(const PlaneSet& ps, int bx, int lg, int z) {
   const int e = bx * blockDim.x + threadIdx.x;
   const int view = z & 1, b = z >> 1;
   const int itgt = view == 0 ? 1 : 2;
-  const int len = rows_mode ? ps.cols : ps.rows, nl = rows_mode ? ps.nrl : ps.ncl;
   const int l0 = lg * kLinesPerSetupThread;
-  if (e >= len || l0 >= nl) return;
-  const int lmax = rows_mode ? ps.rows - 1 : ps.cols + kTransPad - 1;
-  const size_t sp = rows_mode ? (size_t)ps.pitch : (size_t)ps.pitch_t;
-  const size_t tp = ((size_t)b * 4 + itgt) * (rows_mode ? ps.plane : ps.plane_t);
-  const float* g = (rows_mode ? ps.g32 : ps.tg32) + tp;
-  const uint8_t* c = (rows_mode ? ps.img8 : ps.timg8) + tp;
+  if (e >= ps.cols || l0 >= ps.nrl) return;
+  const size_t sp = (size_t)ps.pitch;
+  const size_t tp = ((size_t)b * 4 + itgt) * ps.plane;
+  const float* g = ps.g32 + tp;
+  const uint8_t* c = ps.img8 + tp;
   // lines l0 .. l0 + 5 once (a record holds three consecutive lines: four records share six lines)
   float gv[kLinesPerSetupThread + 2];
   uint32_t cv[kLinesPerSetupThread + 2];
 #pragma unroll
   for (int k = 0; k < kLinesPerSetupThread + 2; ++k) {
-    const size_t so = (size_t)min(l0 + k, lmax) * sp + e;
+    const size_t so = (size_t)min(l0 + k, ps.rows - 1) * sp + e;
     gv[k] = g[so];
     cv[k] = c[so];
   }
-  float4* dst = (float4*)(rows_mode ? ps.rpg : ps.cpg);
+  float4* dst = (float4*)ps.rpg;
 #pragma unroll
   for (int k = 0; k < kLinesPerSetupThread; ++k) {
-    if (l0 + k >= nl) break;
+    if (l0 + k >= ps.nrl) break;
     // one 16-byte record per element: three gradients and three colour bytes -- ONE aligned global_load_dwordx4 in the sweeps
     float4 rec;
     rec.x = gv[k];
     rec.y = gv[k + 1];
     rec.z = gv[k + 2];
     rec.w = __builtin_bit_cast(float, cv[k] | (cv[k + 1] << 8) | (cv[k + 2] << 16));
-    dst[((size_t)z * nl + (l0 + k)) * sp + e] = rec;
+    dst[((size_t)z * ps.nrl + (l0 + k)) * sp + e] = rec;
   }
 }
 
@@ -252,8 +249,8 @@ __device__ __forceinline__ void quads_block(const PlaneSet& ps, int bx, int lg, 
   }
 }
 
-// Column triples (PlaneSet::cpg) straight from the ROW-MAJOR target planes, transposed through LDS: the same records
-// triples_block(rows_mode = 0) builds from the transposed planes (line x of the transposed plane = image column
+// Column triples (PlaneSet::cpg) straight from the ROW-MAJOR target planes, transposed through LDS: triples_block's
+// records with the lines of the transposed planes as lines (line x of the transposed plane = image column
 // min(x, cols - 1): the pad lines replicate the last column), without waiting for those planes to exist -- so every
 // derived plane of a Match comes out of ONE launch.  Block (bx, by, z): lines 32 bx .. 32 bx + 31, rows 64 by .. 64 by + 63;
 // `lds` holds 64 x 35 floats + 64 x 36 bytes.
@@ -295,47 +292,26 @@ __device__ __forceinline__ void col_triples_tile(const PlaneSet& ps, int bx, int
 // The planes derived from k_prep's output in ONE launch instead of nine (each of these passes is a few microseconds of
 // work behind ~10 us of launch latency, and a Match starts with all of them in a row): the four transposes (u8 image,
 // f32 gradient, u8 gradient, u16 packed), the row triples, the reference quads and the column triples -- all read
-// k_prep's planes only.  One linear grid; a block finds its section and its (bx, by, bz) there from the section sizes.
-struct SetupGrid {
-  unsigned tx, ty, tz;  // transpose sections: (ceil(cols/64), ceil(rows/64), B * 4) each
-  unsigned lx, ly, lz;  // row triples / quads: (ceil(cols/256), ceil(nrl / kLinesPerSetupThread), B * 2) each
-  unsigned cx, cy, cz;  // column triples: (ceil(ncl/32), ceil(rows/64), B * 2)
-  int with_lines;       // 0: transposes only (PM_SEM_GPU, plane mode, anchor engines)
-  int view;             // -1: both views (tz = B * 4, lz = cz = B * 2); 0 / 1: that view's planes only (tz = B * 2, lz = cz = B)
-};
+// k_prep's planes only.  One linear grid; pm_head_plan.hpp plans it (SetupGrid, setup_grid) and says what each of its
+// blocks does (setup_decode).
 __device__ __forceinline__ void setup_block(const PlaneSet& ps, const SetupGrid& sg, unsigned b, float* lds) {
-  // plane / slot indices of a one-view launch: planes 2 * view, 2 * view + 1 of every pair; slot = pair * 2 + view
-  auto plane_of = [&](int bz) { return sg.view < 0 ? bz : (bz >> 1) * 4 + 2 * sg.view + (bz & 1); };
-  auto slot_of = [&](int z) { return sg.view < 0 ? z : z * 2 + sg.view; };
-  const unsigned nt = sg.tx * sg.ty * sg.tz;
-  if (b < 4 * nt) {
-    const unsigned kind = b / nt;
-    b -= kind * nt;
-    const int bx = (int)(b % sg.tx), by = (int)((b / sg.tx) % sg.ty), bz = plane_of((int)(b / (sg.tx * sg.ty)));
-    if (kind == 0)
-      transpose_block<uint8_t>(ps.img8, ps.timg8, ps.rows, ps.cols, ps.pitch, ps.pitch_t, ps.plane, ps.plane_t, bx, by, bz, lds);
-    else if (kind == 1)
-      transpose_block<float>(ps.g32, ps.tg32, ps.rows, ps.cols, ps.pitch, ps.pitch_t, ps.plane, ps.plane_t, bx, by, bz, lds);
-    else if (kind == 2)
-      transpose_block<uint8_t>(ps.g8, ps.tg8, ps.rows, ps.cols, ps.pitch, ps.pitch_t, ps.plane, ps.plane_t, bx, by, bz, lds);
-    else
-      transpose_block<uint16_t>(ps.pk16, ps.tpk16, ps.rows, ps.cols, ps.pitch, ps.pitch_t, ps.plane, ps.plane_t, bx, by, bz, lds);
-    return;
+  const SetupBlock w = setup_decode(sg, b);
+  switch (w.section) {
+    case kSetupTransposeImg8:
+      return transpose_block<uint8_t>(ps.img8, ps.timg8, ps.rows, ps.cols, ps.pitch, ps.pitch_t, ps.plane, ps.plane_t, w.bx, w.by, w.z, lds);
+    case kSetupTransposeG32:
+      return transpose_block<float>(ps.g32, ps.tg32, ps.rows, ps.cols, ps.pitch, ps.pitch_t, ps.plane, ps.plane_t, w.bx, w.by, w.z, lds);
+    case kSetupTransposeG8:
+      return transpose_block<uint8_t>(ps.g8, ps.tg8, ps.rows, ps.cols, ps.pitch, ps.pitch_t, ps.plane, ps.plane_t, w.bx, w.by, w.z, lds);
+    case kSetupTransposePk16:
+      return transpose_block<uint16_t>(ps.pk16, ps.tpk16, ps.rows, ps.cols, ps.pitch, ps.pitch_t, ps.plane, ps.plane_t, w.bx, w.by, w.z, lds);
+    case kSetupRowTriples:
+      return triples_block(ps, w.bx, w.by, w.z);
+    case kSetupQuads:
+      return quads_block(ps, w.bx, w.by, w.z);
+    default:
+      return col_triples_tile(ps, w.bx, w.by, w.z, lds);
   }
-  b -= 4 * nt;
-  const unsigned nl = sg.lx * sg.ly * sg.lz;
-  if (b < 2 * nl) {
-    const int bx = (int)(b % sg.lx), l = (int)((b / sg.lx) % sg.ly), z = slot_of((int)((b % nl) / (sg.lx * sg.ly)));
-    if (b < nl) triples_block(ps, 1, bx, l, z);
-    else quads_block(ps, bx, l, z);
-    return;
-  }
-  b -= 2 * nl;
-  col_triples_tile(ps, (int)(b % sg.cx), (int)((b / sg.cx) % sg.cy), slot_of((int)(b / (sg.cx * sg.cy))), lds);
-}
-// blocks of a SetupGrid
-inline unsigned setup_blocks(const SetupGrid& sg) {
-  return 4 * sg.tx * sg.ty * sg.tz + (sg.with_lines ? 2 * sg.lx * sg.ly * sg.lz + sg.cx * sg.cy * sg.cz : 0);
 }
 __global__ void __launch_bounds__(256) k_setup(PlaneSet ps, SetupGrid sg) {
   __shared__ float lds[64 * 65];

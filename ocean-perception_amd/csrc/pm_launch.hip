@@ -16,24 +16,6 @@ namespace {
 dim3 pixel_grid(int cols, int rows, int z) { return dim3((unsigned)((cols + 255) / 256), (unsigned)rows, (unsigned)z); }
 }  // namespace
 
-static SetupGrid setup_grid(pm_handle* h, const PlaneSet& ps, int n, int view) {
-  SetupGrid sg{};
-  sg.view = view;
-  sg.tx = (unsigned)((ps.cols + 63) / 64);
-  sg.ty = (unsigned)((ps.rows + 63) / 64);
-  sg.tz = (unsigned)(n * (view < 0 ? 4 : 2));
-  sg.with_lines = pair_planes_wanted(h) ? 1 : 0;  // the line-triple / quad planes of the run engine (pm_run3.hpp)
-  if (sg.with_lines) {
-    sg.lx = (unsigned)((ps.cols + 255) / 256);
-    sg.ly = (unsigned)((ps.nrl + kLinesPerSetupThread - 1) / kLinesPerSetupThread);
-    sg.lz = (unsigned)(n * (view < 0 ? 2 : 1));
-    sg.cx = (unsigned)((ps.ncl + 31) / 32);
-    sg.cy = (unsigned)((ps.rows + 63) / 64);
-    sg.cz = (unsigned)(n * (view < 0 ? 2 : 1));
-  }
-  return sg;
-}
-
 int launch_prep(pm_handle* h, const PlaneSet& ps, const MatchCall& c, int view, bool ride_seeds, hipStream_t stream) {
   if (c.bgr) {
     hipLaunchKernelGGL(k_prep_bgr, dim3((unsigned)((ps.cols + 63) / 64), (unsigned)((ps.rows + kPrepBgrTileH - 1) / kPrepBgrTileH), (unsigned)c.n),
@@ -56,7 +38,7 @@ int launch_prep_view(pm_handle* h, const PlaneSet& ps, const float* d_iml, const
 
 
 int run_transpose(pm_handle* h, const PlaneSet& ps, int n, int view, hipStream_t stream) {
-  const SetupGrid sg = setup_grid(h, ps, n, view);
+  const SetupGrid sg = setup_grid(ps.rows, ps.cols, ps.nrl, ps.ncl, n, view, pair_planes_wanted(h) ? 1 : 0);
   PlaneSet pp = ps;
   if (sg.with_lines && !pp.rpg) {  // (a plane set made before the line planes existed; pm_create allocates them for the handles that use them)
     if (int rc = pair_planes_alloc(h, stream)) return rc;

@@ -19,7 +19,7 @@
 //   * chain state is one float4 per position {old value, old cost, new value, new cost}: one ds_read_b64 and one
 //     ds_write_b64 per step at the same address, no conditional read;
 //   * three window lines per load: 16-byte records {three gradients, three colour bytes} from LINE-indexed planes
-//     (PlaneSet::rpg / cpg, pm_kernels.hpp::triples_block); the line offsets are wave-uniform base pointers (scalar registers), the
+//     (PlaneSet::rpg / cpg, pm_kernels.hpp::triples_block / col_triples_tile); the line offsets are wave-uniform base pointers (scalar registers), the
 //     lane's column is ONE vector offset shared by all loads of a step.  Round-3 counters (profiles/r03b_*): with the
 //     chip full of sweeps the vector units issue 31-35 % of the time while the texture address / data units are
 //     73-92 % busy -- the memory pipeline works per 4 lanes and cache line (23 accesses per wave-load of 12-byte

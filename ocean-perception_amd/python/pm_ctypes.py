@@ -59,6 +59,7 @@ EXPORTS = [
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
     "pm_debug_match_plan",
     "pm_debug_sweep_plan", "pm_debug_segment_bounds", "pm_debug_propagate_hinted", "pm_debug_match_sweep_hint", "pm_debug_read_stops", "pm_debug_noise_cost_constants", "pm_debug_noise_cost", "pm_debug_remove_background",
+    "pm_debug_head_shape", "pm_debug_head_read", "pm_debug_head_poison",
     "pm_remove_background", "pm_mask_occlusions", "pm_foreground_texture_mask", "pm_sparse_init", "pm_corner_subpix", "pm_profile_enable", "pm_profile_read",
     "pm_debug_seed_plan", "pm_debug_seed_trace", "pm_debug_seed_select", "pm_debug_seed_match", "pm_debug_seed_splat",
     "pm_kernel_name", "pm_debug_counters", "pm_debug_counters_enable",
@@ -176,6 +177,19 @@ SEED_MAX_FEATURES = 1024   # csrc/pm_seed_plan.hpp::kSeedMaxFeatures
 
 # pm_debug_match_route.route (csrc/pm_match_plan.hpp::MatchRoute)
 ROUTE_PLANES, ROUTE_ONE_STREAM, ROUTE_SHARED_HEAD, ROUTE_VIEW_HEADS, ROUTE_CHUNKS = 0, 1, 2, 3, 4
+
+
+class PmDebugHeadShape(C.Structure):  # include/pm/testing.h: pm_debug_head_shape_record
+    _fields_ = [(name, C.c_int) for name in ("pitch", "pitch_t", "nrl", "ncl", "trans_pad", "with_lines", "max_batch")] + \
+               [("plane", C.c_size_t), ("plane_t", C.c_size_t)]
+
+
+HEAD_PLANES = ("img8", "g32", "g8", "pk16", "timg8", "tg32", "tg8", "tpk16", "rpg", "rqk", "cpg")
+HEAD_LINE_PLANES = ("rpg", "rqk", "cpg")
+
+
+class PmDebugHeadPlanes(C.Structure):  # include/pm/testing.h
+    _fields_ = [(name, C.c_void_p) for name in HEAD_PLANES]
 
 
 class PmDebugPlanesVariant(C.Structure):  # include/pm/testing.h
@@ -781,6 +795,12 @@ def load():
     lib.pm_debug_noise_cost.restype = C.c_int
     lib.pm_debug_remove_background.argtypes = [vp, u8p, u8p, C.c_int, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_float]
     lib.pm_debug_remove_background.restype = C.c_int
+    lib.pm_debug_head_shape.argtypes = [vp, C.c_int, C.c_int, C.POINTER(PmDebugHeadShape)]
+    lib.pm_debug_head_shape.restype = C.c_int
+    lib.pm_debug_head_read.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(PmDebugHeadPlanes)]
+    lib.pm_debug_head_read.restype = C.c_int
+    lib.pm_debug_head_poison.argtypes = [vp, C.c_int]
+    lib.pm_debug_head_poison.restype = C.c_int
     lib.pm_mask_occlusions.argtypes = [vp, f32p, f32p, C.c_int, C.c_int]
     lib.pm_mask_occlusions.restype = C.c_int
     lib.pm_foreground_texture_mask.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp]
@@ -1658,6 +1678,34 @@ class Engine:
                                                         d.ctypes.data_as(C.c_void_p), pc, patch_h, patch_w, factor),
                     "pm_debug_remove_background")
         return d
+
+    def debug_head_shape(self, rows, cols):
+        """pm_debug_head_shape: the geometry of the head planes for images of rows x cols, as a dict of the record's fields."""
+        out = PmDebugHeadShape()
+        self._check(self.lib.pm_debug_head_shape(self.h, rows, cols, C.byref(out)), "pm_debug_head_shape")
+        return {n: int(getattr(out, n)) for n, _ in PmDebugHeadShape._fields_}
+
+    def debug_head_read(self, n, rows, cols, planes=None):
+        """pm_debug_head_read: the head planes of pairs 0 .. n - 1 as the last call left them, pitch padding included ->
+        dict name -> array in the layout of include/pm/testing.h.  planes: the names wanted (default: all the handle has)."""
+        s = self.debug_head_shape(rows, cols)
+        if planes is None:
+            planes = [p for p in HEAD_PLANES if s["with_lines"] or p not in HEAD_LINE_PLANES]
+        tl = cols + s["trans_pad"]
+        shapes = {"img8": ((n, 4, rows, s["pitch"]), np.uint8), "g32": ((n, 4, rows, s["pitch"]), np.float32),
+                  "g8": ((n, 4, rows, s["pitch"]), np.uint8), "pk16": ((n, 4, rows, s["pitch"]), np.uint16),
+                  "timg8": ((n, 4, tl, s["pitch_t"]), np.uint8), "tg32": ((n, 4, tl, s["pitch_t"]), np.float32),
+                  "tg8": ((n, 4, tl, s["pitch_t"]), np.uint8), "tpk16": ((n, 4, tl, s["pitch_t"]), np.uint16),
+                  "rpg": ((n, 2, s["nrl"], s["pitch"], 4), np.float32), "rqk": ((n, 2, s["nrl"], s["pitch"], 2), np.uint32),
+                  "cpg": ((n, 2, s["ncl"], s["pitch_t"], 4), np.float32)}
+        out = {p: np.zeros(*shapes[p]) for p in planes}
+        rec = PmDebugHeadPlanes(**{p: a.ctypes.data for p, a in out.items()})
+        self._check(self.lib.pm_debug_head_read(self.h, n, rows, cols, C.byref(rec)), "pm_debug_head_read")
+        return out
+
+    def debug_head_poison(self, byte=0x5A):
+        """pm_debug_head_poison: every head plane of the handle, whole allocation, filled with `byte` (0 .. 254)."""
+        self._check(self.lib.pm_debug_head_poison(self.h, byte), "pm_debug_head_poison")
 
     def sparse_init(self, left, right, dilate_factor=4):
         left, pl = _u8(left)
