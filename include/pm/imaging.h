@@ -912,6 +912,85 @@ int pm_align_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_ali
                        pm_align_info* info /* may be NULL */);
 int pm_motion_compose(const pm_motion* a, const pm_motion* b, pm_motion* out);           /* host only, no handle */
 
+/* ---- colour in the model: a colour volume beside the distance volume, integrated with it and gathered back -----------------------
+ * The distance volume keeps a running weighted mean of the projective distance; the colour volume keeps the same mean of the
+ * colour each frame saw at the surface, so the noisy, view-dependent colour of the frames is fused, not thrown away.  The colour
+ * volume is caller-owned like the distance volume: nx * ny * nz records of 16 bytes {float b, g, r, weight}, x fastest, 16-byte
+ * aligned (pm_device_malloc gives that); weight == 0: never coloured.  pm_tsdf_integrate_color does what pm_tsdf_integrate does and
+ * colours; pm_tsdf_color_map reads the colour back at the pixels of any left map at a pose (a render of the model, or the measured
+ * map itself), pm_tsdf_color_points at any world-frame points (pm_tsdf_mesh's vertices).
+ * Held to its CPU definition (tests/tsdf_color_ref.py) BIT FOR BIT.  Binary64 unless it says binary32, one rounding per operation,
+ * parentheses as written.
+ *   integrate, per voxel:
+ *     distance  everything pm_tsdf_integrate does, with its arithmetic (one shared statement): point, project, measure, weight,
+ *               update.  The distance volume behind this call is BIT-IDENTICAL to what pm_tsdf_integrate writes from the same
+ *               arguments, and so are counts [0] and [1].
+ *     band      bandw = (double)band * trunc, formed once on the host.  A voxel that was updated is COLOURED iff sdf <= bandw and
+ *               sdf >= -bandw and, with d_bgr, the three floats of pixel (iv, iu) are finite.
+ *     pixel     the one the disparity came from: p_c = (float)bgr8[iv][iu][c], or bgr[iv][iu][c] as it is; c = 0, 1, 2 = b, g, r.
+ *     update    binary32, w the colour record's own weight, wn the observation's weight (1.0f, or W(iv, iu)):
+ *               C'_c = ((C_c * w) + (p_c * wn)) / (w + wn);  w' = fminf(w + wn, max_weight).
+ *               A voxel that is not coloured keeps its 16 bytes and is neither read nor written.
+ *     counts    [0] voxels in view, [1] voxels updated, [2] voxels coloured.
+ *   sample at grid coordinates q (both gathers):
+ *     guard     dropped unless fabs(q_i) < 2^30 on every axis (NaN and +-inf fail).
+ *     cell      lo_i = floor(q_i);  fr_i = (float)(q_i - lo_i).
+ *     corners   c = 0..7, bit 0 x, bit 1 y, bit 2 z, at lo + bits;  binary32 tw = (wx * wy) * wz with w = 1.0f - fr on a 0 bit and
+ *               fr on a 1 bit.  A corner TAKES PART iff it lies inside the grid, its weight is > 0 and >= min_weight and its three
+ *               channels are finite.  A corner outside the grid is never read, and there is no inside test on the point itself: a
+ *               vertex on the grid's last node plane, a position a hair outside the grid and a grid one node thick all work.
+ *     mean      binary32, from +0.0f, in ascending corner order, corners that take no part skipped:  den = den + tw;
+ *               num_c = num_c + (tw * C_c).  COLOURED iff den > 0, and then value_c = num_c / den: a NORMALISED trilinear mean (the
+ *               band is thin, corners behind the surface often hold no colour).
+ *     outputs   d_bgr_out: value_c;  d_bgr8_out: (uint8)fminf(fmaxf(rintf(value_c * byte_scale), 0), 255), rintf half to even and
+ *               fmaxf / fminf returning the other operand for a NaN;  zeros in both where not coloured.  counts [0] coloured.
+ *   pm_tsdf_color_map, per pixel (x, y):  d = D(y, x) counts iff d > 0 (never NaN);  s = fxB / (double)d;  the grid coordinates are
+ *     pm_tsdf_raycast's own: its inverse pose, dx, dy, wd_i and q_i = ((c_i + (s * wd_i)) - origin[i]) / voxel.
+ *   pm_tsdf_color_points, per point:  q_i = ((double)P_i - origin[i]) / voxel.  With d_n only the first min(n, *d_n) points are
+ *     worked on (a *d_n < 0 counts as 0); the outputs of the others keep their bytes.  d_n is read on the device, behind whatever the
+ *     stream ran before: pm_tsdf_mesh's device vertex count goes in directly.
+ * All calls enqueue on the handle's stream and are valid in every mode of the handle; a non-NULL host `counts` synchronises, as
+ * pm_tsdf_integrate's does.  pm_tsdf_color_clear is one memset ({+0.0f} x 4); the others are one launch behind a 16-byte memset.  No
+ * voxel, pixel or point is touched by two threads and only integer addition crosses workgroups.  Scratch is the 16 bytes of the
+ * counts that pm_tsdf_integrate and pm_tsdf_raycast already share: handle-owned, allocated on first use, released with the handle.
+ * PM_ERR_INVALID_ARG, with pm_last_error naming the argument and nothing enqueued, the checks in this order -- integrate:
+ * whatever pm_tsdf_integrate refuses, in its order; a null d_colors; both or neither of d_bgr8 and d_bgr; a band that is NaN or
+ * outside (0, 1].  map: a camera pm_backproject refuses; a null volume, pose, options or d_colors; a volume pm_tsdf_integrate
+ * refuses; a non-finite entry of the pose; a null d_disp; a min_weight that is NaN or < 0; a byte_scale that is not finite or
+ * not > 0; rows or cols < 1; no output at all (d_bgr_out, d_bgr8_out, d_counts and counts all NULL).  points: a null volume,
+ * options, d_colors or d_xyz (n == 0 included); the volume; min_weight; byte_scale; n < 0; no output at all.  n == 0 is legal and
+ * only zeroes the count.  PM_ERR_SIZE: nx * ny * nz > 2^31 - 1; more pixels than pm_backproject takes; n > (2^31 - 1) / 3. */
+typedef struct pm_tsdf_color_options {   /* integrate */
+  float min_disp, max_range;             /* pm_tsdf_integrate_options' two, same rules          */
+  float band;                            /* in (0, 1]: colour is taken iff |sdf| <= band * trunc */
+} pm_tsdf_color_options;
+typedef struct pm_tsdf_color_sample_options {
+  float min_weight;                      /* a corner takes part iff weight > 0 and >= min_weight */
+  float byte_scale;                      /* finite, > 0: bytes = saturate(rintf(value * byte_scale)) */
+} pm_tsdf_color_sample_options;
+
+size_t pm_tsdf_color_bytes(const pm_tsdf_volume* volume);   /* 16 per voxel; 0 where pm_tsdf_bytes is 0 */
+int pm_tsdf_color_clear(pm_handle* h, const pm_tsdf_volume* volume, void* d_colors);
+int pm_tsdf_integrate_color(pm_handle* h, const pm_cloud_camera* camera, const pm_tsdf_volume* volume,
+                            const pm_motion* pose /* X_cam = R X_world + t */, const pm_tsdf_color_options* options,
+                            const float* d_disp, const float* d_weight /* may be NULL */,
+                            const uint8_t* d_bgr8 /* [rows][cols][3] */, const float* d_bgr /* [rows][cols][3] */,
+                            /* exactly one of the two */
+                            int rows, int cols, void* d_voxels, void* d_colors,
+                            int* d_counts /* device int[3]: in view, updated, coloured; may be NULL */,
+                            int* counts /* host int[3], may be NULL: non-NULL synchronises */);
+int pm_tsdf_color_map(pm_handle* h, const pm_cloud_camera* camera, const pm_tsdf_volume* volume, const pm_motion* pose,
+                      const pm_tsdf_color_sample_options* options, const void* d_colors, const float* d_disp, int rows, int cols,
+                      float* d_bgr_out /* [rows][cols][3], may be NULL */, uint8_t* d_bgr8_out /* [rows][cols][3], may be NULL */,
+                      int* d_counts /* device int[1]: coloured; may be NULL */,
+                      int* counts /* host int[1], may be NULL: non-NULL synchronises */);
+int pm_tsdf_color_points(pm_handle* h, const pm_tsdf_volume* volume, const pm_tsdf_color_sample_options* options,
+                         const void* d_colors, const float* d_xyz /* [n][3], world frame */, int n,
+                         const int* d_n /* device, may be NULL: only the first min(n, *d_n) */,
+                         float* d_bgr_out /* [n][3], may be NULL */, uint8_t* d_bgr8_out /* [n][3], may be NULL */,
+                         int* d_counts /* device int[1]: coloured; may be NULL */,
+                         int* counts /* host int[1], may be NULL: non-NULL synchronises */);
+
 /* ---- device buffers for host code that does not include HIP (host/imaging.hpp uses them) ------------------
  * pm_device_malloc / pm_device_free wrap hipMalloc / hipFree on the handle's device; pm_upload / pm_download are
  * stream-ordered copies on the handle's stream from / to pageable host memory (pm_download returns after the

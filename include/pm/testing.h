@@ -342,6 +342,12 @@ size_t pm_debug_tsdf_mesh_scratch_bytes(int nx, int ny, int nz);
 void pm_debug_align_constants(int* lanes, int* waves);
 size_t pm_debug_align_scratch_bytes(int rows);
 
+/* ---- the colour volume's launch constants (csrc/pm_tsdf_color_body.hpp) -----------------------------------------------------------
+ * record_bytes: the bytes of one colour record (16: one load, one store); lanes, waves: pm_debug_tsdf_constants' two, which the
+ * colour kernels share -- the tests derive from them the volumes, maps and point counts that cross a wavefront and a block.  Each
+ * may be NULL.  No handle, no device. */
+void pm_debug_tsdf_color_constants(int* record_bytes, int* lanes, int* waves);
+
 /* ---- the row-tiled driver's device discipline, provable on ONE GPU ------------------------------------------------
  * pm_tiled_create with the bands accounted to LOGICAL devices: band k lives on logical_devices[k] (>= 0; several bands
  * may share one) while every HIP call still goes to the physical device of the band's handle.  Such a plan logs every

@@ -27,6 +27,9 @@
 //     pm_tsdf_mesh.hpp   the five kernels of pm_tsdf_mesh (k_tsdf_mesh_flags / _count / _span_offsets / _vertices /
 //                        _triangles); their bodies and the case table are pm_tsdf_mesh_body.hpp's
 //     pm_align.hpp       the two kernels of pm_align_evaluate (k_align_rows, k_align_finish); their bodies are pm_align_body.hpp's
+//     pm_tsdf_color.hpp  the three kernels of pm_tsdf_integrate_color, pm_tsdf_color_map and pm_tsdf_color_points
+//                        (k_tsdf_integrate_color, k_tsdf_color_map, k_tsdf_color_points); their bodies are
+//                        pm_tsdf_color_body.hpp's, the integrate's walk and the count's tail are pm_tsdf.hpp's
 //     pm_track.hpp       the three kernels of pm_track_features (k_track_select, k_track_compact, k_track_match); their
 //                        scalar pieces are pm_track_body.hpp's
 // Every __global__ kernel lives in exactly one unit; the others reach it through the launch functions declared here.

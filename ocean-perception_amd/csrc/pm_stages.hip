@@ -29,6 +29,7 @@
 #include "pm_speckle.hpp"
 #include "pm_track.hpp"
 #include "pm_tsdf.hpp"
+#include "pm_tsdf_color.hpp"
 #include "pm_tsdf_mesh.hpp"
 #include "pm_tune.hpp"
 
@@ -760,9 +761,9 @@ const char* tsdf_volume_fault(const pm_tsdf_volume& v) {
 
 // what pm_tsdf_integrate and pm_tsdf_raycast check in the same order: camera, the null pointers, the volume, the pose
 int check_tsdf_common(pm_handle* h, const char* what, const pm_cloud_camera* camera, const pm_tsdf_volume* volume,
-                      const pm_motion* pose, const void* options, const void* d_voxels) {
+                      const pm_motion* pose, const void* options, const void* d_voxels, const char* voxels_name = "d_voxels") {
   if (int rc = check_cloud_camera(h, what, camera)) return rc;
-  if (int rc = check_not_null(h, what, {{"volume", volume}, {"pose", pose}, {"options", options}, {"d_voxels", d_voxels}}))
+  if (int rc = check_not_null(h, what, {{"volume", volume}, {"pose", pose}, {"options", options}, {voxels_name, d_voxels}}))
     return rc;
   if (const char* fault = tsdf_volume_fault(*volume)) {
     set_err(h, "%s: %s", what, fault);
@@ -777,6 +778,32 @@ int check_tsdf_size(pm_handle* h, const char* what, const pm_tsdf_volume& v) {
     return PM_ERR_SIZE;
   }
   return PM_OK;
+}
+
+// what pm_tsdf_integrate and pm_tsdf_integrate_color check in the same order; Options begins with min_disp and max_range
+template <typename Options>
+int check_tsdf_integrate(pm_handle* h, const char* what, const pm_cloud_camera* camera, const pm_tsdf_volume* volume,
+                         const pm_motion* pose, const Options* options, const float* d_disp, int rows, int cols,
+                         const void* d_voxels) {
+  if (int rc = check_tsdf_common(h, what, camera, volume, pose, options, d_voxels)) return rc;
+  if (int rc = check_not_null(h, what, {{"d_disp", d_disp}})) return rc;
+  if (std::isnan(options->min_disp) || options->min_disp < 0.f) {
+    set_err(h, "%s: min_disp must not be NaN or negative", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (!(options->max_range >= 0.f)) {
+    set_err(h, "%s: max_range must be >= 0 (0 = no limit)", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
+  return check_tsdf_size(h, what, *volume);
+}
+
+// the block count of k_tsdf_integrate and k_tsdf_integrate_color
+dim3 tsdf_span_grid(const pm_tsdf_volume& v) {
+  const size_t spans = (((size_t)v.nx + kTsdfLanes - 1) / kTsdfLanes) * (size_t)v.ny * (size_t)v.nz;
+  const size_t blocks = (spans + kTsdfBlockY - 1) / kTsdfBlockY;
+  return dim3((unsigned)(blocks < kTsdfMaxBlocks ? blocks : kTsdfMaxBlocks));
 }
 }  // namespace
 
@@ -804,18 +831,7 @@ int pm_tsdf_integrate(pm_handle* h, const pm_cloud_camera* camera, const pm_tsdf
                       void* d_voxels, int* d_counts, int* counts) {
   if (!h) return PM_ERR_INVALID_ARG;
   const char* const what = "pm_tsdf_integrate";
-  if (int rc = check_tsdf_common(h, what, camera, volume, pose, options, d_voxels)) return rc;
-  if (int rc = check_not_null(h, what, {{"d_disp", d_disp}})) return rc;
-  if (std::isnan(options->min_disp) || options->min_disp < 0.f) {
-    set_err(h, "%s: min_disp must not be NaN or negative", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (!(options->max_range >= 0.f)) {
-    set_err(h, "%s: max_range must be >= 0 (0 = no limit)", what);
-    return PM_ERR_INVALID_ARG;
-  }
-  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
-  if (int rc = check_tsdf_size(h, what, *volume)) return rc;
+  if (int rc = check_tsdf_integrate(h, what, camera, volume, pose, options, d_disp, rows, cols, d_voxels)) return rc;
   ImagingState* st = nullptr;
   hipStream_t stream = nullptr;
   if (int rc = stage_begin(h, what, &st, &stream)) return rc;
@@ -828,10 +844,7 @@ int pm_tsdf_integrate(pm_handle* h, const pm_cloud_camera* camera, const pm_tsdf
   a.min_disp = options->min_disp, a.max_range = options->max_range;
   a.disp = d_disp, a.weight = d_weight, a.rows = rows, a.cols = cols;
   a.voxels = static_cast<TsdfVoxel*>(d_voxels), a.counts = d_totals;
-  const size_t spans = (((size_t)volume->nx + kTsdfLanes - 1) / kTsdfLanes) * (size_t)volume->ny * (size_t)volume->nz;
-  const size_t blocks = (spans + kTsdfBlockY - 1) / kTsdfBlockY;
-  const dim3 grid((unsigned)(blocks < kTsdfMaxBlocks ? blocks : kTsdfMaxBlocks));
-  hipLaunchKernelGGL(k_tsdf_integrate, grid, dim3(kTsdfBlockX, kTsdfBlockY), 0, stream, a);
+  hipLaunchKernelGGL(k_tsdf_integrate, tsdf_span_grid(*volume), dim3(kTsdfBlockX, kTsdfBlockY), 0, stream, a);
   if (int rc = launch_check(h, "tsdf integrate")) return rc;
   return stage_counts(h, stream, d_totals, 2, d_counts, counts);
 }
@@ -983,6 +996,156 @@ void pm_debug_tsdf_mesh_table(uint8_t* counts, uint8_t* codes) {
 
 size_t pm_debug_tsdf_mesh_scratch_bytes(int nx, int ny, int nz) {
   return nx < 1 || ny < 1 || nz < 1 ? 0 : tsdf_mesh_scratch_bytes(nx, ny, nz);
+}
+
+// ---- colour in the model: a colour volume beside the distance volume, integrated with it and gathered back (pm_tsdf_color.hpp) --
+namespace {
+// what the two gathers check of their options
+int check_tsdf_color_sample(pm_handle* h, const char* what, const pm_tsdf_color_sample_options& o) {
+  if (std::isnan(o.min_weight) || o.min_weight < 0.f) {
+    set_err(h, "%s: min_weight must not be NaN or negative", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (!std::isfinite(o.byte_scale) || !(o.byte_scale > 0.f)) {
+    set_err(h, "%s: byte_scale must be finite and > 0", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  return PM_OK;
+}
+
+TsdfColorSampler tsdf_color_sampler(const pm_tsdf_volume& v, const pm_tsdf_color_sample_options& o, const void* d_colors,
+                                    float* d_bgr_out, uint8_t* d_bgr8_out, int* d_totals) {
+  return TsdfColorSampler{tsdf_grid(v), o.min_weight, o.byte_scale, static_cast<const TsdfColor*>(d_colors), d_bgr_out, d_bgr8_out,
+                          d_totals};
+}
+}  // namespace
+
+size_t pm_tsdf_color_bytes(const pm_tsdf_volume* volume) {
+  if (!volume || tsdf_volume_fault(*volume)) return 0;
+  return tsdf_voxels(*volume) * sizeof(TsdfColor);
+}
+
+int pm_tsdf_color_clear(pm_handle* h, const pm_tsdf_volume* volume, void* d_colors) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_tsdf_color_clear";
+  if (int rc = check_not_null(h, what, {{"volume", volume}, {"d_colors", d_colors}})) return rc;
+  if (const char* fault = tsdf_volume_fault(*volume)) {
+    set_err(h, "%s: %s", what, fault);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_tsdf_size(h, what, *volume)) return rc;
+  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
+  PM_HIP(h, hipMemsetAsync(d_colors, 0, tsdf_voxels(*volume) * sizeof(TsdfColor), pm_internal::stream(h)));
+  return PM_OK;
+}
+
+int pm_tsdf_integrate_color(pm_handle* h, const pm_cloud_camera* camera, const pm_tsdf_volume* volume, const pm_motion* pose,
+                            const pm_tsdf_color_options* options, const float* d_disp, const float* d_weight,
+                            const uint8_t* d_bgr8, const float* d_bgr, int rows, int cols, void* d_voxels, void* d_colors,
+                            int* d_counts, int* counts) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_tsdf_integrate_color";
+  if (int rc = check_tsdf_integrate(h, what, camera, volume, pose, options, d_disp, rows, cols, d_voxels)) return rc;
+  if (int rc = check_not_null(h, what, {{"d_colors", d_colors}})) return rc;
+  if ((d_bgr8 != nullptr) == (d_bgr != nullptr)) {
+    set_err(h, "%s: exactly one of d_bgr8 and d_bgr must be given (%s)", what, d_bgr8 ? "both are" : "neither is");
+    return PM_ERR_INVALID_ARG;
+  }
+  if (!(options->band > 0.f && options->band <= 1.f)) {
+    set_err(h, "%s: band must lie in (0, 1]", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  ImagingState* st = nullptr;
+  hipStream_t stream = nullptr;
+  if (int rc = stage_begin(h, what, &st, &stream)) return rc;
+  int* d_totals = nullptr;
+  if (int rc = counts_scratch(h, st->tsdf_counts, stream, &d_totals)) return rc;
+  TsdfIntegrateColorArgs a = {};
+  a.base.cam = cloud_cam(*camera);
+  a.base.grid = tsdf_grid(*volume);
+  set_motion(a.base.R, a.base.t, pose);
+  a.base.min_disp = options->min_disp, a.base.max_range = options->max_range;
+  a.base.disp = d_disp, a.base.weight = d_weight, a.base.rows = rows, a.base.cols = cols;
+  a.base.voxels = static_cast<TsdfVoxel*>(d_voxels), a.base.counts = d_totals;
+  a.bandw = (double)options->band * volume->trunc;
+  a.bgr8 = d_bgr8, a.bgr = d_bgr, a.colors = static_cast<TsdfColor*>(d_colors);
+  hipLaunchKernelGGL(k_tsdf_integrate_color, tsdf_span_grid(*volume), dim3(kTsdfBlockX, kTsdfBlockY), 0, stream, a);
+  if (int rc = launch_check(h, "tsdf integrate color")) return rc;
+  return stage_counts(h, stream, d_totals, 3, d_counts, counts);
+}
+
+int pm_tsdf_color_map(pm_handle* h, const pm_cloud_camera* camera, const pm_tsdf_volume* volume, const pm_motion* pose,
+                      const pm_tsdf_color_sample_options* options, const void* d_colors, const float* d_disp, int rows, int cols,
+                      float* d_bgr_out, uint8_t* d_bgr8_out, int* d_counts, int* counts) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_tsdf_color_map";
+  if (int rc = check_tsdf_common(h, what, camera, volume, pose, options, d_colors, "d_colors")) return rc;
+  if (int rc = check_not_null(h, what, {{"d_disp", d_disp}})) return rc;
+  if (int rc = check_tsdf_color_sample(h, what, *options)) return rc;
+  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
+  if (int rc = check_any_output(h, what, {d_bgr_out, d_bgr8_out, d_counts, counts}, "d_bgr_out, d_bgr8_out, d_counts and counts"))
+    return rc;
+  if (int rc = check_tsdf_size(h, what, *volume)) return rc;
+  ImagingState* st = nullptr;
+  hipStream_t stream = nullptr;
+  if (int rc = stage_begin(h, what, &st, &stream)) return rc;
+  int* d_totals = nullptr;
+  if (int rc = counts_scratch(h, st->tsdf_counts, stream, &d_totals)) return rc;
+  TsdfColorMapArgs a = {};
+  a.s = tsdf_color_sampler(*volume, *options, d_colors, d_bgr_out, d_bgr8_out, d_totals);
+  a.cam = cloud_cam(*camera);
+  motion_inverse(pose->R, pose->t, a.Ri, a.c);  // in binary64, as pm_tsdf_raycast forms it
+  a.disp = d_disp, a.rows = rows, a.cols = cols;
+  const dim3 grid((unsigned)((cols + kTsdfLanes - 1) / kTsdfLanes), (unsigned)((rows + kTsdfBlockY - 1) / kTsdfBlockY));
+  hipLaunchKernelGGL(k_tsdf_color_map, grid, dim3(kTsdfBlockX, kTsdfBlockY), 0, stream, a);
+  if (int rc = launch_check(h, "tsdf color map")) return rc;
+  return stage_counts(h, stream, d_totals, 1, d_counts, counts);
+}
+
+int pm_tsdf_color_points(pm_handle* h, const pm_tsdf_volume* volume, const pm_tsdf_color_sample_options* options,
+                         const void* d_colors, const float* d_xyz, int n, const int* d_n, float* d_bgr_out, uint8_t* d_bgr8_out,
+                         int* d_counts, int* counts) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_tsdf_color_points";
+  if (int rc = check_not_null(h, what, {{"volume", volume}, {"options", options}, {"d_colors", d_colors}, {"d_xyz", d_xyz}}))
+    return rc;
+  if (const char* fault = tsdf_volume_fault(*volume)) {
+    set_err(h, "%s: %s", what, fault);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_tsdf_color_sample(h, what, *options)) return rc;
+  if (n < 0) {
+    set_err(h, "%s: n %d must be >= 0", what, n);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_any_output(h, what, {d_bgr_out, d_bgr8_out, d_counts, counts}, "d_bgr_out, d_bgr8_out, d_counts and counts"))
+    return rc;
+  if (n > INT32_MAX / 3) {
+    set_err(h, "%s: n %d exceeds (2^31 - 1) / 3 points", what, n);
+    return PM_ERR_SIZE;
+  }
+  if (int rc = check_tsdf_size(h, what, *volume)) return rc;
+  ImagingState* st = nullptr;
+  hipStream_t stream = nullptr;
+  if (int rc = stage_begin(h, what, &st, &stream)) return rc;
+  int* d_totals = nullptr;
+  if (int rc = counts_scratch(h, st->tsdf_counts, stream, &d_totals)) return rc;
+  if (n > 0) {
+    TsdfColorPointsArgs a = {};
+    a.s = tsdf_color_sampler(*volume, *options, d_colors, d_bgr_out, d_bgr8_out, d_totals);
+    a.xyz = d_xyz, a.n = n, a.d_n = d_n;
+    const unsigned per_block = kTsdfBlockX * kTsdfBlockY;
+    hipLaunchKernelGGL(k_tsdf_color_points, dim3(((unsigned)n + per_block - 1) / per_block), dim3(kTsdfBlockX, kTsdfBlockY), 0,
+                       stream, a);
+    if (int rc = launch_check(h, "tsdf color points")) return rc;
+  }
+  return stage_counts(h, stream, d_totals, 1, d_counts, counts);
+}
+
+void pm_debug_tsdf_color_constants(int* record_bytes, int* lanes, int* waves) {
+  if (record_bytes) *record_bytes = (int)sizeof(TsdfColor);
+  if (lanes) *lanes = kTsdfLanes;
+  if (waves) *waves = kTsdfWaves;
 }
 
 // ---- camera motion between two frames: features of the old left image tracked into the new one (pm_track.hpp) ----------------

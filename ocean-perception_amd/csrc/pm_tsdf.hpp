@@ -28,7 +28,23 @@ namespace pm {
 constexpr unsigned kTsdfMaxBlocks = 1u << 20;  // of k_tsdf_integrate: the stride loop takes the rest
 static_assert(sizeof(TsdfIntegrateArgs) <= 320 && sizeof(TsdfRaycastArgs) <= 384, "the by-value arguments stay small");
 
+// The tail of k_tsdf_raycast and of the two colour gathers: the block's lanes that say yes, counted into *count by ballot,
+// through LDS, with one integer add per block.  Every thread of the block calls it.
+__device__ __forceinline__ void tsdf_block_count(bool yes, int* count) {
+  __shared__ int wave_counts[kTsdfBlockY];
+  const int sum = __popcll(__ballot(yes));
+  if (threadIdx.x == 0) wave_counts[threadIdx.y] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0 && threadIdx.y == 0) {
+    int total = 0;
+#pragma unroll
+    for (int w = 0; w < kTsdfBlockY; ++w) total += wave_counts[w];
+    if (total) reproject_add(count, total);
+  }
+}
+
 // grid = (min(ceil(spans / 4), kTsdfMaxBlocks)), block = (64, 4); spans = ceil(nx / 64) * ny * nz
+// (k_tsdf_integrate_color of pm_tsdf_color.hpp is this walk with a third counter: the two change together.)
 __global__ void __launch_bounds__(kTsdfBlockX * kTsdfBlockY) k_tsdf_integrate(TsdfIntegrateArgs a) {
   __shared__ int wave_counts[kTsdfBlockY][2];
   const unsigned x_spans = ((unsigned)a.grid.nx + kTsdfLanes - 1) / kTsdfLanes;
@@ -57,19 +73,10 @@ __global__ void __launch_bounds__(kTsdfBlockX * kTsdfBlockY) k_tsdf_integrate(Ts
 
 // grid = (ceil(cols / 64), ceil(rows / 4)), block = (64, 4)
 __global__ void __launch_bounds__(kTsdfBlockX * kTsdfBlockY) k_tsdf_raycast(TsdfRaycastArgs a) {
-  __shared__ int wave_counts[kTsdfBlockY];
   const int x = (int)(blockIdx.x * kTsdfLanes + threadIdx.x);
   const int y = (int)(blockIdx.y * kTsdfBlockY + threadIdx.y);
   const bool hit = x < a.cols && y < a.rows ? tsdf_ray_lane(a, x, y) : false;  // nobody leaves in front of the ballot
-  const int sum = __popcll(__ballot(hit));
-  if (threadIdx.x == 0) wave_counts[threadIdx.y] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0 && threadIdx.y == 0) {
-    int total = 0;
-#pragma unroll
-    for (int w = 0; w < kTsdfBlockY; ++w) total += wave_counts[w];
-    if (total) reproject_add(a.counts, total);
-  }
+  tsdf_block_count(hit, a.counts);
 }
 
 }  // namespace pm

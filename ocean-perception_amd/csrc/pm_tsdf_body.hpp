@@ -55,9 +55,17 @@ struct TsdfIntegrateArgs {
   int* counts;        // [0] voxels in view, [1] voxels updated; zeroed
 };
 
+// What an updated voxel does beyond its distance record: nothing (pm_tsdf_integrate).  pm_tsdf_color_body.hpp has the other one.
+struct TsdfNoColor {
+  __host__ __device__ __forceinline__ unsigned operator()(size_t, size_t, double, float) const { return 0u; }
+};
+
 // The work of one thread of k_tsdf_integrate: voxel (i, j, k), inside the grid.  Returns bit 0: in view, bit 1: updated.  The
-// voxel's record is touched only behind every test: a voxel outside the view or behind the band costs no volume traffic.
-__host__ __device__ __forceinline__ unsigned tsdf_integrate_lane(const TsdfIntegrateArgs& a, int i, int j, int k) {
+// voxel's record is touched only behind every test: a voxel outside the view or behind the band costs no volume traffic.  An
+// updated voxel is handed to `more` (its number, its pixel's number, sdf, wn), whose bits are or-ed into the result: the ONE
+// statement of the distance arithmetic serves pm_tsdf_integrate_color too.
+template <typename More>
+__host__ __device__ __forceinline__ unsigned tsdf_integrate_lane(const TsdfIntegrateArgs& a, int i, int j, int k, const More& more) {
   const TsdfGrid& g = a.grid;
   const double P[3] = {g.origin[0] + ((double)i * g.voxel), g.origin[1] + ((double)j * g.voxel), g.origin[2] + ((double)k * g.voxel)};
   int iu, iv;
@@ -76,13 +84,18 @@ __host__ __device__ __forceinline__ unsigned tsdf_integrate_lane(const TsdfInteg
   const float wn = a.weight && obs ? a.weight[px] : 1.f;
   obs = obs && fuse_weight(wn) > 0.0;
   if (!obs) return 1u;
-  TsdfVoxel* const at = a.voxels + (((size_t)k * g.ny + j) * g.nx + i);
+  const size_t voxel = ((size_t)k * g.ny + j) * g.nx + i;
+  TsdfVoxel* const at = a.voxels + voxel;
   const TsdfVoxel v = *at;  // one 8-byte load ...
   TsdfVoxel o;
   o.tsdf = ((v.tsdf * v.weight) + (f * wn)) / (v.weight + wn);
   o.weight = __builtin_fminf(v.weight + wn, g.max_weight);
   *at = o;  // ... and one 8-byte store
-  return 3u;
+  return 3u | more(voxel, px, sdf, wn);
+}
+
+__host__ __device__ __forceinline__ unsigned tsdf_integrate_lane(const TsdfIntegrateArgs& a, int i, int j, int k) {
+  return tsdf_integrate_lane(a, i, j, k, TsdfNoColor());
 }
 
 // ---- raycast ------------------------------------------------------------------------------------------------------------------
@@ -150,19 +163,28 @@ __host__ __device__ __forceinline__ bool tsdf_sample(const TsdfGrid& g, const Ts
   return part;
 }
 
-// The grid coordinates of the point at depth s along the ray whose direction in the world frame is wd.
-__host__ __device__ __forceinline__ void tsdf_ray_point(const TsdfRaycastArgs& a, const double wd[3], double s, double q[3]) {
+// The grid coordinates of the point at depth s along the ray from c whose direction in the world frame is wd.
+__host__ __device__ __forceinline__ void tsdf_ray_point(const TsdfGrid& g, const double c[3], const double wd[3], double s, double q[3]) {
 #pragma unroll
-  for (int i = 0; i < 3; ++i) q[i] = ((a.c[i] + (s * wd[i])) - a.grid.origin[i]) / a.grid.voxel;
+  for (int i = 0; i < 3; ++i) q[i] = ((c[i] + (s * wd[i])) - g.origin[i]) / g.voxel;
+}
+__host__ __device__ __forceinline__ void tsdf_ray_point(const TsdfRaycastArgs& a, const double wd[3], double s, double q[3]) {
+  tsdf_ray_point(a.grid, a.c, wd, s, q);
+}
+
+// The ray of pixel (x, y): (dx, dy, 1) in the camera frame, wd in the world frame (Ri: the inverse pose's rotation).
+__host__ __device__ __forceinline__ void tsdf_ray_direction(const CloudCam& cam, const double Ri[9], int x, int y, double* dx, double* dy,
+                                                            double wd[3]) {
+  *dx = ((double)x - cam.cx) / cam.fx, *dy = ((double)y - cam.cy) / cam.fy;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) wd[i] = ((Ri[3 * i] * *dx) + (Ri[3 * i + 1] * *dy)) + Ri[3 * i + 2];
 }
 
 // The work of one thread of k_tsdf_raycast: pixel (x, y), inside the image.  Returns whether the ray hit.  The ray in the camera
 // frame is (dx, dy, 1), so the ray parameter is the camera depth; no operation divides by a component of the direction.
 __host__ __device__ __forceinline__ bool tsdf_ray_lane(const TsdfRaycastArgs& a, int x, int y) {
-  const double dx = ((double)x - a.cam.cx) / a.cam.fx, dy = ((double)y - a.cam.cy) / a.cam.fy;
-  double wd[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) wd[i] = ((a.Ri[3 * i] * dx) + (a.Ri[3 * i + 1] * dy)) + a.Ri[3 * i + 2];
+  double dx, dy, wd[3];
+  tsdf_ray_direction(a.cam, a.Ri, x, y, &dx, &dy, wd);
   bool have_prev = false, hit = false;
   float f_prev = 0.f;
   double s_hit = 1.0;

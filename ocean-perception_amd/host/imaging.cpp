@@ -803,19 +803,21 @@ struct TsdfVolume::Impl {
   pm_handle* const h;
   const pm_tsdf_volume volume;
   void* const voxels;
+  void* const colors;  // null without a colour volume
   // Align's render and the new map on the device, kept from call to call and replaced when a larger map arrives
   float *align_disp = nullptr, *align_normals = nullptr, *align_new = nullptr;
   size_t align_px = 0;
-  Impl(pm_handle* handle, const pm_tsdf_volume& v, size_t bytes) : dev(handle), h(handle), volume(v), voxels(dev.Get(bytes)) {}
+  Impl(pm_handle* handle, const pm_tsdf_volume& v, size_t bytes, size_t color_bytes)
+      : dev(handle), h(handle), volume(v), voxels(dev.Get(bytes)), colors(color_bytes ? dev.Get(color_bytes) : nullptr) {}
 };
 
-TsdfVolume::TsdfVolume(pm::PatchmatchGpu& matcher, const TsdfGrid& grid) : grid_(grid) {
+TsdfVolume::TsdfVolume(pm::PatchmatchGpu& matcher, const TsdfGrid& grid, bool with_color) : grid_(grid) {
   pm_handle* h = MatcherHandle(matcher, "TsdfVolume");
   const pm_tsdf_volume v = {grid.nx, grid.ny, grid.nz, {grid.origin[0], grid.origin[1], grid.origin[2]}, grid.voxel, grid.trunc,
                             grid.max_weight};
   const size_t bytes = pm_tsdf_bytes(&v);
   if (bytes == 0) throw std::invalid_argument("TsdfVolume: the grid is invalid or exceeds 2^31 - 1 voxels");
-  impl_.reset(new Impl(h, v, bytes));
+  impl_.reset(new Impl(h, v, bytes, with_color ? pm_tsdf_color_bytes(&v) : 0));
   Clear();
 }
 
@@ -823,7 +825,117 @@ TsdfVolume::~TsdfVolume() = default;
 
 void* TsdfVolume::device() { return impl_->voxels; }
 
-void TsdfVolume::Clear() { impl_->dev.Check(pm_tsdf_clear(impl_->h, &impl_->volume, device()), "pm_tsdf_clear"); }
+bool TsdfVolume::has_color() const { return impl_->colors != nullptr; }
+
+void* TsdfVolume::color_device() { return impl_->colors; }
+
+void TsdfVolume::Clear() {
+  impl_->dev.Check(pm_tsdf_clear(impl_->h, &impl_->volume, device()), "pm_tsdf_clear");
+  if (has_color()) impl_->dev.Check(pm_tsdf_color_clear(impl_->h, &impl_->volume, color_device()), "pm_tsdf_color_clear");
+}
+
+namespace {
+void NeedColor(const TsdfVolume& v, const char* who) {
+  if (!v.has_color()) throw std::logic_error(std::string(who) + ": the volume was made without a colour volume");
+}
+}  // namespace
+
+std::array<int, 3> TsdfVolume::IntegrateColorDevice(const StereoModel& model, const Motion& pose, const float* d_disp,
+                                                    const float* d_weight, const uint8_t* d_bgr8, const float* d_bgr, int rows,
+                                                    int cols, const TsdfColorOptions& options, bool want_counts) {
+  NeedColor(*this, "TsdfVolume::IntegrateColor");
+  const pm_cloud_camera cam = CloudCamera(model);
+  const pm_motion m = ToC(pose);
+  const pm_tsdf_color_options opt = {options.min_disp, options.max_range, options.band};
+  int counts[3] = {-1, -1, -1};
+  impl_->dev.Check(pm_tsdf_integrate_color(impl_->h, &cam, &impl_->volume, &m, &opt, d_disp, d_weight, d_bgr8, d_bgr, rows, cols,
+                                           device(), color_device(), nullptr, want_counts ? counts : nullptr),
+                   "pm_tsdf_integrate_color");
+  return {{counts[0], counts[1], counts[2]}};
+}
+
+namespace {
+// the host form of IntegrateColor for either pixel type: Pixel is Vec3b (d_bgr8) or Vec3f (d_bgr)
+template <typename Pixel>
+std::array<int, 3> IntegrateColorHost(TsdfVolume& volume, pm_handle* h, const StereoModel& model, const Motion& pose,
+                                      const core::Image<float>& disp, const core::Image<Pixel>& bgr,
+                                      const core::Image<float>* weight, const TsdfColorOptions& options) {
+  if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("TsdfVolume::IntegrateColor: empty map");
+  SameSize(disp.rows, disp.cols, bgr.rows, bgr.cols, "TsdfVolume::IntegrateColor");
+  if (weight) SameSize(disp.rows, disp.cols, weight->rows, weight->cols, "TsdfVolume::IntegrateColor");
+  DeviceBuffers dev(h);
+  const float* d_disp = dev.Put<float>(disp.data(), Bytes(disp));
+  const float* d_weight = weight ? dev.Put<float>(weight->data(), Bytes(*weight)) : nullptr;
+  const void* d_image = dev.Put<void>(bgr.data(), Bytes(bgr));
+  const bool bytes = sizeof(Pixel) == sizeof(core::Vec3b);
+  return volume.IntegrateColorDevice(model, pose, d_disp, d_weight, bytes ? static_cast<const uint8_t*>(d_image) : nullptr,
+                                     bytes ? nullptr : static_cast<const float*>(d_image), disp.rows, disp.cols, options,
+                                     /*want_counts=*/true);  // synchronises: the buffers may go
+}
+}  // namespace
+
+std::array<int, 3> TsdfVolume::IntegrateColor(const StereoModel& model, const Motion& pose, const core::Image<float>& disp,
+                                              const core::Image<core::Vec3b>& bgr, const core::Image<float>* weight,
+                                              const TsdfColorOptions& options) {
+  return IntegrateColorHost(*this, impl_->h, model, pose, disp, bgr, weight, options);
+}
+
+std::array<int, 3> TsdfVolume::IntegrateColor(const StereoModel& model, const Motion& pose, const core::Image<float>& disp,
+                                              const core::Image<core::Vec3f>& bgr, const core::Image<float>* weight,
+                                              const TsdfColorOptions& options) {
+  return IntegrateColorHost(*this, impl_->h, model, pose, disp, bgr, weight, options);
+}
+
+int TsdfVolume::ColorMapDevice(const StereoModel& model, const Motion& pose, const float* d_disp, int rows, int cols,
+                               float* d_bgr_out, uint8_t* d_bgr8_out, const TsdfColorSampleOptions& options, bool want_counts) {
+  NeedColor(*this, "TsdfVolume::ColorMap");
+  const pm_cloud_camera cam = CloudCamera(model);
+  const pm_motion m = ToC(pose);
+  const pm_tsdf_color_sample_options opt = {options.min_weight, options.byte_scale};
+  int colored = -1;
+  impl_->dev.Check(pm_tsdf_color_map(impl_->h, &cam, &impl_->volume, &m, &opt, color_device(), d_disp, rows, cols, d_bgr_out,
+                                     d_bgr8_out, nullptr, want_counts ? &colored : nullptr),
+                   "pm_tsdf_color_map");
+  return colored;
+}
+
+int TsdfVolume::ColorMap(const StereoModel& model, const Motion& pose, const core::Image<float>& disp,
+                         core::Image<core::Vec3f>* bgr, core::Image<core::Vec3b>* bgr8, const TsdfColorSampleOptions& options) {
+  if (disp.rows <= 0 || disp.cols <= 0) throw std::invalid_argument("TsdfVolume::ColorMap: empty map");
+  if (!bgr && !bgr8) throw std::invalid_argument("TsdfVolume::ColorMap: no output");
+  const size_t px = (size_t)disp.rows * disp.cols;
+  DeviceBuffers dev(impl_->h);
+  const float* d_disp = dev.Put<float>(disp.data(), Bytes(disp));
+  float* d_bgr = bgr ? dev.Get<float>(px * sizeof(core::Vec3f)) : nullptr;
+  uint8_t* d_bgr8 = bgr8 ? dev.Get<uint8_t>(px * sizeof(core::Vec3b)) : nullptr;
+  const int colored = ColorMapDevice(model, pose, d_disp, disp.rows, disp.cols, d_bgr, d_bgr8, options, /*want_counts=*/true);
+  if (bgr) dev.Fetch(bgr, d_bgr, disp.rows, disp.cols);
+  if (bgr8) dev.Fetch(bgr8, d_bgr8, disp.rows, disp.cols);
+  return colored;
+}
+
+int TsdfVolume::ColorPoints(const std::vector<core::Vec3f>& xyz, std::vector<core::Vec3f>* bgr, std::vector<core::Vec3b>* bgr8,
+                            const TsdfColorSampleOptions& options) {
+  NeedColor(*this, "TsdfVolume::ColorPoints");
+  if (!bgr && !bgr8) throw std::invalid_argument("TsdfVolume::ColorPoints: no output");
+  if (xyz.size() > (size_t)INT32_MAX) throw std::invalid_argument("TsdfVolume::ColorPoints: too many points");
+  const size_t n = xyz.size();
+  if (bgr) bgr->assign(n, core::Vec3f{{0.f, 0.f, 0.f}});
+  if (bgr8) bgr8->assign(n, core::Vec3b{{0, 0, 0}});
+  if (n == 0) return 0;
+  DeviceBuffers dev(impl_->h);
+  const float* d_xyz = dev.Put<float>(xyz.data(), n * sizeof(core::Vec3f));
+  float* d_bgr = bgr ? dev.Get<float>(n * sizeof(core::Vec3f)) : nullptr;
+  uint8_t* d_bgr8 = bgr8 ? dev.Get<uint8_t>(n * sizeof(core::Vec3b)) : nullptr;
+  const pm_tsdf_color_sample_options opt = {options.min_weight, options.byte_scale};
+  int colored = -1;
+  dev.Check(pm_tsdf_color_points(impl_->h, &impl_->volume, &opt, color_device(), d_xyz, (int)n, nullptr, d_bgr, d_bgr8, nullptr,
+                                 &colored),
+            "pm_tsdf_color_points");
+  if (bgr) dev.Check(pm_download(impl_->h, bgr->data(), d_bgr, n * sizeof(core::Vec3f)), "pm_download");
+  if (bgr8) dev.Check(pm_download(impl_->h, bgr8->data(), d_bgr8, n * sizeof(core::Vec3b)), "pm_download");
+  return colored;
+}
 
 std::array<int, 2> TsdfVolume::IntegrateDevice(const StereoModel& model, const Motion& pose, const float* d_disp,
                                                const float* d_weight, int rows, int cols, const TsdfIntegrateOptions& options,
@@ -908,7 +1020,9 @@ std::array<int, 2> TsdfVolume::MeshDevice(const TsdfMeshOptions& options, int ve
   return {{counts[0], counts[1]}};
 }
 
-TriangleMesh TsdfVolume::Mesh(const TsdfMeshOptions& options, bool want_normals) {
+TriangleMesh TsdfVolume::Mesh(const TsdfMeshOptions& options, bool want_normals, bool want_color,
+                              const TsdfColorSampleOptions& color_options) {
+  if (want_color) NeedColor(*this, "TsdfVolume::Mesh");
   // count first (both capacities 0), then outputs of exactly that size
   const std::array<int, 2> counts = MeshDevice(options, 0, 0, nullptr, nullptr, nullptr);
   TriangleMesh mesh;
@@ -920,6 +1034,15 @@ TriangleMesh TsdfVolume::Mesh(const TsdfMeshOptions& options, bool want_normals)
   int32_t* d_tris = t ? dev.Get<int32_t>(t * 3 * sizeof(int32_t)) : nullptr;
   if (MeshDevice(options, counts[0], counts[1], d_xyz, d_normals, d_tris) != counts)
     throw std::runtime_error("TsdfVolume::Mesh: the counts changed between two passes over one volume");
+  if (want_color) {  // on the device, directly behind the mesh
+    uint8_t* d_bgr8 = dev.Get<uint8_t>(n * sizeof(core::Vec3b));
+    const pm_tsdf_color_sample_options opt = {color_options.min_weight, color_options.byte_scale};
+    dev.Check(pm_tsdf_color_points(impl_->h, &impl_->volume, &opt, color_device(), d_xyz, counts[0], nullptr, nullptr, d_bgr8, nullptr,
+                                   nullptr),
+              "pm_tsdf_color_points");
+    mesh.vertices.bgr.resize(n);
+    dev.Check(pm_download(impl_->h, mesh.vertices.bgr.data(), d_bgr8, n * sizeof(core::Vec3b)), "pm_download");
+  }
   mesh.vertices.xyz.resize(n);
   dev.Check(pm_download(impl_->h, mesh.vertices.xyz.data(), d_xyz, n * sizeof(core::Vec3f)), "pm_download");
   if (want_normals) {

@@ -327,24 +327,38 @@ struct TsdfIntegrateOptions {  // pm_tsdf_integrate_options
 struct TsdfMeshOptions {  // pm_tsdf_mesh_options
   float min_weight = 0.f;  // a node is observed iff weight > 0, weight >= min_weight and its value is finite
 };
+struct TsdfColorOptions {  // pm_tsdf_color_options
+  float min_disp = 0.f;   // TsdfIntegrateOptions' two
+  float max_range = 0.f;
+  float band = 1.f;       // in (0, 1]: a voxel takes the pixel's colour iff |sdf| <= band * trunc
+};
+struct TsdfColorSampleOptions {  // pm_tsdf_color_sample_options
+  float min_weight = 0.f;  // a corner takes part iff its colour weight is > 0 and >= min_weight
+  float byte_scale = 1.f;  // finite, > 0: bytes = saturate(rint(value * byte_scale)); 255 for float images in [0, 1]
+};
 struct TsdfRaycastOptions {  // pm_tsdf_raycast_options
   float min_range = 0.1f, max_range = 10.f;  // finite, 0 < min_range < max_range
   float step = 0.5f;                         // the march's step as a fraction of trunc, in (0, 1]
   float min_weight = 0.f;                    // a voxel takes part iff weight > 0 and weight >= min_weight
 };
-// Owns the volume's device memory (8 bytes per voxel) on the matcher's handle, which must be planned and must outlive the
-// volume; everything runs on that handle's stream.  Throws std::invalid_argument for a grid pm_tsdf_bytes refuses and where
-// image sizes differ, std::runtime_error where the C call refuses.
+// Owns the volume's device memory (8 bytes per voxel, 8 + 16 with a colour volume) on the matcher's handle, which must be
+// planned and must outlive the volume; everything runs on that handle's stream.  Throws std::invalid_argument for a grid
+// pm_tsdf_bytes refuses and where image sizes differ, std::runtime_error where the C call refuses.
+// With with_color it owns a colour volume too (16 bytes per voxel: b, g, r, weight; pm/imaging.h: pm_tsdf_color_*; definition:
+// tests/tsdf_color_ref.py), which IntegrateColor fuses the frames' images into and ColorMap, ColorPoints and Mesh(want_color) read
+// back; without it those throw std::logic_error.
 class TsdfVolume {
  public:
-  TsdfVolume(pm::PatchmatchGpu& matcher, const TsdfGrid& grid);  // allocated and cleared
+  TsdfVolume(pm::PatchmatchGpu& matcher, const TsdfGrid& grid, bool with_color = false);  // allocated and cleared
   ~TsdfVolume();
   TsdfVolume(const TsdfVolume&) = delete;
   TsdfVolume& operator=(const TsdfVolume&) = delete;
   const TsdfGrid& grid() const { return grid_; }
   size_t voxels() const { return (size_t)grid_.nx * grid_.ny * grid_.nz; }
   void* device();  // nx * ny * nz records {float tsdf; float weight}
-  void Clear();
+  bool has_color() const;
+  void* color_device();  // nx * ny * nz records {float b, g, r, weight}; null without a colour volume
+  void Clear();          // both volumes
   // Host map in; weight: a plane of the map's size, null = 1.0.  Returns {voxels in view, voxels updated}.
   std::array<int, 2> Integrate(const StereoModel& model, const Motion& pose, const core::Image<float>& disp,
                                const core::Image<float>* weight = nullptr,
@@ -353,6 +367,27 @@ class TsdfVolume {
   std::array<int, 2> IntegrateDevice(const StereoModel& model, const Motion& pose, const float* d_disp, const float* d_weight,
                                      int rows, int cols, const TsdfIntegrateOptions& options = TsdfIntegrateOptions(),
                                      bool want_counts = true);
+  // Integrate, and the image the map came with -- bytes or floats, the map's size -- fused into the colour volume.  Returns
+  // {voxels in view, updated, coloured}.
+  std::array<int, 3> IntegrateColor(const StereoModel& model, const Motion& pose, const core::Image<float>& disp,
+                                    const core::Image<core::Vec3b>& bgr, const core::Image<float>* weight = nullptr,
+                                    const TsdfColorOptions& options = TsdfColorOptions());
+  std::array<int, 3> IntegrateColor(const StereoModel& model, const Motion& pose, const core::Image<float>& disp,
+                                    const core::Image<core::Vec3f>& bgr, const core::Image<float>* weight = nullptr,
+                                    const TsdfColorOptions& options = TsdfColorOptions());
+  // Device buffers in, exactly one of d_bgr8 and d_bgr; with want_counts = false it only enqueues and returns {-1, -1, -1}.
+  std::array<int, 3> IntegrateColorDevice(const StereoModel& model, const Motion& pose, const float* d_disp, const float* d_weight,
+                                          const uint8_t* d_bgr8, const float* d_bgr, int rows, int cols,
+                                          const TsdfColorOptions& options = TsdfColorOptions(), bool want_counts = true);
+  // The fused colour at the pixels of any left map at `pose` -- a Raycast of the model, or a measured map: floats and bytes, each
+  // where it is asked for (at least one); zeros where a pixel has no value or no colour.  Returns the pixels coloured.
+  int ColorMap(const StereoModel& model, const Motion& pose, const core::Image<float>& disp, core::Image<core::Vec3f>* bgr,
+               core::Image<core::Vec3b>* bgr8 = nullptr, const TsdfColorSampleOptions& options = TsdfColorSampleOptions());
+  int ColorMapDevice(const StereoModel& model, const Motion& pose, const float* d_disp, int rows, int cols, float* d_bgr_out,
+                     uint8_t* d_bgr8_out, const TsdfColorSampleOptions& options = TsdfColorSampleOptions(), bool want_counts = true);
+  // The fused colour at world-frame points; each output where it is asked for (at least one).  Returns the points coloured.
+  int ColorPoints(const std::vector<core::Vec3f>& xyz, std::vector<core::Vec3f>* bgr, std::vector<core::Vec3b>* bgr8 = nullptr,
+                  const TsdfColorSampleOptions& options = TsdfColorSampleOptions());
   // Host images out, each where it is asked for (at least one).  Returns the pixels hit.
   int Raycast(const StereoModel& model, const Motion& pose, int rows, int cols, core::Image<float>* disp,
               core::Image<core::Vec3f>* normals = nullptr, const TsdfRaycastOptions& options = TsdfRaycastOptions());
@@ -363,8 +398,10 @@ class TsdfVolume {
   // The model taken out of the volume: its zero level set as ONE welded triangle mesh in the WORLD frame, one vertex per
   // crossed grid edge (pm/imaging.h: pm_tsdf_mesh; definition: tests/tsdf_mesh_ref.py).  A count call, then one call sized to
   // fit.  vertices.xyz always, vertices.normals (toward free space; (0, 0, 0) where the volume's gradient is not known) with
-  // want_normals; no colour and no index.  WritePly takes the result unchanged.
-  TriangleMesh Mesh(const TsdfMeshOptions& options = TsdfMeshOptions(), bool want_normals = true);
+  // want_normals; vertices.bgr (the fused colour through pm_tsdf_color_points, on the device behind pm_tsdf_mesh; (0, 0, 0) where
+  // a vertex has none) with want_color; no index.  WritePly takes the result unchanged, colour included.
+  TriangleMesh Mesh(const TsdfMeshOptions& options = TsdfMeshOptions(), bool want_normals = true, bool want_color = false,
+                    const TsdfColorSampleOptions& color_options = TsdfColorSampleOptions());
   // Device streams out, each may be null: d_xyz_out and d_normals_out vertex_capacity x 3 floats, d_tri_out tri_capacity x 3
   // int32, d_counts two device ints.  Returns {vertices, triangles}, both counted beyond the capacities; with want_counts =
   // false it only enqueues and returns {-1, -1}.

@@ -53,6 +53,8 @@ EXPORTS = [
     "pm_fuse_disparity",
     "pm_tsdf_bytes", "pm_tsdf_clear", "pm_tsdf_integrate", "pm_tsdf_raycast", "pm_debug_tsdf_constants",
     "pm_tsdf_mesh", "pm_debug_tsdf_mesh_table", "pm_debug_tsdf_mesh_scratch_bytes",
+    "pm_tsdf_color_bytes", "pm_tsdf_color_clear", "pm_tsdf_integrate_color", "pm_tsdf_color_map", "pm_tsdf_color_points",
+    "pm_debug_tsdf_color_constants",
     "pm_track_features", "pm_solve_motion", "pm_estimate_motion",
     "pm_align_evaluate", "pm_align_step", "pm_align_disparity", "pm_motion_compose", "pm_debug_align_constants",
     "pm_debug_align_scratch_bytes",
@@ -358,6 +360,26 @@ def tsdf_constants():
     a, b = C.c_int(0), C.c_int(0)
     load().pm_debug_tsdf_constants(C.byref(a), C.byref(b))
     return a.value, b.value
+
+
+class PmTsdfColorOptions(C.Structure):  # pm_tsdf_integrate_color
+    _fields_ = [("min_disp", C.c_float), ("max_range", C.c_float), ("band", C.c_float)]
+
+
+class PmTsdfColorSampleOptions(C.Structure):  # pm_tsdf_color_map, pm_tsdf_color_points
+    _fields_ = [("min_weight", C.c_float), ("byte_scale", C.c_float)]
+
+
+def tsdf_color_bytes(volume):
+    """pm_tsdf_color_bytes: the bytes of the colour volume's device buffer (16 per voxel), 0 where tsdf_bytes is 0."""
+    return int(load().pm_tsdf_color_bytes(_ref(tsdf_volume(volume))))
+
+
+def tsdf_color_constants():
+    """pm_debug_tsdf_color_constants: (bytes of a colour record, lanes, waves -- tsdf_constants' two)."""
+    a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+    load().pm_debug_tsdf_color_constants(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
 
 
 def tsdf_mesh_table():
@@ -719,6 +741,23 @@ def load():
     lib.pm_debug_tsdf_mesh_table.restype = None
     lib.pm_debug_tsdf_mesh_scratch_bytes.argtypes = [C.c_int] * 3
     lib.pm_debug_tsdf_mesh_scratch_bytes.restype = C.c_size_t
+    lib.pm_tsdf_color_bytes.argtypes = [C.POINTER(PmTsdfVolume)]
+    lib.pm_tsdf_color_bytes.restype = C.c_size_t
+    lib.pm_tsdf_color_clear.argtypes = [vp, C.POINTER(PmTsdfVolume), vp]
+    lib.pm_tsdf_color_clear.restype = C.c_int
+    lib.pm_tsdf_integrate_color.argtypes = [vp, C.POINTER(PmCloudCamera), C.POINTER(PmTsdfVolume), C.POINTER(PmMotion),
+                                            C.POINTER(PmTsdfColorOptions), vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp,
+                                            C.POINTER(C.c_int)]
+    lib.pm_tsdf_integrate_color.restype = C.c_int
+    lib.pm_tsdf_color_map.argtypes = [vp, C.POINTER(PmCloudCamera), C.POINTER(PmTsdfVolume), C.POINTER(PmMotion),
+                                      C.POINTER(PmTsdfColorSampleOptions), vp, vp, C.c_int, C.c_int, vp, vp, vp,
+                                      C.POINTER(C.c_int)]
+    lib.pm_tsdf_color_map.restype = C.c_int
+    lib.pm_tsdf_color_points.argtypes = [vp, C.POINTER(PmTsdfVolume), C.POINTER(PmTsdfColorSampleOptions), vp, vp, C.c_int, vp, vp,
+                                         vp, vp, C.POINTER(C.c_int)]
+    lib.pm_tsdf_color_points.restype = C.c_int
+    lib.pm_debug_tsdf_color_constants.argtypes = [C.POINTER(C.c_int)] * 3
+    lib.pm_debug_tsdf_color_constants.restype = None
     lib.pm_track_features.argtypes = [vp, C.POINTER(PmCloudCamera), C.POINTER(PmTrackOptions), C.POINTER(PmMotion), vp, vp, vp,
                                       C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_int)]
     lib.pm_track_features.restype = C.c_int
@@ -1481,6 +1520,47 @@ class Engine:
         self._check(self.lib.pm_tsdf_mesh(self.h, _ref(tsdf_volume(volume)), C.byref(o), d_voxels, vertex_capacity, tri_capacity,
                                           d_xyz_out, d_normals_out, d_tri_out, d_counts, n if want_counts else None), "pm_tsdf_mesh")
         return (n[0], n[1]) if want_counts else None
+
+    def tsdf_color_clear(self, volume, d_colors):
+        """pm_tsdf_color_clear (raw device address): every colour record becomes four +0.0, on the handle's stream."""
+        self._check(self.lib.pm_tsdf_color_clear(self.h, _ref(tsdf_volume(volume)), d_colors), "pm_tsdf_color_clear")
+
+    def tsdf_integrate_color(self, camera, volume, pose, d_disp, rows, cols, d_voxels, d_colors, d_bgr8=None, d_bgr=None,
+                             min_disp=0.0, max_range=0.0, band=1.0, d_weight=None, d_counts=None, want_counts=False):
+        """pm_tsdf_integrate_color (raw device addresses): pm_tsdf_integrate, and the colour of the map's image -- d_bgr8 uint8 or
+        d_bgr float32, [rows][cols][3], exactly one -- folded into the colour volume at d_colors where |sdf| <= band * trunc.
+        d_counts: three device ints.  -> (in view, updated, coloured) with want_counts (the call then synchronises)."""
+        c = cloud_camera(camera)
+        o = PmTsdfColorOptions(min_disp, max_range, band)
+        n = (C.c_int * 3)(-1, -1, -1)
+        self._check(self.lib.pm_tsdf_integrate_color(self.h, _ref(c), _ref(tsdf_volume(volume)), _ref(as_motion(pose)), C.byref(o),
+                                                     d_disp, d_weight, d_bgr8, d_bgr, rows, cols, d_voxels, d_colors, d_counts,
+                                                     n if want_counts else None), "pm_tsdf_integrate_color")
+        return tuple(n) if want_counts else None
+
+    def tsdf_color_map(self, camera, volume, pose, d_colors, d_disp, rows, cols, min_weight=0.0, byte_scale=1.0, d_bgr_out=None,
+                       d_bgr8_out=None, d_counts=None, want_counts=False):
+        """pm_tsdf_color_map (raw device addresses): the colour volume read at the pixels of the left map d_disp seen from pose,
+        into d_bgr_out float32 and d_bgr8_out uint8, [rows][cols][3], each where given.  -> the pixels coloured with want_counts
+        (the call then synchronises), else None."""
+        c = cloud_camera(camera)
+        o = PmTsdfColorSampleOptions(min_weight, byte_scale)
+        n = (C.c_int * 1)(-1)
+        self._check(self.lib.pm_tsdf_color_map(self.h, _ref(c), _ref(tsdf_volume(volume)), _ref(as_motion(pose)), C.byref(o),
+                                               d_colors, d_disp, rows, cols, d_bgr_out, d_bgr8_out, d_counts,
+                                               n if want_counts else None), "pm_tsdf_color_map")
+        return n[0] if want_counts else None
+
+    def tsdf_color_points(self, volume, d_colors, d_xyz, n, min_weight=0.0, byte_scale=1.0, d_n=None, d_bgr_out=None,
+                          d_bgr8_out=None, d_counts=None, want_counts=False):
+        """pm_tsdf_color_points (raw device addresses): the colour volume read at n world-frame points d_xyz [n][3] float32 -- with
+        d_n, one device int, at the first min(n, *d_n) -- into d_bgr_out float32 and d_bgr8_out uint8, [n][3], each where given.
+        -> the points coloured with want_counts (the call then synchronises), else None."""
+        o = PmTsdfColorSampleOptions(min_weight, byte_scale)
+        m = (C.c_int * 1)(-1)
+        self._check(self.lib.pm_tsdf_color_points(self.h, _ref(tsdf_volume(volume)), C.byref(o), d_colors, d_xyz, n, d_n, d_bgr_out,
+                                                  d_bgr8_out, d_counts, m if want_counts else None), "pm_tsdf_color_points")
+        return m[0] if want_counts else None
 
     def track_features(self, camera, d_left_old, d_disp_old, d_left_new, rows, cols, guess=None, cell=16, patch_radius=3,
                        search_radius=5, min_score=1, min_disp=0.0, max_disp=0.0, max_sad=0, min_gap=0, capacity=0, d_tracks=None,
