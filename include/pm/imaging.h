@@ -991,6 +991,93 @@ int pm_tsdf_color_points(pm_handle* h, const pm_tsdf_volume* volume, const pm_ts
                          int* d_counts /* device int[1]: coloured; may be NULL */,
                          int* counts /* host int[1], may be NULL: non-NULL synchronises */);
 
+/* ---- a photometric term for the dense alignment: the model's colour against the new image --------------------------------------
+ * pm_align_disparity is point-to-plane only: on a fronto-parallel plane -- a camera looking down at a flat seabed -- three of the
+ * six parameters are free.  pm_tsdf_color_map renders the model's colour beside pm_tsdf_raycast's map and normals; the term below
+ * compares it with the new image where each model pixel projects to, and pm_align_color_disparity runs pm_align_disparity's loop
+ * on the sum of both terms.  Held to its CPU definition (tests/align_photo_ref.py) BIT FOR BIT.  Binary64 unless it says binary32,
+ * one rounding per operation, parentheses as written.  The motion, the classes, the 28 terms, the 240-byte record and the ORDER of
+ * the sum are pm_align_evaluate's.
+ *   pm_bgr_luma, per pixel, binary32: p_c = (float)byte, or the float as it is;  L = ((b * 0.114f) + (g * 0.587f)) + (r * 0.299f).
+ *     The output is the quiet NaN 0x7FC00000 where a channel is not finite, or where zero_is_absent != 0 and all three channels
+ *     are == 0 (pm_tsdf_color_map's "not coloured").  NaN is the one "absent" marker of a luma plane.  One launch.
+ *   pm_align_photo_evaluate, per model pixel (x, y):
+ *     model     d = Dm(y, x) counts as in pm_align_evaluate;  Lm = (double)Lum_m(y, x) counts iff finite.  Otherwise NO_MODEL.
+ *               P = pm_reproject_disparity's point of (d, x, y).
+ *     project   pm_align_evaluate's, untouched: Q = (Xn, Yn, Zn), dq, (iu, iv); a dropped pixel is OUTSIDE.  Then
+ *               u = (fx * (Xn / Zn)) + cx;  v = (fy * (Yn / Zn)) + cy (that projection's own expressions, recomputed);
+ *               x0 = floor(u); y0 = floor(v), in binary64;  OUTSIDE also unless x0 >= 0 && x0 + 1 <= cols - 1 && y0 >= 0 &&
+ *               y0 + 1 <= rows - 1: an image of one column or one row has no USED pixel.
+ *     measure   d2 = Dn(iv, iu) counts as d does;  the taps L00 = Ln(y0, x0), L01 = Ln(y0, x0 + 1), L10 = Ln(y0 + 1, x0),
+ *               L11 = Ln(y0 + 1, x0 + 1) are all finite.  Otherwise UNMEASURED.  d2 is read first, the taps only where it counts.
+ *     gate      fabs((double)dq - (double)d2) <= (double)max_diff; otherwise GATED: the geometric term's occlusion test.
+ *     sample    the taps converted to binary64;  a = u - x0;  b = v - y0;  dt = L01 - L00;  db = L11 - L10;
+ *               top = L00 + (a * dt);  bot = L10 + (a * db);  val = top + (b * (bot - top));  gx = dt + (b * (db - dt));
+ *               gy = bot - top: the bilinear value and the exact gradient of the bilinear interpolant, from four taps.
+ *     residual  r = val - Lm, in levels.
+ *     row       bx = (gx * fx) / Qz;  by = (gy * fy) / Qz;  bz = -(((bx * Qx) + (by * Qy)) / Qz);
+ *               J = ((Qy*bz) - (Qz*by), (Qz*bx) - (Qx*bz), (Qx*by) - (Qy*bx), bx, by, bz): the derivative of r under the same left
+ *               perturbation Q' = Q + omega x Q + upsilon, so pm_align_step solves it unchanged.
+ *     weight    ar = fabs(r); w = 1.0 if ar <= huber_levels, else huber_levels / ar.
+ *     terms, sum, counts, planes: pm_align_evaluate's, r in levels.
+ *   pm_align_sums_blend (host, no handle): l2 = lambda * lambda, formed once; each of the 28 doubles is geo + (l2 * photo); the
+ *     three counts are integer sums, pad is 0; out may alias either input.  lambda converts levels into pixels of disparity
+ *     (sigma_d / sigma_I).  PM_ERR_INVALID_ARG by status alone: a null pointer; a lambda that is not finite or < 0.
+ *   pm_align_color_disparity: the two luma planes once per call (the model's with zero_is_absent = 1, the new image's with 0);
+ *     per update one pm_align_evaluate and one pm_align_photo_evaluate under the same motion (the photometric term with align's
+ *     min_disp and max_diff), both records behind ONE synchronisation, pm_align_sums_blend, pm_align_step.  The stop rule and the
+ *     "invalid answer is the guess" rule are pm_align_disparity's.  One more pair of evaluations under the motion reached gives
+ *     the info: geo as pm_align_disparity fills it from the geometric record (geo.valid the call's validity, geo.iterations its
+ *     updates, geo.H the geometric matrix), the photometric counts, rms_levels = sqrt(rr_photo / n_photo_used) (0 without a used
+ *     pixel) and H, the blended matrix.  valid iff no factorisation failed and geo.n_used + n_photo_used >= align.min_used.
+ * The device calls enqueue on the handle's stream and are valid in every mode; a non-NULL host `sums` synchronises, and
+ * pm_align_color_disparity always does.  An evaluation is two launches behind a 16-byte memset (its second launch is
+ * pm_align_evaluate's); no atomics on floating-point values, no cross-workgroup waits: two runs give the same bytes.
+ * Scratch: a second 256-byte record slot and a second run of `rows` row sums, then the loop's two luma planes, in ONE further
+ * handle-owned allocation (256 + 224 rows + 8 rows cols bytes) made on first use, grown under a stream synchronisation and
+ * released with the handle, and one further page-locked record.  pm_align_evaluate's own scratch is as it was.
+ * PM_ERR_INVALID_ARG, with pm_last_error naming the argument and nothing enqueued, the checks in this order -- luma: both or
+ * neither of d_bgr8 and d_bgr; a null d_luma_out; rows or cols < 1.  evaluate: a camera pm_backproject refuses; a null options,
+ * d_disp_model, d_luma_model, d_disp_new or d_luma_new; a non-finite entry of the motion; min_disp NaN; max_diff not finite or
+ * < 0; huber_levels not > 0; rows or cols < 1; no output at all.  loop: whatever pm_align_disparity refuses, in its order; a null
+ * d_bgr_model; both or neither of d_bgr8_new and d_bgr_new; huber_levels; a lambda that is not finite or < 0.  PM_ERR_SIZE as for
+ * pm_backproject. */
+typedef struct pm_align_photo_options {
+  float min_disp;
+  float max_diff;        /* >= 0, finite: the gate, in pixels of disparity */
+  double huber_levels;   /* > 0 */
+} pm_align_photo_options;
+typedef struct pm_align_color_options {
+  pm_align_options align;   /* the geometric term and the loop */
+  double huber_levels;      /* > 0 */
+  double lambda;            /* finite, >= 0: levels into pixels of disparity */
+} pm_align_color_options;
+typedef struct pm_align_color_info {
+  pm_align_info geo;
+  int n_photo_model, n_photo_gate, n_photo_used;
+  double rms_levels;
+  double H[21];             /* the blended matrix */
+} pm_align_color_info;
+
+int pm_bgr_luma(pm_handle* h, const uint8_t* d_bgr8 /* [rows][cols][3] */, const float* d_bgr /* [rows][cols][3] */,
+                /* exactly one of the two */
+                int rows, int cols, int zero_is_absent, float* d_luma_out /* [rows][cols] */);
+int pm_align_photo_evaluate(pm_handle* h, const pm_cloud_camera* camera, const pm_align_photo_options* options,
+                            const pm_motion* motion /* NULL = identity */, const float* d_disp_model,
+                            const float* d_luma_model, const float* d_disp_new, const float* d_luma_new, int rows, int cols,
+                            uint8_t* d_class_out /* may be NULL */, float* d_residual_out /* may be NULL */,
+                            pm_align_sums* d_sums /* device, may be NULL */,
+                            pm_align_sums* sums /* host, may be NULL: non-NULL synchronises */);
+int pm_align_sums_blend(const pm_align_sums* geo, const pm_align_sums* photo, double lambda,
+                        pm_align_sums* out);                                              /* host only, no handle */
+int pm_align_color_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_align_color_options* options,
+                             const pm_motion* guess /* NULL = identity */, const float* d_disp_model,
+                             const float* d_normals_model,
+                             const float* d_bgr_model /* [rows][cols][3]: pm_tsdf_color_map's d_bgr_out */,
+                             const float* d_disp_new, const uint8_t* d_bgr8_new, const float* d_bgr_new,
+                             /* exactly one of the two */
+                             int rows, int cols, pm_motion* out /* may be NULL */, pm_align_color_info* info /* may be NULL */);
+
 /* ---- device buffers for host code that does not include HIP (host/imaging.hpp uses them) ------------------
  * pm_device_malloc / pm_device_free wrap hipMalloc / hipFree on the handle's device; pm_upload / pm_download are
  * stream-ordered copies on the handle's stream from / to pageable host memory (pm_download returns after the

@@ -341,6 +341,9 @@ size_t pm_debug_tsdf_mesh_scratch_bytes(int nx, int ny, int nz);
  * device scratch a call on a map of `rows` rows reserves.  No handle, no device. */
 void pm_debug_align_constants(int* lanes, int* waves);
 size_t pm_debug_align_scratch_bytes(int rows);
+/* pm_align_photo_evaluate / pm_align_color_disparity: the bytes of their ONE further device allocation for a rows x cols map -- a
+ * second record slot and run of row sums, then two luma planes; 0 for rows or cols < 1. */
+size_t pm_debug_align_photo_scratch_bytes(int rows, int cols);
 
 /* ---- the colour volume's launch constants (csrc/pm_tsdf_color_body.hpp) -----------------------------------------------------------
  * record_bytes: the bytes of one colour record (16: one load, one store); lanes, waves: pm_debug_tsdf_constants' two, which the

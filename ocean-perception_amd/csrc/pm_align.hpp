@@ -2,7 +2,7 @@
 // the per-thread bodies (align_lane, align_total) are pm_align_body.hpp's, the definition is tests/align_ref.py (DESIGN.md
 // section 8c-12).
 //
-//   k_align_rows    block (64, 4), one WAVEFRONT per row.  Lane l walks the pixels x = 64 c + l of its row and keeps its 28 lane
+//   k_align_rows    (k_align_walk over align_lane) block (64, 4), one WAVEFRONT per row.  Lane l walks the pixels x = 64 c + l of its row and keeps its 28 lane
 //                   sums in registers (56 VGPRs, binary64).  The camera, the motion and the options arrive by value and are
 //                   wave-uniform: scalar registers.  The model map and its normals are coalesced loads; the new map is one gather
 //                   per pixel behind every earlier test (align_pixel).  At the row's end each term's 64 lane sums meet in ONE
@@ -52,8 +52,11 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return v;
 }
 
+// The row walk, stated once as a kernel template: k_align_rows below and k_align_photo_rows (pm_align_photo.hpp) are its two
+// instances.  Lane()(a, x, y, acc) is one trip of one lane (align_lane): it adds the pixel's terms to acc and returns its class.
 // grid = (ceil(rows / 4)), block = (64, 4)
-__global__ void __launch_bounds__(kAlignBlockX * kAlignBlockY) k_align_rows(AlignArgs a) {
+template <typename Args, typename Lane>
+__global__ void __launch_bounds__(kAlignBlockX * kAlignBlockY) k_align_walk(Args a) {
   __shared__ int wave_counts[kAlignBlockY][3];
   const int y = (int)(blockIdx.x * kAlignBlockY + threadIdx.y);
   const int chunks = y < a.rows ? align_chunks(a.cols) : 0;  // wave-uniform: nobody leaves in front of a ballot
@@ -64,7 +67,7 @@ __global__ void __launch_bounds__(kAlignBlockX * kAlignBlockY) k_align_rows(Alig
 #pragma unroll 1
   for (int c = 0; c < chunks; ++c) {
     const int x = c * kAlignLanes + (int)threadIdx.x;
-    const int cls = x < a.cols ? align_lane(a, x, y, acc) : kAlignNoModel;  // beyond the row's end: +0.0 to every sum
+    const int cls = x < a.cols ? Lane()(a, x, y, acc) : kAlignNoModel;  // beyond the row's end: +0.0 to every sum
     n_model += __popcll(__ballot(cls != kAlignNoModel));
     n_gate += __popcll(__ballot(cls >= kAlignGated));
     n_used += __popcll(__ballot(cls == kAlignUsed));
@@ -85,6 +88,11 @@ __global__ void __launch_bounds__(kAlignBlockX * kAlignBlockY) k_align_rows(Alig
     if (sum) reproject_add(a.counts + threadIdx.x, sum);
   }
 }
+
+struct AlignLane {
+  __device__ __forceinline__ int operator()(const AlignArgs& a, int x, int y, double* acc) const { return align_lane(a, x, y, acc); }
+};
+constexpr auto k_align_rows = &k_align_walk<AlignArgs, AlignLane>;
 
 // grid = (1), block = (64).  `record` is the handle's; `also` the caller's d_sums, or null.
 __global__ void __launch_bounds__(kAlignLanes) k_align_finish(const double* row_sums, int rows, const int* counts,

@@ -47,6 +47,34 @@ struct AlignArgs {
   int* counts;          // [0] model pixels, [1] pixels that reached the gate, [2] used pixels; zeroed
 };
 
+// The 28 terms of a used pixel from its row J, its residual r and the Huber threshold in r's unit: shared by the geometric pixel
+// below and the photometric one (pm_align_photo_body.hpp).
+__host__ __device__ __forceinline__ void align_terms(const double J[6], double r, double huber, double term[kAlignTerms]) {
+  const double ar = __builtin_fabs(r);
+  const double w = ar <= huber ? 1.0 : huber / ar;
+  int k = 0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    const double wj = w * J[i];
+#pragma unroll
+    for (int j = i; j < 6; ++j) term[k++] = wj * J[j];
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) term[21 + i] = (w * J[i]) * r;
+  term[27] = r * r;
+}
+
+// The end of one trip of one lane: a pixel's terms are added to the lane's sums (a pixel that is not used adds +0.0 to each)
+// and the optional planes are written.
+__host__ __device__ __forceinline__ void align_lane_tail(int cls, const double term[kAlignTerms], double r, size_t px,
+                                                         uint8_t* class_out, float* residual_out, double acc[kAlignTerms]) {
+  const bool used = cls == kAlignUsed;
+#pragma unroll
+  for (int k = 0; k < kAlignTerms; ++k) acc[k] = acc[k] + (used ? term[k] : 0.0);
+  if (class_out) class_out[px] = (uint8_t)cls;
+  if (residual_out) residual_out[px] = used ? (float)r : 0.f;
+}
+
 // Model pixel (x, y) with disparity d and normal n: its class and, where that is kAlignUsed, its 28 terms and its residual in
 // pixels of disparity.  The new map is read behind every earlier test.
 __host__ __device__ __forceinline__ int align_pixel(const AlignArgs& a, int x, int y, float d, const float n[3],
@@ -73,18 +101,7 @@ __host__ __device__ __forceinline__ int align_pixel(const AlignArgs& a, int x, i
   const double r = e / s;
   const double J[6] = {((P2[1] * m2) - (P2[2] * m1)) / s, ((P2[2] * m0) - (P2[0] * m2)) / s, ((P2[0] * m1) - (P2[1] * m0)) / s,
                        m0 / s, m1 / s, m2 / s};
-  const double ar = __builtin_fabs(r);
-  const double w = ar <= a.huber_px ? 1.0 : a.huber_px / ar;
-  int k = 0;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    const double wj = w * J[i];
-#pragma unroll
-    for (int j = i; j < 6; ++j) term[k++] = wj * J[j];
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) term[21 + i] = (w * J[i]) * r;
-  term[27] = r * r;
+  align_terms(J, r, a.huber_px, term);
   *residual = r;
   return kAlignUsed;
 }
@@ -98,11 +115,7 @@ __host__ __device__ __forceinline__ int align_lane(const AlignArgs& a, int x, in
   const float n[3] = {np[0], np[1], np[2]};
   double term[kAlignTerms], r = 0.0;
   const int cls = align_pixel(a, x, y, d, n, term, &r);
-  const bool used = cls == kAlignUsed;
-#pragma unroll
-  for (int k = 0; k < kAlignTerms; ++k) acc[k] = acc[k] + (used ? term[k] : 0.0);
-  if (a.class_out) a.class_out[px] = (uint8_t)cls;
-  if (a.residual_out) a.residual_out[px] = used ? (float)r : 0.f;
+  align_lane_tail(cls, term, r, px, a.class_out, a.residual_out, acc);
   return cls;
 }
 

@@ -27,6 +27,8 @@
 //     pm_tsdf_mesh.hpp   the five kernels of pm_tsdf_mesh (k_tsdf_mesh_flags / _count / _span_offsets / _vertices /
 //                        _triangles); their bodies and the case table are pm_tsdf_mesh_body.hpp's
 //     pm_align.hpp       the two kernels of pm_align_evaluate (k_align_rows, k_align_finish); their bodies are pm_align_body.hpp's
+//     pm_align_photo.hpp the two kernels of pm_bgr_luma and pm_align_photo_evaluate (k_bgr_luma, k_align_photo_rows: pm_align.hpp's
+//                        row walk over another lane body); their bodies are pm_align_photo_body.hpp's
 //     pm_tsdf_color.hpp  the three kernels of pm_tsdf_integrate_color, pm_tsdf_color_map and pm_tsdf_color_points
 //                        (k_tsdf_integrate_color, k_tsdf_color_map, k_tsdf_color_points); their bodies are
 //                        pm_tsdf_color_body.hpp's, the integrate's walk and the count's tail are pm_tsdf.hpp's

@@ -69,6 +69,11 @@ struct ImagingState {
   // them, cleared per call), then one row sum of 28 doubles per row; and the page-locked record the downloads land in
   DevBuf<char> align_buf;
   HostBuf align_host;
+  // pm_align_photo_evaluate / pm_align_color_disparity: a second 256-byte record slot and a second run of row sums, then the two
+  // luma planes of pm_align_color_disparity (the model's, the new image's), one float per pixel each; and the page-locked
+  // record the photometric downloads land in
+  DevBuf<char> align_photo_buf;
+  HostBuf align_photo_host;
 };
 
 #define PM_HIP(h, call)                                                                                     \

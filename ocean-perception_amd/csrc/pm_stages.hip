@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "pm_align.hpp"
+#include "pm_align_photo.hpp"
 #include "pm_cloud.hpp"
 #include "pm_confidence.hpp"
 #include "pm_consistency.hpp"
@@ -1397,6 +1398,28 @@ int align_download(pm_handle* h, ImagingState* st, hipStream_t stream, const pm_
   std::memcpy(sums, st->align_host.base(), sizeof(pm_align_sums));
   return PM_OK;
 }
+
+// The Gauss-Newton loop of pm_align_disparity and pm_align_color_disparity: record(m, &sums) gives the normal equations under m,
+// pm_align_step solves and updates; it stops where a factorisation fails, after the update whose largest |delta_i| is below
+// epsilon, or after `iterations` updates.  Behind it, one more record under the motion reached is in *sums.
+template <typename Record>
+int align_iterate(const pm_align_options& o, pm_motion* m, bool* failed, int* done, pm_align_sums* sums, Record record) {
+  for (int it = 0; it < o.iterations; ++it) {
+    if (int rc = record(*m, sums)) return rc;
+    double delta[6];
+    int factorised = 0;
+    pm_align_step(sums, m, m, delta, &factorised);
+    if (!factorised) {
+      *failed = true;
+      break;
+    }
+    ++*done;
+    double biggest = 0.0;
+    for (double v : delta) biggest = std::fabs(v) > biggest ? std::fabs(v) : biggest;
+    if (biggest < o.epsilon) break;
+  }
+  return record(*m, sums);
+}
 }  // namespace
 
 int pm_align_evaluate(pm_handle* h, const pm_cloud_camera* camera, const pm_align_options* options, const pm_motion* motion,
@@ -1430,25 +1453,13 @@ int pm_align_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_ali
   hipStream_t stream = nullptr;
   pm_align_sums* d_record = nullptr;
   pm_align_sums sums;
+  const auto record = [&](const pm_motion& at, pm_align_sums* into) -> int {
+    if (int rc = run_align(h, what, in, &at, nullptr, nullptr, nullptr, &st, &stream, &d_record)) return rc;
+    return align_download(h, st, stream, d_record, into);
+  };
   bool failed = false;
   int done = 0;
-  for (int it = 0; it < options->iterations; ++it) {
-    if (int rc = run_align(h, what, in, &m, nullptr, nullptr, nullptr, &st, &stream, &d_record)) return rc;
-    if (int rc = align_download(h, st, stream, d_record, &sums)) return rc;
-    double delta[6];
-    int factorised = 0;
-    pm_align_step(&sums, &m, &m, delta, &factorised);
-    if (!factorised) {
-      failed = true;
-      break;
-    }
-    ++done;
-    double biggest = 0.0;
-    for (double v : delta) biggest = std::fabs(v) > biggest ? std::fabs(v) : biggest;
-    if (biggest < options->epsilon) break;
-  }
-  if (int rc = run_align(h, what, in, &m, nullptr, nullptr, nullptr, &st, &stream, &d_record)) return rc;
-  if (int rc = align_download(h, st, stream, d_record, &sums)) return rc;
+  if (int rc = align_iterate(*options, &m, &failed, &done, &sums, record)) return rc;
   const bool valid = !failed && sums.n_used >= options->min_used;
   if (out) *out = valid ? m : start;
   if (info) {
@@ -1467,3 +1478,186 @@ void pm_debug_align_constants(int* lanes, int* waves) {
 }
 
 size_t pm_debug_align_scratch_bytes(int rows) { return rows < 1 ? 0 : align_scratch_bytes(rows); }
+
+// ---- the photometric term of the dense alignment: lumas, one evaluation, the blended loop (pm_align_photo.hpp) ------------------
+namespace {
+// a second record slot and a second run of row sums, then the two luma planes of pm_align_color_disparity
+size_t align_photo_scratch_bytes(int rows, int cols) {
+  return align_scratch_bytes(rows) + 2 * sizeof(float) * (size_t)rows * (size_t)cols;
+}
+
+int check_one_image(pm_handle* h, const char* what, const uint8_t* d_bgr8, const float* d_bgr, const char* name8, const char* name) {
+  if ((d_bgr8 != nullptr) == (d_bgr != nullptr)) {
+    set_err(h, "%s: exactly one of %s and %s must be given (%s)", what, name8, name, d_bgr8 ? "both are" : "neither is");
+    return PM_ERR_INVALID_ARG;
+  }
+  return PM_OK;
+}
+
+// One luma plane behind the checks: one launch.
+int run_luma(pm_handle* h, hipStream_t stream, const uint8_t* d_bgr8, const float* d_bgr, int rows, int cols, int zero_is_absent,
+             float* d_luma_out) {
+  const LumaArgs a = {d_bgr8, d_bgr, rows, cols, zero_is_absent, d_luma_out};
+  const LumaBlocks blocks = luma_blocks(rows, cols);
+  hipLaunchKernelGGL(k_bgr_luma, dim3(blocks.x, blocks.y), dim3(kAlignBlockX, kAlignBlockY), 0, stream, a);
+  return launch_check(h, "bgr luma");
+}
+
+// what pm_align_photo_evaluate is given and pm_align_color_disparity makes
+struct AlignPhotoInputs {
+  const pm_cloud_camera* camera;
+  float min_disp, max_diff;
+  double huber_levels;
+  const float* disp_model;
+  const float* luma_model;
+  const float* disp_new;
+  const float* luma_new;
+  int rows, cols;
+};
+
+int check_huber_levels(pm_handle* h, const char* what, double huber_levels) {
+  if (!(huber_levels > 0.0)) {
+    set_err(h, "%s: huber_levels must be > 0 and not NaN", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  return PM_OK;
+}
+
+// One photometric evaluation behind the checks, as run_align: the 16-byte memset of the counts and the two launches.
+int run_align_photo(pm_handle* h, const char* what, const AlignPhotoInputs& in, const pm_motion* motion, uint8_t* d_class_out,
+                    float* d_residual_out, pm_align_sums* d_sums, ImagingState** state, hipStream_t* stream_out,
+                    pm_align_sums** d_record) {
+  ImagingState* st = nullptr;
+  hipStream_t stream = nullptr;
+  if (int rc = stage_begin(h, what, &st, &stream)) return rc;
+  PM_HIP(h, st->align_photo_buf.reserve(align_photo_scratch_bytes(in.rows, in.cols), stream));
+  if (!st->align_photo_host.base()) PM_HIP(h, st->align_photo_host.alloc(sizeof(pm_align_sums)));
+  pm_align_sums* record = reinterpret_cast<pm_align_sums*>(st->align_photo_buf.get());
+  AlignPhotoArgs a = {};
+  a.cam = cloud_cam(*in.camera);
+  set_motion(a.R, a.t, motion);
+  a.min_disp = in.min_disp, a.max_diff = in.max_diff, a.huber_levels = in.huber_levels;
+  a.disp_model = in.disp_model, a.luma_model = in.luma_model, a.disp_new = in.disp_new, a.luma_new = in.luma_new;
+  a.rows = in.rows, a.cols = in.cols;
+  a.class_out = d_class_out, a.residual_out = d_residual_out;
+  a.row_sums = reinterpret_cast<double*>(st->align_photo_buf.get() + kAlignRecordSlot);
+  a.counts = &record->n_model;
+  PM_HIP(h, hipMemsetAsync(a.counts, 0, 4 * sizeof(int), stream));
+  hipLaunchKernelGGL(k_align_photo_rows, dim3(align_row_blocks(in.rows)), dim3(kAlignBlockX, kAlignBlockY), 0, stream, a);
+  hipLaunchKernelGGL(k_align_finish, dim3(1), dim3(kAlignLanes), 0, stream, (const double*)a.row_sums, in.rows,
+                     (const int*)a.counts, record, d_sums);
+  if (int rc = launch_check(h, "align photo")) return rc;
+  *state = st, *stream_out = stream, *d_record = record;
+  return PM_OK;
+}
+}  // namespace
+
+int pm_bgr_luma(pm_handle* h, const uint8_t* d_bgr8, const float* d_bgr, int rows, int cols, int zero_is_absent,
+                float* d_luma_out) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_bgr_luma";
+  if (int rc = check_one_image(h, what, d_bgr8, d_bgr, "d_bgr8", "d_bgr")) return rc;
+  if (int rc = check_not_null(h, what, {{"d_luma_out", d_luma_out}})) return rc;
+  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
+  PM_HIP(h, hipSetDevice(pm_internal::device(h)));
+  return run_luma(h, pm_internal::stream(h), d_bgr8, d_bgr, rows, cols, zero_is_absent, d_luma_out);
+}
+
+int pm_align_photo_evaluate(pm_handle* h, const pm_cloud_camera* camera, const pm_align_photo_options* options,
+                            const pm_motion* motion, const float* d_disp_model, const float* d_luma_model, const float* d_disp_new,
+                            const float* d_luma_new, int rows, int cols, uint8_t* d_class_out, float* d_residual_out,
+                            pm_align_sums* d_sums, pm_align_sums* sums) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_align_photo_evaluate";
+  if (int rc = check_cloud_camera(h, what, camera)) return rc;
+  if (int rc = check_not_null(h, what, {{"options", options}, {"d_disp_model", d_disp_model}, {"d_luma_model", d_luma_model},
+                                        {"d_disp_new", d_disp_new}, {"d_luma_new", d_luma_new}}))
+    return rc;
+  if (motion)
+    if (int rc = check_motion(h, what, *motion, "the motion")) return rc;
+  if (std::isnan(options->min_disp)) {
+    set_err(h, "%s: min_disp must not be NaN", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  if (int rc = check_max_diff(h, what, options->max_diff)) return rc;
+  if (int rc = check_huber_levels(h, what, options->huber_levels)) return rc;
+  if (int rc = check_cloud_shape(h, what, rows, cols)) return rc;
+  if (int rc = check_any_output(h, what, {d_class_out, d_residual_out, d_sums, sums}, "d_class_out, d_residual_out, d_sums and sums"))
+    return rc;
+  const AlignPhotoInputs in = {camera, options->min_disp, options->max_diff, options->huber_levels, d_disp_model, d_luma_model,
+                               d_disp_new, d_luma_new, rows, cols};
+  ImagingState* st = nullptr;
+  hipStream_t stream = nullptr;
+  pm_align_sums* d_record = nullptr;
+  if (int rc = run_align_photo(h, what, in, motion, d_class_out, d_residual_out, d_sums, &st, &stream, &d_record)) return rc;
+  if (!sums) return PM_OK;
+  PM_HIP(h, hipMemcpyAsync(st->align_photo_host.base(), d_record, sizeof(pm_align_sums), hipMemcpyDeviceToHost, stream));
+  PM_HIP(h, hipStreamSynchronize(stream));
+  std::memcpy(sums, st->align_photo_host.base(), sizeof(pm_align_sums));
+  return PM_OK;
+}
+
+int pm_align_color_disparity(pm_handle* h, const pm_cloud_camera* camera, const pm_align_color_options* options,
+                             const pm_motion* guess, const float* d_disp_model, const float* d_normals_model,
+                             const float* d_bgr_model, const float* d_disp_new, const uint8_t* d_bgr8_new, const float* d_bgr_new,
+                             int rows, int cols, pm_motion* out, pm_align_color_info* info) {
+  if (!h) return PM_ERR_INVALID_ARG;
+  const char* const what = "pm_align_color_disparity";
+  const AlignInputs in = {camera, options ? &options->align : nullptr, guess, d_disp_model, d_normals_model, d_disp_new, rows, cols};
+  if (int rc = check_align(h, what, in, "the guess")) return rc;
+  if (int rc = check_any_output(h, what, {out, info}, "out and info")) return rc;
+  if (int rc = check_not_null(h, what, {{"d_bgr_model", d_bgr_model}})) return rc;
+  if (int rc = check_one_image(h, what, d_bgr8_new, d_bgr_new, "d_bgr8_new", "d_bgr_new")) return rc;
+  if (int rc = check_huber_levels(h, what, options->huber_levels)) return rc;
+  if (!(std::isfinite(options->lambda) && options->lambda >= 0.0)) {
+    set_err(h, "%s: lambda must be finite and >= 0", what);
+    return PM_ERR_INVALID_ARG;
+  }
+  ImagingState* st = nullptr;
+  hipStream_t stream = nullptr;
+  if (int rc = stage_begin(h, what, &st, &stream)) return rc;
+  // the two luma planes, once per call, behind the record slot and the row sums of the evaluations below
+  PM_HIP(h, st->align_photo_buf.reserve(align_photo_scratch_bytes(rows, cols), stream));
+  float* luma_model = reinterpret_cast<float*>(st->align_photo_buf.get() + align_scratch_bytes(rows));
+  float* luma_new = luma_model + (size_t)rows * cols;
+  if (int rc = run_luma(h, stream, nullptr, d_bgr_model, rows, cols, 1, luma_model)) return rc;
+  if (int rc = run_luma(h, stream, d_bgr8_new, d_bgr_new, rows, cols, 0, luma_new)) return rc;
+  const AlignPhotoInputs photo_in = {camera, options->align.min_disp, options->align.max_diff, options->huber_levels, d_disp_model,
+                                     luma_model, d_disp_new, luma_new, rows, cols};
+  pm_motion start;
+  set_motion(start.R, start.t, guess);
+  pm_motion m = start;
+  pm_align_sums geo, photo, sums;
+  // one geometric and one photometric evaluation under the same motion, both records behind one synchronisation, blended
+  const auto record = [&](const pm_motion& at, pm_align_sums* into) -> int {
+    pm_align_sums *d_geo = nullptr, *d_photo = nullptr;
+    if (int rc = run_align(h, what, in, &at, nullptr, nullptr, nullptr, &st, &stream, &d_geo)) return rc;
+    if (int rc = run_align_photo(h, what, photo_in, &at, nullptr, nullptr, nullptr, &st, &stream, &d_photo)) return rc;
+    PM_HIP(h, hipMemcpyAsync(st->align_host.base(), d_geo, sizeof(pm_align_sums), hipMemcpyDeviceToHost, stream));
+    PM_HIP(h, hipMemcpyAsync(st->align_photo_host.base(), d_photo, sizeof(pm_align_sums), hipMemcpyDeviceToHost, stream));
+    PM_HIP(h, hipStreamSynchronize(stream));
+    std::memcpy(&geo, st->align_host.base(), sizeof geo);
+    std::memcpy(&photo, st->align_photo_host.base(), sizeof photo);
+    return pm_align_sums_blend(&geo, &photo, options->lambda, into);
+  };
+  bool failed = false;
+  int done = 0;
+  if (int rc = align_iterate(options->align, &m, &failed, &done, &sums, record)) return rc;
+  const bool valid = !failed && geo.n_used + photo.n_used >= options->align.min_used;
+  if (out) *out = valid ? m : start;
+  if (info) {
+    info->geo.valid = valid ? 1 : 0;
+    info->geo.n_model = geo.n_model, info->geo.n_gate = geo.n_gate, info->geo.n_used = geo.n_used;
+    info->geo.iterations = done;
+    info->geo.rms_px = geo.n_used ? std::sqrt(geo.rr / (double)geo.n_used) : 0.0;
+    for (int i = 0; i < 21; ++i) info->geo.H[i] = geo.H[i];
+    info->n_photo_model = photo.n_model, info->n_photo_gate = photo.n_gate, info->n_photo_used = photo.n_used;
+    info->rms_levels = photo.n_used ? std::sqrt(photo.rr / (double)photo.n_used) : 0.0;
+    for (int i = 0; i < 21; ++i) info->H[i] = sums.H[i];
+  }
+  return PM_OK;
+}
+
+size_t pm_debug_align_photo_scratch_bytes(int rows, int cols) {
+  return rows < 1 || cols < 1 ? 0 : align_photo_scratch_bytes(rows, cols);
+}

@@ -1,4 +1,5 @@
-// align.cpp -- pm_align_step and pm_motion_compose (include/pm/imaging.h): the host half of pm_align_disparity, in binary64.
+// align.cpp -- pm_align_step, pm_motion_compose and pm_align_sums_blend (include/pm/imaging.h): the host half of
+// pm_align_disparity and pm_align_color_disparity, in binary64.
 // Held to tests/align_ref.py::step and ::compose BIT FOR BIT: the solve and the update are motion_solve.hpp's, shared with
 // pm_solve_motion; every operation is one rounding; this unit is compiled with -ffp-contract=off.  It sees the C ABI only, no
 // handle and no HIP header.
@@ -33,5 +34,19 @@ extern "C" int pm_motion_compose(const pm_motion* a, const pm_motion* b, pm_moti
     m.t[i] = (((a->R[3 * i] * b->t[0]) + (a->R[3 * i + 1] * b->t[1])) + (a->R[3 * i + 2] * b->t[2])) + a->t[i];
   }
   *out = m;
+  return PM_OK;
+}
+
+// Held to tests/align_photo_ref.py::blend BIT FOR BIT: l2 once, then one multiplication and one addition per double.
+extern "C" int pm_align_sums_blend(const pm_align_sums* geo, const pm_align_sums* photo, double lambda, pm_align_sums* out) {
+  if (!geo || !photo || !out || !(lambda >= 0.0) || !(lambda - lambda == 0.0)) return PM_ERR_INVALID_ARG;
+  const double l2 = lambda * lambda;
+  pm_align_sums s;
+  for (int i = 0; i < 21; ++i) s.H[i] = geo->H[i] + (l2 * photo->H[i]);
+  for (int i = 0; i < 6; ++i) s.g[i] = geo->g[i] + (l2 * photo->g[i]);
+  s.rr = geo->rr + (l2 * photo->rr);
+  s.n_model = geo->n_model + photo->n_model, s.n_gate = geo->n_gate + photo->n_gate, s.n_used = geo->n_used + photo->n_used;
+  s.pad = 0;
+  *out = s;  // out may alias either input
   return PM_OK;
 }

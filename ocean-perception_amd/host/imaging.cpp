@@ -736,6 +736,63 @@ Motion AlignDisparity(pm::PatchmatchGpu& matcher, const StereoModel& model, cons
   return FromC(out);
 }
 
+namespace {
+pm_align_color_options ToC(const AlignColorOptions& o) { return pm_align_color_options{ToC(o.align), o.huber_levels, o.lambda}; }
+
+// the new image on the device as the one of pm_align_color_disparity's two arguments that its pixel type names
+struct NewImage {
+  const uint8_t* bgr8 = nullptr;
+  const float* bgr = nullptr;
+  NewImage(DeviceBuffers& dev, const core::Image<core::Vec3b>& image)
+      : bgr8(dev.Put<uint8_t>(reinterpret_cast<const uint8_t*>(image.data()), Bytes(image))) {}
+  NewImage(DeviceBuffers& dev, const core::Image<core::Vec3f>& image)
+      : bgr(dev.Put<float>(reinterpret_cast<const float*>(image.data()), Bytes(image))) {}
+};
+
+template <typename Pixel>
+Motion AlignColorHost(pm::PatchmatchGpu& matcher, const StereoModel& model, const AlignColorOptions& options, const Motion* guess,
+                      const core::Image<float>& disp_model, const core::Image<core::Vec3f>& normals_model,
+                      const core::Image<core::Vec3f>& bgr_model, const core::Image<float>& disp_new,
+                      const core::Image<Pixel>& bgr_new, pm_align_color_info* info) {
+  const char* const who = "AlignColorDisparity";
+  DeviceBuffers dev(MatcherHandle(matcher, who));
+  const int rows = disp_model.rows, cols = disp_model.cols;
+  if (rows <= 0 || cols <= 0) throw std::invalid_argument("AlignColorDisparity: empty map");
+  SameSize(rows, cols, normals_model.rows, normals_model.cols, who);
+  SameSize(rows, cols, bgr_model.rows, bgr_model.cols, who);
+  SameSize(rows, cols, disp_new.rows, disp_new.cols, who);
+  SameSize(rows, cols, bgr_new.rows, bgr_new.cols, who);
+  const float* d_model = dev.Put<float>(disp_model.data(), Bytes(disp_model));
+  const float* d_normals = dev.Put<float>(reinterpret_cast<const float*>(normals_model.data()), Bytes(normals_model));
+  const float* d_bgr_model = dev.Put<float>(reinterpret_cast<const float*>(bgr_model.data()), Bytes(bgr_model));
+  const float* d_new = dev.Put<float>(disp_new.data(), Bytes(disp_new));
+  const NewImage image(dev, bgr_new);
+  const pm_cloud_camera cam = CloudCamera(model);
+  const pm_align_color_options opt = ToC(options);
+  const pm_motion g = ToC(guess ? *guess : Motion());
+  pm_motion out;
+  pm_align_color_info local;
+  dev.Check(pm_align_color_disparity(dev.handle(), &cam, &opt, &g, d_model, d_normals, d_bgr_model, d_new, image.bgr8, image.bgr, rows,
+                                     cols, &out, info ? info : &local),
+            "pm_align_color_disparity");
+  return FromC(out);
+}
+}  // namespace
+
+Motion AlignColorDisparity(pm::PatchmatchGpu& matcher, const StereoModel& model, const AlignColorOptions& options,
+                           const Motion* guess, const core::Image<float>& disp_model, const core::Image<core::Vec3f>& normals_model,
+                           const core::Image<core::Vec3f>& bgr_model, const core::Image<float>& disp_new,
+                           const core::Image<core::Vec3b>& bgr_new, pm_align_color_info* info) {
+  return AlignColorHost(matcher, model, options, guess, disp_model, normals_model, bgr_model, disp_new, bgr_new, info);
+}
+
+Motion AlignColorDisparity(pm::PatchmatchGpu& matcher, const StereoModel& model, const AlignColorOptions& options,
+                           const Motion* guess, const core::Image<float>& disp_model, const core::Image<core::Vec3f>& normals_model,
+                           const core::Image<core::Vec3f>& bgr_model, const core::Image<float>& disp_new,
+                           const core::Image<core::Vec3f>& bgr_new, pm_align_color_info* info) {
+  return AlignColorHost(matcher, model, options, guess, disp_model, normals_model, bgr_model, disp_new, bgr_new, info);
+}
+
 Motion ComposeMotion(const Motion& a, const Motion& b) {
   const pm_motion ca = ToC(a), cb = ToC(b);
   pm_motion out;
@@ -1008,6 +1065,53 @@ Motion TsdfVolume::Align(const StereoModel& model, const Motion& pose_guess, con
   m.dev.Check(pm_align_disparity(m.h, &cam, &opt, nullptr, m.align_disp, m.align_normals, m.align_new, rows, cols, &out, report),
               "pm_align_disparity");
   return report->valid ? ComposeMotion(FromC(out), pose_guess) : pose_guess;
+}
+
+namespace {
+// TsdfVolume::AlignColor behind its two signatures: the render, its colour and the new frame live in buffers of this call.
+template <typename Pixel>
+Motion AlignColorVolume(TsdfVolume& v, pm_handle* h, const StereoModel& model, const Motion& pose_guess,
+                        const core::Image<float>& disp_new, const core::Image<Pixel>& bgr_new,
+                        const TsdfRaycastOptions& raycast_options, const AlignColorOptions& align_options,
+                        const TsdfColorSampleOptions& color_options, pm_align_color_info* info) {
+  const char* const who = "TsdfVolume::AlignColor";
+  NeedColor(v, who);
+  const int rows = disp_new.rows, cols = disp_new.cols;
+  if (rows <= 0 || cols <= 0) throw std::invalid_argument("TsdfVolume::AlignColor: empty map");
+  SameSize(rows, cols, bgr_new.rows, bgr_new.cols, who);
+  const size_t px = (size_t)rows * cols;
+  DeviceBuffers dev(h);
+  float* d_disp = dev.Get<float>(4 * px);
+  float* d_normals = dev.Get<float>(12 * px);
+  float* d_bgr = dev.Get<float>(12 * px);
+  const float* d_new = dev.Put<float>(disp_new.data(), Bytes(disp_new));
+  const NewImage image(dev, bgr_new);
+  v.RaycastDevice(model, pose_guess, rows, cols, d_disp, d_normals, raycast_options, /*want_counts=*/false);
+  v.ColorMapDevice(model, pose_guess, d_disp, rows, cols, d_bgr, nullptr, color_options, /*want_counts=*/false);
+  const pm_cloud_camera cam = CloudCamera(model);
+  const pm_align_color_options opt = ToC(align_options);
+  pm_motion out;
+  pm_align_color_info local;
+  pm_align_color_info* const report = info ? info : &local;
+  dev.Check(pm_align_color_disparity(h, &cam, &opt, nullptr, d_disp, d_normals, d_bgr, d_new, image.bgr8, image.bgr, rows, cols, &out,
+                                     report),
+            "pm_align_color_disparity");  // synchronises: the buffers may go
+  return report->geo.valid ? ComposeMotion(FromC(out), pose_guess) : pose_guess;
+}
+}  // namespace
+
+Motion TsdfVolume::AlignColor(const StereoModel& model, const Motion& pose_guess, const core::Image<float>& disp_new,
+                              const core::Image<core::Vec3b>& bgr_new, const TsdfRaycastOptions& raycast_options,
+                              const AlignColorOptions& align_options, const TsdfColorSampleOptions& color_options,
+                              pm_align_color_info* info) {
+  return AlignColorVolume(*this, impl_->h, model, pose_guess, disp_new, bgr_new, raycast_options, align_options, color_options, info);
+}
+
+Motion TsdfVolume::AlignColor(const StereoModel& model, const Motion& pose_guess, const core::Image<float>& disp_new,
+                              const core::Image<core::Vec3f>& bgr_new, const TsdfRaycastOptions& raycast_options,
+                              const AlignColorOptions& align_options, const TsdfColorSampleOptions& color_options,
+                              pm_align_color_info* info) {
+  return AlignColorVolume(*this, impl_->h, model, pose_guess, disp_new, bgr_new, raycast_options, align_options, color_options, info);
 }
 
 std::array<int, 2> TsdfVolume::MeshDevice(const TsdfMeshOptions& options, int vertex_capacity, int tri_capacity, float* d_xyz_out,

@@ -303,6 +303,23 @@ struct AlignOptions {  // pm_align_options
 Motion AlignDisparity(pm::PatchmatchGpu& matcher, const StereoModel& model, const AlignOptions& options, const Motion* guess,
                       const core::Image<float>& disp_model, const core::Image<core::Vec3f>& normals_model,
                       const core::Image<float>& disp_new, pm_align_info* info = nullptr);
+// AlignDisparity with a PHOTOMETRIC term blended in: the model's colour (TsdfVolume::ColorMap at the render's pose; zeros = not
+// coloured) against the new frame's image, bytes or floats (pm/imaging.h: pm_align_color_disparity; definition:
+// tests/align_photo_ref.py).  It constrains what point-to-plane leaves free on a flat scene.  info->geo.valid == 0: the returned
+// motion is the guess.
+struct AlignColorOptions {  // pm_align_color_options
+  AlignOptions align;          // the geometric term and the loop
+  double huber_levels = 20.0;  // > 0: the Huber threshold of the photometric residual, in levels
+  double lambda = 0.03;        // finite, >= 0: levels into pixels of disparity (sigma_d / sigma_I)
+};
+Motion AlignColorDisparity(pm::PatchmatchGpu& matcher, const StereoModel& model, const AlignColorOptions& options,
+                           const Motion* guess, const core::Image<float>& disp_model, const core::Image<core::Vec3f>& normals_model,
+                           const core::Image<core::Vec3f>& bgr_model, const core::Image<float>& disp_new,
+                           const core::Image<core::Vec3b>& bgr_new, pm_align_color_info* info = nullptr);
+Motion AlignColorDisparity(pm::PatchmatchGpu& matcher, const StereoModel& model, const AlignColorOptions& options,
+                           const Motion* guess, const core::Image<float>& disp_model, const core::Image<core::Vec3f>& normals_model,
+                           const core::Image<core::Vec3f>& bgr_model, const core::Image<float>& disp_new,
+                           const core::Image<core::Vec3f>& bgr_new, pm_align_color_info* info = nullptr);
 // Host only: X -> a(b(X)) (pm_motion_compose).  The pose of a frame aligned against a render at pose_ref is
 // ComposeMotion(M, pose_ref).
 Motion ComposeMotion(const Motion& a, const Motion& b);
@@ -413,6 +430,16 @@ class TsdfVolume {
   Motion Align(const StereoModel& model, const Motion& pose_guess, const core::Image<float>& disp_new,
                const TsdfRaycastOptions& raycast_options = TsdfRaycastOptions(), const AlignOptions& align_options = AlignOptions(),
                pm_align_info* info = nullptr);
+  // Align with colour, for a volume that has a colour volume: raycast and ColorMapDevice at pose_guess, AlignColorDisparity's loop
+  // from the identity against that render, ComposeMotion(M, pose_guess); pose_guess itself where info->geo.valid == 0.
+  Motion AlignColor(const StereoModel& model, const Motion& pose_guess, const core::Image<float>& disp_new,
+                    const core::Image<core::Vec3b>& bgr_new, const TsdfRaycastOptions& raycast_options = TsdfRaycastOptions(),
+                    const AlignColorOptions& align_options = AlignColorOptions(),
+                    const TsdfColorSampleOptions& color_options = TsdfColorSampleOptions(), pm_align_color_info* info = nullptr);
+  Motion AlignColor(const StereoModel& model, const Motion& pose_guess, const core::Image<float>& disp_new,
+                    const core::Image<core::Vec3f>& bgr_new, const TsdfRaycastOptions& raycast_options = TsdfRaycastOptions(),
+                    const AlignColorOptions& align_options = AlignColorOptions(),
+                    const TsdfColorSampleOptions& color_options = TsdfColorSampleOptions(), pm_align_color_info* info = nullptr);
   // The records, 2 floats per voxel (tsdf, weight), x fastest; synchronises.
   std::vector<float> Download();
 

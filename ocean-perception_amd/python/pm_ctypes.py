@@ -58,6 +58,8 @@ EXPORTS = [
     "pm_track_features", "pm_solve_motion", "pm_estimate_motion",
     "pm_align_evaluate", "pm_align_step", "pm_align_disparity", "pm_motion_compose", "pm_debug_align_constants",
     "pm_debug_align_scratch_bytes",
+    "pm_bgr_luma", "pm_align_photo_evaluate", "pm_align_sums_blend", "pm_align_color_disparity",
+    "pm_debug_align_photo_scratch_bytes",
     "pm_gradient_magnitude", "pm_unit_noise", "pm_add_noise", "pm_propagate", "pm_debug_propagate",
     "pm_debug_match_plan",
     "pm_debug_sweep_plan", "pm_debug_segment_bounds", "pm_debug_propagate_hinted", "pm_debug_match_sweep_hint", "pm_debug_read_stops", "pm_debug_noise_cost_constants", "pm_debug_noise_cost", "pm_debug_remove_background",
@@ -503,6 +505,59 @@ def align_scratch_bytes(rows):
     return int(load().pm_debug_align_scratch_bytes(int(rows)))
 
 
+class PmAlignPhotoOptions(C.Structure):  # pm_align_photo_evaluate
+    _fields_ = [("min_disp", C.c_float), ("max_diff", C.c_float), ("huber_levels", C.c_double)]
+
+
+class PmAlignColorOptions(C.Structure):  # pm_align_color_disparity
+    _fields_ = [("align", PmAlignOptions), ("huber_levels", C.c_double), ("lam", C.c_double)]  # lam: the C field `lambda`
+
+
+class PmAlignColorInfo(C.Structure):
+    _fields_ = [("geo", PmAlignInfo), ("n_photo_model", C.c_int), ("n_photo_gate", C.c_int), ("n_photo_used", C.c_int),
+                ("rms_levels", C.c_double), ("H", C.c_double * 21)]
+
+    def as_dict(self):
+        return dict(geo=self.geo.as_dict(), n_photo_model=self.n_photo_model, n_photo_gate=self.n_photo_gate,
+                    n_photo_used=self.n_photo_used, rms_levels=self.rms_levels, H=np.array(self.H[:]))
+
+
+ALIGN_PHOTO_DEFAULTS = dict(min_disp=0.0, max_diff=1.0, huber_levels=20.0)
+ALIGN_COLOR_DEFAULTS = dict(ALIGN_DEFAULTS, huber_levels=20.0, lam=0.03)
+
+
+def align_photo_options(values=None):
+    """A PmAlignPhotoOptions from a dict of its fields over ALIGN_PHOTO_DEFAULTS; a PmAlignPhotoOptions passes through."""
+    if isinstance(values, PmAlignPhotoOptions):
+        return values
+    o = dict(ALIGN_PHOTO_DEFAULTS)
+    o.update(values or {})
+    return PmAlignPhotoOptions(**o)
+
+
+def align_color_options(values=None):
+    """A PmAlignColorOptions from a flat dict over ALIGN_COLOR_DEFAULTS: PmAlignOptions' fields, huber_levels and lam (lambda)."""
+    if isinstance(values, PmAlignColorOptions):
+        return values
+    o = dict(ALIGN_COLOR_DEFAULTS)
+    o.update(values or {})
+    return PmAlignColorOptions(PmAlignOptions(**{k: o[k] for k in ALIGN_DEFAULTS}), o["huber_levels"], o["lam"])
+
+
+def align_sums_blend(geo, photo, lam, out=None):
+    """pm_align_sums_blend (host only, no handle): geo + lam^2 photo -> the PmAlignSums (`out`, which may be geo or photo)."""
+    out = PmAlignSums() if out is None else out
+    rc = load().pm_align_sums_blend(C.byref(geo), C.byref(photo), float(lam), C.byref(out))
+    if rc != PM_OK:
+        raise PmError(rc, "pm_align_sums_blend", "refused its arguments")
+    return out
+
+
+def align_photo_scratch_bytes(rows, cols):
+    """pm_debug_align_photo_scratch_bytes: the further device scratch of the photometric term on a rows x cols map."""
+    return int(load().pm_debug_align_photo_scratch_bytes(int(rows), int(cols)))
+
+
 def solve_motion(camera, tracks, guess=None, iterations=10, huber_px=1.0, epsilon=1e-9, inlier_px=1.0, min_inliers=12):
     """pm_solve_motion (host only, no handle): tracks, a TRACK_DTYPE array -> (R[9], t[3], info dict).  Raises PmError where
     the arguments are refused."""
@@ -783,6 +838,18 @@ def load():
     lib.pm_debug_align_constants.restype = None
     lib.pm_debug_align_scratch_bytes.argtypes = [C.c_int]
     lib.pm_debug_align_scratch_bytes.restype = C.c_size_t
+    lib.pm_bgr_luma.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.pm_bgr_luma.restype = C.c_int
+    lib.pm_align_photo_evaluate.argtypes = [vp, C.POINTER(PmCloudCamera), C.POINTER(PmAlignPhotoOptions), C.POINTER(PmMotion), vp, vp,
+                                            vp, vp, C.c_int, C.c_int, vp, vp, vp, C.POINTER(PmAlignSums)]
+    lib.pm_align_photo_evaluate.restype = C.c_int
+    lib.pm_align_sums_blend.argtypes = [C.POINTER(PmAlignSums), C.POINTER(PmAlignSums), C.c_double, C.POINTER(PmAlignSums)]
+    lib.pm_align_sums_blend.restype = C.c_int
+    lib.pm_align_color_disparity.argtypes = [vp, C.POINTER(PmCloudCamera), C.POINTER(PmAlignColorOptions), C.POINTER(PmMotion), vp, vp,
+                                             vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(PmMotion), C.POINTER(PmAlignColorInfo)]
+    lib.pm_align_color_disparity.restype = C.c_int
+    lib.pm_debug_align_photo_scratch_bytes.argtypes = [C.c_int, C.c_int]
+    lib.pm_debug_align_photo_scratch_bytes.restype = C.c_size_t
     lib.pm_debug_confidence_constants.argtypes = [C.POINTER(C.c_int)] * 3
     lib.pm_debug_confidence_constants.restype = None
     lib.pm_device_malloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
@@ -1618,6 +1685,37 @@ class Engine:
         self._check(self.lib.pm_align_disparity(self.h, _ref(c), C.byref(o), _ref(as_motion(guess)), d_disp_model,
                                                 d_normals_model, d_disp_new, rows, cols, C.byref(out), C.byref(info)),
                     "pm_align_disparity")
+        return np.array(out.R[:]), np.array(out.t[:]), info.as_dict()
+
+    def bgr_luma(self, rows, cols, d_luma_out, d_bgr8=None, d_bgr=None, zero_is_absent=False):
+        """pm_bgr_luma (raw device addresses): the luma plane of a BGR image of bytes (d_bgr8) or floats (d_bgr), exactly one of
+        the two; NaN where a channel is not finite and, with zero_is_absent, where all three are 0.  Enqueues only."""
+        self._check(self.lib.pm_bgr_luma(self.h, d_bgr8, d_bgr, rows, cols, int(bool(zero_is_absent)), d_luma_out), "pm_bgr_luma")
+
+    def align_photo_evaluate(self, camera, d_disp_model, d_luma_model, d_disp_new, d_luma_new, rows, cols, motion=None, options=None,
+                             d_class_out=None, d_residual_out=None, d_sums=None, want_sums=False):
+        """pm_align_photo_evaluate (raw device addresses): one photometric evaluation, as align_evaluate with luma planes in the
+        place of the normals.  options: a dict of PmAlignPhotoOptions' fields over ALIGN_PHOTO_DEFAULTS.  -> the PmAlignSums with
+        want_sums (the call then synchronises), else None."""
+        c = cloud_camera(camera)
+        o = align_photo_options(options)
+        sums = PmAlignSums()
+        self._check(self.lib.pm_align_photo_evaluate(self.h, _ref(c), C.byref(o), _ref(as_motion(motion)), d_disp_model, d_luma_model,
+                                                     d_disp_new, d_luma_new, rows, cols, d_class_out, d_residual_out, d_sums,
+                                                     C.byref(sums) if want_sums else None), "pm_align_photo_evaluate")
+        return sums if want_sums else None
+
+    def align_color_disparity(self, camera, d_disp_model, d_normals_model, d_bgr_model, d_disp_new, rows, cols, d_bgr8_new=None,
+                              d_bgr_new=None, guess=None, options=None):
+        """pm_align_color_disparity (raw device addresses): align_disparity with the photometric term blended in -> (R[9], t[3],
+        info dict).  d_bgr_model float32 [rows][cols][3] (tsdf_color_map's d_bgr_out); the new image as bytes or floats, exactly
+        one of the two.  options: a flat dict over ALIGN_COLOR_DEFAULTS.  Synchronises."""
+        c = cloud_camera(camera)
+        o = align_color_options(options)
+        out, info = PmMotion(), PmAlignColorInfo()
+        self._check(self.lib.pm_align_color_disparity(self.h, _ref(c), C.byref(o), _ref(as_motion(guess)), d_disp_model,
+                                                      d_normals_model, d_bgr_model, d_disp_new, d_bgr8_new, d_bgr_new, rows, cols,
+                                                      C.byref(out), C.byref(info)), "pm_align_color_disparity")
         return np.array(out.R[:]), np.array(out.t[:]), info.as_dict()
 
     def normalize(self, d_bgr, rows, cols, d_out):
